@@ -196,6 +196,14 @@ def _script(tmp_path, body):
     return str(p)
 
 
+def _spawn_ranks(script, argv, world):
+    """launch.spawn_ranks from a parent process of its own: the launcher refuses a parent that has initialised the GPU,
+    which this one has when GPU tests ran before in the same session."""
+    code = (f"import sys; sys.path.insert(0, {ROOT!r}); from dwt_amd import launch; "
+            f"sys.exit(launch.spawn_ranks({script!r}, {argv!r}, {world}))")
+    return subprocess.run([sys.executable, "-c", code], timeout=300).returncode
+
+
 def test_spawn_ranks_sets_the_rendezvous_environment(tmp_path):
     out = tmp_path / "out"
     out.mkdir()
@@ -204,7 +212,7 @@ def test_spawn_ranks_sets_the_rendezvous_environment(tmp_path):
         keys = ["RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"]
         open(os.path.join({str(out)!r}, os.environ["RANK"]), "w").write(" ".join(os.environ[k] for k in keys) + " " + " ".join(sys.argv[1:]))
     """)
-    assert launch.spawn_ranks(script, ["--gpus", "3"], 3) == 0
+    assert _spawn_ranks(script, ["--gpus", "3"], 3) == 0
     seen = sorted(open(out / f).read().split() for f in os.listdir(out))
     assert [s[0] for s in seen] == ["0", "1", "2"] and [s[1] for s in seen] == ["0", "1", "2"]
     assert all(s[2] == "3" and s[3] == "127.0.0.1" and s[5:] == ["--gpus", "3"] for s in seen)
@@ -220,7 +228,7 @@ def test_spawn_ranks_propagates_a_failing_rank(tmp_path):
     """)
     import time
     t0 = time.time()
-    assert launch.spawn_ranks(script, [], 2) == 7
+    assert _spawn_ranks(script, [], 2) == 7
     assert time.time() - t0 < 30
 
 

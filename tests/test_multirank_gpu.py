@@ -21,7 +21,7 @@ def test_two_ranks_encode_gather_decode(tmp_path, geom, frames, mode):
     dump = str(tmp_path / "gathered.npz")
     cmd = [sys.executable, os.path.join(orc.ROOT, "bench.py"), "--gpus", "2", "--one-device", "--backend", "gloo",
            "--steps", "3", "--warmup", "1", "--frames", str(frames), "--geometry", str(W), str(H), str(C),
-           "--cpu-frames", "0", "--lift-reps", "1", "--dump-gathered", dump, "--gather", mode]
+           "--full", "--cpu-frames", "0", "--lift-reps", "1", "--dump-gathered", dump, "--gather", mode]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -49,7 +49,7 @@ def test_one_rank_under_a_launcher_uses_rccl(tmp_path):
     world size that disagrees with --gpus is refused."""
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
     cmd = [sys.executable, os.path.join(orc.ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--frames", "2",
-           "--geometry", "256", "256", "1", "--cpu-frames", "0", "--lift-reps", "1"]
+           "--geometry", "256", "256", "1", "--full", "--cpu-frames", "0", "--lift-reps", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

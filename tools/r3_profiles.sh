@@ -8,7 +8,7 @@ prof() { # name cmd...
 }
 tools/pmc_coder.sh 16 > $O/r03_coder_insts.json 2> $O/pmc_coder.err
 mkdir -p profiles && cp $O/r03_coder_insts.json profiles/r03_coder_insts.json
-prof r03_bench_gray4096_64frames_kernel_stats python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --cpu-frames 0 --extras 0
+prof r03_bench_gray4096_64frames_kernel_stats python3 "$PWD/bench.py" --full --steps 20 --warmup 5 --cpu-frames 0 --extras 0
 cp $O/r03_bench_gray4096_64frames_kernel_stats.out $O/r03_bench_line_under_rocprof.json
 prof r03_lifting_only_64planes_kernel_stats python3 $GRAFT_REPO_ROOT/tools/time_lift.py 4096 64
 export DWTX_ONE_STREAM=1
