@@ -2591,7 +2591,7 @@ int dwtx_encode_planes_ex(dwtx_ctx *ctx, const int32_t *lin, const int32_t *pyr,
 		w.live = (unsigned *)(small + o_lv);
 		DWTX_HIP(hipMemsetAsync(small, 0, o_sd, ctx->stream));
 		if (ctx->opt[DWTX_OPT_EXACT_ORDERS])   // test hook: take the hierarchical 32-state pass for every image
-			DWTX_HIP(hipMemsetAsync(small + o_slow, 1, sizeof(int) * n, ctx->stream));
+			DWTX_HIP(hipMemsetD32Async((hipDeviceptr_t)(small + o_slow), 1, (size_t)n, ctx->stream));   // (ints of 1: hipMemsetAsync would set bytes)
 
 		off = 0;
 		const size_t o_on = take(sizeof(short) * (size_t)n * w.ES);

@@ -95,8 +95,11 @@ def _synthetic_planes(rng, W, H, Cn, bits, density):
     return lin.astype(np.int32)
 
 
-@pytest.mark.parametrize("case", [(64, 64, 1, 16, 0.5), (200, 120, 3, 16, 0.02), (256, 256, 1, 13, 0.9), (333, 111, 3, 10, 0.3),
-                                  (512, 384, 1, 16, 0.0005), (96, 96, 3, 9, 1.0), (1024, 512, 1, 12, 0.001)])
+SYNTHETIC_CASES = [(64, 64, 1, 16, 0.5), (200, 120, 3, 16, 0.02), (256, 256, 1, 13, 0.9), (333, 111, 3, 10, 0.3),
+                   (512, 384, 1, 16, 0.0005), (96, 96, 3, 9, 1.0), (1024, 512, 1, 12, 0.001)]
+
+
+@pytest.mark.parametrize("case", SYNTHETIC_CASES)
 def test_entropy_stage_on_synthetic_coefficient_planes(ctx, case):
     """dwtx_encode_planes / dwtx_decode_planes on coefficient planes with up to 16 bit planes (the 64-bit count
     registers of k_code), very sparse ones (runs of hundreds of thousands: escaped tokens, high VLI orders, codes
