@@ -304,9 +304,15 @@ __global__ __launch_bounds__(PK_THREADS) void k_pack_streams(uint8_t *out, unsig
 	const unsigned long long last = first + PK_PIECE < len8 ? first + PK_PIECE : len8;
 	const unsigned long long *src = reinterpret_cast<const unsigned long long *>(streams + (unsigned long long)i * stride);
 	unsigned long long *dst = reinterpret_cast<unsigned long long *>(out + off);
-	for (unsigned long long b = first + 8ull * threadIdx.x; b < last; b += 8ull * PK_THREADS)
-		if (off + b + 8 <= out_bytes)
+	for (unsigned long long b = first + 8ull * threadIdx.x; b < last; b += 8ull * PK_THREADS) {
+		if (off + b + 8 <= out_bytes) {
 			dst[b >> 3] = src[b >> 3];
+		} else if (off + b < out_bytes) {   // the piece out_bytes cuts: its bytes before the cut, one by one
+			const uint8_t *s8 = streams + (unsigned long long)i * stride + b;
+			for (unsigned long long k = 0; off + b + k < out_bytes; ++k)
+				out[off + b + k] = s8[k];
+		}
+	}
 }
 } // namespace
 
@@ -549,6 +555,12 @@ extern "C" int dwtx_decode_images_info(dwtx_ctx *ctx, const uint8_t *streams, si
 				continue;
 			}
 			const int lo = I.level + 1;
+			if ((size_t)g.widths[lo] * g.heights[lo] * C > pix_stride) {   // as dwtx_decode_device: nothing written past a slot
+				dwtx_set_error("image %d: %dx%dx%d pixels do not fit the pixel stride %zu", i0 + i, g.widths[lo], g.heights[lo], C, pix_stride);
+				outW[i0 + i] = outH[i0 + i] = 0;
+				rc = DWTX_ERR_ARG;
+				break;
+			}
 			outW[i0 + i] = g.widths[lo];
 			outH[i0 + i] = g.heights[lo];
 			e = hipMemcpyAsync(pix + pix_stride * (size_t)(i0 + i), dpix + img_bytes * ((size_t)slot * P + i),
@@ -556,6 +568,8 @@ extern "C" int dwtx_decode_images_info(dwtx_ctx *ctx, const uint8_t *streams, si
 		}
 		if (e == hipSuccess)
 			e = hipEventRecord(ev_out[slot], cs);
+		if (rc == DWTX_ERR_ARG)
+			break;
 	}
 	const int s = sync_all(ctx);
 	if (infos && e == hipSuccess && !s && (rc == DWTX_OK || rc == DWTX_ERR_IO || rc == DWTX_ERR_ARG))

@@ -33,6 +33,7 @@ def packed_offsets(lens, stride=None):
 
 def torch_pack(streams, lens_host, out):
     """The packing of dwtx_pack_streams with plain tensor copies (CPU tensors / no library at hand): one slice copy per stream."""
+    assert streams.shape[1] % 8 == 0, "the stream stride must be a multiple of 8 (rows are moved in 8-byte pieces)"
     off = packed_offsets(lens_host, streams.shape[1])
     for i in range(streams.shape[0]):
         n8 = off[i + 1] - off[i]
@@ -50,9 +51,9 @@ class Gathered:
 
     def stream(self, r, i):
         length = int(self.lens[r * self.n + i])
-        if self.mode == "packed":
-            o = self.offsets[r][i]
-            return self.bufs[r][o:o + length]
+        if self.mode == "packed":   # a length beyond the stride was clamped to it by the sender: so is the view
+            o, end = self.offsets[r][i], self.offsets[r][i + 1]
+            return self.bufs[r][o:o + min(length, end - o)]
         return self.bufs[r][i, :length]
 
     def rank_bytes(self, r):
@@ -115,6 +116,8 @@ class StreamGather:
         """Exchange the lengths of step k.  streams: uint8 [n, stride] (kept by reference until collect(k)),
         lens: int64 [n] on the same device."""
         torch, dist = self.torch, self.dist
+        # (the constructor does not see the stride: the first place it is known is here)
+        assert streams.shape[1] % 8 == 0, "the stream stride must be a multiple of 8 (packed offsets and rows are 8-byte rounded)"
         s = k % self.slots
         self.wait(k - self.slots)
         self.streams[s] = streams

@@ -233,10 +233,15 @@ int dwtx_reconstruction(dwtx_ctx *ctx, int32_t *dev_pyr, const int32_t *dev_lin,
 /* encode.c:166-221: header, root image, plane counts, bit-plane segments in
  * schedule order, final run flush — for n images at once.  dev_lin is the
  * output of dwtx_linearization ([n*C][W*H], two's complement).  Image i's
- * stream is written to dev_out + i*out_stride (out_stride a multiple of 4; at
- * most out_stride bytes are ever written, so it should be >= capacity when
- * capacity > 0).  capacity <= 0 means unlimited (encode.c:150-152).
- * dev_info[i].nbytes is the length of stream i. */
+ * stream is written to dev_out + i*out_stride (out_stride a multiple of 4, at
+ * least 8, else DWTX_ERR_ARG; at most out_stride bytes are ever written, so it
+ * should be >= capacity when capacity > 0).  capacity <= 0 means unlimited
+ * (encode.c:150-152).  dev_info[i].nbytes and .total_bits are those of the
+ * whole stream even when it is longer than out_stride: the slot then holds its
+ * first out_stride bytes.  A stream that CAPACITY does not cut and that ends
+ * inside its slot is followed by zeros up to min(out_stride, 4*ceil(nbytes/4) + 16)
+ * bytes; the slot's bytes beyond are left as they were.  (When CAPACITY cuts,
+ * the rest of the last segment coded may follow, up to out_stride.) */
 int dwtx_encode_planes(dwtx_ctx *ctx, const int32_t *dev_lin, int W, int H, int C, int n, long capacity,
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
 
@@ -244,7 +249,11 @@ int dwtx_encode_planes(dwtx_ctx *ctx, const int32_t *dev_lin, int W, int H, int 
  * streams of identical geometry (W, H, C as in their headers) into linearised
  * two's-complement planes dev_lin [n*C][W*H] (zero where the stream ended
  * early).  Stream i occupies dev_streams + i*stream_stride (stride a multiple
- * of 8), its byte length is dev_lens[i].  levels_max < 0 = all levels
+ * of 8, at least 64), its byte length is dev_lens[i] (a length beyond the
+ * stride is taken as the stride).  The decoder reads nothing outside the n
+ * rows (no slack behind the last one), and whatever a row holds past its
+ * stream's length — the rest of a longer stream, another stream, garbage —
+ * does not change any result: a prefix decodes in place.  levels_max < 0 = all levels
  * (decode.c:163-171 computes it from the PIXELS argument).  Synchronous:
  * host_info[i] is filled on return (level and missing[] drive
  * dwtx_reconstruction / dwtx_transformation_inv). */
@@ -261,9 +270,12 @@ size_t dwtx_encode_bound(int W, int H, int C);
 int dwtx_encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int C, int n, long capacity,
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
 
-/* decode.c:174-264 with everything resident in HBM.  Image i is written densely
- * at dev_pix + i*pix_stride with the size the stream supports
- * (widths/heights[host_info[i].level + 1], decode.c:251-254).  Synchronises once
+/* decode.c:174-264 with everything resident in HBM (streams as for
+ * dwtx_decode_planes).  Image i is written densely at dev_pix + i*pix_stride
+ * with the size the stream supports (widths/heights[host_info[i].level + 1],
+ * decode.c:251-254); no other byte of dev_pix is written, so pix_stride may
+ * carry padding and dev_pix needs no alignment.  A picture larger than
+ * pix_stride is DWTX_ERR_ARG, and nothing is written for it.  Synchronises once
  * (after the token walk) to learn that size. */
 int dwtx_decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
 	const unsigned long long *dev_lens, int W, int H, int C, int n, int levels_max,
@@ -275,8 +287,9 @@ int dwtx_decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_
  * contiguous buffer, stream i at byte offset sum over j < i of round8(dev_lens[j]) — so that a step's streams travel as one
  * message per peer instead of one per frame.  dev_offsets (optional, [n + 1]) receives the offsets, [n] = the total; the
  * receiver computes the same offsets from the gathered lengths.  A length beyond the stride is clamped to it; nothing is
- * written beyond out_bytes (size it from the lengths: the sum of the rounded lengths, at most n * stream_stride).
- * Asynchronous on the context's stream. */
+ * written beyond out_bytes (size it from the lengths: the sum of the rounded lengths, at most n * stream_stride).  A
+ * shorter out_bytes receives the first out_bytes bytes of the message, and dev_offsets[n] still reports the size the
+ * whole message needs: the caller detects the cut by comparing the two.  Asynchronous on the context's stream. */
 int dwtx_pack_streams(dwtx_ctx *ctx, uint8_t *dev_out, size_t out_bytes, unsigned long long *dev_offsets,
 	const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens, int n);
 
@@ -284,7 +297,12 @@ int dwtx_pack_streams(dwtx_ctx *ctx, uint8_t *dev_out, size_t out_bytes, unsigne
  * read_pnm/write_pnm and the byte sink.  pixels_max < 0 = no PIXELS argument.
  * dwtx_decode_images returns DWTX_ERR_ARG for a bad header and DWTX_ERR_IO when
  * the root image or plane counts cannot be read (both exit code 1 in decode.c); a
- * single stream that claims more than 16 bit planes is DWTX_ERR_ARG too (status 2). */
+ * single stream that claims more than 16 bit planes is DWTX_ERR_ARG too (status 2).
+ * dwtx_encode_images: out_stride a multiple of 8; a stream longer than out_stride is
+ * DWTX_ERR_CAPACITY, its slot is not written, and neither is anything past
+ * out_lens[i] bytes of a slot.  dwtx_decode_images: lens[i] <= stream_stride (a
+ * multiple of 8), else DWTX_ERR_ARG; pixels as for dwtx_decode_device (a picture
+ * larger than pix_stride is DWTX_ERR_ARG and is not written). */
 int dwtx_encode_images(dwtx_ctx *ctx, const uint8_t *host_pix, int W, int H, int C, int n, long capacity,
 	uint8_t *host_out, size_t out_stride, size_t *out_lens, dwtx_stats *stats);
 int dwtx_decode_images(dwtx_ctx *ctx, const uint8_t *host_streams, size_t stream_stride, const size_t *lens, int n,

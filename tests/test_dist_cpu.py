@@ -6,6 +6,7 @@ import subprocess
 import sys
 import textwrap
 
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -146,6 +147,43 @@ def _worker_uneven(rank, world, port, q):
 
 def test_gather_with_empty_uneven_and_many_streams_world2():
     assert all(r[1] for r in _run_world(_worker_uneven))
+
+
+def _worker_beyond_stride(rank, world, port, q):
+    """Lengths beyond the stride (a caller's bookkeeping, or lengths of a capacity above the stride): the sender clamps
+    them to the stride, and so must the receiver's views — a packed view cut at the announced length would run into
+    the next stream's bytes."""
+    from dwt_amd.dist import gather_streams
+
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    n, stride = 5, 64
+    lens = torch.tensor([10, 64, 65, 1000, 7], dtype=torch.int64)
+    streams = (torch.arange(n * stride, dtype=torch.int64) * (rank + 3) + 1).remainder(251).to(torch.uint8).view(n, stride)
+    ok = True
+    for mode in ("packed", "rows"):
+        got = gather_streams(streams, lens, dst=0, mode=mode)
+        if rank == 0:
+            for r in range(world):
+                want = (torch.arange(n * stride, dtype=torch.int64) * (r + 3) + 1).remainder(251).to(torch.uint8).view(n, stride)
+                for i in range(n):
+                    v = got.stream(r, i)
+                    ok &= bool(torch.equal(v, want[i, :min(int(lens[i]), stride)]))
+    q.put((rank, bool(ok)))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_lengths_beyond_the_stride_are_clamped_in_both_modes_world2():
+    assert all(r[1] for r in _run_world(_worker_beyond_stride))
+
+
+def test_strides_that_are_not_a_multiple_of_8_are_refused():
+    from dwt_amd.dist import torch_pack
+
+    with pytest.raises(AssertionError):
+        torch_pack(torch.zeros((2, 60), dtype=torch.uint8), [4, 4], torch.zeros(64, dtype=torch.uint8))
 
 
 def test_packed_offsets_and_torch_pack_agree():
