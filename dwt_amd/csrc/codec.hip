@@ -6,8 +6,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-enum { SLOT_CD_A = 16, SLOT_CD_B, SLOT_CD_INFO, SLOT_CD_IO, SLOT_CD_IO2, SLOT_CD_LENS, SLOT_CD_F16 };
-
 extern "C" size_t dwtx_encode_bound(int W, int H, int C)
 {
 	// 8-bit sources: at most 11 bit planes per coefficient (9 bits of pixel range, +1 for YCoCg chroma, +1

@@ -102,11 +102,42 @@ static inline bool dwtx_dims_ok(int W, int H)
 		}                                                                                   \
 	} while (0)
 
-// scratch slot assignment
+// scratch slot assignment, for every file in one place
 enum {
-	SLOT_LIFT_A = 0,
-	SLOT_LIFT_B = 1,
+	SLOT_LIFT_A = 0, SLOT_LIFT_B,   // lift.hip
+	SLOT_PK_CUM, SLOT_PK_SMALL, SLOT_PK_ENT, SLOT_PK_TOKBIG, SLOT_PK_TOK16, SLOT_PK_LUT, SLOT_PK_CHUNK, SLOT_PK_STAGE,   // pack.hip
+	SLOT_UP_SMALL = 12, SLOT_UP_BITS, SLOT_UP_TILES, SLOT_UP_CHUNKS,   // unpack.hip
+	SLOT_CD_A, SLOT_CD_B, SLOT_CD_INFO, SLOT_CD_IO, SLOT_CD_IO2, SLOT_CD_LENS, SLOT_CD_F16,   // codec.hip
 };
+static_assert(SLOT_CD_F16 < DWTX_SCRATCH_SLOTS, "more scratch slots than dwtx_ctx has");
+
+static inline size_t dwtx_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Host: typed tables one after the other in one scratch slot, each starting on a 256-byte boundary (the slot's size
+// is rounded up to one too).  carve() calls fn(Carve &) twice: once to measure the slot (base null: only offsets
+// move), then, once dwtx_scratch has it, to point every table into it.  Returns the slot, or null if it could not
+// be had (the tables are then not set).
+struct Carve {
+	char *base;
+	size_t off;
+	template <class T> void take(T *&table, size_t count)
+	{
+		if (base)
+			table = (T *)(base + off);
+		off = dwtx_align_up(off + sizeof(T) * count, 256);
+	}
+};
+template <class F> char *carve(dwtx_ctx *ctx, int slot, F &&fn)
+{
+	Carve c{ nullptr, 0 };
+	fn(c);
+	c.base = (char *)dwtx_scratch(ctx, slot, c.off);
+	if (c.base) {
+		c.off = 0;
+		fn(c);
+	}
+	return c.base;
+}
 
 // lift.hip: the finest lifting level reads / writes 8-bit pixels itself (the widening of pnm.h:69-74, the
 // clamp of pnm.h:108 and, for RGB, the YCoCg-R colour transform of image.h:39-65 fused into it).  dwtx_gray8_ok says whether the
@@ -160,6 +191,35 @@ int dwtx_fwd_pixels8_hist(dwtx_ctx *ctx, int32_t *out, const uint8_t *pix, int W
 int dwtx_transformation_fwd_hist(dwtx_ctx *ctx, int32_t *out, const int32_t *in, int W, int H, int nplanes, const dwtx_hist_sink *sink,
 	unsigned *hist_levels);
 int dwtx_get_tiles(dwtx_ctx *ctx, int W, int H, dwtx_tiles *out);
+
+// What the entropy stage's geometries (PackGeom in pack.hip, UnpackGeom in unpack.hip) share: sizes, rings and tiles,
+// with no pyramid to read or write yet
+template <class G> int dwtx_fill_geom(dwtx_ctx *ctx, int W, int H, int C, G &g, dwtx_tiles &tiles)
+{
+	int lengths[DWTX_MAX_LEVELS], pixels[DWTX_MAX_LEVELS], widths[DWTX_MAX_LEVELS], heights[DWTX_MAX_LEVELS];
+	g.levels = dwtx_compute_lengths(lengths, pixels, widths, heights, W, H, DWTX_MIN_LEN);
+	for (int l = 0; l <= g.levels; ++l) {
+		g.pixels[l] = pixels[l];
+		g.side[l] = l < g.levels ? lengths[l + 1] : 0;
+	}
+	g.C = C;
+	g.W = W;
+	g.H = H;
+	g.total = (long)W * H;
+	g.pyr = nullptr;
+	g.fine16 = nullptr;
+	g.lv16 = 0u;
+	g.sq_levels = 0;
+	const int rc = dwtx_get_tiles(ctx, W, H, &tiles);
+	if (rc)
+		return rc;
+	for (int l = 0; l <= g.levels; ++l)
+		g.tile_first[l] = tiles.tile_first[l];
+	g.tile_base = tiles.base;
+	g.tile_cnt = tiles.cnt;
+	g.tile_blk = tiles.blk;
+	return DWTX_OK;
+}
 
 // Tiles straight from / to the pyramid (hilbert_dev.h): on the ring levels in the mask, tiles that are whole 32x32
 // squares need no linearised copy — the entropy stage reads (pack.hip) / writes (unpack.hip) them in the pyramid itself;

@@ -2422,12 +2422,6 @@ __global__ __launch_bounds__(256) void k_refcopy(Work w, unsigned *out, long out
 
 // ------------------------------------------------------------------ driver ---
 
-enum {
-	SLOT_PK_CUM = 2, SLOT_PK_SMALL, SLOT_PK_ENT, SLOT_PK_TOKBIG, SLOT_PK_TOK16, SLOT_PK_LUT, SLOT_PK_CHUNK, SLOT_PK_STAGE,
-};
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 extern "C" int dwtx_encode_planes(dwtx_ctx *ctx, const int32_t *lin, int W, int H, int C, int n, long capacity,
 	uint8_t *out, size_t out_stride, dwtx_stream_info *dev_info)
 {
@@ -2438,40 +2432,18 @@ extern "C" int dwtx_encode_planes(dwtx_ctx *ctx, const int32_t *lin, int W, int 
 // entropy stage start from)
 static int pack_geometry(dwtx_ctx *ctx, int W, int H, int C, int n, PackGeom &g, Work &w, dwtx_tiles &tiles)
 {
-	{
-		int lengths[DWTX_MAX_LEVELS], pixels[DWTX_MAX_LEVELS], widths[DWTX_MAX_LEVELS], heights[DWTX_MAX_LEVELS];
-		g.levels = dwtx_compute_lengths(lengths, pixels, widths, heights, W, H, DWTX_MIN_LEN);
-		for (int l = 0; l <= g.levels; ++l)
-			g.pixels[l] = pixels[l];
-		for (int l = 0; l < g.levels; ++l)
-			g.side[l] = lengths[l + 1];
-		g.side[g.levels] = 0;
-	}
-	g.pyr = nullptr;
-	g.fine16 = nullptr;
-	g.lv16 = 0u;
-	g.sq_levels = 0;
-	g.C = C;
-	g.W = W;
-	g.H = H;
-	g.total = (long)W * H;
-	const int rc = dwtx_get_tiles(ctx, W, H, &tiles);
+	const int rc = dwtx_fill_geom(ctx, W, H, C, g, tiles);
 	if (rc)
 		return rc;
-	for (int l = 0; l <= g.levels; ++l)
-		g.tile_first[l] = tiles.tile_first[l];
-	g.tile_base = tiles.base;
-	g.tile_cnt = tiles.cnt;
-	g.tile_blk = tiles.blk;
 	memset(&w, 0, sizeof(w));
 	w.NT = tiles.NT;
 	w.NTP = (tiles.NT + 3) / 4 * 4;
-	const size_t b = align_up(sizeof(unsigned short) * (size_t)n * C * w.NT * NCUM, 256);
-	w.cum = (unsigned short *)dwtx_scratch(ctx, SLOT_PK_CUM, b + sizeof(unsigned) * (size_t)n * C * w.NTP);
-	if (!w.cum)
-		return DWTX_ERR_NOMEM;
-	w.tile_mx = (unsigned *)((char *)w.cum + b);
-	return DWTX_OK;
+	const size_t nplanes = (size_t)n * C;
+	const bool ok = carve(ctx, SLOT_PK_CUM, [&](Carve &c) {
+		c.take(w.cum, nplanes * w.NT * NCUM);
+		c.take(w.tile_mx, nplanes * w.NTP);
+	});
+	return ok ? DWTX_OK : DWTX_ERR_NOMEM;
 }
 
 // The forward transform of the same n images, queued after this on the context's stream, adds the histograms of the
@@ -2563,91 +2535,60 @@ int dwtx_encode_planes_ex(dwtx_ctx *ctx, const int32_t *lin, const int32_t *pyr,
 	const int nplanes = n * C;
 
 	// carve scratch
-	{
-		size_t off = 0;
-		auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-		const size_t o_info = take(sizeof(ImgInfo) * n);
-		const size_t o_slow = take(sizeof(int) * n);
-		const size_t o_sbits = take(sizeof(unsigned long long) * n);
-		const size_t o_sd = take(sizeof(int) * (size_t)n * MAX_SEGS);
-		const size_t o_eb = take(sizeof(int) * (size_t)n * (MAX_SEGS + 1));
-		const size_t o_sr = take(sizeof(unsigned) * (size_t)n * MAX_SEGS);
-		const size_t o_ro = take(sizeof(unsigned long long) * (size_t)n * MAX_SEGS);
-		const size_t o_bt = take(sizeof(unsigned) * (size_t)n * MAX_SEGS);
-		const size_t o_sx = take(sizeof(int) * (size_t)n * 48 * MAX_PLANES);
-		const size_t o_lv = take(sizeof(unsigned) * (size_t)n * 48);
-		char *small = (char *)dwtx_scratch(ctx, SLOT_PK_SMALL, off);
-		if (!small)
-			return DWTX_ERR_NOMEM;
-		w.info = (ImgInfo *)(small + o_info);
-		w.slow = (int *)(small + o_slow);
-		w.stream_bits = (unsigned long long *)(small + o_sbits);
-		w.seg_desc = (int *)(small + o_sd);
-		w.seg_ebase = (int *)(small + o_eb);
-		w.seg_refs = (unsigned *)(small + o_sr);
-		w.seg_rawoff = (unsigned long long *)(small + o_ro);
-		w.brk_tok = (unsigned *)(small + o_bt);
-		w.segidx = (int *)(small + o_sx);
-		w.live = (unsigned *)(small + o_lv);
-		DWTX_HIP(hipMemsetAsync(small, 0, o_sd, ctx->stream));
-		if (ctx->opt[DWTX_OPT_EXACT_ORDERS])   // test hook: take the hierarchical 32-state pass for every image
-			DWTX_HIP(hipMemsetD32Async((hipDeviceptr_t)(small + o_slow), 1, (size_t)n, ctx->stream));   // (ints of 1: hipMemsetAsync would set bytes)
+	const size_t imgs = n;
+	char *small = carve(ctx, SLOT_PK_SMALL, [&](Carve &c) {
+		c.take(w.info, imgs);
+		c.take(w.slow, imgs);
+		c.take(w.stream_bits, imgs);
+		c.take(w.seg_desc, imgs * MAX_SEGS);
+		c.take(w.seg_ebase, imgs * (MAX_SEGS + 1));
+		c.take(w.seg_refs, imgs * MAX_SEGS);
+		c.take(w.seg_rawoff, imgs * MAX_SEGS);
+		c.take(w.brk_tok, imgs * MAX_SEGS);
+		c.take(w.segidx, imgs * 48 * MAX_PLANES);
+		c.take(w.live, imgs * 48);
+	});
+	if (!small)
+		return DWTX_ERR_NOMEM;
+	DWTX_HIP(hipMemsetAsync(w.info, 0, (char *)w.seg_desc - (char *)w.info, ctx->stream));   // info, slow, stream_bits
+	if (ctx->opt[DWTX_OPT_EXACT_ORDERS])   // test hook: take the hierarchical 32-state pass for every image
+		DWTX_HIP(hipMemsetD32Async((hipDeviceptr_t)w.slow, 1, (size_t)n, ctx->stream));   // (ints of 1: hipMemsetAsync would set bytes)
 
-		off = 0;
-		const size_t o_on = take(sizeof(short) * (size_t)n * w.ES);
-		const size_t o_ze = take(sizeof(short) * (size_t)n * w.ES);
-		const size_t o_re = take(sizeof(short) * (size_t)n * w.ES);
-		const size_t o_tz = take(sizeof(short) * (size_t)n * w.ES);
-		const size_t o_sg = take(sizeof(short) * (size_t)n * w.ES);
-		const size_t o_tb = take(sizeof(unsigned) * (size_t)n * (w.ES + 1));
-		const size_t o_rc = take(sizeof(unsigned) * (size_t)n * (w.ES + 1));
-		const size_t o_rw = take(sizeof(unsigned) * (size_t)n * (w.ES + 1));
-		const size_t o_ca = take(sizeof(RunMap) * (size_t)n * w.NCB);
-		const size_t o_ci = take(sizeof(unsigned) * (size_t)n * w.NCB);
-		const size_t o_ek = take(sizeof(unsigned) * 3 * (size_t)n * w.NCB);
-		char *ent = (char *)dwtx_scratch(ctx, SLOT_PK_ENT, off);
-		if (!ent)
-			return DWTX_ERR_NOMEM;
-		w.ent_ones = (unsigned short *)(ent + o_on);
-		w.ent_zeros = (unsigned short *)(ent + o_ze);
-		w.ent_refs = (unsigned short *)(ent + o_re);
-		w.ent_tz = (unsigned short *)(ent + o_tz);
-		w.ent_seg = (unsigned short *)(ent + o_sg);
-		w.ent_tokbase = (unsigned *)(ent + o_tb);
-		w.ent_refscum = (unsigned *)(ent + o_rc);
-		w.ent_refw = (unsigned *)(ent + o_rw);
-		w.carry_agg = (RunMap *)(ent + o_ca);
-		w.carry_in = (unsigned *)(ent + o_ci);
-		w.ent_blk = (unsigned *)(ent + o_ek);
+	char *ent = carve(ctx, SLOT_PK_ENT, [&](Carve &c) {
+		c.take(w.ent_ones, imgs * w.ES);
+		c.take(w.ent_zeros, imgs * w.ES);
+		c.take(w.ent_refs, imgs * w.ES);
+		c.take(w.ent_tz, imgs * w.ES);
+		c.take(w.ent_seg, imgs * w.ES);
+		c.take(w.ent_tokbase, imgs * (w.ES + 1));
+		c.take(w.ent_refscum, imgs * (w.ES + 1));
+		c.take(w.ent_refw, imgs * (w.ES + 1));
+		c.take(w.carry_agg, imgs * w.NCB);
+		c.take(w.carry_in, imgs * w.NCB);
+		c.take(w.ent_blk, imgs * w.NCB * 3);
+	});
+	if (!ent)
+		return DWTX_ERR_NOMEM;
 
-		w.tok_big = (unsigned *)dwtx_scratch(ctx, SLOT_PK_TOKBIG, sizeof(unsigned) * (size_t)n * w.TS);
-		w.tok16 = (unsigned short *)dwtx_scratch(ctx, SLOT_PK_TOK16, sizeof(unsigned short) * (size_t)n * w.TS);
-		w.stage = (unsigned *)dwtx_scratch(ctx, SLOT_PK_STAGE, sizeof(unsigned) * (size_t)n * w.SW);
-		if (!w.tok_big || !w.tok16 || !w.stage)
-			return DWTX_ERR_NOMEM;
+	w.tok_big = (unsigned *)dwtx_scratch(ctx, SLOT_PK_TOKBIG, sizeof(unsigned) * (size_t)n * w.TS);
+	w.tok16 = (unsigned short *)dwtx_scratch(ctx, SLOT_PK_TOK16, sizeof(unsigned short) * (size_t)n * w.TS);
+	w.stage = (unsigned *)dwtx_scratch(ctx, SLOT_PK_STAGE, sizeof(unsigned) * (size_t)n * w.SW);
+	if (!w.tok_big || !w.tok16 || !w.stage)
+		return DWTX_ERR_NOMEM;
 
-		w.sublut = (unsigned char *)dwtx_scratch(ctx, SLOT_PK_LUT, (size_t)n * w.NCS * 64 * 32);
-		off = 0;
-		const size_t o_lut = take((size_t)n * w.NCS * 32);
-		const size_t o_gl = take((size_t)n * w.NGS * 32);
-		const size_t o_ce = take((size_t)n * w.NCS);
-		const size_t o_ge = take((size_t)n * w.NGS);
-		const size_t o_go = take((size_t)n * w.NCS * 64);
-		const size_t o_cb = take(sizeof(unsigned long long) * (size_t)n * w.NCS);
-		const size_t o_cs = take(sizeof(unsigned long long) * (size_t)n * w.NCS);
-		const size_t o_lb = take(sizeof(unsigned long long) * (size_t)n * w.NCS * 64);
-		char *ch = (char *)dwtx_scratch(ctx, SLOT_PK_CHUNK, off);
-		if (!w.sublut || !ch)
-			return DWTX_ERR_NOMEM;
-		w.lut = (unsigned char *)(ch + o_lut);
-		w.glut = (unsigned char *)(ch + o_gl);
-		w.chunk_entry = (unsigned char *)(ch + o_ce);
-		w.group_entry = (unsigned char *)(ch + o_ge);
-		w.grp_ord = (unsigned char *)(ch + o_go);
-		w.chunk_bits = (unsigned long long *)(ch + o_cb);
-		w.chunk_base = (unsigned long long *)(ch + o_cs);
-		w.lane_bits = (unsigned long long *)(ch + o_lb);
-	}
+	w.sublut = (unsigned char *)dwtx_scratch(ctx, SLOT_PK_LUT, (size_t)n * w.NCS * 64 * 32);
+	char *ch = carve(ctx, SLOT_PK_CHUNK, [&](Carve &c) {
+		c.take(w.lut, imgs * w.NCS * 32);
+		c.take(w.glut, imgs * w.NGS * 32);
+		c.take(w.chunk_entry, imgs * w.NCS);
+		c.take(w.group_entry, imgs * w.NGS);
+		c.take(w.grp_ord, imgs * w.NCS * 64);
+		c.take(w.chunk_bits, imgs * w.NCS);
+		c.take(w.chunk_base, imgs * w.NCS);
+		c.take(w.lane_bits, imgs * w.NCS * 64);
+	});
+	if (!w.sublut || !ch)
+		return DWTX_ERR_NOMEM;
 
 	hipStream_t s = ctx->stream;
 	const long out_words = (long)(out_stride / 4);

@@ -145,7 +145,7 @@ struct DWork {
 	unsigned *hop_ntok;             // [n][MAX_HOPS] tokens to apply (walker-parsed chunk pieces)
 	unsigned *breaks;               // [n*FAM][NCH] chunk indices whose arriving path does not rejoin, ascending
 	unsigned *todo[2];              // [n*FAM][LINK_SHARDS][todo_cap] chunks to re-parse, this round / next round
-	unsigned *todo_count;           // [LINK_ROUNDS + 1][n*FAM][LINK_SHARDS]: entries queued for round r, zeroed once per call
+	unsigned *todo_count;           // [LINK_ROUNDS + 2][n*FAM][LINK_SHARDS]: entries queued for round r, zeroed once per call
 	long todo_round;                // elements per round of todo_count
 	long todo_cap;
 	unsigned long long *dbg;
@@ -2388,9 +2388,50 @@ __global__ __launch_bounds__(256) void k_nch(DWork w, const unsigned long long *
 
 } // namespace
 
-enum { SLOT_UP_SMALL = 12, SLOT_UP_BITS, SLOT_UP_TILES, SLOT_UP_CHUNKS };
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// Every per-image table of DWork, and the decoder's clear_words, in the order of their slots: f(slot, table, elements per
+// image, rows).  A table is `rows` blocks of [n][elements] (todo_count: [LINK_ROUNDS + 2][n*FAM][LINK_SHARDS]); image i's
+// part of every block starts at table + i * elements.  The one list both carves the slots and slices a batch
+// (dwtx_decode_planes_ex); the sizes in `w` (BW, NT, NCH, NB, MAX_HOPS, todo_cap) are set before either.
+template <class F> static void dwork_tables(DWork &w, unsigned *&clear_words, int C, F &&f)
+{
+	auto t = [&](int slot, auto *&table, long elems) { f(slot, table, elems, 1l); };
+	t(SLOT_UP_SMALL, w.info, 1);
+	t(SLOT_UP_SMALL, w.segidx, 48 * MAX_PLANES);
+	t(SLOT_UP_SMALL, w.seg_desc, MAX_SEGS);
+	t(SLOT_UP_SMALL, w.seg_symbase, MAX_SEGS);
+	t(SLOT_UP_SMALL, w.seg_b2, MAX_SEGS);
+	t(SLOT_UP_SMALL, w.seg_n2done, MAX_SEGS);
+	t(SLOT_UP_SMALL, w.nonsig, 48);
+	t(SLOT_UP_BITS, w.symbits, w.BW);
+	t(SLOT_UP_TILES, w.tile_nonsig, (long)C * w.NT);
+	t(SLOT_UP_TILES, w.tile_rank, (long)C * MAX_PLANES * w.NT);
+	t(SLOT_UP_TILES, w.count_base, (long)C * 16);
+	t(SLOT_UP_CHUNKS, w.exitX, FAM * w.NCH);
+	t(SLOT_UP_CHUNKS, w.entryE, FAM * w.NCH);
+	t(SLOT_UP_CHUNKS, w.cs, FAM * (w.NCH + 1));
+	t(SLOT_UP_CHUNKS, w.ct, FAM * (w.NCH + 1));
+	t(SLOT_UP_CHUNKS, w.cg, FAM * (w.NCH + 1));
+	t(SLOT_UP_CHUNKS, w.part_s, FAM * w.NB);
+	t(SLOT_UP_CHUNKS, w.part_t, FAM * w.NB);
+	t(SLOT_UP_CHUNKS, w.part_g, FAM * w.NB);
+	t(SLOT_UP_CHUNKS, w.hop_seg, w.MAX_HOPS);
+	t(SLOT_UP_CHUNKS, w.hop_first, w.MAX_HOPS);
+	t(SLOT_UP_CHUNKS, w.hop_last, w.MAX_HOPS);
+	t(SLOT_UP_CHUNKS, w.hop_q0, w.MAX_HOPS);
+	t(SLOT_UP_CHUNKS, w.hop_entry, w.MAX_HOPS);
+	t(SLOT_UP_CHUNKS, w.hop_ntok, w.MAX_HOPS);
+	t(SLOT_UP_CHUNKS, w.breaks, FAM * w.NCH);
+	t(SLOT_UP_CHUNKS, w.todo[0], FAM * 64 * w.todo_cap);
+	t(SLOT_UP_CHUNKS, w.todo[1], FAM * 64 * w.todo_cap);   // (= todo[0] + n*FAM*64*todo_cap: a multiple of 256 bytes)
+	f(SLOT_UP_CHUNKS, w.todo_count, (long)FAM * LINK_SHARDS, (long)LINK_ROUNDS + 2);
+	t(SLOT_UP_CHUNKS, w.nhops, 1);
+	t(SLOT_UP_CHUNKS, w.nch, 1);
+	t(SLOT_UP_CHUNKS, clear_words, 1);
+	t(SLOT_UP_CHUNKS, w.idx, MAX_SEGS);
+	t(SLOT_UP_CHUNKS, w.segres, MAX_SEGS);
+	t(SLOT_UP_CHUNKS, w.idx_nsegs, 1);
+	t(SLOT_UP_CHUNKS, w.seg_slot, MAX_SEGS + 1);
+}
 
 // `done(user, first, count)` (optional) is called on the host as soon as host_info[first..first+count)
 // is valid and every kernel writing those images' planes has been enqueued on ctx->stream (or
@@ -2406,46 +2447,21 @@ int dwtx_decode_planes_ex(dwtx_ctx *ctx, int32_t *lin, int32_t *pyr, const uint8
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
 	UnpackGeom g;
+	dwtx_tiles tiles;
 	{
-		int lengths[DWTX_MAX_LEVELS], pixels[DWTX_MAX_LEVELS], widths[DWTX_MAX_LEVELS], heights[DWTX_MAX_LEVELS];
-		g.levels = dwtx_compute_lengths(lengths, pixels, widths, heights, W, H, DWTX_MIN_LEN);
-		for (int l = 0; l <= g.levels; ++l)
-			g.pixels[l] = pixels[l];
+		const int rc_geom = dwtx_fill_geom(ctx, W, H, C, g, tiles);
+		if (rc_geom)
+			return rc_geom;
 	}
-	g.C = C;
-	g.W = W;
-	g.H = H;
-	g.total = (long)W * H;
 	g.lin_stride = g.total;
 	g.levels_max = levels_max < 0 || levels_max > g.levels ? g.levels : levels_max;
-	g.pyr = nullptr;
-	g.fine16 = nullptr;
-	g.lv16 = 0u;
-	g.sq_levels = 0;
-	{
-		dwtx_geom gg;
-		dwtx_geometry(&gg, W, H);
-		for (int l = 0; l <= g.levels; ++l)
-			g.side[l] = l < g.levels ? gg.lengths[l + 1] : 0;
-	}
 	// the levels that are full power-of-two squares can go straight into the pyramid (k_apply_all)
 	const unsigned sq_all = pyr && !((uintptr_t)pyr & 15) && !ctx->opt[DWTX_OPT_NO_SQUARE_TILES] ? dwtx_square_levels(W, H) : 0u;
 	constexpr int MAX_PARTS = 4;
 	unsigned part_mask[MAX_PARTS] = { 0u, 0u, 0u, 0u };
 	int part_first[MAX_PARTS + 1] = { 0, 0, 0, 0, 0 };   // images [part_first[k], part_first[k+1]) are part k
 	auto part_of = [&](int i0) { int k = 0; while (k + 1 < MAX_PARTS && part_first[k + 1] <= i0 && part_first[k + 1] > 0) ++k; return k; };
-	dwtx_tiles tiles;
-	{
-		const int rc_tiles = dwtx_get_tiles(ctx, W, H, &tiles);
-		if (rc_tiles)
-			return rc_tiles;
-	}
 	const int NT = tiles.NT;
-	for (int l = 0; l <= g.levels; ++l)
-		g.tile_first[l] = tiles.tile_first[l];
-	g.tile_base = tiles.base;
-	g.tile_cnt = tiles.cnt;
-	g.tile_blk = tiles.blk;
 	const int nplanes = n * C;
 
 	DWork w;
@@ -2468,101 +2484,31 @@ int dwtx_decode_planes_ex(dwtx_ctx *ctx, int32_t *lin, int32_t *pyr, const uint8
 #endif
 	// every segment owns ceil32(ring size) symbol slots; at most MAX_PLANES segments per (channel, level)
 	w.BW = ((long)((((unsigned long long)g.total + 32ull * g.levels) * C * MAX_PLANES) >> 4) + 128 + 3) & ~3l;   // 2 bits per symbol; whole 16-byte groups per image
+	// speculative chunk tables
+	w.NCH = (long)((stream_stride * 8 + CH_BITS - 1) / CH_BITS);
+	w.NCH = (w.NCH + 1 + 3) / 4 * 4 - 1;   // NCH+1 table rows per stream, a multiple of 4 for the vectorised scans
+	w.NB = (w.NCH + 1 + SCAN_BLOCK - 1) / SCAN_BLOCK;
+	w.MAX_HOPS = 8 * MAX_SEGS + w.NCH / 8;
+	w.fam = 1;
+	w.todo_cap = ((w.NCH + 256) / 256 + 63) / 64 * 256 + 256;   // chunks whose workgroup maps to one shard
+	w.todo_round = (long)n * FAM * LINK_SHARDS;
+	auto carve_tables = [&](int slot) {
+		return carve(ctx, slot, [&](Carve &c) {
+			dwork_tables(w, clear_words, C, [&](int in_slot, auto *&table, long elems, long rows) {
+				if (in_slot == slot)
+					c.take(table, (size_t)n * rows * elems);
+			});
+		});
+	};
 	{
-		size_t off = 0;
-		auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-		const size_t o_info = take(sizeof(DecInfo) * n);
-		const size_t o_idx = take(sizeof(int) * (size_t)n * 48 * MAX_PLANES);
-		const size_t o_zero_end = off;
-		const size_t o_sd = take(sizeof(int) * (size_t)n * MAX_SEGS);
-		const size_t o_sym = take(sizeof(unsigned long long) * (size_t)n * MAX_SEGS);
-		const size_t o_b2 = take(sizeof(unsigned long long) * (size_t)n * MAX_SEGS);
-		const size_t o_n2 = take(sizeof(unsigned) * (size_t)n * MAX_SEGS);
-		const size_t o_ns = take(sizeof(int) * (size_t)n * 48);
-		char *small = (char *)dwtx_scratch(ctx, SLOT_UP_SMALL, off);
-		unsigned *bits = (unsigned *)dwtx_scratch(ctx, SLOT_UP_BITS, sizeof(unsigned) * (size_t)n * w.BW);
-		off = 0;
-		const size_t o_ts = take(sizeof(short) * (size_t)nplanes * NT);
-		const size_t o_tr = take(sizeof(unsigned) * (size_t)nplanes * MAX_PLANES * NT);
-		const size_t o_cb = take(sizeof(unsigned long long) * (size_t)nplanes * 16);
-		char *tiles = (char *)dwtx_scratch(ctx, SLOT_UP_TILES, off);
-		if (!small || !bits || !tiles)
+		char *small = carve_tables(SLOT_UP_SMALL);
+		char *bits = carve_tables(SLOT_UP_BITS);
+		char *tile_tables = carve_tables(SLOT_UP_TILES);
+		if (!small || !bits || !tile_tables || !carve_tables(SLOT_UP_CHUNKS))
 			return DWTX_ERR_NOMEM;
-		w.info = (DecInfo *)(small + o_info);
-		w.segidx = (int *)(small + o_idx);
-		w.seg_desc = (int *)(small + o_sd);
-		w.seg_symbase = (unsigned long long *)(small + o_sym);
-		w.seg_b2 = (unsigned long long *)(small + o_b2);
-		w.seg_n2done = (unsigned *)(small + o_n2);
-		w.nonsig = (int *)(small + o_ns);
-		w.symbits = bits;
-		w.tile_nonsig = (unsigned short *)(tiles + o_ts);
-		w.tile_rank = (unsigned *)(tiles + o_tr);
-		w.count_base = (unsigned long long *)(tiles + o_cb);
-		// speculative chunk tables
-		w.NCH = (long)((stream_stride * 8 + CH_BITS - 1) / CH_BITS);
-		w.NCH = (w.NCH + 1 + 3) / 4 * 4 - 1;   // NCH+1 table rows per stream, a multiple of 4 for the vectorised scans
-		w.NB = (w.NCH + 1 + SCAN_BLOCK - 1) / SCAN_BLOCK;
-		off = 0;
-		w.MAX_HOPS = 8 * MAX_SEGS + w.NCH / 8;
-		w.fam = 1;
-		const size_t o_ep = take(sizeof(short) * (size_t)n * FAM * w.NCH);
-		const size_t o_eq = take(sizeof(short) * (size_t)n * FAM * w.NCH);
-		const size_t o_cs = take(sizeof(unsigned long long) * (size_t)n * FAM * (w.NCH + 1));
-		const size_t o_ct = take(sizeof(unsigned) * (size_t)n * FAM * (w.NCH + 1));
-		const size_t o_cg = take(sizeof(unsigned) * (size_t)n * FAM * (w.NCH + 1));
-		const size_t o_ps = take(sizeof(unsigned long long) * (size_t)n * FAM * w.NB);
-		const size_t o_pt = take(sizeof(unsigned) * (size_t)n * FAM * w.NB);
-		const size_t o_pg = take(sizeof(unsigned) * (size_t)n * FAM * w.NB);
-		const size_t o_hs = take(sizeof(int) * (size_t)n * w.MAX_HOPS);
-		const size_t o_hf = take(sizeof(unsigned) * (size_t)n * w.MAX_HOPS);
-		const size_t o_hl = take(sizeof(unsigned) * (size_t)n * w.MAX_HOPS);
-		const size_t o_hq = take(sizeof(unsigned) * (size_t)n * w.MAX_HOPS);
-		const size_t o_he = take(sizeof(unsigned) * (size_t)n * w.MAX_HOPS);
-		const size_t o_hn = take(sizeof(unsigned) * (size_t)n * w.MAX_HOPS);
-		const size_t o_br = take(sizeof(unsigned) * (size_t)n * FAM * w.NCH);
-		w.todo_cap = ((w.NCH + 256) / 256 + 63) / 64 * 256 + 256;   // chunks whose workgroup maps to one shard
-		const size_t o_td = take(sizeof(unsigned) * 2 * (size_t)n * FAM * 64 * w.todo_cap);
-		const size_t o_tc = take(sizeof(unsigned) * (LINK_ROUNDS + 2) * (size_t)n * FAM * LINK_SHARDS);
-		const size_t o_nh = take(sizeof(int) * (size_t)n);
-		const size_t o_nc = take(sizeof(int) * (size_t)n);
-		const size_t o_cw = take(sizeof(unsigned) * (size_t)n);
-		const size_t o_ix = take(sizeof(SegIndex) * (size_t)n * MAX_SEGS);
-		const size_t o_sr = take(sizeof(SegResult) * (size_t)n * MAX_SEGS);
-		const size_t o_in = take(sizeof(int) * (size_t)n);
-		const size_t o_sl = take(sizeof(unsigned) * (size_t)n * (MAX_SEGS + 1));
-		char *chunks = (char *)dwtx_scratch(ctx, SLOT_UP_CHUNKS, off);
-		if (!chunks)
-			return DWTX_ERR_NOMEM;
-		w.exitX = (unsigned short *)(chunks + o_ep);
-		w.entryE = (unsigned short *)(chunks + o_eq);
-		w.cs = (unsigned long long *)(chunks + o_cs);
-		w.ct = (unsigned *)(chunks + o_ct);
-		w.cg = (unsigned *)(chunks + o_cg);
-		w.part_s = (unsigned long long *)(chunks + o_ps);
-		w.part_t = (unsigned *)(chunks + o_pt);
-		w.part_g = (unsigned *)(chunks + o_pg);
-		w.hop_seg = (int *)(chunks + o_hs);
-		w.hop_first = (unsigned *)(chunks + o_hf);
-		w.hop_last = (unsigned *)(chunks + o_hl);
-		w.hop_q0 = (unsigned *)(chunks + o_hq);
-		w.hop_entry = (unsigned *)(chunks + o_he);
-		w.hop_ntok = (unsigned *)(chunks + o_hn);
-		w.breaks = (unsigned *)(chunks + o_br);
-		w.todo[0] = (unsigned *)(chunks + o_td);
-		w.todo[1] = w.todo[0] + (size_t)n * FAM * 64 * w.todo_cap;
-		w.todo_count = (unsigned *)(chunks + o_tc);
-		w.todo_round = (long)n * FAM * LINK_SHARDS;
 		DWTX_HIP(hipMemsetAsync(w.todo_count, 0, sizeof(unsigned) * (LINK_ROUNDS + 2) * (size_t)w.todo_round, ctx->stream));
-		w.nhops = (int *)(chunks + o_nh);
-		w.nch = (int *)(chunks + o_nc);
-		clear_words = (unsigned *)(chunks + o_cw);
-		w.idx = (SegIndex *)(chunks + o_ix);
-		w.segres = (SegResult *)(chunks + o_sr);
-		w.idx_nsegs = (int *)(chunks + o_in);
-		w.seg_slot = (unsigned *)(chunks + o_sl);
 		DWTX_HIP(hipMemsetAsync(w.nhops, 0, sizeof(int) * (size_t)n, ctx->stream));
-		DWTX_HIP(hipMemsetAsync(small, 0, o_zero_end, ctx->stream));
+		DWTX_HIP(hipMemsetAsync(w.info, 0, (char *)w.seg_desc - (char *)w.info, ctx->stream));   // info, segidx
 		// The symbol bitmap (the one big clear, ~64 MB per 4096x4096 plane) is only needed by the token walk:
 		// it is cleared on the second stream while the chunk tables are built on the first.
 		{
@@ -2573,7 +2519,7 @@ int dwtx_decode_planes_ex(dwtx_ctx *ctx, int32_t *lin, int32_t *pyr, const uint8
 		DWTX_HIP(hipEventRecord(ctx->ev[2], ctx->stream));            // earlier work on the main stream may still read the bitmap
 		DWTX_HIP(hipStreamWaitEvent(ctx->aux, ctx->ev[2], 0));
 		hipLaunchKernelGGL(k_peek, dim3(dwtx_cdiv(n, 64)), dim3(64), 0, ctx->aux, g, streams, (long)stream_stride, dev_lens, w.BW, clear_words, n);
-		hipLaunchKernelGGL(k_clear_bitmaps, dim3(64, n), dim3(256), 0, ctx->aux, bits, w.BW, clear_words);
+		hipLaunchKernelGGL(k_clear_bitmaps, dim3(64, n), dim3(256), 0, ctx->aux, w.symbits, w.BW, clear_words);
 		// (the per-tile counters are first used after the token walk too: beside the clear, on the main stream, this
 		// trivial kernel waited 0.5 ms for a free slot and held the chunk kernels up)
 		hipLaunchKernelGGL(k_tiles_init, dim3(dwtx_cdiv(NT, 256), nplanes), dim3(256), 0, ctx->aux, g, w, nplanes);
@@ -2588,43 +2534,12 @@ int dwtx_decode_planes_ex(dwtx_ctx *ctx, int32_t *lin, int32_t *pyr, const uint8
 	// everything below works on a range of images [i0, i0+cnt): all tables are per image
 	auto slice = [&](int i0) {
 		DWork h = w;
-		h.info += i0;
-		h.segidx += (size_t)i0 * 48 * MAX_PLANES;
-		h.seg_desc += (size_t)i0 * MAX_SEGS;
-		h.seg_symbase += (size_t)i0 * MAX_SEGS;
-		h.seg_b2 += (size_t)i0 * MAX_SEGS;
-		h.seg_n2done += (size_t)i0 * MAX_SEGS;
-		h.nonsig += (size_t)i0 * 48;
-		h.symbits += (size_t)i0 * w.BW;
-		h.tile_nonsig += (size_t)i0 * C * NT;
-		h.tile_rank += (size_t)i0 * C * MAX_PLANES * NT;
-		h.count_base += (size_t)i0 * C * 16;
-		h.exitX += (size_t)i0 * FAM * w.NCH;
-		h.entryE += (size_t)i0 * FAM * w.NCH;
-		h.cs += (size_t)i0 * FAM * (w.NCH + 1);
-		h.ct += (size_t)i0 * FAM * (w.NCH + 1);
-		h.cg += (size_t)i0 * FAM * (w.NCH + 1);
-		h.part_s += (size_t)i0 * FAM * w.NB;
-		h.part_t += (size_t)i0 * FAM * w.NB;
-		h.part_g += (size_t)i0 * FAM * w.NB;
-		h.hop_seg += (size_t)i0 * w.MAX_HOPS;
-		h.hop_first += (size_t)i0 * w.MAX_HOPS;
-		h.hop_last += (size_t)i0 * w.MAX_HOPS;
-		h.hop_q0 += (size_t)i0 * w.MAX_HOPS;
-		h.hop_entry += (size_t)i0 * w.MAX_HOPS;
-		h.hop_ntok += (size_t)i0 * w.MAX_HOPS;
-		h.breaks += (size_t)i0 * FAM * w.NCH;
-		for (int k = 0; k < 2; ++k)
-			h.todo[k] += (size_t)i0 * FAM * 64 * w.todo_cap;
-		h.todo_count += (size_t)i0 * FAM * LINK_SHARDS;
-		h.nhops += i0;
-		h.nch += i0;
-		h.idx += (size_t)i0 * MAX_SEGS;
-		h.segres += (size_t)i0 * MAX_SEGS;
-		h.idx_nsegs += i0;
-		h.seg_slot += (size_t)i0 * (MAX_SEGS + 1);
+		unsigned *cw = clear_words;   // (not DWork's: k_peek takes the whole batch's)
+		dwork_tables(h, cw, C, [&](int, auto *&table, long elems, long) { table += (size_t)i0 * elems; });
+#ifdef DWTX_DEBUG_HOOKS
 		if (h.dbg)
 			h.dbg += (size_t)i0 * 8;
+#endif
 		return h;
 	};
 	// chunk tables; then (walk) token walk and symbol bits of the hopped-over chunks
