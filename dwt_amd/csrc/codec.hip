@@ -35,13 +35,13 @@ static int encode_part(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int 
 		return rc;
 	// encode.c:160: levels that are full power-of-two squares stay in the pyramid (the coder reads their tiles there)
 	const unsigned sq = ctx->opt[DWTX_OPT_NO_SQUARE_TILES] ? 0u : dwtx_square_levels(W, H);
-	// The finest rings (up to five levels) as 16-bit values in planes of their own when the transform starts from 8-bit
-	// pixels — the finest ring, three quarters of all coefficients, cannot leave 11 bits then, the fifth level's not 15
-	// (lift.hip k_fwd_level_w) — and the coder reads their squares in place: the transform writes, and the coder reads,
-	// half the bytes for them.
+	// The finest rings as 16-bit values in planes of their own when the transform starts from 8-bit pixels — the finest
+	// ring, three quarters of all coefficients, cannot leave 11 bits then, and lift.hip bounds how many levels stay below
+	// 16 (dwtx_levels16) — and the coder reads their squares in place: the transform writes, and the coder reads, half the
+	// bytes for them.
 	dwtx_p16 fine16 = { nullptr, 0u };
 	const bool from_pixels = dwtx_gray8_ok(W, H, dev_pix, (size_t)W * H * C);
-	if (from_pixels && sq && !ctx->opt[DWTX_OPT_NO_FINE16] && (fine16.levels = dwtx_levels16(W, H, sq, 5))) {
+	if (from_pixels && sq && !ctx->opt[DWTX_OPT_NO_FINE16] && (fine16.levels = dwtx_levels16(W, H, sq))) {
 		fine16.planes = (int16_t *)dwtx_scratch(ctx, SLOT_CD_F16, sizeof(int16_t) * (size_t)W * H * C * n);
 		if (!fine16.planes)
 			return DWTX_ERR_NOMEM;
@@ -84,7 +84,7 @@ extern "C" int dwtx_transformation_fwd_pixels(dwtx_ctx *ctx, int32_t *dev_pyr, i
 		return rc;
 	dwtx_p16 fine16 = { nullptr, 0u };
 	const unsigned sq = dwtx_square_levels(W, H);
-	if (dev_rings16 && sq && (fine16.levels = dwtx_levels16(W, H, sq, 5)))
+	if (dev_rings16 && sq && (fine16.levels = dwtx_levels16(W, H, sq)))
 		fine16.planes = dev_rings16;
 	if (levels16)
 		*levels16 = fine16.planes ? fine16.levels : 0u;
@@ -102,7 +102,7 @@ extern "C" int dwtx_transformation_inv_pixels(dwtx_ctx *ctx, uint8_t *dev_pix, c
 		dwtx_set_error("the pixel transforms need W %% 4 == 0, more than 64 pixels on a side and 4-byte aligned pixels (%dx%d)", W, H);
 		return DWTX_ERR_ARG;
 	}
-	if (levels16 && levels16 != dwtx_levels16(W, H, dwtx_square_levels(W, H), 5))
+	if (levels16 && levels16 != dwtx_levels16(W, H, dwtx_square_levels(W, H)))
 		return DWTX_ERR_ARG;   // (the mask the forward call reported for this geometry, or none)
 	const dwtx_p16 f16 = { levels16 ? const_cast<int16_t *>(dev_rings16) : nullptr, levels16 };
 	return dwtx_inv_pixels8(ctx, dev_pix, (size_t)W * H * C, dev_pyr, W, H, C, n, &f16);
@@ -177,26 +177,23 @@ extern "C" int dwtx_decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, siz
 		return DWTX_ERR_NOMEM;
 	const size_t plane_ints = (size_t)W * H;
 	// 16-bit planes for the finest ring of whole pictures (see encode_part; the decoder checks the streams' plane counts)
-	// (every ring the 16-byte-per-lane inverse kernels take, up to five levels: what a stream holds is bounded by its
-	// plane counts on every level; the LL bands between the levels are sums of those and stay int32)
+	// (every ring the 16-byte-per-lane inverse kernels take: what a stream holds is bounded by its plane counts on
+	// every level; the LL bands between the levels are sums of those and stay int32)
 	dwtx_p16 fine16 = { nullptr, 0u };
 	{
 		const unsigned sq = ctx->opt[DWTX_OPT_NO_SQUARE_TILES] ? 0u : dwtx_square_levels(W, H);
-		if (sq && !ctx->opt[DWTX_OPT_NO_FINE16] && dwtx_gray8_ok(W, H, dev_pix, pix_stride) && (fine16.levels = dwtx_levels16(W, H, sq, 5))) {
+		if (sq && !ctx->opt[DWTX_OPT_NO_FINE16] && dwtx_gray8_ok(W, H, dev_pix, pix_stride) && (fine16.levels = dwtx_levels16(W, H, sq))) {
 			fine16.planes = (int16_t *)dwtx_scratch(ctx, SLOT_CD_F16, sizeof(int16_t) * (size_t)W * H * C * n);
 			if (!fine16.planes)
 				return DWTX_ERR_NOMEM;
 		}
 	}
-	// scratch both parts of the batch will ask for, sized once for the larger request
-	{
-		const size_t part_planes = (size_t)(n < 4 ? n : n - n / 2) * C;
-		const size_t w1 = (W + 1) / 2, h1 = (H + 1) / 2, w2 = (w1 + 1) / 2, h2 = (h1 + 1) / 2;
-		if (!dwtx_scratch(ctx, SLOT_CD_INFO, sizeof(int) * 48 * (size_t)n) ||
-			!dwtx_scratch(ctx, SLOT_LIFT_A, sizeof(int) * w1 * h1 * part_planes) ||
-			!dwtx_scratch(ctx, SLOT_LIFT_B, sizeof(int) * w2 * h2 * part_planes))
-			return DWTX_ERR_NOMEM;
-	}
+	// scratch both parts of the batch will ask for, sized once for the larger request (a slot that grows waits for the
+	// stream: `finish` must not grow one in the middle of the pipeline)
+	if (!dwtx_scratch(ctx, SLOT_CD_INFO, sizeof(int) * 48 * (size_t)n))
+		return DWTX_ERR_NOMEM;
+	if ((rc = dwtx_lift_scratch(ctx, W, H, (n < 4 ? n : n - n / 2) * C)))
+		return rc;
 	// reconstruction -> inverse transform -> pixels for images [first, first+count), queued on ctx->stream
 	auto finish = [&](int first, int count, unsigned fused) -> int {
 		const dwtx_decode_info &I = host_info[first];

@@ -143,7 +143,8 @@ template <class F> char *carve(dwtx_ctx *ctx, int slot, F &&fn)
 // clamp of pnm.h:108 and, for RGB, the YCoCg-R colour transform of image.h:39-65 fused into it).  dwtx_gray8_ok says whether the
 // shape allows it; image i of the inverse is written at pix + i*image_stride.
 bool dwtx_gray8_ok(int W, int H, const void *pix, size_t image_stride);
-int dwtx_fwd_pixels8(dwtx_ctx *ctx, int32_t *out, const uint8_t *pix, int W, int H, int C, int n);   // C = 3: YCoCg-R fused too (image.h:52-65)
+// lift.hip: asks for the scratch planes every lifting call of a W*H transform over nplanes planes asks for
+int dwtx_lift_scratch(dwtx_ctx *ctx, int W, int H, int nplanes);
 struct dwtx_p16;
 int dwtx_inv_pixels8(dwtx_ctx *ctx, uint8_t *pix, size_t image_stride, const int32_t *in, int W, int H, int C, int n, const dwtx_p16 *p16 = nullptr);   // C = 3: image.h:39-50 fused too
 
@@ -225,9 +226,9 @@ template <class G> int dwtx_fill_geom(dwtx_ctx *ctx, int W, int H, int C, G &g, 
 // squares need no linearised copy — the entropy stage reads (pack.hip) / writes (unpack.hip) them in the pyramid itself;
 // only the blocks the ring's edges cut (image border, LL quadrant) still go through `lin`.
 unsigned dwtx_square_levels(int W, int H);
-// the up to `max_levels` finest ring levels that may live in 16-bit planes: whole squares read / written in place (in
-// sq_levels) and transformed by the 16-byte-per-lane lifting kernels; 0 if the finest one does not qualify
-unsigned dwtx_levels16(int W, int H, unsigned sq_levels, int max_levels);
+// lift.hip: the finest ring levels that may live in 16-bit planes: whole squares read / written in place (in sq_levels)
+// and transformed by the 16-byte-per-lane lifting kernels, as many as those allow; 0 if the finest one does not qualify
+unsigned dwtx_levels16(int W, int H, unsigned sq_levels);
 int dwtx_linearization_ex(dwtx_ctx *ctx, int32_t *lin, const int32_t *pyr, int W, int H, int nplanes, unsigned skip_levels,
 	dwtx_p16 p16 = dwtx_p16{ nullptr, 0u });
 int dwtx_reconstruction_ex(dwtx_ctx *ctx, int32_t *pyr, const int32_t *lin, const int *dev_missing, int levels_out, int W, int H,

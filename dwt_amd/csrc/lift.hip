@@ -2284,20 +2284,43 @@ __global__ __launch_bounds__(256) void k_synth(uint8_t *__restrict__ pix, int W,
 	}
 }
 
-// transform steps of a W*H plane, fine to coarse: sizes[t] -> sizes[t+1]
-// (encode.c:24-29: recurse while both halves are >= N0; the first step always runs)
-int lift_steps(int W, int H, int *ws, int *hs)
+// The steps of a W*H transform, fine to coarse: step t takes the ws[t] x hs[t] plane to its ws[t+1] x hs[t+1] LL band and
+// three detail bands (encode.c:24-29: recurse while both halves are >= N0; the first step always runs).  The steps from
+// tail_from on run in one launch of the LDS tail kernel.  The LL bands between the finest step and the pyramid live in two
+// scratch planes: level1 holds the ws[1] x hs[1] band of every plane, small the bands from ws[2] x hs[2] down.
+struct LiftLayout {
+	int T, tail_from;
+	int ws[DWTX_MAX_LEVELS + 2], hs[DWTX_MAX_LEVELS + 2];
+	int *level1, *small;   // null where no step needs them
+};
+
+// ctx null: the sizes only
+int lift_layout(dwtx_ctx *ctx, int W, int H, int nplanes, LiftLayout &L)
 {
 	int n = 0;
-	ws[0] = W;
-	hs[0] = H;
+	L.ws[0] = W;
+	L.hs[0] = H;
 	do {
-		ws[n + 1] = (ws[n] + 1) >> 1;
-		hs[n + 1] = (hs[n] + 1) >> 1;
+		L.ws[n + 1] = (L.ws[n] + 1) >> 1;
+		L.hs[n + 1] = (L.hs[n] + 1) >> 1;
 		++n;
-	} while (n < DWTX_MAX_LEVELS && ws[n] >= DWTX_MIN_LEN && hs[n] >= DWTX_MIN_LEN);
-	return n;
+	} while (n < DWTX_MAX_LEVELS && L.ws[n] >= DWTX_MIN_LEN && L.hs[n] >= DWTX_MIN_LEN);
+	L.T = n;
+	int t = 0;
+	while (t < n && (L.ws[t] > TAIL_MAX || L.hs[t] > TAIL_MAX))
+		++t;
+	L.tail_from = t;
+	L.level1 = L.small = nullptr;
+	if (ctx && n > 1 && !(L.level1 = (int *)dwtx_scratch(ctx, SLOT_LIFT_A, sizeof(int) * (size_t)L.ws[1] * L.hs[1] * nplanes)))
+		return DWTX_ERR_NOMEM;
+	if (ctx && n > 2 && !(L.small = (int *)dwtx_scratch(ctx, SLOT_LIFT_B, sizeof(int) * (size_t)L.ws[2] * L.hs[2] * nplanes)))
+		return DWTX_ERR_NOMEM;
+	return DWTX_OK;
 }
+
+// 16-bit detail bands (dwtx_p16) come from the wide forward kernel reading 8-bit pixels, on at most this many of the
+// finest levels: the magnitude bound of k_fwd_level_w
+constexpr int LEVELS16_MAX = 5;
 
 } // namespace
 
@@ -2339,16 +2362,54 @@ extern "C" int dwtx_pixels_from_planes(dwtx_ctx *ctx, uint8_t *pix, const int32_
 
 static bool aligned_to(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
-// fewer rows per wave on small levels so that a few thousand waves are in flight
+// Fewer rows per wave on small levels so that a few thousand waves are in flight: `start` halved, not below `floor`,
+// while `strips` columns of waves (all planes) over `rows` rows make fewer than 4096
+static int fill_chip(int start, int floor, long strips, int rows)
+{
+	int r = start;
+	while (r > floor && strips * dwtx_cdiv(rows, r) < 4096)
+		r >>= 1;
+	return r;
+}
+
+// row pairs per wave of the one-level kernels (their waves are counted on h2 rounded up to whole strips of the start)
 static int pick_rpw(int strips_x, int h2, int nplanes)
 {
-	long waves32 = (long)strips_x * dwtx_cdiv(h2, MAX_ROWS_PER_WAVE) * nplanes;
-	int rpw = MAX_ROWS_PER_WAVE;
-	while (rpw > 4 && waves32 < 4096) {
-		rpw >>= 1;
-		waves32 <<= 1;
+	return fill_chip(MAX_ROWS_PER_WAVE, 4, (long)strips_x * nplanes, dwtx_cdiv(h2, MAX_ROWS_PER_WAVE) * MAX_ROWS_PER_WAVE);
+}
+
+// the LDS tail's steps tail_from .. T-1 of a pyramid; the caller adds the plane it reads (forward) or writes (inverse)
+static TailArgs tail_args(const LiftLayout &L, int *pyr)
+{
+	TailArgs ta{};
+	ta.pyr = pyr;
+	ta.pyr_ps = (long)L.ws[0] * L.hs[0];
+	ta.ppitch = L.ws[0];
+	ta.nsteps = L.T - L.tail_from;
+	for (int k = 0; k <= ta.nsteps; ++k) {
+		ta.ws[k] = L.ws[L.tail_from + k];
+		ta.hs[k] = L.hs[L.tail_from + k];
 	}
-	return rpw;
+	return ta;
+}
+
+using WideKernel = void (*)(LevelArgsW);
+
+// channels8: the step reads 8-bit pixels (1 gray, 3 RGB); else int32 planes, or src16 the 16-bit bands of the level before
+static WideKernel fwd_wide_kernel(bool hist, int channels8, bool src16)
+{
+	if (hist) {
+		if (channels8 == 3)
+			return k_fwd_pixels_w<Rgb8, true>;
+		if (channels8)
+			return k_fwd_pixels_w<uint8_t, true>;
+		return src16 ? k_fwd_level_w<true, true> : k_fwd_level_w<true, false>;
+	}
+	if (channels8 == 3)
+		return k_fwd_pixels_w<Rgb8, false>;
+	if (channels8)
+		return k_fwd_pixels_w<uint8_t, false>;
+	return src16 ? k_fwd_level_w<false, true> : k_fwd_level_w<false, false>;
 }
 
 // in8 != nullptr: the source is 8-bit pixels, gray (in8_channels 1: plane p = image p) or interleaved RGB
@@ -2361,19 +2422,10 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 	if (!ctx || !out || (!in && !in8) || W < 2 || H < 2 || nplanes < 1 || nplanes > 65535)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
-	int ws[DWTX_MAX_LEVELS + 2], hs[DWTX_MAX_LEVELS + 2];
-	const int T = lift_steps(W, H, ws, hs);
-	int *tmp[2] = { nullptr, nullptr };
-	if (T > 1) {
-		tmp[0] = (int *)dwtx_scratch(ctx, SLOT_LIFT_A, sizeof(int) * (size_t)ws[1] * hs[1] * nplanes);
-		if (!tmp[0])
-			return DWTX_ERR_NOMEM;
-	}
-	if (T > 2) {
-		tmp[1] = (int *)dwtx_scratch(ctx, SLOT_LIFT_B, sizeof(int) * (size_t)ws[2] * hs[2] * nplanes);
-		if (!tmp[1])
-			return DWTX_ERR_NOMEM;
-	}
+	LiftLayout L;
+	if (const int rc = lift_layout(ctx, W, H, nplanes, L))
+		return rc;
+	const int T = L.T, tail_from = L.tail_from, *ws = L.ws, *hs = L.hs;
 	const long full_ps = (long)W * H;
 	// histograms ride along from the finest level down for as long as the levels allow it (the wide kernel, blocks
 	// that the 16-lane rows cover exactly): pack.hip's k_hist counts the tiles of the levels below
@@ -2383,14 +2435,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 		if (hist_on && (dwtx_geometry(&gg, W, H) || gg.levels != T))
 			hist_on = false;
 	}
-	int tail_from = T;   // first step that runs inside the LDS tail kernel
-	for (int t = 0; t < T; ++t)
-		if (ws[t] <= TAIL_MAX && hs[t] <= TAIL_MAX) {
-			tail_from = t;
-			break;
-		}
-	// the LL band ping-pongs between the two scratch planes (tmp[0] holds up to ws[1]*hs[1], tmp[1]
-	// up to ws[2]*hs[2]); the last level writes it into the pyramid itself
+	// the LL band ping-pongs between the two scratch planes; the last level writes it into the pyramid itself
 	const int *src = in;
 	long src_ps = full_ps;
 	int spitch = W;
@@ -2403,27 +2448,16 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 			pitch = W;
 			return;
 		}
-		p = src == tmp[0] ? tmp[1] : tmp[0];   // never the plane being read; from tmp[0] only bands <= ws[2]*hs[2] follow
+		p = src == L.level1 ? L.small : L.level1;   // never the plane being read; from level1 only bands <= ws[2]*hs[2] follow
 		ps = (long)ws[k] * hs[k];
 		pitch = ws[k];
 	};
 	for (int t = 0; t < T;) {
 		if (t == tail_from) {
-			TailArgs ta;
+			TailArgs ta = tail_args(L, out);
 			ta.src = src;
 			ta.src_ps = src_ps;
 			ta.spitch = spitch;
-			ta.dst = nullptr;
-			ta.dst_ps = 0;
-			ta.dpitch2 = 0;
-			ta.pyr = out;
-			ta.pyr_ps = full_ps;
-			ta.ppitch = W;
-			ta.nsteps = T - t;
-			for (int k = 0; k <= T - t; ++k) {
-				ta.ws[k] = ws[t + k];
-				ta.hs[k] = hs[t + k];
-			}
 			hipLaunchKernelGGL(k_fwd_tail, dim3(nplanes), dim3(TAIL_THREADS), 0, ctx->stream, ta);
 			DWTX_LAUNCH_CHECK();
 			break;
@@ -2431,7 +2465,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 		// two levels in one pass where the shapes allow it (k_fwd2_level_w): plain int32 planes, no histograms
 		if (!in8 && !p16.planes && !hist_on && !ctx->opt[DWTX_OPT_NO_FUSED_LEVELS] && t + 1 < tail_from && t + 2 <= T &&
 			ws[t] % 4 == 0 && hs[t] % 4 == 0 && spitch % 4 == 0 && src_ps % 4 == 0 && aligned_to(src, 16) && W % 2 == 0 && aligned_to(out, 8)) {
-			Level2Args f;
+			Level2Args f{};
 			f.src = src;
 			f.src_ps = src_ps;
 			f.spitch = spitch;
@@ -2443,9 +2477,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 			f.h = hs[t];
 			f.nquads = ws[t] / 4;
 			const int strips = dwtx_cdiv(f.nquads, F2_OWN), h4 = hs[t] / 4;
-			f.mpw = F2_MPW;
-			while (f.mpw > 2 && (long)strips * dwtx_cdiv(h4, f.mpw) * nplanes < 4096)
-				f.mpw >>= 1;
+			f.mpw = fill_chip(F2_MPW, 2, (long)strips * nplanes, h4);
 			hipLaunchKernelGGL(k_fwd2_level_w, dim3(dwtx_cdiv(strips, WAVES), dwtx_cdiv(h4, f.mpw), nplanes), dim3(64 * WAVES), 0, ctx->stream, f);
 			DWTX_LAUNCH_CHECK();
 			src = f.ll2;
@@ -2454,30 +2486,31 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 			t += 2;
 			continue;
 		}
-		LevelArgs a;
+		LevelArgs a{};
 		a.w = ws[t];
 		a.h = hs[t];
 		a.w2 = ws[t + 1];
 		a.h2 = hs[t + 1];
 		const bool bytes_in = in8 && t == 0;
-		a.src = bytes_in ? nullptr : src;
-		a.src8 = bytes_in ? in8 : nullptr;
-		a.dst8 = nullptr;
-		a.src_ps = bytes_in ? (long)in8_channels * full_ps : src_ps;
-		a.spitch = bytes_in ? in8_channels * W : spitch;
+		if (bytes_in) {
+			a.src8 = in8;
+			a.src_ps = (long)in8_channels * full_ps;
+			a.spitch = in8_channels * W;
+		} else {
+			a.src = src;
+			a.src_ps = src_ps;
+			a.spitch = spitch;
+		}
 		ll_dest(t + 1, a.ll, a.ll_ps, a.llpitch);
 		a.det = out;
 		a.det_ps = full_ps;
 		a.dpitch = W;
-		a.det16 = nullptr;
-		a.src16 = nullptr;
-		a.ll16 = nullptr;
 		// 16-bit bands (dwtx_p16): the levels in the mask write their details there; between two such levels the LL
 		// band travels as 16-bit values too (in the scratch planes, which are sized for int32).  Only from 8-bit pixels:
 		// that is what bounds the magnitudes (see k_fwd_level_w).
-		auto in_mask = [&](int step) { return p16.planes && step < T && step < tail_from && ((p16.levels >> (T - 1 - step)) & 1u); };
+		auto in_mask = [&](int step) { return p16.planes && step < tail_from && ((p16.levels >> (T - 1 - step)) & 1u); };
 		if (in_mask(t)) {
-			if (!in8 || (t == 0) != bytes_in || t > 4 || (t > 0 && !in_mask(t - 1)) || !aligned_to(p16.planes, 16))
+			if (!in8 || t >= LEVELS16_MAX || (t > 0 && !in_mask(t - 1)) || !aligned_to(p16.planes, 16))
 				return DWTX_ERR_ARG;
 			a.det16 = p16.planes;
 			if (t > 0)
@@ -2496,45 +2529,25 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 		// transform — and pays for the histogram in full: 3.2 -> 4.7 ms per 256 frames of 1080p against the 1.4 ms k_hist takes)
 		const bool hist_here = hist_on && wide && a.w2 % 32 == 0 && sink->tiles.nbs[level] > 0;
 		if (wide) {
-			LevelArgsW A;
+			LevelArgsW A{};
 			A.nquads = a.w / 4;
-			a.rpw = pick_rpw(dwtx_cdiv(A.nquads, 64), a.h2, nplanes);
 			const int strips = dwtx_cdiv(A.nquads, 64);
+			a.rpw = pick_rpw(strips, a.h2, nplanes);
 			A.wx_log2 = strips >= 4 ? 2 : strips >= 2 ? 1 : 0;
-			const int sx = dwtx_cdiv(strips, 1 << A.wx_log2);
 			A.a = a;
-			A.hist = HistArgs{ nullptr, nullptr, nullptr, 0, 0, 0 };
-			dim3 grid(sx, dwtx_cdiv(a.h2, (WAVES >> A.wx_log2) * a.rpw), nplanes);
-			dim3 rgb_grid(sx * 3, grid.y, nplanes / 3);   // the three channels of a strip side by side (xcd_strip_rgb)
 			if (hist_here) {
-				A.hist.cum32 = sink->cum32;
-				A.hist.tile_mx = sink->tile_mx;
-				A.hist.xy2tile = sink->tiles.xy2tile + sink->tiles.xy_first[level];
-				A.hist.NT = sink->NT;
-				A.hist.NTP = sink->NTP;
-				A.hist.nbs = sink->tiles.nbs[level];
+				A.hist = HistArgs{ sink->cum32, sink->tile_mx, sink->tiles.xy2tile + sink->tiles.xy_first[level], sink->NT, sink->NTP,
+					sink->tiles.nbs[level] };
 				*hist_levels |= 1u << level;
-				if (bytes_in && in8_channels == 3)
-					hipLaunchKernelGGL((k_fwd_pixels_w<Rgb8, true>), rgb_grid, dim3(64 * WAVES), 0, ctx->stream, A);
-				else if (bytes_in)
-					hipLaunchKernelGGL((k_fwd_pixels_w<uint8_t, true>), grid, dim3(64 * WAVES), 0, ctx->stream, A);
-				else if (a.src16)
-					hipLaunchKernelGGL((k_fwd_level_w<true, true>), grid, dim3(64 * WAVES), 0, ctx->stream, A);
-				else
-					hipLaunchKernelGGL((k_fwd_level_w<true, false>), grid, dim3(64 * WAVES), 0, ctx->stream, A);
-			} else if (bytes_in && in8_channels == 3)
-				hipLaunchKernelGGL((k_fwd_pixels_w<Rgb8, false>), rgb_grid, dim3(64 * WAVES), 0, ctx->stream, A);
-			else if (bytes_in)
-				hipLaunchKernelGGL((k_fwd_pixels_w<uint8_t, false>), grid, dim3(64 * WAVES), 0, ctx->stream, A);
-			else if (a.src16)
-				hipLaunchKernelGGL((k_fwd_level_w<false, true>), grid, dim3(64 * WAVES), 0, ctx->stream, A);
-			else
-				hipLaunchKernelGGL((k_fwd_level_w<false, false>), grid, dim3(64 * WAVES), 0, ctx->stream, A);
+			}
+			const int ch = bytes_in ? in8_channels : 0;
+			const int sx = dwtx_cdiv(strips, 1 << A.wx_log2), gy = dwtx_cdiv(a.h2, (WAVES >> A.wx_log2) * a.rpw);
+			const dim3 grid = ch == 3 ? dim3(sx * 3, gy, nplanes / 3) : dim3(sx, gy, nplanes);   // (RGB: the three channels of a strip side by side, xcd_strip_rgb)
+			hipLaunchKernelGGL(fwd_wide_kernel(hist_here, ch, a.src16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {
 			const int sx = dwtx_cdiv(a.w2, 64);
 			a.rpw = pick_rpw(sx, a.h2, nplanes);
-			dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), nplanes);
-			hipLaunchKernelGGL(k_fwd_level, grid, dim3(64 * WAVES), 0, ctx->stream, a);
+			hipLaunchKernelGGL(k_fwd_level, dim3(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), nplanes), dim3(64 * WAVES), 0, ctx->stream, a);
 		}
 		DWTX_LAUNCH_CHECK();
 		src = a.ll;
@@ -2558,6 +2571,26 @@ bool dwtx_gray8_ok(int W, int H, const void *pix, size_t image_stride)
 	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && image_stride % 4 == 0 && aligned_to(pix, 4);
 }
 
+unsigned dwtx_levels16(int W, int H, unsigned sq_levels)
+{
+	LiftLayout L;
+	lift_layout(nullptr, W, H, 0, L);
+	unsigned mask = 0u;
+	for (int t = 0; t < LEVELS16_MAX && t < L.tail_from; ++t) {
+		const int l = L.T - 1 - t;   // ring level of step t
+		if (!((sq_levels >> l) & 1u) || L.ws[t] % 4 != 0)
+			break;
+		mask |= 1u << l;
+	}
+	return mask;
+}
+
+int dwtx_lift_scratch(dwtx_ctx *ctx, int W, int H, int nplanes)
+{
+	LiftLayout L;
+	return lift_layout(ctx, W, H, nplanes, L);
+}
+
 int dwtx_fwd_pixels8_hist(dwtx_ctx *ctx, int32_t *out, const uint8_t *pix, int W, int H, int C, int n, const dwtx_hist_sink *sink, unsigned *hist_levels,
 	dwtx_p16 p16)
 {
@@ -2574,11 +2607,26 @@ int dwtx_transformation_fwd_hist(dwtx_ctx *ctx, int32_t *out, const int32_t *in,
 	return lift_fwd(ctx, out, in, nullptr, 0, W, H, nplanes, sink, hist_levels);
 }
 
-int dwtx_fwd_pixels8(dwtx_ctx *ctx, int32_t *out, const uint8_t *pix, int W, int H, int C, int n)
+using Inv2Kernel = void (*)(Inv2Args);
+
+// channels8: the pair writes 8-bit pixels (1 gray, 3 RGB), which it does from 16-bit bands only
+static Inv2Kernel inv2_kernel(int channels8, bool det16)
 {
-	if (!pix || W < 2 || H < 2 || (C != 1 && C != 3) || !dwtx_gray8_ok(W, H, pix, (size_t)W * H * C))
-		return DWTX_ERR_ARG;
-	return lift_fwd(ctx, out, nullptr, pix, C, W, H, n * C);
+	if (channels8 == 3)
+		return k_inv2_level_w_rgb<true>;
+	if (channels8)
+		return k_inv2_level_w<uint8_t, true>;
+	return det16 ? k_inv2_level_w<int, true> : k_inv2_level_w<int, false>;
+}
+
+// channels8: the step writes 8-bit pixels (1 gray, 3 RGB)
+static WideKernel inv_wide_kernel(int channels8, bool det16)
+{
+	if (channels8 == 3)
+		return det16 ? k_inv_level_w_rgb<true> : k_inv_level_w_rgb<false>;
+	if (channels8)
+		return det16 ? k_inv_level_w<uint8_t, true> : k_inv_level_w<uint8_t, false>;
+	return det16 ? k_inv_level_w<int, true> : k_inv_level_w<int, false>;
 }
 
 // out8 != nullptr: the finest level writes clamped 8-bit pixels (gray, or interleaved RGB after the
@@ -2589,39 +2637,25 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 	if (!ctx || (!out && !out8) || !in || W < 2 || H < 2 || nplanes < 1 || nplanes > 65535)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
-	int ws[DWTX_MAX_LEVELS + 2], hs[DWTX_MAX_LEVELS + 2];
-	const int T = lift_steps(W, H, ws, hs);
-	int *tmp[2] = { nullptr, nullptr };
-	if (T > 1) {
-		tmp[1] = (int *)dwtx_scratch(ctx, SLOT_LIFT_A, sizeof(int) * (size_t)ws[1] * hs[1] * nplanes);
-		if (!tmp[1])
-			return DWTX_ERR_NOMEM;
-	}
-	if (T > 2) {
-		tmp[0] = (int *)dwtx_scratch(ctx, SLOT_LIFT_B, sizeof(int) * (size_t)ws[2] * hs[2] * nplanes);
-		if (!tmp[0])
-			return DWTX_ERR_NOMEM;
-	}
+	LiftLayout L;
+	if (const int rc = lift_layout(ctx, W, H, nplanes, L))
+		return rc;
+	const int T = L.T, tail_from = L.tail_from, *ws = L.ws, *hs = L.hs;
 	const long full_ps = (long)W * H;
-	// The LL band the next step reads: the pyramid's root, then the output of the step before.  Intermediate planes live in
-	// two scratch planes — tmp[1] holds up to ws[1]*hs[1] samples, tmp[0] up to ws[2]*hs[2] — and a step never writes the
-	// plane it reads: the ws[k] x hs[k] plane goes to tmp[(k + flip) & 1].  One step at a time alternates by itself; a
-	// two-level step (k_inv2_level_w) reads plane k+2 and writes plane k, same parity, so it flips the assignment for
-	// everything after it — allowed only if all later planes still fit (fuse_ok looks ahead).
-	const int *cur = in;
-	long cur_ps = full_ps;
-	int cur_pitch = W;
-	int flip = 0;
-	auto plane_of = [&](int k, int fl) -> int * { return tmp[(k + fl) & 1]; };
-	auto fits = [&](int k, int fl) { return ((k + fl) & 1) == 1 || k >= 2; };   // (tmp[0] is the small one)
+	// Step t rebuilds plane t, ws[t] x hs[t], from plane t+1: plane T is the pyramid's root, plane 0 the output.  The planes in
+	// between live in the two scratch planes, and a step never writes the plane it reads: plane k goes to level1 if k + fl is
+	// odd, to small if it is even.  One step at a time alternates by itself; a two-level step (k_inv2_level_w) reads plane k+2
+	// and writes plane k, same parity, so it flips `fl` for everything after it — allowed only if all later planes still fit.
+	auto plane_of = [&](int k, int fl) { return (k + fl) & 1 ? L.level1 : L.small; };
+	auto fits = [&](int k, int fl) { return ((k + fl) & 1) == 1 || k >= 2; };   // (small holds the planes from 2 on)
 	// two levels per pass (k_inv2_level_w): int32 planes throughout, or — the codec's pipelines — both levels' detail bands as 16-bit values
 	// (dwtx_p16), the finest step then writing a gray picture's 8-bit pixels itself; an RGB picture's last step keeps its own kernel
 	const bool have16 = p16 && p16->planes;
 	const bool fusing = !ctx->opt[DWTX_OPT_NO_FUSED_LEVELS] && W % 4 == 0 && aligned_to(in, 8) && (out8 ? aligned_to(out8, 4) && out8_ps % 4 == 0 : aligned_to(out, 16)) &&
 		(!have16 || aligned_to(p16->planes, 4));
 	auto in16 = [&](int t) { return have16 && ((p16->levels >> (T - 1 - t)) & 1u) != 0; };   // step t's detail bands are 16-bit values
-	auto can_fuse = [&](int t) {
-		if (!fusing || t < 1 || ws[t - 1] % 4 != 0 || hs[t - 1] % 4 != 0 || in16(t) != in16(t - 1))
+	auto can_fuse = [&](int t) {   // (t == T - 1 reads the root LL in the pyramid itself: no pair there)
+		if (!fusing || t < 1 || t == T - 1 || ws[t - 1] % 4 != 0 || hs[t - 1] % 4 != 0 || in16(t) != in16(t - 1))
 			return false;
 		if (t - 1 == 0 && out8)   // (the 8-bit variants exist for 16-bit bands only: what the pipelines run; RGB: three planes per wave)
 			return in16(0) && (out8_channels == 1 || (out8_channels == 3 && nplanes % 3 == 0));
@@ -2629,69 +2663,65 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 	};
 	// Steps t .. 0 with the planes from here on assigned with `fl`: the most samples that can go through two-level steps (a pair is
 	// worth the plane it writes: fusing the two finest levels saves sixteen times what the pair below them saves), -1 if the planes
-	// do not fit.  At most 2^16 paths, a handful in practice.
-	auto best = [&](auto &&self, int t, int fl) -> long {
+	// do not fit, and whether step t starts a pair on that path (a pair wins ties).  At most 2^16 paths, a handful in practice.
+	struct Best {
+		long samples;
+		bool pair;
+	};
+	auto best = [&](auto &&self, int t, int fl) -> Best {
 		if (t < 0)
-			return 0;
-		long b = -1;
+			return { 0, false };
+		Best b = { -1, false };
 		if (can_fuse(t) && (t - 1 == 0 || fits(t - 1, fl ^ 1))) {
-			const long r = self(self, t - 2, fl ^ 1);
+			const long r = self(self, t - 2, fl ^ 1).samples;
 			if (r >= 0)
-				b = r + (long)ws[t - 1] * hs[t - 1];
+				b = { r + (long)ws[t - 1] * hs[t - 1], true };
 		}
 		if (t == 0 || fits(t, fl)) {
-			const long r = self(self, t - 1, fl);
-			if (r > b)
-				b = r;
+			const long r = self(self, t - 1, fl).samples;
+			if (r > b.samples)
+				b = { r, false };
 		}
 		return b;
 	};
-	// take the two-level step at t if no plan that takes one step here does better
-	auto fuse_ok = [&](int t) {
-		if (!can_fuse(t) || cur == in || !(t - 1 == 0 || fits(t - 1, flip ^ 1)))
-			return false;
-		const long with = best(best, t - 2, flip ^ 1);
-		if (with < 0)
-			return false;
-		const long without = (t == 0 || fits(t, flip)) ? best(best, t - 1, flip) : -1;
-		return with + (long)ws[t - 1] * hs[t - 1] >= without;
-	};
-	int tail_from = T;
-	for (int t = 0; t < T; ++t)
-		if (ws[t] <= TAIL_MAX && hs[t] <= TAIL_MAX) {
-			tail_from = t;
-			break;
-		}
-	if (tail_from < T) {
-		const int t = tail_from;
-		TailArgs ta;
-		ta.src = nullptr;
-		ta.src_ps = 0;
-		ta.spitch = 0;
-		if (t == 0 && out8)
+	// The plan, made before the first launch: pair[t], steps t and t-1 run as one two-level launch, and plane[k], the scratch plane
+	// that plane k goes to
+	bool pair[DWTX_MAX_LEVELS + 1] = {};
+	int *plane[DWTX_MAX_LEVELS + 2] = {};
+	if (tail_from > 0 && tail_from < T)
+		plane[tail_from] = plane_of(tail_from, 0);
+	for (int t = tail_from - 1, fl = 0; t >= 0; --t) {
+		if (can_fuse(t) && best(best, t, fl).pair) {   // (no search where no pair can start)
+			pair[t] = true;
+			fl ^= 1;
+			--t;
+		} else if (t > 0 && (!fits(t, fl) || plane_of(t, fl) == plane[t + 1])) {
+			dwtx_set_error("inverse transform: no scratch plane for step %d", t);
 			return DWTX_ERR_ARG;
-		ta.dst = t == 0 ? out : tmp[t & 1];
-		ta.dst_ps = t == 0 ? full_ps : (long)ws[t] * hs[t];
-		ta.dpitch2 = t == 0 ? W : ws[t];
+		}
+		if (t > 0)
+			plane[t] = plane_of(t, fl);
+	}
+	// the LL band the next launch reads: the pyramid's root, then the output of the launch before
+	const int *cur = in;
+	long cur_ps = full_ps;
+	int cur_pitch = W;
+	if (tail_from < T) {
+		if (tail_from == 0 && out8)
+			return DWTX_ERR_ARG;
+		TailArgs ta = tail_args(L, const_cast<int *>(in));
+		ta.dst = tail_from == 0 ? out : plane[tail_from];
+		ta.dst_ps = tail_from == 0 ? full_ps : (long)ws[tail_from] * hs[tail_from];
+		ta.dpitch2 = tail_from == 0 ? W : ws[tail_from];
+		hipLaunchKernelGGL(k_inv_tail, dim3(nplanes), dim3(TAIL_THREADS), 0, ctx->stream, ta);
+		DWTX_LAUNCH_CHECK();
 		cur = ta.dst;
 		cur_ps = ta.dst_ps;
 		cur_pitch = ta.dpitch2;
-		ta.pyr = const_cast<int *>(in);
-		ta.pyr_ps = full_ps;
-		ta.ppitch = W;
-		ta.nsteps = T - t;
-		for (int k = 0; k <= T - t; ++k) {
-			ta.ws[k] = ws[t + k];
-			ta.hs[k] = hs[t + k];
-		}
-		hipLaunchKernelGGL(k_inv_tail, dim3(nplanes), dim3(TAIL_THREADS), 0, ctx->stream, ta);
-		DWTX_LAUNCH_CHECK();
 	}
-	// step t rebuilds the ws[t]*hs[t] plane; its output goes to tmp[t&1] (t odd: the big one)
 	for (int t = tail_from - 1; t >= 0; --t) {
-		// two levels in one pass (k_inv2_level_w): steps t and t-1 — plain int32 planes, shapes whose two levels have whole row pairs
-		if (fuse_ok(t)) {
-			Inv2Args f;
+		if (pair[t]) {   // steps t and t-1: shapes whose two levels have whole row pairs
+			Inv2Args f{};
 			f.ll2 = cur;           // the LL band step t reads: ws[t+1] x hs[t+1]
 			f.ll2_ps = cur_ps;
 			f.ll2pitch = cur_pitch;
@@ -2699,48 +2729,36 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 			f.det_ps = full_ps;
 			f.dpitch = W;
 			f.det16 = in16(t) ? p16->planes : nullptr;
-			f.dst8 = nullptr;
 			if (t - 1 == 0 && out8) {
-				f.dst = nullptr;
 				f.dst8 = out8;
 				f.dst_ps = out8_ps;
-				f.opitch = W;
+				f.opitch = out8_channels * W;
 			} else if (t - 1 == 0) {
 				f.dst = out;
 				f.dst_ps = full_ps;
 				f.opitch = W;
 			} else {
-				f.dst = plane_of(t - 1, flip ^ 1);
+				f.dst = plane[t - 1];
 				f.dst_ps = (long)ws[t - 1] * hs[t - 1];
 				f.opitch = ws[t - 1];
 			}
 			f.w = ws[t - 1];
 			f.h = hs[t - 1];
 			f.nquads = f.w / 4;
-			{
-				const int strips = dwtx_cdiv(f.nquads, V2_OWN), h4 = f.h / 4;
-				f.mpw = F2_MPW;
-				while (f.mpw > 2 && (long)strips * dwtx_cdiv(h4, f.mpw) * nplanes < 4096)
-					f.mpw >>= 1;
-				if (f.dst8 && out8_channels == 3) {
-					f.opitch = 3 * W;
-					hipLaunchKernelGGL(k_inv2_level_w_rgb<true>, dim3(dwtx_cdiv(strips, WAVES), dwtx_cdiv(h4, f.mpw), nplanes / 3), dim3(64 * WAVES), 0, ctx->stream, f);
-				} else if (f.dst8)
-					hipLaunchKernelGGL((k_inv2_level_w<uint8_t, true>), dim3(dwtx_cdiv(strips, WAVES), dwtx_cdiv(h4, f.mpw), nplanes), dim3(64 * WAVES), 0, ctx->stream, f);
-				else if (f.det16)
-					hipLaunchKernelGGL((k_inv2_level_w<int, true>), dim3(strips, dwtx_cdiv(h4, WAVES * f.mpw), nplanes), dim3(64 * WAVES), 0, ctx->stream, f);
-				else
-					hipLaunchKernelGGL((k_inv2_level_w<int, false>), dim3(strips, dwtx_cdiv(h4, WAVES * f.mpw), nplanes), dim3(64 * WAVES), 0, ctx->stream, f);
-				DWTX_LAUNCH_CHECK();
-				cur = f.dst;
-				cur_ps = f.dst_ps;
-				cur_pitch = f.opitch;
-				flip ^= 1;
-				--t;   // (the loop's own step takes the second)
-				continue;
-			}
+			const int strips = dwtx_cdiv(f.nquads, V2_OWN), h4 = f.h / 4;
+			f.mpw = fill_chip(F2_MPW, 2, (long)strips * nplanes, h4);
+			// (the 8-bit kernels put a block's waves side by side; RGB: three planes per wave)
+			const int ch = f.dst8 ? out8_channels : 0;
+			const dim3 grid = ch ? dim3(dwtx_cdiv(strips, WAVES), dwtx_cdiv(h4, f.mpw), nplanes / ch) : dim3(strips, dwtx_cdiv(h4, WAVES * f.mpw), nplanes);
+			hipLaunchKernelGGL(inv2_kernel(ch, f.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, f);
+			DWTX_LAUNCH_CHECK();
+			cur = f.dst;
+			cur_ps = f.dst_ps;
+			cur_pitch = f.opitch;
+			--t;   // (the loop's own step takes the second)
+			continue;
 		}
-		LevelArgs a;
+		LevelArgs a{};
 		a.w = ws[t];
 		a.h = hs[t];
 		a.w2 = ws[t + 1];
@@ -2749,10 +2767,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 		a.src_ps = cur_ps;
 		a.spitch = cur_pitch;
 		const bool bytes_out = out8 && t == 0;
-		a.src8 = nullptr;
-		a.dst8 = nullptr;
 		if (bytes_out) {
-			a.ll = nullptr;
 			a.dst8 = out8;
 			a.ll_ps = out8_ps;
 			a.llpitch = out8_channels * W;
@@ -2761,19 +2776,14 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 			a.ll_ps = full_ps;
 			a.llpitch = W;
 		} else {
-			a.ll = plane_of(t, flip);
-			if (!fits(t, flip) || a.ll == cur) {   // (fuse_ok's look-ahead keeps this from happening)
-				dwtx_set_error("inverse transform: no scratch plane for step %d", t);
-				return DWTX_ERR_ARG;
-			}
+			a.ll = plane[t];
 			a.ll_ps = (long)a.w * a.h;
 			a.llpitch = a.w;
 		}
 		a.det = const_cast<int *>(in);
 		a.det_ps = full_ps;
 		a.dpitch = W;
-		a.det16 = nullptr;
-		if (p16 && p16->planes && ((p16->levels >> (T - 1 - t)) & 1u)) {   // this level's detail bands are 16-bit values
+		if (in16(t)) {
 			if (!out8 || !aligned_to(p16->planes, 4))
 				return DWTX_ERR_ARG;
 			a.det16 = p16->planes;
@@ -2785,33 +2795,18 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 		if ((bytes_out || a.det16) && !wide)
 			return DWTX_ERR_ARG;
 		if (wide) {
-			LevelArgsW A;
+			LevelArgsW A{};
 			A.nquads = a.w / 4;
-			const int per_wave = bytes_out && out8_channels == 3 ? INV_QUADS : 64;   // (the RGB kernel's waves overlap by a lane on each side)
-			a.rpw = pick_rpw(dwtx_cdiv(A.nquads, per_wave), a.h2, nplanes);
-			const int sx = dwtx_cdiv(A.nquads, per_wave);
-			A.wx_log2 = 0;
+			const int ch = bytes_out ? out8_channels : 0;
+			const int sx = dwtx_cdiv(A.nquads, ch == 3 ? INV_QUADS : 64);   // (the RGB kernel's waves overlap by a lane on each side)
+			a.rpw = pick_rpw(sx, a.h2, nplanes);
 			A.a = a;
-			dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), nplanes);
-			if (bytes_out && out8_channels == 3) {
-				grid.z = nplanes / 3;
-				if (a.det16)
-					hipLaunchKernelGGL(k_inv_level_w_rgb<true>, grid, dim3(64 * WAVES), 0, ctx->stream, A);
-				else
-					hipLaunchKernelGGL(k_inv_level_w_rgb<false>, grid, dim3(64 * WAVES), 0, ctx->stream, A);
-			} else if (bytes_out && a.det16)
-				hipLaunchKernelGGL((k_inv_level_w<uint8_t, true>), grid, dim3(64 * WAVES), 0, ctx->stream, A);
-			else if (bytes_out)
-				hipLaunchKernelGGL((k_inv_level_w<uint8_t, false>), grid, dim3(64 * WAVES), 0, ctx->stream, A);
-			else if (a.det16)
-				hipLaunchKernelGGL((k_inv_level_w<int, true>), grid, dim3(64 * WAVES), 0, ctx->stream, A);
-			else
-				hipLaunchKernelGGL((k_inv_level_w<int, false>), grid, dim3(64 * WAVES), 0, ctx->stream, A);
+			const dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), ch == 3 ? nplanes / 3 : nplanes);
+			hipLaunchKernelGGL(inv_wide_kernel(ch, a.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {
 			const int sx = dwtx_cdiv(a.w2, INV_PAIRS);
 			a.rpw = pick_rpw(sx, a.h2, nplanes);
-			dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), nplanes);
-			hipLaunchKernelGGL(k_inv_level, grid, dim3(64 * WAVES), 0, ctx->stream, a);
+			hipLaunchKernelGGL(k_inv_level, dim3(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), nplanes), dim3(64 * WAVES), 0, ctx->stream, a);
 		}
 		DWTX_LAUNCH_CHECK();
 		cur = a.ll;   // (null after the last step, which may have written 8-bit pixels: nothing reads it)

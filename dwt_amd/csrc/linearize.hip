@@ -545,22 +545,6 @@ unsigned dwtx_square_levels(int W, int H)
 	return mask;
 }
 
-unsigned dwtx_levels16(int W, int H, unsigned sq_levels, int max_levels)
-{
-	dwtx_geom g;
-	if (dwtx_geometry(&g, W, H) || g.levels < 1)
-		return 0u;
-	unsigned mask = 0u;
-	for (int t = 0; t < max_levels && t < g.levels; ++t) {
-		const int l = g.levels - 1 - t;           // ring level of lifting step t
-		const int w = g.widths[l + 1], h = g.heights[l + 1];   // what that step transforms
-		if (!((sq_levels >> l) & 1u) || w % 4 != 0 || (w <= 64 && h <= 64))   // (lift.hip: wide kernel, not the LDS tail)
-			break;
-		mask |= 1u << l;
-	}
-	return mask;
-}
-
 extern "C" int dwtx_linearization(dwtx_ctx *ctx, int32_t *lin, const int32_t *pyr, int W, int H, int nplanes)
 {
 	return dwtx_linearization_ex(ctx, lin, pyr, W, H, nplanes, 0u);
