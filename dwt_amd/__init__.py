@@ -12,7 +12,7 @@ import ctypes as C
 from . import _lib
 from ._lib import Geom, Stats, StreamInfo, DecodeInfo, Index, SegIndex, INDEX_MAGIC, INDEX_MAX_SEGS, LIB_PATH  # noqa: F401
 
-__all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "Geom", "Stats"]
+__all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "Geom", "Stats"]
 
 
 class DwtxError(RuntimeError):
@@ -43,6 +43,14 @@ def geometry(W, H):
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr())
+
+
+def index_from_row(row):
+    """One row of the device tensor of Context.set_encode_index(device=True) (uint8, sizeof(Index) bytes; a torch tensor
+    or anything bytes() takes) -> Index."""
+    if hasattr(row, "cpu"):
+        row = row.cpu().numpy().tobytes()
+    return Index.from_buffer_copy(bytes(row))
 
 
 class Context:
@@ -88,6 +96,24 @@ class Context:
         self._index = (offered, out)   # the library keeps the pointers
         _check(self.lib.dwtx_ctx_set_index(self.h, C.cast(offered, C.c_void_p) if offered is not None else None,
                                            C.cast(out, C.c_void_p) if out is not None else None), "dwtx_ctx_set_index")
+        return out
+
+    def set_encode_index(self, wanted=0, device=False):
+        """Sidecar indices from the encode calls that follow (dwtx_ctx_set_encode_index): entry i receives the index of
+        image i of a call.  device=False: a ctypes array of `wanted` Index entries, for encode() (host buffers);
+        device=True: a uint8 device tensor [wanted, sizeof(Index)], for encode_planes() / encode_device(), written on the
+        context's stream like the info records (index_from_row() reads a downloaded row).  Entries are not cleared: an
+        encode writes an entry's header and seg[:nsegs].  set_encode_index() ends it."""
+        if not wanted:
+            out, ptr = None, None
+        elif device:
+            out = self.torch.empty((wanted, C.sizeof(Index)), dtype=self.torch.uint8, device=self.device)
+            ptr = _ptr(out)
+        else:
+            out = (Index * wanted)()
+            ptr = C.cast(out, C.c_void_p)
+        self._encode_index = out   # the library keeps the pointer
+        _check(self.lib.dwtx_ctx_set_encode_index(self.h, ptr), "dwtx_ctx_set_encode_index")
         return out
 
     def sync(self):

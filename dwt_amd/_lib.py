@@ -80,6 +80,7 @@ SYMBOLS = {
     "dwtx_last_error": (C.c_char_p, []),
     "dwtx_sync": (_i, [_vp]),
     "dwtx_ctx_set_index": (_i, [_vp, _vp, _vp]),
+    "dwtx_ctx_set_encode_index": (_i, [_vp, _vp]),
     "dwtx_stream": (_vp, [_vp]),
     "dwtx_ctx_set_option": (_i, [_vp, _i, C.c_long]),
     "dwtx_ctx_get_option": (C.c_long, [_vp, _i]),

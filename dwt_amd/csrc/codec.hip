@@ -19,7 +19,7 @@ extern "C" size_t dwtx_encode_bound(int W, int H, int C)
 // pixels (device) -> streams (device) for one part of a batch, on the part's context; `lifted` (optional) is recorded
 // once the part's transform and linearisation are queued
 static int encode_part(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int C, int n, long capacity,
-	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, hipEvent_t lifted)
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, hipEvent_t lifted, dwtx_index *dev_index)
 {
 	const size_t bytes = sizeof(int) * (size_t)W * H * C * n;
 	int *a = (int *)dwtx_scratch(ctx, SLOT_CD_A, bytes);
@@ -59,7 +59,7 @@ static int encode_part(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int 
 		return rc;
 	if (lifted)
 		DWTX_HIP(hipEventRecord(lifted, ctx->stream));
-	return dwtx_encode_planes_ex(ctx, a, b, sq, hist_levels, W, H, C, n, capacity, dev_out, out_stride, dev_info, fine16);   // encode.c:163-221
+	return dwtx_encode_planes_ex(ctx, a, b, sq, hist_levels, W, H, C, n, capacity, dev_out, out_stride, dev_info, fine16, dev_index);   // encode.c:163-221
 }
 
 // The pipelines' transforms on their own (include/dwtx.h): what encode_part / dwtx_decode_device's `finish` run around the
@@ -112,8 +112,9 @@ extern "C" int dwtx_transformation_inv_pixels(dwtx_ctx *ctx, uint8_t *dev_pix, c
 // The transform is bound by memory, the entropy stage by vector-instruction issue: a batch runs as parts on streams of
 // their own, staggered so that part k's transform runs beside part k-1's entropy stage (the transforms follow one
 // another: each fills the memory system by itself).  The caller's stream waits for all parts.
-extern "C" int dwtx_encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int C, int n, long capacity,
-	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+// dev_index (device memory, or null): entry i receives the sidecar index of image i (dwtx_ctx_set_encode_index)
+static int encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int C, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, dwtx_index *dev_index)
 {
 	if (!ctx || !dev_pix || !dev_out || !dev_info || (C != 1 && C != 3) || n < 1)
 		return DWTX_ERR_ARG;
@@ -124,7 +125,7 @@ extern "C" int dwtx_encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, 
 	// 6.57 -> 6.72 and 16 frames 1.98 -> 2.17 the wrong way)
 	const int K = ctx->opt[DWTX_OPT_ONE_STREAM] || n < 32 * DWTX_ENC_PARTS ? 1 : DWTX_ENC_PARTS;
 	if (K == 1)
-		return encode_part(ctx, dev_pix, W, H, C, n, capacity, dev_out, out_stride, dev_info, nullptr);
+		return encode_part(ctx, dev_pix, W, H, C, n, capacity, dev_out, out_stride, dev_info, nullptr, dev_index);
 	dwtx_ctx *part[DWTX_ENC_PARTS];
 	int rc;
 	for (int k = 0; k < K; ++k)
@@ -145,7 +146,7 @@ extern "C" int dwtx_encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, 
 			break;
 		}
 		rc = encode_part(part[k], dev_pix + img_bytes * i0, W, H, C, cnt, capacity, dev_out + out_stride * (size_t)i0, out_stride,
-			dev_info + i0, lifted[k]);
+			dev_info + i0, lifted[k], dev_index ? dev_index + i0 : nullptr);
 		if (hipEventRecord(done[k], st) != hipSuccess && !rc)
 			rc = DWTX_ERR_DEVICE;
 		queued = k + 1;
@@ -154,6 +155,12 @@ extern "C" int dwtx_encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, 
 		if (hipStreamWaitEvent(ctx->stream, done[k], 0) != hipSuccess && !rc)
 			rc = DWTX_ERR_DEVICE;
 	return rc;
+}
+
+extern "C" int dwtx_encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int C, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	return encode_device(ctx, dev_pix, W, H, C, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
 }
 
 // streams (device) -> pixels (device).  Image i is written densely (ow*oh*C bytes)
@@ -363,10 +370,17 @@ extern "C" int dwtx_encode_images(dwtx_ctx *ctx, const uint8_t *pix, int W, int 
 	uint8_t *dpix = (uint8_t *)dwtx_scratch(ctx, SLOT_CD_IO, 2 * img_bytes * P);
 	uint8_t *dout = (uint8_t *)dwtx_scratch(ctx, SLOT_CD_IO2, 2 * out_stride * (size_t)P);
 	dwtx_stream_info *dinfo = (dwtx_stream_info *)dwtx_scratch(ctx, SLOT_CD_LENS, 2 * sizeof(dwtx_stream_info) * (size_t)P);
+	// sidecar indices (dwtx_ctx_set_encode_index; host memory here): a part's records are made on the device, their headers
+	// come over with the part's info records, and drain() fetches what each holds — header and seg[0 .. nsegs)
+	dwtx_index *hix = ctx->enc_index;
+	dwtx_index *dix = hix ? (dwtx_index *)dwtx_scratch(ctx, SLOT_CD_INDEX, 2 * sizeof(dwtx_index) * (size_t)P) : nullptr;
+	constexpr size_t ix_head = offsetof(dwtx_index, seg);
+	const size_t hinfo_bytes = 2 * sizeof(dwtx_stream_info) * (size_t)P;
 	dwtx_stream_info *hinfo = nullptr;   // page-locked: its copy must not block the host
-	if (hipHostMalloc((void **)&hinfo, 2 * sizeof(dwtx_stream_info) * (size_t)P, hipHostMallocDefault) != hipSuccess)
+	if (hipHostMalloc((void **)&hinfo, hinfo_bytes + (hix ? 2 * ix_head * (size_t)P : 0), hipHostMallocDefault) != hipSuccess)
 		hinfo = nullptr;
-	if (!dpix || !dout || !dinfo || !hinfo) {
+	char *hhead = (char *)hinfo + hinfo_bytes;   // [2][P] index headers
+	if (!dpix || !dout || !dinfo || !hinfo || (hix && !dix)) {
 		if (hinfo)
 			(void)hipHostFree(hinfo);
 		return DWTX_ERR_NOMEM;
@@ -396,6 +410,12 @@ extern "C" int dwtx_encode_images(dwtx_ctx *ctx, const uint8_t *pix, int W, int 
 			out_lens[i0 + i] = (size_t)hi[i].nbytes;
 			e = hipMemcpyAsync(out + out_stride * (i0 + i), dout + out_stride * ((size_t)slot * P + i), (size_t)hi[i].nbytes,
 				hipMemcpyDeviceToHost, cs);
+			if (hix) {
+				dwtx_index &X = hix[i0 + i];
+				memcpy(&X, hhead + ix_head * ((size_t)slot * P + i), ix_head);
+				if (e == hipSuccess && X.nsegs > 0)
+					e = hipMemcpyAsync(X.seg, dix[(size_t)slot * P + i].seg, sizeof(dwtx_seg_index) * (size_t)X.nsegs, hipMemcpyDeviceToHost, cs);
+			}
 			if (stats) {
 				dwtx_stats &st = stats[i0 + i];
 				st.meta_bits = (int)hi[i].meta_bits;                 // encode.c:175
@@ -426,12 +446,15 @@ extern "C" int dwtx_encode_images(dwtx_ctx *ctx, const uint8_t *pix, int W, int 
 			e = hipStreamWaitEvent(ms, ev_in[slot], 0);
 		if (e != hipSuccess)
 			break;
-		rc = dwtx_encode_device(ctx, dpix + (size_t)slot * P * img_bytes, W, H, C, cnt, capacity,
-			dout + out_stride * (size_t)slot * P, out_stride, dinfo + (size_t)slot * P);
+		rc = encode_device(ctx, dpix + (size_t)slot * P * img_bytes, W, H, C, cnt, capacity,
+			dout + out_stride * (size_t)slot * P, out_stride, dinfo + (size_t)slot * P, dix ? dix + (size_t)slot * P : nullptr);
 		if (rc)
 			break;
 		e = hipMemcpyAsync(hinfo + (size_t)slot * P, dinfo + (size_t)slot * P, sizeof(dwtx_stream_info) * (size_t)cnt,
 			hipMemcpyDeviceToHost, ms);
+		if (e == hipSuccess && dix)
+			e = hipMemcpy2DAsync(hhead + ix_head * (size_t)slot * P, ix_head, dix + (size_t)slot * P, sizeof(dwtx_index), ix_head, (size_t)cnt,
+				hipMemcpyDeviceToHost, ms);
 		if (e == hipSuccess)
 			e = hipEventRecord(ev_enc[slot], ms);
 		if (k >= 1 && e == hipSuccess)

@@ -110,6 +110,14 @@ extern "C" int dwtx_ctx_set_index(dwtx_ctx *c, const dwtx_index *in, dwtx_index 
 	return DWTX_OK;
 }
 
+extern "C" int dwtx_ctx_set_encode_index(dwtx_ctx *c, dwtx_index *out)
+{
+	if (!c)
+		return DWTX_ERR_ARG;
+	c->enc_index = out;
+	return DWTX_OK;
+}
+
 int dwtx_need_side_streams(dwtx_ctx *c, bool more)
 {
 	if (!c->have_aux) {

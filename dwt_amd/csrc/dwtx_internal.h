@@ -30,6 +30,7 @@ struct dwtx_ctx {
 	const dwtx_index *index_in;   // dwtx_ctx_set_index: sidecar indices offered to / asked from the decode calls
 	dwtx_index *index_out;
 	size_t index_base;            // entry of the current call's first image (the host pipeline decodes a batch in parts)
+	dwtx_index *enc_index;        // dwtx_ctx_set_encode_index: where the encode calls leave the sidecar indices of their streams
 	long opt[DWTX_OPT_COUNT];     // dwtx_ctx_set_option: diagnostic switches (tests, tools), all 0 by default
 	// dwtx_encode_device cuts a batch into parts that run on contexts of their own (stream + scratch each): one part's
 	// memory-bound lifting overlaps the instruction-bound entropy stage of the part before (codec.hip)
@@ -107,9 +108,9 @@ enum {
 	SLOT_LIFT_A = 0, SLOT_LIFT_B,   // lift.hip
 	SLOT_PK_CUM, SLOT_PK_SMALL, SLOT_PK_ENT, SLOT_PK_TOKBIG, SLOT_PK_TOK16, SLOT_PK_LUT, SLOT_PK_CHUNK, SLOT_PK_STAGE,   // pack.hip
 	SLOT_UP_SMALL = 12, SLOT_UP_BITS, SLOT_UP_TILES, SLOT_UP_CHUNKS,   // unpack.hip
-	SLOT_CD_A, SLOT_CD_B, SLOT_CD_INFO, SLOT_CD_IO, SLOT_CD_IO2, SLOT_CD_LENS, SLOT_CD_F16,   // codec.hip
+	SLOT_CD_A, SLOT_CD_B, SLOT_CD_INFO, SLOT_CD_IO, SLOT_CD_IO2, SLOT_CD_LENS, SLOT_CD_F16, SLOT_CD_INDEX,   // codec.hip
 };
-static_assert(SLOT_CD_F16 < DWTX_SCRATCH_SLOTS, "more scratch slots than dwtx_ctx has");
+static_assert(SLOT_CD_INDEX < DWTX_SCRATCH_SLOTS, "more scratch slots than dwtx_ctx has");
 
 static inline size_t dwtx_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -234,8 +235,10 @@ int dwtx_linearization_ex(dwtx_ctx *ctx, int32_t *lin, const int32_t *pyr, int W
 int dwtx_reconstruction_ex(dwtx_ctx *ctx, int32_t *pyr, const int32_t *lin, const int *dev_missing, int levels_out, int W, int H,
 	int C, int n, unsigned skip_levels, dwtx_p16 p16 = dwtx_p16{ nullptr, 0u });
 // hist_levels: ring levels whose tile histograms the forward transform has already written (dwtx_hist_begin)
+// dev_index (optional, device memory): entry i receives the sidecar index of image i's stream
 int dwtx_encode_planes_ex(dwtx_ctx *ctx, const int32_t *lin, const int32_t *pyr, unsigned sq_levels, unsigned hist_levels, int W, int H, int C, int n,
-	long capacity, uint8_t *out, size_t out_stride, dwtx_stream_info *dev_info, dwtx_p16 p16 = dwtx_p16{ nullptr, 0u });
+	long capacity, uint8_t *out, size_t out_stride, dwtx_stream_info *dev_info, dwtx_p16 p16 = dwtx_p16{ nullptr, 0u },
+	dwtx_index *dev_index = nullptr);
 
 // unpack.hip: dwtx_decode_planes with a host callback per finished part of the batch (see there)
 // `pyr` (optional): pyramid planes [n*C][H][W]; for parts of the batch that decode at full resolution the tiles of

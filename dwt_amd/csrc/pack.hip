@@ -43,6 +43,8 @@
 //             through an LDS window of the wave's stretch of the stream.
 //   k_refcopy refinement blocks from the staging buffer to their place behind
 //             each segment's tokens (a shifted copy).
+//   k_index   only when asked for (dwtx_ctx_set_encode_index): the stream's sidecar
+//             index, one lane per segment, read out of the tables above.
 #include "hilbert_dev.h"
 
 #include <stdlib.h>
@@ -143,6 +145,7 @@ struct Work {
 	int *slow;                         // [n] set when the fast order pass could not resolve an image
 	long ES, TS, NCS, NGS, NCB, SW;
 	int NT, NTP;
+	unsigned *seg_run;                 // [n][MAX_SEGS] pending run entering the segment's first entry (k_carry_apply<true> -> k_index)
 };
 
 __device__ __forceinline__ int lane_id()
@@ -1459,6 +1462,8 @@ __global__ __launch_bounds__(CARRY_BLOCK) void k_carry_blocks(Work w)
 		token_store(w, img, I.T - 1, s, T_NOSIGN);   // encode.c:221 rle_flush: always emitted
 }
 
+// INDEX: the sidecar index was asked for (k_index): the pending run a segment is entered with is noted on the way
+template <bool INDEX>
 __global__ __launch_bounds__(CARRY_THREADS) void k_carry_apply(Work w)
 {
 	__shared__ RunMap wagg[16];
@@ -1494,6 +1499,11 @@ __global__ __launch_bounds__(CARRY_THREADS) void k_carry_apply(Work w)
 		if (e >= I.E)
 			break;
 		const unsigned tb = w.ent_tokbase[img * (w.ES + 1) + e];
+		if constexpr (INDEX) {
+			const int k = w.ent_seg[img * w.ES + e];
+			if (e == w.seg_ebase[(long)img * (MAX_SEGS + 1) + k])
+				w.seg_run[(long)img * MAX_SEGS + k] = s_in;
+		}
 		if (has_one[j] && s_in) {   // the entry's first token: its run began before this tile
 			const unsigned tk = w.tok16[img * w.TS + tb];
 			token_store(w, img, tb, (tk & T_RUN) + s_in, tk & ~T_RUN);
@@ -2418,6 +2428,146 @@ __global__ __launch_bounds__(256) void k_refcopy(Work w, unsigned *out, long out
 	}
 }
 
+// ----------------------------------------------------------------- k_index ---
+// The sidecar index of the stream just built (include/dwtx.h dwtx_index; only launched when one was asked for): what the
+// decoder's serial walk notes where a segment's first pass begins (decode.c:67-100) — stream position, VLI order
+// (vli.h:24), run counter (rle.h:25), coefficients still insignificant — read out of the encoder's own tables.  One lane
+// per segment, one more for the header:
+//   n1        the ring's coefficients below 2^(p+1): all that are not refinement bits of the segment (seg_refs).
+//   sym_base  the decoder's symbol slots, 32-aligned per segment: a scan over the schedule.
+//   no run pending (k_carry_apply's seg_run is 0): the emitter's position and order where it reaches the segment's
+//             first token slot — its group's (chunk_base + lane_bits, grp_ord) plus a walk over the slots before it.
+//   inside a run of which j zeros lie before the segment: the decoder has read the code of the token that carries the
+//             run — the first slot at or after the segment's that is not void — but not the sign behind it; with v the
+//             token's run, rle.h:66-78 leaves v - j + 1 in the counter (get_rle does not count down on the call that
+//             reads the token).  Position and order are those behind that code.
+//   stream_bits  where the decoder stops: it reads the final flush (encode.c:221) only if a run is pending there.
+// A stream that CAPACITY shortened, a flat picture and one with too many planes get a header with nsegs = 0 (and
+// stream_bits 0).  Only the header and seg[0 .. nsegs) are written.
+constexpr int IDX_THREADS = 832;   // MAX_SEGS + 1 lanes, in whole waves
+static_assert(IDX_THREADS > MAX_SEGS && IDX_THREADS % 64 == 0, "one lane per segment and one for the header");
+
+__global__ __launch_bounds__(IDX_THREADS) void k_index(PackGeom g, Work w, dwtx_index *index)
+{
+	__shared__ unsigned long long wsum[IDX_THREADS / 64];
+	__shared__ unsigned nxt[IDX_THREADS];
+	__shared__ unsigned btok[MAX_SEGS], srefs[MAX_SEGS];   // break slots and refinement bits of the segments: the walk looks them up
+	const int img = blockIdx.x;
+	const ImgInfo &I = w.info[img];
+	dwtx_index &X = index[img];
+	const int K = I.K;
+	const bool whole = I.nbytes >= (w.stream_bits[img] + 7) >> 3;
+	if (K <= 0 || I.pmax <= 0 || I.error || I.cut || !whole) {   // (uniform)
+		if (threadIdx.x == 0) {
+			X.magic = DWTX_INDEX_MAGIC;
+			X.W = g.W;
+			X.H = g.H;
+			X.C = g.C;
+			X.nsegs = 0;
+			X.reserved = 0;
+			X.stream_bits = 0ull;
+		}
+		return;
+	}
+	const int k = threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const int *sd = w.seg_desc + (long)img * MAX_SEGS;
+	int num = 0;
+	if (k < K) {
+		int c, l, p;
+		seg_unpack(sd[k], c, l, p);
+		num = g.pixels[l + 1] - g.pixels[l];
+	}
+	const long T = I.T;
+	const unsigned short *tok16 = w.tok16 + img * w.TS;
+	const unsigned *big = w.tok_big + img * w.TS;
+	if (k < K) {
+		btok[k] = w.brk_tok[(long)img * MAX_SEGS + k];
+		srefs[k] = w.seg_refs[(long)img * MAX_SEGS + k];
+	}
+	// A segment's slots are its ones and then its break slot: where the first of them is void the segment is that one slot
+	// (no ones, nothing to end a run for).  The token that carries a run into segment k is therefore the first slot of the
+	// first segment from k on whose first slot is not void, or the final flush: a suffix minimum over the segments.
+	long t0 = T - 1;
+	if (k < K) {
+		t0 = w.ent_tokbase[img * (w.ES + 1) + w.seg_ebase[(long)img * (MAX_SEGS + 1) + k]];
+		nxt[k] = (tok16[t0] & T_VOID) ? (unsigned)(T - 1) : (unsigned)t0;
+	} else {
+		nxt[k] = (unsigned)(T - 1);
+	}
+	unsigned long long wtot;
+	unsigned long long sym_base = wave_excl_scan64(((unsigned long long)num + 31ull) & ~31ull, wtot);
+	if (lane == 0)
+		wsum[wv] = wtot;
+	__syncthreads();
+	for (int i = 0; i < wv; ++i)
+		sym_base += wsum[i];
+	for (int d = 1; d < IDX_THREADS; d <<= 1) {
+		const unsigned a = nxt[k], b = k + d < IDX_THREADS ? nxt[k + d] : a;
+		__syncthreads();
+		nxt[k] = a < b ? a : b;
+		__syncthreads();
+	}
+	if (k > K)
+		return;
+	// the slot to stand in front of: the segment's first, or — inside a run — the token that carries the run; lane K: the final flush
+	const unsigned j = k < K ? w.seg_run[(long)img * MAX_SEGS + k] : 0u;
+	const long tt = j ? (long)nxt[k] : t0;
+	const long S = tt / SUB;
+	const int per = w.slow[img] ? 64 : FSUBS;
+	unsigned long long pos = w.chunk_base[img * w.NCS + S / per] + w.lane_bits[img * w.NCS * 64 + S];
+	int o = w.grp_ord[img * w.NCS * 64 + S];
+	// the slots of the group before it: the whole group is loaded at once (the token arrays are whole groups long), the
+	// walk then only waits for the escapes and break slots it meets
+	uint4 grp[8];
+#pragma unroll
+	for (int q = 0; q < 8; ++q)
+		grp[q] = *reinterpret_cast<const uint4 *>(tok16 + S * SUB + 8 * q);
+	const int before = (int)(tt - S * SUB);
+	int kb = (int)find_break_seg(btok, K, (unsigned)(S * SUB));   // the segment of the first break slot the walk can meet
+#pragma unroll
+	for (int q = 0; q < 32; ++q) {
+		const uint4 x4 = grp[q >> 2];
+		const unsigned x = (q & 3) == 0 ? x4.x : (q & 3) == 1 ? x4.y : (q & 3) == 2 ? x4.z : x4.w;
+#pragma unroll
+		for (int h = 0; h < 2; ++h) {
+			const unsigned tk = h ? x >> 16 : x & 0xffffu;
+			const long t = S * SUB + 2 * q + h;
+			if (2 * q + h < before) {
+				if (!(tk & T_VOID)) {
+					const int top = vli_top(o, token_run(tk, big, t));
+					pos += (unsigned)(2 * top - o + 1) + ((tk & T_NOSIGN) ? 0u : 1u);
+					o = vli_next(top);
+				}
+				if (tk & T_BREAK)
+					pos += srefs[kb++];
+			}
+		}
+	}
+	const unsigned v = token_run(tok16[tt], big, tt);
+	if (k < K ? j != 0u : v != 0u) {   // the decoder has read this token's code
+		const int top = vli_top(o, v);
+		pos += (unsigned)(2 * top - o + 1);
+		o = vli_next(top);
+	}
+	if (k < K) {
+		dwtx_seg_index &e = X.seg[k];
+		e.bit = pos;
+		e.sym_base = sym_base;
+		e.n1 = (unsigned)num - srefs[k];
+		e.cnt = j ? v - j + 1u : 0u;
+		e.desc = (unsigned)sd[k];
+		e.order = (unsigned)o;
+	} else {
+		X.magic = DWTX_INDEX_MAGIC;
+		X.W = g.W;
+		X.H = g.H;
+		X.C = g.C;
+		X.nsegs = K;
+		X.reserved = 0;
+		X.stream_bits = pos;
+	}
+}
+
 } // namespace
 
 // ------------------------------------------------------------------ driver ---
@@ -2425,7 +2575,8 @@ __global__ __launch_bounds__(256) void k_refcopy(Work w, unsigned *out, long out
 extern "C" int dwtx_encode_planes(dwtx_ctx *ctx, const int32_t *lin, int W, int H, int C, int n, long capacity,
 	uint8_t *out, size_t out_stride, dwtx_stream_info *dev_info)
 {
-	return dwtx_encode_planes_ex(ctx, lin, nullptr, 0u, 0u, W, H, C, n, capacity, out, out_stride, dev_info);
+	return dwtx_encode_planes_ex(ctx, lin, nullptr, 0u, 0u, W, H, C, n, capacity, out, out_stride, dev_info, dwtx_p16{ nullptr, 0u },
+		ctx ? ctx->enc_index : nullptr);
 }
 
 // geometry, tiles and the histogram records of n images (what both the forward transform's histograms and the
@@ -2497,7 +2648,7 @@ extern "C" int dwtx_debug_hist_copy(dwtx_ctx *ctx, int W, int H, int C, int n, u
 // pyr / sq_levels: the ring levels flagged in sq_levels are not in `lin`; their tiles are read from the
 // 32x32 squares of the pyramid planes `pyr` (same plane order, pitch W) — see hilbert_dev.h
 int dwtx_encode_planes_ex(dwtx_ctx *ctx, const int32_t *lin, const int32_t *pyr, unsigned sq_levels, unsigned hist_levels, int W, int H, int C,
-	int n, long capacity, uint8_t *out, size_t out_stride, dwtx_stream_info *dev_info, dwtx_p16 p16)
+	int n, long capacity, uint8_t *out, size_t out_stride, dwtx_stream_info *dev_info, dwtx_p16 p16, dwtx_index *dev_index)
 {
 	if (!ctx || !lin || !out || !dev_info || (C != 1 && C != 3) || n < 1 || n > 65535 || (out_stride & 3) || out_stride < 8)
 		return DWTX_ERR_ARG;
@@ -2547,6 +2698,7 @@ int dwtx_encode_planes_ex(dwtx_ctx *ctx, const int32_t *lin, const int32_t *pyr,
 		c.take(w.brk_tok, imgs * MAX_SEGS);
 		c.take(w.segidx, imgs * 48 * MAX_PLANES);
 		c.take(w.live, imgs * 48);
+		c.take(w.seg_run, imgs * MAX_SEGS);
 	});
 	if (!small)
 		return DWTX_ERR_NOMEM;
@@ -2608,7 +2760,10 @@ int dwtx_encode_planes_ex(dwtx_ctx *ctx, const int32_t *lin, const int32_t *pyr,
 	hipLaunchKernelGGL(k_code<true>, dim3(dwtx_cdiv(NT, 4) < 64 ? dwtx_cdiv(NT, 4) : 64, nplanes), dim3(256), 0, s, g, lin, w);
 	hipLaunchKernelGGL(k_carry_local, dim3((unsigned)w.NCB, n), dim3(CARRY_THREADS), 0, s, w);
 	hipLaunchKernelGGL(k_carry_blocks, dim3(n), dim3(CARRY_BLOCK), 0, s, w);
-	hipLaunchKernelGGL(k_carry_apply, dim3((unsigned)w.NCB, n), dim3(CARRY_THREADS), 0, s, w);
+	if (dev_index)
+		hipLaunchKernelGGL(k_carry_apply<true>, dim3((unsigned)w.NCB, n), dim3(CARRY_THREADS), 0, s, w);
+	else
+		hipLaunchKernelGGL(k_carry_apply<false>, dim3((unsigned)w.NCB, n), dim3(CARRY_THREADS), 0, s, w);
 	hipLaunchKernelGGL(k_gorder, dim3((int)((w.NCS + GO_WAVES - 1) / GO_WAVES), n), dim3(64 * GO_WAVES), 0, s, w);
 	// exact pass: only images the fast pass flagged (their kernels return at once otherwise)
 	hipLaunchKernelGGL(k_lut, dim3(512, n), dim3(256), 0, s, w);
@@ -2622,6 +2777,8 @@ int dwtx_encode_planes_ex(dwtx_ctx *ctx, const int32_t *lin, const int32_t *pyr,
 	}
 	hipLaunchKernelGGL(k_emit, dim3((unsigned)((w.TS / CHUNK + 1 + 3) / 4), n), dim3(256), 0, s, w, outw, out_words);
 	hipLaunchKernelGGL(k_refcopy, dim3(256, n), dim3(256), 0, s, w, outw, out_words);
+	if (dev_index)   // the sidecar index, when asked for (dwtx_ctx_set_encode_index)
+		hipLaunchKernelGGL(k_index, dim3(n), dim3(IDX_THREADS), 0, s, g, w, dev_index);
 	DWTX_LAUNCH_CHECK();
 	static_assert(sizeof(dwtx_stream_info) == sizeof(ImgInfo), "ImgInfo is the device image of dwtx_stream_info");
 	DWTX_HIP(hipMemcpyAsync(dev_info, w.info, sizeof(ImgInfo) * (size_t)n, hipMemcpyDeviceToDevice, s));

@@ -113,7 +113,7 @@ typedef struct dwtx_decode_info {
  * are still insignificant).  A decode that is given the index walks all segments at once instead of one after
  * the other; it checks on the way that the segments fit together, so a wrong, stale or foreign index cannot
  * change the result: the decoder then falls back to the plain walk.  A decode produces the index of every stream
- * it decodes to its end. */
+ * it decodes to its end, and an encode that of every stream it writes whole (dwtx_ctx_set_encode_index). */
 #define DWTX_INDEX_MAGIC 0x49545744u   /* "DWTI" */
 #define DWTX_INDEX_MAX_SEGS 768         /* 3 channels x 16 levels x 16 planes */
 typedef struct dwtx_seg_index {
@@ -148,6 +148,13 @@ int dwtx_sync(dwtx_ctx *ctx);
  * index of image i (nsegs = 0 if it has none).  Both are host arrays that must stay valid until replaced;
  * dwtx_ctx_set_index(ctx, NULL, NULL) ends it. */
 int dwtx_ctx_set_index(dwtx_ctx *ctx, const dwtx_index *in, dwtx_index *out);
+/* Sidecar indices from the ENCODE calls that follow on this context: entry i of `out` receives the index of image i of
+ * a call.  For dwtx_encode_planes / dwtx_encode_device `out` is DEVICE memory, written asynchronously on the context's
+ * stream like dev_info; for dwtx_encode_images it is HOST memory, filled on return.  NULL ends it.  The encoder writes
+ * the index the decoder would make of the same stream (only the header and seg[0 .. nsegs) of an entry are written); a
+ * stream that CAPACITY shortened, a flat picture and one that is refused have none (nsegs = 0, stream_bits = 0).
+ * Independent of dwtx_ctx_set_index, which belongs to the decode calls. */
+int dwtx_ctx_set_encode_index(dwtx_ctx *ctx, dwtx_index *out);
 void *dwtx_stream(dwtx_ctx *ctx);
 
 /* Diagnostic switches of a context, all off (0) by default.  They exist for the tests, the profiling tools and
