@@ -356,3 +356,126 @@ class Context:
         _check(self.lib.dwtx_decode_device(self.h, _ptr(streams), stride, _ptr(lens), W, H, C_, n, levels_max,
                                            _ptr(out), W * H * C_, C.cast(infos, C.c_void_p)), "dwtx_decode_device")
         return out, list(infos)
+
+    # -- deep pixels: uint16 samples, maxval up to 65535 (the *16 calls of include/dwtx.h) -----------------------
+    # torch's uint16 has few operators on the device, so deep device tensors may be torch.uint16 or torch.int16
+    # (the same two bytes); results come back as torch.uint16.
+
+    def _is16(self, t):
+        return t.dtype in (self.torch.uint16, self.torch.int16) and t.is_contiguous() and t.device == self.device
+
+    def planes_from_pixels16(self, pix):
+        """16-bit [n,H,W,C] interleaved device tensor -> int32 [n*C,H,W] planar (YCoCg-R if C==3)."""
+        torch = self.torch
+        n, H, W, Cn = pix.shape
+        assert self._is16(pix)
+        out = torch.empty((n * Cn, H, W), dtype=torch.int32, device=self.device)
+        _check(self.lib.dwtx_planes_from_pixels16(self.h, _ptr(out), _ptr(pix), W, H, Cn, n), "dwtx_planes_from_pixels16")
+        return out
+
+    def pixels16_from_planes(self, planes, C_, maxval):
+        """int32 [n*C,H,W] -> uint16 [n,H,W,C] with the reference's clamps at maxval."""
+        torch = self.torch
+        nC, H, W = planes.shape
+        n = nC // C_
+        assert planes.dtype == torch.int32 and planes.is_contiguous()
+        out = torch.empty((n, H, W, C_), dtype=torch.uint16, device=self.device)
+        _check(self.lib.dwtx_pixels16_from_planes(self.h, _ptr(out), _ptr(planes), W, H, C_, n, maxval), "dwtx_pixels16_from_planes")
+        return out
+
+    def transformation_fwd_pixels16(self, pix, out=None):
+        """encode.c:155-159 for deep pixels: 16-bit [n,H,W,C] -> int32 pyramid [n*C,H,W]."""
+        torch = self.torch
+        n, H, W, Cn = pix.shape
+        assert self._is16(pix)
+        if out is None:
+            out = torch.empty((n * Cn, H, W), dtype=torch.int32, device=self.device)
+        _check(self.lib.dwtx_transformation_fwd_pixels16(self.h, _ptr(out), _ptr(pix), W, H, Cn, n), "dwtx_transformation_fwd_pixels16")
+        return out
+
+    def transformation_inv_pixels16(self, pyr, Cn, maxval, out=None):
+        """decode.c:258-264 for deep pixels: int32 pyramid [n*C,H,W] -> uint16 [n,H,W,C], clamps at maxval."""
+        torch = self.torch
+        P, H, W = pyr.shape
+        n = P // Cn
+        assert pyr.dtype == torch.int32 and pyr.is_contiguous()
+        if out is None:
+            out = torch.empty((n, H, W, Cn), dtype=torch.uint16, device=self.device)
+        _check(self.lib.dwtx_transformation_inv_pixels16(self.h, _ptr(out), _ptr(pyr), W, H, Cn, n, maxval),
+               "dwtx_transformation_inv_pixels16")
+        return out
+
+    def encode16(self, pix, capacity=0):
+        """uint16 numpy [n,H,W,C] (or [H,W,C]) -> list of .dwt byte strings, list of Stats.  A picture that needs more
+        than 16 bit planes raises DwtxError (rc -3)."""
+        import numpy as np
+
+        single = pix.ndim == 3
+        pix = np.ascontiguousarray(pix[None] if single else pix, dtype=np.uint16)
+        n, H, W, Cn = pix.shape
+        stride = self.lib.dwtx_encode_bound16(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
+        out = np.empty((n, stride), dtype=np.uint8)
+        lens = (C.c_size_t * n)()
+        stats = (Stats * n)()
+        _check(self.lib.dwtx_encode_images16(self.h, pix.ctypes.data, W, H, Cn, n, capacity, out.ctypes.data, stride,
+                                             C.cast(lens, C.c_void_p), C.cast(stats, C.c_void_p)), "dwtx_encode_images16")
+        streams = [out[i, : lens[i]].tobytes() for i in range(n)]
+        return (streams[0], stats[0]) if single else (streams, list(stats))
+
+    def decode16(self, streams, maxval, pixels_max=-1):
+        """.dwt byte string (or list of same-geometry ones) -> uint16 numpy [h,w,C] (or list); None if unreadable.
+        maxval (1..65535) is what the pictures were encoded from: a .dwt does not record it."""
+        import numpy as np
+
+        single = isinstance(streams, (bytes, bytearray))
+        lst = [streams] if single else list(streams)
+        n = len(lst)
+        if len(lst[0]) < 6:
+            raise DwtxError(-3, "dwtx_decode_images16 (short header)")
+        W = (lst[0][2] | (lst[0][3] << 8)) + 1
+        H = (lst[0][4] | (lst[0][5] << 8)) + 1
+        Cn = 3 if lst[0][1:2] == b"6" else 1
+        stride = (max(len(s) for s in lst) + 64 + 7) // 8 * 8
+        host = np.zeros((n, stride), dtype=np.uint8)
+        for i, s in enumerate(lst):
+            host[i, : len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
+        lens = (C.c_size_t * n)(*[len(s) for s in lst])
+        pstride = W * H * Cn
+        pix = np.empty((n, pstride), dtype=np.uint16)
+        ow, oh, oc = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        rc = self.lib.dwtx_decode_images16(self.h, host.ctypes.data, stride, C.cast(lens, C.c_void_p), n, pixels_max,
+                                           pix.ctypes.data, pstride, maxval, ow, oh, oc, None)
+        if rc == -1 and n == 1:   # as decode()
+            return None if single else [None]
+        _check(rc, "dwtx_decode_images16")
+        outs = [pix[i, : ow[i] * oh[i] * oc[i]].reshape(oh[i], ow[i], oc[i]).copy() if ow[i] else None for i in range(n)]
+        return outs[0] if single else outs
+
+    def encode_device16(self, pix, capacity=0, out=None, info=None):
+        """16-bit device tensor [n,H,W,C] -> (streams uint8 [n,stride], info uint8 [n,sizeof(StreamInfo)]) on device; async."""
+        torch = self.torch
+        n, H, W, Cn = pix.shape
+        assert self._is16(pix)
+        stride = self.lib.dwtx_encode_bound16(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
+        if out is None:
+            out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
+        if info is None:
+            info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
+        _check(self.lib.dwtx_encode_device16(self.h, _ptr(pix), W, H, Cn, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
+               "dwtx_encode_device16")
+        return out, info
+
+    def decode_device16(self, streams, lens, W, H, C_, maxval, levels_max=-1, out=None):
+        """device streams [n,stride] + int64 lens -> (uint16 [n, W*H*C] pixels, list of DecodeInfo); syncs once.
+        `out`: a 16-bit device tensor [n, pix_stride] with pix_stride (in samples) >= the pictures' size."""
+        torch = self.torch
+        n, stride = streams.shape
+        assert streams.dtype == torch.uint8 and streams.is_contiguous() and stride % 8 == 0
+        assert lens.dtype == torch.int64 and lens.numel() == n
+        if out is None:
+            out = torch.empty((n, W * H * C_), dtype=torch.uint16, device=self.device)
+        assert self._is16(out) and out.shape[0] == n
+        infos = (DecodeInfo * n)()
+        _check(self.lib.dwtx_decode_device16(self.h, _ptr(streams), stride, _ptr(lens), W, H, C_, n, levels_max,
+                                             _ptr(out), out.shape[1], maxval, C.cast(infos, C.c_void_p)), "dwtx_decode_device16")
+        return out, list(infos)

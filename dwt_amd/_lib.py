@@ -69,7 +69,7 @@ class Stats(C.Structure):
 # enum dwtx_option (include/dwtx.h): diagnostic switches of a context
 OPTIONS = {name: i for i, name in enumerate((
     "exact_orders", "no_square_tiles", "part_images", "one_stream", "decode_parts", "two_families", "no_second_walk",
-    "no_index", "no_index_fallback", "no_capacity_cut", "no_fine16", "no_fused_levels"))}
+    "no_index", "no_index_fallback", "no_capacity_cut", "no_fine16", "no_fused_levels", "no_pixels16"))}
 
 # name -> (restype, argtypes); must list every symbol include/dwtx.h declares
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
@@ -110,6 +110,16 @@ SYMBOLS = {
     "dwtx_decode_images_info": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "dwtx_decode_planes": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _vp]),
     "dwtx_encode_planes": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
+    # deep pixels (uint16 samples)
+    "dwtx_planes_from_pixels16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    "dwtx_pixels16_from_planes": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "dwtx_transformation_fwd_pixels16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    "dwtx_transformation_inv_pixels16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "dwtx_encode_bound16": (_sz, [_i, _i, _i]),
+    "dwtx_encode_device16": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
+    "dwtx_decode_device16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
+    "dwtx_encode_images16": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp, _vp]),
+    "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -8,6 +8,9 @@
  * stream it is offered to the decoder as the stream's sidecar index (include/dwtx.h dwtx_index: all segments
  * are then walked at once; an index that does not fit is noticed and ignored), and with DWTX_WRITE_INDEX set
  * in the environment the decode leaves that file behind.
+ * With DWTX_MAXVAL=<256..65535> in the environment the stream is taken as that of a deep picture (bin/encode under
+ * DWTX_DEEP; a .dwt does not record its depth): decoded through dwtx_decode_images16 with the clamps at that maxval
+ * and written as "P5|P6 w h <maxval>" with two bytes per sample, most significant first.
  */
 #include "../../../include/dwtx.h"
 #include "pnm_io.h"
@@ -57,7 +60,16 @@ int main(int argc, char **argv)
 	uint8_t *padded = (uint8_t *)calloc(stride, 1);
 	memcpy(padded, raw, len);
 	free(raw);
-	uint8_t *pix = (uint8_t *)malloc((size_t)W * H * C);
+	int maxval = 255;
+	if (getenv("DWTX_MAXVAL")) {
+		maxval = atoi(getenv("DWTX_MAXVAL"));
+		if (maxval < 256 || maxval > 65535) {
+			fprintf(stderr, "DWTX_MAXVAL must be 256..65535\n");
+			return 1;
+		}
+	}
+	const int deep = maxval > 255;
+	void *pix = malloc((size_t)W * H * C * (deep ? 2 : 1));
 	dwtx_ctx *ctx;
 	if (dwtx_ctx_create(0, &ctx)) {
 		fprintf(stderr, "%s\n", dwtx_last_error());
@@ -91,7 +103,8 @@ int main(int argc, char **argv)
 		dwtx_ctx_set_option(ctx, DWTX_OPT_NO_INDEX_FALLBACK, 1);
 	int ow, oh, oc;
 	dwtx_decode_info info;
-	int rc = dwtx_decode_images_info(ctx, padded, stride, &len, 1, pixels_max, pix, (size_t)W * H * C, &ow, &oh, &oc, &info);
+	int rc = deep ? dwtx_decode_images16(ctx, padded, stride, &len, 1, pixels_max, (uint16_t *)pix, (size_t)W * H * C, maxval, &ow, &oh, &oc, &info)
+		: dwtx_decode_images_info(ctx, padded, stride, &len, 1, pixels_max, (uint8_t *)pix, (size_t)W * H * C, &ow, &oh, &oc, &info);
 	if (rc == DWTX_ERR_IO) {   /* decode.c:181,185: root image or plane counts cut off */
 		fprintf(stderr, "reached end of file \"%s\"\n", argv[1]);
 		return 1;
@@ -104,7 +117,7 @@ int main(int argc, char **argv)
 		fprintf(stderr, "reached end of file \"%s\"\n", argv[1]);
 	if (info.zeros_left > 1)   /* rle.h:43-46: the PIXELS cap (or the end of data) left part of a zero run unread */
 		fprintf(stderr, "%u zeros not read.\n", info.zeros_left);
-	if (!pnm_write(argv[2], pix, ow, oh, oc))
+	if (!pnm_write(argv[2], pix, ow, oh, oc, maxval))
 		return 1;
 	if (ix_out && ix_out->nsegs > 0) {
 		FILE *fo = fopen(iname, "wb");

@@ -7,6 +7,9 @@
  *
  * Beyond the reference: with DWTX_WRITE_INDEX set in the environment the encoder also writes the stream's sidecar index
  * (include/dwtx.h dwtx_index, dwtx_ctx_set_encode_index), which is left in "output.dwt.idx" for later decodes to find.
+ * With DWTX_DEEP set, P5 / P6 files with a maxval of 256..65535 (two bytes per sample) are encoded too, through
+ * dwtx_encode_images16; without it they are refused with the reference's message (pnm.h:63-64).  The .dwt does not
+ * record the maxval: the decoder has to be told (DWTX_MAXVAL).
  */
 #include "../../../include/dwtx.h"
 #include "pnm_io.h"
@@ -18,7 +21,9 @@ int main(int argc, char **argv)
 		return 1;
 	}
 	int W, H, C;
-	uint8_t *pix = pnm_read(argv[1], &W, &H, &C);
+	int maxval = 255;
+	void *pix = pnm_read(argv[1], &W, &H, &C, getenv("DWTX_DEEP") ? &maxval : NULL);
+	const int deep = maxval > 255;
 	if (!pix || W > 65536 || H > 65536)          /* encode.c:140 */
 		return 1;
 	if (W < DWTX_MIN_LEN || H < DWTX_MIN_LEN)    /* encode.c:145 */
@@ -35,7 +40,7 @@ int main(int argc, char **argv)
 		return 1;
 	}
 	/* a CAPACITY beyond what the image can need must not size the buffers */
-	size_t stride = dwtx_encode_bound(W, H, C);
+	size_t stride = deep ? dwtx_encode_bound16(W, H, C) : dwtx_encode_bound(W, H, C);
 	if (capacity > 0 && ((size_t)capacity + 15) / 8 * 8 < stride)
 		stride = ((size_t)capacity + 15) / 8 * 8;
 	uint8_t *out = (uint8_t *)malloc(stride);
@@ -46,7 +51,8 @@ int main(int argc, char **argv)
 		ix = (dwtx_index *)calloc(1, sizeof(dwtx_index));
 		dwtx_ctx_set_encode_index(ctx, ix);
 	}
-	int rc = dwtx_encode_images(ctx, pix, W, H, C, 1, capacity, out, stride, &len, &st);
+	int rc = deep ? dwtx_encode_images16(ctx, (const uint16_t *)pix, W, H, C, 1, capacity, out, stride, &len, &st)
+		: dwtx_encode_images(ctx, (const uint8_t *)pix, W, H, C, 1, capacity, out, stride, &len, &st);
 	if (rc) {
 		fprintf(stderr, "%s\n", dwtx_last_error());
 		return 1;

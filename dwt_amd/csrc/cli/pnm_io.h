@@ -1,7 +1,9 @@
 /* pnm_io.h — PNM (P5/P6, maxval 255) and whole-file byte I/O for the CLIs.
  * Host-side edge of the pipeline: pnm.h:14-117 and bytes.h:24-118 of the
  * reference do this one fgetc/fputc at a time; here it is bulk fread/fwrite
- * with the same accepted inputs, messages and "-" = stdin/stdout rule. */
+ * with the same accepted inputs, messages and "-" = stdin/stdout rule.
+ * Beyond the reference, and only where the caller asks for it: deep PNM files,
+ * maxval 256..65535, two bytes per sample, most significant first (Netpbm). */
 #ifndef DWTX_PNM_IO_H
 #define DWTX_PNM_IO_H
 
@@ -51,8 +53,10 @@ static uint8_t *read_all(FILE *f, size_t *len)
 	return b;
 }
 
-/* pnm.h:14-90.  Returns malloc'ed pixel payload or NULL (message printed). */
-static uint8_t *pnm_read(const char *name, int *W, int *H, int *C)
+/* pnm.h:14-90.  Returns malloc'ed pixel payload or NULL (message printed).
+ * maxval == NULL: 8-bit files only, as the reference.  Otherwise files with a maxval of 256..65535 are read too:
+ * *maxval receives the file's, and above 255 the payload is native-endian uint16_t samples. */
+static void *pnm_read(const char *name, int *W, int *H, int *C, int *maxval)
 {
 	const char *fname = std_name(name, "/dev/stdin");
 	FILE *f = open_stream(name, fname, 0);
@@ -95,10 +99,29 @@ static uint8_t *pnm_read(const char *name, int *W, int *H, int *C)
 		free(b);
 		return 0;
 	}
-	if (v[2] != 255) {
+	if (v[2] != 255 && !(maxval && v[2] >= 256 && v[2] <= 65535)) {
 		fprintf(stderr, "cant read \"%s\", only 8 bit per channel SRGB supported at the moment.\n", fname);
 		free(b);
 		return 0;
+	}
+	if (maxval)
+		*maxval = (int)v[2];
+	if (v[2] > 255) {
+		size_t samples = (size_t)v[0] * (size_t)v[1] * (size_t)*C;
+		if (p + 2 * samples > len)
+			goto eof;
+		uint16_t *pix = (uint16_t *)malloc(samples ? 2 * samples : 2);
+		if (!pix) {
+			fprintf(stderr, "could not read image file \"%s\".\n", fname);
+			free(b);
+			return 0;
+		}
+		for (size_t i = 0; i < samples; ++i)
+			pix[i] = (uint16_t)(b[p + 2 * i] << 8 | b[p + 2 * i + 1]);
+		free(b);
+		*W = (int)v[0];
+		*H = (int)v[1];
+		return pix;
 	}
 	{
 		size_t need = (size_t)v[0] * (size_t)v[1] * (size_t)*C;
@@ -117,8 +140,9 @@ eof:
 	return 0;
 }
 
-/* pnm.h:92-117 (values are already clamped to 0..255 by the device kernel) */
-static int pnm_write(const char *name, const uint8_t *pix, int W, int H, int C)
+/* pnm.h:92-117 (values are already clamped to 0..maxval by the device kernel).  maxval 255: pix is bytes, as the
+ * reference writes them; above: native-endian uint16_t samples, written most significant byte first. */
+static int pnm_write(const char *name, const void *pix, int W, int H, int C, int maxval)
 {
 	const char *fname = std_name(name, "/dev/stdout");
 	FILE *f = open_stream(name, fname, 1);
@@ -126,8 +150,19 @@ static int pnm_write(const char *name, const uint8_t *pix, int W, int H, int C)
 		fprintf(stderr, "could not open \"%s\" file to write.\n", fname);
 		return 0;
 	}
-	if (fprintf(f, "P%d %d %d 255\n", C == 1 ? 5 : 6, W, H) < 0 ||
-		fwrite(pix, 1, (size_t)W * H * C, f) != (size_t)W * H * C) {
+	const size_t samples = (size_t)W * H * C, bytes = maxval > 255 ? 2 * samples : samples;
+	uint8_t *be = NULL;
+	if (maxval > 255) {
+		be = (uint8_t *)malloc(bytes ? bytes : 1);
+		for (size_t i = 0; be && i < samples; ++i) {
+			be[2 * i] = (uint8_t)(((const uint16_t *)pix)[i] >> 8);
+			be[2 * i + 1] = (uint8_t)((const uint16_t *)pix)[i];
+		}
+	}
+	const int ok = (maxval <= 255 || be) && fprintf(f, "P%d %d %d %d\n", C == 1 ? 5 : 6, W, H, maxval) >= 0 &&
+		fwrite(be ? (const void *)be : pix, 1, bytes, f) == bytes;
+	free(be);
+	if (!ok) {
 		fprintf(stderr, "EOF while writing to \"%s\".\n", fname);
 		fclose(f);
 		return 0;

@@ -8,17 +8,34 @@
 
 extern "C" size_t dwtx_encode_bound(int W, int H, int C)
 {
-	// 8-bit sources: at most 11 bit planes per coefficient (9 bits of pixel range, +1 for YCoCg chroma, +1
-	// for the HH gain of the 5/3 lifting), each plane costs a coefficient at most 2 bits (a raw refinement
-	// bit, or a pass-1 symbol: VLI(0) at order 0 is one bit, plus the sign) -> below 3 bytes per sample;
-	// uniform noise measures ~9 bit/sample
+	// 8-bit sources: at most 12 bit planes per coefficient (the transform's worst gain is 4.54 for gray and 9.07 for the
+	// chroma of YCoCg-R, whose range is twice the pixels': 9.07 * 255 < 2^12; DESIGN.md sections 4.8 and 7), each plane
+	// costs a coefficient at most 2 bits (a raw refinement bit, or a pass-1 symbol: VLI(0) at order 0 is one bit, plus
+	// the sign) -> 3 bytes per sample; uniform noise measures ~9 bit/sample
 	size_t b = (size_t)3 * W * H * C + 4096;
 	return (b + 7) / 8 * 8;
 }
 
+extern "C" size_t dwtx_encode_bound16(int W, int H, int C)
+{
+	// deep sources: the coder's 16 planes x 2 bits = 4 bytes per sample (a picture that needs more is refused)
+	size_t b = (size_t)4 * W * H * C + 4096;
+	return (b + 7) / 8 * 8;
+}
+
+// The pixels a pipeline starts from or ends in: the reference's bytes (sample_bytes 1, maxval 255) or deep pixels
+// (include/dwtx.h: native-endian uint16_t, the maxval the caller names).  Pixel buffers travel as bytes here; strides of
+// deep buffers count samples at the interface and are scaled where addresses are made.
+struct PixFmt {
+	int sample_bytes;
+	int maxval;
+	bool deep() const { return sample_bytes == 2; }
+};
+constexpr PixFmt PIX8 = { 1, 255 };
+
 // pixels (device) -> streams (device) for one part of a batch, on the part's context; `lifted` (optional) is recorded
 // once the part's transform and linearisation are queued
-static int encode_part(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int C, int n, long capacity,
+static int encode_part(dwtx_ctx *ctx, const uint8_t *dev_pix, PixFmt fmt, int W, int H, int C, int n, long capacity,
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, hipEvent_t lifted, dwtx_index *dev_index)
 {
 	const size_t bytes = sizeof(int) * (size_t)W * H * C * n;
@@ -29,9 +46,11 @@ static int encode_part(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int 
 	int rc;
 	// the forward transform leaves the tiles' magnitude histograms behind where it can (encode.c:112-131's maximum and
 	// everything the entropy stage counts before it codes): the coefficients are not read a second time for them
+	// (not for deep pixels: lift.hip's histogram accumulators hold magnitudes below 2^15, a deep picture's coefficients
+	// reach 2^16 — pack.hip's k_hist counts every level then, as it does for dwtx_encode_planes)
 	dwtx_hist_sink sink;
 	unsigned hist_levels = 0;
-	if ((rc = dwtx_hist_begin(ctx, W, H, C, n, &sink)))
+	if (!fmt.deep() && (rc = dwtx_hist_begin(ctx, W, H, C, n, &sink)))
 		return rc;
 	// encode.c:160: levels that are full power-of-two squares stay in the pyramid (the coder reads their tiles there)
 	const unsigned sq = ctx->opt[DWTX_OPT_NO_SQUARE_TILES] ? 0u : dwtx_square_levels(W, H);
@@ -40,7 +59,7 @@ static int encode_part(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int 
 	// 16 (dwtx_levels16) — and the coder reads their squares in place: the transform writes, and the coder reads, half the
 	// bytes for them.
 	dwtx_p16 fine16 = { nullptr, 0u };
-	const bool from_pixels = dwtx_gray8_ok(W, H, dev_pix, (size_t)W * H * C);
+	const bool from_pixels = !fmt.deep() && dwtx_gray8_ok(W, H, dev_pix, (size_t)W * H * C);
 	if (from_pixels && sq && !ctx->opt[DWTX_OPT_NO_FINE16] && (fine16.levels = dwtx_levels16(W, H, sq))) {
 		fine16.planes = (int16_t *)dwtx_scratch(ctx, SLOT_CD_F16, sizeof(int16_t) * (size_t)W * H * C * n);
 		if (!fine16.planes)
@@ -48,6 +67,14 @@ static int encode_part(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int 
 	}
 	if (from_pixels) {
 		if ((rc = dwtx_fwd_pixels8_hist(ctx, b, dev_pix, W, H, C, n, &sink, &hist_levels, fine16)))   // encode.c:155-159 in one pass
+			return rc;
+	} else if (fmt.deep() && !ctx->opt[DWTX_OPT_NO_PIXELS16] && dwtx_pixels16_ok(W, H, dev_pix, (size_t)W * H * C)) {
+		if ((rc = dwtx_fwd_pixels16(ctx, b, reinterpret_cast<const uint16_t *>(dev_pix), W, H, C, n)))   // encode.c:155-159 in one pass
+			return rc;
+	} else if (fmt.deep()) {
+		if ((rc = dwtx_planes_from_pixels16(ctx, a, reinterpret_cast<const uint16_t *>(dev_pix), W, H, C, n)))   // encode.c:155-156
+			return rc;
+		if ((rc = dwtx_transformation_fwd(ctx, b, a, W, H, n * C)))            // encode.c:159
 			return rc;
 	} else {
 		if ((rc = dwtx_planes_from_pixels(ctx, a, dev_pix, W, H, C, n)))       // encode.c:155-156
@@ -113,10 +140,10 @@ extern "C" int dwtx_transformation_inv_pixels(dwtx_ctx *ctx, uint8_t *dev_pix, c
 // their own, staggered so that part k's transform runs beside part k-1's entropy stage (the transforms follow one
 // another: each fills the memory system by itself).  The caller's stream waits for all parts.
 // dev_index (device memory, or null): entry i receives the sidecar index of image i (dwtx_ctx_set_encode_index)
-static int encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int C, int n, long capacity,
+static int encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, PixFmt fmt, int W, int H, int C, int n, long capacity,
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, dwtx_index *dev_index)
 {
-	if (!ctx || !dev_pix || !dev_out || !dev_info || (C != 1 && C != 3) || n < 1)
+	if (!ctx || !dev_pix || !dev_out || !dev_info || (C != 1 && C != 3) || n < 1 || ((uintptr_t)dev_pix & (fmt.sample_bytes - 1)))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
@@ -125,7 +152,7 @@ static int encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, in
 	// 6.57 -> 6.72 and 16 frames 1.98 -> 2.17 the wrong way)
 	const int K = ctx->opt[DWTX_OPT_ONE_STREAM] || n < 32 * DWTX_ENC_PARTS ? 1 : DWTX_ENC_PARTS;
 	if (K == 1)
-		return encode_part(ctx, dev_pix, W, H, C, n, capacity, dev_out, out_stride, dev_info, nullptr, dev_index);
+		return encode_part(ctx, dev_pix, fmt, W, H, C, n, capacity, dev_out, out_stride, dev_info, nullptr, dev_index);
 	dwtx_ctx *part[DWTX_ENC_PARTS];
 	int rc;
 	for (int k = 0; k < K; ++k)
@@ -133,7 +160,7 @@ static int encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, in
 			return rc;
 	hipEvent_t *lifted = ctx->enc_ev, *done = ctx->enc_ev + DWTX_ENC_PARTS, start = ctx->enc_ev[2 * DWTX_ENC_PARTS];
 	DWTX_HIP(hipEventRecord(start, ctx->stream));   // the pixels are the caller's earlier work on its stream
-	const size_t img_bytes = (size_t)W * H * C;
+	const size_t img_bytes = (size_t)W * H * C * fmt.sample_bytes;
 	rc = DWTX_OK;
 	int queued = 0;
 	for (int k = 0; k < K && !rc; ++k) {
@@ -145,7 +172,7 @@ static int encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, in
 			rc = DWTX_ERR_DEVICE;
 			break;
 		}
-		rc = encode_part(part[k], dev_pix + img_bytes * i0, W, H, C, cnt, capacity, dev_out + out_stride * (size_t)i0, out_stride,
+		rc = encode_part(part[k], dev_pix + img_bytes * i0, fmt, W, H, C, cnt, capacity, dev_out + out_stride * (size_t)i0, out_stride,
 			dev_info + i0, lifted[k], dev_index ? dev_index + i0 : nullptr);
 		if (hipEventRecord(done[k], st) != hipSuccess && !rc)
 			rc = DWTX_ERR_DEVICE;
@@ -160,16 +187,25 @@ static int encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, in
 extern "C" int dwtx_encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int C, int n, long capacity,
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
 {
-	return encode_device(ctx, dev_pix, W, H, C, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
+	return encode_device(ctx, dev_pix, PIX8, W, H, C, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
 }
 
-// streams (device) -> pixels (device).  Image i is written densely (ow*oh*C bytes)
-// at dev_pix + i*pix_stride; its size is widths/heights[info[i].level + 1].
-extern "C" int dwtx_decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
-	const unsigned long long *dev_lens, int W, int H, int C, int n, int levels_max,
-	uint8_t *dev_pix, size_t pix_stride, dwtx_decode_info *host_info)
+extern "C" int dwtx_encode_device16(dwtx_ctx *ctx, const uint16_t *dev_pix, int W, int H, int C, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
 {
-	if (!ctx || !dev_streams || !dev_lens || !dev_pix || !host_info || n < 1)
+	return encode_device(ctx, reinterpret_cast<const uint8_t *>(dev_pix), PixFmt{ 2, 65535 }, W, H, C, n, capacity, dev_out, out_stride, dev_info,
+		ctx ? ctx->enc_index : nullptr);
+}
+
+// streams (device) -> pixels (device).  Image i is written densely (ow*oh*C samples)
+// at dev_pix + i*pix_stride (in samples); its size is widths/heights[info[i].level + 1].
+static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int C, int n, int levels_max,
+	uint8_t *dev_pix, PixFmt fmt, size_t pix_stride, dwtx_decode_info *host_info)
+{
+	if (!ctx || !dev_streams || !dev_lens || !dev_pix || !host_info || n < 1 || ((uintptr_t)dev_pix & (fmt.sample_bytes - 1)))
+		return DWTX_ERR_ARG;
+	if (!dwtx_maxval_ok(fmt.maxval))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
@@ -189,7 +225,8 @@ extern "C" int dwtx_decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, siz
 	dwtx_p16 fine16 = { nullptr, 0u };
 	{
 		const unsigned sq = ctx->opt[DWTX_OPT_NO_SQUARE_TILES] ? 0u : dwtx_square_levels(W, H);
-		if (sq && !ctx->opt[DWTX_OPT_NO_FINE16] && dwtx_gray8_ok(W, H, dev_pix, pix_stride) && (fine16.levels = dwtx_levels16(W, H, sq))) {
+		// (the planes end in the lifting kernels that write 8-bit pixels: not for deep pictures)
+		if (sq && !fmt.deep() && !ctx->opt[DWTX_OPT_NO_FINE16] && dwtx_gray8_ok(W, H, dev_pix, pix_stride) && (fine16.levels = dwtx_levels16(W, H, sq))) {
 			fine16.planes = (int16_t *)dwtx_scratch(ctx, SLOT_CD_F16, sizeof(int16_t) * (size_t)W * H * C * n);
 			if (!fine16.planes)
 				return DWTX_ERR_NOMEM;
@@ -233,15 +270,22 @@ extern "C" int dwtx_decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, siz
 		int r;
 		if ((r = dwtx_reconstruction_ex(ctx, pyr, lin, miss, lo, W, H, C, count, fused, f16)))    // decode.c:257 (the rest of it)
 			return r;
-		if (dwtx_gray8_ok(ow, oh, dev_pix + pix_stride * first, pix_stride))
+		if (fmt.deep() && !ctx->opt[DWTX_OPT_NO_PIXELS16] && dwtx_pixels16_ok(ow, oh, reinterpret_cast<uint16_t *>(dev_pix) + pix_stride * first, pix_stride))
+			return dwtx_inv_pixels16(ctx, reinterpret_cast<uint16_t *>(dev_pix) + pix_stride * first, pix_stride, pyr, ow, oh, C, count, fmt.maxval);   // decode.c:258-264
+		if (!fmt.deep() && dwtx_gray8_ok(ow, oh, dev_pix + pix_stride * first, pix_stride))
 			return dwtx_inv_pixels8(ctx, dev_pix + pix_stride * first, pix_stride, pyr, ow, oh, C, count, &f16);   // decode.c:258-264
 		if ((r = dwtx_transformation_inv(ctx, img, pyr, ow, oh, count * C)))                 // decode.c:258
 			return r;
+		// decode.c:262-264: k images from `planes` into the pixel slots from `slot` on
+		auto egress = [&](int slot, const int *planes, int k) -> int {
+			if (fmt.deep())
+				return dwtx_pixels16_from_planes(ctx, reinterpret_cast<uint16_t *>(dev_pix) + pix_stride * slot, planes, ow, oh, C, k, fmt.maxval);
+			return dwtx_pixels_from_planes(ctx, dev_pix + pix_stride * slot, planes, ow, oh, C, k);
+		};
 		if (count == 1 || (size_t)ow * oh * C == pix_stride)
-			return dwtx_pixels_from_planes(ctx, dev_pix + pix_stride * first, img, ow, oh, C, count);   // decode.c:262-264
+			return egress(first, img, count);
 		for (int i = 0; i < count; ++i)
-			if ((r = dwtx_pixels_from_planes(ctx, dev_pix + pix_stride * (first + i),
-					img + (size_t)ow * oh * C * i, ow, oh, C, 1)))
+			if ((r = egress(first + i, img + (size_t)ow * oh * C * i, 1)))
 				return r;
 		return DWTX_OK;
 	};
@@ -263,6 +307,55 @@ extern "C" int dwtx_decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, siz
 	using Part = decltype(part);
 	return dwtx_decode_planes_ex(ctx, a, b, dev_streams, stream_stride, dev_lens, W, H, C, n, levels_max, host_info,
 		[](void *user, int first, int count, unsigned fused) { return (*(Part *)user)(first, count, fused); }, &part, fine16);
+}
+
+extern "C" int dwtx_decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int C, int n, int levels_max,
+	uint8_t *dev_pix, size_t pix_stride, dwtx_decode_info *host_info)
+{
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, C, n, levels_max, dev_pix, PIX8, pix_stride, host_info);
+}
+
+extern "C" int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int C, int n, int levels_max,
+	uint16_t *dev_pix, size_t pix_stride, int maxval, dwtx_decode_info *host_info)
+{
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, C, n, levels_max, reinterpret_cast<uint8_t *>(dev_pix),
+		PixFmt{ 2, maxval }, pix_stride, host_info);
+}
+
+// The general transforms of deep pixels on their own (include/dwtx.h): what encode_part and `finish` run around the entropy
+// stage for them — the 16-bit ingest / egress kernel and the int32 transform, through a scratch copy of the planes.
+extern "C" int dwtx_transformation_fwd_pixels16(dwtx_ctx *ctx, int32_t *dev_pyr, const uint16_t *dev_pix, int W, int H, int C, int n)
+{
+	if (!ctx || !dev_pyr || !dev_pix || (C != 1 && C != 3) || n < 1)
+		return DWTX_ERR_ARG;
+	DWTX_ENTER(ctx);
+	DWTX_CHECK_DIMS(W, H);
+	if (!ctx->opt[DWTX_OPT_NO_PIXELS16] && dwtx_pixels16_ok(W, H, dev_pix, (size_t)W * H * C))
+		return dwtx_fwd_pixels16(ctx, dev_pyr, dev_pix, W, H, C, n);              // encode.c:155-159 in one pass
+	int *a = (int *)dwtx_scratch(ctx, SLOT_CD_A, sizeof(int) * (size_t)W * H * C * n);
+	if (!a)
+		return DWTX_ERR_NOMEM;
+	if (const int rc = dwtx_planes_from_pixels16(ctx, a, dev_pix, W, H, C, n))   // encode.c:155-156
+		return rc;
+	return dwtx_transformation_fwd(ctx, dev_pyr, a, W, H, n * C);                // encode.c:159
+}
+
+extern "C" int dwtx_transformation_inv_pixels16(dwtx_ctx *ctx, uint16_t *dev_pix, const int32_t *dev_pyr, int W, int H, int C, int n, int maxval)
+{
+	if (!ctx || !dev_pyr || !dev_pix || (C != 1 && C != 3) || n < 1 || !dwtx_maxval_ok(maxval))
+		return DWTX_ERR_ARG;
+	DWTX_ENTER(ctx);
+	DWTX_CHECK_DIMS(W, H);
+	if (!ctx->opt[DWTX_OPT_NO_PIXELS16] && dwtx_pixels16_ok(W, H, dev_pix, (size_t)W * H * C))
+		return dwtx_inv_pixels16(ctx, dev_pix, (size_t)W * H * C, dev_pyr, W, H, C, n, maxval);   // decode.c:258-264 in one pass
+	int *a = (int *)dwtx_scratch(ctx, SLOT_CD_A, sizeof(int) * (size_t)W * H * C * n);
+	if (!a)
+		return DWTX_ERR_NOMEM;
+	if (const int rc = dwtx_transformation_inv(ctx, a, dev_pyr, W, H, n * C))    // decode.c:258
+		return rc;
+	return dwtx_pixels16_from_planes(ctx, dev_pix, a, W, H, C, n, maxval);       // decode.c:262-264
 }
 
 // ---- dwtx_pack_streams: a step's streams as one message (include/dwtx.h) -------------------------------------------
@@ -355,7 +448,7 @@ static int sync_all(dwtx_ctx *ctx)
 	return a == hipSuccess && b == hipSuccess ? DWTX_OK : DWTX_ERR_DEVICE;
 }
 
-extern "C" int dwtx_encode_images(dwtx_ctx *ctx, const uint8_t *pix, int W, int H, int C, int n, long capacity,
+static int encode_images(dwtx_ctx *ctx, const uint8_t *pix, PixFmt fmt, int W, int H, int C, int n, long capacity,
 	uint8_t *out, size_t out_stride, size_t *out_lens, dwtx_stats *stats)
 {
 	if (!ctx || !pix || !out || !out_lens || (out_stride & 7) || n < 1 || (C != 1 && C != 3))
@@ -363,7 +456,7 @@ extern "C" int dwtx_encode_images(dwtx_ctx *ctx, const uint8_t *pix, int W, int 
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
 	const int P = part_size(ctx, W, H, C, n), parts = (n + P - 1) / P;
-	const size_t img_bytes = (size_t)W * H * C;
+	const size_t img_bytes = (size_t)W * H * C * fmt.sample_bytes;
 	int rc = dwtx_need_copy_stream(ctx);
 	if (rc)
 		return rc;
@@ -446,7 +539,7 @@ extern "C" int dwtx_encode_images(dwtx_ctx *ctx, const uint8_t *pix, int W, int 
 			e = hipStreamWaitEvent(ms, ev_in[slot], 0);
 		if (e != hipSuccess)
 			break;
-		rc = encode_device(ctx, dpix + (size_t)slot * P * img_bytes, W, H, C, cnt, capacity,
+		rc = encode_device(ctx, dpix + (size_t)slot * P * img_bytes, fmt, W, H, C, cnt, capacity,
 			dout + out_stride * (size_t)slot * P, out_stride, dinfo + (size_t)slot * P, dix ? dix + (size_t)slot * P : nullptr);
 		if (rc)
 			break;
@@ -471,16 +564,31 @@ extern "C" int dwtx_encode_images(dwtx_ctx *ctx, const uint8_t *pix, int W, int 
 	return rc;
 }
 
+extern "C" int dwtx_encode_images(dwtx_ctx *ctx, const uint8_t *pix, int W, int H, int C, int n, long capacity,
+	uint8_t *out, size_t out_stride, size_t *out_lens, dwtx_stats *stats)
+{
+	return encode_images(ctx, pix, PIX8, W, H, C, n, capacity, out, out_stride, out_lens, stats);
+}
+
+extern "C" int dwtx_encode_images16(dwtx_ctx *ctx, const uint16_t *pix, int W, int H, int C, int n, long capacity,
+	uint8_t *out, size_t out_stride, size_t *out_lens, dwtx_stats *stats)
+{
+	return encode_images(ctx, reinterpret_cast<const uint8_t *>(pix), PixFmt{ 2, 65535 }, W, H, C, n, capacity, out, out_stride, out_lens, stats);
+}
+
 extern "C" int dwtx_decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_stride, const size_t *lens, int n,
 	int pixels_max, uint8_t *pix, size_t pix_stride, int *outW, int *outH, int *outC)
 {
 	return dwtx_decode_images_info(ctx, streams, stream_stride, lens, n, pixels_max, pix, pix_stride, outW, outH, outC, nullptr);
 }
 
-extern "C" int dwtx_decode_images_info(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_stride, const size_t *lens, int n,
-	int pixels_max, uint8_t *pix, size_t pix_stride, int *outW, int *outH, int *outC, dwtx_decode_info *infos)
+// (pix_stride and img_samples count samples; the pixel buffers are addressed in bytes)
+static int decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_stride, const size_t *lens, int n,
+	int pixels_max, uint8_t *pix, PixFmt fmt, size_t pix_stride, int *outW, int *outH, int *outC, dwtx_decode_info *infos)
 {
 	if (!ctx || !streams || !lens || !pix || !outW || !outH || !outC || n < 1 || (stream_stride & 7))
+		return DWTX_ERR_ARG;
+	if (!dwtx_maxval_ok(fmt.maxval))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	// decode.c:142-159: geometry comes from the first stream's header; all streams of a batch share it
@@ -503,12 +611,12 @@ extern "C" int dwtx_decode_images_info(dwtx_ctx *ctx, const uint8_t *streams, si
 			--levels_max;
 	}
 	const int P = part_size(ctx, W, H, C, n), parts = (n + P - 1) / P;
-	const size_t img_bytes = (size_t)W * H * C;
+	const size_t img_samples = (size_t)W * H * C, sb = (size_t)fmt.sample_bytes;
 	int rc = dwtx_need_copy_stream(ctx);
 	if (rc)
 		return rc;
 	uint8_t *dstr = (uint8_t *)dwtx_scratch(ctx, SLOT_CD_IO, 2 * stream_stride * (size_t)P + 64);
-	uint8_t *dpix = (uint8_t *)dwtx_scratch(ctx, SLOT_CD_IO2, 2 * img_bytes * P);
+	uint8_t *dpix = (uint8_t *)dwtx_scratch(ctx, SLOT_CD_IO2, 2 * img_samples * sb * P);
 	unsigned long long *dlens = (unsigned long long *)dwtx_scratch(ctx, SLOT_CD_LENS, 2 * sizeof(unsigned long long) * (size_t)P);
 	unsigned long long *hl = (unsigned long long *)malloc(sizeof(unsigned long long) * (size_t)n);
 	dwtx_decode_info *info = (dwtx_decode_info *)malloc(sizeof(dwtx_decode_info) * (size_t)n);
@@ -549,8 +657,8 @@ extern "C" int dwtx_decode_images_info(dwtx_ctx *ctx, const uint8_t *streams, si
 		if (e != hipSuccess)
 			break;
 		ctx->index_base = (size_t)i0;   // sidecar index entries follow the images (dwtx_ctx_set_index)
-		const int r = dwtx_decode_device(ctx, dstr + stream_stride * (size_t)slot * P, stream_stride, dlens + (size_t)slot * P, W, H, C, cnt,
-			levels_max, dpix + img_bytes * (size_t)slot * P, img_bytes, info + i0);
+		const int r = decode_device(ctx, dstr + stream_stride * (size_t)slot * P, stream_stride, dlens + (size_t)slot * P, W, H, C, cnt,
+			levels_max, dpix + img_samples * sb * (size_t)slot * P, fmt, img_samples, info + i0);
 		ctx->index_base = 0;
 		if (r) {
 			rc = r;
@@ -581,8 +689,8 @@ extern "C" int dwtx_decode_images_info(dwtx_ctx *ctx, const uint8_t *streams, si
 			}
 			outW[i0 + i] = g.widths[lo];
 			outH[i0 + i] = g.heights[lo];
-			e = hipMemcpyAsync(pix + pix_stride * (size_t)(i0 + i), dpix + img_bytes * ((size_t)slot * P + i),
-				(size_t)outW[i0 + i] * outH[i0 + i] * C, hipMemcpyDeviceToHost, cs);
+			e = hipMemcpyAsync(pix + pix_stride * sb * (size_t)(i0 + i), dpix + img_samples * sb * ((size_t)slot * P + i),
+				(size_t)outW[i0 + i] * outH[i0 + i] * C * sb, hipMemcpyDeviceToHost, cs);
 		}
 		if (e == hipSuccess)
 			e = hipEventRecord(ev_out[slot], cs);
@@ -599,4 +707,17 @@ extern "C" int dwtx_decode_images_info(dwtx_ctx *ctx, const uint8_t *streams, si
 		return DWTX_ERR_DEVICE;
 	}
 	return rc;
+}
+
+extern "C" int dwtx_decode_images_info(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_stride, const size_t *lens, int n,
+	int pixels_max, uint8_t *pix, size_t pix_stride, int *outW, int *outH, int *outC, dwtx_decode_info *infos)
+{
+	return decode_images(ctx, streams, stream_stride, lens, n, pixels_max, pix, PIX8, pix_stride, outW, outH, outC, infos);
+}
+
+extern "C" int dwtx_decode_images16(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_stride, const size_t *lens, int n,
+	int pixels_max, uint16_t *pix, size_t pix_stride, int maxval, int *outW, int *outH, int *outC, dwtx_decode_info *infos)
+{
+	return decode_images(ctx, streams, stream_stride, lens, n, pixels_max, reinterpret_cast<uint8_t *>(pix), PixFmt{ 2, maxval }, pix_stride,
+		outW, outH, outC, infos);
 }

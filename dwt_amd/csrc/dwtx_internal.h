@@ -88,6 +88,15 @@ void *dwtx_scratch(dwtx_ctx *ctx, int slot, size_t bytes);
 
 static inline int dwtx_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// the maxval a deep decode is told (include/dwtx.h): what a 16-bit sample can hold
+static inline bool dwtx_maxval_ok(int maxval)
+{
+	if (maxval >= 1 && maxval <= 65535)
+		return true;
+	dwtx_set_error("maxval %d is outside 1..65535", maxval);
+	return false;
+}
+
 // Image sizes: sides of 8..DWTX_MAX_SIDE (above it the reference's own arithmetic overflows, include/dwtx.h), and the
 // kernels' int indices want one plane (W*H) below 2^31 — which 32768 x 32768 = 2^30 always is; the check stays for
 // whoever raises DWTX_MAX_SIDE (the reference itself indexes with int, encode.c:40 `channels*(width*y+x)`).
@@ -146,6 +155,12 @@ template <class F> char *carve(dwtx_ctx *ctx, int slot, F &&fn)
 bool dwtx_gray8_ok(int W, int H, const void *pix, size_t image_stride);
 // lift.hip: asks for the scratch planes every lifting call of a W*H transform over nplanes planes asks for
 int dwtx_lift_scratch(dwtx_ctx *ctx, int W, int H, int nplanes);
+// lift.hip: the same for deep pixels (uint16_t samples, include/dwtx.h): W % 4 == 0, more than 64 pixels on a side, the
+// picture 8-byte aligned and image_stride (in samples) a multiple of 4.  int32 arithmetic and int32 bands; no histograms
+// ride along (lift.hip hist_add) and no 16-bit ring planes — both bounds are for 8-bit sources.
+bool dwtx_pixels16_ok(int W, int H, const void *pix, size_t image_stride);
+int dwtx_fwd_pixels16(dwtx_ctx *ctx, int32_t *out, const uint16_t *pix, int W, int H, int C, int n);
+int dwtx_inv_pixels16(dwtx_ctx *ctx, uint16_t *pix, size_t image_stride, const int32_t *in, int W, int H, int C, int n, int maxval);
 struct dwtx_p16;
 int dwtx_inv_pixels8(dwtx_ctx *ctx, uint8_t *pix, size_t image_stride, const int32_t *in, int W, int H, int C, int n, const dwtx_p16 *p16 = nullptr);   // C = 3: image.h:39-50 fused too
 

@@ -43,6 +43,7 @@ struct LevelArgs {
 	short *det16;          // or null: this level's detail bands live here as 16-bit values (same positions, pitch and plane stride as det)
 	const short *src16;    // forward, or null: the input band as 16-bit values (pitch and plane stride of src)
 	short *ll16;           // forward, or null: the LL band goes out as 16-bit values (pitch and plane stride of ll)
+	int maxval;            // deep pixels (uint16_t samples behind src8 / dst8, strides in samples): the inverse's clamps; 0 = 8-bit pixels
 };
 
 // ---------------------------------------------------------------- forward ---
@@ -286,8 +287,9 @@ __device__ __forceinline__ void hist_add(HistAcc &h, int v)
 {
 	const unsigned a = (unsigned)(v < 0 ? -v : v);
 	h.mx |= a;
-	// (a magnitude of 2^15 and more counts as 15 bits here: its plane has more than 16 bit planes — mx says so — and
-	// is refused before any of these counts is used)
+	// (a magnitude of 2^15 and more counts as 15 bits here.  Magnitudes in [2^15, 2^16) are 16 bit planes, which the
+	// coder accepts (k_plan in pack.hip refuses pmax > 16), and would be miscounted: these accumulators are for transforms
+	// of 8-bit pixels, whose coefficients stay below 2^12 — a transform of deep pixels leaves every histogram to k_hist)
 	const unsigned t = min(32u - (unsigned)__clz((int)a), 15u);
 	h.R += 0x1111111111111111ull << (4u * t);
 }
@@ -547,20 +549,6 @@ __device__ __forceinline__ void st2(short *p, I2 v)
 	*reinterpret_cast<unsigned *>(p) = ((unsigned)v.a & 0xffffu) | ((unsigned)v.b << 16);
 }
 
-// the band a forward level reads, as the kernel variant sees it
-template <bool P16>
-struct SrcBand {
-	typedef const int *ptr;
-	typedef FwdRawI raw;
-	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane) { return a.src + plane * a.src_ps; }
-};
-template <>
-struct SrcBand<true> {
-	typedef const short *ptr;
-	typedef FwdRawS raw;
-	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane) { return a.src16 + plane * a.src_ps; }
-};
-
 __device__ __forceinline__ FwdRaw hold(const FwdRawI &r)
 {
 	FwdRaw o;
@@ -569,6 +557,138 @@ __device__ __forceinline__ FwdRaw hold(const FwdRawI &r)
 	o.left = make_int2(o.xr, hold(r.e.y));
 	return o;
 }
+
+// Deep pixels (uint16_t samples, include/dwtx.h) as the finest level's source.  Gray: the row is loaded like a 16-bit
+// band — a lane's quad is 8 bytes — and widened without a sign (pnm.h:69-74).
+struct FwdRawU {
+	uint2 x;          // x[4q .. 4q+3]
+	unsigned e;       // lane 0: x[4q-2], x[4q-1]; the other lanes: its low half = x[4q+4]
+};
+__device__ __forceinline__ FwdRaw widen(const FwdRawU &r)
+{
+	FwdRaw o;
+	o.x = make_int4((int)(r.x.x & 0xffffu), (int)(r.x.x >> 16), (int)(r.x.y & 0xffffu), (int)(r.x.y >> 16));
+	o.xr = (int)(r.e & 0xffffu);
+	o.left = make_int2(o.xr, (int)(r.e >> 16));
+	return o;
+}
+// Interleaved RGB16: a lane's four pixels are 24 bytes (three 8-byte loads; rows of W % 4 == 0 pixels are multiples of
+// 24 bytes, so they stay 8-byte aligned), the neighbours' pixels three words: lane 0 pixels 4q-2 and 4q-1, the other lanes
+// pixel 4q+4 in the first three samples.  Every plane's launch takes its own channel of image.h:52-65 when the row is used.
+struct FwdRawRgb16 {
+	uint2 a, b, c;
+	unsigned e0, e1, e2;
+};
+__device__ __forceinline__ int ycocg_ch(int r, int g, int b, int ch)   // image.h:52-65, channel ch (uniform)
+{
+	const int co = r - b;
+	if (ch == 1)
+		return co;
+	const int t = b + tdiv2(co);
+	const int cg = g - t;
+	return ch == 2 ? cg : t + tdiv2(cg);
+}
+__device__ __forceinline__ FwdRaw widen(const FwdRawRgb16 &r, int ch)
+{
+	auto lo = [](unsigned w) { return (int)(w & 0xffffu); };
+	auto hi = [](unsigned w) { return (int)(w >> 16); };
+	FwdRaw o;
+	o.x.x = ycocg_ch(lo(r.a.x), hi(r.a.x), lo(r.a.y), ch);
+	o.x.y = ycocg_ch(hi(r.a.y), lo(r.b.x), hi(r.b.x), ch);
+	o.x.z = ycocg_ch(lo(r.b.y), hi(r.b.y), lo(r.c.x), ch);
+	o.x.w = ycocg_ch(hi(r.c.x), lo(r.c.y), hi(r.c.y), ch);
+	o.xr = ycocg_ch(lo(r.e0), hi(r.e0), lo(r.e1), ch);
+	o.left = make_int2(o.xr, ycocg_ch(hi(r.e1), lo(r.e2), hi(r.e2), ch));
+	return o;
+}
+
+// the band a forward level reads, as the kernel variant sees it: int32 planes, 16-bit planes (dwtx_p16: the detail bands
+// go out as 16-bit values too), or — the finest level of a deep picture — uint16_t pixels, gray or interleaved RGB
+enum { SRC_I32 = 0, SRC_I16 = 1, SRC_U16 = 2, SRC_RGB16 = 3 };
+template <int SRC>
+struct SrcBand {
+	typedef const int *ptr;
+	typedef FwdRawI raw;
+	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &) { return a.src + plane * a.src_ps; }
+	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads) { return lane_at_i(q, lane, nquads); }
+	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at) { return fwd_load_i(row, at); }
+	static __device__ __forceinline__ FwdRaw wide(const raw &r, int) { return widen(r); }
+	static __device__ __forceinline__ FwdRaw held(const raw &r, int) { return hold(r); }
+};
+template <>
+struct SrcBand<SRC_I16> {
+	typedef const short *ptr;
+	typedef FwdRawS raw;
+	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &) { return a.src16 + plane * a.src_ps; }
+	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads) { return lane_at_i(q, lane, nquads); }
+	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at) { return fwd_load_i(row, at); }
+	static __device__ __forceinline__ FwdRaw wide(const raw &r, int) { return widen(r); }
+	static __device__ __forceinline__ FwdRaw held(const raw &r, int) { return hold(r); }
+};
+template <>
+struct SrcBand<SRC_U16> {
+	typedef const uint16_t *ptr;
+	typedef FwdRawU raw;
+	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &) { return reinterpret_cast<const uint16_t *>(a.src8) + plane * a.src_ps; }
+	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads) { return lane_at_i(q, lane, nquads); }
+	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at)
+	{
+		raw r;
+		r.x = *reinterpret_cast<const uint2 *>(row + at.main);
+		r.e = *reinterpret_cast<const unsigned *>(row + at.edge);
+		return r;
+	}
+	static __device__ __forceinline__ FwdRaw wide(const raw &r, int) { return widen(r); }
+	static __device__ __forceinline__ FwdRaw held(const raw &r, int)
+	{
+		raw h;
+		h.x = make_uint2(hold(r.x.x), hold(r.x.y));
+		h.e = hold(r.e);
+		return widen(h);
+	}
+};
+template <>
+struct SrcBand<SRC_RGB16> {
+	typedef const uint16_t *ptr;
+	typedef FwdRawRgb16 raw;
+	// plane p = channel p % 3 of image p / 3; src_ps = samples per interleaved image, spitch = samples per row
+	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &ch)
+	{
+		ch = (int)(plane % 3);
+		return reinterpret_cast<const uint16_t *>(a.src8) + (plane / 3) * a.src_ps;
+	}
+	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads)
+	{
+		const int qa = min(q, nquads - 1);
+		LaneAtI o = { 12 * qa, lane == 0 ? max(12 * qa - 6, 0) : min(12 * qa + 12, 12 * nquads - 6) };
+		return o;
+	}
+	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at)
+	{
+		raw r;
+		const uint2 *m = reinterpret_cast<const uint2 *>(row + at.main);
+		const unsigned *e = reinterpret_cast<const unsigned *>(row + at.edge);
+		r.a = m[0];
+		r.b = m[1];
+		r.c = m[2];
+		r.e0 = e[0];
+		r.e1 = e[1];
+		r.e2 = e[2];
+		return r;
+	}
+	static __device__ __forceinline__ FwdRaw wide(const raw &r, int ch) { return widen(r, ch); }
+	static __device__ __forceinline__ FwdRaw held(const raw &r, int ch)
+	{
+		raw h;
+		h.a = make_uint2(hold(r.a.x), hold(r.a.y));
+		h.b = make_uint2(hold(r.b.x), hold(r.b.y));
+		h.c = make_uint2(hold(r.c.x), hold(r.c.y));
+		h.e0 = hold(r.e0);
+		h.e1 = hold(r.e1);
+		h.e2 = hold(r.e2);
+		return widen(h, ch);
+	}
+};
 
 // Forward level on int32 planes (every level of dwtx_transformation_fwd; the levels below the finest in the codec).
 // Memory operations retire in order on this part (one counter for loads and stores): a wave that waits for rows it
@@ -581,7 +701,9 @@ __device__ __forceinline__ FwdRaw hold(const FwdRawI &r)
 // low-pass of cdf53.h:9-34 has an l1 norm of 1.5 per direction, the high-pass of 2 — i.e. 26 142 on the fifth level;
 // that bound is loose: the composed five-level response has an l1 norm of 7.95, 2 028 for 8-bit samples, and
 // tests/test_codec_gpu.py builds the picture that gets there); the arithmetic is int32 either way.
-template <bool HIST, bool P16>
+// SRC_U16 / SRC_RGB16: the finest level of a deep picture reads its uint16_t pixels itself (widening and YCoCg-R fused);
+// everything it writes is int32.
+template <bool HIST, int SRC>
 __global__ __launch_bounds__(64 * WAVES) void k_fwd_level_w(LevelArgsW A)
 {
 	const LevelArgs &a = A.a;
@@ -596,7 +718,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_fwd_level_w(LevelArgsW A)
 	const int j1 = min(j0 + a.rpw, a.h2);
 	const int plane = blockIdx.z;
 	const bool valid = q < A.nquads;
-	const typename SrcBand<P16>::ptr src = SrcBand<P16>::of(a, plane);
+	constexpr bool P16 = SRC == SRC_I16;
+	typedef SrcBand<SRC> Band;
+	int ch = 0;   // (the RGB16 source: the plane's channel; uniform)
+	const typename Band::ptr src = Band::of(a, plane, ch);
 	int *ll = a.ll + plane * a.ll_ps;
 	short *ll16 = a.ll16 ? a.ll16 + plane * a.ll_ps : nullptr;   // (uniform)
 	int *det = a.det + plane * a.det_ps;
@@ -604,15 +729,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_fwd_level_w(LevelArgsW A)
 
 	constexpr int S = 2;
 	const int jfirst = j0 > 0 ? j0 - 1 : 0;
-	const LaneAtI at = lane_at_i(q, lane, A.nquads);
+	const LaneAtI at = Band::at(q, lane, A.nquads);
 	I2 l0, h0, pl = { 0, 0 }, ph = { 0, 0 };
-	fwd_lift_w(widen(fwd_load_i(src + (long)(2 * jfirst) * a.spitch, at)), q, lane, A.nquads, l0, h0);
+	fwd_lift_w(Band::wide(Band::load(src + (long)(2 * jfirst) * a.spitch, at), ch), q, lane, A.nquads, l0, h0);
 	auto rowp = [&](int r) { return src + (long)min(r, a.h - 1) * a.spitch; };
 	FwdRaw cur[2 * S];
-	typename SrcBand<P16>::raw nxt[2 * S];
+	typename Band::raw nxt[2 * S];
 #pragma unroll
 	for (int k = 0; k < 2 * S; ++k)
-		nxt[k] = fwd_load_i(rowp(2 * jfirst + 1 + k), at);
+		nxt[k] = Band::load(rowp(2 * jfirst + 1 + k), at);
 	I2 osl[S], osh[S], odl[S], odh[S];   // a batch's results wait here for the next iteration's stores
 	auto store_batch = [&](int jb) {
 #pragma unroll
@@ -643,13 +768,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_fwd_level_w(LevelArgsW A)
 	for (int jb = jfirst; jb < j1; jb += S) {
 #pragma unroll
 		for (int k = 0; k < 2 * S; ++k)
-			cur[k] = hold(nxt[k]);   // the one wait of the iteration: everything outstanding is a batch old
+			cur[k] = Band::held(nxt[k], ch);   // the one wait of the iteration: everything outstanding is a batch old
 		if (jb > jfirst)
 			store_batch(jb - S);
 		if (jb + S < j1) {
 #pragma unroll
 			for (int k = 0; k < 2 * S; ++k)
-				nxt[k] = fwd_load_i(rowp(2 * (jb + S) + 1 + k), at);
+				nxt[k] = Band::load(rowp(2 * (jb + S) + 1 + k), at);
 		}
 #pragma unroll
 		for (int s = 0; s < S; ++s) {
@@ -1408,13 +1533,24 @@ __device__ __forceinline__ Quad4 inv_row_vals(int qd, int nquads, I2 lo, I2 hi)
 template <typename DstT>
 struct OutRow {
 	typedef int4 type;
-	static __device__ __forceinline__ type of(const Quad4 &v) { return make_int4(v.v[0], v.v[1], v.v[2], v.v[3]); }
+	static __device__ __forceinline__ type of(const Quad4 &v, int) { return make_int4(v.v[0], v.v[1], v.v[2], v.v[3]); }
 	static __device__ __forceinline__ void store(int *__restrict__ row, int qd, const type &v) { *reinterpret_cast<int4 *>(row + 4 * qd) = v; }
+};
+// four deep pixels clamped to [0, maxval] (pnm.h:108 with the picture's maxval for 255): 8 bytes per lane
+template <>
+struct OutRow<uint16_t> {
+	typedef uint2 type;
+	static __device__ __forceinline__ type of(const Quad4 &v, int M)
+	{
+		auto c = [M](int x) { return (unsigned)(x < 0 ? 0 : x > M ? M : x); };
+		return make_uint2(c(v.v[0]) | (c(v.v[1]) << 16), c(v.v[2]) | (c(v.v[3]) << 16));
+	}
+	static __device__ __forceinline__ void store(uint16_t *__restrict__ row, int qd, const type &v) { *reinterpret_cast<uint2 *>(row + 4 * qd) = v; }
 };
 template <>
 struct OutRow<uint8_t> {
 	typedef unsigned type;
-	static __device__ __forceinline__ type of(const Quad4 &v)
+	static __device__ __forceinline__ type of(const Quad4 &v, int)
 	{
 		auto c8 = [](int x) { return (unsigned)(x < 0 ? 0 : x > 255 ? 255 : x); };
 		return c8(v.v[0]) | (c8(v.v[1]) << 8) | (c8(v.v[2]) << 16) | (c8(v.v[3]) << 24);
@@ -1428,6 +1564,8 @@ template <>
 __device__ __forceinline__ int *inv_dst<int>(const LevelArgs &a) { return a.ll; }
 template <>
 __device__ __forceinline__ uint8_t *inv_dst<uint8_t>(const LevelArgs &a) { return a.dst8; }
+template <>
+__device__ __forceinline__ uint16_t *inv_dst<uint16_t>(const LevelArgs &a) { return reinterpret_cast<uint16_t *>(a.dst8); }   // (ll_ps, llpitch in samples)
 
 // The vertical state of one plane between row pairs: detail rows dl / dh and even rows el / eh of the current pair.
 struct InvCols {
@@ -1595,8 +1733,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 			RowLH e, o, ex, ox;
 			inv_cols(a, jj, c, cur[s], e, o);
 			inv_cols(a, jj, cx, curx[s], ex, ox);
-			orow[2 * s] = Out::of(inv_row_vals_h(qd, A.nquads, lane, e, ex));
-			orow[2 * s + 1] = Out::of(inv_row_vals_h(qd, A.nquads, lane, o, ox));
+			orow[2 * s] = Out::of(inv_row_vals_h(qd, A.nquads, lane, e, ex), a.maxval);
+			orow[2 * s + 1] = Out::of(inv_row_vals_h(qd, A.nquads, lane, o, ox), a.maxval);
 		}
 	}
 	store_batch(j0 + (j1 - 1 - j0) / S * S);
@@ -1783,8 +1921,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w(Inv2Args a)
 		}
 		const Quad4 ev = inv_row_vals(q, a.nquads, cel, ceh);
 		const Quad4 od = inv_row_vals(q, a.nquads, i2_add2(cdl, cel, nel), i2_add2(cdh, ceh, neh));
-		even = OutRow<DstT>::of(ev);
-		odd = OutRow<DstT>::of(od);
+		even = OutRow<DstT>::of(ev, 0);
+		odd = OutRow<DstT>::of(od, 0);
 		cdl = ndl;
 		cdh = ndh;
 		cel = nel;
@@ -1832,6 +1970,55 @@ __device__ __forceinline__ int clamp_to(int v, int lo, int hi)
 struct Rgb12 {
 	unsigned w[3];   // four pixels
 };
+struct Rgb24 {
+	unsigned w[6];   // four deep pixels
+};
+
+// the same for deep pixels: the clamps at the picture's maxval M
+__device__ __forceinline__ Rgb24 rgb16_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M)
+{
+	unsigned px[12];
+#pragma unroll
+	for (int k = 0; k < 4; ++k) {
+		const int yy = clamp_to(y.v[k], 0, M), c0 = clamp_to(co.v[k], -M, M), c1 = clamp_to(cg.v[k], -M, M);
+		const int t = yy - tdiv2(c1);
+		const int g = c1 + t;
+		const int b = t - tdiv2(c0);
+		const int r = b + c0;
+		px[3 * k] = (unsigned)clamp_to(r, 0, M);
+		px[3 * k + 1] = (unsigned)clamp_to(g, 0, M);
+		px[3 * k + 2] = (unsigned)clamp_to(b, 0, M);
+	}
+	Rgb24 o;
+#pragma unroll
+	for (int k = 0; k < 6; ++k)
+		o.w[k] = px[2 * k] | (px[2 * k + 1] << 16);
+	return o;
+}
+
+// what the RGB kernel's lanes write per row: twelve bytes of 8-bit pixels, or twenty-four of deep ones
+template <typename PixT>
+struct RgbOut {
+	typedef Rgb12 row;
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int);
+	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v)
+	{
+		U32x3 x = { v.w[0], v.w[1], v.w[2] };
+		*reinterpret_cast<U32x3 *>(dst + r * pitch + 12 * qd) = x;
+	}
+};
+template <>
+struct RgbOut<uint16_t> {
+	typedef Rgb24 row;
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M) { return rgb16_of(y, co, cg, M); }
+	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v)   // (pitch in samples; rows and quads are multiples of 8 bytes)
+	{
+		uint2 *p = reinterpret_cast<uint2 *>(reinterpret_cast<uint16_t *>(dst) + r * pitch + 12 * qd);
+		p[0] = make_uint2(v.w[0], v.w[1]);
+		p[1] = make_uint2(v.w[2], v.w[3]);
+		p[2] = make_uint2(v.w[4], v.w[5]);
+	}
+};
 
 __device__ __forceinline__ Rgb12 rgb_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg)
 {
@@ -1854,7 +2041,11 @@ __device__ __forceinline__ Rgb12 rgb_of(const Quad4 &y, const Quad4 &co, const Q
 	return o;
 }
 
-template <bool F16>
+template <typename PixT>
+__device__ __forceinline__ typename RgbOut<PixT>::row RgbOut<PixT>::of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgb_of(y, co, cg); }
+
+// PixT = uint16_t: deep pixels (dst8 points to uint16_t samples, ll_ps / llpitch count samples, clamps at a.maxval)
+template <bool F16, typename PixT = uint8_t>
 __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 {
 	const LevelArgs &a = A.a;
@@ -1877,7 +2068,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 		llp[ch] = a.src + (long)(3 * image + ch) * a.src_ps;
 		det[ch] = DetPtr<F16>::of(a, 3 * image + ch);
 	}
-	uint8_t *dst = a.dst8 + image * a.ll_ps;
+	typedef RgbOut<PixT> Out;
+	uint8_t *dst = a.dst8 + image * a.ll_ps * (long)sizeof(PixT);
 	const InvAt at = inv_at(a, qd, A.nquads);
 
 	// (one row pair per batch: three planes' worth of arithmetic lies between two waits as it is)
@@ -1888,13 +2080,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 		c[ch] = inv_first(a, j0, inv_load_w(a, llp[ch], det[ch], j0 > 0 ? j0 - 1 : 0, at), inv_load_w(a, llp[ch], det[ch], j0, at));
 		nxt[ch] = inv_load_w(a, llp[ch], det[ch], j0 + 1, at);
 	}
-	Rgb12 orow[2];
+	typename Out::row orow[2];
 	auto store_pair = [&](int j) {
-		if (writes) {   // twelve bytes per lane in one store: the wave's 56 lanes write 672 consecutive bytes
-			U32x3 v0 = { orow[0].w[0], orow[0].w[1], orow[0].w[2] }, v1 = { orow[1].w[0], orow[1].w[1], orow[1].w[2] };
-			*reinterpret_cast<U32x3 *>(dst + (long)(2 * j) * a.llpitch + 12 * qd) = v0;
+		if (writes) {   // twelve bytes per lane in one store: the wave's 56 lanes write 672 consecutive bytes (deep pixels: twice that)
+			Out::store(dst, a.llpitch, 2 * j, qd, orow[0]);
 			if (2 * j + 1 < a.h)
-				*reinterpret_cast<U32x3 *>(dst + (long)(2 * j + 1) * a.llpitch + 12 * qd) = v1;
+				Out::store(dst, a.llpitch, 2 * j + 1, qd, orow[1]);
 		}
 	};
 	for (int jj = j0; jj < j1; ++jj) {
@@ -1912,8 +2103,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 #pragma unroll
 		for (int ch = 0; ch < 3; ++ch)
 			inv_pair(a, jj, qd, A.nquads, c[ch], cur[ch], even[ch], odd[ch]);
-		orow[0] = rgb_of(even[0], even[1], even[2]);
-		orow[1] = rgb_of(odd[0], odd[1], odd[2]);
+		orow[0] = Out::of(even[0], even[1], even[2], a.maxval);
+		orow[1] = Out::of(odd[0], odd[1], odd[2], a.maxval);
 	}
 	store_pair(j1 - 1);
 }
@@ -2201,8 +2392,10 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_inv_tail(TailArgs t)
 
 // ------------------------------------------------------- pixels <-> planes ---
 
-// pnm.h:69-74 (byte -> int) fused with image.h:52-65 rgb2ycocg.
-__global__ __launch_bounds__(256) void k_planes_from_pixels(int *__restrict__ planes, const uint8_t *__restrict__ pix,
+// pnm.h:69-74 (byte -> int) fused with image.h:52-65 rgb2ycocg.  P = uint8_t, or uint16_t for deep pixels (the same
+// arithmetic: nothing in it knows the depth).
+template <class P>
+__global__ __launch_bounds__(256) void k_planes_from_pixels(int *__restrict__ planes, const P *__restrict__ pix,
 	long npix_per_image, int C, long total_pixels)
 {
 	long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2229,9 +2422,11 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi)
 	return v < lo ? lo : v > hi ? hi : v;
 }
 
-// image.h:39-50 ycocg2rgb (input clamps included) + pnm.h:108 output clamp.
-__global__ __launch_bounds__(256) void k_pixels_from_planes(uint8_t *__restrict__ pix, const int *__restrict__ planes,
-	long npix_per_image, int C, long total_pixels)
+// image.h:39-50 ycocg2rgb (input clamps included) + pnm.h:108 output clamp, with M (the pixels' maxval) where the
+// reference has 255: Y and the output to [0, M], Co and Cg to [-M, M].  P = uint8_t (M = 255) or uint16_t.
+template <class P>
+__global__ __launch_bounds__(256) void k_pixels_from_planes(P *__restrict__ pix, const int *__restrict__ planes,
+	long npix_per_image, int C, long total_pixels, int M)
 {
 	long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
 	const long stride = (long)gridDim.x * blockDim.x;
@@ -2239,18 +2434,18 @@ __global__ __launch_bounds__(256) void k_pixels_from_planes(uint8_t *__restrict_
 		const long img = i / npix_per_image, off = i - img * npix_per_image;
 		const int *src = planes + img * C * npix_per_image + off;
 		if (C == 1) {
-			pix[i] = (uint8_t)clampi(src[0], 0, 255);
+			pix[i] = (P)clampi(src[0], 0, M);
 		} else {
-			const int y = clampi(src[0], 0, 255);
-			const int co = clampi(src[npix_per_image], -255, 255);
-			const int cg = clampi(src[2 * npix_per_image], -255, 255);
+			const int y = clampi(src[0], 0, M);
+			const int co = clampi(src[npix_per_image], -M, M);
+			const int cg = clampi(src[2 * npix_per_image], -M, M);
 			const int t = y - tdiv2(cg);
 			const int g = cg + t;
 			const int b = t - tdiv2(co);
 			const int r = b + co;
-			pix[3 * i] = (uint8_t)clampi(r, 0, 255);
-			pix[3 * i + 1] = (uint8_t)clampi(g, 0, 255);
-			pix[3 * i + 2] = (uint8_t)clampi(b, 0, 255);
+			pix[3 * i] = (P)clampi(r, 0, M);
+			pix[3 * i + 1] = (P)clampi(g, 0, M);
+			pix[3 * i + 2] = (P)clampi(b, 0, M);
 		}
 	}
 }
@@ -2343,7 +2538,19 @@ extern "C" int dwtx_planes_from_pixels(dwtx_ctx *ctx, int32_t *planes, const uin
 	DWTX_ENTER(ctx);
 	const long npix = (long)W * H, total = npix * n;
 	const int blocks = (int)min((total + 255) / 256, (long)256 * 16);
-	hipLaunchKernelGGL(k_planes_from_pixels, dim3(blocks), dim3(256), 0, ctx->stream, planes, pix, npix, C, total);
+	hipLaunchKernelGGL(k_planes_from_pixels<uint8_t>, dim3(blocks), dim3(256), 0, ctx->stream, planes, pix, npix, C, total);
+	DWTX_LAUNCH_CHECK();
+	return DWTX_OK;
+}
+
+extern "C" int dwtx_planes_from_pixels16(dwtx_ctx *ctx, int32_t *planes, const uint16_t *pix, int W, int H, int C, int n)
+{
+	if (!ctx || !planes || !pix || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || ((uintptr_t)pix & 1))
+		return DWTX_ERR_ARG;
+	DWTX_ENTER(ctx);
+	const long npix = (long)W * H, total = npix * n;
+	const int blocks = (int)min((total + 255) / 256, (long)256 * 16);
+	hipLaunchKernelGGL(k_planes_from_pixels<uint16_t>, dim3(blocks), dim3(256), 0, ctx->stream, planes, pix, npix, C, total);
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
@@ -2355,7 +2562,21 @@ extern "C" int dwtx_pixels_from_planes(dwtx_ctx *ctx, uint8_t *pix, const int32_
 	DWTX_ENTER(ctx);
 	const long npix = (long)W * H, total = npix * n;
 	const int blocks = (int)min((total + 255) / 256, (long)256 * 16);
-	hipLaunchKernelGGL(k_pixels_from_planes, dim3(blocks), dim3(256), 0, ctx->stream, pix, planes, npix, C, total);
+	hipLaunchKernelGGL(k_pixels_from_planes<uint8_t>, dim3(blocks), dim3(256), 0, ctx->stream, pix, planes, npix, C, total, 255);
+	DWTX_LAUNCH_CHECK();
+	return DWTX_OK;
+}
+
+extern "C" int dwtx_pixels16_from_planes(dwtx_ctx *ctx, uint16_t *pix, const int32_t *planes, int W, int H, int C, int n, int maxval)
+{
+	if (!ctx || !planes || !pix || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || ((uintptr_t)pix & 1))
+		return DWTX_ERR_ARG;
+	if (!dwtx_maxval_ok(maxval))
+		return DWTX_ERR_ARG;
+	DWTX_ENTER(ctx);
+	const long npix = (long)W * H, total = npix * n;
+	const int blocks = (int)min((total + 255) / 256, (long)256 * 16);
+	hipLaunchKernelGGL(k_pixels_from_planes<uint16_t>, dim3(blocks), dim3(256), 0, ctx->stream, pix, planes, npix, C, total, maxval);
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
@@ -2403,20 +2624,23 @@ static WideKernel fwd_wide_kernel(bool hist, int channels8, bool src16)
 			return k_fwd_pixels_w<Rgb8, true>;
 		if (channels8)
 			return k_fwd_pixels_w<uint8_t, true>;
-		return src16 ? k_fwd_level_w<true, true> : k_fwd_level_w<true, false>;
+		return src16 ? k_fwd_level_w<true, SRC_I16> : k_fwd_level_w<true, SRC_I32>;
 	}
 	if (channels8 == 3)
 		return k_fwd_pixels_w<Rgb8, false>;
 	if (channels8)
 		return k_fwd_pixels_w<uint8_t, false>;
-	return src16 ? k_fwd_level_w<false, true> : k_fwd_level_w<false, false>;
+	return src16 ? k_fwd_level_w<false, SRC_I16> : k_fwd_level_w<false, SRC_I32>;
 }
 
 // in8 != nullptr: the source is 8-bit pixels, gray (in8_channels 1: plane p = image p) or interleaved RGB
-// (in8_channels 3: plane p = channel p%3 of image p/3 after YCoCg-R); needs a finest level the wide kernel takes
+// (in8_channels 3: plane p = channel p%3 of image p/3 after YCoCg-R); needs a finest level the wide kernel takes.
+// deep: in8 points to uint16_t samples instead (no histograms, no 16-bit bands: their bounds are for 8-bit sources)
 static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_t *in8, int in8_channels, int W, int H, int nplanes,
-	const dwtx_hist_sink *sink = nullptr, unsigned *hist_levels = nullptr, dwtx_p16 p16 = dwtx_p16{ nullptr, 0u })
+	const dwtx_hist_sink *sink = nullptr, unsigned *hist_levels = nullptr, dwtx_p16 p16 = dwtx_p16{ nullptr, 0u }, bool deep = false)
 {
+	if (deep && (sink || p16.planes))
+		return DWTX_ERR_ARG;
 	if (hist_levels)
 		*hist_levels = 0u;
 	if (!ctx || !out || (!in && !in8) || W < 2 || H < 2 || nplanes < 1 || nplanes > 65535)
@@ -2519,7 +2743,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 				a.ll16 = reinterpret_cast<short *>(a.ll);
 		}
 		const bool wide = a.w % 4 == 0 && a.spitch % 4 == 0 && a.src_ps % 4 == 0 &&
-			(bytes_in ? aligned_to(a.src8, 4) : aligned_to(a.src, 16)) &&
+			(bytes_in ? aligned_to(a.src8, deep ? 8 : 4) : aligned_to(a.src, 16)) &&
 			a.llpitch % 2 == 0 && a.ll_ps % 2 == 0 && aligned_to(a.ll, 8) &&
 			a.dpitch % 2 == 0 && a.det_ps % 2 == 0 && aligned_to(a.det, 8);
 		if ((bytes_in || a.det16) && !wide)
@@ -2542,8 +2766,13 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 			}
 			const int ch = bytes_in ? in8_channels : 0;
 			const int sx = dwtx_cdiv(strips, 1 << A.wx_log2), gy = dwtx_cdiv(a.h2, (WAVES >> A.wx_log2) * a.rpw);
+			if (bytes_in && deep) {   // (src_ps and spitch count samples; one launch per plane, each taking its channel)
+				const WideKernel deep_kernel = ch == 3 ? k_fwd_level_w<false, SRC_RGB16> : k_fwd_level_w<false, SRC_U16>;
+				hipLaunchKernelGGL(deep_kernel, dim3(sx, gy, nplanes), dim3(64 * WAVES), 0, ctx->stream, A);
+			} else {
 			const dim3 grid = ch == 3 ? dim3(sx * 3, gy, nplanes / 3) : dim3(sx, gy, nplanes);   // (RGB: the three channels of a strip side by side, xcd_strip_rgb)
 			hipLaunchKernelGGL(fwd_wide_kernel(hist_here, ch, a.src16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
+			}
 		} else {
 			const int sx = dwtx_cdiv(a.w2, 64);
 			a.rpw = pick_rpw(sx, a.h2, nplanes);
@@ -2569,6 +2798,12 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 bool dwtx_gray8_ok(int W, int H, const void *pix, size_t image_stride)
 {
 	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && image_stride % 4 == 0 && aligned_to(pix, 4);
+}
+
+// The same for deep pixels (2-byte samples; image_stride in samples): a lane's quad is 8 bytes (gray) or 24 (RGB16)
+bool dwtx_pixels16_ok(int W, int H, const void *pix, size_t image_stride)
+{
+	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && image_stride % 4 == 0 && aligned_to(pix, 8);
 }
 
 unsigned dwtx_levels16(int W, int H, unsigned sq_levels)
@@ -2597,6 +2832,13 @@ int dwtx_fwd_pixels8_hist(dwtx_ctx *ctx, int32_t *out, const uint8_t *pix, int W
 	if (!pix || (C != 1 && C != 3) || !dwtx_gray8_ok(W, H, pix, (size_t)W * H * C))
 		return DWTX_ERR_ARG;
 	return lift_fwd(ctx, out, nullptr, pix, C, W, H, n * C, sink, hist_levels, p16);
+}
+
+int dwtx_fwd_pixels16(dwtx_ctx *ctx, int32_t *out, const uint16_t *pix, int W, int H, int C, int n)
+{
+	if (!pix || (C != 1 && C != 3) || !dwtx_pixels16_ok(W, H, pix, (size_t)W * H * C))
+		return DWTX_ERR_ARG;
+	return lift_fwd(ctx, out, nullptr, reinterpret_cast<const uint8_t *>(pix), C, W, H, n * C, nullptr, nullptr, dwtx_p16{ nullptr, 0u }, true);
 }
 
 int dwtx_transformation_fwd_hist(dwtx_ctx *ctx, int32_t *out, const int32_t *in, int W, int H, int nplanes, const dwtx_hist_sink *sink,
@@ -2631,9 +2873,12 @@ static WideKernel inv_wide_kernel(int channels8, bool det16)
 
 // out8 != nullptr: the finest level writes clamped 8-bit pixels (gray, or interleaved RGB after the
 // inverse colour transform when out8_channels == 3), image i at out8 + i*out8_ps
+// maxval16 > 0: out8 points to deep pixels (uint16_t samples, out8_ps in samples), clamped at that maxval
 static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, int out8_channels, const int32_t *in, int W, int H, int nplanes,
-	const dwtx_p16 *p16 = nullptr)
+	const dwtx_p16 *p16 = nullptr, int maxval16 = 0)
 {
+	if (maxval16 && (!out8 || (p16 && p16->planes)))
+		return DWTX_ERR_ARG;
 	if (!ctx || (!out && !out8) || !in || W < 2 || H < 2 || nplanes < 1 || nplanes > 65535)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
@@ -2771,6 +3016,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 			a.dst8 = out8;
 			a.ll_ps = out8_ps;
 			a.llpitch = out8_channels * W;
+			a.maxval = maxval16;
 		} else if (t == 0) {
 			a.ll = out;
 			a.ll_ps = full_ps;
@@ -2789,7 +3035,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 			a.det16 = p16->planes;
 		}
 		const bool wide = a.w % 4 == 0 && a.llpitch % 4 == 0 && a.ll_ps % 4 == 0 &&
-			(bytes_out ? aligned_to(a.dst8, 4) : aligned_to(a.ll, 16)) &&
+			(bytes_out ? aligned_to(a.dst8, maxval16 ? 8 : 4) : aligned_to(a.ll, 16)) &&
 			a.spitch % 2 == 0 && a.src_ps % 2 == 0 && aligned_to(a.src, 8) &&
 			a.dpitch % 2 == 0 && a.det_ps % 2 == 0 && aligned_to(a.det, 8);
 		if ((bytes_out || a.det16) && !wide)
@@ -2802,7 +3048,11 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 			a.rpw = pick_rpw(sx, a.h2, nplanes);
 			A.a = a;
 			const dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), ch == 3 ? nplanes / 3 : nplanes);
-			hipLaunchKernelGGL(inv_wide_kernel(ch, a.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
+			if (bytes_out && maxval16) {
+				const WideKernel deep_kernel = ch == 3 ? k_inv_level_w_rgb<false, uint16_t> : k_inv_level_w<uint16_t, false>;
+				hipLaunchKernelGGL(deep_kernel, grid, dim3(64 * WAVES), 0, ctx->stream, A);
+			} else
+				hipLaunchKernelGGL(inv_wide_kernel(ch, a.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {
 			const int sx = dwtx_cdiv(a.w2, INV_PAIRS);
 			a.rpw = pick_rpw(sx, a.h2, nplanes);
@@ -2828,4 +3078,11 @@ int dwtx_inv_pixels8(dwtx_ctx *ctx, uint8_t *pix, size_t image_stride, const int
 	if (!pix || W < 2 || H < 2 || (C != 1 && C != 3) || !dwtx_gray8_ok(W, H, pix, image_stride))
 		return DWTX_ERR_ARG;
 	return lift_inv(ctx, nullptr, pix, (long)image_stride, C, in, W, H, n * C, p16);
+}
+
+int dwtx_inv_pixels16(dwtx_ctx *ctx, uint16_t *pix, size_t image_stride, const int32_t *in, int W, int H, int C, int n, int maxval)
+{
+	if (!pix || W < 2 || H < 2 || (C != 1 && C != 3) || maxval < 1 || maxval > 65535 || !dwtx_pixels16_ok(W, H, pix, image_stride))
+		return DWTX_ERR_ARG;
+	return lift_inv(ctx, nullptr, reinterpret_cast<uint8_t *>(pix), (long)image_stride, C, in, W, H, n * C, nullptr, maxval);
 }

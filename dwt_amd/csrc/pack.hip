@@ -626,6 +626,14 @@ __global__ __launch_bounds__(1024) void k_plan(PackGeom g, const int *__restrict
 	int *eb = w.seg_ebase + (long)img * (MAX_SEGS + 1);
 	int *sx = w.segidx + (long)img * 48 * MAX_PLANES;
 	int K = 0, E = 0;
+	if (I.error) {
+		// refused: nothing of it is coded.  The entry, token and refinement tables of an image are sized for MAX_PLANES
+		// planes; the schedule of more would run them over into the next image's (and segidx has no slot for plane 16)
+		eb[0] = 0;
+		I.K = 0;
+		I.E = 0;
+		return;
+	}
 	auto add = [&](int c, int l, int p) {
 		if (K >= MAX_SEGS)
 			return;

@@ -173,6 +173,7 @@ enum dwtx_option {
 	DWTX_OPT_NO_CAPACITY_CUT,      /* encoder: CAPACITY only clips the finished stream (all segments are coded) */
 	DWTX_OPT_NO_FINE16,            /* the finest ring stays in the int32 pyramid (no 16-bit planes for it) */
 	DWTX_OPT_NO_FUSED_LEVELS,      /* transforms on int32 planes: one launch per level (no two-levels-per-pass kernels) */
+	DWTX_OPT_NO_PIXELS16,          /* deep pixels: the finest level never reads / writes the uint16_t pixels itself (widened int32 planes in between) */
 	DWTX_OPT_COUNT
 };
 int dwtx_ctx_set_option(dwtx_ctx *ctx, int option, long value);
@@ -206,6 +207,24 @@ int dwtx_planes_from_pixels(dwtx_ctx *ctx, int32_t *dev_planes, const uint8_t *d
 /* image.h:74-79 rgb_from_ycocg (with its clamps, image.h:41-43) + pnm.h:108 clamp. */
 int dwtx_pixels_from_planes(dwtx_ctx *ctx, uint8_t *dev_pix, const int32_t *dev_planes, int W, int H, int C, int n);
 
+/* ---- deep pixels: samples of more than 8 bits (maxval up to 65535) ---------------------------------------------
+ * The reference reads and writes 8-bit PNM only and calls that temporary (pnm.h:63-64 "only 8 bit per channel SRGB
+ * supported at the moment"); nothing else in its algorithm knows the depth: encode.c:155-221 and decode.c:174-264
+ * work on `int` throughout.  The *16 entry points are the same pipelines with native-endian uint16_t pixels,
+ * interleaved [n][H][W][C] like the bytes, C = 1 or 3; strides of pixel buffers count SAMPLES (uint16_t elements).
+ * The .dwt format is unchanged and records no depth: `maxval` (1..65535, else DWTX_ERR_ARG) is the caller's
+ * knowledge, like the pixel format of a raw buffer.  Only the decoder needs it, for the clamps of image.h:41-43 and
+ * pnm.h:108 with maxval where those have 255 — which only act on streams that were cut short.  With maxval 255 the
+ * results are the 8-bit entry points', widened.  The coder's limit of 16 bit planes stays: a picture whose detail
+ * coefficients need more is refused per image as ever (dwtx_stream_info.error).  Pictures with maxval <= 4095 never
+ * are, gray ones up to 8191 neither; above that it depends on the data. */
+
+/* pnm.h:69-74 widening + image.h:67-72 ycocg_from_rgb (C==3) for 16-bit samples. */
+int dwtx_planes_from_pixels16(dwtx_ctx *ctx, int32_t *dev_planes, const uint16_t *dev_pix, int W, int H, int C, int n);
+/* image.h:74-79 rgb_from_ycocg with the clamps of image.h:41-43 at maxval (Y to [0, maxval], Co and Cg to
+ * [-maxval, maxval]) + pnm.h:108's clamp to [0, maxval]. */
+int dwtx_pixels16_from_planes(dwtx_ctx *ctx, uint16_t *dev_pix, const int32_t *dev_planes, int W, int H, int C, int n, int maxval);
+
 /* encode.c:16-30 transformation(): multi-level forward CDF 5/3 of `nplanes`
  * planar W*H images.  dev_in is preserved; dev_out receives the Mallat pyramid. */
 int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *dev_out, const int32_t *dev_in, int W, int H, int nplanes);
@@ -224,6 +243,14 @@ int dwtx_transformation_fwd_pixels(dwtx_ctx *ctx, int32_t *dev_pyr, int16_t *dev
 	const uint8_t *dev_pix, int W, int H, int C, int n);
 int dwtx_transformation_inv_pixels(dwtx_ctx *ctx, uint8_t *dev_pix, const int32_t *dev_pyr, const int16_t *dev_rings16,
 	unsigned levels16, int W, int H, int C, int n);
+
+/* encode.c:155-159 and decode.c:258-264 for deep pixels, any shape: the two transforms as dwtx_encode_device16 /
+ * dwtx_decode_device16 run them, everything in dev_pyr [n*C][H][W].  Pictures with W % 4 == 0, more than 64 pixels on a
+ * side and 8-byte aligned pixels take the finest level straight from / to the uint16_t pixels (widening, colour transform
+ * and clamps fused into it); every other shape goes through 16-bit ingest / egress kernels and widened int32 planes
+ * (DWTX_OPT_NO_PIXELS16 forces that for all).  Same results either way. */
+int dwtx_transformation_fwd_pixels16(dwtx_ctx *ctx, int32_t *dev_pyr, const uint16_t *dev_pix, int W, int H, int C, int n);
+int dwtx_transformation_inv_pixels16(dwtx_ctx *ctx, uint16_t *dev_pix, const int32_t *dev_pyr, int W, int H, int C, int n, int maxval);
 
 /* encode.c:32-58 linearization(): Mallat pyramid planes [nplanes][H][W] ->
  * Hilbert-linearised planes [nplanes][W*H] (root raster first, then the detail
@@ -272,6 +299,10 @@ int dwtx_decode_planes(dwtx_ctx *ctx, int32_t *dev_lin, const uint8_t *dev_strea
 /* A safe out_stride for unlimited-capacity encodes of W*H*C images (multiple of 8). */
 size_t dwtx_encode_bound(int W, int H, int C);
 
+/* The same for dwtx_encode_device16 / dwtx_encode_images16: the coder's 16 bit planes x 2 bits = 4 bytes per sample,
+ * plus 4096, a multiple of 8 (encode.c:183-221 cannot write more for a picture that is not refused). */
+size_t dwtx_encode_bound16(int W, int H, int C);
+
 /* encode.c:155-221 with everything resident in HBM: 8-bit interleaved pixels
  * [n][H][W][C] -> n streams at dev_out + i*out_stride.  Asynchronous. */
 int dwtx_encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int C, int n, long capacity,
@@ -287,6 +318,16 @@ int dwtx_encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int 
 int dwtx_decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
 	const unsigned long long *dev_lens, int W, int H, int C, int n, int levels_max,
 	uint8_t *dev_pix, size_t pix_stride, dwtx_decode_info *host_info);
+
+/* encode.c:155-221 / decode.c:174-264 for deep pixels, everything resident in HBM: dwtx_encode_device /
+ * dwtx_decode_device in every respect but the samples (pix_stride counts samples; dev_pix 2-byte aligned).  Encoding
+ * takes no maxval: samples are what they are, and a picture that needs more than 16 bit planes gets
+ * dev_info[i].error = 1 while the others of its batch are coded. */
+int dwtx_encode_device16(dwtx_ctx *ctx, const uint16_t *dev_pix, int W, int H, int C, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
+int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int C, int n, int levels_max,
+	uint16_t *dev_pix, size_t pix_stride, int maxval, dwtx_decode_info *host_info);
 
 /* The sender's side of the one exchange step between GPUs (the encoded streams of a step travel to one
  * rank; no reference counterpart — the reference writes one file per process): the n streams of a batch, stream i at
@@ -318,6 +359,14 @@ int dwtx_decode_images(dwtx_ctx *ctx, const uint8_t *host_streams, size_t stream
  * stderr diagnostics (bytes.h:101, rle.h:45). */
 int dwtx_decode_images_info(dwtx_ctx *ctx, const uint8_t *host_streams, size_t stream_stride, const size_t *lens, int n,
 	int pixels_max, uint8_t *host_pix, size_t pix_stride, int *outW, int *outH, int *outC, dwtx_decode_info *infos);
+
+/* encode.c:133-232 / decode.c:136-268 between the PNM and the byte sink for deep pixels: dwtx_encode_images /
+ * dwtx_decode_images_info with 16-bit samples (pix_stride in samples; `infos` may be NULL).  A picture that needs more
+ * than 16 bit planes is DWTX_ERR_ARG ("image %d needs more than 16 bit planes"). */
+int dwtx_encode_images16(dwtx_ctx *ctx, const uint16_t *host_pix, int W, int H, int C, int n, long capacity,
+	uint8_t *host_out, size_t out_stride, size_t *out_lens, dwtx_stats *stats);
+int dwtx_decode_images16(dwtx_ctx *ctx, const uint8_t *host_streams, size_t stream_stride, const size_t *lens, int n,
+	int pixels_max, uint16_t *host_pix, size_t pix_stride, int maxval, int *outW, int *outH, int *outC, dwtx_decode_info *infos);
 
 #ifdef __cplusplus
 }
