@@ -127,23 +127,27 @@ class Context:
 
     # -- stage kernels -------------------------------------------------------
 
-    def planes_from_pixels(self, pix):
-        """uint8 [n,H,W,C] interleaved -> int32 [n*C,H,W] planar (YCoCg-R if C==3)."""
-        torch = self.torch
+    def _planes_from_pixels(self, sym, pix):
         n, H, W, Cn = pix.shape
-        assert pix.dtype == torch.uint8 and pix.is_contiguous() and pix.device == self.device
-        out = torch.empty((n * Cn, H, W), dtype=torch.int32, device=self.device)
-        _check(self.lib.dwtx_planes_from_pixels(self.h, _ptr(out), _ptr(pix), W, H, Cn, n), "dwtx_planes_from_pixels")
+        out = self.torch.empty((n * Cn, H, W), dtype=self.torch.int32, device=self.device)
+        _check(getattr(self.lib, sym)(self.h, _ptr(out), _ptr(pix), W, H, Cn, n), sym)
         return out
 
-    def pixels_from_planes(self, planes, C_):
-        torch = self.torch
+    def _pixels_from_planes(self, sym, dtype, planes, C_, *maxval):
         nC, H, W = planes.shape
         n = nC // C_
-        assert planes.dtype == torch.int32 and planes.is_contiguous()
-        out = torch.empty((n, H, W, C_), dtype=torch.uint8, device=self.device)
-        _check(self.lib.dwtx_pixels_from_planes(self.h, _ptr(out), _ptr(planes), W, H, C_, n), "dwtx_pixels_from_planes")
+        assert planes.dtype == self.torch.int32 and planes.is_contiguous()
+        out = self.torch.empty((n, H, W, C_), dtype=dtype, device=self.device)
+        _check(getattr(self.lib, sym)(self.h, _ptr(out), _ptr(planes), W, H, C_, n, *maxval), sym)
         return out
+
+    def planes_from_pixels(self, pix):
+        """uint8 [n,H,W,C] interleaved -> int32 [n*C,H,W] planar (YCoCg-R if C==3)."""
+        assert pix.dtype == self.torch.uint8 and pix.is_contiguous() and pix.device == self.device
+        return self._planes_from_pixels("dwtx_planes_from_pixels", pix)
+
+    def pixels_from_planes(self, planes, C_):
+        return self._pixels_from_planes("dwtx_pixels_from_planes", self.torch.uint8, planes, C_)
 
     def transformation_fwd(self, planes, out=None):
         """encode.c:16 transformation: int32 [P,H,W] -> Mallat pyramid [P,H,W]."""
@@ -267,31 +271,30 @@ class Context:
 
     # -- whole images (host numpy in/out; what the CLIs do) ---------------------
 
-    def encode(self, pix, capacity=0):
-        """uint8 numpy [n,H,W,C] (or [H,W,C]) -> list of .dwt byte strings, list of Stats."""
+    def _encode(self, sym, dtype, bound, pix, capacity):
         import numpy as np
 
         single = pix.ndim == 3
-        pix = np.ascontiguousarray(pix[None] if single else pix, dtype=np.uint8)
+        pix = np.ascontiguousarray(pix[None] if single else pix, dtype=dtype)
         n, H, W, Cn = pix.shape
-        stride = self.lib.dwtx_encode_bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
+        stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
         out = np.empty((n, stride), dtype=np.uint8)
         lens = (C.c_size_t * n)()
         stats = (Stats * n)()
-        _check(self.lib.dwtx_encode_images(self.h, pix.ctypes.data, W, H, Cn, n, capacity, out.ctypes.data, stride,
-                                           C.cast(lens, C.c_void_p), C.cast(stats, C.c_void_p)), "dwtx_encode_images")
+        _check(getattr(self.lib, sym)(self.h, pix.ctypes.data, W, H, Cn, n, capacity, out.ctypes.data, stride,
+                                      C.cast(lens, C.c_void_p), C.cast(stats, C.c_void_p)), sym)
         streams = [out[i, : lens[i]].tobytes() for i in range(n)]
         return (streams[0], stats[0]) if single else (streams, list(stats))
 
-    def decode(self, streams, pixels_max=-1):
-        """.dwt byte string (or list of same-geometry ones) -> uint8 numpy [h,w,C] (or list); None if unreadable."""
+    def _decode(self, sym, dtype, streams, pixels_max, maxval=None):
+        """maxval None: bytes; else deep pixels, whose symbol takes maxval and (unused here) an array of DecodeInfo."""
         import numpy as np
 
         single = isinstance(streams, (bytes, bytearray))
         lst = [streams] if single else list(streams)
         n = len(lst)
         if len(lst[0]) < 6:
-            raise DwtxError(-3, "dwtx_decode_images (short header)")
+            raise DwtxError(-3, sym + " (short header)")
         W = (lst[0][2] | (lst[0][3] << 8)) + 1
         H = (lst[0][4] | (lst[0][5] << 8)) + 1
         Cn = 3 if lst[0][1:2] == b"6" else 1
@@ -301,31 +304,46 @@ class Context:
             host[i, : len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
         lens = (C.c_size_t * n)(*[len(s) for s in lst])
         pstride = W * H * Cn
-        pix = np.empty((n, pstride), dtype=np.uint8)
+        pix = np.empty((n, pstride), dtype=dtype)
         ow, oh, oc = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        rc = self.lib.dwtx_decode_images(self.h, host.ctypes.data, stride, C.cast(lens, C.c_void_p), n, pixels_max,
-                                         pix.ctypes.data, pstride, ow, oh, oc)
+        sizes = (ow, oh, oc) if maxval is None else (maxval, ow, oh, oc, None)
+        rc = getattr(self.lib, sym)(self.h, host.ctypes.data, stride, C.cast(lens, C.c_void_p), n, pixels_max,
+                                    pix.ctypes.data, pstride, *sizes)
         if rc == -1 and n == 1:   # one unreadable stream is an error code (decode.c exits 1), in a batch it is a missing picture
             return None if single else [None]
-        _check(rc, "dwtx_decode_images")
+        _check(rc, sym)
         outs = [pix[i, : ow[i] * oh[i] * oc[i]].reshape(oh[i], ow[i], oc[i]).copy() if ow[i] else None for i in range(n)]
         return outs[0] if single else outs
 
+    def encode(self, pix, capacity=0):
+        """uint8 numpy [n,H,W,C] (or [H,W,C]) -> list of .dwt byte strings, list of Stats."""
+        import numpy as np
+
+        return self._encode("dwtx_encode_images", np.uint8, self.lib.dwtx_encode_bound, pix, capacity)
+
+    def decode(self, streams, pixels_max=-1):
+        """.dwt byte string (or list of same-geometry ones) -> uint8 numpy [h,w,C] (or list); None if unreadable."""
+        import numpy as np
+
+        return self._decode("dwtx_decode_images", np.uint8, streams, pixels_max)
+
     # -- whole images, device resident (what bench.py times) --------------------
 
-    def encode_device(self, pix, capacity=0, out=None, info=None):
-        """uint8 device tensor [n,H,W,C] -> (streams uint8 [n,stride], info uint8 [n,sizeof(StreamInfo)]) on device; async."""
+    def _encode_device(self, sym, bound, pix, capacity, out, info):
         torch = self.torch
         n, H, W, Cn = pix.shape
-        assert pix.dtype == torch.uint8 and pix.is_contiguous()
-        stride = self.lib.dwtx_encode_bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
+        stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
         if out is None:
             out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         if info is None:
             info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
-        _check(self.lib.dwtx_encode_device(self.h, _ptr(pix), W, H, Cn, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
-               "dwtx_encode_device")
+        _check(getattr(self.lib, sym)(self.h, _ptr(pix), W, H, Cn, n, capacity, _ptr(out), out.shape[1], _ptr(info)), sym)
         return out, info
+
+    def encode_device(self, pix, capacity=0, out=None, info=None):
+        """uint8 device tensor [n,H,W,C] -> (streams uint8 [n,stride], info uint8 [n,sizeof(StreamInfo)]) on device; async."""
+        assert pix.dtype == self.torch.uint8 and pix.is_contiguous()
+        return self._encode_device("dwtx_encode_device", self.lib.dwtx_encode_bound, pix, capacity, out, info)
 
     def stream_lengths(self, info):
         """int64 device tensor of stream byte lengths from the info records of encode_device."""
@@ -344,18 +362,27 @@ class Context:
                                           _ptr(streams), stride, _ptr(lens), n), "dwtx_pack_streams")
         return out
 
-    def decode_device(self, streams, lens, W, H, C_, levels_max=-1, out=None):
-        """device streams [n,stride] + int64 lens -> (uint8 [n, W*H*C] pixels, list of DecodeInfo); syncs once."""
+    def _decode_device(self, sym, dtype, streams, lens, W, H, C_, levels_max, out, maxval=None):
+        """maxval None: bytes, slots of W*H*C samples; else deep pixels, slots of out.shape[1] samples."""
         torch = self.torch
         n, stride = streams.shape
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and stride % 8 == 0
         assert lens.dtype == torch.int64 and lens.numel() == n
         if out is None:
-            out = torch.empty((n, W * H * C_), dtype=torch.uint8, device=self.device)
+            out = torch.empty((n, W * H * C_), dtype=dtype, device=self.device)
+        if maxval is None:
+            slot = (W * H * C_,)
+        else:
+            assert self._is16(out) and out.shape[0] == n
+            slot = (out.shape[1], maxval)
         infos = (DecodeInfo * n)()
-        _check(self.lib.dwtx_decode_device(self.h, _ptr(streams), stride, _ptr(lens), W, H, C_, n, levels_max,
-                                           _ptr(out), W * H * C_, C.cast(infos, C.c_void_p)), "dwtx_decode_device")
+        _check(getattr(self.lib, sym)(self.h, _ptr(streams), stride, _ptr(lens), W, H, C_, n, levels_max,
+                                      _ptr(out), *slot, C.cast(infos, C.c_void_p)), sym)
         return out, list(infos)
+
+    def decode_device(self, streams, lens, W, H, C_, levels_max=-1, out=None):
+        """device streams [n,stride] + int64 lens -> (uint8 [n, W*H*C] pixels, list of DecodeInfo); syncs once."""
+        return self._decode_device("dwtx_decode_device", self.torch.uint8, streams, lens, W, H, C_, levels_max, out)
 
     # -- deep pixels: uint16 samples, maxval up to 65535 (the *16 calls of include/dwtx.h) -----------------------
     # torch's uint16 has few operators on the device, so deep device tensors may be torch.uint16 or torch.int16
@@ -366,22 +393,12 @@ class Context:
 
     def planes_from_pixels16(self, pix):
         """16-bit [n,H,W,C] interleaved device tensor -> int32 [n*C,H,W] planar (YCoCg-R if C==3)."""
-        torch = self.torch
-        n, H, W, Cn = pix.shape
         assert self._is16(pix)
-        out = torch.empty((n * Cn, H, W), dtype=torch.int32, device=self.device)
-        _check(self.lib.dwtx_planes_from_pixels16(self.h, _ptr(out), _ptr(pix), W, H, Cn, n), "dwtx_planes_from_pixels16")
-        return out
+        return self._planes_from_pixels("dwtx_planes_from_pixels16", pix)
 
     def pixels16_from_planes(self, planes, C_, maxval):
         """int32 [n*C,H,W] -> uint16 [n,H,W,C] with the reference's clamps at maxval."""
-        torch = self.torch
-        nC, H, W = planes.shape
-        n = nC // C_
-        assert planes.dtype == torch.int32 and planes.is_contiguous()
-        out = torch.empty((n, H, W, C_), dtype=torch.uint16, device=self.device)
-        _check(self.lib.dwtx_pixels16_from_planes(self.h, _ptr(out), _ptr(planes), W, H, C_, n, maxval), "dwtx_pixels16_from_planes")
-        return out
+        return self._pixels_from_planes("dwtx_pixels16_from_planes", self.torch.uint16, planes, C_, maxval)
 
     def transformation_fwd_pixels16(self, pix, out=None):
         """encode.c:155-159 for deep pixels: 16-bit [n,H,W,C] -> int32 pyramid [n*C,H,W]."""
@@ -410,72 +427,21 @@ class Context:
         than 16 bit planes raises DwtxError (rc -3)."""
         import numpy as np
 
-        single = pix.ndim == 3
-        pix = np.ascontiguousarray(pix[None] if single else pix, dtype=np.uint16)
-        n, H, W, Cn = pix.shape
-        stride = self.lib.dwtx_encode_bound16(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
-        out = np.empty((n, stride), dtype=np.uint8)
-        lens = (C.c_size_t * n)()
-        stats = (Stats * n)()
-        _check(self.lib.dwtx_encode_images16(self.h, pix.ctypes.data, W, H, Cn, n, capacity, out.ctypes.data, stride,
-                                             C.cast(lens, C.c_void_p), C.cast(stats, C.c_void_p)), "dwtx_encode_images16")
-        streams = [out[i, : lens[i]].tobytes() for i in range(n)]
-        return (streams[0], stats[0]) if single else (streams, list(stats))
+        return self._encode("dwtx_encode_images16", np.uint16, self.lib.dwtx_encode_bound16, pix, capacity)
 
     def decode16(self, streams, maxval, pixels_max=-1):
         """.dwt byte string (or list of same-geometry ones) -> uint16 numpy [h,w,C] (or list); None if unreadable.
         maxval (1..65535) is what the pictures were encoded from: a .dwt does not record it."""
         import numpy as np
 
-        single = isinstance(streams, (bytes, bytearray))
-        lst = [streams] if single else list(streams)
-        n = len(lst)
-        if len(lst[0]) < 6:
-            raise DwtxError(-3, "dwtx_decode_images16 (short header)")
-        W = (lst[0][2] | (lst[0][3] << 8)) + 1
-        H = (lst[0][4] | (lst[0][5] << 8)) + 1
-        Cn = 3 if lst[0][1:2] == b"6" else 1
-        stride = (max(len(s) for s in lst) + 64 + 7) // 8 * 8
-        host = np.zeros((n, stride), dtype=np.uint8)
-        for i, s in enumerate(lst):
-            host[i, : len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
-        lens = (C.c_size_t * n)(*[len(s) for s in lst])
-        pstride = W * H * Cn
-        pix = np.empty((n, pstride), dtype=np.uint16)
-        ow, oh, oc = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        rc = self.lib.dwtx_decode_images16(self.h, host.ctypes.data, stride, C.cast(lens, C.c_void_p), n, pixels_max,
-                                           pix.ctypes.data, pstride, maxval, ow, oh, oc, None)
-        if rc == -1 and n == 1:   # as decode()
-            return None if single else [None]
-        _check(rc, "dwtx_decode_images16")
-        outs = [pix[i, : ow[i] * oh[i] * oc[i]].reshape(oh[i], ow[i], oc[i]).copy() if ow[i] else None for i in range(n)]
-        return outs[0] if single else outs
+        return self._decode("dwtx_decode_images16", np.uint16, streams, pixels_max, maxval)
 
     def encode_device16(self, pix, capacity=0, out=None, info=None):
         """16-bit device tensor [n,H,W,C] -> (streams uint8 [n,stride], info uint8 [n,sizeof(StreamInfo)]) on device; async."""
-        torch = self.torch
-        n, H, W, Cn = pix.shape
         assert self._is16(pix)
-        stride = self.lib.dwtx_encode_bound16(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
-        if out is None:
-            out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
-        if info is None:
-            info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
-        _check(self.lib.dwtx_encode_device16(self.h, _ptr(pix), W, H, Cn, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
-               "dwtx_encode_device16")
-        return out, info
+        return self._encode_device("dwtx_encode_device16", self.lib.dwtx_encode_bound16, pix, capacity, out, info)
 
     def decode_device16(self, streams, lens, W, H, C_, maxval, levels_max=-1, out=None):
         """device streams [n,stride] + int64 lens -> (uint16 [n, W*H*C] pixels, list of DecodeInfo); syncs once.
         `out`: a 16-bit device tensor [n, pix_stride] with pix_stride (in samples) >= the pictures' size."""
-        torch = self.torch
-        n, stride = streams.shape
-        assert streams.dtype == torch.uint8 and streams.is_contiguous() and stride % 8 == 0
-        assert lens.dtype == torch.int64 and lens.numel() == n
-        if out is None:
-            out = torch.empty((n, W * H * C_), dtype=torch.uint16, device=self.device)
-        assert self._is16(out) and out.shape[0] == n
-        infos = (DecodeInfo * n)()
-        _check(self.lib.dwtx_decode_device16(self.h, _ptr(streams), stride, _ptr(lens), W, H, C_, n, levels_max,
-                                             _ptr(out), out.shape[1], maxval, C.cast(infos, C.c_void_p)), "dwtx_decode_device16")
-        return out, list(infos)
+        return self._decode_device("dwtx_decode_device16", self.torch.uint16, streams, lens, W, H, C_, levels_max, out, maxval)

@@ -6,82 +6,124 @@
 #include <stdlib.h>
 #include <string.h>
 
+static size_t encode_bound(int bytes_per_sample, int W, int H, int C)
+{
+	size_t b = (size_t)bytes_per_sample * W * H * C + 4096;
+	return (b + 7) / 8 * 8;
+}
+
 extern "C" size_t dwtx_encode_bound(int W, int H, int C)
 {
 	// 8-bit sources: at most 12 bit planes per coefficient (the transform's worst gain is 4.54 for gray and 9.07 for the
 	// chroma of YCoCg-R, whose range is twice the pixels': 9.07 * 255 < 2^12; DESIGN.md sections 4.8 and 7), each plane
 	// costs a coefficient at most 2 bits (a raw refinement bit, or a pass-1 symbol: VLI(0) at order 0 is one bit, plus
 	// the sign) -> 3 bytes per sample; uniform noise measures ~9 bit/sample
-	size_t b = (size_t)3 * W * H * C + 4096;
-	return (b + 7) / 8 * 8;
+	return encode_bound(3, W, H, C);
 }
 
 extern "C" size_t dwtx_encode_bound16(int W, int H, int C)
 {
 	// deep sources: the coder's 16 planes x 2 bits = 4 bytes per sample (a picture that needs more is refused)
-	size_t b = (size_t)4 * W * H * C + 4096;
-	return (b + 7) / 8 * 8;
+	return encode_bound(4, W, H, C);
 }
 
-// The pixels a pipeline starts from or ends in: the reference's bytes (sample_bytes 1, maxval 255) or deep pixels
-// (include/dwtx.h: native-endian uint16_t, the maxval the caller names).  Pixel buffers travel as bytes here; strides of
-// deep buffers count samples at the interface and are scaled where addresses are made.
-struct PixFmt {
-	int sample_bytes;
-	int maxval;
-	bool deep() const { return sample_bytes == 2; }
-};
-constexpr PixFmt PIX8 = { 1, 255 };
+// The pixels a pipeline starts from or ends in travel as a dwtx_pixels view (dwtx_internal.h): the reference's bytes or
+// deep pixels, with the channels, the distance between images (in samples) and the maxval the caller names.
+
+// Which ring levels of a W*H transform from / to `px` live in 16-bit planes, and the planes: `own`, or SLOT_CD_F16 of the
+// context for n images.  The finest rings of a transform that starts from 8-bit pixels — the finest ring, three quarters
+// of all coefficients, cannot leave 11 bits then, and lift.hip bounds how many levels stay below 16 (dwtx_levels16) — when
+// the lifting kernels reach the pixels themselves (the planes start / end in those kernels: not for deep pictures), and
+// the coder reads / writes their squares in place (sq: the levels whose squares stay in the pyramid; 0: none wanted).
+static int rings16(dwtx_ctx *ctx, const dwtx_pixels &px, int W, int H, int n, unsigned sq, int16_t *own, dwtx_p16 *f)
+{
+	*f = dwtx_p16{ nullptr, 0u };
+	unsigned levels;
+	if (px.deep() || !sq || !dwtx_pixels_ok(px, W, H) || !(levels = dwtx_levels16(W, H, sq)))
+		return DWTX_OK;
+	int16_t *planes = own ? own : (int16_t *)dwtx_scratch(ctx, SLOT_CD_F16, sizeof(int16_t) * (size_t)W * H * px.channels * n);
+	if (!planes)
+		return DWTX_ERR_NOMEM;
+	*f = dwtx_p16{ planes, levels };
+	return DWTX_OK;
+}
+
+// the int32 planes of n images between the general conversions and the general transforms: `tmp`, or SLOT_CD_A
+static int32_t *planes_between(dwtx_ctx *ctx, int32_t *tmp, int W, int H, int C, int n)
+{
+	return tmp ? tmp : (int32_t *)dwtx_scratch(ctx, SLOT_CD_A, sizeof(int32_t) * (size_t)W * H * C * n);
+}
+
+// pixels -> pyramid (encode.c:155-159): in one pass where the finest level can read the pixels itself (dwtx_pixels_ok;
+// DWTX_OPT_NO_PIXELS16 keeps deep pictures off it), else ingest into planes (`tmp`, or scratch) and the int32 transform.
+// Bytes only: the transform leaves the tiles' magnitude histograms behind where it can (*hist_levels; encode.c:112-131's
+// maximum and everything the entropy stage counts before it codes: the coefficients are not read a second time for them),
+// and the finest rings go to 16-bit planes (*fine16, see rings16: of the levels in sq16, into own16 or scratch).
+// (Not for deep pixels: lift.hip's histogram accumulators hold magnitudes below 2^15, a deep picture's coefficients reach
+// 2^16 — pack.hip's k_hist counts every level then, as it does for dwtx_encode_planes.)
+static int pyramid_from_pixels(dwtx_ctx *ctx, int32_t *pyr, int32_t *tmp, const dwtx_pixels &px, int W, int H, int n, unsigned sq16, int16_t *own16,
+	unsigned *hist_levels, dwtx_p16 *fine16)
+{
+	const int C = px.channels;
+	int rc;
+	dwtx_hist_sink sink;
+	const dwtx_hist_sink *hist = px.deep() ? nullptr : &sink;
+	*hist_levels = 0u;
+	*fine16 = dwtx_p16{ nullptr, 0u };
+	if (hist && (rc = dwtx_hist_begin(ctx, W, H, C, n, &sink)))
+		return rc;
+	if ((rc = rings16(ctx, px, W, H, n, sq16, own16, fine16)))
+		return rc;
+	if (dwtx_pixels_ok(px, W, H) && !(px.deep() && ctx->opt[DWTX_OPT_NO_PIXELS16]))
+		return dwtx_fwd_pixels(ctx, pyr, px, W, H, n, hist, hist_levels, *fine16);             // encode.c:155-159 in one pass
+	if (!(tmp = planes_between(ctx, tmp, W, H, C, n)))
+		return DWTX_ERR_NOMEM;
+	if ((rc = dwtx_pixels_to_planes(ctx, tmp, px, W, H, n)))                                   // encode.c:155-156
+		return rc;
+	return dwtx_transformation_fwd_hist(ctx, pyr, tmp, W, H, n * C, hist, hist_levels);        // encode.c:159
+}
+
+// pyramid -> pixels (decode.c:258-264), image i of the n at px.image(i): in one pass where the finest level can write the
+// pixels itself (as above; f16: rings the decoder left in 16-bit planes), else the int32 transform into planes (`tmp`, or
+// scratch) and egress — image by image where the slots are padded
+static int pixels_from_pyramid(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *pyr, int32_t *tmp, int W, int H, int n, const dwtx_p16 *f16)
+{
+	const int C = px.channels;
+	int rc;
+	if (dwtx_pixels_ok(px, W, H) && !(px.deep() && ctx->opt[DWTX_OPT_NO_PIXELS16]))
+		return dwtx_inv_pixels(ctx, px, pyr, W, H, n, f16);                                    // decode.c:258-264 in one pass
+	if (!(tmp = planes_between(ctx, tmp, W, H, C, n)))
+		return DWTX_ERR_NOMEM;
+	if ((rc = dwtx_transformation_inv(ctx, tmp, pyr, W, H, n * C)))                            // decode.c:258
+		return rc;
+	const size_t samples = (size_t)W * H * C;
+	if (n == 1 || samples == px.image_stride)
+		return dwtx_planes_to_pixels(ctx, px, tmp, W, H, n);                                   // decode.c:262-264
+	for (int i = 0; i < n; ++i)
+		if ((rc = dwtx_planes_to_pixels(ctx, px.image(i), tmp + samples * i, W, H, 1)))
+			return rc;
+	return DWTX_OK;
+}
 
 // pixels (device) -> streams (device) for one part of a batch, on the part's context; `lifted` (optional) is recorded
 // once the part's transform and linearisation are queued
-static int encode_part(dwtx_ctx *ctx, const uint8_t *dev_pix, PixFmt fmt, int W, int H, int C, int n, long capacity,
+static int encode_part(dwtx_ctx *ctx, const dwtx_pixels &px, int W, int H, int n, long capacity,
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, hipEvent_t lifted, dwtx_index *dev_index)
 {
+	const int C = px.channels;
 	const size_t bytes = sizeof(int) * (size_t)W * H * C * n;
 	int *a = (int *)dwtx_scratch(ctx, SLOT_CD_A, bytes);
 	int *b = (int *)dwtx_scratch(ctx, SLOT_CD_B, bytes);
 	if (!a || !b)
 		return DWTX_ERR_NOMEM;
 	int rc;
-	// the forward transform leaves the tiles' magnitude histograms behind where it can (encode.c:112-131's maximum and
-	// everything the entropy stage counts before it codes): the coefficients are not read a second time for them
-	// (not for deep pixels: lift.hip's histogram accumulators hold magnitudes below 2^15, a deep picture's coefficients
-	// reach 2^16 — pack.hip's k_hist counts every level then, as it does for dwtx_encode_planes)
-	dwtx_hist_sink sink;
-	unsigned hist_levels = 0;
-	if (!fmt.deep() && (rc = dwtx_hist_begin(ctx, W, H, C, n, &sink)))
-		return rc;
 	// encode.c:160: levels that are full power-of-two squares stay in the pyramid (the coder reads their tiles there)
 	const unsigned sq = ctx->opt[DWTX_OPT_NO_SQUARE_TILES] ? 0u : dwtx_square_levels(W, H);
-	// The finest rings as 16-bit values in planes of their own when the transform starts from 8-bit pixels — the finest
-	// ring, three quarters of all coefficients, cannot leave 11 bits then, and lift.hip bounds how many levels stay below
-	// 16 (dwtx_levels16) — and the coder reads their squares in place: the transform writes, and the coder reads, half the
-	// bytes for them.
-	dwtx_p16 fine16 = { nullptr, 0u };
-	const bool from_pixels = !fmt.deep() && dwtx_gray8_ok(W, H, dev_pix, (size_t)W * H * C);
-	if (from_pixels && sq && !ctx->opt[DWTX_OPT_NO_FINE16] && (fine16.levels = dwtx_levels16(W, H, sq))) {
-		fine16.planes = (int16_t *)dwtx_scratch(ctx, SLOT_CD_F16, sizeof(int16_t) * (size_t)W * H * C * n);
-		if (!fine16.planes)
-			return DWTX_ERR_NOMEM;
-	}
-	if (from_pixels) {
-		if ((rc = dwtx_fwd_pixels8_hist(ctx, b, dev_pix, W, H, C, n, &sink, &hist_levels, fine16)))   // encode.c:155-159 in one pass
-			return rc;
-	} else if (fmt.deep() && !ctx->opt[DWTX_OPT_NO_PIXELS16] && dwtx_pixels16_ok(W, H, dev_pix, (size_t)W * H * C)) {
-		if ((rc = dwtx_fwd_pixels16(ctx, b, reinterpret_cast<const uint16_t *>(dev_pix), W, H, C, n)))   // encode.c:155-159 in one pass
-			return rc;
-	} else if (fmt.deep()) {
-		if ((rc = dwtx_planes_from_pixels16(ctx, a, reinterpret_cast<const uint16_t *>(dev_pix), W, H, C, n)))   // encode.c:155-156
-			return rc;
-		if ((rc = dwtx_transformation_fwd(ctx, b, a, W, H, n * C)))            // encode.c:159
-			return rc;
-	} else {
-		if ((rc = dwtx_planes_from_pixels(ctx, a, dev_pix, W, H, C, n)))       // encode.c:155-156
-			return rc;
-		if ((rc = dwtx_transformation_fwd_hist(ctx, b, a, W, H, n * C, &sink, &hist_levels)))   // encode.c:159
-			return rc;
-	}
+	// (the finest rings in 16-bit planes: the transform writes, and the coder reads, half the bytes for them)
+	unsigned hist_levels;
+	dwtx_p16 fine16;
+	if ((rc = pyramid_from_pixels(ctx, b, a, px, W, H, n, ctx->opt[DWTX_OPT_NO_FINE16] ? 0u : sq, nullptr, &hist_levels, &fine16)))
+		return rc;
 	if ((rc = dwtx_linearization_ex(ctx, a, b, W, H, n * C, sq, fine16)))
 		return rc;
 	if (lifted)
@@ -90,7 +132,17 @@ static int encode_part(dwtx_ctx *ctx, const uint8_t *dev_pix, PixFmt fmt, int W,
 }
 
 // The pipelines' transforms on their own (include/dwtx.h): what encode_part / dwtx_decode_device's `finish` run around the
-// entropy stage, with the tiles' histograms riding along in the forward direction as they do there.
+// entropy stage, with the tiles' histograms riding along in the forward direction as they do there.  The 8-bit calls are
+// the fused pass and refuse a shape it does not take; the deep calls take every shape, through a scratch copy of the
+// planes (the 16-bit ingest / egress kernel and the int32 transform) where the fused pass does not.
+static bool fused_shape(const dwtx_pixels &px, int W, int H)
+{
+	if (dwtx_pixels_ok(px, W, H))
+		return true;
+	dwtx_set_error("the pixel transforms need W %% 4 == 0, more than 64 pixels on a side and 4-byte aligned pixels (%dx%d)", W, H);
+	return false;
+}
+
 extern "C" int dwtx_transformation_fwd_pixels(dwtx_ctx *ctx, int32_t *dev_pyr, int16_t *dev_rings16, unsigned *levels16,
 	const uint8_t *dev_pix, int W, int H, int C, int n)
 {
@@ -100,22 +152,16 @@ extern "C" int dwtx_transformation_fwd_pixels(dwtx_ctx *ctx, int32_t *dev_pyr, i
 	DWTX_CHECK_DIMS(W, H);
 	if (levels16)
 		*levels16 = 0u;
-	if (!dwtx_gray8_ok(W, H, dev_pix, (size_t)W * H * C)) {
-		dwtx_set_error("the pixel transforms need W %% 4 == 0, more than 64 pixels on a side and 4-byte aligned pixels (%dx%d)", W, H);
+	const dwtx_pixels px = dwtx_pixels8(dev_pix, C, (size_t)W * H * C);
+	if (!fused_shape(px, W, H))
 		return DWTX_ERR_ARG;
-	}
-	int rc;
-	dwtx_hist_sink sink;
-	unsigned hist_levels = 0;
-	if ((rc = dwtx_hist_begin(ctx, W, H, C, n, &sink)))
-		return rc;
-	dwtx_p16 fine16 = { nullptr, 0u };
-	const unsigned sq = dwtx_square_levels(W, H);
-	if (dev_rings16 && sq && (fine16.levels = dwtx_levels16(W, H, sq)))
-		fine16.planes = dev_rings16;
+	unsigned hist_levels;
+	dwtx_p16 fine16;
+	// (the caller's ring planes, if it brought any: asked for by the call, whatever DWTX_OPT_NO_FINE16 says about the pipelines')
+	const int rc = pyramid_from_pixels(ctx, dev_pyr, nullptr, px, W, H, n, dev_rings16 ? dwtx_square_levels(W, H) : 0u, dev_rings16, &hist_levels, &fine16);
 	if (levels16)
-		*levels16 = fine16.planes ? fine16.levels : 0u;
-	return dwtx_fwd_pixels8_hist(ctx, dev_pyr, dev_pix, W, H, C, n, &sink, &hist_levels, fine16);
+		*levels16 = fine16.levels;
+	return rc;
 }
 
 extern "C" int dwtx_transformation_inv_pixels(dwtx_ctx *ctx, uint8_t *dev_pix, const int32_t *dev_pyr, const int16_t *dev_rings16,
@@ -125,14 +171,33 @@ extern "C" int dwtx_transformation_inv_pixels(dwtx_ctx *ctx, uint8_t *dev_pix, c
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
-	if (!dwtx_gray8_ok(W, H, dev_pix, (size_t)W * H * C)) {
-		dwtx_set_error("the pixel transforms need W %% 4 == 0, more than 64 pixels on a side and 4-byte aligned pixels (%dx%d)", W, H);
+	const dwtx_pixels px = dwtx_pixels8(dev_pix, C, (size_t)W * H * C);
+	if (!fused_shape(px, W, H))
 		return DWTX_ERR_ARG;
-	}
 	if (levels16 && levels16 != dwtx_levels16(W, H, dwtx_square_levels(W, H)))
 		return DWTX_ERR_ARG;   // (the mask the forward call reported for this geometry, or none)
 	const dwtx_p16 f16 = { levels16 ? const_cast<int16_t *>(dev_rings16) : nullptr, levels16 };
-	return dwtx_inv_pixels8(ctx, dev_pix, (size_t)W * H * C, dev_pyr, W, H, C, n, &f16);
+	return pixels_from_pyramid(ctx, px, dev_pyr, nullptr, W, H, n, &f16);
+}
+
+extern "C" int dwtx_transformation_fwd_pixels16(dwtx_ctx *ctx, int32_t *dev_pyr, const uint16_t *dev_pix, int W, int H, int C, int n)
+{
+	if (!ctx || !dev_pyr || !dev_pix || (C != 1 && C != 3) || n < 1)
+		return DWTX_ERR_ARG;
+	DWTX_ENTER(ctx);
+	DWTX_CHECK_DIMS(W, H);
+	unsigned hist_levels;
+	dwtx_p16 fine16;
+	return pyramid_from_pixels(ctx, dev_pyr, nullptr, dwtx_pixels16(dev_pix, C, (size_t)W * H * C), W, H, n, 0u, nullptr, &hist_levels, &fine16);
+}
+
+extern "C" int dwtx_transformation_inv_pixels16(dwtx_ctx *ctx, uint16_t *dev_pix, const int32_t *dev_pyr, int W, int H, int C, int n, int maxval)
+{
+	if (!ctx || !dev_pyr || !dev_pix || (C != 1 && C != 3) || n < 1 || !dwtx_maxval_ok(maxval))
+		return DWTX_ERR_ARG;
+	DWTX_ENTER(ctx);
+	DWTX_CHECK_DIMS(W, H);
+	return pixels_from_pyramid(ctx, dwtx_pixels16(dev_pix, C, (size_t)W * H * C, maxval), dev_pyr, nullptr, W, H, n, nullptr);
 }
 
 // pixels (device) -> streams (device); async on the context's stream.
@@ -140,10 +205,11 @@ extern "C" int dwtx_transformation_inv_pixels(dwtx_ctx *ctx, uint8_t *dev_pix, c
 // their own, staggered so that part k's transform runs beside part k-1's entropy stage (the transforms follow one
 // another: each fills the memory system by itself).  The caller's stream waits for all parts.
 // dev_index (device memory, or null): entry i receives the sidecar index of image i (dwtx_ctx_set_encode_index)
-static int encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, PixFmt fmt, int W, int H, int C, int n, long capacity,
+static int encode_device(dwtx_ctx *ctx, const dwtx_pixels &px, int W, int H, int n, long capacity,
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, dwtx_index *dev_index)
 {
-	if (!ctx || !dev_pix || !dev_out || !dev_info || (C != 1 && C != 3) || n < 1 || ((uintptr_t)dev_pix & (fmt.sample_bytes - 1)))
+	const int C = px.channels;
+	if (!ctx || !px.base || !dev_out || !dev_info || (C != 1 && C != 3) || n < 1 || !px.sample_aligned())
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
@@ -152,7 +218,7 @@ static int encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, PixFmt fmt, int 
 	// 6.57 -> 6.72 and 16 frames 1.98 -> 2.17 the wrong way)
 	const int K = ctx->opt[DWTX_OPT_ONE_STREAM] || n < 32 * DWTX_ENC_PARTS ? 1 : DWTX_ENC_PARTS;
 	if (K == 1)
-		return encode_part(ctx, dev_pix, fmt, W, H, C, n, capacity, dev_out, out_stride, dev_info, nullptr, dev_index);
+		return encode_part(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, nullptr, dev_index);
 	dwtx_ctx *part[DWTX_ENC_PARTS];
 	int rc;
 	for (int k = 0; k < K; ++k)
@@ -160,7 +226,6 @@ static int encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, PixFmt fmt, int 
 			return rc;
 	hipEvent_t *lifted = ctx->enc_ev, *done = ctx->enc_ev + DWTX_ENC_PARTS, start = ctx->enc_ev[2 * DWTX_ENC_PARTS];
 	DWTX_HIP(hipEventRecord(start, ctx->stream));   // the pixels are the caller's earlier work on its stream
-	const size_t img_bytes = (size_t)W * H * C * fmt.sample_bytes;
 	rc = DWTX_OK;
 	int queued = 0;
 	for (int k = 0; k < K && !rc; ++k) {
@@ -172,7 +237,7 @@ static int encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, PixFmt fmt, int 
 			rc = DWTX_ERR_DEVICE;
 			break;
 		}
-		rc = encode_part(part[k], dev_pix + img_bytes * i0, fmt, W, H, C, cnt, capacity, dev_out + out_stride * (size_t)i0, out_stride,
+		rc = encode_part(part[k], px.image(i0), W, H, cnt, capacity, dev_out + out_stride * (size_t)i0, out_stride,
 			dev_info + i0, lifted[k], dev_index ? dev_index + i0 : nullptr);
 		if (hipEventRecord(done[k], st) != hipSuccess && !rc)
 			rc = DWTX_ERR_DEVICE;
@@ -187,25 +252,24 @@ static int encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, PixFmt fmt, int 
 extern "C" int dwtx_encode_device(dwtx_ctx *ctx, const uint8_t *dev_pix, int W, int H, int C, int n, long capacity,
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
 {
-	return encode_device(ctx, dev_pix, PIX8, W, H, C, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
+	return encode_device(ctx, dwtx_pixels8(dev_pix, C, (size_t)W * H * C), W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
 }
 
 extern "C" int dwtx_encode_device16(dwtx_ctx *ctx, const uint16_t *dev_pix, int W, int H, int C, int n, long capacity,
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
 {
-	return encode_device(ctx, reinterpret_cast<const uint8_t *>(dev_pix), PixFmt{ 2, 65535 }, W, H, C, n, capacity, dev_out, out_stride, dev_info,
-		ctx ? ctx->enc_index : nullptr);
+	return encode_device(ctx, dwtx_pixels16(dev_pix, C, (size_t)W * H * C), W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
 }
 
 // streams (device) -> pixels (device).  Image i is written densely (ow*oh*C samples)
-// at dev_pix + i*pix_stride (in samples); its size is widths/heights[info[i].level + 1].
+// at px.image(i); its size is widths/heights[info[i].level + 1].
 static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
-	const unsigned long long *dev_lens, int W, int H, int C, int n, int levels_max,
-	uint8_t *dev_pix, PixFmt fmt, size_t pix_stride, dwtx_decode_info *host_info)
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_pixels &px, dwtx_decode_info *host_info)
 {
-	if (!ctx || !dev_streams || !dev_lens || !dev_pix || !host_info || n < 1 || ((uintptr_t)dev_pix & (fmt.sample_bytes - 1)))
+	const int C = px.channels;
+	if (!ctx || !dev_streams || !dev_lens || !px.base || !host_info || n < 1 || !px.sample_aligned())
 		return DWTX_ERR_ARG;
-	if (!dwtx_maxval_ok(fmt.maxval))
+	if (!dwtx_maxval_ok(px.maxval))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
@@ -219,19 +283,13 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 	if (!a || !b)
 		return DWTX_ERR_NOMEM;
 	const size_t plane_ints = (size_t)W * H;
-	// 16-bit planes for the finest ring of whole pictures (see encode_part; the decoder checks the streams' plane counts)
-	// (every ring the 16-byte-per-lane inverse kernels take: what a stream holds is bounded by its plane counts on
-	// every level; the LL bands between the levels are sums of those and stay int32)
-	dwtx_p16 fine16 = { nullptr, 0u };
-	{
-		const unsigned sq = ctx->opt[DWTX_OPT_NO_SQUARE_TILES] ? 0u : dwtx_square_levels(W, H);
-		// (the planes end in the lifting kernels that write 8-bit pixels: not for deep pictures)
-		if (sq && !fmt.deep() && !ctx->opt[DWTX_OPT_NO_FINE16] && dwtx_gray8_ok(W, H, dev_pix, pix_stride) && (fine16.levels = dwtx_levels16(W, H, sq))) {
-			fine16.planes = (int16_t *)dwtx_scratch(ctx, SLOT_CD_F16, sizeof(int16_t) * (size_t)W * H * C * n);
-			if (!fine16.planes)
-				return DWTX_ERR_NOMEM;
-		}
-	}
+	// 16-bit planes for the finest rings of whole pictures (rings16; the decoder checks the streams' plane counts):
+	// every ring the 16-byte-per-lane inverse kernels take: what a stream holds is bounded by its plane counts on
+	// every level; the LL bands between the levels are sums of those and stay int32
+	dwtx_p16 fine16;
+	const unsigned sq = ctx->opt[DWTX_OPT_NO_SQUARE_TILES] ? 0u : dwtx_square_levels(W, H);
+	if ((rc = rings16(ctx, px, W, H, n, ctx->opt[DWTX_OPT_NO_FINE16] ? 0u : sq, nullptr, &fine16)))
+		return rc;
 	// scratch both parts of the batch will ask for, sized once for the larger request (a slot that grows waits for the
 	// stream: `finish` must not grow one in the middle of the pipeline)
 	if (!dwtx_scratch(ctx, SLOT_CD_INFO, sizeof(int) * 48 * (size_t)n))
@@ -243,7 +301,7 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 		const dwtx_decode_info &I = host_info[first];
 		const int lo = I.level + 1;                                          // decode.c:251
 		const int ow = g.widths[lo], oh = g.heights[lo];
-		if ((size_t)ow * oh * C > pix_stride)
+		if ((size_t)ow * oh * C > px.image_stride)
 			return DWTX_ERR_ARG;
 		int *miss = nullptr;
 		bool biased = false;
@@ -267,27 +325,9 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 			f16.levels = fine16.levels;
 		}
 		fused &= ~DWTX_FUSED_FINE16;
-		int r;
-		if ((r = dwtx_reconstruction_ex(ctx, pyr, lin, miss, lo, W, H, C, count, fused, f16)))    // decode.c:257 (the rest of it)
+		if (const int r = dwtx_reconstruction_ex(ctx, pyr, lin, miss, lo, W, H, C, count, fused, f16))    // decode.c:257 (the rest of it)
 			return r;
-		if (fmt.deep() && !ctx->opt[DWTX_OPT_NO_PIXELS16] && dwtx_pixels16_ok(ow, oh, reinterpret_cast<uint16_t *>(dev_pix) + pix_stride * first, pix_stride))
-			return dwtx_inv_pixels16(ctx, reinterpret_cast<uint16_t *>(dev_pix) + pix_stride * first, pix_stride, pyr, ow, oh, C, count, fmt.maxval);   // decode.c:258-264
-		if (!fmt.deep() && dwtx_gray8_ok(ow, oh, dev_pix + pix_stride * first, pix_stride))
-			return dwtx_inv_pixels8(ctx, dev_pix + pix_stride * first, pix_stride, pyr, ow, oh, C, count, &f16);   // decode.c:258-264
-		if ((r = dwtx_transformation_inv(ctx, img, pyr, ow, oh, count * C)))                 // decode.c:258
-			return r;
-		// decode.c:262-264: k images from `planes` into the pixel slots from `slot` on
-		auto egress = [&](int slot, const int *planes, int k) -> int {
-			if (fmt.deep())
-				return dwtx_pixels16_from_planes(ctx, reinterpret_cast<uint16_t *>(dev_pix) + pix_stride * slot, planes, ow, oh, C, k, fmt.maxval);
-			return dwtx_pixels_from_planes(ctx, dev_pix + pix_stride * slot, planes, ow, oh, C, k);
-		};
-		if (count == 1 || (size_t)ow * oh * C == pix_stride)
-			return egress(first, img, count);
-		for (int i = 0; i < count; ++i)
-			if ((r = egress(first + i, img + (size_t)ow * oh * C * i, 1)))
-				return r;
-		return DWTX_OK;
+		return pixels_from_pyramid(ctx, px.image(first), pyr, img, ow, oh, count, &f16);          // decode.c:258-264
 	};
 	// called by the decoder for each part of the batch as soon as its coefficients are on their way
 	auto part = [&](int first, int count, unsigned fused) -> int {
@@ -313,49 +353,14 @@ extern "C" int dwtx_decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, siz
 	const unsigned long long *dev_lens, int W, int H, int C, int n, int levels_max,
 	uint8_t *dev_pix, size_t pix_stride, dwtx_decode_info *host_info)
 {
-	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, C, n, levels_max, dev_pix, PIX8, pix_stride, host_info);
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dwtx_pixels8(dev_pix, C, pix_stride), host_info);
 }
 
 extern "C" int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
 	const unsigned long long *dev_lens, int W, int H, int C, int n, int levels_max,
 	uint16_t *dev_pix, size_t pix_stride, int maxval, dwtx_decode_info *host_info)
 {
-	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, C, n, levels_max, reinterpret_cast<uint8_t *>(dev_pix),
-		PixFmt{ 2, maxval }, pix_stride, host_info);
-}
-
-// The general transforms of deep pixels on their own (include/dwtx.h): what encode_part and `finish` run around the entropy
-// stage for them — the 16-bit ingest / egress kernel and the int32 transform, through a scratch copy of the planes.
-extern "C" int dwtx_transformation_fwd_pixels16(dwtx_ctx *ctx, int32_t *dev_pyr, const uint16_t *dev_pix, int W, int H, int C, int n)
-{
-	if (!ctx || !dev_pyr || !dev_pix || (C != 1 && C != 3) || n < 1)
-		return DWTX_ERR_ARG;
-	DWTX_ENTER(ctx);
-	DWTX_CHECK_DIMS(W, H);
-	if (!ctx->opt[DWTX_OPT_NO_PIXELS16] && dwtx_pixels16_ok(W, H, dev_pix, (size_t)W * H * C))
-		return dwtx_fwd_pixels16(ctx, dev_pyr, dev_pix, W, H, C, n);              // encode.c:155-159 in one pass
-	int *a = (int *)dwtx_scratch(ctx, SLOT_CD_A, sizeof(int) * (size_t)W * H * C * n);
-	if (!a)
-		return DWTX_ERR_NOMEM;
-	if (const int rc = dwtx_planes_from_pixels16(ctx, a, dev_pix, W, H, C, n))   // encode.c:155-156
-		return rc;
-	return dwtx_transformation_fwd(ctx, dev_pyr, a, W, H, n * C);                // encode.c:159
-}
-
-extern "C" int dwtx_transformation_inv_pixels16(dwtx_ctx *ctx, uint16_t *dev_pix, const int32_t *dev_pyr, int W, int H, int C, int n, int maxval)
-{
-	if (!ctx || !dev_pyr || !dev_pix || (C != 1 && C != 3) || n < 1 || !dwtx_maxval_ok(maxval))
-		return DWTX_ERR_ARG;
-	DWTX_ENTER(ctx);
-	DWTX_CHECK_DIMS(W, H);
-	if (!ctx->opt[DWTX_OPT_NO_PIXELS16] && dwtx_pixels16_ok(W, H, dev_pix, (size_t)W * H * C))
-		return dwtx_inv_pixels16(ctx, dev_pix, (size_t)W * H * C, dev_pyr, W, H, C, n, maxval);   // decode.c:258-264 in one pass
-	int *a = (int *)dwtx_scratch(ctx, SLOT_CD_A, sizeof(int) * (size_t)W * H * C * n);
-	if (!a)
-		return DWTX_ERR_NOMEM;
-	if (const int rc = dwtx_transformation_inv(ctx, a, dev_pyr, W, H, n * C))    // decode.c:258
-		return rc;
-	return dwtx_pixels16_from_planes(ctx, dev_pix, a, W, H, C, n, maxval);       // decode.c:262-264
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dwtx_pixels16(dev_pix, C, pix_stride, maxval), host_info);
 }
 
 // ---- dwtx_pack_streams: a step's streams as one message (include/dwtx.h) -------------------------------------------
@@ -448,19 +453,20 @@ static int sync_all(dwtx_ctx *ctx)
 	return a == hipSuccess && b == hipSuccess ? DWTX_OK : DWTX_ERR_DEVICE;
 }
 
-static int encode_images(dwtx_ctx *ctx, const uint8_t *pix, PixFmt fmt, int W, int H, int C, int n, long capacity,
+// host: the caller's pictures (host memory), dense
+static int encode_images(dwtx_ctx *ctx, const dwtx_pixels &host, int W, int H, int n, long capacity,
 	uint8_t *out, size_t out_stride, size_t *out_lens, dwtx_stats *stats)
 {
-	if (!ctx || !pix || !out || !out_lens || (out_stride & 7) || n < 1 || (C != 1 && C != 3))
+	const int C = host.channels;
+	if (!ctx || !host.base || !out || !out_lens || (out_stride & 7) || n < 1 || (C != 1 && C != 3))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
 	const int P = part_size(ctx, W, H, C, n), parts = (n + P - 1) / P;
-	const size_t img_bytes = (size_t)W * H * C * fmt.sample_bytes;
 	int rc = dwtx_need_copy_stream(ctx);
 	if (rc)
 		return rc;
-	uint8_t *dpix = (uint8_t *)dwtx_scratch(ctx, SLOT_CD_IO, 2 * img_bytes * P);
+	const dwtx_pixels stage = host.moved(dwtx_scratch(ctx, SLOT_CD_IO, host.bytes(2 * host.image_stride * P)));   // [2][P] images
 	uint8_t *dout = (uint8_t *)dwtx_scratch(ctx, SLOT_CD_IO2, 2 * out_stride * (size_t)P);
 	dwtx_stream_info *dinfo = (dwtx_stream_info *)dwtx_scratch(ctx, SLOT_CD_LENS, 2 * sizeof(dwtx_stream_info) * (size_t)P);
 	// sidecar indices (dwtx_ctx_set_encode_index; host memory here): a part's records are made on the device, their headers
@@ -473,7 +479,7 @@ static int encode_images(dwtx_ctx *ctx, const uint8_t *pix, PixFmt fmt, int W, i
 	if (hipHostMalloc((void **)&hinfo, hinfo_bytes + (hix ? 2 * ix_head * (size_t)P : 0), hipHostMallocDefault) != hipSuccess)
 		hinfo = nullptr;
 	char *hhead = (char *)hinfo + hinfo_bytes;   // [2][P] index headers
-	if (!dpix || !dout || !dinfo || !hinfo || (hix && !dix)) {
+	if (!stage.base || !dout || !dinfo || !hinfo || (hix && !dix)) {
 		if (hinfo)
 			(void)hipHostFree(hinfo);
 		return DWTX_ERR_NOMEM;
@@ -531,7 +537,7 @@ static int encode_images(dwtx_ctx *ctx, const uint8_t *pix, PixFmt fmt, int W, i
 				e = hipStreamWaitEvent(ms, ev_out[slot], 0); // and its streams have left this output buffer
 		}
 		if (e == hipSuccess)
-			e = hipMemcpyAsync(dpix + (size_t)slot * P * img_bytes, pix + (size_t)i0 * img_bytes, img_bytes * cnt,
+			e = hipMemcpyAsync(stage.image((size_t)slot * P).base, host.image(i0).base, host.bytes(host.image_stride * cnt),
 				hipMemcpyHostToDevice, cs);
 		if (e == hipSuccess)
 			e = hipEventRecord(ev_in[slot], cs);
@@ -539,7 +545,7 @@ static int encode_images(dwtx_ctx *ctx, const uint8_t *pix, PixFmt fmt, int W, i
 			e = hipStreamWaitEvent(ms, ev_in[slot], 0);
 		if (e != hipSuccess)
 			break;
-		rc = encode_device(ctx, dpix + (size_t)slot * P * img_bytes, fmt, W, H, C, cnt, capacity,
+		rc = encode_device(ctx, stage.image((size_t)slot * P), W, H, cnt, capacity,
 			dout + out_stride * (size_t)slot * P, out_stride, dinfo + (size_t)slot * P, dix ? dix + (size_t)slot * P : nullptr);
 		if (rc)
 			break;
@@ -567,13 +573,13 @@ static int encode_images(dwtx_ctx *ctx, const uint8_t *pix, PixFmt fmt, int W, i
 extern "C" int dwtx_encode_images(dwtx_ctx *ctx, const uint8_t *pix, int W, int H, int C, int n, long capacity,
 	uint8_t *out, size_t out_stride, size_t *out_lens, dwtx_stats *stats)
 {
-	return encode_images(ctx, pix, PIX8, W, H, C, n, capacity, out, out_stride, out_lens, stats);
+	return encode_images(ctx, dwtx_pixels8(pix, C, (size_t)W * H * C), W, H, n, capacity, out, out_stride, out_lens, stats);
 }
 
 extern "C" int dwtx_encode_images16(dwtx_ctx *ctx, const uint16_t *pix, int W, int H, int C, int n, long capacity,
 	uint8_t *out, size_t out_stride, size_t *out_lens, dwtx_stats *stats)
 {
-	return encode_images(ctx, reinterpret_cast<const uint8_t *>(pix), PixFmt{ 2, 65535 }, W, H, C, n, capacity, out, out_stride, out_lens, stats);
+	return encode_images(ctx, dwtx_pixels16(pix, C, (size_t)W * H * C), W, H, n, capacity, out, out_stride, out_lens, stats);
 }
 
 extern "C" int dwtx_decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_stride, const size_t *lens, int n,
@@ -582,13 +588,13 @@ extern "C" int dwtx_decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t 
 	return dwtx_decode_images_info(ctx, streams, stream_stride, lens, n, pixels_max, pix, pix_stride, outW, outH, outC, nullptr);
 }
 
-// (pix_stride and img_samples count samples; the pixel buffers are addressed in bytes)
+// host: the caller's pixel slots (host memory); its channels are the streams' and are filled in here
 static int decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_stride, const size_t *lens, int n,
-	int pixels_max, uint8_t *pix, PixFmt fmt, size_t pix_stride, int *outW, int *outH, int *outC, dwtx_decode_info *infos)
+	int pixels_max, dwtx_pixels host, int *outW, int *outH, int *outC, dwtx_decode_info *infos)
 {
-	if (!ctx || !streams || !lens || !pix || !outW || !outH || !outC || n < 1 || (stream_stride & 7))
+	if (!ctx || !streams || !lens || !host.base || !outW || !outH || !outC || n < 1 || (stream_stride & 7))
 		return DWTX_ERR_ARG;
-	if (!dwtx_maxval_ok(fmt.maxval))
+	if (!dwtx_maxval_ok(host.maxval))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	// decode.c:142-159: geometry comes from the first stream's header; all streams of a batch share it
@@ -601,6 +607,7 @@ static int decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_st
 		}
 	const int C = streams[1] == '6' ? 3 : 1;
 	const int W = (streams[2] | (streams[3] << 8)) + 1, H = (streams[4] | (streams[5] << 8)) + 1;
+	host.channels = C;
 	DWTX_CHECK_DIMS(W, H);
 	dwtx_geom g;
 	dwtx_geometry(&g, W, H);
@@ -611,16 +618,17 @@ static int decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_st
 			--levels_max;
 	}
 	const int P = part_size(ctx, W, H, C, n), parts = (n + P - 1) / P;
-	const size_t img_samples = (size_t)W * H * C, sb = (size_t)fmt.sample_bytes;
+	const size_t img_samples = (size_t)W * H * C;
 	int rc = dwtx_need_copy_stream(ctx);
 	if (rc)
 		return rc;
 	uint8_t *dstr = (uint8_t *)dwtx_scratch(ctx, SLOT_CD_IO, 2 * stream_stride * (size_t)P + 64);
-	uint8_t *dpix = (uint8_t *)dwtx_scratch(ctx, SLOT_CD_IO2, 2 * img_samples * sb * P);
+	dwtx_pixels stage = host.moved(dwtx_scratch(ctx, SLOT_CD_IO2, host.bytes(2 * img_samples * P)));   // [2][P] images, dense at full size
+	stage.image_stride = img_samples;
 	unsigned long long *dlens = (unsigned long long *)dwtx_scratch(ctx, SLOT_CD_LENS, 2 * sizeof(unsigned long long) * (size_t)P);
 	unsigned long long *hl = (unsigned long long *)malloc(sizeof(unsigned long long) * (size_t)n);
 	dwtx_decode_info *info = (dwtx_decode_info *)malloc(sizeof(dwtx_decode_info) * (size_t)n);
-	if (!dstr || !dpix || !dlens || !hl || !info) {
+	if (!dstr || !stage.base || !dlens || !hl || !info) {
 		free(hl);
 		free(info);
 		return DWTX_ERR_NOMEM;
@@ -657,8 +665,8 @@ static int decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_st
 		if (e != hipSuccess)
 			break;
 		ctx->index_base = (size_t)i0;   // sidecar index entries follow the images (dwtx_ctx_set_index)
-		const int r = decode_device(ctx, dstr + stream_stride * (size_t)slot * P, stream_stride, dlens + (size_t)slot * P, W, H, C, cnt,
-			levels_max, dpix + img_samples * sb * (size_t)slot * P, fmt, img_samples, info + i0);
+		const int r = decode_device(ctx, dstr + stream_stride * (size_t)slot * P, stream_stride, dlens + (size_t)slot * P, W, H, cnt,
+			levels_max, stage.image((size_t)slot * P), info + i0);
 		ctx->index_base = 0;
 		if (r) {
 			rc = r;
@@ -681,16 +689,16 @@ static int decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_st
 				continue;
 			}
 			const int lo = I.level + 1;
-			if ((size_t)g.widths[lo] * g.heights[lo] * C > pix_stride) {   // as dwtx_decode_device: nothing written past a slot
-				dwtx_set_error("image %d: %dx%dx%d pixels do not fit the pixel stride %zu", i0 + i, g.widths[lo], g.heights[lo], C, pix_stride);
+			if ((size_t)g.widths[lo] * g.heights[lo] * C > host.image_stride) {   // as dwtx_decode_device: nothing written past a slot
+				dwtx_set_error("image %d: %dx%dx%d pixels do not fit the pixel stride %zu", i0 + i, g.widths[lo], g.heights[lo], C, host.image_stride);
 				outW[i0 + i] = outH[i0 + i] = 0;
 				rc = DWTX_ERR_ARG;
 				break;
 			}
 			outW[i0 + i] = g.widths[lo];
 			outH[i0 + i] = g.heights[lo];
-			e = hipMemcpyAsync(pix + pix_stride * sb * (size_t)(i0 + i), dpix + img_samples * sb * ((size_t)slot * P + i),
-				(size_t)outW[i0 + i] * outH[i0 + i] * C * sb, hipMemcpyDeviceToHost, cs);
+			e = hipMemcpyAsync(host.image(i0 + i).base, stage.image((size_t)slot * P + i).base,
+				host.bytes((size_t)outW[i0 + i] * outH[i0 + i] * C), hipMemcpyDeviceToHost, cs);
 		}
 		if (e == hipSuccess)
 			e = hipEventRecord(ev_out[slot], cs);
@@ -712,12 +720,11 @@ static int decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_st
 extern "C" int dwtx_decode_images_info(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_stride, const size_t *lens, int n,
 	int pixels_max, uint8_t *pix, size_t pix_stride, int *outW, int *outH, int *outC, dwtx_decode_info *infos)
 {
-	return decode_images(ctx, streams, stream_stride, lens, n, pixels_max, pix, PIX8, pix_stride, outW, outH, outC, infos);
+	return decode_images(ctx, streams, stream_stride, lens, n, pixels_max, dwtx_pixels8(pix, 0, pix_stride), outW, outH, outC, infos);
 }
 
 extern "C" int dwtx_decode_images16(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_stride, const size_t *lens, int n,
 	int pixels_max, uint16_t *pix, size_t pix_stride, int maxval, int *outW, int *outH, int *outC, dwtx_decode_info *infos)
 {
-	return decode_images(ctx, streams, stream_stride, lens, n, pixels_max, reinterpret_cast<uint8_t *>(pix), PixFmt{ 2, maxval }, pix_stride,
-		outW, outH, outC, infos);
+	return decode_images(ctx, streams, stream_stride, lens, n, pixels_max, dwtx_pixels16(pix, 0, pix_stride, maxval), outW, outH, outC, infos);
 }

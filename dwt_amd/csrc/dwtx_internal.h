@@ -149,20 +149,53 @@ template <class F> char *carve(dwtx_ctx *ctx, int slot, F &&fn)
 	return c.base;
 }
 
-// lift.hip: the finest lifting level reads / writes 8-bit pixels itself (the widening of pnm.h:69-74, the
-// clamp of pnm.h:108 and, for RGB, the YCoCg-R colour transform of image.h:39-65 fused into it).  dwtx_gray8_ok says whether the
-// shape allows it; image i of the inverse is written at pix + i*image_stride.
-bool dwtx_gray8_ok(int W, int H, const void *pix, size_t image_stride);
+// A batch of interleaved pictures in memory (device memory, or the host buffers codec.hip stages them from / to): the
+// reference's bytes, or deep pixels (include/dwtx.h: native-endian uint16_t samples).  The one place that knows how a
+// sample offset becomes an address: everything that is counted here — image_stride, the argument of at() — counts
+// samples, whatever their size.  (A view of a source is only read; the view does not say which it is.)
+struct dwtx_pixels {
+	void *base;            // image 0's first sample
+	int sample_bytes;      // 1 or 2
+	int channels;          // 1 gray, 3 interleaved RGB
+	size_t image_stride;   // image i starts image_stride * i samples after image 0
+	int maxval;            // 255 for bytes; a deep picture's own (what the inverse direction clamps at)
+
+	bool deep() const { return sample_bytes == 2; }
+	size_t bytes(size_t samples) const { return samples * (size_t)sample_bytes; }
+	void *at(size_t sample) const { return static_cast<char *>(base) + bytes(sample); }
+	// typed for the kernels: u16() for deep pixels; u8() for bytes — and for the fields that carry either kind as bytes
+	// (lift.hip's LevelArgs::src8 / dst8, whose kernels know which they were compiled for)
+	uint8_t *u8() const { return static_cast<uint8_t *>(base); }
+	uint16_t *u16() const { return static_cast<uint16_t *>(base); }
+	// the same pictures from image i on / the same layout somewhere else
+	dwtx_pixels image(size_t i) const { return moved(at(image_stride * i)); }
+	dwtx_pixels moved(void *to) const { return dwtx_pixels{ to, sample_bytes, channels, image_stride, maxval }; }
+	bool aligned(size_t a) const { return ((uintptr_t)base & (a - 1)) == 0; }
+	bool sample_aligned() const { return aligned((size_t)sample_bytes); }
+	// What lift.hip's wide kernels ask of the buffer when the finest level reads / writes the pixels itself: a lane's
+	// quad of samples — 4 bytes, 8 of a deep picture (gray; RGB lanes take three) — is one aligned access in every image
+	bool wide() const { return image_stride % 4 == 0 && aligned(4 * (size_t)sample_bytes); }
+};
+static inline dwtx_pixels dwtx_pixels8(const uint8_t *pix, int channels, size_t image_stride)
+{
+	return dwtx_pixels{ const_cast<uint8_t *>(pix), 1, channels, image_stride, 255 };
+}
+static inline dwtx_pixels dwtx_pixels16(const uint16_t *pix, int channels, size_t image_stride, int maxval = 65535)
+{
+	return dwtx_pixels{ const_cast<uint16_t *>(pix), 2, channels, image_stride, maxval };
+}
+
+// lift.hip: the finest lifting level reads / writes pixels itself (the widening of pnm.h:69-74, the clamp of pnm.h:108
+// and, for RGB, the YCoCg-R colour transform of image.h:39-65 fused into it).  dwtx_pixels_ok says whether the shape and
+// the buffer allow it: W % 4 == 0, more than 64 pixels on a side (the wide kernel, not the LDS tail) and px.wide().
+bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H);
 // lift.hip: asks for the scratch planes every lifting call of a W*H transform over nplanes planes asks for
 int dwtx_lift_scratch(dwtx_ctx *ctx, int W, int H, int nplanes);
-// lift.hip: the same for deep pixels (uint16_t samples, include/dwtx.h): W % 4 == 0, more than 64 pixels on a side, the
-// picture 8-byte aligned and image_stride (in samples) a multiple of 4.  int32 arithmetic and int32 bands; no histograms
-// ride along (lift.hip hist_add) and no 16-bit ring planes — both bounds are for 8-bit sources.
-bool dwtx_pixels16_ok(int W, int H, const void *pix, size_t image_stride);
-int dwtx_fwd_pixels16(dwtx_ctx *ctx, int32_t *out, const uint16_t *pix, int W, int H, int C, int n);
-int dwtx_inv_pixels16(dwtx_ctx *ctx, uint16_t *pix, size_t image_stride, const int32_t *in, int W, int H, int C, int n, int maxval);
-struct dwtx_p16;
-int dwtx_inv_pixels8(dwtx_ctx *ctx, uint8_t *pix, size_t image_stride, const int32_t *in, int W, int H, int C, int n, const dwtx_p16 *p16 = nullptr);   // C = 3: image.h:39-50 fused too
+// lift.hip: the general way between pixels and int32 planes [n*C][H][W] (pnm.h:69-74 / pnm.h:108, YCoCg-R if C == 3): what
+// the extern "C" conversions of include/dwtx.h run.  Dense batches only: image i is taken at W*H*C * i whatever px.image_stride
+// says (a caller with padded slots converts image by image)
+int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n);
+int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int n);
 
 // The entropy stage's tiles (linearize.hip): the Hilbert curve of ring level l visits every aligned 32x32 square of
 // its lengths[l+1]-sided square contiguously ("curve block"), so the ring's coefficients, in the order of
@@ -203,8 +236,12 @@ struct dwtx_p16 {
 	int16_t *planes;
 	unsigned levels;
 };
-int dwtx_fwd_pixels8_hist(dwtx_ctx *ctx, int32_t *out, const uint8_t *pix, int W, int H, int C, int n, const dwtx_hist_sink *sink, unsigned *hist_levels,
-	dwtx_p16 p16 = dwtx_p16{ nullptr, 0u });
+// The transforms whose finest level reads / writes the pixels itself; both need dwtx_pixels_ok(px, W, H), and image i of
+// the inverse is written at px.image(i).  Deep pixels: int32 arithmetic and int32 bands; no histograms ride along
+// (lift.hip hist_add) and no 16-bit ring planes — both bounds are for 8-bit sources, and a deep view with either is DWTX_ERR_ARG.
+int dwtx_fwd_pixels(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels &px, int W, int H, int n, const dwtx_hist_sink *sink = nullptr,
+	unsigned *hist_levels = nullptr, dwtx_p16 p16 = dwtx_p16{ nullptr, 0u });
+int dwtx_inv_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *in, int W, int H, int n, const dwtx_p16 *p16 = nullptr);
 int dwtx_transformation_fwd_hist(dwtx_ctx *ctx, int32_t *out, const int32_t *in, int W, int H, int nplanes, const dwtx_hist_sink *sink,
 	unsigned *hist_levels);
 int dwtx_get_tiles(dwtx_ctx *ctx, int W, int H, dwtx_tiles *out);

@@ -2531,54 +2531,59 @@ extern "C" int dwtx_synth_pixels(dwtx_ctx *ctx, uint8_t *pix, int W, int H, int 
 	return DWTX_OK;
 }
 
-extern "C" int dwtx_planes_from_pixels(dwtx_ctx *ctx, int32_t *planes, const uint8_t *pix, int W, int H, int C, int n)
+int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
 {
-	if (!ctx || !planes || !pix || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1)
+	const int C = px.channels;
+	if (!ctx || !planes || !px.base || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || !px.sample_aligned())
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	const long npix = (long)W * H, total = npix * n;
-	const int blocks = (int)min((total + 255) / 256, (long)256 * 16);
-	hipLaunchKernelGGL(k_planes_from_pixels<uint8_t>, dim3(blocks), dim3(256), 0, ctx->stream, planes, pix, npix, C, total);
+	const dim3 blocks((unsigned)min((total + 255) / 256, (long)256 * 16));
+	if (!px.deep())
+		hipLaunchKernelGGL(k_planes_from_pixels<uint8_t>, blocks, dim3(256), 0, ctx->stream, planes, px.u8(), npix, C, total);
+	else
+		hipLaunchKernelGGL(k_planes_from_pixels<uint16_t>, blocks, dim3(256), 0, ctx->stream, planes, px.u16(), npix, C, total);
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
+}
+
+int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int n)
+{
+	const int C = px.channels;
+	if (!ctx || !planes || !px.base || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || !px.sample_aligned())
+		return DWTX_ERR_ARG;
+	if (!dwtx_maxval_ok(px.maxval))
+		return DWTX_ERR_ARG;
+	DWTX_ENTER(ctx);
+	const long npix = (long)W * H, total = npix * n;
+	const dim3 blocks((unsigned)min((total + 255) / 256, (long)256 * 16));
+	if (!px.deep())
+		hipLaunchKernelGGL(k_pixels_from_planes<uint8_t>, blocks, dim3(256), 0, ctx->stream, px.u8(), planes, npix, C, total, px.maxval);
+	else
+		hipLaunchKernelGGL(k_pixels_from_planes<uint16_t>, blocks, dim3(256), 0, ctx->stream, px.u16(), planes, npix, C, total, px.maxval);
+	DWTX_LAUNCH_CHECK();
+	return DWTX_OK;
+}
+
+// (an odd pointer to 16-bit samples fails the launchers' sample_aligned())
+extern "C" int dwtx_planes_from_pixels(dwtx_ctx *ctx, int32_t *planes, const uint8_t *pix, int W, int H, int C, int n)
+{
+	return dwtx_pixels_to_planes(ctx, planes, dwtx_pixels8(pix, C, (size_t)W * H * C), W, H, n);
 }
 
 extern "C" int dwtx_planes_from_pixels16(dwtx_ctx *ctx, int32_t *planes, const uint16_t *pix, int W, int H, int C, int n)
 {
-	if (!ctx || !planes || !pix || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || ((uintptr_t)pix & 1))
-		return DWTX_ERR_ARG;
-	DWTX_ENTER(ctx);
-	const long npix = (long)W * H, total = npix * n;
-	const int blocks = (int)min((total + 255) / 256, (long)256 * 16);
-	hipLaunchKernelGGL(k_planes_from_pixels<uint16_t>, dim3(blocks), dim3(256), 0, ctx->stream, planes, pix, npix, C, total);
-	DWTX_LAUNCH_CHECK();
-	return DWTX_OK;
+	return dwtx_pixels_to_planes(ctx, planes, dwtx_pixels16(pix, C, (size_t)W * H * C), W, H, n);
 }
 
 extern "C" int dwtx_pixels_from_planes(dwtx_ctx *ctx, uint8_t *pix, const int32_t *planes, int W, int H, int C, int n)
 {
-	if (!ctx || !planes || !pix || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1)
-		return DWTX_ERR_ARG;
-	DWTX_ENTER(ctx);
-	const long npix = (long)W * H, total = npix * n;
-	const int blocks = (int)min((total + 255) / 256, (long)256 * 16);
-	hipLaunchKernelGGL(k_pixels_from_planes<uint8_t>, dim3(blocks), dim3(256), 0, ctx->stream, pix, planes, npix, C, total, 255);
-	DWTX_LAUNCH_CHECK();
-	return DWTX_OK;
+	return dwtx_planes_to_pixels(ctx, dwtx_pixels8(pix, C, (size_t)W * H * C), planes, W, H, n);
 }
 
 extern "C" int dwtx_pixels16_from_planes(dwtx_ctx *ctx, uint16_t *pix, const int32_t *planes, int W, int H, int C, int n, int maxval)
 {
-	if (!ctx || !planes || !pix || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || ((uintptr_t)pix & 1))
-		return DWTX_ERR_ARG;
-	if (!dwtx_maxval_ok(maxval))
-		return DWTX_ERR_ARG;
-	DWTX_ENTER(ctx);
-	const long npix = (long)W * H, total = npix * n;
-	const int blocks = (int)min((total + 255) / 256, (long)256 * 16);
-	hipLaunchKernelGGL(k_pixels_from_planes<uint16_t>, dim3(blocks), dim3(256), 0, ctx->stream, pix, planes, npix, C, total, maxval);
-	DWTX_LAUNCH_CHECK();
-	return DWTX_OK;
+	return dwtx_planes_to_pixels(ctx, dwtx_pixels16(pix, C, (size_t)W * H * C, maxval), planes, W, H, n);
 }
 
 static bool aligned_to(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
@@ -2616,9 +2621,11 @@ static TailArgs tail_args(const LiftLayout &L, int *pyr)
 
 using WideKernel = void (*)(LevelArgsW);
 
-// channels8: the step reads 8-bit pixels (1 gray, 3 RGB); else int32 planes, or src16 the 16-bit bands of the level before
-static WideKernel fwd_wide_kernel(bool hist, int channels8, bool src16)
+// The wide kernel of a forward step.  px: the step reads these pixels (gray or RGB; deep ones leave no histograms); null:
+// int32 planes, or src16 the 16-bit bands of the level before
+static WideKernel fwd_wide_kernel(const dwtx_pixels *px, bool hist, bool src16)
 {
+	const int channels8 = px && !px->deep() ? px->channels : 0;
 	if (hist) {
 		if (channels8 == 3)
 			return k_fwd_pixels_w<Rgb8, true>;
@@ -2630,20 +2637,22 @@ static WideKernel fwd_wide_kernel(bool hist, int channels8, bool src16)
 		return k_fwd_pixels_w<Rgb8, false>;
 	if (channels8)
 		return k_fwd_pixels_w<uint8_t, false>;
-	return src16 ? k_fwd_level_w<false, SRC_I16> : k_fwd_level_w<false, SRC_I32>;
+	if (!px)
+		return src16 ? k_fwd_level_w<false, SRC_I16> : k_fwd_level_w<false, SRC_I32>;
+	return px->channels == 3 ? k_fwd_level_w<false, SRC_RGB16> : k_fwd_level_w<false, SRC_U16>;
 }
 
-// in8 != nullptr: the source is 8-bit pixels, gray (in8_channels 1: plane p = image p) or interleaved RGB
-// (in8_channels 3: plane p = channel p%3 of image p/3 after YCoCg-R); needs a finest level the wide kernel takes.
-// deep: in8 points to uint16_t samples instead (no histograms, no 16-bit bands: their bounds are for 8-bit sources)
-static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_t *in8, int in8_channels, int W, int H, int nplanes,
-	const dwtx_hist_sink *sink = nullptr, unsigned *hist_levels = nullptr, dwtx_p16 p16 = dwtx_p16{ nullptr, 0u }, bool deep = false)
+// px != nullptr (`in` is then not read): the source is pixels, gray (plane p = image p) or interleaved RGB (plane p =
+// channel p%3 of image p/3 after YCoCg-R), image i at px->image(i); needs a finest level the wide kernel takes
+// (dwtx_pixels_ok).  Deep pixels: no histograms, no 16-bit bands (their bounds are for 8-bit sources).
+static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_pixels *px, int W, int H, int nplanes,
+	const dwtx_hist_sink *sink = nullptr, unsigned *hist_levels = nullptr, dwtx_p16 p16 = dwtx_p16{ nullptr, 0u })
 {
-	if (deep && (sink || p16.planes))
+	if (px && px->deep() && (sink || p16.planes))
 		return DWTX_ERR_ARG;
 	if (hist_levels)
 		*hist_levels = 0u;
-	if (!ctx || !out || (!in && !in8) || W < 2 || H < 2 || nplanes < 1 || nplanes > 65535)
+	if (!ctx || !out || (!in && !px) || W < 2 || H < 2 || nplanes < 1 || nplanes > 65535)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	LiftLayout L;
@@ -2663,7 +2672,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 	const int *src = in;
 	long src_ps = full_ps;
 	int spitch = W;
-	if (in8 && tail_from == 0)
+	if (px && tail_from == 0)
 		return DWTX_ERR_ARG;
 	auto ll_dest = [&](int k, int *&p, long &ps, int &pitch) {   // destination of the ws[k]*hs[k] LL band
 		if (k == T) {
@@ -2687,7 +2696,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 			break;
 		}
 		// two levels in one pass where the shapes allow it (k_fwd2_level_w): plain int32 planes, no histograms
-		if (!in8 && !p16.planes && !hist_on && !ctx->opt[DWTX_OPT_NO_FUSED_LEVELS] && t + 1 < tail_from && t + 2 <= T &&
+		if (!px && !p16.planes && !hist_on && !ctx->opt[DWTX_OPT_NO_FUSED_LEVELS] && t + 1 < tail_from && t + 2 <= T &&
 			ws[t] % 4 == 0 && hs[t] % 4 == 0 && spitch % 4 == 0 && src_ps % 4 == 0 && aligned_to(src, 16) && W % 2 == 0 && aligned_to(out, 8)) {
 			Level2Args f{};
 			f.src = src;
@@ -2715,11 +2724,11 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 		a.h = hs[t];
 		a.w2 = ws[t + 1];
 		a.h2 = hs[t + 1];
-		const bool bytes_in = in8 && t == 0;
-		if (bytes_in) {
-			a.src8 = in8;
-			a.src_ps = (long)in8_channels * full_ps;
-			a.spitch = in8_channels * W;
+		const dwtx_pixels *pix_in = t == 0 ? px : nullptr;   // this step reads the pixels
+		if (pix_in) {   // (deep pixels: uint16_t samples behind src8; src_ps and spitch count samples either way)
+			a.src8 = px->u8();
+			a.src_ps = (long)px->image_stride;
+			a.spitch = px->channels * W;
 		} else {
 			a.src = src;
 			a.src_ps = src_ps;
@@ -2734,7 +2743,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 		// that is what bounds the magnitudes (see k_fwd_level_w).
 		auto in_mask = [&](int step) { return p16.planes && step < tail_from && ((p16.levels >> (T - 1 - step)) & 1u); };
 		if (in_mask(t)) {
-			if (!in8 || t >= LEVELS16_MAX || (t > 0 && !in_mask(t - 1)) || !aligned_to(p16.planes, 16))
+			if (!px || t >= LEVELS16_MAX || (t > 0 && !in_mask(t - 1)) || !aligned_to(p16.planes, 16))
 				return DWTX_ERR_ARG;
 			a.det16 = p16.planes;
 			if (t > 0)
@@ -2743,11 +2752,11 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 				a.ll16 = reinterpret_cast<short *>(a.ll);
 		}
 		const bool wide = a.w % 4 == 0 && a.spitch % 4 == 0 && a.src_ps % 4 == 0 &&
-			(bytes_in ? aligned_to(a.src8, deep ? 8 : 4) : aligned_to(a.src, 16)) &&
+			(pix_in ? px->wide() : aligned_to(a.src, 16)) &&
 			a.llpitch % 2 == 0 && a.ll_ps % 2 == 0 && aligned_to(a.ll, 8) &&
 			a.dpitch % 2 == 0 && a.det_ps % 2 == 0 && aligned_to(a.det, 8);
-		if ((bytes_in || a.det16) && !wide)
-			return DWTX_ERR_ARG;   // callers check dwtx_gray8_ok() / dwtx_levels16() first
+		if ((pix_in || a.det16) && !wide)
+			return DWTX_ERR_ARG;   // callers check dwtx_pixels_ok() / dwtx_levels16() first
 		const int level = T - 1 - t;   // the ring level this step's detail bands are
 		// (the RGB kernel is bound by its own arithmetic — every plane's launch unpacks the pixels and does the colour
 		// transform — and pays for the histogram in full: 3.2 -> 4.7 ms per 256 frames of 1080p against the 1.4 ms k_hist takes)
@@ -2764,15 +2773,11 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const uint8_
 					sink->tiles.nbs[level] };
 				*hist_levels |= 1u << level;
 			}
-			const int ch = bytes_in ? in8_channels : 0;
 			const int sx = dwtx_cdiv(strips, 1 << A.wx_log2), gy = dwtx_cdiv(a.h2, (WAVES >> A.wx_log2) * a.rpw);
-			if (bytes_in && deep) {   // (src_ps and spitch count samples; one launch per plane, each taking its channel)
-				const WideKernel deep_kernel = ch == 3 ? k_fwd_level_w<false, SRC_RGB16> : k_fwd_level_w<false, SRC_U16>;
-				hipLaunchKernelGGL(deep_kernel, dim3(sx, gy, nplanes), dim3(64 * WAVES), 0, ctx->stream, A);
-			} else {
-			const dim3 grid = ch == 3 ? dim3(sx * 3, gy, nplanes / 3) : dim3(sx, gy, nplanes);   // (RGB: the three channels of a strip side by side, xcd_strip_rgb)
-			hipLaunchKernelGGL(fwd_wide_kernel(hist_here, ch, a.src16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
-			}
+			// (8-bit RGB: the three channels of a strip side by side, xcd_strip_rgb; deep RGB: a block per plane, each taking its channel)
+			const bool rgb8 = pix_in && !px->deep() && px->channels == 3;
+			const dim3 grid = rgb8 ? dim3(sx * 3, gy, nplanes / 3) : dim3(sx, gy, nplanes);
+			hipLaunchKernelGGL(fwd_wide_kernel(pix_in, hist_here, a.src16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {
 			const int sx = dwtx_cdiv(a.w2, 64);
 			a.rpw = pick_rpw(sx, a.h2, nplanes);
@@ -2791,19 +2796,13 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 {
 	if (!in)
 		return DWTX_ERR_ARG;
-	return lift_fwd(ctx, out, in, nullptr, 0, W, H, nplanes);
+	return lift_fwd(ctx, out, in, nullptr, W, H, nplanes);
 }
 
-// Can the finest level of a W*H gray image read / write 8-bit pixels directly?  (wide kernel, not the LDS tail)
-bool dwtx_gray8_ok(int W, int H, const void *pix, size_t image_stride)
+// Can the finest level of a W*H image read / write these pixels directly?  (wide kernel, not the LDS tail)
+bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H)
 {
-	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && image_stride % 4 == 0 && aligned_to(pix, 4);
-}
-
-// The same for deep pixels (2-byte samples; image_stride in samples): a lane's quad is 8 bytes (gray) or 24 (RGB16)
-bool dwtx_pixels16_ok(int W, int H, const void *pix, size_t image_stride)
-{
-	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && image_stride % 4 == 0 && aligned_to(pix, 8);
+	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide();
 }
 
 unsigned dwtx_levels16(int W, int H, unsigned sq_levels)
@@ -2826,19 +2825,12 @@ int dwtx_lift_scratch(dwtx_ctx *ctx, int W, int H, int nplanes)
 	return lift_layout(ctx, W, H, nplanes, L);
 }
 
-int dwtx_fwd_pixels8_hist(dwtx_ctx *ctx, int32_t *out, const uint8_t *pix, int W, int H, int C, int n, const dwtx_hist_sink *sink, unsigned *hist_levels,
+int dwtx_fwd_pixels(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels &px, int W, int H, int n, const dwtx_hist_sink *sink, unsigned *hist_levels,
 	dwtx_p16 p16)
 {
-	if (!pix || (C != 1 && C != 3) || !dwtx_gray8_ok(W, H, pix, (size_t)W * H * C))
+	if (!px.base || (px.channels != 1 && px.channels != 3) || !dwtx_pixels_ok(px, W, H))
 		return DWTX_ERR_ARG;
-	return lift_fwd(ctx, out, nullptr, pix, C, W, H, n * C, sink, hist_levels, p16);
-}
-
-int dwtx_fwd_pixels16(dwtx_ctx *ctx, int32_t *out, const uint16_t *pix, int W, int H, int C, int n)
-{
-	if (!pix || (C != 1 && C != 3) || !dwtx_pixels16_ok(W, H, pix, (size_t)W * H * C))
-		return DWTX_ERR_ARG;
-	return lift_fwd(ctx, out, nullptr, reinterpret_cast<const uint8_t *>(pix), C, W, H, n * C, nullptr, nullptr, dwtx_p16{ nullptr, 0u }, true);
+	return lift_fwd(ctx, out, nullptr, &px, W, H, n * px.channels, sink, hist_levels, p16);
 }
 
 int dwtx_transformation_fwd_hist(dwtx_ctx *ctx, int32_t *out, const int32_t *in, int W, int H, int nplanes, const dwtx_hist_sink *sink,
@@ -2846,40 +2838,41 @@ int dwtx_transformation_fwd_hist(dwtx_ctx *ctx, int32_t *out, const int32_t *in,
 {
 	if (!in)
 		return DWTX_ERR_ARG;
-	return lift_fwd(ctx, out, in, nullptr, 0, W, H, nplanes, sink, hist_levels);
+	return lift_fwd(ctx, out, in, nullptr, W, H, nplanes, sink, hist_levels);
 }
 
 using Inv2Kernel = void (*)(Inv2Args);
 
-// channels8: the pair writes 8-bit pixels (1 gray, 3 RGB), which it does from 16-bit bands only
-static Inv2Kernel inv2_kernel(int channels8, bool det16)
+// px: the pair writes these pixels (8-bit ones, gray or RGB), which it does from 16-bit bands only
+static Inv2Kernel inv2_kernel(const dwtx_pixels *px, bool det16)
 {
-	if (channels8 == 3)
+	if (px && px->channels == 3)
 		return k_inv2_level_w_rgb<true>;
-	if (channels8)
+	if (px)
 		return k_inv2_level_w<uint8_t, true>;
 	return det16 ? k_inv2_level_w<int, true> : k_inv2_level_w<int, false>;
 }
 
-// channels8: the step writes 8-bit pixels (1 gray, 3 RGB)
-static WideKernel inv_wide_kernel(int channels8, bool det16)
+// The wide kernel of an inverse step.  px: the step writes these pixels (gray or RGB; deep ones never from 16-bit bands)
+static WideKernel inv_wide_kernel(const dwtx_pixels *px, bool det16)
 {
+	const int channels8 = px && !px->deep() ? px->channels : 0;
 	if (channels8 == 3)
 		return det16 ? k_inv_level_w_rgb<true> : k_inv_level_w_rgb<false>;
 	if (channels8)
 		return det16 ? k_inv_level_w<uint8_t, true> : k_inv_level_w<uint8_t, false>;
-	return det16 ? k_inv_level_w<int, true> : k_inv_level_w<int, false>;
+	if (!px)
+		return det16 ? k_inv_level_w<int, true> : k_inv_level_w<int, false>;
+	return px->channels == 3 ? k_inv_level_w_rgb<false, uint16_t> : k_inv_level_w<uint16_t, false>;
 }
 
-// out8 != nullptr: the finest level writes clamped 8-bit pixels (gray, or interleaved RGB after the
-// inverse colour transform when out8_channels == 3), image i at out8 + i*out8_ps
-// maxval16 > 0: out8 points to deep pixels (uint16_t samples, out8_ps in samples), clamped at that maxval
-static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, int out8_channels, const int32_t *in, int W, int H, int nplanes,
-	const dwtx_p16 *p16 = nullptr, int maxval16 = 0)
+// px != nullptr (`out` is then not written): the finest level writes clamped pixels (gray, or interleaved RGB after the
+// inverse colour transform), image i at px->image(i); deep pixels are clamped at px->maxval and take no 16-bit bands
+static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const int32_t *in, int W, int H, int nplanes, const dwtx_p16 *p16 = nullptr)
 {
-	if (maxval16 && (!out8 || (p16 && p16->planes)))
+	if (px && px->deep() && p16 && p16->planes)
 		return DWTX_ERR_ARG;
-	if (!ctx || (!out && !out8) || !in || W < 2 || H < 2 || nplanes < 1 || nplanes > 65535)
+	if (!ctx || (!out && !px) || !in || W < 2 || H < 2 || nplanes < 1 || nplanes > 65535)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	LiftLayout L;
@@ -2896,14 +2889,14 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 	// two levels per pass (k_inv2_level_w): int32 planes throughout, or — the codec's pipelines — both levels' detail bands as 16-bit values
 	// (dwtx_p16), the finest step then writing a gray picture's 8-bit pixels itself; an RGB picture's last step keeps its own kernel
 	const bool have16 = p16 && p16->planes;
-	const bool fusing = !ctx->opt[DWTX_OPT_NO_FUSED_LEVELS] && W % 4 == 0 && aligned_to(in, 8) && (out8 ? aligned_to(out8, 4) && out8_ps % 4 == 0 : aligned_to(out, 16)) &&
+	const bool fusing = !ctx->opt[DWTX_OPT_NO_FUSED_LEVELS] && W % 4 == 0 && aligned_to(in, 8) && (px ? px->wide() : aligned_to(out, 16)) &&
 		(!have16 || aligned_to(p16->planes, 4));
 	auto in16 = [&](int t) { return have16 && ((p16->levels >> (T - 1 - t)) & 1u) != 0; };   // step t's detail bands are 16-bit values
 	auto can_fuse = [&](int t) {   // (t == T - 1 reads the root LL in the pyramid itself: no pair there)
 		if (!fusing || t < 1 || t == T - 1 || ws[t - 1] % 4 != 0 || hs[t - 1] % 4 != 0 || in16(t) != in16(t - 1))
 			return false;
-		if (t - 1 == 0 && out8)   // (the 8-bit variants exist for 16-bit bands only: what the pipelines run; RGB: three planes per wave)
-			return in16(0) && (out8_channels == 1 || (out8_channels == 3 && nplanes % 3 == 0));
+		if (t - 1 == 0 && px)   // (the 8-bit variants exist for 16-bit bands only: what the pipelines run; RGB: three planes per wave)
+			return in16(0) && (px->channels == 1 || (px->channels == 3 && nplanes % 3 == 0));
 		return true;
 	};
 	// Steps t .. 0 with the planes from here on assigned with `fl`: the most samples that can go through two-level steps (a pair is
@@ -2952,7 +2945,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 	long cur_ps = full_ps;
 	int cur_pitch = W;
 	if (tail_from < T) {
-		if (tail_from == 0 && out8)
+		if (tail_from == 0 && px)
 			return DWTX_ERR_ARG;
 		TailArgs ta = tail_args(L, const_cast<int *>(in));
 		ta.dst = tail_from == 0 ? out : plane[tail_from];
@@ -2974,10 +2967,11 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 			f.det_ps = full_ps;
 			f.dpitch = W;
 			f.det16 = in16(t) ? p16->planes : nullptr;
-			if (t - 1 == 0 && out8) {
-				f.dst8 = out8;
-				f.dst_ps = out8_ps;
-				f.opitch = out8_channels * W;
+			const dwtx_pixels *pix_out = t - 1 == 0 ? px : nullptr;   // the pair writes the pixels
+			if (pix_out) {
+				f.dst8 = px->u8();
+				f.dst_ps = (long)px->image_stride;
+				f.opitch = px->channels * W;
 			} else if (t - 1 == 0) {
 				f.dst = out;
 				f.dst_ps = full_ps;
@@ -2993,9 +2987,9 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 			const int strips = dwtx_cdiv(f.nquads, V2_OWN), h4 = f.h / 4;
 			f.mpw = fill_chip(F2_MPW, 2, (long)strips * nplanes, h4);
 			// (the 8-bit kernels put a block's waves side by side; RGB: three planes per wave)
-			const int ch = f.dst8 ? out8_channels : 0;
-			const dim3 grid = ch ? dim3(dwtx_cdiv(strips, WAVES), dwtx_cdiv(h4, f.mpw), nplanes / ch) : dim3(strips, dwtx_cdiv(h4, WAVES * f.mpw), nplanes);
-			hipLaunchKernelGGL(inv2_kernel(ch, f.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, f);
+			const dim3 grid = pix_out ? dim3(dwtx_cdiv(strips, WAVES), dwtx_cdiv(h4, f.mpw), nplanes / px->channels)
+			                          : dim3(strips, dwtx_cdiv(h4, WAVES * f.mpw), nplanes);
+			hipLaunchKernelGGL(inv2_kernel(pix_out, f.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, f);
 			DWTX_LAUNCH_CHECK();
 			cur = f.dst;
 			cur_ps = f.dst_ps;
@@ -3011,12 +3005,12 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 		a.src = cur;   // (without a tail the first step reads the root LL in the pyramid itself)
 		a.src_ps = cur_ps;
 		a.spitch = cur_pitch;
-		const bool bytes_out = out8 && t == 0;
-		if (bytes_out) {
-			a.dst8 = out8;
-			a.ll_ps = out8_ps;
-			a.llpitch = out8_channels * W;
-			a.maxval = maxval16;
+		const dwtx_pixels *pix_out = t == 0 ? px : nullptr;   // this step writes the pixels
+		if (pix_out) {   // (deep pixels: uint16_t samples behind dst8; ll_ps and llpitch count samples either way)
+			a.dst8 = px->u8();
+			a.ll_ps = (long)px->image_stride;
+			a.llpitch = px->channels * W;
+			a.maxval = px->deep() ? px->maxval : 0;
 		} else if (t == 0) {
 			a.ll = out;
 			a.ll_ps = full_ps;
@@ -3030,29 +3024,25 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, uint8_t *out8, long out8_ps, in
 		a.det_ps = full_ps;
 		a.dpitch = W;
 		if (in16(t)) {
-			if (!out8 || !aligned_to(p16->planes, 4))
+			if (!px || !aligned_to(p16->planes, 4))
 				return DWTX_ERR_ARG;
 			a.det16 = p16->planes;
 		}
 		const bool wide = a.w % 4 == 0 && a.llpitch % 4 == 0 && a.ll_ps % 4 == 0 &&
-			(bytes_out ? aligned_to(a.dst8, maxval16 ? 8 : 4) : aligned_to(a.ll, 16)) &&
+			(pix_out ? px->wide() : aligned_to(a.ll, 16)) &&
 			a.spitch % 2 == 0 && a.src_ps % 2 == 0 && aligned_to(a.src, 8) &&
 			a.dpitch % 2 == 0 && a.det_ps % 2 == 0 && aligned_to(a.det, 8);
-		if ((bytes_out || a.det16) && !wide)
+		if ((pix_out || a.det16) && !wide)
 			return DWTX_ERR_ARG;
 		if (wide) {
 			LevelArgsW A{};
 			A.nquads = a.w / 4;
-			const int ch = bytes_out ? out8_channels : 0;
-			const int sx = dwtx_cdiv(A.nquads, ch == 3 ? INV_QUADS : 64);   // (the RGB kernel's waves overlap by a lane on each side)
+			const bool rgb = pix_out && px->channels == 3;
+			const int sx = dwtx_cdiv(A.nquads, rgb ? INV_QUADS : 64);   // (the RGB kernel's waves overlap by a lane on each side)
 			a.rpw = pick_rpw(sx, a.h2, nplanes);
 			A.a = a;
-			const dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), ch == 3 ? nplanes / 3 : nplanes);
-			if (bytes_out && maxval16) {
-				const WideKernel deep_kernel = ch == 3 ? k_inv_level_w_rgb<false, uint16_t> : k_inv_level_w<uint16_t, false>;
-				hipLaunchKernelGGL(deep_kernel, grid, dim3(64 * WAVES), 0, ctx->stream, A);
-			} else
-				hipLaunchKernelGGL(inv_wide_kernel(ch, a.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
+			const dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), rgb ? nplanes / 3 : nplanes);
+			hipLaunchKernelGGL(inv_wide_kernel(pix_out, a.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {
 			const int sx = dwtx_cdiv(a.w2, INV_PAIRS);
 			a.rpw = pick_rpw(sx, a.h2, nplanes);
@@ -3070,19 +3060,12 @@ extern "C" int dwtx_transformation_inv(dwtx_ctx *ctx, int32_t *out, const int32_
 {
 	if (!out)
 		return DWTX_ERR_ARG;
-	return lift_inv(ctx, out, nullptr, 0, 0, in, W, H, nplanes);
+	return lift_inv(ctx, out, nullptr, in, W, H, nplanes);
 }
 
-int dwtx_inv_pixels8(dwtx_ctx *ctx, uint8_t *pix, size_t image_stride, const int32_t *in, int W, int H, int C, int n, const dwtx_p16 *p16)
+int dwtx_inv_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *in, int W, int H, int n, const dwtx_p16 *p16)
 {
-	if (!pix || W < 2 || H < 2 || (C != 1 && C != 3) || !dwtx_gray8_ok(W, H, pix, image_stride))
+	if (!px.base || W < 2 || H < 2 || (px.channels != 1 && px.channels != 3) || px.maxval < 1 || px.maxval > 65535 || !dwtx_pixels_ok(px, W, H))
 		return DWTX_ERR_ARG;
-	return lift_inv(ctx, nullptr, pix, (long)image_stride, C, in, W, H, n * C, p16);
-}
-
-int dwtx_inv_pixels16(dwtx_ctx *ctx, uint16_t *pix, size_t image_stride, const int32_t *in, int W, int H, int C, int n, int maxval)
-{
-	if (!pix || W < 2 || H < 2 || (C != 1 && C != 3) || maxval < 1 || maxval > 65535 || !dwtx_pixels16_ok(W, H, pix, image_stride))
-		return DWTX_ERR_ARG;
-	return lift_inv(ctx, nullptr, reinterpret_cast<uint8_t *>(pix), (long)image_stride, C, in, W, H, n * C, nullptr, maxval);
+	return lift_inv(ctx, nullptr, &px, in, W, H, n * px.channels, p16);
 }
