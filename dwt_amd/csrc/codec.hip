@@ -174,8 +174,11 @@ extern "C" int dwtx_transformation_inv_pixels(dwtx_ctx *ctx, uint8_t *dev_pix, c
 	const dwtx_pixels px = dwtx_pixels8(dev_pix, C, (size_t)W * H * C);
 	if (!fused_shape(px, W, H))
 		return DWTX_ERR_ARG;
-	if (levels16 && levels16 != dwtx_levels16(W, H, dwtx_square_levels(W, H)))
-		return DWTX_ERR_ARG;   // (the mask the forward call reported for this geometry, or none)
+	if (levels16 && levels16 != dwtx_levels16(W, H, dwtx_square_levels(W, H))) {   // (the mask the forward call reported for this geometry, or none)
+		dwtx_set_error("levels16 mask 0x%x is not the one the forward transform reports for %dx%d (0x%x)", levels16, W, H,
+			dwtx_levels16(W, H, dwtx_square_levels(W, H)));
+		return DWTX_ERR_ARG;
+	}
 	const dwtx_p16 f16 = { levels16 ? const_cast<int16_t *>(dev_rings16) : nullptr, levels16 };
 	return pixels_from_pyramid(ctx, px, dev_pyr, nullptr, W, H, n, &f16);
 }
