@@ -10,9 +10,9 @@ raise.
 import ctypes as C
 
 from . import _lib
-from ._lib import Geom, Stats, StreamInfo, DecodeInfo, Index, SegIndex, INDEX_MAGIC, INDEX_MAX_SEGS, LIB_PATH  # noqa: F401
+from ._lib import Geom, Stats, StreamInfo, DecodeInfo, Index, SegIndex, View, TileGroup, INDEX_MAGIC, INDEX_MAX_SEGS, LIB_PATH  # noqa: F401
 
-__all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "Geom", "Stats"]
+__all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "tile_groups", "Geom", "Stats", "View", "TileGroup"]
 
 
 class DwtxError(RuntimeError):
@@ -39,6 +39,16 @@ def geometry(W, H):
     g = Geom()
     _check(_lib.load().dwtx_geometry(C.byref(g), W, H), "dwtx_geometry")
     return g
+
+
+def tile_groups(W, H, tile):
+    """dwtx_tile_groups: the 1 to 4 same-geometry groups (TileGroup) of a W x H frame cut into `tile`-sided tiles —
+    interior, right column, bottom row, corner.  Host arithmetic only."""
+    out = (TileGroup * 4)()
+    k = _lib.load().dwtx_tile_groups(W, H, tile, out)
+    if k < 0:
+        raise DwtxError(k, "dwtx_tile_groups")
+    return [TileGroup.from_buffer_copy(bytes(out[i])) for i in range(k)]
 
 
 def _ptr(t):
@@ -445,3 +455,54 @@ class Context:
         """device streams [n,stride] + int64 lens -> (uint16 [n, W*H*C] pixels, list of DecodeInfo); syncs once.
         `out`: a 16-bit device tensor [n, pix_stride] with pix_stride (in samples) >= the pictures' size."""
         return self._decode_device("dwtx_decode_device16", self.torch.uint16, streams, lens, W, H, C_, levels_max, out, maxval)
+
+    # -- strided views: windows and tile grids of a larger frame (dwtx_encode_view / dwtx_decode_view) -----------
+
+    def _view(self, t, maxval):
+        """View of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (uint8, or uint16 / int16 for deep pixels):
+        the windows stay where they are; only the channel and column strides must be those of interleaved pixels."""
+        torch = self.torch
+        if t.dtype not in (torch.uint8, torch.uint16, torch.int16) or t.device != self.device or t.dim() not in (4, 5):
+            raise ValueError("a view needs a uint8 / uint16 / int16 tensor [n,H,W,C] or [bands,cols,H,W,C] on the context's device")
+        H, W, Cn = t.shape[-3:]
+        sh, sw, sc = t.stride()[-3:]
+        if Cn not in (1, 3) or (Cn > 1 and sc != 1) or sw != Cn:
+            raise ValueError(f"a view needs interleaved pixels: channel stride 1 and column stride C, not {sc} and {sw} (C = {Cn})")
+        deep = t.dtype != torch.uint8
+        if maxval is None:
+            maxval = 65535 if deep else 255
+        if t.dim() == 4:
+            n, cols, band = t.shape[0], 0, 0
+        else:
+            n, cols, band = t.shape[0] * t.shape[1], t.shape[1], t.stride(0)
+        v = View(t.data_ptr(), 2 if deep else 1, Cn, maxval, cols, sh, t.stride(-4), band)
+        return v, W, H, Cn, n
+
+    def encode_view(self, t, capacity=0, out=None, info=None):
+        """dwtx_encode_view: the windows of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (a slice, a crop, a
+        grid of tiles: see _view) -> (streams uint8 [n,stride], info uint8 [n,sizeof(StreamInfo)]) on device, as
+        encode_device / encode_device16 give for the contiguous copy; async."""
+        torch = self.torch
+        v, W, H, Cn, n = self._view(t, None)
+        bound = self.lib.dwtx_encode_bound16 if v.sample_bytes == 2 else self.lib.dwtx_encode_bound
+        stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
+        if out is None:
+            out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
+        if info is None:
+            info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
+        _check(self.lib.dwtx_encode_view(self.h, C.byref(v), W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view")
+        return out, info
+
+    def decode_view(self, streams, lens, into, maxval=None, levels_max=-1):
+        """dwtx_decode_view: device streams [n,stride] + int64 lens -> the windows of the strided device tensor `into`
+        ([n,H,W,C] or [bands,cols,H,W,C]), each picture in its window's top-left corner at the size its stream supports;
+        nothing else of `into`'s storage is written.  maxval: the deep pictures' (default 65535).  Returns the list of
+        DecodeInfo; syncs once."""
+        torch = self.torch
+        v, W, H, Cn, n = self._view(into, maxval)
+        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
+        assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
+        infos = (DecodeInfo * n)()
+        _check(self.lib.dwtx_decode_view(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
+                                         C.cast(infos, C.c_void_p)), "dwtx_decode_view")
+        return list(infos)

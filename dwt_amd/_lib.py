@@ -55,6 +55,17 @@ class Index(C.Structure):
                 ("reserved", C.c_int), ("stream_bits", C.c_ulonglong), ("seg", SegIndex * INDEX_MAX_SEGS)]
 
 
+class View(C.Structure):
+    """dwtx_view: n same-geometry windows of a larger frame (include/dwtx.h); strides count samples."""
+    _fields_ = [("dev", C.c_void_p), ("sample_bytes", C.c_int), ("channels", C.c_int), ("maxval", C.c_int), ("cols", C.c_int),
+                ("row_pitch", C.c_size_t), ("image_stride", C.c_size_t), ("band_stride", C.c_size_t)]
+
+
+class TileGroup(C.Structure):
+    """dwtx_tile_group: a cols x rows grid of W x H tiles whose first tile's corner is (x0, y0)."""
+    _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("W", C.c_int), ("H", C.c_int), ("cols", C.c_int), ("rows", C.c_int)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("meta_bits", C.c_int),
@@ -119,6 +130,10 @@ SYMBOLS = {
     "dwtx_encode_device16": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
     "dwtx_decode_device16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
     "dwtx_encode_images16": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp, _vp]),
+    # strided views and the tiling plan
+    "dwtx_encode_view": (_i, [_vp, C.POINTER(View), _i, _i, _i, C.c_long, _vp, _sz, _vp]),
+    "dwtx_decode_view": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _vp]),
+    "dwtx_tile_groups": (_i, [_i, _i, _i, C.POINTER(TileGroup)]),
     "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }
 

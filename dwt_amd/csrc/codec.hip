@@ -85,7 +85,7 @@ static int pyramid_from_pixels(dwtx_ctx *ctx, int32_t *pyr, int32_t *tmp, const 
 
 // pyramid -> pixels (decode.c:258-264), image i of the n at px.image(i): in one pass where the finest level can write the
 // pixels itself (as above; f16: rings the decoder left in 16-bit planes), else the int32 transform into planes (`tmp`, or
-// scratch) and egress — image by image where the slots are padded
+// scratch) and egress, which knows the view's strides
 static int pixels_from_pyramid(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *pyr, int32_t *tmp, int W, int H, int n, const dwtx_p16 *f16)
 {
 	const int C = px.channels;
@@ -96,13 +96,7 @@ static int pixels_from_pyramid(dwtx_ctx *ctx, const dwtx_pixels &px, const int32
 		return DWTX_ERR_NOMEM;
 	if ((rc = dwtx_transformation_inv(ctx, tmp, pyr, W, H, n * C)))                            // decode.c:258
 		return rc;
-	const size_t samples = (size_t)W * H * C;
-	if (n == 1 || samples == px.image_stride)
-		return dwtx_planes_to_pixels(ctx, px, tmp, W, H, n);                                   // decode.c:262-264
-	for (int i = 0; i < n; ++i)
-		if ((rc = dwtx_planes_to_pixels(ctx, px.image(i), tmp + samples * i, W, H, 1)))
-			return rc;
-	return DWTX_OK;
+	return dwtx_planes_to_pixels(ctx, px, tmp, W, H, n);                                       // decode.c:262-264
 }
 
 // pixels (device) -> streams (device) for one part of a batch, on the part's context; `lifted` (optional) is recorded
@@ -264,8 +258,8 @@ extern "C" int dwtx_encode_device16(dwtx_ctx *ctx, const uint16_t *dev_pix, int 
 	return encode_device(ctx, dwtx_pixels16(dev_pix, C, (size_t)W * H * C), W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
 }
 
-// streams (device) -> pixels (device).  Image i is written densely (ow*oh*C samples)
-// at px.image(i); its size is widths/heights[info[i].level + 1].
+// streams (device) -> pixels (device).  Image i is written at px.image(i) — densely (ow*oh*C samples), or with the view's
+// row pitch into its window's corner; its size is widths/heights[info[i].level + 1].
 static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
 	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_pixels &px, dwtx_decode_info *host_info)
 {
@@ -304,7 +298,7 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 		const dwtx_decode_info &I = host_info[first];
 		const int lo = I.level + 1;                                          // decode.c:251
 		const int ow = g.widths[lo], oh = g.heights[lo];
-		if ((size_t)ow * oh * C > px.image_stride)
+		if (!px.row_pitch && (size_t)ow * oh * C > px.image_stride)   // (dense slots; a window with a pitch holds its own corner)
 			return DWTX_ERR_ARG;
 		int *miss = nullptr;
 		bool biased = false;
@@ -364,6 +358,113 @@ extern "C" int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, s
 	uint16_t *dev_pix, size_t pix_stride, int maxval, dwtx_decode_info *host_info)
 {
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dwtx_pixels16(dev_pix, C, pix_stride, maxval), host_info);
+}
+
+// ---- views (include/dwtx.h): windows and tile grids of a larger frame ----------------------------------------------
+
+// dwtx_view -> dwtx_pixels for n windows of W x H, checked; `dst`: the view will be written (maxval, disjoint windows)
+static int pixels_of_view(const dwtx_view *v, int W, int H, int n, bool dst, dwtx_pixels *px)
+{
+	if (!v || !v->dev || n < 1) {
+		dwtx_set_error("no view, no pixels or no windows");
+		return DWTX_ERR_ARG;
+	}
+	DWTX_CHECK_DIMS(W, H);
+	if ((v->sample_bytes != 1 && v->sample_bytes != 2) || (v->channels != 1 && v->channels != 3) || v->cols < 0) {
+		dwtx_set_error("view: sample_bytes %d (1 or 2), channels %d (1 or 3), cols %d (>= 0)", v->sample_bytes, v->channels, v->cols);
+		return DWTX_ERR_ARG;
+	}
+	const size_t row = (size_t)W * v->channels;
+	if (v->row_pitch < row) {
+		dwtx_set_error("view: row_pitch %zu is less than a window's row of %zu samples", v->row_pitch, row);
+		return DWTX_ERR_ARG;
+	}
+	if ((uintptr_t)v->dev % (size_t)v->sample_bytes) {
+		dwtx_set_error("view: dev is not aligned to its %d-byte samples", v->sample_bytes);
+		return DWTX_ERR_ARG;
+	}
+	const size_t cols = v->cols && v->cols < n ? (size_t)v->cols : (size_t)n;
+	const bool bands = cols < (size_t)n;
+	if (dst) {
+		if (v->sample_bytes == 1 ? v->maxval != 255 : !dwtx_maxval_ok(v->maxval)) {
+			if (v->sample_bytes == 1)
+				dwtx_set_error("view: maxval %d with 1-byte samples (255)", v->maxval);
+			return DWTX_ERR_ARG;
+		}
+		const size_t window = (size_t)(H - 1) * v->row_pitch + row;   // from a window's first sample to behind its last
+		const bool stacked = v->image_stride >= window;
+		const bool beside = v->image_stride >= row && v->row_pitch >= (cols - 1) * v->image_stride + row;
+		if (cols > 1 && !stacked && !beside) {
+			dwtx_set_error("view: windows overlap (image_stride %zu, row_pitch %zu, %zu windows per band of %zu x %d samples)",
+				v->image_stride, v->row_pitch, cols, row, H);
+			return DWTX_ERR_ARG;
+		}
+		if (bands && v->band_stride < (cols - 1) * v->image_stride + window) {
+			dwtx_set_error("view: bands overlap (band_stride %zu, a band spans %zu samples)", v->band_stride, (cols - 1) * v->image_stride + window);
+			return DWTX_ERR_ARG;
+		}
+	}
+	*px = v->sample_bytes == 1 ? dwtx_pixels8((const uint8_t *)v->dev, v->channels, v->image_stride)
+		: dwtx_pixels16((const uint16_t *)v->dev, v->channels, v->image_stride, dst ? v->maxval : 65535);
+	px->row_pitch = v->row_pitch;
+	if (bands) {
+		px->cols = (int)cols;
+		px->band_stride = v->band_stride;
+	}
+	return DWTX_OK;
+}
+
+extern "C" int dwtx_encode_view(dwtx_ctx *ctx, const dwtx_view *src, int W, int H, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	dwtx_pixels px;
+	if (const int rc = pixels_of_view(src, W, H, n, false, &px))
+		return rc;
+	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
+}
+
+extern "C" int dwtx_decode_view(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, dwtx_decode_info *host_info)
+{
+	dwtx_pixels px;
+	if (const int rc = pixels_of_view(dst, W, H, n, true, &px))
+		return rc;
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
+}
+
+// one axis of dwtx_tile_groups: `full` tiles of `tile`, then one of `last` (0: none)
+static void tile_axis(int side, int tile, int *full, int *last)
+{
+	const int rem = side % tile;
+	*full = side / tile;
+	*last = rem;
+	if (*full && rem && rem < DWTX_MIN_LEN) {   // too thin to be a picture: the last full tile takes it
+		--*full;
+		*last = tile + rem;
+	}
+}
+
+extern "C" int dwtx_tile_groups(int frameW, int frameH, int tile, dwtx_tile_group out[4])
+{
+	if (!out || tile < DWTX_MIN_LEN || tile % 4 || tile > DWTX_MAX_SIDE || frameW < DWTX_MIN_LEN || frameH < DWTX_MIN_LEN) {
+		dwtx_set_error("tile plan: tile %d (a multiple of 4 in 8..%d), frame %dx%d (8 or more per side)", tile, DWTX_MAX_SIDE, frameW, frameH);
+		return DWTX_ERR_ARG;
+	}
+	int fx, lx, fy, ly;
+	tile_axis(frameW, tile, &fx, &lx);
+	tile_axis(frameH, tile, &fy, &ly);
+	if (lx > DWTX_MAX_SIDE || ly > DWTX_MAX_SIDE) {
+		dwtx_set_error("tile plan: the widened last tile (%d x %d) is beyond %d", lx, ly, DWTX_MAX_SIDE);
+		return DWTX_ERR_ARG;
+	}
+	// columns of tiles: the full ones, then the last; rows the same — interior, right column, bottom row, corner
+	const int xs[2][3] = { { 0, tile, fx }, { fx * tile, lx, lx ? 1 : 0 } }, ys[2][3] = { { 0, tile, fy }, { fy * tile, ly, ly ? 1 : 0 } };
+	int k = 0;
+	for (int b = 0; b < 2; ++b)
+		for (int a = 0; a < 2; ++a)
+			if (xs[a][2] && ys[b][2])
+				out[k++] = dwtx_tile_group{ xs[a][0], ys[b][0], xs[a][1], ys[b][1], xs[a][2], ys[b][2] };
+	return k;
 }
 
 // ---- dwtx_pack_streams: a step's streams as one message (include/dwtx.h) -------------------------------------------

@@ -32,6 +32,26 @@ constexpr int WAVES = 4;          // waves per block, stacked along y
 // loses with the same arrangement — 36.1 -> 39.8 us — and keeps its four waves stacked.)
 constexpr int MAX_ROWS_PER_WAVE = 64; // output row pairs per wave strip (fewer on small levels, to keep the chip full); 64 instead of 32: half the halo rows, forward 37 -> 34.5 us per 4096x4096 plane
 
+// Where the pictures of a launch that reads / writes pixels lie when they are windows of a larger frame (dwtx_pixels):
+// picture i is window first + i of a grid of bands of `cols` windows, the windows of a band `ps` samples apart (the
+// launch's src_ps / ll_ps / dst_ps), the bands band_ps.  cols == 0: one band, picture i at i * ps as ever.
+struct WinGrid {
+	unsigned cols, first;
+	long band_ps;
+};
+
+// The one place the kernels take a window's first sample from: its offset from the grid's origin, in samples.  The
+// picture's index is the same for a whole wave, so the division is scalar arithmetic (readfirstlane says so where the
+// index was computed from a vector register), and a one-band launch pays a compare for it.
+__device__ __forceinline__ long win_off(const WinGrid &g, long ps, int image)
+{
+	if (g.cols == 0)
+		return image * ps;
+	const unsigned i = (unsigned)__builtin_amdgcn_readfirstlane(image) + g.first;
+	const unsigned band = i / g.cols;
+	return (long)band * g.band_ps + (long)(i - band * g.cols) * ps;
+}
+
 struct LevelArgs {
 	const int *src;  long src_ps;  int spitch;  // forward: input w*h      | inverse: LL (w2*h2)
 	int *ll;         long ll_ps;   int llpitch; // forward: LL out (w2*h2) | inverse: output w*h
@@ -44,6 +64,7 @@ struct LevelArgs {
 	const short *src16;    // forward, or null: the input band as 16-bit values (pitch and plane stride of src)
 	short *ll16;           // forward, or null: the LL band goes out as 16-bit values (pitch and plane stride of ll)
 	int maxval;            // deep pixels (uint16_t samples behind src8 / dst8, strides in samples): the inverse's clamps; 0 = 8-bit pixels
+	WinGrid grid;          // the windows behind src8 / dst8 (src_ps / ll_ps apart in a band)
 };
 
 // ---------------------------------------------------------------- forward ---
@@ -414,12 +435,12 @@ __device__ __forceinline__ void st2(int *p, I2 v)
 __device__ __forceinline__ const uint8_t *fwd_base(SrcTag<uint8_t>, const LevelArgs &a, int plane, int &ch)
 {
 	ch = 0;
-	return a.src8 + plane * a.src_ps;
+	return a.src8 + win_off(a.grid, a.src_ps, plane);
 }
 __device__ __forceinline__ const uint8_t *fwd_base(SrcTag<Rgb8>, const LevelArgs &a, int plane, int &ch)
 {
 	ch = plane % 3;
-	return a.src8 + (plane / 3) * a.src_ps;   // src_ps = bytes per interleaved image, spitch = bytes per row
+	return a.src8 + win_off(a.grid, a.src_ps, plane / 3);   // src_ps = bytes from an interleaved image to the next, spitch = bytes per row
 }
 
 // Workgroups are dealt round-robin over the 8 XCDs (each with an L2 of its own): with the plain mapping the
@@ -629,7 +650,7 @@ template <>
 struct SrcBand<SRC_U16> {
 	typedef const uint16_t *ptr;
 	typedef FwdRawU raw;
-	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &) { return reinterpret_cast<const uint16_t *>(a.src8) + plane * a.src_ps; }
+	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &) { return reinterpret_cast<const uint16_t *>(a.src8) + win_off(a.grid, a.src_ps, (int)plane); }
 	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads) { return lane_at_i(q, lane, nquads); }
 	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at)
 	{
@@ -655,7 +676,7 @@ struct SrcBand<SRC_RGB16> {
 	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &ch)
 	{
 		ch = (int)(plane % 3);
-		return reinterpret_cast<const uint16_t *>(a.src8) + (plane / 3) * a.src_ps;
+		return reinterpret_cast<const uint16_t *>(a.src8) + win_off(a.grid, a.src_ps, (int)(plane / 3));
 	}
 	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads)
 	{
@@ -1566,6 +1587,11 @@ template <>
 __device__ __forceinline__ uint8_t *inv_dst<uint8_t>(const LevelArgs &a) { return a.dst8; }
 template <>
 __device__ __forceinline__ uint16_t *inv_dst<uint16_t>(const LevelArgs &a) { return reinterpret_cast<uint16_t *>(a.dst8); }   // (ll_ps, llpitch in samples)
+// (planes lie one after the other; pixels may be windows of a frame)
+template <typename DstT>
+__device__ __forceinline__ long inv_dst_off(const LevelArgs &a, int plane) { return win_off(a.grid, a.ll_ps, plane); }
+template <>
+__device__ __forceinline__ long inv_dst_off<int>(const LevelArgs &a, int plane) { return plane * a.ll_ps; }
 
 // The vertical state of one plane between row pairs: detail rows dl / dh and even rows el / eh of the current pair.
 struct InvCols {
@@ -1683,7 +1709,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 	const typename DetPtr<F16>::type det = DetPtr<F16>::of(a, plane);
 	typedef InvRawT<F16> InvRaw;
 	typedef OutRow<DstT> Out;
-	DstT *dst = inv_dst<DstT>(a) + plane * a.ll_ps;
+	DstT *dst = inv_dst<DstT>(a) + inv_dst_off<DstT>(a, plane);
 	const InvAt at = inv_at(a, qd, A.nquads);
 
 	constexpr int S = 2;
@@ -1756,6 +1782,7 @@ struct Inv2Args {
 	int mpw;          // level k+1 row pairs per wave strip
 	const short *det16;   // F16: the detail bands of BOTH levels as 16-bit values (positions, pitch and plane stride of det)
 	uint8_t *dst8;        // 8-bit output (the finest level of a gray picture: pnm.h:108's clamp fused), dst_ps / opitch in bytes
+	WinGrid grid;         // the windows behind dst8 (dst_ps apart in a band)
 };
 constexpr int V2_FIRST = 4, V2_OWN = 56;
 
@@ -1837,7 +1864,7 @@ struct OutPlane {
 template <>
 struct OutPlane<uint8_t> {
 	typedef unsigned row;
-	static __device__ __forceinline__ uint8_t *of(const Inv2Args &a, long plane) { return a.dst8 + plane * a.dst_ps; }
+	static __device__ __forceinline__ uint8_t *of(const Inv2Args &a, long plane) { return a.dst8 + win_off(a.grid, a.dst_ps, (int)plane); }
 	static __device__ __forceinline__ void store(uint8_t *p, unsigned v) { __builtin_nontemporal_store(v, reinterpret_cast<unsigned *>(p)); }
 };
 
@@ -2069,7 +2096,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 		det[ch] = DetPtr<F16>::of(a, 3 * image + ch);
 	}
 	typedef RgbOut<PixT> Out;
-	uint8_t *dst = a.dst8 + image * a.ll_ps * (long)sizeof(PixT);
+	uint8_t *dst = a.dst8 + win_off(a.grid, a.ll_ps, image) * (long)sizeof(PixT);
 	const InvAt at = inv_at(a, qd, A.nquads);
 
 	// (one row pair per batch: three planes' worth of arithmetic lies between two waits as it is)
@@ -2141,7 +2168,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 		ll2[ch] = a.ll2 + (long)(3 * image + ch) * a.ll2_ps + qc;
 		det[ch] = DetBand<F16>::of(a, 3 * image + ch);
 	}
-	uint8_t *dst = a.dst8 + image * a.dst_ps;
+	uint8_t *dst = a.dst8 + win_off(a.grid, a.dst_ps, image);
 	auto load2 = [&](int ch, int m) {
 		const int mm = min(max(m, 0), h4 - 1);
 		Raw2 r = { ll2[ch][(long)mm * a.ll2pitch], (int)det[ch][(long)mm * a.dpitch + w4 + qc], (int)det[ch][(long)(h4 + mm) * a.dpitch + qc],
@@ -2392,27 +2419,40 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_inv_tail(TailArgs t)
 
 // ------------------------------------------------------- pixels <-> planes ---
 
+// Where the windows of a view lie (dwtx_pixels; win_off finds window i), in samples, and the planes' side of the
+// conversion: W x H pixels of C channels per window, n windows.
+struct PixGrid {
+	long image_stride, row_pitch;
+	WinGrid grid;
+	int W, H, C, n;
+};
+
+constexpr int PX_LANES = 64, PX_ROWS = 4;   // a workgroup of the conversions: one wave per row, a lane per pixel
+
 // pnm.h:69-74 (byte -> int) fused with image.h:52-65 rgb2ycocg.  P = uint8_t, or uint16_t for deep pixels (the same
-// arithmetic: nothing in it knows the depth).
+// arithmetic: nothing in it knows the depth).  grid: (64 pixels of a row, 4 rows, window): a wave reads 64 neighbouring
+// pixels of one row, and nothing divides per sample.
 template <class P>
-__global__ __launch_bounds__(256) void k_planes_from_pixels(int *__restrict__ planes, const P *__restrict__ pix,
-	long npix_per_image, int C, long total_pixels)
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *__restrict__ planes, const P *__restrict__ pix, PixGrid g)
 {
-	long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-	const long stride = (long)gridDim.x * blockDim.x;
-	for (; i < total_pixels; i += stride) {
-		const long img = i / npix_per_image, off = i - img * npix_per_image;
-		int *dst = planes + img * C * npix_per_image + off;
-		if (C == 1) {
-			dst[0] = pix[i];
+	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
+	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
+	if (x >= g.W || y >= g.H)
+		return;
+	const long npix = (long)g.W * g.H;
+	for (unsigned win = blockIdx.z; win < (unsigned)g.n; win += gridDim.z) {
+		const P *row = pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
+		int *dst = planes + (long)win * g.C * npix + (long)y * g.W + x;
+		if (g.C == 1) {
+			dst[0] = row[x];
 		} else {
-			const int r = pix[3 * i], g = pix[3 * i + 1], b = pix[3 * i + 2];
+			const int r = row[3 * x], gr = row[3 * x + 1], b = row[3 * x + 2];
 			const int co = r - b;
 			const int t = b + tdiv2(co);
-			const int cg = g - t;
+			const int cg = gr - t;
 			dst[0] = t + tdiv2(cg);
-			dst[npix_per_image] = co;
-			dst[2 * npix_per_image] = cg;
+			dst[npix] = co;
+			dst[2 * npix] = cg;
 		}
 	}
 }
@@ -2423,29 +2463,32 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi)
 }
 
 // image.h:39-50 ycocg2rgb (input clamps included) + pnm.h:108 output clamp, with M (the pixels' maxval) where the
-// reference has 255: Y and the output to [0, M], Co and Cg to [-M, M].  P = uint8_t (M = 255) or uint16_t.
+// reference has 255: Y and the output to [0, M], Co and Cg to [-M, M].  P = uint8_t (M = 255) or uint16_t.  Same grid as
+// above; only the W*C samples of a window's H rows are written.
 template <class P>
-__global__ __launch_bounds__(256) void k_pixels_from_planes(P *__restrict__ pix, const int *__restrict__ planes,
-	long npix_per_image, int C, long total_pixels, int M)
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, int M)
 {
-	long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-	const long stride = (long)gridDim.x * blockDim.x;
-	for (; i < total_pixels; i += stride) {
-		const long img = i / npix_per_image, off = i - img * npix_per_image;
-		const int *src = planes + img * C * npix_per_image + off;
-		if (C == 1) {
-			pix[i] = (P)clampi(src[0], 0, M);
+	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
+	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
+	if (x >= g.W || y >= g.H)
+		return;
+	const long npix = (long)g.W * g.H;
+	for (unsigned win = blockIdx.z; win < (unsigned)g.n; win += gridDim.z) {
+		P *row = pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
+		const int *src = planes + (long)win * g.C * npix + (long)y * g.W + x;
+		if (g.C == 1) {
+			row[x] = (P)clampi(src[0], 0, M);
 		} else {
-			const int y = clampi(src[0], 0, M);
-			const int co = clampi(src[npix_per_image], -M, M);
-			const int cg = clampi(src[2 * npix_per_image], -M, M);
-			const int t = y - tdiv2(cg);
-			const int g = cg + t;
+			const int yy = clampi(src[0], 0, M);
+			const int co = clampi(src[npix], -M, M);
+			const int cg = clampi(src[2 * npix], -M, M);
+			const int t = yy - tdiv2(cg);
+			const int gr = cg + t;
 			const int b = t - tdiv2(co);
 			const int r = b + co;
-			pix[3 * i] = (P)clampi(r, 0, M);
-			pix[3 * i + 1] = (P)clampi(g, 0, M);
-			pix[3 * i + 2] = (P)clampi(b, 0, M);
+			row[3 * x] = (P)clampi(r, 0, M);
+			row[3 * x + 1] = (P)clampi(gr, 0, M);
+			row[3 * x + 2] = (P)clampi(b, 0, M);
 		}
 	}
 }
@@ -2489,6 +2532,8 @@ struct LiftLayout {
 	int *level1, *small;   // null where no step needs them
 };
 
+WinGrid win_grid(const dwtx_pixels &px) { return WinGrid{ (unsigned)px.cols, (unsigned)px.first, (long)px.band_stride }; }
+
 // ctx null: the sizes only
 int lift_layout(dwtx_ctx *ctx, int W, int H, int nplanes, LiftLayout &L)
 {
@@ -2531,18 +2576,25 @@ extern "C" int dwtx_synth_pixels(dwtx_ctx *ctx, uint8_t *pix, int W, int H, int 
 	return DWTX_OK;
 }
 
+// the conversions' view of px and their launch grid
+static PixGrid pix_grid(const dwtx_pixels &px, int W, int H, int n, dim3 *grid)
+{
+	*grid = dim3((unsigned)dwtx_cdiv(W, PX_LANES), (unsigned)dwtx_cdiv(H, PX_ROWS), (unsigned)min(n, 65535));
+	return PixGrid{ (long)px.image_stride, (long)px.pitch(W), win_grid(px), W, H, px.channels, n };
+}
+
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
 {
 	const int C = px.channels;
 	if (!ctx || !planes || !px.base || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || !px.sample_aligned())
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
-	const long npix = (long)W * H, total = npix * n;
-	const dim3 blocks((unsigned)min((total + 255) / 256, (long)256 * 16));
+	dim3 grid;
+	const PixGrid g = pix_grid(px, W, H, n, &grid);
 	if (!px.deep())
-		hipLaunchKernelGGL(k_planes_from_pixels<uint8_t>, blocks, dim3(256), 0, ctx->stream, planes, px.u8(), npix, C, total);
+		hipLaunchKernelGGL(k_planes_from_pixels<uint8_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, px.u8(), g);
 	else
-		hipLaunchKernelGGL(k_planes_from_pixels<uint16_t>, blocks, dim3(256), 0, ctx->stream, planes, px.u16(), npix, C, total);
+		hipLaunchKernelGGL(k_planes_from_pixels<uint16_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, px.u16(), g);
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
@@ -2555,12 +2607,12 @@ int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *p
 	if (!dwtx_maxval_ok(px.maxval))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
-	const long npix = (long)W * H, total = npix * n;
-	const dim3 blocks((unsigned)min((total + 255) / 256, (long)256 * 16));
+	dim3 grid;
+	const PixGrid g = pix_grid(px, W, H, n, &grid);
 	if (!px.deep())
-		hipLaunchKernelGGL(k_pixels_from_planes<uint8_t>, blocks, dim3(256), 0, ctx->stream, px.u8(), planes, npix, C, total, px.maxval);
+		hipLaunchKernelGGL(k_pixels_from_planes<uint8_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, px.u8(), planes, g, px.maxval);
 	else
-		hipLaunchKernelGGL(k_pixels_from_planes<uint16_t>, blocks, dim3(256), 0, ctx->stream, px.u16(), planes, npix, C, total, px.maxval);
+		hipLaunchKernelGGL(k_pixels_from_planes<uint16_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, px.u16(), planes, g, px.maxval);
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
@@ -2728,7 +2780,8 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 		if (pix_in) {   // (deep pixels: uint16_t samples behind src8; src_ps and spitch count samples either way)
 			a.src8 = px->u8();
 			a.src_ps = (long)px->image_stride;
-			a.spitch = px->channels * W;
+			a.spitch = (int)px->pitch(W);
+			a.grid = win_grid(*px);
 		} else {
 			a.src = src;
 			a.src_ps = src_ps;
@@ -2800,9 +2853,12 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 }
 
 // Can the finest level of a W*H image read / write these pixels directly?  (wide kernel, not the LDS tail)
+// Windows of a frame too (dwtx_pixels: row pitch, bands): the kernels touch only the W * channels samples of a window's
+// rows, so all they ask is that every row of every window starts on a quad (px.wide()) and that the pitch fits their int.
+// Any other view goes through the general conversions (dwtx_pixels_to_planes / dwtx_planes_to_pixels).
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H)
 {
-	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide();
+	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide() && px.pitch(W) <= 0x7fffffffu;
 }
 
 unsigned dwtx_levels16(int W, int H, unsigned sq_levels)
@@ -2971,7 +3027,8 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 			if (pix_out) {
 				f.dst8 = px->u8();
 				f.dst_ps = (long)px->image_stride;
-				f.opitch = px->channels * W;
+				f.opitch = (int)px->pitch(W);
+				f.grid = win_grid(*px);
 			} else if (t - 1 == 0) {
 				f.dst = out;
 				f.dst_ps = full_ps;
@@ -3009,7 +3066,8 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 		if (pix_out) {   // (deep pixels: uint16_t samples behind dst8; ll_ps and llpitch count samples either way)
 			a.dst8 = px->u8();
 			a.ll_ps = (long)px->image_stride;
-			a.llpitch = px->channels * W;
+			a.llpitch = (int)px->pitch(W);
+			a.grid = win_grid(*px);
 			a.maxval = px->deep() ? px->maxval : 0;
 		} else if (t == 0) {
 			a.ll = out;

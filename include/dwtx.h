@@ -329,6 +329,55 @@ int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 	const unsigned long long *dev_lens, int W, int H, int C, int n, int levels_max,
 	uint16_t *dev_pix, size_t pix_stride, int maxval, dwtx_decode_info *host_info);
 
+/* ---- strided views: windows and tile grids of a larger frame ------------------------------------------------------
+ * dwtx_encode_device / dwtx_decode_device (and their 16 versions) for pictures that are parts of something larger that
+ * stays where it is in HBM: a crop, a pitch-aligned surface, a stack of padded pictures, or the tiles of a frame too big
+ * to code whole — n same-geometry W x H windows, addressed by a row pitch and a grid.  All strides count SAMPLES, as in
+ * the *16 calls.  Window i starts at dev + (i / cols) * band_stride + (i % cols) * image_stride, its row y row_pitch * y
+ * further on.  Three layouts: a stack of padded pictures (cols = 0); a row of windows side by side in one frame
+ * (image_stride = W*channels, row_pitch = the frame's width * channels); a whole tile grid in one call (cols tiles per
+ * band, band_stride = H * row_pitch). */
+typedef struct dwtx_view {
+	void  *dev;            /* first sample of window 0 */
+	int    sample_bytes;   /* 1: uint8_t, 2: native-endian uint16_t (deep pixels) */
+	int    channels;       /* 1 or 3, interleaved */
+	int    maxval;         /* decode: clamp bound (255 required when sample_bytes == 1); encode ignores it */
+	int    cols;           /* windows per band; 0 or >= n: all n windows in one band */
+	size_t row_pitch;      /* samples from a window's row to its next row, >= W*channels */
+	size_t image_stride;   /* samples from a window to the next one of its band */
+	size_t band_stride;    /* samples from a band's first window to the next band's */
+} dwtx_view;
+
+/* dwtx_encode_device / dwtx_encode_device16 from a view: stream i and dev_info[i] are those of window i's pixels, the same
+ * bytes as from a dense copy.  Only the W*channels samples of a window's H rows are read; windows may overlap.
+ * DWTX_ERR_ARG (with a dwtx_last_error() text): row_pitch < W*channels, dev not aligned to sample_bytes. */
+int dwtx_encode_view(dwtx_ctx *ctx, const dwtx_view *src, int W, int H, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
+/* dwtx_decode_device / dwtx_decode_device16 into a view.  A stream that supports only ow x oh (cut short, or levels_max)
+ * is written into its window's top-left corner, rows row_pitch apart; no sample outside the ow x oh rectangle of a window
+ * is written — not in the rest of the window and not in the frame around it.  The windows must be provably disjoint, else
+ * DWTX_ERR_ARG and nothing is written: with cols_eff = min(cols ? cols : n, n), either
+ *   image_stride >= (H-1)*row_pitch + W*channels                                            (stacked), or
+ *   image_stride >= W*channels and row_pitch >= (cols_eff-1)*image_stride + W*channels      (side by side);
+ * and with more than one band, band_stride >= (cols_eff-1)*image_stride + (H-1)*row_pitch + W*channels. */
+int dwtx_decode_view(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max,
+	const dwtx_view *dst, dwtx_decode_info *host_info);
+
+/* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
+ * interior, right column, bottom row, corner, in that order, those that exist — each a cols x rows grid of W x H tiles
+ * whose first tile's corner is (x0, y0): one dwtx_encode_view / dwtx_decode_view call per group.  Per axis, with
+ * rem = side % tile: rem == 0 gives side / tile tiles; rem >= 8 one more tile of rem; 0 < rem < 8 widens the last tile to
+ * tile + rem; side < tile gives one tile of side — every tile side lies in [8, tile + 7].  tile >= 8 and a multiple of 4,
+ * frame sides >= 8 (and of any size: only the tiles' sides have to meet DWTX_MAX_SIDE), else DWTX_ERR_ARG.  Returns the
+ * number of groups.  A tiled frame is that many ordinary .dwt streams plus the caller's knowledge of the plan. */
+typedef struct dwtx_tile_group {
+	int x0, y0;
+	int W, H;
+	int cols, rows;
+} dwtx_tile_group;
+int dwtx_tile_groups(int frameW, int frameH, int tile, dwtx_tile_group out[4]);
+
 /* The sender's side of the one exchange step between GPUs (the encoded streams of a step travel to one
  * rank; no reference counterpart — the reference writes one file per process): the n streams of a batch, stream i at
  * dev_streams + i*stream_stride with dev_lens[i] bytes (as dwtx_encode_device leaves them), are moved together into ONE
