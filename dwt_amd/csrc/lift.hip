@@ -2650,10 +2650,33 @@ static int fill_chip(int start, int floor, long strips, int rows)
 	return r;
 }
 
-// row pairs per wave of the one-level kernels (their waves are counted on h2 rounded up to whole strips of the start)
-static int pick_rpw(int strips_x, int h2, int nplanes)
+// DWTX_OPT_LIFT_ROWS: 0, or the row pairs per wave strip that every one-level launch of the context takes instead of
+// fill_chip()'s choice (the two-level launches an eighth of it) — the launch shapes a large batch gets, on any batch
+static int forced_rows(const dwtx_ctx *ctx, int *forced)
 {
+	const long v = ctx->opt[DWTX_OPT_LIFT_ROWS];
+	if (v != 0 && v != 4 && v != 8 && v != 16 && v != 32 && v != MAX_ROWS_PER_WAVE) {
+		dwtx_set_error("DWTX_OPT_LIFT_ROWS is %ld: it takes 0 (automatic), 4, 8, 16, 32 or %d row pairs per wave strip", v, MAX_ROWS_PER_WAVE);
+		return DWTX_ERR_ARG;
+	}
+	*forced = (int)v;
+	return DWTX_OK;
+}
+
+// row pairs per wave of the one-level kernels (their waves are counted on h2 rounded up to whole strips of the start)
+static int pick_rpw(int strips_x, int h2, int nplanes, int forced)
+{
+	if (forced)
+		return forced;
 	return fill_chip(MAX_ROWS_PER_WAVE, 4, (long)strips_x * nplanes, dwtx_cdiv(h2, MAX_ROWS_PER_WAVE) * MAX_ROWS_PER_WAVE);
+}
+
+// coarse row pairs per wave of the two-level kernels
+static int pick_mpw(int strips_x, int h4, int nplanes, int forced)
+{
+	if (forced)
+		return forced / 8 > 2 ? forced / 8 : 2;
+	return fill_chip(F2_MPW, 2, (long)strips_x * nplanes, h4);
 }
 
 // the LDS tail's steps tail_from .. T-1 of a pyramid; the caller adds the plane it reads (forward) or writes (inverse)
@@ -2707,6 +2730,9 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 	if (!ctx || !out || (!in && !px) || W < 2 || H < 2 || nplanes < 1 || nplanes > 65535)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
+	int forced;
+	if (const int rc = forced_rows(ctx, &forced))
+		return rc;
 	LiftLayout L;
 	if (const int rc = lift_layout(ctx, W, H, nplanes, L))
 		return rc;
@@ -2762,7 +2788,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			f.h = hs[t];
 			f.nquads = ws[t] / 4;
 			const int strips = dwtx_cdiv(f.nquads, F2_OWN), h4 = hs[t] / 4;
-			f.mpw = fill_chip(F2_MPW, 2, (long)strips * nplanes, h4);
+			f.mpw = pick_mpw(strips, h4, nplanes, forced);
 			hipLaunchKernelGGL(k_fwd2_level_w, dim3(dwtx_cdiv(strips, WAVES), dwtx_cdiv(h4, f.mpw), nplanes), dim3(64 * WAVES), 0, ctx->stream, f);
 			DWTX_LAUNCH_CHECK();
 			src = f.ll2;
@@ -2818,7 +2844,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			LevelArgsW A{};
 			A.nquads = a.w / 4;
 			const int strips = dwtx_cdiv(A.nquads, 64);
-			a.rpw = pick_rpw(strips, a.h2, nplanes);
+			a.rpw = pick_rpw(strips, a.h2, nplanes, forced);
 			A.wx_log2 = strips >= 4 ? 2 : strips >= 2 ? 1 : 0;
 			A.a = a;
 			if (hist_here) {
@@ -2833,7 +2859,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			hipLaunchKernelGGL(fwd_wide_kernel(pix_in, hist_here, a.src16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {
 			const int sx = dwtx_cdiv(a.w2, 64);
-			a.rpw = pick_rpw(sx, a.h2, nplanes);
+			a.rpw = pick_rpw(sx, a.h2, nplanes, forced);
 			hipLaunchKernelGGL(k_fwd_level, dim3(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), nplanes), dim3(64 * WAVES), 0, ctx->stream, a);
 		}
 		DWTX_LAUNCH_CHECK();
@@ -2931,6 +2957,9 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 	if (!ctx || (!out && !px) || !in || W < 2 || H < 2 || nplanes < 1 || nplanes > 65535)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
+	int forced;
+	if (const int rc = forced_rows(ctx, &forced))
+		return rc;
 	LiftLayout L;
 	if (const int rc = lift_layout(ctx, W, H, nplanes, L))
 		return rc;
@@ -3042,7 +3071,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 			f.h = hs[t - 1];
 			f.nquads = f.w / 4;
 			const int strips = dwtx_cdiv(f.nquads, V2_OWN), h4 = f.h / 4;
-			f.mpw = fill_chip(F2_MPW, 2, (long)strips * nplanes, h4);
+			f.mpw = pick_mpw(strips, h4, nplanes, forced);
 			// (the 8-bit kernels put a block's waves side by side; RGB: three planes per wave)
 			const dim3 grid = pix_out ? dim3(dwtx_cdiv(strips, WAVES), dwtx_cdiv(h4, f.mpw), nplanes / px->channels)
 			                          : dim3(strips, dwtx_cdiv(h4, WAVES * f.mpw), nplanes);
@@ -3097,13 +3126,13 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 			A.nquads = a.w / 4;
 			const bool rgb = pix_out && px->channels == 3;
 			const int sx = dwtx_cdiv(A.nquads, rgb ? INV_QUADS : 64);   // (the RGB kernel's waves overlap by a lane on each side)
-			a.rpw = pick_rpw(sx, a.h2, nplanes);
+			a.rpw = pick_rpw(sx, a.h2, nplanes, forced);
 			A.a = a;
 			const dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), rgb ? nplanes / 3 : nplanes);
 			hipLaunchKernelGGL(inv_wide_kernel(pix_out, a.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {
 			const int sx = dwtx_cdiv(a.w2, INV_PAIRS);
-			a.rpw = pick_rpw(sx, a.h2, nplanes);
+			a.rpw = pick_rpw(sx, a.h2, nplanes, forced);
 			hipLaunchKernelGGL(k_inv_level, dim3(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), nplanes), dim3(64 * WAVES), 0, ctx->stream, a);
 		}
 		DWTX_LAUNCH_CHECK();

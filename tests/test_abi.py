@@ -52,3 +52,16 @@ def test_no_gpu_fails_loudly():
 
     with pytest.raises(RuntimeError):
         dwt_amd.Context(0)
+
+
+def test_option_names_follow_the_enum():
+    """dwt_amd/_lib.py's OPTIONS: one name per entry of enum dwtx_option, in the enum's order."""
+    from dwt_amd import _lib
+
+    text = open(os.path.join(ROOT, "include", "dwtx.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    body = re.search(r"enum dwtx_option\s*\{(.*?)\}", text, flags=re.S).group(1)
+    entries = re.findall(r"\bDWTX_OPT_([A-Z0-9_]+)", body)
+    assert entries[-1] == "COUNT"
+    assert [e.lower() for e in entries[:-1]] == list(_lib.OPTIONS)
+    assert list(_lib.OPTIONS.values()) == list(range(len(entries) - 1))

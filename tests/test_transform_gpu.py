@@ -146,11 +146,13 @@ def test_pixel_transforms_refuse_shapes_their_kernels_do_not_take(ctx):
 
 @pytest.mark.parametrize("shape", [(68, 244), (132, 248), (260, 488), (516, 492), (72, 976), (128, 980), (388, 1220), (1080, 1920), (2048, 2048),
                                    (68, 68), (512, 4), (260, 8), (1028, 260), (68, 192), (132, 196), (260, 224), (516, 228), (1040, 448), (76, 452),
-                                   (4096, 96), (644, 3588)])
+                                   (4096, 96), (644, 3588), (132, 388)])
 def test_two_levels_per_pass_equal_one_launch_per_level(ctx, shape, opts):
     """k_fwd2_level_w / k_inv2_level_w (two levels of cdf53.h:9-61 / encode.c:16-30, decode.c:16-30 in one pass, the LL band between them never in memory):
-    widths around whole numbers of 61-quad wave strips, heights that end strips inside / at the end of a row pair of the
-    coarser level, the smallest shapes it takes — against the oracle, and the same bytes as one launch per level."""
+    widths around whole numbers of the waves' strips — F2_OWN = 48 quads forward (192, 196, 388: one strip, one quad into a
+    second, one quad into a third), V2_OWN = 56 quads inverse (224, 228, 448, 452) —, heights that end strips inside / at the
+    end of a row pair of the coarser level, the smallest shapes it takes — against the oracle, and the same bytes as one
+    launch per level."""
     import torch
 
     H, W = shape
