@@ -460,14 +460,17 @@ class Context:
 
     def _view(self, t, maxval):
         """View of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (uint8, or uint16 / int16 for deep pixels):
-        the windows stay where they are; only the channel and column strides must be those of interleaved pixels."""
+        the windows stay where they are.  RGB pixels are interleaved (channel stride 1, column stride 3) or planar (column
+        stride 1, any channel stride): `nchw.permute(0, 2, 3, 1)` and `chw.permute(1, 2, 0)` are views as they are."""
         torch = self.torch
         if t.dtype not in (torch.uint8, torch.uint16, torch.int16) or t.device != self.device or t.dim() not in (4, 5):
             raise ValueError("a view needs a uint8 / uint16 / int16 tensor [n,H,W,C] or [bands,cols,H,W,C] on the context's device")
         H, W, Cn = t.shape[-3:]
         sh, sw, sc = t.stride()[-3:]
-        if Cn not in (1, 3) or (Cn > 1 and sc != 1) or sw != Cn:
-            raise ValueError(f"a view needs interleaved pixels: channel stride 1 and column stride C, not {sc} and {sw} (C = {Cn})")
+        planar = Cn == 3 and sw == 1 and sc >= 1
+        if Cn not in (1, 3) or not (planar or (sw == Cn and (Cn == 1 or sc == 1))):
+            raise ValueError("a view needs 1 or 3 channels, RGB pixels either interleaved (channel stride 1, column stride 3) or planar "
+                             f"(column stride 1, any channel stride), not channel stride {sc} and column stride {sw} (C = {Cn})")
         deep = t.dtype != torch.uint8
         if maxval is None:
             maxval = 65535 if deep else 255
@@ -475,13 +478,13 @@ class Context:
             n, cols, band = t.shape[0], 0, 0
         else:
             n, cols, band = t.shape[0] * t.shape[1], t.shape[1], t.stride(0)
-        v = View(t.data_ptr(), 2 if deep else 1, Cn, maxval, cols, sh, t.stride(-4), band)
+        v = View(t.data_ptr(), 2 if deep else 1, Cn, maxval, cols, sh, t.stride(-4), band, sc if planar else 0)
         return v, W, H, Cn, n
 
     def encode_view(self, t, capacity=0, out=None, info=None):
         """dwtx_encode_view: the windows of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (a slice, a crop, a
-        grid of tiles: see _view) -> (streams uint8 [n,stride], info uint8 [n,sizeof(StreamInfo)]) on device, as
-        encode_device / encode_device16 give for the contiguous copy; async."""
+        grid of tiles, a channel-first batch permuted to channel-last: see _view) -> (streams uint8 [n,stride], info uint8
+        [n,sizeof(StreamInfo)]) on device, as encode_device / encode_device16 give for the contiguous copy; async."""
         torch = self.torch
         v, W, H, Cn, n = self._view(t, None)
         bound = self.lib.dwtx_encode_bound16 if v.sample_bytes == 2 else self.lib.dwtx_encode_bound

@@ -56,9 +56,10 @@ class Index(C.Structure):
 
 
 class View(C.Structure):
-    """dwtx_view: n same-geometry windows of a larger frame (include/dwtx.h); strides count samples."""
+    """dwtx_view: n same-geometry windows of a larger frame (include/dwtx.h); strides count samples.  channel_stride
+    (last; 0 when left out): planar RGB, three planes that far apart, instead of interleaved pixels."""
     _fields_ = [("dev", C.c_void_p), ("sample_bytes", C.c_int), ("channels", C.c_int), ("maxval", C.c_int), ("cols", C.c_int),
-                ("row_pitch", C.c_size_t), ("image_stride", C.c_size_t), ("band_stride", C.c_size_t)]
+                ("row_pitch", C.c_size_t), ("image_stride", C.c_size_t), ("band_stride", C.c_size_t), ("channel_stride", C.c_size_t)]
 
 
 class TileGroup(C.Structure):

@@ -374,7 +374,8 @@ static int pixels_of_view(const dwtx_view *v, int W, int H, int n, bool dst, dwt
 		dwtx_set_error("view: sample_bytes %d (1 or 2), channels %d (1 or 3), cols %d (>= 0)", v->sample_bytes, v->channels, v->cols);
 		return DWTX_ERR_ARG;
 	}
-	const size_t row = (size_t)W * v->channels;
+	const size_t cs = v->channels == 3 ? v->channel_stride : 0;   // planar RGB; a gray view has no use for it
+	const size_t row = cs ? (size_t)W : (size_t)W * v->channels;  // a row of a window (planar: of one of its planes)
 	if (v->row_pitch < row) {
 		dwtx_set_error("view: row_pitch %zu is less than a window's row of %zu samples", v->row_pitch, row);
 		return DWTX_ERR_ARG;
@@ -391,22 +392,36 @@ static int pixels_of_view(const dwtx_view *v, int W, int H, int n, bool dst, dwt
 				dwtx_set_error("view: maxval %d with 1-byte samples (255)", v->maxval);
 			return DWTX_ERR_ARG;
 		}
-		const size_t window = (size_t)(H - 1) * v->row_pitch + row;   // from a window's first sample to behind its last
+		const size_t window = (size_t)(H - 1) * v->row_pitch + row;   // from a window's (a plane's) first sample to behind its last
 		const bool stacked = v->image_stride >= window;
 		const bool beside = v->image_stride >= row && v->row_pitch >= (cols - 1) * v->image_stride + row;
-		if (cols > 1 && !stacked && !beside) {
+		// planar, first form: a window holds its three planes (an NCHW stack): the windows are then 2 * cs + window long
+		const size_t win3 = 2 * cs + window;
+		const bool inside = cs >= window && (cols == 1 || v->image_stride >= win3) && (!bands || v->band_stride >= (cols - 1) * v->image_stride + win3);
+		if (cs && inside)
+			;   // (disjoint as they are)
+		else if (cols > 1 && !stacked && !beside) {
 			dwtx_set_error("view: windows overlap (image_stride %zu, row_pitch %zu, %zu windows per band of %zu x %d samples)",
 				v->image_stride, v->row_pitch, cols, row, H);
 			return DWTX_ERR_ARG;
-		}
-		if (bands && v->band_stride < (cols - 1) * v->image_stride + window) {
+		} else if (bands && v->band_stride < (cols - 1) * v->image_stride + window) {
 			dwtx_set_error("view: bands overlap (band_stride %zu, a band spans %zu samples)", v->band_stride, (cols - 1) * v->image_stride + window);
 			return DWTX_ERR_ARG;
+		} else if (cs) {
+			// planar, second form: the channel planes of the whole view apart (a CHW frame and its tiles, CNHW)
+			const size_t nbands = ((size_t)n + cols - 1) / cols;
+			const size_t span = (nbands - 1) * (bands ? v->band_stride : 0) + (cols - 1) * v->image_stride + window;
+			if (cs < span) {
+				dwtx_set_error("view: planes overlap (channel_stride %zu: neither at least a window's plane of %zu samples with windows of %zu apart, "
+					"nor at least one channel of the whole view, %zu samples)", cs, window, win3, span);
+				return DWTX_ERR_ARG;
+			}
 		}
 	}
 	*px = v->sample_bytes == 1 ? dwtx_pixels8((const uint8_t *)v->dev, v->channels, v->image_stride)
 		: dwtx_pixels16((const uint16_t *)v->dev, v->channels, v->image_stride, dst ? v->maxval : 65535);
 	px->row_pitch = v->row_pitch;
+	px->channel_stride = cs;
 	if (bands) {
 		px->cols = (int)cols;
 		px->band_stride = v->band_stride;

@@ -149,22 +149,25 @@ template <class F> char *carve(dwtx_ctx *ctx, int slot, F &&fn)
 	return c.base;
 }
 
-// A batch of interleaved pictures in memory (device memory, or the host buffers codec.hip stages them from / to): the
+// A batch of pictures in memory (device memory, or the host buffers codec.hip stages them from / to): the
 // reference's bytes, or deep pixels (include/dwtx.h: native-endian uint16_t samples).  The one place that knows how a
 // sample offset becomes an address: everything that is counted here — the strides, the argument of at() — counts
 // samples, whatever their size.  (A view of a source is only read; the view does not say which it is.)
 // The pictures may be windows of a larger frame (include/dwtx.h, dwtx_view): rows row_pitch apart, the windows a grid of
 // bands of `cols` each.  Window i of the view is window first + i of the grid, which starts at `base`.
+// RGB samples are interleaved, or planar (channel_stride != 0, views only: include/dwtx.h): three planes per window,
+// columns one sample apart; the host-buffer pipelines and every dense entry point stay interleaved.
 struct dwtx_pixels {
 	void *base;            // the grid's window 0, first sample
 	int sample_bytes;      // 1 or 2
-	int channels;          // 1 gray, 3 interleaved RGB
+	int channels;          // 1 gray, 3 RGB (interleaved unless channel_stride says otherwise)
 	size_t image_stride;   // from a window to the next one of its band
 	int maxval;            // 255 for bytes; a deep picture's own (what the inverse direction clamps at)
 	size_t row_pitch = 0;  // from a row to the next; 0: dense rows — the width a call works at (a reduced decode's own) times channels
 	int cols = 0;          // windows per band; 0: one band
 	size_t band_stride = 0;   // from a band's first window to the next band's
 	size_t first = 0;      // the view's first window in the grid (parts of a batch start anywhere in it)
+	size_t channel_stride = 0;   // 0: interleaved; else planar RGB: from a window's plane of one channel to the next one's (image() and moved() keep it)
 
 	bool deep() const { return sample_bytes == 2; }
 	size_t bytes(size_t samples) const { return samples * (size_t)sample_bytes; }
@@ -174,7 +177,8 @@ struct dwtx_pixels {
 	uint8_t *u8() const { return static_cast<uint8_t *>(base); }
 	uint16_t *u16() const { return static_cast<uint16_t *>(base); }
 	bool one_band() const { return cols == 0; }
-	size_t pitch(int W) const { return row_pitch ? row_pitch : (size_t)W * channels; }
+	bool planar() const { return channel_stride != 0; }
+	size_t pitch(int W) const { return row_pitch ? row_pitch : (size_t)W * (planar() ? 1 : channels); }
 	// the same pictures from image i on: a one-band view moves its base (first stays 0), a grid keeps its origin and moves the index
 	dwtx_pixels image(size_t i) const
 	{
@@ -195,8 +199,12 @@ struct dwtx_pixels {
 	bool aligned(size_t a) const { return ((uintptr_t)base & (a - 1)) == 0; }
 	bool sample_aligned() const { return aligned((size_t)sample_bytes); }
 	// What lift.hip's wide kernels ask of the buffer when the finest level reads / writes the pixels itself: a lane's
-	// quad of samples — 4 bytes, 8 of a deep picture (gray; RGB lanes take three) — is one aligned access in every row of every image
-	bool wide() const { return image_stride % 4 == 0 && row_pitch % 4 == 0 && band_stride % 4 == 0 && aligned(4 * (size_t)sample_bytes); }
+	// quad of samples — 4 bytes, 8 of a deep picture (gray, and each plane of planar RGB; interleaved RGB lanes take three) — is
+	// one aligned access in every row of every image
+	bool wide() const
+	{
+		return image_stride % 4 == 0 && row_pitch % 4 == 0 && band_stride % 4 == 0 && channel_stride % 4 == 0 && aligned(4 * (size_t)sample_bytes);
+	}
 };
 static inline dwtx_pixels dwtx_pixels8(const uint8_t *pix, int channels, size_t image_stride)
 {
@@ -209,14 +217,14 @@ static inline dwtx_pixels dwtx_pixels16(const uint16_t *pix, int channels, size_
 
 // lift.hip: the finest lifting level reads / writes pixels itself (the widening of pnm.h:69-74, the clamp of pnm.h:108
 // and, for RGB, the YCoCg-R colour transform of image.h:39-65 fused into it).  dwtx_pixels_ok says whether the shape and
-// the buffer allow it: W % 4 == 0, more than 64 pixels on a side (the wide kernel, not the LDS tail), px.wide(), and
-// windows the kernels can address (lift.hip).
+// the buffer allow it: W % 4 == 0, more than 64 pixels on a side (the wide kernel, not the LDS tail), px.wide() (a planar
+// picture's channel stride on the quad grid too), and windows the kernels can address (lift.hip).
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H);
 // lift.hip: asks for the scratch planes every lifting call of a W*H transform over nplanes planes asks for
 int dwtx_lift_scratch(dwtx_ctx *ctx, int W, int H, int nplanes);
 // lift.hip: the general way between pixels and int32 planes [n*C][H][W] (pnm.h:69-74 / pnm.h:108, YCoCg-R if C == 3): what
 // the extern "C" conversions of include/dwtx.h run, and every view the wide kernels do not take: one launch for the n
-// windows, whatever their pitch, stride and grid; only the W*C samples of a window's H rows are read / written
+// windows, whatever their pitch, strides (a planar view's channel stride too) and grid; only the W*C samples of a window's H rows are read / written
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n);
 int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int n);
 

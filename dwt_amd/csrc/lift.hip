@@ -294,6 +294,8 @@ struct LevelArgsW {
 	int nquads;       // w / 4
 	int wx_log2;      // forward: 1 << wx_log2 waves of a block side by side
 	HistArgs hist;
+	long cstride;     // planar RGB pixels behind src8 / dst8 (dwtx_pixels::channel_stride, in samples): from a window's plane to its next; 0: interleaved.
+	                  // (Last, so that the interleaved kernels find their arguments where they were.)
 };
 
 // Per lane and subband: counts of "magnitude below 2^q" for q = 0..15 — nibbles of R for the last few coefficients
@@ -376,6 +378,8 @@ struct FwdRaw {
 // Where the finest forward level may read its samples instead of int32 planes: 8-bit gray pixels (pnm.h:69-74 fused)
 // or 8-bit interleaved RGB pixels, of which each plane's launch takes its own YCoCg-R channel (image.h:52-65 fused).
 struct Rgb8 {};
+// or 8-bit planar RGB pixels (dwtx_pixels::channel_stride): three gray-style rows per row, one per plane, no unpacking
+struct RgbP8 {};
 template <typename SrcT>
 struct SrcTag {};
 
@@ -442,6 +446,11 @@ __device__ __forceinline__ const uint8_t *fwd_base(SrcTag<Rgb8>, const LevelArgs
 	ch = plane % 3;
 	return a.src8 + win_off(a.grid, a.src_ps, plane / 3);   // src_ps = bytes from an interleaved image to the next, spitch = bytes per row
 }
+__device__ __forceinline__ const uint8_t *fwd_base(SrcTag<RgbP8>, const LevelArgs &a, int plane, int &ch)
+{
+	ch = plane % 3;
+	return a.src8 + win_off(a.grid, a.src_ps, plane / 3);   // channel 0's plane of the window; spitch = bytes per row of a plane
+}
 
 // Workgroups are dealt round-robin over the 8 XCDs (each with an L2 of its own): with the plain mapping the
 // strips left and right of a strip — whose edge sectors it also loads as halo — sit on other XCDs and those
@@ -486,6 +495,10 @@ struct IsRgb {
 };
 template <>
 struct IsRgb<Rgb8> {
+	static constexpr bool value = true;
+};
+template <>
+struct IsRgb<RgbP8> {
 	static constexpr bool value = true;
 };
 
@@ -624,15 +637,16 @@ __device__ __forceinline__ FwdRaw widen(const FwdRawRgb16 &r, int ch)
 }
 
 // the band a forward level reads, as the kernel variant sees it: int32 planes, 16-bit planes (dwtx_p16: the detail bands
-// go out as 16-bit values too), or — the finest level of a deep picture — uint16_t pixels, gray or interleaved RGB
-enum { SRC_I32 = 0, SRC_I16 = 1, SRC_U16 = 2, SRC_RGB16 = 3 };
+// go out as 16-bit values too), or — the finest level of a deep picture — uint16_t pixels, gray, interleaved RGB or planar RGB
+// (load()'s last argument: the planar pixels' channel stride, LevelArgsW::cstride; the others have no use for it)
+enum { SRC_I32 = 0, SRC_I16 = 1, SRC_U16 = 2, SRC_RGB16 = 3, SRC_RGBP16 = 4 };
 template <int SRC>
 struct SrcBand {
 	typedef const int *ptr;
 	typedef FwdRawI raw;
 	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &) { return a.src + plane * a.src_ps; }
 	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads) { return lane_at_i(q, lane, nquads); }
-	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at) { return fwd_load_i(row, at); }
+	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at, long) { return fwd_load_i(row, at); }
 	static __device__ __forceinline__ FwdRaw wide(const raw &r, int) { return widen(r); }
 	static __device__ __forceinline__ FwdRaw held(const raw &r, int) { return hold(r); }
 };
@@ -642,7 +656,7 @@ struct SrcBand<SRC_I16> {
 	typedef FwdRawS raw;
 	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &) { return a.src16 + plane * a.src_ps; }
 	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads) { return lane_at_i(q, lane, nquads); }
-	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at) { return fwd_load_i(row, at); }
+	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at, long) { return fwd_load_i(row, at); }
 	static __device__ __forceinline__ FwdRaw wide(const raw &r, int) { return widen(r); }
 	static __device__ __forceinline__ FwdRaw held(const raw &r, int) { return hold(r); }
 };
@@ -652,7 +666,7 @@ struct SrcBand<SRC_U16> {
 	typedef FwdRawU raw;
 	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &) { return reinterpret_cast<const uint16_t *>(a.src8) + win_off(a.grid, a.src_ps, (int)plane); }
 	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads) { return lane_at_i(q, lane, nquads); }
-	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at)
+	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at, long = 0)
 	{
 		raw r;
 		r.x = *reinterpret_cast<const uint2 *>(row + at.main);
@@ -684,7 +698,7 @@ struct SrcBand<SRC_RGB16> {
 		LaneAtI o = { 12 * qa, lane == 0 ? max(12 * qa - 6, 0) : min(12 * qa + 12, 12 * nquads - 6) };
 		return o;
 	}
-	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at)
+	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at, long)
 	{
 		raw r;
 		const uint2 *m = reinterpret_cast<const uint2 *>(row + at.main);
@@ -710,6 +724,49 @@ struct SrcBand<SRC_RGB16> {
 		return widen(h, ch);
 	}
 };
+// Planar RGB16: the same row of the window's three planes, each loaded as a gray deep row is (8 bytes for the lane's quad, a
+// word of neighbours, inside the row's own W samples of that plane); the plane's launch takes its channel of image.h:52-65
+struct FwdRawRgbU3 {
+	FwdRawU r, g, b;
+};
+__device__ __forceinline__ FwdRaw widen(const FwdRawRgbU3 &p, int ch)
+{
+	const FwdRaw r = widen(p.r), g = widen(p.g), b = widen(p.b);
+	FwdRaw o;
+	o.x.x = ycocg_ch(r.x.x, g.x.x, b.x.x, ch);
+	o.x.y = ycocg_ch(r.x.y, g.x.y, b.x.y, ch);
+	o.x.z = ycocg_ch(r.x.z, g.x.z, b.x.z, ch);
+	o.x.w = ycocg_ch(r.x.w, g.x.w, b.x.w, ch);
+	o.xr = ycocg_ch(r.xr, g.xr, b.xr, ch);
+	o.left = make_int2(o.xr, ycocg_ch(r.left.y, g.left.y, b.left.y, ch));
+	return o;
+}
+template <>
+struct SrcBand<SRC_RGBP16> {
+	typedef const uint16_t *ptr;
+	typedef FwdRawRgbU3 raw;
+	typedef SrcBand<SRC_U16> Gray;
+	// plane p = channel p % 3 of image p / 3; the pointer is channel 0's plane of the window, spitch = samples per row of a plane
+	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &ch) { return SrcBand<SRC_RGB16>::of(a, plane, ch); }
+	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads) { return lane_at_i(q, lane, nquads); }
+	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at, long cs)
+	{
+		raw r = { Gray::load(row, at), Gray::load(row + cs, at), Gray::load(row + 2 * cs, at) };
+		return r;
+	}
+	static __device__ __forceinline__ FwdRaw wide(const raw &r, int ch) { return widen(r, ch); }
+	static __device__ __forceinline__ FwdRaw held(const raw &r, int ch)
+	{
+		auto h = [](const FwdRawU &u) {
+			FwdRawU o;
+			o.x = make_uint2(hold(u.x.x), hold(u.x.y));
+			o.e = hold(u.e);
+			return o;
+		};
+		const raw k = { h(r.r), h(r.g), h(r.b) };
+		return widen(k, ch);
+	}
+};
 
 // Forward level on int32 planes (every level of dwtx_transformation_fwd; the levels below the finest in the codec).
 // Memory operations retire in order on this part (one counter for loads and stores): a wave that waits for rows it
@@ -722,7 +779,7 @@ struct SrcBand<SRC_RGB16> {
 // low-pass of cdf53.h:9-34 has an l1 norm of 1.5 per direction, the high-pass of 2 — i.e. 26 142 on the fifth level;
 // that bound is loose: the composed five-level response has an l1 norm of 7.95, 2 028 for 8-bit samples, and
 // tests/test_codec_gpu.py builds the picture that gets there); the arithmetic is int32 either way.
-// SRC_U16 / SRC_RGB16: the finest level of a deep picture reads its uint16_t pixels itself (widening and YCoCg-R fused);
+// SRC_U16 / SRC_RGB16 / SRC_RGBP16: the finest level of a deep picture reads its uint16_t pixels itself (widening and YCoCg-R fused);
 // everything it writes is int32.
 template <bool HIST, int SRC>
 __global__ __launch_bounds__(64 * WAVES) void k_fwd_level_w(LevelArgsW A)
@@ -752,13 +809,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_fwd_level_w(LevelArgsW A)
 	const int jfirst = j0 > 0 ? j0 - 1 : 0;
 	const LaneAtI at = Band::at(q, lane, A.nquads);
 	I2 l0, h0, pl = { 0, 0 }, ph = { 0, 0 };
-	fwd_lift_w(Band::wide(Band::load(src + (long)(2 * jfirst) * a.spitch, at), ch), q, lane, A.nquads, l0, h0);
+	fwd_lift_w(Band::wide(Band::load(src + (long)(2 * jfirst) * a.spitch, at, A.cstride), ch), q, lane, A.nquads, l0, h0);
 	auto rowp = [&](int r) { return src + (long)min(r, a.h - 1) * a.spitch; };
 	FwdRaw cur[2 * S];
 	typename Band::raw nxt[2 * S];
 #pragma unroll
 	for (int k = 0; k < 2 * S; ++k)
-		nxt[k] = Band::load(rowp(2 * jfirst + 1 + k), at);
+		nxt[k] = Band::load(rowp(2 * jfirst + 1 + k), at, A.cstride);
 	I2 osl[S], osh[S], odl[S], odh[S];   // a batch's results wait here for the next iteration's stores
 	auto store_batch = [&](int jb) {
 #pragma unroll
@@ -795,7 +852,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_fwd_level_w(LevelArgsW A)
 		if (jb + S < j1) {
 #pragma unroll
 			for (int k = 0; k < 2 * S; ++k)
-				nxt[k] = Band::load(rowp(2 * (jb + S) + 1 + k), at);
+				nxt[k] = Band::load(rowp(2 * (jb + S) + 1 + k), at, A.cstride);
 		}
 #pragma unroll
 		for (int s = 0; s < S; ++s) {
@@ -1160,7 +1217,7 @@ __device__ __forceinline__ LaneAt lane_at(SrcTag<Rgb8>, int q, int lane, int nqu
 	return o;
 }
 
-__device__ __forceinline__ FwdRaw8 fwd_load_p(SrcTag<uint8_t>, const uint8_t *__restrict__ row, const LaneAt &at)
+__device__ __forceinline__ FwdRaw8 fwd_load_p(SrcTag<uint8_t>, const uint8_t *__restrict__ row, const LaneAt &at, long = 0, int = 0)
 {
 	FwdRaw8 r;
 	r.v = *reinterpret_cast<const unsigned *>(row + at.main);
@@ -1177,7 +1234,7 @@ struct FwdRawRgbP {
 	U32x2 e;     // lane 63: e.x = the word with pixel 4q+4; lane 0: bytes 12q-8 .. 12q-1
 };
 
-__device__ __forceinline__ FwdRawRgbP fwd_load_p(SrcTag<Rgb8>, const uint8_t *__restrict__ row, const LaneAt &at)
+__device__ __forceinline__ FwdRawRgbP fwd_load_p(SrcTag<Rgb8>, const uint8_t *__restrict__ row, const LaneAt &at, long, int)
 {
 	FwdRawRgbP r;
 	r.abc = *reinterpret_cast<const U32x3 *>(row + at.main);
@@ -1202,16 +1259,52 @@ __device__ __forceinline__ FwdRawRgb as_used(const FwdRawRgbP &r)
 }
 __device__ __forceinline__ FwdRaw8 as_used(const FwdRaw8 &r) { return r; }
 
+// Planar RGB rows: the same row of the window's three planes, each as a gray row is loaded — the lane's quad is one aligned
+// word per channel and the neighbours' another, both inside the row's own W bytes of that plane (lane_at of gray rows).
+// Nothing is unpacked: the bytes of a word are four pixels of ONE channel, so the even / odd pairs of row_p(FwdRaw8) feed
+// the packed colour transform as they are (against six v_perm_b32 per row and two for the edges from interleaved pixels).
+struct FwdRawRgb3 {
+	FwdRaw8 r, g, b;
+};
+__device__ __forceinline__ LaneAt lane_at(SrcTag<RgbP8>, int q, int lane, int nquads) { return lane_at(SrcTag<uint8_t>(), q, lane, nquads); }
+// (ch: the channel the workgroup extracts, a constant where this is inlined: Co is R - B and leaves the G plane unloaded)
+__device__ __forceinline__ FwdRawRgb3 fwd_load_p(SrcTag<RgbP8>, const uint8_t *__restrict__ row, const LaneAt &at, long cs, int ch)
+{
+	const FwdRaw8 r = fwd_load_p(SrcTag<uint8_t>(), row, at), b = fwd_load_p(SrcTag<uint8_t>(), row + 2 * cs, at);
+	FwdRawRgb3 o = { r, ch == 1 ? r : fwd_load_p(SrcTag<uint8_t>(), row + cs, at), b };
+	return o;
+}
+__device__ __forceinline__ FwdRawRgb3 hold(const FwdRawRgb3 &r)
+{
+	FwdRawRgb3 o = { hold(r.r), hold(r.g), hold(r.b) };
+	return o;
+}
+__device__ __forceinline__ FwdRawRgb3 as_used(const FwdRawRgb3 &r) { return r; }
+__device__ __forceinline__ RowP row_p(const FwdRawRgb3 &r, int ch)
+{
+	const RowP R = row_p(r.r, 0), G = row_p(r.g, 0), B = row_p(r.b, 0);
+	RowP o = { ycocg_p(R.E, G.E, B.E, ch), ycocg_p(R.O, G.O, B.O, ch), ycocg_p(R.xr, G.xr, B.xr, ch), ycocg_p(R.left, G.left, B.left, ch) };
+	return o;
+}
+
 // the row as it is loaded / as it is used
 template <typename SrcT>
 struct RowRegs {
 	typedef FwdRaw8 Loaded;
 	typedef FwdRaw8 Used;
+	static constexpr int S = 2;   // row pairs per batch of fwd_pixels_body's loop
 };
 template <>
 struct RowRegs<Rgb8> {
 	typedef FwdRawRgbP Loaded;
 	typedef FwdRawRgb Used;
+	static constexpr int S = 2;
+};
+template <>
+struct RowRegs<RgbP8> {
+	typedef FwdRawRgb3 Loaded;
+	typedef FwdRawRgb3 Used;
+	static constexpr int S = 1;   // (a row is six registers: batches of two pairs took the kernel with histograms to 133, three waves per SIMD)
 };
 
 // CH: the YCoCg-R channel the launch's workgroup extracts, as a compile-time constant (RGB; the kernel below branches —
@@ -1244,13 +1337,13 @@ __device__ __forceinline__ void fwd_pixels_body(const LevelArgsW &A, int bx, int
 	// everything.  So the loop works in batches of S row pairs: wait once, send the previous batch's results out, ask
 	// for the next batch's rows, then compute S row pairs without touching memory — by the next wait both the stores
 	// and the loads are a whole batch of arithmetic old.
-	constexpr int S = 2;
+	constexpr int S = RowRegs<SrcT>::S;
 	const int jfirst = j0 > 0 ? j0 - 1 : 0;
 	const P2 zero = p2_of(0u);
 	P2 l0, h0, pl = zero, ph = zero;
 	const LaneAt at = lane_at(SrcTag<SrcT>(), q, lane, A.nquads);
 	{
-		const typename RowRegs<SrcT>::Loaded r0 = fwd_load_p(SrcTag<SrcT>(), src + (long)(2 * jfirst) * a.spitch, at);
+		const typename RowRegs<SrcT>::Loaded r0 = fwd_load_p(SrcTag<SrcT>(), src + (long)(2 * jfirst) * a.spitch, at, A.cstride, CH);
 		fwd_lift_p(row_p(as_used(r0), ch), q, lane, A.nquads, l0, h0);
 	}
 	auto rowp = [&](int r) { return src + (long)min(r, a.h - 1) * a.spitch; };
@@ -1258,7 +1351,7 @@ __device__ __forceinline__ void fwd_pixels_body(const LevelArgsW &A, int bx, int
 	typename RowRegs<SrcT>::Loaded nxt[2 * S];
 #pragma unroll
 	for (int k = 0; k < 2 * S; ++k)
-		nxt[k] = fwd_load_p(SrcTag<SrcT>(), rowp(2 * jfirst + 1 + k), at);
+		nxt[k] = fwd_load_p(SrcTag<SrcT>(), rowp(2 * jfirst + 1 + k), at, A.cstride, CH);
 	P2 osl[S], osh[S], odl[S], odh[S];   // a batch's results wait here for the next iteration's stores
 	auto store_batch = [&](int jb) {
 #pragma unroll
@@ -1296,7 +1389,7 @@ __device__ __forceinline__ void fwd_pixels_body(const LevelArgsW &A, int bx, int
 		if (jb + S < j1) {
 #pragma unroll
 			for (int k = 0; k < 2 * S; ++k)
-				nxt[k] = fwd_load_p(SrcTag<SrcT>(), rowp(2 * (jb + S) + 1 + k), at);
+				nxt[k] = fwd_load_p(SrcTag<SrcT>(), rowp(2 * (jb + S) + 1 + k), at, A.cstride, CH);
 		}
 #pragma unroll
 		for (int s = 0; s < S; ++s) {
@@ -1783,6 +1876,7 @@ struct Inv2Args {
 	const short *det16;   // F16: the detail bands of BOTH levels as 16-bit values (positions, pitch and plane stride of det)
 	uint8_t *dst8;        // 8-bit output (the finest level of a gray picture: pnm.h:108's clamp fused), dst_ps / opitch in bytes
 	WinGrid grid;         // the windows behind dst8 (dst_ps apart in a band)
+	long cstride;         // planar RGB pixels behind dst8: from a window's plane to its next (bytes); 0: interleaved.  (Last, as in LevelArgsW.)
 };
 constexpr int V2_FIRST = 4, V2_OWN = 56;
 
@@ -2023,27 +2117,93 @@ __device__ __forceinline__ Rgb24 rgb16_of(const Quad4 &y, const Quad4 &co, const
 	return o;
 }
 
-// what the RGB kernel's lanes write per row: twelve bytes of 8-bit pixels, or twenty-four of deep ones
-template <typename PixT>
+// the same colour transform and clamps (M: 255, or a deep picture's maxval) for planar pixels: the lane's four pixels as one
+// quad per channel — px[c][k] = channel c of pixel k
+__device__ __forceinline__ void rgb_planes_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M, unsigned (&px)[3][4])
+{
+#pragma unroll
+	for (int k = 0; k < 4; ++k) {
+		const int yy = clamp_to(y.v[k], 0, M), c0 = clamp_to(co.v[k], -M, M), c1 = clamp_to(cg.v[k], -M, M);
+		const int t = yy - tdiv2(c1);
+		const int g = c1 + t;
+		const int b = t - tdiv2(c0);
+		const int r = b + c0;
+		px[0][k] = (unsigned)clamp_to(r, 0, M);
+		px[1][k] = (unsigned)clamp_to(g, 0, M);
+		px[2][k] = (unsigned)clamp_to(b, 0, M);
+	}
+}
+// w[c] = the four bytes of channel c
+__device__ __forceinline__ Rgb12 rgb_planar_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg)
+{
+	unsigned px[3][4];
+	rgb_planes_of(y, co, cg, 255, px);
+	Rgb12 o;
+#pragma unroll
+	for (int c = 0; c < 3; ++c)
+		o.w[c] = px[c][0] | (px[c][1] << 8) | (px[c][2] << 16) | (px[c][3] << 24);
+	return o;
+}
+// w[2c], w[2c+1] = the four samples of channel c
+__device__ __forceinline__ Rgb24 rgb16_planar_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M)
+{
+	unsigned px[3][4];
+	rgb_planes_of(y, co, cg, M, px);
+	Rgb24 o;
+#pragma unroll
+	for (int c = 0; c < 3; ++c) {
+		o.w[2 * c] = px[c][0] | (px[c][1] << 16);
+		o.w[2 * c + 1] = px[c][2] | (px[c][3] << 16);
+	}
+	return o;
+}
+
+// what the RGB kernel's lanes write per row: twelve bytes of 8-bit pixels, or twenty-four of deep ones — interleaved in one
+// piece, or (PLANAR; cs = the channel stride in samples) as three aligned quads, one per plane: 4 bytes each, 8 of deep pixels
+template <typename PixT, bool PLANAR = false>
 struct RgbOut {
 	typedef Rgb12 row;
 	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int);
-	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v)
+	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long)
 	{
 		U32x3 x = { v.w[0], v.w[1], v.w[2] };
 		*reinterpret_cast<U32x3 *>(dst + r * pitch + 12 * qd) = x;
 	}
 };
 template <>
-struct RgbOut<uint16_t> {
+struct RgbOut<uint16_t, false> {
 	typedef Rgb24 row;
 	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M) { return rgb16_of(y, co, cg, M); }
-	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v)   // (pitch in samples; rows and quads are multiples of 8 bytes)
+	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long)   // (pitch in samples; rows and quads are multiples of 8 bytes)
 	{
 		uint2 *p = reinterpret_cast<uint2 *>(reinterpret_cast<uint16_t *>(dst) + r * pitch + 12 * qd);
 		p[0] = make_uint2(v.w[0], v.w[1]);
 		p[1] = make_uint2(v.w[2], v.w[3]);
 		p[2] = make_uint2(v.w[4], v.w[5]);
+	}
+};
+template <>
+struct RgbOut<uint8_t, true> {
+	typedef Rgb12 row;
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgb_planar_of(y, co, cg); }
+	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long cs)
+	{
+		uint8_t *p = dst + r * pitch + 4 * qd;
+#pragma unroll
+		for (int c = 0; c < 3; ++c)
+			*reinterpret_cast<unsigned *>(p + c * cs) = v.w[c];
+	}
+};
+template <>
+struct RgbOut<uint16_t, true> {
+	typedef Rgb24 row;
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M) { return rgb16_planar_of(y, co, cg, M); }
+	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long cs)
+	{
+		uint16_t *p = reinterpret_cast<uint16_t *>(dst) + r * pitch + 4 * qd;
+#pragma unroll
+		for (int c = 0; c < 3; ++c)
+			*reinterpret_cast<uint2 *>(p + c * cs) = make_uint2(v.w[2 * c], v.w[2 * c + 1]);
 	}
 };
 
@@ -2068,11 +2228,12 @@ __device__ __forceinline__ Rgb12 rgb_of(const Quad4 &y, const Quad4 &co, const Q
 	return o;
 }
 
-template <typename PixT>
-__device__ __forceinline__ typename RgbOut<PixT>::row RgbOut<PixT>::of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgb_of(y, co, cg); }
+template <typename PixT, bool PLANAR>
+__device__ __forceinline__ typename RgbOut<PixT, PLANAR>::row RgbOut<PixT, PLANAR>::of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgb_of(y, co, cg); }
 
 // PixT = uint16_t: deep pixels (dst8 points to uint16_t samples, ll_ps / llpitch count samples, clamps at a.maxval)
-template <bool F16, typename PixT = uint8_t>
+// PLANAR: dst8 is channel 0's plane of the window, the others A.cstride samples apart, llpitch the pitch of a plane's rows
+template <bool F16, typename PixT = uint8_t, bool PLANAR = false>
 __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 {
 	const LevelArgs &a = A.a;
@@ -2095,7 +2256,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 		llp[ch] = a.src + (long)(3 * image + ch) * a.src_ps;
 		det[ch] = DetPtr<F16>::of(a, 3 * image + ch);
 	}
-	typedef RgbOut<PixT> Out;
+	typedef RgbOut<PixT, PLANAR> Out;
 	uint8_t *dst = a.dst8 + win_off(a.grid, a.ll_ps, image) * (long)sizeof(PixT);
 	const InvAt at = inv_at(a, qd, A.nquads);
 
@@ -2109,10 +2270,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 	}
 	typename Out::row orow[2];
 	auto store_pair = [&](int j) {
-		if (writes) {   // twelve bytes per lane in one store: the wave's 56 lanes write 672 consecutive bytes (deep pixels: twice that)
-			Out::store(dst, a.llpitch, 2 * j, qd, orow[0]);
+		if (writes) {   // twelve bytes per lane in one store: the wave's 56 lanes write 672 consecutive bytes (deep pixels: twice that; planar: a third of it to each plane)
+			Out::store(dst, a.llpitch, 2 * j, qd, orow[0], A.cstride);
 			if (2 * j + 1 < a.h)
-				Out::store(dst, a.llpitch, 2 * j + 1, qd, orow[1]);
+				Out::store(dst, a.llpitch, 2 * j + 1, qd, orow[1], A.cstride);
 		}
 	};
 	for (int jj = j0; jj < j1; ++jj) {
@@ -2142,7 +2303,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 // 32-byte pieces, the block's four waves side by side 21 whole lines.  Three planes' state and rows in flight: ~150 vector
 // registers, three waves per SIMD — and still the faster way: the int32 LL planes of the second level (3 B per pixel written,
 // 3 B read) are gone.  grid.z = image.
-template <bool F16>
+// PLANAR: the lane's four pixels go out as one word to each of the window's three planes (a.cstride apart) instead
+template <bool F16, bool PLANAR = false>
 __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 {
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -2208,8 +2370,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 			return;
 #pragma unroll
 		for (int k = 0; k < 4; ++k) {
-			const U32x3 v = { orow[k].w[0], orow[k].w[1], orow[k].w[2] };
-			__builtin_nontemporal_store(v, reinterpret_cast<U32x3 *>(dst + (long)(4 * m + k) * a.opitch + 12 * q));
+			if (PLANAR) {
+				uint8_t *p = dst + (long)(4 * m + k) * a.opitch + 4 * q;
+#pragma unroll
+				for (int c = 0; c < 3; ++c)
+					__builtin_nontemporal_store(orow[k].w[c], reinterpret_cast<unsigned *>(p + c * a.cstride));
+			} else {
+				const U32x3 v = { orow[k].w[0], orow[k].w[1], orow[k].w[2] };
+				__builtin_nontemporal_store(v, reinterpret_cast<U32x3 *>(dst + (long)(4 * m + k) * a.opitch + 12 * q));
+			}
 		}
 	};
 	for (int m = m0; m < m1; ++m) {
@@ -2269,7 +2438,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 		}
 #pragma unroll
 		for (int k = 0; k < 4; ++k)
-			orow[k] = rgb_of(rows[0][k], rows[1][k], rows[2][k]);
+			orow[k] = PLANAR ? rgb_planar_of(rows[0][k], rows[1][k], rows[2][k]) : rgb_of(rows[0][k], rows[1][k], rows[2][k]);
 	}
 	store_rows(m1 - 1);
 }
@@ -2425,13 +2594,15 @@ struct PixGrid {
 	long image_stride, row_pitch;
 	WinGrid grid;
 	int W, H, C, n;
+	long chan_stride;   // RGB: from a pixel's sample of one channel to the next one's — 1 interleaved, dwtx_pixels::channel_stride planar
+	int col_step;       // from a pixel to the next one of its row: C interleaved, 1 planar
 };
 
 constexpr int PX_LANES = 64, PX_ROWS = 4;   // a workgroup of the conversions: one wave per row, a lane per pixel
 
 // pnm.h:69-74 (byte -> int) fused with image.h:52-65 rgb2ycocg.  P = uint8_t, or uint16_t for deep pixels (the same
 // arithmetic: nothing in it knows the depth).  grid: (64 pixels of a row, 4 rows, window): a wave reads 64 neighbouring
-// pixels of one row, and nothing divides per sample.
+// pixels of one row, and nothing divides per sample.  Planar RGB: the wave reads 64 neighbouring samples of each plane.
 template <class P>
 __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *__restrict__ planes, const P *__restrict__ pix, PixGrid g)
 {
@@ -2446,7 +2617,8 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *
 		if (g.C == 1) {
 			dst[0] = row[x];
 		} else {
-			const int r = row[3 * x], gr = row[3 * x + 1], b = row[3 * x + 2];
+			const P *p = row + (long)x * g.col_step;
+			const int r = p[0], gr = p[g.chan_stride], b = p[2 * g.chan_stride];
 			const int co = r - b;
 			const int t = b + tdiv2(co);
 			const int cg = gr - t;
@@ -2486,9 +2658,10 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__
 			const int gr = cg + t;
 			const int b = t - tdiv2(co);
 			const int r = b + co;
-			row[3 * x] = (P)clampi(r, 0, M);
-			row[3 * x + 1] = (P)clampi(gr, 0, M);
-			row[3 * x + 2] = (P)clampi(b, 0, M);
+			P *p = row + (long)x * g.col_step;
+			p[0] = (P)clampi(r, 0, M);
+			p[g.chan_stride] = (P)clampi(gr, 0, M);
+			p[2 * g.chan_stride] = (P)clampi(b, 0, M);
 		}
 	}
 }
@@ -2580,7 +2753,8 @@ extern "C" int dwtx_synth_pixels(dwtx_ctx *ctx, uint8_t *pix, int W, int H, int 
 static PixGrid pix_grid(const dwtx_pixels &px, int W, int H, int n, dim3 *grid)
 {
 	*grid = dim3((unsigned)dwtx_cdiv(W, PX_LANES), (unsigned)dwtx_cdiv(H, PX_ROWS), (unsigned)min(n, 65535));
-	return PixGrid{ (long)px.image_stride, (long)px.pitch(W), win_grid(px), W, H, px.channels, n };
+	return PixGrid{ (long)px.image_stride, (long)px.pitch(W), win_grid(px), W, H, px.channels, n, px.planar() ? (long)px.channel_stride : 1L,
+		px.planar() ? 1 : px.channels };
 }
 
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
@@ -2701,6 +2875,11 @@ using WideKernel = void (*)(LevelArgsW);
 static WideKernel fwd_wide_kernel(const dwtx_pixels *px, bool hist, bool src16)
 {
 	const int channels8 = px && !px->deep() ? px->channels : 0;
+	const bool planar = px && px->channels == 3 && px->planar();
+	if (planar && channels8)
+		return hist ? k_fwd_pixels_w<RgbP8, true> : k_fwd_pixels_w<RgbP8, false>;
+	if (planar)
+		return k_fwd_level_w<false, SRC_RGBP16>;
 	if (hist) {
 		if (channels8 == 3)
 			return k_fwd_pixels_w<Rgb8, true>;
@@ -2717,7 +2896,7 @@ static WideKernel fwd_wide_kernel(const dwtx_pixels *px, bool hist, bool src16)
 	return px->channels == 3 ? k_fwd_level_w<false, SRC_RGB16> : k_fwd_level_w<false, SRC_U16>;
 }
 
-// px != nullptr (`in` is then not read): the source is pixels, gray (plane p = image p) or interleaved RGB (plane p =
+// px != nullptr (`in` is then not read): the source is pixels, gray (plane p = image p) or RGB, interleaved or planar (plane p =
 // channel p%3 of image p/3 after YCoCg-R), image i at px->image(i); needs a finest level the wide kernel takes
 // (dwtx_pixels_ok).  Deep pixels: no histograms, no 16-bit bands (their bounds are for 8-bit sources).
 static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_pixels *px, int W, int H, int nplanes,
@@ -2847,6 +3026,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			a.rpw = pick_rpw(strips, a.h2, nplanes, forced);
 			A.wx_log2 = strips >= 4 ? 2 : strips >= 2 ? 1 : 0;
 			A.a = a;
+			A.cstride = pix_in && px->channels == 3 ? (long)px->channel_stride : 0;
 			if (hist_here) {
 				A.hist = HistArgs{ sink->cum32, sink->tile_mx, sink->tiles.xy2tile + sink->tiles.xy_first[level], sink->NT, sink->NTP,
 					sink->tiles.nbs[level] };
@@ -2880,7 +3060,8 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 
 // Can the finest level of a W*H image read / write these pixels directly?  (wide kernel, not the LDS tail)
 // Windows of a frame too (dwtx_pixels: row pitch, bands): the kernels touch only the W * channels samples of a window's
-// rows, so all they ask is that every row of every window starts on a quad (px.wide()) and that the pitch fits their int.
+// rows, so all they ask is that every row of every window — of every plane of a planar window — starts on a quad (px.wide())
+// and that the pitch fits their int.
 // Any other view goes through the general conversions (dwtx_pixels_to_planes / dwtx_planes_to_pixels).
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H)
 {
@@ -2929,7 +3110,7 @@ using Inv2Kernel = void (*)(Inv2Args);
 static Inv2Kernel inv2_kernel(const dwtx_pixels *px, bool det16)
 {
 	if (px && px->channels == 3)
-		return k_inv2_level_w_rgb<true>;
+		return px->planar() ? k_inv2_level_w_rgb<true, true> : k_inv2_level_w_rgb<true>;
 	if (px)
 		return k_inv2_level_w<uint8_t, true>;
 	return det16 ? k_inv2_level_w<int, true> : k_inv2_level_w<int, false>;
@@ -2939,6 +3120,11 @@ static Inv2Kernel inv2_kernel(const dwtx_pixels *px, bool det16)
 static WideKernel inv_wide_kernel(const dwtx_pixels *px, bool det16)
 {
 	const int channels8 = px && !px->deep() ? px->channels : 0;
+	if (px && px->channels == 3 && px->planar()) {
+		if (px->deep())
+			return k_inv_level_w_rgb<false, uint16_t, true>;
+		return det16 ? k_inv_level_w_rgb<true, uint8_t, true> : k_inv_level_w_rgb<false, uint8_t, true>;
+	}
 	if (channels8 == 3)
 		return det16 ? k_inv_level_w_rgb<true> : k_inv_level_w_rgb<false>;
 	if (channels8)
@@ -2948,7 +3134,7 @@ static WideKernel inv_wide_kernel(const dwtx_pixels *px, bool det16)
 	return px->channels == 3 ? k_inv_level_w_rgb<false, uint16_t> : k_inv_level_w<uint16_t, false>;
 }
 
-// px != nullptr (`out` is then not written): the finest level writes clamped pixels (gray, or interleaved RGB after the
+// px != nullptr (`out` is then not written): the finest level writes clamped pixels (gray, or RGB — interleaved or planar — after the
 // inverse colour transform), image i at px->image(i); deep pixels are clamped at px->maxval and take no 16-bit bands
 static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const int32_t *in, int W, int H, int nplanes, const dwtx_p16 *p16 = nullptr)
 {
@@ -3058,6 +3244,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 				f.dst_ps = (long)px->image_stride;
 				f.opitch = (int)px->pitch(W);
 				f.grid = win_grid(*px);
+				f.cstride = px->channels == 3 ? (long)px->channel_stride : 0;
 			} else if (t - 1 == 0) {
 				f.dst = out;
 				f.dst_ps = full_ps;
@@ -3128,6 +3315,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 			const int sx = dwtx_cdiv(A.nquads, rgb ? INV_QUADS : 64);   // (the RGB kernel's waves overlap by a lane on each side)
 			a.rpw = pick_rpw(sx, a.h2, nplanes, forced);
 			A.a = a;
+			A.cstride = rgb ? (long)px->channel_stride : 0;
 			const dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), rgb ? nplanes / 3 : nplanes);
 			hipLaunchKernelGGL(inv_wide_kernel(pix_out, a.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {

@@ -6,7 +6,8 @@ from . import tile_groups
 
 
 def group_view(frame, g):
-    """The tiles of group g (TileGroup) of a device tensor frame [H,W,C], as a strided tensor [rows,cols,g.H,g.W,C]."""
+    """The tiles of group g (TileGroup) of a device tensor frame [H,W,C], as a strided tensor [rows,cols,g.H,g.W,C].  The
+    frame's own strides are kept: a planar frame, `chw.permute(1, 2, 0)`, gives planar tiles."""
     if frame.dim() != 3:
         raise ValueError("a frame is a tensor [H,W,C]")
     sh, sw, sc = frame.stride()
@@ -15,7 +16,7 @@ def group_view(frame, g):
 
 
 def encode_frame(ctx, frame, tile, capacity=0):
-    """frame: device tensor [H,W,C] (uint8, or uint16 / int16) -> one (TileGroup, streams, lens, info) per group of
+    """frame: device tensor [H,W,C] (uint8, or uint16 / int16; interleaved, or a planar [C,H,W] frame permuted) -> one (TileGroup, streams, lens, info) per group of
     tile_groups(W, H, tile); a group's stream i is its tile (i // cols, i % cols).  Async, like encode_view."""
     out = []
     for g in tile_groups(frame.shape[1], frame.shape[0], tile):

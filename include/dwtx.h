@@ -338,21 +338,30 @@ int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
  * the *16 calls.  Window i starts at dev + (i / cols) * band_stride + (i % cols) * image_stride, its row y row_pitch * y
  * further on.  Three layouts: a stack of padded pictures (cols = 0); a row of windows side by side in one frame
  * (image_stride = W*channels, row_pitch = the frame's width * channels); a whole tile grid in one call (cols tiles per
- * band, band_stride = H * row_pitch). */
+ * band, band_stride = H * row_pitch).
+ * RGB pixels are interleaved (channel_stride = 0: sample c of pixel x at 3*x + c) or PLANAR, channel-first
+ * (channel_stride != 0): a window is three planes channel_stride samples apart, each H rows of W samples, columns one
+ * sample apart, rows row_pitch apart — torch's [N,3,H,W] and [3,H,W] as they lie, permuted to channel-last without a copy.
+ * The window origin is channel 0's first sample; image_stride, band_stride and cols mean what they mean for interleaved
+ * windows.  The streams are those of the interleaved copy: the .dwt format knows nothing of the layout. */
 typedef struct dwtx_view {
 	void  *dev;            /* first sample of window 0 */
 	int    sample_bytes;   /* 1: uint8_t, 2: native-endian uint16_t (deep pixels) */
-	int    channels;       /* 1 or 3, interleaved */
+	int    channels;       /* 1 or 3 (interleaved, or planar: channel_stride) */
 	int    maxval;         /* decode: clamp bound (255 required when sample_bytes == 1); encode ignores it */
 	int    cols;           /* windows per band; 0 or >= n: all n windows in one band */
-	size_t row_pitch;      /* samples from a window's row to its next row, >= W*channels */
+	size_t row_pitch;      /* samples from a window's row to its next row, >= W*channels (planar: >= W) */
 	size_t image_stride;   /* samples from a window to the next one of its band */
 	size_t band_stride;    /* samples from a band's first window to the next band's */
+	size_t channel_stride; /* 0: interleaved (sample c of pixel x at 3*x + c). Otherwise planar: channel c of a
+	                          window starts c * channel_stride samples after the window's first sample, columns
+	                          are 1 sample apart, rows row_pitch apart. Ignored when channels == 1. */
 } dwtx_view;
 
 /* dwtx_encode_device / dwtx_encode_device16 from a view: stream i and dev_info[i] are those of window i's pixels, the same
- * bytes as from a dense copy.  Only the W*channels samples of a window's H rows are read; windows may overlap.
- * DWTX_ERR_ARG (with a dwtx_last_error() text): row_pitch < W*channels, dev not aligned to sample_bytes. */
+ * bytes as from a dense copy (a planar window's: those of its interleaved copy).  Only the W*channels samples of a window's
+ * H rows are read (planar: the W samples of the H rows of its three planes); windows, and planes, may overlap.
+ * DWTX_ERR_ARG (with a dwtx_last_error() text): row_pitch < W*channels (planar: < W), dev not aligned to sample_bytes. */
 int dwtx_encode_view(dwtx_ctx *ctx, const dwtx_view *src, int W, int H, int n, long capacity,
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
 /* dwtx_decode_device / dwtx_decode_device16 into a view.  A stream that supports only ow x oh (cut short, or levels_max)
@@ -361,7 +370,15 @@ int dwtx_encode_view(dwtx_ctx *ctx, const dwtx_view *src, int W, int H, int n, l
  * DWTX_ERR_ARG and nothing is written: with cols_eff = min(cols ? cols : n, n), either
  *   image_stride >= (H-1)*row_pitch + W*channels                                            (stacked), or
  *   image_stride >= W*channels and row_pitch >= (cols_eff-1)*image_stride + W*channels      (side by side);
- * and with more than one band, band_stride >= (cols_eff-1)*image_stride + (H-1)*row_pitch + W*channels. */
+ * and with more than one band, band_stride >= (cols_eff-1)*image_stride + (H-1)*row_pitch + W*channels.
+ * A planar destination (channel_stride != 0, channels == 3): the ow x oh rectangle of each of the window's three planes is
+ * written and no other sample.  With pw = (H-1)*row_pitch + W (a plane of a window) and nbands = ceil(n / cols_eff), one of
+ * two forms must hold, else DWTX_ERR_ARG and nothing is written:
+ *   planes inside the window (an NCHW stack): channel_stride >= pw, and with win = 2*channel_stride + pw:
+ *     image_stride >= win if cols_eff > 1, band_stride >= (cols_eff-1)*image_stride + win with more than one band; or
+ *   the planes of the whole view apart (a CHW frame, a tile grid of one, CNHW): the rules above for one channel (a row is W
+ *     samples), and channel_stride >= (nbands-1)*band_stride + (cols_eff-1)*image_stride + pw.
+ * Both are sufficient, not necessary, like the rules above. */
 int dwtx_decode_view(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
 	const unsigned long long *dev_lens, int W, int H, int n, int levels_max,
 	const dwtx_view *dst, dwtx_decode_info *host_info);
