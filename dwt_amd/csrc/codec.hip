@@ -221,7 +221,7 @@ static int encode_device(dwtx_ctx *ctx, const dwtx_pixels &px, int W, int H, int
 	for (int k = 0; k < K; ++k)
 		if ((rc = dwtx_encoder_part(ctx, k, &part[k])))
 			return rc;
-	hipEvent_t *lifted = ctx->enc_ev, *done = ctx->enc_ev + DWTX_ENC_PARTS, start = ctx->enc_ev[2 * DWTX_ENC_PARTS];
+	hipEvent_t *lifted = ctx->enc_ev.lifted, *done = ctx->enc_ev.done, start = ctx->enc_ev.start;
 	DWTX_HIP(hipEventRecord(start, ctx->stream));   // the pixels are the caller's earlier work on its stream
 	rc = DWTX_OK;
 	int queued = 0;
@@ -604,7 +604,7 @@ static int encode_images(dwtx_ctx *ctx, const dwtx_pixels &host, int W, int H, i
 		return DWTX_ERR_NOMEM;
 	}
 	hipStream_t ms = ctx->stream, cs = ctx->copy;
-	hipEvent_t *ev_in = ctx->cev, *ev_enc = ctx->cev + 2, *ev_out = ctx->cev + 4;   // per staging slot
+	hipEvent_t *ev_in = ctx->copy_ev.in, *ev_enc = ctx->copy_ev.coded, *ev_out = ctx->copy_ev.out;   // per staging slot
 	hipError_t e = hipSuccess;
 	rc = DWTX_OK;
 	auto first_of = [&](int k) { return k * P; };
@@ -755,7 +755,7 @@ static int decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_st
 	for (int i = 0; i < n; ++i)
 		hl[i] = lens[i];
 	hipStream_t ms = ctx->stream, cs = ctx->copy;
-	hipEvent_t *ev_in = ctx->cev, *ev_dec = ctx->cev + 2, *ev_out = ctx->cev + 4;   // per staging slot
+	hipEvent_t *ev_in = ctx->copy_ev.in, *ev_dec = ctx->copy_ev.coded, *ev_out = ctx->copy_ev.out;   // per staging slot
 	hipError_t e = hipSuccess;
 	rc = DWTX_OK;
 	auto count_of = [&](int k) { return k == parts - 1 ? n - k * P : P; };

@@ -118,21 +118,29 @@ extern "C" int dwtx_ctx_set_encode_index(dwtx_ctx *c, dwtx_index *out)
 	return DWTX_OK;
 }
 
-int dwtx_need_side_streams(dwtx_ctx *c, bool more)
+// An event group is a struct of events and nothing else (dwtx_ctx::dec_ev, enc_ev, copy_ev)
+template <class G> static int make_events(G &group)
 {
-	if (!c->have_aux) {
-		DWTX_HIP(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
-		for (int i = 0; i < 4; ++i)
-			DWTX_HIP(hipEventCreateWithFlags(&c->ev[i], hipEventDisableTiming));
-		c->have_aux = true;
-	}
-	if (more && !c->have_more) {
-		for (int i = 0; i < 2; ++i)
-			DWTX_HIP(hipStreamCreateWithFlags(&c->more[i], hipStreamNonBlocking));
-		for (int i = 0; i < 8; ++i)
-			DWTX_HIP(hipEventCreateWithFlags(&c->pev[i], hipEventDisableTiming));
-		c->have_more = true;
-	}
+	hipEvent_t *ev = reinterpret_cast<hipEvent_t *>(&group);
+	for (size_t i = 0; i < sizeof(G) / sizeof(hipEvent_t); ++i)
+		DWTX_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+	return DWTX_OK;
+}
+
+template <class G> static void destroy_events(G &group)
+{
+	hipEvent_t *ev = reinterpret_cast<hipEvent_t *>(&group);
+	for (size_t i = 0; i < sizeof(G) / sizeof(hipEvent_t); ++i)
+		(void)hipEventDestroy(ev[i]);
+}
+
+int dwtx_need_part_streams(dwtx_ctx *c, int parts)
+{
+	int rc;
+	if (!c->nside && (rc = make_events(c->dec_ev)))
+		return rc;
+	for (const int want = parts <= 2 ? 1 : DWTX_PART_STREAMS - 1; c->nside < want; ++c->nside)
+		DWTX_HIP(hipStreamCreateWithFlags(&c->side[c->nside], hipStreamNonBlocking));
 	return DWTX_OK;
 }
 
@@ -140,9 +148,10 @@ int dwtx_encoder_part(dwtx_ctx *c, int k, dwtx_ctx **part)
 {
 	if (k < 0 || k >= DWTX_ENC_PARTS)
 		return DWTX_ERR_ARG;
+	int rc;
 	if (!c->have_enc_ev) {
-		for (int i = 0; i < 2 * DWTX_ENC_PARTS + 1; ++i)
-			DWTX_HIP(hipEventCreateWithFlags(&c->enc_ev[i], hipEventDisableTiming));
+		if ((rc = make_events(c->enc_ev)))
+			return rc;
 		c->have_enc_ev = true;
 	}
 	if (k == 0) {   // part 0 runs on the caller's stream: the context itself, with the scratch it already has for small batches
@@ -150,11 +159,9 @@ int dwtx_encoder_part(dwtx_ctx *c, int k, dwtx_ctx **part)
 		return DWTX_OK;
 	}
 	if (!c->enc_part[k]) {
-		int rc = dwtx_need_side_streams(c, true);
-		if (rc)
+		if ((rc = dwtx_need_part_streams(c, DWTX_ENC_PARTS)))
 			return rc;
-		hipStream_t st = k == 1 ? c->aux : c->more[k - 2];
-		if ((rc = ctx_create(c->device, (void *)st, false, &c->enc_part[k])))
+		if ((rc = ctx_create(c->device, (void *)dwtx_part_stream(c, k), false, &c->enc_part[k])))
 			return rc;
 	}
 	memcpy(c->enc_part[k]->opt, c->opt, sizeof(c->opt));
@@ -168,31 +175,22 @@ extern "C" void dwtx_ctx_destroy(dwtx_ctx *c)
 		return;
 	(void)hipSetDevice(c->device);
 	(void)hipStreamSynchronize(c->stream);
-	for (int k = 0; k < DWTX_ENC_PARTS; ++k)
+	for (int k = 0; k < DWTX_ENC_PARTS; ++k)   // (before the streams they run on)
 		if (c->enc_part[k])
 			dwtx_ctx_destroy(c->enc_part[k]);
 	if (c->have_enc_ev)
-		for (int i = 0; i < 2 * DWTX_ENC_PARTS + 1; ++i)
-			(void)hipEventDestroy(c->enc_ev[i]);
+		destroy_events(c->enc_ev);
 	dwtx_free_plans(c);
 	for (int i = 0; i < DWTX_SCRATCH_SLOTS; ++i)
 		if (c->scratch[i])
 			(void)hipFree(c->scratch[i]);
-	if (c->have_more) {
-		for (int i = 0; i < 2; ++i)
-			(void)hipStreamDestroy(c->more[i]);
-		for (int i = 0; i < 8; ++i)
-			(void)hipEventDestroy(c->pev[i]);
-	}
-	if (c->have_aux) {
-		(void)hipStreamDestroy(c->aux);
-		for (int i = 0; i < 4; ++i)
-			(void)hipEventDestroy(c->ev[i]);
-	}
+	for (int i = c->nside - 1; i >= 0; --i)
+		(void)hipStreamDestroy(c->side[i]);
+	if (c->nside)
+		destroy_events(c->dec_ev);
 	if (c->have_copy) {
 		(void)hipStreamDestroy(c->copy);
-		for (int i = 0; i < 6; ++i)
-			(void)hipEventDestroy(c->cev[i]);
+		destroy_events(c->copy_ev);
 	}
 	if (c->own_stream)
 		(void)hipStreamDestroy(c->stream);
@@ -205,8 +203,9 @@ int dwtx_need_copy_stream(dwtx_ctx *c)
 		return DWTX_OK;
 	DWTX_ENTER(c);
 	DWTX_HIP(hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking));
-	for (int i = 0; i < 6; ++i)
-		DWTX_HIP(hipEventCreateWithFlags(&c->cev[i], hipEventDisableTiming));
+	const int rc = make_events(c->copy_ev);
+	if (rc)
+		return rc;
 	c->have_copy = true;
 	return DWTX_OK;
 }

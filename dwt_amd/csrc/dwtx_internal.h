@@ -7,10 +7,16 @@
 #include "../../include/dwtx.h"
 
 #define DWTX_SCRATCH_SLOTS 24
-#define DWTX_ENC_PARTS 4
+#define DWTX_PART_STREAMS 4   // parts a batch runs as at the most, one stream each
+#define DWTX_ENC_PARTS DWTX_PART_STREAMS
 
 struct dwtx_linplan;
 
+// Streams: a context works on the caller's stream, on up to three side streams and on a copy stream, and no more
+// (DESIGN 6).  A batch is cut into parts, and part k of the encoder (codec.hip) and of the decoder (unpack.hip) alike runs
+// on dwtx_part_stream(ctx, k): the runtime maps streams onto a handful of hardware queues, and streams that share a queue
+// run one after the other.  Events are members named after what has happened when they fire; the arrays among them
+// have one event per part, or per staging slot of the host-buffer pipelines.
 struct dwtx_ctx {
 	int device;
 	hipStream_t stream;
@@ -18,25 +24,28 @@ struct dwtx_ctx {
 	void *scratch[DWTX_SCRATCH_SLOTS];
 	size_t scratch_bytes[DWTX_SCRATCH_SLOTS];
 	dwtx_linplan *plans;   // per-geometry Hilbert block tables (linearize.hip)
-	hipStream_t aux;       // second stream: half of a decode batch runs here so that one half's serial
-	hipEvent_t ev[4];      // token walk overlaps the other half's parallel kernels (unpack.hip); [2],[3]: bitmap clear
-	bool have_aux;
-	hipStream_t more[2];   // decode batches of small pictures run as four parts, one stream each (unpack.hip)
-	hipEvent_t pev[8];     // [k] part k's chunk tables done, [4+k] part k's scatter done
-	bool have_more;
-	hipStream_t copy;      // host-buffer wrappers: transfers of one part of a batch overlap the kernels of another (codec.hip)
-	hipEvent_t cev[6];
-	bool have_copy;
+	hipStream_t side[DWTX_PART_STREAMS - 1];   // the streams of parts 1.. (dwtx_need_part_streams)
+	int nside;                                 // how many of them exist: 0, 1 or all; dec_ev exists with the first
+	// decoder (unpack.hip): one part's serial token walk overlaps the other parts' parallel kernels.  start, cleared: the
+	// bitmap clear's fork from the caller's stream and its end on side[0]; tables[k]: part k's chunk tables are queued (part
+	// k + 1 builds its own; the last part records none); scattered[k]: part k's scatter is queued (k >= 1: the caller's stream goes on)
+	struct { hipEvent_t start, cleared, tables[DWTX_PART_STREAMS], scattered[DWTX_PART_STREAMS]; } dec_ev;
+	// dwtx_encode_device cuts a batch into parts that run on contexts of their own (stream + scratch each): one part's
+	// memory-bound lifting overlaps the instruction-bound entropy stage of the part before (codec.hip)
+	dwtx_ctx *enc_part[DWTX_ENC_PARTS];
+	// start: the caller's stream when the call began; lifted[k]: part k's transform is queued; done[k]: part k is done
+	struct { hipEvent_t start, lifted[DWTX_ENC_PARTS], done[DWTX_ENC_PARTS]; } enc_ev;
+	bool have_enc_ev;
+	// host-buffer wrappers: transfers of one part of a batch overlap the kernels of another (codec.hip).  Per staging slot:
+	// its input has arrived, it is encoded / decoded, its output has left
+	hipStream_t copy;
+	struct { hipEvent_t in[2], coded[2], out[2]; } copy_ev;
+	bool have_copy;        // copy and copy_ev exist
 	const dwtx_index *index_in;   // dwtx_ctx_set_index: sidecar indices offered to / asked from the decode calls
 	dwtx_index *index_out;
 	size_t index_base;            // entry of the current call's first image (the host pipeline decodes a batch in parts)
 	dwtx_index *enc_index;        // dwtx_ctx_set_encode_index: where the encode calls leave the sidecar indices of their streams
 	long opt[DWTX_OPT_COUNT];     // dwtx_ctx_set_option: diagnostic switches (tests, tools), all 0 by default
-	// dwtx_encode_device cuts a batch into parts that run on contexts of their own (stream + scratch each): one part's
-	// memory-bound lifting overlaps the instruction-bound entropy stage of the part before (codec.hip)
-	dwtx_ctx *enc_part[DWTX_ENC_PARTS];
-	hipEvent_t enc_ev[2 * DWTX_ENC_PARTS + 1];   // [k] part k's transform is queued, [PARTS + k] part k is done, [2 * PARTS] the call's start
-	bool have_enc_ev;
 };
 
 // Every entry point that allocates, launches or copies makes the context's device the calling thread's current
@@ -55,12 +64,14 @@ int dwtx_debug_check_device(dwtx_ctx *ctx, const char *file, int line);
 #endif
 
 void dwtx_free_plans(dwtx_ctx *ctx);
-int dwtx_need_side_streams(dwtx_ctx *ctx, bool more);            // ctx.hip: creates aux / ev (and more / pev) on first use
-// ctx.hip: part k's context (made on first use) with the parent's options.  Parts run on the context's own streams — the
-// caller's, aux, more[0], more[1]: the runtime maps streams onto a handful of hardware queues, and streams that share a
-// queue run one after the other; the encoder's and the decoder's parts therefore use the same four.
+// ctx.hip: the side streams that `parts` parts need, made on first use: one for two parts (or for the decoder's bitmap
+// clear alone), all three beyond — a process that never runs big batches opens two streams, not four
+int dwtx_need_part_streams(dwtx_ctx *ctx, int parts);
+// the stream of part k: the caller's, then the side streams (the one place that maps parts to streams)
+static inline hipStream_t dwtx_part_stream(const dwtx_ctx *ctx, int k) { return k == 0 ? ctx->stream : ctx->side[k - 1]; }
+// ctx.hip: the encoder's part k: a context (made on first use) on dwtx_part_stream(ctx, k) with the parent's options
 int dwtx_encoder_part(dwtx_ctx *ctx, int k, dwtx_ctx **part);
-int dwtx_need_copy_stream(dwtx_ctx *ctx);   // creates ctx->copy / ctx->cev on first use
+int dwtx_need_copy_stream(dwtx_ctx *ctx);   // creates ctx->copy / ctx->copy_ev on first use
 
 void dwtx_set_error(const char *fmt, ...);
 // grow-only per-slot device scratch; contents undefined after a grow

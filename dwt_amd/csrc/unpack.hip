@@ -2391,7 +2391,7 @@ __global__ __launch_bounds__(256) void k_nch(DWork w, const unsigned long long *
 // Every per-image table of DWork, and the decoder's clear_words, in the order of their slots: f(slot, table, elements per
 // image, rows).  A table is `rows` blocks of [n][elements] (todo_count: [LINK_ROUNDS + 2][n*FAM][LINK_SHARDS]); image i's
 // part of every block starts at table + i * elements.  The one list both carves the slots and slices a batch
-// (dwtx_decode_planes_ex); the sizes in `w` (BW, NT, NCH, NB, MAX_HOPS, todo_cap) are set before either.
+// (DecodeCall); the sizes in `w` (dwork_sizes: BW, NT, NCH, NB, MAX_HOPS, todo_cap) are set before either.
 template <class F> static void dwork_tables(DWork &w, unsigned *&clear_words, int C, F &&f)
 {
 	auto t = [&](int slot, auto *&table, long elems) { f(slot, table, elems, 1l); };
@@ -2433,6 +2433,340 @@ template <class F> static void dwork_tables(DWork &w, unsigned *&clear_words, in
 	t(SLOT_UP_CHUNKS, w.seg_slot, MAX_SEGS + 1);
 }
 
+// The sizes the tables are laid out for: n streams of stream_stride bytes of geometry g
+static void dwork_sizes(DWork &w, const UnpackGeom &g, int NT, size_t stream_stride, int n)
+{
+	w.NT = NT;
+	w.streak_max = WALK_STREAK_MAX;
+	w.scans_base = WALK_SCANS_BASE;
+	// every segment owns ceil32(ring size) symbol slots; at most MAX_PLANES segments per (channel, level)
+	w.BW = ((long)((((unsigned long long)g.total + 32ull * g.levels) * g.C * MAX_PLANES) >> 4) + 128 + 3) & ~3l;   // 2 bits per symbol; whole 16-byte groups per image
+	// speculative chunk tables
+	w.NCH = (long)((stream_stride * 8 + CH_BITS - 1) / CH_BITS);
+	w.NCH = (w.NCH + 1 + 3) / 4 * 4 - 1;   // NCH+1 table rows per stream, a multiple of 4 for the vectorised scans
+	w.NB = (w.NCH + 1 + SCAN_BLOCK - 1) / SCAN_BLOCK;
+	w.MAX_HOPS = 8 * MAX_SEGS + w.NCH / 8;
+	w.fam = 1;
+	w.todo_cap = ((w.NCH + 256) / 256 + 63) / 64 * 256 + 256;   // chunks whose workgroup maps to one shard
+	w.todo_round = (long)n * FAM * LINK_SHARDS;
+}
+
+#ifdef DWTX_DEBUG_HOOKS
+// What the development tools set through the environment (never in the shipped build)
+static void debug_hooks(DWork &w, int &link_rounds)
+{
+	// tools/dbg_walker.py: device address for the walker's cycle counters
+	w.dbg = (unsigned long long *)getenv("DWTX_DBG_PTR") ? (unsigned long long *)strtoull(getenv("DWTX_DBG_PTR"), 0, 0) : nullptr;
+	// tools/find_second_walk.py: other limits to try
+	if (getenv("DWTX_DBG_STREAK"))
+		w.streak_max = (unsigned)strtoul(getenv("DWTX_DBG_STREAK"), 0, 0);
+	if (getenv("DWTX_DBG_SCANS"))
+		w.scans_base = (unsigned)strtoul(getenv("DWTX_DBG_SCANS"), 0, 0);
+	if (getenv("DWTX_DBG_ROUNDS") && atoi(getenv("DWTX_DBG_ROUNDS")) >= 1 && atoi(getenv("DWTX_DBG_ROUNDS")) <= LINK_ROUNDS)
+		link_rounds = atoi(getenv("DWTX_DBG_ROUNDS"));
+}
+#endif
+
+namespace {
+
+// A part of a decode call's batch: images [first, first + count), everything of theirs on one stream
+struct DecPart {
+	int first, count;
+	hipStream_t stream;   // dwtx_part_stream(ctx, k) of part k
+	bool indexed;         // its walk was the segment-parallel one (DecodeCall::run decides; recover() asks)
+	unsigned fused;       // what `done` is told: the ring levels scatter() wrote into the pyramid, DWTX_FUSED_FINE16
+};
+
+// One call of dwtx_decode_planes_ex: what its steps share.  Every table is per image, so every step works on a range
+// of images [first, first + count) and a stream.
+struct DecodeCall {
+	dwtx_ctx *ctx;
+	int n;
+	const uint8_t *streams;
+	size_t stream_stride;
+	const unsigned long long *dev_lens;
+	int32_t *lin, *pyr;
+	dwtx_p16 p16;
+	dwtx_decode_info *host_info;
+	UnpackGeom g;
+	DWork w;                 // the whole batch's tables (dwork_tables) and their sizes (dwork_sizes)
+	unsigned *clear_words;   // [n] bitmap words each image can use (k_peek)
+	unsigned sq_all;         // the levels that are full power-of-two squares can go straight into the pyramid (k_apply_all)
+	int link_rounds;
+	int fam0;                // families of recorded paths the first walk of every image uses
+	const dwtx_index *ix_in; // dwtx_ctx_set_index: offered / wanted, entry 0 = this call's image 0
+	dwtx_index *ix_out;
+	std::vector<int> index_segs;   // [n] staging of idx_nsegs (lives as long as this call: walk()'s copy may still be reading it)
+
+	char *carve_slot(int slot)
+	{
+		return carve(ctx, slot, [&](Carve &c) {
+			dwork_tables(w, clear_words, g.C, [&](int in_slot, auto *&table, long elems, long rows) {
+				if (in_slot == slot)
+					c.take(table, (size_t)n * rows * elems);
+			});
+		});
+	}
+
+	// What every part finds zeroed: the small counters and the root image on the caller's stream, the symbol bitmap beside them
+	int queue_clears()
+	{
+		hipStream_t s = ctx->stream;
+		const int nplanes = n * g.C;
+		DWTX_HIP(hipMemsetAsync(w.todo_count, 0, sizeof(unsigned) * (LINK_ROUNDS + 2) * (size_t)w.todo_round, s));
+		DWTX_HIP(hipMemsetAsync(w.nhops, 0, sizeof(int) * (size_t)n, s));
+		DWTX_HIP(hipMemsetAsync(w.info, 0, (char *)w.seg_desc - (char *)w.info, s));   // info, segidx
+		// The symbol bitmap (the one big clear, ~64 MB per 4096x4096 plane) is only needed by the token walk:
+		// it is cleared on the first side stream while the chunk tables are built on the caller's.
+		const int rc = dwtx_need_part_streams(ctx, 2);
+		if (rc)
+			return rc;
+		hipStream_t side = dwtx_part_stream(ctx, 1);
+		DWTX_HIP(hipEventRecord(ctx->dec_ev.start, s));            // earlier work on the main stream may still read the bitmap
+		DWTX_HIP(hipStreamWaitEvent(side, ctx->dec_ev.start, 0));
+		hipLaunchKernelGGL(k_peek, dim3(dwtx_cdiv(n, 64)), dim3(64), 0, side, g, streams, (long)stream_stride, dev_lens, w.BW, clear_words, n);
+		hipLaunchKernelGGL(k_clear_bitmaps, dim3(64, n), dim3(256), 0, side, w.symbits, w.BW, clear_words);
+		// (the per-tile counters are first used after the token walk too: beside the clear, on the main stream, this
+		// trivial kernel waited 0.5 ms for a free slot and held the chunk kernels up)
+		hipLaunchKernelGGL(k_tiles_init, dim3(dwtx_cdiv(w.NT, 256), nplanes), dim3(256), 0, side, g, w, nplanes);
+		DWTX_HIP(hipEventRecord(ctx->dec_ev.cleared, side));
+		// decode.c:177-179 zeroes everything; here the rings are written exactly once by k_apply_all, so only
+		// the root image (written by the token walker when it has any bits) needs clearing
+		DWTX_HIP(hipMemset2DAsync(lin, sizeof(int) * (size_t)g.lin_stride, 0, sizeof(int) * (size_t)g.pixels[0], nplanes, s));
+		hipLaunchKernelGGL(k_nch, dim3(dwtx_cdiv(n, 256)), dim3(256), 0, s, w, dev_lens, n);
+		return DWTX_OK;
+	}
+
+	DWork slice(int first) const
+	{
+		DWork h = w;
+		unsigned *cw = clear_words;   // (not DWork's: k_peek takes the whole batch's)
+		dwork_tables(h, cw, g.C, [&](int, auto *&table, long elems, long) { table += (size_t)first * elems; });
+#ifdef DWTX_DEBUG_HOOKS
+		if (h.dbg)
+			h.dbg += (size_t)first * 8;
+#endif
+		return h;
+	}
+
+	// The chunk tables of the images' streams, for `fam` families of recorded paths
+	int chunk_tables(hipStream_t st, int first, int count, int fam)
+	{
+		DWork h = slice(first);
+		h.fam = fam;
+		const unsigned char *str = streams + (size_t)first * stream_stride;
+		const unsigned fblocks = (unsigned)((w.NCH + 1 + 256 * LINK_RUN - 1) / (256 * LINK_RUN));
+		hipLaunchKernelGGL(k_link_first, dim3(fblocks < CHUNK_GRID ? fblocks : CHUNK_GRID, count * h.fam), dim3(256), 0, st, h, str,
+			(long)stream_stride);   // speculation and round 1 in one, fills the list of chunks to redo
+		int cur = 1;
+		for (int r = 2; r <= link_rounds; ++r) {   // the lists shrink: fewer workgroups per shard after the first rounds
+			hipLaunchKernelGGL(k_link_work, dim3(LINK_SHARDS * (r <= 3 ? 4 : 1), count * h.fam), dim3(256), 0, st, h, str, (long)stream_stride, cur, r);
+			cur ^= 1;
+		}
+		const unsigned sblocks = (unsigned)(w.NB < SCAN_GRID ? w.NB : SCAN_GRID);
+		hipLaunchKernelGGL(k_scan_local, dim3(sblocks, count * h.fam), dim3(256), 0, st, h);
+		hipLaunchKernelGGL(k_scan_parts, dim3(count * h.fam), dim3(256), 0, st, h);
+		hipLaunchKernelGGL(k_scan_add, dim3(sblocks, count * h.fam), dim3(256), 0, st, h);
+		DWTX_LAUNCH_CHECK();
+		return DWTX_OK;
+	}
+
+	// Sidecar indices (dwtx_ctx_set_index): a part of the batch whose images all come with a plausible index is
+	// walked segment-parallel; k_segjoin proves the index on the way or hands the part back to the serial walk.
+	bool index_usable(int first, int count) const
+	{
+		if (!ix_in || g.levels_max < g.levels || ctx->opt[DWTX_OPT_NO_INDEX])
+			return false;
+		for (int i = first; i < first + count; ++i)
+			if (ix_in[i].magic != DWTX_INDEX_MAGIC || ix_in[i].W != g.W || ix_in[i].H != g.H || ix_in[i].C != g.C || ix_in[i].nsegs <= 0 ||
+				ix_in[i].nsegs > MAX_SEGS)
+				return false;
+		return true;
+	}
+
+	// Token walk, serial or (use_index) one wave per segment of the offered indices, and the symbol bits of the hopped-over chunks
+	int walk(hipStream_t st, int first, int count, int fam, bool use_index)
+	{
+		DWork h = slice(first);
+		h.fam = fam;
+		const unsigned char *str = streams + (size_t)first * stream_stride;
+		int32_t *out = lin + (size_t)first * g.C * g.lin_stride;
+		DWTX_HIP(hipStreamWaitEvent(st, ctx->dec_ev.cleared, 0));   // the bitmap is clear
+		if (use_index) {
+			int maxk = 0;
+			for (int i = 0; i < count; ++i) {
+				const int k = ix_in[first + i].nsegs;
+				index_segs[(size_t)(first + i)] = k;
+				maxk = k > maxk ? k : maxk;
+				DWTX_HIP(hipMemcpyAsync(h.idx + (size_t)i * MAX_SEGS, ix_in[first + i].seg, sizeof(SegIndex) * (size_t)k, hipMemcpyHostToDevice, st));
+			}
+			DWTX_HIP(hipMemcpyAsync(h.idx_nsegs, index_segs.data() + first, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, st));
+			hipLaunchKernelGGL(k_segprep, dim3(dwtx_cdiv(count, 64)), dim3(64), 0, st, h, dev_lens + first, (long)stream_stride, count);
+			hipLaunchKernelGGL(k_tokenize<true>, dim3(maxk, count), dim3(64), 0, st, g, h, str, (long)stream_stride, dev_lens + first, out, count);
+			hipLaunchKernelGGL(k_segjoin, dim3(count), dim3(64), 0, st, g, h, str, (long)stream_stride, dev_lens + first, out, count);
+		} else
+			hipLaunchKernelGGL(k_tokenize<false>, dim3(count), dim3(64), 0, st, g, h, str, (long)stream_stride, dev_lens + first, out, count);
+		const unsigned hblocks = (unsigned)((w.NCH + 255) / 256);
+		hipLaunchKernelGGL(k_hopbits, dim3(hblocks < CHUNK_GRID ? hblocks : CHUNK_GRID, count), dim3(256), 0, st, h, str, (long)stream_stride);
+		DWTX_LAUNCH_CHECK();
+		return DWTX_OK;
+	}
+
+	// walker results to the host (synchronises the stream)
+	int fetch_infos(hipStream_t st, int first, int count)
+	{
+		DWTX_HIP(hipMemcpyAsync(host_info + first, w.info + first, sizeof(DecInfo) * (size_t)count, hipMemcpyDeviceToHost, st));
+		DWTX_HIP(hipStreamSynchronize(st));
+		return DWTX_OK;
+	}
+
+	bool gave_up(int first, int count) const
+	{
+		bool any = false;
+		for (int i = first; i < first + count; ++i)
+			any = any || host_info[i].hops == WALK_GAVE_UP;
+		return any;
+	}
+
+	// Only the images whose walk gave up are done again, serially, run by run of consecutive ones (the tables are per image;
+	// the other images of the range keep what their walks found).  Round 4: one frame in 200 of the benchmark's
+	// synthetic ones takes the second walk — repeating its whole part of 48 frames cost the batch 40 % of its
+	// decoding time (18.5 -> 27.2 ms for 160 -> 192 frames), repeating the one frame is lost in it.
+	int walk_again(hipStream_t st, int first, int count, int fam, bool fresh_tables)
+	{
+		for (int i = first; i < first + count;) {
+			if (host_info[i].hops != WALK_GAVE_UP) {
+				++i;
+				continue;
+			}
+			int j = i + 1;
+			while (j < first + count && host_info[j].hops == WALK_GAVE_UP)
+				++j;
+			const int c = j - i;
+			const DWork hs = slice(i);
+			const long items = (long)c * FAM * LINK_SHARDS > (long)c * 48 * MAX_PLANES ? (long)c * FAM * LINK_SHARDS : (long)c * 48 * MAX_PLANES;
+			hipLaunchKernelGGL(k_part_reset, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, hs, c);
+			DWTX_HIP(hipMemsetAsync(hs.symbits, 0, sizeof(unsigned) * (size_t)c * w.BW, st));
+			int rc = fresh_tables ? chunk_tables(st, i, c, fam) : DWTX_OK;
+			if (rc || (rc = walk(st, i, c, fam, false)))
+				return rc;
+			i = j;
+		}
+		return fetch_infos(st, first, count);
+	}
+
+	// An indexed walk whose index does not fit the stream is repeated serially (same tables); then a one-family serial
+	// walk that gave up (k_tokenize) is repeated with its images parsed again for both families.
+	int recover(const DecPart &p)
+	{
+		int rc;
+		if (p.indexed && gave_up(p.first, p.count)) {
+			if (ctx->opt[DWTX_OPT_NO_INDEX_FALLBACK]) {   // test hook: shows that an index was turned down
+				dwtx_set_error("the sidecar index does not fit the stream (DWTX_OPT_NO_INDEX_FALLBACK forbids the serial walk)");
+				return DWTX_ERR_DEVICE;
+			}
+			if ((rc = walk_again(p.stream, p.first, p.count, fam0, false)))
+				return rc;
+		}
+		if (gave_up(p.first, p.count)) {
+			if (ctx->opt[DWTX_OPT_NO_SECOND_WALK]) {   // test hook: shows that a stream takes this path
+				dwtx_set_error("the one-family token walk gave up (DWTX_OPT_NO_SECOND_WALK forbids the second)");
+				return DWTX_ERR_DEVICE;
+			}
+			if ((rc = walk_again(p.stream, p.first, p.count, FAM, true)))
+				return rc;
+		}
+		return DWTX_OK;
+	}
+
+	// the index of every stream that was decoded to its end (the serial walk wrote it, the indexed one proved it)
+	int write_indices(int first, int count)
+	{
+		for (int i = first; i < first + count; ++i) {
+			dwtx_index &X = ix_out[i];
+			const DecInfo &D = reinterpret_cast<const DecInfo *>(host_info)[i];
+			X.magic = DWTX_INDEX_MAGIC;
+			X.W = g.W;
+			X.H = g.H;
+			X.C = g.C;
+			X.reserved = 0;
+			X.stream_bits = D.bits_used;
+			X.nsegs = !D.status && !D.truncated && g.levels_max >= g.levels && D.nsegs > 0 && D.nsegs <= MAX_SEGS ? D.nsegs : 0;
+			if (X.nsegs)
+				DWTX_HIP(hipMemcpy(X.seg, w.idx + (size_t)i * MAX_SEGS, sizeof(SegIndex) * (size_t)X.nsegs, hipMemcpyDeviceToHost));
+		}
+		return DWTX_OK;
+	}
+
+	// Ranking and the plane scatter of a part whose infos are on the host
+	int scatter(DecPart &p)
+	{
+		const DWork h = slice(p.first);
+		const int end = p.first + p.count, C = g.C;
+		int pmax = 0;
+		for (int i = p.first; i < end; ++i)
+			if (!host_info[i].status && host_info[i].pmax > pmax)
+				pmax = host_info[i].pmax;
+		for (int b = pmax - 1; b >= 0; --b) {
+			hipLaunchKernelGGL(k_rank, dim3(g.levels, p.count * C), dim3(1024), 0, p.stream, g, h, b);
+			hipLaunchKernelGGL(k_count, dim3(dwtx_cdiv(w.NT, 256), p.count * C), dim3(256), 0, p.stream, g, h, b);
+		}
+		// Whole-resolution images only (decode.c:251-254: a stream that ends early gives a smaller picture, whose
+		// pyramid has another pitch): then reconstruction() of the square levels happens inside k_apply_all.
+		bool whole = sq_all != 0;
+		for (int i = p.first; i < end; ++i)
+			whole = whole && !host_info[i].status && host_info[i].level == g.levels - 1;
+		UnpackGeom ga = g;
+		ga.sq_levels = whole ? sq_all : 0u;
+		ga.pyr = whole ? pyr + (size_t)p.first * C * g.lin_stride : nullptr;
+		// 16-bit planes for the finest ring if the caller keeps them and no stream of the part claims coefficients
+		// beyond 15 bits (an 8-bit source never does; a damaged stream may: then the part stays in the int32 pyramid)
+		const bool fine = whole && p16.planes && p16.levels && !((uintptr_t)p16.planes & 15) && !(p16.levels & ~sq_all) && pmax <= 15;
+		ga.fine16 = fine ? p16.planes + (size_t)p.first * C * g.lin_stride : nullptr;
+		ga.lv16 = fine ? p16.levels : 0u;
+		p.fused = ga.sq_levels | (fine ? DWTX_FUSED_FINE16 : 0u);
+		hipLaunchKernelGGL(k_apply_all, dim3(dwtx_cdiv(w.NT, 4), p.count * C), dim3(256), 0, p.stream, ga, h,
+			streams + (size_t)p.first * stream_stride, (long)stream_stride, lin + (size_t)p.first * C * g.lin_stride);
+		DWTX_LAUNCH_CHECK();
+		return DWTX_OK;
+	}
+
+	// The token walk is one wave per image and leaves the chip idle: the batch runs as parts, one stream each, the
+	// parts' chunk-table kernels one after the other (each fills the chip) and every part's walk beside the tables
+	// of the parts after it and the scatter of the parts before it.  (One part records and waits for no event here.)
+	int run(DecPart *part, int K, int (*done)(void *user, int first, int count, unsigned fused_levels), void *user)
+	{
+		int rc;
+		for (int k = 0; k < K; ++k) {
+			DecPart &p = part[k];
+			if (k > 0)   // after the tables of the part before (and, through them, after everything earlier on the main stream)
+				DWTX_HIP(hipStreamWaitEvent(p.stream, ctx->dec_ev.tables[k - 1], 0));
+			if ((rc = chunk_tables(p.stream, p.first, p.count, fam0)))
+				return rc;
+			if (k + 1 < K)
+				DWTX_HIP(hipEventRecord(ctx->dec_ev.tables[k], p.stream));
+			p.indexed = index_usable(p.first, p.count);
+			if ((rc = walk(p.stream, p.first, p.count, fam0, p.indexed)))
+				return rc;
+		}
+		for (int k = 0; k < K; ++k) {   // each part's scatter as soon as its walk is over, then the caller's follow-up on the main stream
+			DecPart &p = part[k];
+			if ((rc = fetch_infos(p.stream, p.first, p.count)) || (rc = recover(p)) || (ix_out && (rc = write_indices(p.first, p.count))) ||
+				(rc = scatter(p)))
+				return rc;
+			if (k > 0) {
+				DWTX_HIP(hipEventRecord(ctx->dec_ev.scattered[k], p.stream));
+				DWTX_HIP(hipStreamWaitEvent(ctx->stream, ctx->dec_ev.scattered[k], 0));
+			}
+			if (done && (rc = done(user, p.first, p.count, p.fused)))
+				return rc;
+		}
+		return DWTX_OK;
+	}
+};
+
+} // namespace
+
 // `done(user, first, count)` (optional) is called on the host as soon as host_info[first..first+count)
 // is valid and every kernel writing those images' planes has been enqueued on ctx->stream (or
 // ordered before it): the caller can queue its own follow-up work for that part of the batch
@@ -2446,329 +2780,50 @@ int dwtx_decode_planes_ex(dwtx_ctx *ctx, int32_t *lin, int32_t *pyr, const uint8
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
-	UnpackGeom g;
+	static_assert(sizeof(dwtx_seg_index) == sizeof(SegIndex) && DWTX_INDEX_MAX_SEGS == MAX_SEGS, "SegIndex is the device image of dwtx_seg_index");
+	static_assert(sizeof(dwtx_decode_info) == sizeof(DecInfo), "DecInfo is the device image of dwtx_decode_info");
+	DecodeCall d{ ctx, n, streams, stream_stride, dev_lens, lin, pyr, p16, host_info };
 	dwtx_tiles tiles;
-	{
-		const int rc_geom = dwtx_fill_geom(ctx, W, H, C, g, tiles);
-		if (rc_geom)
-			return rc_geom;
-	}
-	g.lin_stride = g.total;
-	g.levels_max = levels_max < 0 || levels_max > g.levels ? g.levels : levels_max;
-	// the levels that are full power-of-two squares can go straight into the pyramid (k_apply_all)
-	const unsigned sq_all = pyr && !((uintptr_t)pyr & 15) && !ctx->opt[DWTX_OPT_NO_SQUARE_TILES] ? dwtx_square_levels(W, H) : 0u;
-	constexpr int MAX_PARTS = 4;
-	unsigned part_mask[MAX_PARTS] = { 0u, 0u, 0u, 0u };
-	int part_first[MAX_PARTS + 1] = { 0, 0, 0, 0, 0 };   // images [part_first[k], part_first[k+1]) are part k
-	auto part_of = [&](int i0) { int k = 0; while (k + 1 < MAX_PARTS && part_first[k + 1] <= i0 && part_first[k + 1] > 0) ++k; return k; };
-	const int NT = tiles.NT;
-	const int nplanes = n * C;
-
-	DWork w;
-	unsigned *clear_words = nullptr;   // [n] bitmap words each image can use (k_peek)
-	memset(&w, 0, sizeof(w));
-	w.NT = NT;
-#ifdef DWTX_DEBUG_HOOKS   // tools/dbg_walker.py: device address for the walker's cycle counters (never in the shipped build)
-	w.dbg = (unsigned long long *)getenv("DWTX_DBG_PTR") ? (unsigned long long *)strtoull(getenv("DWTX_DBG_PTR"), 0, 0) : nullptr;
-#endif
-	int link_rounds = LINK_ROUNDS;
-	w.streak_max = WALK_STREAK_MAX;
-	w.scans_base = WALK_SCANS_BASE;
-#ifdef DWTX_DEBUG_HOOKS   // tools/find_second_walk.py: other limits to try
-	if (getenv("DWTX_DBG_STREAK"))
-		w.streak_max = (unsigned)strtoul(getenv("DWTX_DBG_STREAK"), 0, 0);
-	if (getenv("DWTX_DBG_SCANS"))
-		w.scans_base = (unsigned)strtoul(getenv("DWTX_DBG_SCANS"), 0, 0);
-	if (getenv("DWTX_DBG_ROUNDS") && atoi(getenv("DWTX_DBG_ROUNDS")) >= 1 && atoi(getenv("DWTX_DBG_ROUNDS")) <= LINK_ROUNDS)
-		link_rounds = atoi(getenv("DWTX_DBG_ROUNDS"));
-#endif
-	// every segment owns ceil32(ring size) symbol slots; at most MAX_PLANES segments per (channel, level)
-	w.BW = ((long)((((unsigned long long)g.total + 32ull * g.levels) * C * MAX_PLANES) >> 4) + 128 + 3) & ~3l;   // 2 bits per symbol; whole 16-byte groups per image
-	// speculative chunk tables
-	w.NCH = (long)((stream_stride * 8 + CH_BITS - 1) / CH_BITS);
-	w.NCH = (w.NCH + 1 + 3) / 4 * 4 - 1;   // NCH+1 table rows per stream, a multiple of 4 for the vectorised scans
-	w.NB = (w.NCH + 1 + SCAN_BLOCK - 1) / SCAN_BLOCK;
-	w.MAX_HOPS = 8 * MAX_SEGS + w.NCH / 8;
-	w.fam = 1;
-	w.todo_cap = ((w.NCH + 256) / 256 + 63) / 64 * 256 + 256;   // chunks whose workgroup maps to one shard
-	w.todo_round = (long)n * FAM * LINK_SHARDS;
-	auto carve_tables = [&](int slot) {
-		return carve(ctx, slot, [&](Carve &c) {
-			dwork_tables(w, clear_words, C, [&](int in_slot, auto *&table, long elems, long rows) {
-				if (in_slot == slot)
-					c.take(table, (size_t)n * rows * elems);
-			});
-		});
-	};
-	{
-		char *small = carve_tables(SLOT_UP_SMALL);
-		char *bits = carve_tables(SLOT_UP_BITS);
-		char *tile_tables = carve_tables(SLOT_UP_TILES);
-		if (!small || !bits || !tile_tables || !carve_tables(SLOT_UP_CHUNKS))
-			return DWTX_ERR_NOMEM;
-		DWTX_HIP(hipMemsetAsync(w.todo_count, 0, sizeof(unsigned) * (LINK_ROUNDS + 2) * (size_t)w.todo_round, ctx->stream));
-		DWTX_HIP(hipMemsetAsync(w.nhops, 0, sizeof(int) * (size_t)n, ctx->stream));
-		DWTX_HIP(hipMemsetAsync(w.info, 0, (char *)w.seg_desc - (char *)w.info, ctx->stream));   // info, segidx
-		// The symbol bitmap (the one big clear, ~64 MB per 4096x4096 plane) is only needed by the token walk:
-		// it is cleared on the second stream while the chunk tables are built on the first.
-		{
-			const int rc_side = dwtx_need_side_streams(ctx, false);
-			if (rc_side)
-				return rc_side;
-		}
-		DWTX_HIP(hipEventRecord(ctx->ev[2], ctx->stream));            // earlier work on the main stream may still read the bitmap
-		DWTX_HIP(hipStreamWaitEvent(ctx->aux, ctx->ev[2], 0));
-		hipLaunchKernelGGL(k_peek, dim3(dwtx_cdiv(n, 64)), dim3(64), 0, ctx->aux, g, streams, (long)stream_stride, dev_lens, w.BW, clear_words, n);
-		hipLaunchKernelGGL(k_clear_bitmaps, dim3(64, n), dim3(256), 0, ctx->aux, w.symbits, w.BW, clear_words);
-		// (the per-tile counters are first used after the token walk too: beside the clear, on the main stream, this
-		// trivial kernel waited 0.5 ms for a free slot and held the chunk kernels up)
-		hipLaunchKernelGGL(k_tiles_init, dim3(dwtx_cdiv(NT, 256), nplanes), dim3(256), 0, ctx->aux, g, w, nplanes);
-		DWTX_HIP(hipEventRecord(ctx->ev[3], ctx->aux));
-	}
-	hipStream_t s = ctx->stream;
-	// decode.c:177-179 zeroes everything; here the rings are written exactly once by k_apply_all, so only
-	// the root image (written by the token walker when it has any bits) needs clearing
-	DWTX_HIP(hipMemset2DAsync(lin, sizeof(int) * (size_t)g.lin_stride, 0, sizeof(int) * (size_t)g.pixels[0], nplanes, s));
-	hipLaunchKernelGGL(k_nch, dim3(dwtx_cdiv(n, 256)), dim3(256), 0, s, w, dev_lens, n);
-
-	// everything below works on a range of images [i0, i0+cnt): all tables are per image
-	auto slice = [&](int i0) {
-		DWork h = w;
-		unsigned *cw = clear_words;   // (not DWork's: k_peek takes the whole batch's)
-		dwork_tables(h, cw, C, [&](int, auto *&table, long elems, long) { table += (size_t)i0 * elems; });
+	int rc = dwtx_fill_geom(ctx, W, H, C, d.g, tiles);
+	if (rc)
+		return rc;
+	d.g.lin_stride = d.g.total;
+	d.g.levels_max = levels_max < 0 || levels_max > d.g.levels ? d.g.levels : levels_max;
+	d.sq_all = pyr && !((uintptr_t)pyr & 15) && !ctx->opt[DWTX_OPT_NO_SQUARE_TILES] ? dwtx_square_levels(W, H) : 0u;
+	d.link_rounds = LINK_ROUNDS;
+	dwork_sizes(d.w, d.g, tiles.NT, stream_stride, n);
 #ifdef DWTX_DEBUG_HOOKS
-		if (h.dbg)
-			h.dbg += (size_t)i0 * 8;
+	debug_hooks(d.w, d.link_rounds);
 #endif
-		return h;
-	};
-	// chunk tables; then (walk) token walk and symbol bits of the hopped-over chunks
-	auto pre = [&](hipStream_t st, int i0, int cnt, int fam) -> int {
-		DWork h = slice(i0);
-		h.fam = fam;
-		const unsigned char *str = streams + (size_t)i0 * stream_stride;
-		const unsigned cblocks = (unsigned)((w.NCH + 1 + 255) / 256);
-		const dim3 cg(cblocks < CHUNK_GRID ? cblocks : CHUNK_GRID, cnt * h.fam);
-		const unsigned fblocks = (unsigned)((w.NCH + 1 + 256 * LINK_RUN - 1) / (256 * LINK_RUN));
-		hipLaunchKernelGGL(k_link_first, dim3(fblocks < CHUNK_GRID ? fblocks : CHUNK_GRID, cnt * h.fam), dim3(256), 0, st, h, str,
-			(long)stream_stride);   // speculation and round 1 in one, fills the list of chunks to redo
-		int cur = 1;
-		for (int r = 2; r <= link_rounds; ++r) {   // the lists shrink: fewer workgroups per shard after the first rounds
-			hipLaunchKernelGGL(k_link_work, dim3(LINK_SHARDS * (r <= 3 ? 4 : 1), cnt * h.fam), dim3(256), 0, st, h, str, (long)stream_stride, cur, r);
-			cur ^= 1;
-		}
-		const unsigned sblocks = (unsigned)(w.NB < SCAN_GRID ? w.NB : SCAN_GRID);
-		hipLaunchKernelGGL(k_scan_local, dim3(sblocks, cnt * h.fam), dim3(256), 0, st, h);
-		hipLaunchKernelGGL(k_scan_parts, dim3(cnt * h.fam), dim3(256), 0, st, h);
-		hipLaunchKernelGGL(k_scan_add, dim3(sblocks, cnt * h.fam), dim3(256), 0, st, h);
-		DWTX_LAUNCH_CHECK();
-		return DWTX_OK;
-	};
+	for (int slot : { SLOT_UP_SMALL, SLOT_UP_BITS, SLOT_UP_TILES, SLOT_UP_CHUNKS })
+		if (!d.carve_slot(slot))
+			return DWTX_ERR_NOMEM;
+	if ((rc = d.queue_clears()))
+		return rc;
 	// One family of recorded paths is enough for almost every stream (k_link_first); DWTX_TWO_FAMILIES starts with both
 	// (a test hook: it is the path a walk that gave up falls back to).
 	// One or two images leave most of the chip idle anyway: both families then, for the shorter walk.
-	const int fam0 = n <= 2 || ctx->opt[DWTX_OPT_TWO_FAMILIES] ? FAM : 1;
-	// Sidecar indices (dwtx_ctx_set_index): a part of the batch whose images all come with a plausible index is
-	// walked segment-parallel; k_segjoin proves the index on the way or hands the part back to the serial walk.
-	const dwtx_index *ix_in = ctx->index_in ? ctx->index_in + ctx->index_base : nullptr;
-	dwtx_index *ix_out = ctx->index_out ? ctx->index_out + ctx->index_base : nullptr;
-	static_assert(sizeof(dwtx_seg_index) == sizeof(SegIndex) && DWTX_INDEX_MAX_SEGS == MAX_SEGS, "SegIndex is the device image of dwtx_seg_index");
-	auto indexed = [&](int i0, int cnt) -> bool {
-		if (!ix_in || g.levels_max < g.levels || ctx->opt[DWTX_OPT_NO_INDEX])
-			return false;
-		for (int i = i0; i < i0 + cnt; ++i)
-			if (ix_in[i].magic != DWTX_INDEX_MAGIC || ix_in[i].W != W || ix_in[i].H != H || ix_in[i].C != C || ix_in[i].nsegs <= 0 ||
-				ix_in[i].nsegs > MAX_SEGS)
-				return false;
-		return true;
-	};
-	bool part_indexed[MAX_PARTS] = { false, false, false, false };
-	std::vector<int> index_segs(ix_in ? (size_t)n : 0u);
-	auto walk = [&](hipStream_t st, int i0, int cnt, int fam, bool use_index) -> int {
-		DWork h = slice(i0);
-		h.fam = fam;
-		const unsigned char *str = streams + (size_t)i0 * stream_stride;
-		DWTX_HIP(hipStreamWaitEvent(st, ctx->ev[3], 0));   // the bitmap is clear
-		part_indexed[part_of(i0)] = use_index;
-		if (use_index) {
-			int maxk = 0;
-			for (int i = 0; i < cnt; ++i) {
-				const int k = ix_in[i0 + i].nsegs;
-				index_segs[(size_t)(i0 + i)] = k;   // (lives as long as this call: the copy below may still be reading it)
-				maxk = k > maxk ? k : maxk;
-				DWTX_HIP(hipMemcpyAsync(h.idx + (size_t)i * MAX_SEGS, ix_in[i0 + i].seg, sizeof(SegIndex) * (size_t)k, hipMemcpyHostToDevice, st));
-			}
-			DWTX_HIP(hipMemcpyAsync(h.idx_nsegs, index_segs.data() + i0, sizeof(int) * (size_t)cnt, hipMemcpyHostToDevice, st));
-			hipLaunchKernelGGL(k_segprep, dim3(dwtx_cdiv(cnt, 64)), dim3(64), 0, st, h, dev_lens + i0, (long)stream_stride, cnt);
-			hipLaunchKernelGGL(k_tokenize<true>, dim3(maxk, cnt), dim3(64), 0, st, g, h, str, (long)stream_stride, dev_lens + i0,
-				lin + (size_t)i0 * C * g.lin_stride, cnt);
-			hipLaunchKernelGGL(k_segjoin, dim3(cnt), dim3(64), 0, st, g, h, str, (long)stream_stride, dev_lens + i0,
-				lin + (size_t)i0 * C * g.lin_stride, cnt);
-		} else
-		hipLaunchKernelGGL(k_tokenize<false>, dim3(cnt), dim3(64), 0, st, g, h, str, (long)stream_stride, dev_lens + i0,
-			lin + (size_t)i0 * C * g.lin_stride, cnt);
-		const unsigned hblocks = (unsigned)((w.NCH + 255) / 256);
-		hipLaunchKernelGGL(k_hopbits, dim3(hblocks < CHUNK_GRID ? hblocks : CHUNK_GRID, cnt), dim3(256), 0, st, h, str, (long)stream_stride);
-		DWTX_LAUNCH_CHECK();
-		return DWTX_OK;
-	};
-	static_assert(sizeof(dwtx_decode_info) == sizeof(DecInfo), "DecInfo is the device image of dwtx_decode_info");
-	// walker results to the host (synchronises the stream), then the plane scatter
-	auto post = [&](hipStream_t st, int i0, int cnt) -> int {
-		const DWork h = slice(i0);
-		DWTX_HIP(hipMemcpyAsync(host_info + i0, h.info, sizeof(DecInfo) * (size_t)cnt, hipMemcpyDeviceToHost, st));
-		DWTX_HIP(hipStreamSynchronize(st));
-		// A walk that did not come through leaves the marker: an indexed walk whose index does not fit the stream is
-		// repeated serially (same tables), a one-family serial walk that gave up (k_tokenize) is repeated with the
-		// part parsed again for both families.
-		auto gave_up = [&]() {
-			bool any = false;
-			for (int i = i0; i < i0 + cnt; ++i)
-				any = any || host_info[i].hops == WALK_GAVE_UP;
-			return any;
-		};
-		// Only the images whose walk gave up are done again, run by run of consecutive ones (the tables are per image;
-		// the other images of the part keep what their walks found).  Round 4: one frame in 200 of the benchmark's
-		// synthetic ones takes the second walk — repeating its whole part of 48 frames cost the batch 40 % of its
-		// decoding time (18.5 -> 27.2 ms for 160 -> 192 frames), repeating the one frame is lost in it.
-		auto again = [&](int fam, bool tables) -> int {
-			int rc3 = DWTX_OK;
-			for (int i = i0; i < i0 + cnt && !rc3;) {
-				if (host_info[i].hops != WALK_GAVE_UP) {
-					++i;
-					continue;
-				}
-				int j = i + 1;
-				while (j < i0 + cnt && host_info[j].hops == WALK_GAVE_UP)
-					++j;
-				const int c = j - i;
-				const DWork hs = slice(i);
-				const long items = (long)c * FAM * LINK_SHARDS > (long)c * 48 * MAX_PLANES ? (long)c * FAM * LINK_SHARDS : (long)c * 48 * MAX_PLANES;
-				hipLaunchKernelGGL(k_part_reset, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, hs, c);
-				DWTX_HIP(hipMemsetAsync(hs.symbits, 0, sizeof(unsigned) * (size_t)c * w.BW, st));
-				if (tables)
-					rc3 = pre(st, i, c, fam);
-				if (!rc3)
-					rc3 = walk(st, i, c, fam, false);
-				i = j;
-			}
-			if (rc3)
-				return rc3;
-			DWTX_HIP(hipMemcpyAsync(host_info + i0, h.info, sizeof(DecInfo) * (size_t)cnt, hipMemcpyDeviceToHost, st));
-			DWTX_HIP(hipStreamSynchronize(st));
-			return DWTX_OK;
-		};
-		int rc2;
-		if (part_indexed[part_of(i0)] && gave_up()) {
-			if (ctx->opt[DWTX_OPT_NO_INDEX_FALLBACK]) {   // test hook: shows that an index was turned down
-				dwtx_set_error("the sidecar index does not fit the stream (DWTX_OPT_NO_INDEX_FALLBACK forbids the serial walk)");
-				return DWTX_ERR_DEVICE;
-			}
-			if ((rc2 = again(fam0, false)))
-				return rc2;
-		}
-		if (gave_up()) {
-			if (ctx->opt[DWTX_OPT_NO_SECOND_WALK]) {   // test hook: shows that a stream takes this path
-				dwtx_set_error("the one-family token walk gave up (DWTX_OPT_NO_SECOND_WALK forbids the second)");
-				return DWTX_ERR_DEVICE;
-			}
-			if ((rc2 = again(FAM, true)))
-				return rc2;
-		}
-		if (ix_out)   // the index of every stream that was decoded to its end (the serial walk wrote it, the indexed one proved it)
-			for (int i = i0; i < i0 + cnt; ++i) {
-				dwtx_index &X = ix_out[i];
-				const DecInfo &D = reinterpret_cast<const DecInfo *>(host_info)[i];
-				X.magic = DWTX_INDEX_MAGIC;
-				X.W = W;
-				X.H = H;
-				X.C = C;
-				X.reserved = 0;
-				X.stream_bits = D.bits_used;
-				X.nsegs = !D.status && !D.truncated && g.levels_max >= g.levels && D.nsegs > 0 && D.nsegs <= MAX_SEGS ? D.nsegs : 0;
-				if (X.nsegs)
-					DWTX_HIP(hipMemcpy(X.seg, h.idx + (size_t)(i - i0) * MAX_SEGS, sizeof(SegIndex) * (size_t)X.nsegs, hipMemcpyDeviceToHost));
-			}
-		int pmax = 0;
-		for (int i = i0; i < i0 + cnt; ++i)
-			if (!host_info[i].status && host_info[i].pmax > pmax)
-				pmax = host_info[i].pmax;
-		for (int p = pmax - 1; p >= 0; --p) {
-			hipLaunchKernelGGL(k_rank, dim3(g.levels, cnt * C), dim3(1024), 0, st, g, h, p);
-			hipLaunchKernelGGL(k_count, dim3(dwtx_cdiv(NT, 256), cnt * C), dim3(256), 0, st, g, h, p);
-		}
-		// Whole-resolution images only (decode.c:251-254: a stream that ends early gives a smaller picture, whose
-		// pyramid has another pitch): then reconstruction() of the square levels happens inside k_apply_all.
-		bool whole = sq_all != 0;
-		for (int i = i0; i < i0 + cnt; ++i)
-			whole = whole && !host_info[i].status && host_info[i].level == g.levels - 1;
-		UnpackGeom ga = g;
-		ga.sq_levels = whole ? sq_all : 0u;
-		ga.pyr = whole ? pyr + (size_t)i0 * C * g.lin_stride : nullptr;
-		// 16-bit planes for the finest ring if the caller keeps them and no stream of the part claims coefficients
-		// beyond 15 bits (an 8-bit source never does; a damaged stream may: then the part stays in the int32 pyramid)
-		const bool fine = whole && p16.planes && p16.levels && !((uintptr_t)p16.planes & 15) && !(p16.levels & ~sq_all) && pmax <= 15;
-		ga.fine16 = fine ? p16.planes + (size_t)i0 * C * g.lin_stride : nullptr;
-		ga.lv16 = fine ? p16.levels : 0u;
-		part_mask[part_of(i0)] = ga.sq_levels | (fine ? DWTX_FUSED_FINE16 : 0u);
-		hipLaunchKernelGGL(k_apply_all, dim3(dwtx_cdiv(NT, 4), cnt * C), dim3(256), 0, st, ga, h,
-			streams + (size_t)i0 * stream_stride, (long)stream_stride, lin + (size_t)i0 * C * g.lin_stride);
-		DWTX_LAUNCH_CHECK();
-		return DWTX_OK;
-	};
-	int rc;
-	if (n < 4 || ctx->opt[DWTX_OPT_ONE_STREAM]) {
-		if ((rc = pre(s, 0, n, fam0)) || (rc = walk(s, 0, n, fam0, indexed(0, n))) || (rc = post(s, 0, n)))
-			return rc;
-		return done ? done(user, 0, n, part_mask[0]) : DWTX_OK;
-	}
-	// The token walk is one wave per image and leaves the chip idle: the batch runs as parts, one stream each, the
-	// parts' chunk-table kernels one after the other (each fills the chip) and every part's walk beside the tables
-	// of the parts after it and the scatter of the parts before it.  Four parts from 24 images on (measured on 64
-	// frames: 4096x4096 gray 10.6 -> 10.3 ms, 16 x 4096x4096 RGB 11.0 -> 10.8, 1080p RGB the same 6.7: there the
-	// walk itself, 2.5 ms whatever the part, and the last part's scatter are the critical path), else two.
+	d.fam0 = n <= 2 || ctx->opt[DWTX_OPT_TWO_FAMILIES] ? FAM : 1;
+	d.ix_in = ctx->index_in ? ctx->index_in + ctx->index_base : nullptr;
+	d.ix_out = ctx->index_out ? ctx->index_out + ctx->index_base : nullptr;
+	d.index_segs.resize(d.ix_in ? (size_t)n : 0u);
+	// Parts (DecodeCall::run): four from 24 images on (measured on 64 frames: 4096x4096 gray 10.6 -> 10.3 ms,
+	// 16 x 4096x4096 RGB 11.0 -> 10.8, 1080p RGB the same 6.7: there the walk itself, 2.5 ms whatever the part, and the
+	// last part's scatter are the critical path), else two; fewer than four images are one part.
 	const long want_parts = ctx->opt[DWTX_OPT_DECODE_PARTS];
-	const int K = want_parts ? (want_parts < 2 ? 2 : want_parts > MAX_PARTS ? MAX_PARTS : (int)want_parts) : (n >= 24 ? 4 : 2);
-	for (int k = 0; k <= K; ++k)
-		part_first[k] = (int)((long)n * k / K);
-	for (int k = K + 1; k <= MAX_PARTS; ++k)
-		part_first[k] = 0;
-	if (K > 2 && (rc = dwtx_need_side_streams(ctx, true)))
+	const int K = n < 4 || ctx->opt[DWTX_OPT_ONE_STREAM] ? 1
+		: want_parts ? (want_parts < 2 ? 2 : want_parts > DWTX_PART_STREAMS ? DWTX_PART_STREAMS : (int)want_parts) : (n >= 24 ? 4 : 2);
+	if ((rc = dwtx_need_part_streams(ctx, K)))
 		return rc;
-	auto stream_of = [&](int k) { return k == 0 ? s : k == 1 ? ctx->aux : ctx->more[k - 2]; };
-	auto run_parts = [&]() -> int {
-		for (int k = 0; k < K; ++k) {
-			const int i0 = part_first[k], cnt = part_first[k + 1] - part_first[k];
-			hipStream_t st = stream_of(k);
-			if (k == 1)
-				DWTX_HIP(hipStreamWaitEvent(st, ctx->ev[0], 0));
-			else if (k > 1)
-				DWTX_HIP(hipStreamWaitEvent(st, ctx->pev[k - 1], 0));   // after the tables of the part before (and, through them, after everything earlier on the main stream)
-			if ((rc = pre(st, i0, cnt, fam0)))
-				return rc;
-			if (k + 1 < K)
-				DWTX_HIP(hipEventRecord(k == 0 ? ctx->ev[0] : ctx->pev[k], st));
-			if ((rc = walk(st, i0, cnt, fam0, indexed(i0, cnt))))
-				return rc;
-		}
-		for (int k = 0; k < K; ++k) {   // each part's scatter as soon as its walk is over, then the caller's follow-up on the main stream
-			const int i0 = part_first[k], cnt = part_first[k + 1] - part_first[k];
-			if ((rc = post(stream_of(k), i0, cnt)))
-				return rc;
-			if (k > 0) {
-				hipEvent_t ev = k == 1 ? ctx->ev[1] : ctx->pev[4 + k];
-				DWTX_HIP(hipEventRecord(ev, stream_of(k)));
-				DWTX_HIP(hipStreamWaitEvent(s, ev, 0));
-			}
-			if (done && (rc = done(user, i0, cnt, part_mask[k])))
-				return rc;
-		}
-		return DWTX_OK;
-	};
-	rc = run_parts();
+	DecPart part[DWTX_PART_STREAMS];
+	for (int k = 0; k < K; ++k) {
+		const int first = (int)((long)n * k / K);
+		part[k] = DecPart{ first, (int)((long)n * (k + 1) / K) - first, dwtx_part_stream(ctx, k), false, 0u };
+	}
+	rc = d.run(part, K, done, user);
 	if (rc)   // a part failed: what the other parts still have queued on their streams uses the shared tables — it
 		for (int k = 1; k < K; ++k)   // must be over before the caller (or the next call's clears) touches them
-			(void)hipStreamSynchronize(stream_of(k));
+			(void)hipStreamSynchronize(part[k].stream);
 	return rc;
 }
 

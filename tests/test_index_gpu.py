@@ -146,3 +146,78 @@ def test_whole_images_through_the_host_pipeline_with_an_index(ctx, opts):
     outs = ctx.decode(streams)
     assert all((o == p).all() for o, p in zip(outs, pix))
     ctx.set_index()
+
+
+def _copy_of(made):
+    import dwt_amd
+
+    out = (dwt_amd.Index * len(made))()
+    ctypes.memmove(out, made, ctypes.sizeof(out))
+    return out
+
+
+def test_index_fallback_and_second_walk_in_one_batch_of_parts(ctx, opts):
+    """Both recoveries of the decoder's driver in one batch that runs as parts: an index that is turned down (serial walk
+    on the same tables) and a one-family walk that gives up (both families, fresh tables), in that order, image by image
+    of a part — next to a part without a usable index, which is walked plainly.  Whatever the parts are, planes, infos
+    and the indices handed back are those of a decode without any index."""
+    import dwt_amd
+    from test_pack_gpu import _parity_locked_planes
+
+    W = H = 512   # the smallest size at which _parity_locked_planes makes the one-family walk give up
+    n = 8
+    levels, _, pixels, _, _ = dwt_amd.compute_lengths(W, H)
+    rng = np.random.default_rng(8)
+    locked = {2: 1, 3: -1, 5: 1}
+    planes = []
+    for i in range(n):
+        if i in locked:
+            planes.append(_parity_locked_planes(W, H, locked[i], 0))
+        else:
+            lin = np.zeros((1, W * H), dtype=np.int32)
+            lin[0, :pixels[levels]] = rng.laplace(0.0, 3.0 + i, pixels[levels]).astype(np.int32)
+            planes.append(lin)
+    streams = [orc.encode_lin(lin, W, H)[0] for lin in planes]
+
+    made = ctx.set_index(None, n)
+    want, winfos = _decode(ctx, streams, W, H, 1)
+    assert (want == np.concatenate(planes)).all()
+    assert all(i.status == 0 and not i.truncated for i in winfos)
+    assert all(m.magic == dwt_amd.INDEX_MAGIC and m.nsegs > 0 for m in made)
+
+    # images 0-3 (a part of their own when there are two): right, damaged, locked + right, locked + damaged;
+    # image 4 comes without an index, so its part is walked plainly, the locked image 5 with it
+    offered = _copy_of(made)
+    offered[1].seg[made[1].nsegs // 2].bit += 1
+    offered[3].seg[made[3].nsegs // 2].bit += 1
+    offered[4].magic = 0
+
+    def same_as_the_first_decode():
+        again = ctx.set_index(offered, n)
+        got, ginfos = _decode(ctx, streams, W, H, 1)
+        assert (got == want).all()
+        for a, b in zip(ginfos, winfos):
+            _same_info(a, b)
+        for i in range(n):
+            assert again[i].nsegs == made[i].nsegs, i
+            assert bytes(again[i])[:32 + 32 * made[i].nsegs] == bytes(made[i])[:32 + 32 * made[i].nsegs], i
+
+    def raises():
+        ctx.set_index(offered, n)
+        with pytest.raises(dwt_amd.DwtxError):
+            _decode(ctx, streams, W, H, 1)
+
+    for name, value in (("decode_parts", 2), ("decode_parts", 4), ("one_stream", 1)):
+        opts.set(name, value)
+        same_as_the_first_decode()
+        opts.set("no_second_walk", 1)
+        raises()
+        opts.set("no_second_walk", 0)
+        opts.set("no_index_fallback", 1)
+        if name == "decode_parts":
+            raises()
+        else:   # one part: image 4 has no index, so none is used and none can be turned down
+            same_as_the_first_decode()
+        opts.set("no_index_fallback", 0)
+        opts.set(name, 0)
+    ctx.set_index()
