@@ -119,6 +119,7 @@ struct SegResult {
 
 struct DWork {
 	DecInfo *info;                  // [n]
+	unsigned *seg_ones;             // [n][MAX_SEGS] 1: the segment's symbols may hold a "one" in symbits (raised by whoever sets one); 0: none does
 	int *seg_desc;                  // [n][MAX_SEGS]
 	unsigned long long *seg_symbase; // [n][MAX_SEGS]
 	unsigned long long *seg_b2;     // [n][MAX_SEGS]
@@ -912,13 +913,14 @@ struct Quad {
 	uint4 t, g;
 };
 
-__device__ __forceinline__ Quad quad_load(const DWork &w, long at)
+// (k_scan_local makes the flags itself: WITH_G = false leaves cg unread)
+template <bool WITH_G = true> __device__ __forceinline__ Quad quad_load(const DWork &w, long at)
 {
 	Quad q;
 	q.s01 = *reinterpret_cast<const ulonglong2 *>(w.cs + at);
 	q.s23 = *reinterpret_cast<const ulonglong2 *>(w.cs + at + 2);
 	q.t = *reinterpret_cast<const uint4 *>(w.ct + at);
-	q.g = *reinterpret_cast<const uint4 *>(w.cg + at);
+	q.g = WITH_G ? *reinterpret_cast<const uint4 *>(w.cg + at) : make_uint4(0u, 0u, 0u, 0u);
 	return q;
 }
 
@@ -948,7 +950,7 @@ __global__ __launch_bounds__(256) void k_scan_local(DWork w)
 		q.s01 = q.s23 = make_ulonglong2(0ull, 0ull);
 		q.t = q.g = make_uint4(0u, 0u, 0u, 0u);
 		if (in) {
-			q = quad_load(w, vs * n + i);
+			q = quad_load<false>(w, vs * n + i);
 			unsigned long long *sv[4] = { &q.s01.x, &q.s01.y, &q.s23.x, &q.s23.y };
 			unsigned *tv[4] = { &q.t.x, &q.t.y, &q.t.z, &q.t.w }, *gv[4] = { &q.g.x, &q.g.y, &q.g.z, &q.g.w };
 			unsigned short prev = i >= 1 && i - 1 < nch ? exitX[i - 1] : (unsigned short)0xffff;
@@ -1173,6 +1175,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
 				mybuf[i] = 0u;
 			}
 		}
+		if (rp != rp0)   // the piece had a token, so a one was set, in the row or beyond it: k_rank may not skip the segment's count
+			w.seg_ones[(long)img * MAX_SEGS + k] = 1u;
 	};
 	const bool mine = chunk < w.nch[img] && chunk >= 1;
 	// Most workgroups lie inside one long hop: its record is then the same for every thread and is
@@ -1196,9 +1200,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
 		const unsigned long long seg0 = w.seg_symbase[(long)img * MAX_SEGS + k] + w.hop_q0[(long)img * w.MAX_HOPS + lo] -
 			w.cs[vs * n + hf[lo]];
 		const unsigned long long base_w = (seg0 + w.cs[vs * n + first_chunk]) >> 4;   // uniform
+		unsigned *has_ones = w.seg_ones + (long)img * MAX_SEGS + k;                   // uniform: the whole stretch is segment k's
 		if (threadIdx.x == 0)
 			win_last = 0u;
 		__syncthreads();
+		bool placed;   // this thread's chunk had a token: a one was set, in the window or beyond it
 		{
 			const ChunkWin cw = chunk_load((const unsigned long long *)(streams + img * stream_stride), stream_stride >> 3, chunk);
 			const unsigned short in = w.exitX[vs * w.NCH + chunk - 1];
@@ -1219,7 +1225,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
 					++roff;
 				},
 				[&]() { roff_prev = roff; }, [&]() { roff = roff_prev; });
-			if (roff > roff0) {
+			placed = roff > roff0;
+			if (placed) {
 				const unsigned lw = (roff - 1) >> 4;
 				atomicMax(&win_last, lw < (unsigned)HB_WIN - 1u ? lw : (unsigned)HB_WIN - 1u);
 			}
@@ -1236,6 +1243,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
 				else if (v)
 					atomicOr(gp + i, v);
 			}
+			if (placed)   // k_rank may not skip the segment's count (one store per wave, beside the window's: the barrier below waits for both)
+				*has_ones = 1u;
 		}
 		__syncthreads();   // the window is reused by the next virtual block
 		continue;
@@ -1264,6 +1273,8 @@ __global__ __launch_bounds__(256) void k_part_reset(DWork h, int cnt)
 		h.nhops[t] = 0;
 	if (t < (long)cnt * 48 * MAX_PLANES)
 		h.segidx[t] = 0;
+	if (t < (long)cnt * MAX_SEGS)   // (the bitmap is cleared beside this: a flag of the first attempt would only be a false 1)
+		h.seg_ones[t] = 0u;
 	if (t < (long)cnt * (long)(sizeof(DecInfo) / sizeof(int)))
 		reinterpret_cast<int *>(h.info)[t] = 0;
 }
@@ -1478,6 +1489,7 @@ __global__ __launch_bounds__(64) void k_tokenize(UnpackGeom g, DWork w, const un
 		nonsig_own[0] = (int)idx[seg_k].n1;
 	}
 	int *sd = w.seg_desc + (long)img * MAX_SEGS;
+	unsigned *sones = w.seg_ones + (long)img * MAX_SEGS;
 	unsigned long long *ssym = w.seg_symbase + (long)img * MAX_SEGS;
 	unsigned long long *sb2 = w.seg_b2 + (long)img * MAX_SEGS;
 	unsigned *sn2 = w.seg_n2done + (long)img * MAX_SEGS;
@@ -1704,8 +1716,10 @@ __global__ __launch_bounds__(64) void k_tokenize(UnpackGeom g, DWork w, const un
 			}
 			q += (int)zr;
 			cnt = 0;
-			if (p >= 0)
+			if (p >= 0) {   // (a token read by hand, never one of a stitched stretch: those are k_hopbits')
 				bm.set_one(sym0 + (unsigned)q);
+				sones[k] = 1u;
+			}
 			++ones;
 			if (!br_synced) {
 				br.seek(br.b);
@@ -1952,7 +1966,11 @@ __global__ __launch_bounds__(64) void k_segjoin(UnpackGeom g, DWork w, const uns
 // (-> first symbol index of every tile at this plane) and k_count subtracts the
 // ones the plane finds in each tile.  No coefficient is touched yet.
 
-__global__ __launch_bounds__(1024) void k_rank(UnpackGeom g, DWork w, int p)
+// A segment in which nobody set a one (seg_ones: the walker and k_hopbits raise it where they set bits) gets no
+// count_base: k_count leaves its tiles alone, their slices of the bitmap are all zeros.  The ranks are still
+// needed (k_apply_all: refinement bits of the tiles that are already on).  every_plane (DWTX_OPT_COUNT_EVERY_PLANE)
+// counts regardless.
+__global__ __launch_bounds__(1024) void k_rank(UnpackGeom g, DWork w, int p, bool every_plane)
 {
 	__shared__ unsigned wsum[16];
 	__shared__ unsigned carry;
@@ -1961,7 +1979,8 @@ __global__ __launch_bounds__(1024) void k_rank(UnpackGeom g, DWork w, int p)
 	const int img = plane / g.C, c = plane - img * g.C;
 	const int k1 = w.info[img].status ? 0 : w.segidx[((long)img * 48 + c * 16 + l) * MAX_PLANES + p];
 	if (threadIdx.x == 0)   // k_count's tiles find their segment's symbols with one look-up
-		w.count_base[(long)plane * 16 + l] = k1 ? 1ull + 2ull * w.seg_symbase[(long)img * MAX_SEGS + k1 - 1] : 0ull;
+		w.count_base[(long)plane * 16 + l] = k1 && (every_plane || w.seg_ones[(long)img * MAX_SEGS + k1 - 1]) ?
+			1ull + 2ull * w.seg_symbase[(long)img * MAX_SEGS + k1 - 1] : 0ull;
 	if (!k1)
 		return;
 	const int t0 = g.tile_first[l], nt = g.tile_first[l + 1] - t0;
@@ -2397,6 +2416,7 @@ template <class F> static void dwork_tables(DWork &w, unsigned *&clear_words, in
 	auto t = [&](int slot, auto *&table, long elems) { f(slot, table, elems, 1l); };
 	t(SLOT_UP_SMALL, w.info, 1);
 	t(SLOT_UP_SMALL, w.segidx, 48 * MAX_PLANES);
+	t(SLOT_UP_SMALL, w.seg_ones, MAX_SEGS);   // (before seg_desc: queue_clears zeroes up to there)
 	t(SLOT_UP_SMALL, w.seg_desc, MAX_SEGS);
 	t(SLOT_UP_SMALL, w.seg_symbase, MAX_SEGS);
 	t(SLOT_UP_SMALL, w.seg_b2, MAX_SEGS);
@@ -2515,7 +2535,7 @@ struct DecodeCall {
 		const int nplanes = n * g.C;
 		DWTX_HIP(hipMemsetAsync(w.todo_count, 0, sizeof(unsigned) * (LINK_ROUNDS + 2) * (size_t)w.todo_round, s));
 		DWTX_HIP(hipMemsetAsync(w.nhops, 0, sizeof(int) * (size_t)n, s));
-		DWTX_HIP(hipMemsetAsync(w.info, 0, (char *)w.seg_desc - (char *)w.info, s));   // info, segidx
+		DWTX_HIP(hipMemsetAsync(w.info, 0, (char *)w.seg_desc - (char *)w.info, s));   // info, segidx, seg_ones
 		// The symbol bitmap (the one big clear, ~64 MB per 4096x4096 plane) is only needed by the token walk:
 		// it is cleared on the first side stream while the chunk tables are built on the caller's.
 		const int rc = dwtx_need_part_streams(ctx, 2);
@@ -2707,8 +2727,9 @@ struct DecodeCall {
 		for (int i = p.first; i < end; ++i)
 			if (!host_info[i].status && host_info[i].pmax > pmax)
 				pmax = host_info[i].pmax;
+		const bool every_plane = ctx->opt[DWTX_OPT_COUNT_EVERY_PLANE] != 0;
 		for (int b = pmax - 1; b >= 0; --b) {
-			hipLaunchKernelGGL(k_rank, dim3(g.levels, p.count * C), dim3(1024), 0, p.stream, g, h, b);
+			hipLaunchKernelGGL(k_rank, dim3(g.levels, p.count * C), dim3(1024), 0, p.stream, g, h, b, every_plane);
 			hipLaunchKernelGGL(k_count, dim3(dwtx_cdiv(w.NT, 256), p.count * C), dim3(256), 0, p.stream, g, h, b);
 		}
 		// Whole-resolution images only (decode.c:251-254: a stream that ends early gives a smaller picture, whose

@@ -176,6 +176,7 @@ enum dwtx_option {
 	DWTX_OPT_NO_PIXELS16,          /* deep pixels: the finest level never reads / writes the uint16_t pixels itself (widened int32 planes in between) */
 	DWTX_OPT_LIFT_ROWS,            /* transforms: row pairs per wave strip of every lifting launch, 4, 8, 16, 32 or 64 (0 = automatic, by the size of the batch);
 	                                * the two-levels-per-pass kernels take max(2, value / 8) of their coarser row pairs; any other value: DWTX_ERR_ARG from the call */
+	DWTX_OPT_COUNT_EVERY_PLANE,    /* decoder: the ones count reads every (plane, ring) segment, also those in which no one was set */
 	DWTX_OPT_COUNT
 };
 int dwtx_ctx_set_option(dwtx_ctx *ctx, int option, long value);
