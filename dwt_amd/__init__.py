@@ -12,7 +12,8 @@ import ctypes as C
 from . import _lib
 from ._lib import Geom, Stats, StreamInfo, DecodeInfo, Index, SegIndex, View, TileGroup, INDEX_MAGIC, INDEX_MAX_SEGS, LIB_PATH  # noqa: F401
 
-__all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "tile_groups", "Geom", "Stats", "View", "TileGroup"]
+__all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "tile_groups", "view_fields", "Geom", "Stats", "View",
+           "TileGroup"]
 
 
 class DwtxError(RuntimeError):
@@ -49,6 +50,32 @@ def tile_groups(W, H, tile):
     if k < 0:
         raise DwtxError(k, "dwtx_tile_groups")
     return [TileGroup.from_buffer_copy(bytes(out[i])) for i in range(k)]
+
+
+def view_fields(shape, strides, stepped=False):
+    """Shape and strides (in samples) of a tensor [n,H,W,C] or [bands,cols,H,W,C] -> the fields of its dwtx_view and its
+    pixel step: a dict with W, H, channels, n, cols, row_pitch, image_stride, band_stride, channel_stride and pixel_step
+    (0: dense).  Needs no device.  RGB pixels are interleaved (channel stride 1, column stride 3) or planar (column stride 1,
+    any channel stride).  stepped=True also takes pixels that lie further apart than their own samples — RGB with channel
+    stride 1 and a column stride of 3 or more (`rgba[..., :3]`), one channel with any column stride of 1 or more
+    (`rgba[..., 3:]`, `uv[:, :, 0::2]`) — and reports the column stride as pixel_step, for the *_view_step calls."""
+    if len(shape) not in (4, 5) or len(strides) != len(shape):
+        raise ValueError("a view needs a tensor [n,H,W,C] or [bands,cols,H,W,C]")
+    H, W, Cn = shape[-3:]
+    sh, sw, sc = strides[-3:]
+    planar = Cn == 3 and sw == 1 and sc >= 1
+    step = 0
+    if Cn in (1, 3) and not planar and stepped and sw >= Cn and (Cn == 1 or sc == 1):
+        step = 0 if sw == Cn else sw
+    elif Cn not in (1, 3) or not (planar or (sw == Cn and (Cn == 1 or sc == 1))):
+        raise ValueError("a view needs 1 or 3 channels, RGB pixels either interleaved (channel stride 1, column stride 3) or planar "
+                         f"(column stride 1, any channel stride), not channel stride {sc} and column stride {sw} (C = {Cn})")
+    if len(shape) == 4:
+        n, cols, band = shape[0], 0, 0
+    else:
+        n, cols, band = shape[0] * shape[1], shape[1], strides[0]
+    return dict(W=W, H=H, channels=Cn, n=n, cols=cols, row_pitch=sh, image_stride=strides[-4], band_stride=band,
+                channel_stride=sc if planar else 0, pixel_step=step)
 
 
 def _ptr(t):
@@ -458,54 +485,57 @@ class Context:
 
     # -- strided views: windows and tile grids of a larger frame (dwtx_encode_view / dwtx_decode_view) -----------
 
-    def _view(self, t, maxval):
+    def _view(self, t, maxval, stepped=False):
         """View of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (uint8, or uint16 / int16 for deep pixels):
         the windows stay where they are.  RGB pixels are interleaved (channel stride 1, column stride 3) or planar (column
-        stride 1, any channel stride): `nchw.permute(0, 2, 3, 1)` and `chw.permute(1, 2, 0)` are views as they are."""
+        stride 1, any channel stride): `nchw.permute(0, 2, 3, 1)` and `chw.permute(1, 2, 0)` are views as they are.
+        stepped: pixels further apart than their samples too (view_fields); the last value returned is their pixel step."""
         torch = self.torch
         if t.dtype not in (torch.uint8, torch.uint16, torch.int16) or t.device != self.device or t.dim() not in (4, 5):
             raise ValueError("a view needs a uint8 / uint16 / int16 tensor [n,H,W,C] or [bands,cols,H,W,C] on the context's device")
-        H, W, Cn = t.shape[-3:]
-        sh, sw, sc = t.stride()[-3:]
-        planar = Cn == 3 and sw == 1 and sc >= 1
-        if Cn not in (1, 3) or not (planar or (sw == Cn and (Cn == 1 or sc == 1))):
-            raise ValueError("a view needs 1 or 3 channels, RGB pixels either interleaved (channel stride 1, column stride 3) or planar "
-                             f"(column stride 1, any channel stride), not channel stride {sc} and column stride {sw} (C = {Cn})")
+        f = view_fields(tuple(t.shape), tuple(t.stride()), stepped)
         deep = t.dtype != torch.uint8
         if maxval is None:
             maxval = 65535 if deep else 255
-        if t.dim() == 4:
-            n, cols, band = t.shape[0], 0, 0
-        else:
-            n, cols, band = t.shape[0] * t.shape[1], t.shape[1], t.stride(0)
-        v = View(t.data_ptr(), 2 if deep else 1, Cn, maxval, cols, sh, t.stride(-4), band, sc if planar else 0)
-        return v, W, H, Cn, n
+        v = View(t.data_ptr(), 2 if deep else 1, f["channels"], maxval, f["cols"], f["row_pitch"], f["image_stride"], f["band_stride"],
+                 f["channel_stride"])
+        return v, f["W"], f["H"], f["channels"], f["n"], f["pixel_step"]
 
-    def encode_view(self, t, capacity=0, out=None, info=None):
+    def encode_view(self, t, capacity=0, out=None, info=None, stepped=False):
         """dwtx_encode_view: the windows of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (a slice, a crop, a
         grid of tiles, a channel-first batch permuted to channel-last: see _view) -> (streams uint8 [n,stride], info uint8
-        [n,sizeof(StreamInfo)]) on device, as encode_device / encode_device16 give for the contiguous copy; async."""
+        [n,sizeof(StreamInfo)]) on device, as encode_device / encode_device16 give for the contiguous copy; async.
+        stepped=True: dwtx_encode_view_step — `rgba[..., :3]`, `rgba[..., 3:]` and `uv[:, :, 0::2]` are views as they lie."""
         torch = self.torch
-        v, W, H, Cn, n = self._view(t, None)
+        v, W, H, Cn, n, step = self._view(t, None, stepped)
         bound = self.lib.dwtx_encode_bound16 if v.sample_bytes == 2 else self.lib.dwtx_encode_bound
         stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
         if out is None:
             out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         if info is None:
             info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
-        _check(self.lib.dwtx_encode_view(self.h, C.byref(v), W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view")
+        if stepped:
+            _check(self.lib.dwtx_encode_view_step(self.h, C.byref(v), step, W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
+                   "dwtx_encode_view_step")
+        else:
+            _check(self.lib.dwtx_encode_view(self.h, C.byref(v), W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view")
         return out, info
 
-    def decode_view(self, streams, lens, into, maxval=None, levels_max=-1):
+    def decode_view(self, streams, lens, into, maxval=None, levels_max=-1, stepped=False):
         """dwtx_decode_view: device streams [n,stride] + int64 lens -> the windows of the strided device tensor `into`
         ([n,H,W,C] or [bands,cols,H,W,C]), each picture in its window's top-left corner at the size its stream supports;
         nothing else of `into`'s storage is written.  maxval: the deep pictures' (default 65535).  Returns the list of
-        DecodeInfo; syncs once."""
+        DecodeInfo; syncs once.  stepped=True: dwtx_decode_view_step, for the tensors encode_view takes with it; the
+        samples between the pixels (an RGBA surface's alpha) are not written either."""
         torch = self.torch
-        v, W, H, Cn, n = self._view(into, maxval)
+        v, W, H, Cn, n, step = self._view(into, maxval, stepped)
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
         assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
         infos = (DecodeInfo * n)()
-        _check(self.lib.dwtx_decode_view(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
-                                         C.cast(infos, C.c_void_p)), "dwtx_decode_view")
+        if stepped:
+            _check(self.lib.dwtx_decode_view_step(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step,
+                                                  C.cast(infos, C.c_void_p)), "dwtx_decode_view_step")
+        else:
+            _check(self.lib.dwtx_decode_view(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
+                                             C.cast(infos, C.c_void_p)), "dwtx_decode_view")
         return list(infos)

@@ -362,8 +362,10 @@ extern "C" int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, s
 
 // ---- views (include/dwtx.h): windows and tile grids of a larger frame ----------------------------------------------
 
-// dwtx_view -> dwtx_pixels for n windows of W x H, checked; `dst`: the view will be written (maxval, disjoint windows)
-static int pixels_of_view(const dwtx_view *v, int W, int H, int n, bool dst, dwtx_pixels *px)
+// dwtx_view -> dwtx_pixels for n windows of W x H, checked; `dst`: the view will be written (maxval, disjoint windows).
+// pixel_step (the *_view_step calls; the plain ones pass 0): samples from a pixel to the next one of its row; 0 and
+// `channels` are both the dense case and leave px->pixel_step 0, so that everything downstream is the plain call's.
+static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int W, int H, int n, bool dst, dwtx_pixels *px)
 {
 	if (!v || !v->dev || n < 1) {
 		dwtx_set_error("no view, no pixels or no windows");
@@ -375,7 +377,17 @@ static int pixels_of_view(const dwtx_view *v, int W, int H, int n, bool dst, dwt
 		return DWTX_ERR_ARG;
 	}
 	const size_t cs = v->channels == 3 ? v->channel_stride : 0;   // planar RGB; a gray view has no use for it
-	const size_t row = cs ? (size_t)W : (size_t)W * v->channels;  // a row of a window (planar: of one of its planes)
+	const size_t step = pixel_step == (size_t)v->channels ? 0 : pixel_step;
+	if (step && (step < (size_t)v->channels || step > 0x7fffffffu)) {
+		dwtx_set_error("view: pixel_step %zu is less than the %d channels of a pixel (or beyond 2^31)", pixel_step, v->channels);
+		return DWTX_ERR_ARG;
+	}
+	if (step && cs) {
+		dwtx_set_error("view: pixel_step %zu with planar pixels (channel_stride %zu): the rows of a plane are dense", pixel_step, cs);
+		return DWTX_ERR_ARG;
+	}
+	// a row of a window (planar: of one of its planes), from its first sample to behind its last
+	const size_t row = cs ? (size_t)W : step ? (size_t)(W - 1) * step + v->channels : (size_t)W * v->channels;
 	if (v->row_pitch < row) {
 		dwtx_set_error("view: row_pitch %zu is less than a window's row of %zu samples", v->row_pitch, row);
 		return DWTX_ERR_ARG;
@@ -422,6 +434,7 @@ static int pixels_of_view(const dwtx_view *v, int W, int H, int n, bool dst, dwt
 		: dwtx_pixels16((const uint16_t *)v->dev, v->channels, v->image_stride, dst ? v->maxval : 65535);
 	px->row_pitch = v->row_pitch;
 	px->channel_stride = cs;
+	px->pixel_step = step;
 	if (bands) {
 		px->cols = (int)cols;
 		px->band_stride = v->band_stride;
@@ -433,7 +446,16 @@ extern "C" int dwtx_encode_view(dwtx_ctx *ctx, const dwtx_view *src, int W, int 
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
 {
 	dwtx_pixels px;
-	if (const int rc = pixels_of_view(src, W, H, n, false, &px))
+	if (const int rc = pixels_of_view(src, 0, W, H, n, false, &px))
+		return rc;
+	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
+}
+
+extern "C" int dwtx_encode_view_step(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int W, int H, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	dwtx_pixels px;
+	if (const int rc = pixels_of_view(src, pixel_step, W, H, n, false, &px))
 		return rc;
 	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
 }
@@ -442,7 +464,16 @@ extern "C" int dwtx_decode_view(dwtx_ctx *ctx, const uint8_t *dev_streams, size_
 	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, dwtx_decode_info *host_info)
 {
 	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, W, H, n, true, &px))
+	if (const int rc = pixels_of_view(dst, 0, W, H, n, true, &px))
+		return rc;
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
+}
+
+extern "C" int dwtx_decode_view_step(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, dwtx_decode_info *host_info)
+{
+	dwtx_pixels px;
+	if (const int rc = pixels_of_view(dst, pixel_step, W, H, n, true, &px))
 		return rc;
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
 }

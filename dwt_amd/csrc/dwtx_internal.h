@@ -168,6 +168,9 @@ template <class F> char *carve(dwtx_ctx *ctx, int slot, F &&fn)
 // bands of `cols` each.  Window i of the view is window first + i of the grid, which starts at `base`.
 // RGB samples are interleaved, or planar (channel_stride != 0, views only: include/dwtx.h): three planes per window,
 // columns one sample apart; the host-buffer pipelines and every dense entry point stay interleaved.
+// Interleaved and gray pixels may lie further apart than their own samples (pixel_step, the *_view_step calls only): the
+// RGB of an RGBA surface, its alpha, one plane of a mosaic — what lies between a pixel's samples and the next pixel is
+// never written, and read only by lift.hip's Rgbx8 source (the fourth byte of a window's own 4-byte pixels, never used).
 struct dwtx_pixels {
 	void *base;            // the grid's window 0, first sample
 	int sample_bytes;      // 1 or 2
@@ -179,6 +182,7 @@ struct dwtx_pixels {
 	size_t band_stride = 0;   // from a band's first window to the next band's
 	size_t first = 0;      // the view's first window in the grid (parts of a batch start anywhere in it)
 	size_t channel_stride = 0;   // 0: interleaved; else planar RGB: from a window's plane of one channel to the next one's (image() and moved() keep it)
+	size_t pixel_step = 0;       // 0: dense (a pixel is its channels); else from a pixel to the next one of its row, above channels (image() and moved() keep it)
 
 	bool deep() const { return sample_bytes == 2; }
 	size_t bytes(size_t samples) const { return samples * (size_t)sample_bytes; }
@@ -189,6 +193,11 @@ struct dwtx_pixels {
 	uint16_t *u16() const { return static_cast<uint16_t *>(base); }
 	bool one_band() const { return cols == 0; }
 	bool planar() const { return channel_stride != 0; }
+	bool stepped() const { return pixel_step != 0; }
+	// from a pixel to the next one of its row
+	size_t step() const { return planar() ? 1 : pixel_step ? pixel_step : (size_t)channels; }
+	// 8-bit RGB in 4-byte pixels (RGBA / RGBX surfaces): the one stepped layout lift.hip's wide kernels take
+	bool rgbx8() const { return pixel_step == 4 && channels == 3 && sample_bytes == 1 && !planar(); }
 	size_t pitch(int W) const { return row_pitch ? row_pitch : (size_t)W * (planar() ? 1 : channels); }
 	// the same pictures from image i on: a one-band view moves its base (first stays 0), a grid keeps its origin and moves the index
 	dwtx_pixels image(size_t i) const
@@ -229,7 +238,8 @@ static inline dwtx_pixels dwtx_pixels16(const uint16_t *pix, int channels, size_
 // lift.hip: the finest lifting level reads / writes pixels itself (the widening of pnm.h:69-74, the clamp of pnm.h:108
 // and, for RGB, the YCoCg-R colour transform of image.h:39-65 fused into it).  dwtx_pixels_ok says whether the shape and
 // the buffer allow it: W % 4 == 0, more than 64 pixels on a side (the wide kernel, not the LDS tail), px.wide() (a planar
-// picture's channel stride on the quad grid too), and windows the kernels can address (lift.hip).
+// picture's channel stride on the quad grid too), and windows the kernels can address (lift.hip).  Of the stepped views
+// (dwtx_pixels::pixel_step) only 8-bit RGB in 4-byte pixels qualifies: every other one takes the general conversions.
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H);
 // lift.hip: asks for the scratch planes every lifting call of a W*H transform over nplanes planes asks for
 int dwtx_lift_scratch(dwtx_ctx *ctx, int W, int H, int nplanes);

@@ -380,6 +380,9 @@ struct FwdRaw {
 struct Rgb8 {};
 // or 8-bit planar RGB pixels (dwtx_pixels::channel_stride): three gray-style rows per row, one per plane, no unpacking
 struct RgbP8 {};
+// or 8-bit RGB in 4-byte pixels (dwtx_pixels::rgbx8(): RGBA / RGBX surfaces, pixel step 4): interleaved like Rgb8, a lane's
+// four pixels one 16-byte piece whose every fourth byte is loaded and never used
+struct Rgbx8 {};
 template <typename SrcT>
 struct SrcTag {};
 
@@ -446,6 +449,10 @@ __device__ __forceinline__ const uint8_t *fwd_base(SrcTag<Rgb8>, const LevelArgs
 	ch = plane % 3;
 	return a.src8 + win_off(a.grid, a.src_ps, plane / 3);   // src_ps = bytes from an interleaved image to the next, spitch = bytes per row
 }
+__device__ __forceinline__ const uint8_t *fwd_base(SrcTag<Rgbx8>, const LevelArgs &a, int plane, int &ch)
+{
+	return fwd_base(SrcTag<Rgb8>(), a, plane, ch);   // (spitch = bytes per row of 4-byte pixels)
+}
 __device__ __forceinline__ const uint8_t *fwd_base(SrcTag<RgbP8>, const LevelArgs &a, int plane, int &ch)
 {
 	ch = plane % 3;
@@ -499,6 +506,10 @@ struct IsRgb<Rgb8> {
 };
 template <>
 struct IsRgb<RgbP8> {
+	static constexpr bool value = true;
+};
+template <>
+struct IsRgb<Rgbx8> {
 	static constexpr bool value = true;
 };
 
@@ -1287,6 +1298,55 @@ __device__ __forceinline__ RowP row_p(const FwdRawRgb3 &r, int ch)
 	return o;
 }
 
+// RGB in 4-byte pixels: the lane's four pixels are one 16-byte load (rows and window origins are multiples of 4 bytes:
+// dwtx_pixels::wide()), a word per pixel, the fourth byte of each never used; the edge is the neighbours' two words — lane 0:
+// pixels 4q-2 and 4q-1, the others: pixel 4q+4 first — clamped into the row's own 4*W bytes like every edge here.
+typedef unsigned U32x4 __attribute__((ext_vector_type(4)));
+struct FwdRawRgbxP {
+	U32x4 px;    // pixels 4q .. 4q+3
+	U32x2 e;
+};
+struct FwdRawRgbx {
+	unsigned a, b, c, d;   // pixels 4q .. 4q+3
+	unsigned e0, e1;
+};
+__device__ __forceinline__ LaneAt lane_at(SrcTag<Rgbx8>, int q, int lane, int nquads)
+{
+	const int qa = min(q, nquads - 1);
+	LaneAt o = { 16 * qa, lane == 0 ? max(16 * qa - 8, 0) : min(16 * qa + 16, 16 * nquads - 8) };
+	return o;
+}
+__device__ __forceinline__ FwdRawRgbxP fwd_load_p(SrcTag<Rgbx8>, const uint8_t *__restrict__ row, const LaneAt &at, long, int)
+{
+	FwdRawRgbxP r;
+	r.px = *reinterpret_cast<const U32x4 *>(row + at.main);
+	r.e = *reinterpret_cast<const U32x2 *>(row + at.edge);
+	return r;
+}
+__device__ __forceinline__ FwdRawRgbx hold(const FwdRawRgbxP &r)
+{
+	FwdRawRgbx o = { hold(r.px.x), hold(r.px.y), hold(r.px.z), hold(r.px.w), hold(r.e.x), hold(r.e.y) };
+	return o;
+}
+__device__ __forceinline__ FwdRawRgbx as_used(const FwdRawRgbxP &r)
+{
+	FwdRawRgbx o = { r.px.x, r.px.y, r.px.z, r.px.w, r.e.x, r.e.y };
+	return o;
+}
+// channel ch of the pixels in the words lo and hi, as a packed pair (v_perm_b32 as in row_p(FwdRawRgb): a word is R G B x)
+__device__ __forceinline__ P2 rgbx_pair(unsigned lo, unsigned hi, int ch)
+{
+	return ycocg_p(p2_of(__builtin_amdgcn_perm(hi, lo, 0x0c040c00u)), p2_of(__builtin_amdgcn_perm(hi, lo, 0x0c050c01u)),
+		p2_of(__builtin_amdgcn_perm(hi, lo, 0x0c060c02u)), ch);
+}
+__device__ __forceinline__ RowP row_p(const FwdRawRgbx &r, int ch)
+{
+	RowP o = { rgbx_pair(r.a, r.c, ch), rgbx_pair(r.b, r.d, ch),
+		ycocg_p(p2_of(r.e0 & 255u), p2_of((r.e0 >> 8) & 255u), p2_of((r.e0 >> 16) & 255u), ch),   // lane 63: e0 = pixel 4q+4
+		rgbx_pair(r.e0, r.e1, ch) };                                                              // lane 0: e0, e1 = pixels 4q-2, 4q-1
+	return o;
+}
+
 // the row as it is loaded / as it is used
 template <typename SrcT>
 struct RowRegs {
@@ -1298,6 +1358,12 @@ template <>
 struct RowRegs<Rgb8> {
 	typedef FwdRawRgbP Loaded;
 	typedef FwdRawRgb Used;
+	static constexpr int S = 2;
+};
+template <>
+struct RowRegs<Rgbx8> {
+	typedef FwdRawRgbxP Loaded;
+	typedef FwdRawRgbx Used;
 	static constexpr int S = 2;
 };
 template <>
@@ -2159,8 +2225,31 @@ __device__ __forceinline__ Rgb24 rgb16_planar_of(const Quad4 &y, const Quad4 &co
 }
 
 // what the RGB kernel's lanes write per row: twelve bytes of 8-bit pixels, or twenty-four of deep ones — interleaved in one
-// piece, or (PLANAR; cs = the channel stride in samples) as three aligned quads, one per plane: 4 bytes each, 8 of deep pixels
-template <typename PixT, bool PLANAR = false>
+// piece (PIX_PACKED), or (PIX_PLANAR; cs = the channel stride in samples) as three aligned quads, one per plane: 4 bytes each,
+// 8 of deep pixels, or (PIX_STEP4: 8-bit RGB in 4-byte pixels, dwtx_pixels::rgbx8()) the three colour bytes of each of the four
+// pixels and NOT the fourth: a halfword and a byte per pixel, nothing read, merged and written back (include/dwtx.h: another
+// stream may be writing the fourth bytes at the same moment)
+enum PixLayout { PIX_PACKED = 0, PIX_PLANAR = 1, PIX_STEP4 = 2 };
+struct Rgbx16 {
+	unsigned w[4];   // four pixels: R | G << 8 | B << 16
+};
+template <bool NT>
+__device__ __forceinline__ void rgbx_store(uint8_t *p, const Rgbx16 &v)
+{
+#pragma unroll
+	for (int k = 0; k < 4; ++k) {
+		const unsigned short rg = (unsigned short)v.w[k];
+		const uint8_t b = (uint8_t)(v.w[k] >> 16);
+		if (NT) {
+			__builtin_nontemporal_store(rg, reinterpret_cast<unsigned short *>(p + 4 * k));
+			__builtin_nontemporal_store(b, p + 4 * k + 2);
+		} else {
+			*reinterpret_cast<unsigned short *>(p + 4 * k) = rg;
+			p[4 * k + 2] = b;
+		}
+	}
+}
+template <typename PixT, PixLayout LAYOUT = PIX_PACKED>
 struct RgbOut {
 	typedef Rgb12 row;
 	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int);
@@ -2171,7 +2260,7 @@ struct RgbOut {
 	}
 };
 template <>
-struct RgbOut<uint16_t, false> {
+struct RgbOut<uint16_t, PIX_PACKED> {
 	typedef Rgb24 row;
 	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M) { return rgb16_of(y, co, cg, M); }
 	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long)   // (pitch in samples; rows and quads are multiples of 8 bytes)
@@ -2183,7 +2272,7 @@ struct RgbOut<uint16_t, false> {
 	}
 };
 template <>
-struct RgbOut<uint8_t, true> {
+struct RgbOut<uint8_t, PIX_PLANAR> {
 	typedef Rgb12 row;
 	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgb_planar_of(y, co, cg); }
 	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long cs)
@@ -2195,7 +2284,7 @@ struct RgbOut<uint8_t, true> {
 	}
 };
 template <>
-struct RgbOut<uint16_t, true> {
+struct RgbOut<uint16_t, PIX_PLANAR> {
 	typedef Rgb24 row;
 	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M) { return rgb16_planar_of(y, co, cg, M); }
 	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long cs)
@@ -2204,6 +2293,25 @@ struct RgbOut<uint16_t, true> {
 #pragma unroll
 		for (int c = 0; c < 3; ++c)
 			*reinterpret_cast<uint2 *>(p + c * cs) = make_uint2(v.w[2 * c], v.w[2 * c + 1]);
+	}
+};
+__device__ __forceinline__ Rgbx16 rgbx_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg)
+{
+	unsigned px[3][4];
+	rgb_planes_of(y, co, cg, 255, px);
+	Rgbx16 o;
+#pragma unroll
+	for (int k = 0; k < 4; ++k)
+		o.w[k] = px[0][k] | (px[1][k] << 8) | (px[2][k] << 16);
+	return o;
+}
+template <>
+struct RgbOut<uint8_t, PIX_STEP4> {
+	typedef Rgbx16 row;
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgbx_of(y, co, cg); }
+	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long)
+	{
+		rgbx_store<false>(dst + r * pitch + 16 * qd, v);
 	}
 };
 
@@ -2228,12 +2336,13 @@ __device__ __forceinline__ Rgb12 rgb_of(const Quad4 &y, const Quad4 &co, const Q
 	return o;
 }
 
-template <typename PixT, bool PLANAR>
-__device__ __forceinline__ typename RgbOut<PixT, PLANAR>::row RgbOut<PixT, PLANAR>::of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgb_of(y, co, cg); }
+template <typename PixT, PixLayout LAYOUT>
+__device__ __forceinline__ typename RgbOut<PixT, LAYOUT>::row RgbOut<PixT, LAYOUT>::of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgb_of(y, co, cg); }
 
 // PixT = uint16_t: deep pixels (dst8 points to uint16_t samples, ll_ps / llpitch count samples, clamps at a.maxval)
-// PLANAR: dst8 is channel 0's plane of the window, the others A.cstride samples apart, llpitch the pitch of a plane's rows
-template <bool F16, typename PixT = uint8_t, bool PLANAR = false>
+// PIX_PLANAR: dst8 is channel 0's plane of the window, the others A.cstride samples apart, llpitch the pitch of a plane's rows
+// PIX_STEP4: llpitch is the pitch of rows of 4-byte pixels; the step is the constant 4 here, no argument carries it
+template <bool F16, typename PixT = uint8_t, PixLayout LAYOUT = PIX_PACKED>
 __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 {
 	const LevelArgs &a = A.a;
@@ -2256,7 +2365,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 		llp[ch] = a.src + (long)(3 * image + ch) * a.src_ps;
 		det[ch] = DetPtr<F16>::of(a, 3 * image + ch);
 	}
-	typedef RgbOut<PixT, PLANAR> Out;
+	typedef RgbOut<PixT, LAYOUT> Out;
 	uint8_t *dst = a.dst8 + win_off(a.grid, a.ll_ps, image) * (long)sizeof(PixT);
 	const InvAt at = inv_at(a, qd, A.nquads);
 
@@ -2303,8 +2412,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 // 32-byte pieces, the block's four waves side by side 21 whole lines.  Three planes' state and rows in flight: ~150 vector
 // registers, three waves per SIMD — and still the faster way: the int32 LL planes of the second level (3 B per pixel written,
 // 3 B read) are gone.  grid.z = image.
-// PLANAR: the lane's four pixels go out as one word to each of the window's three planes (a.cstride apart) instead
-template <bool F16, bool PLANAR = false>
+// PIX_PLANAR: the lane's four pixels go out as one word to each of the window's three planes (a.cstride apart) instead
+// PIX_STEP4: into 4-byte pixels, three bytes of each (rgbx_store)
+template <bool F16, PixLayout LAYOUT = PIX_PACKED>
 __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 {
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -2364,13 +2474,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 		n1a[ch] = load1(ch, 2 * m0 + 1);
 		n1b[ch] = load1(ch, 2 * m0 + 2);
 	}
-	Rgb12 orow[4];
+	typename RgbOut<uint8_t, LAYOUT>::row orow[4];
 	auto store_rows = [&](int m) {
 		if (!own)
 			return;
 #pragma unroll
 		for (int k = 0; k < 4; ++k) {
-			if (PLANAR) {
+			if constexpr (LAYOUT == PIX_STEP4) {
+				rgbx_store<true>(dst + (long)(4 * m + k) * a.opitch + 16 * q, orow[k]);
+			} else if constexpr (LAYOUT == PIX_PLANAR) {
 				uint8_t *p = dst + (long)(4 * m + k) * a.opitch + 4 * q;
 #pragma unroll
 				for (int c = 0; c < 3; ++c)
@@ -2438,7 +2550,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 		}
 #pragma unroll
 		for (int k = 0; k < 4; ++k)
-			orow[k] = PLANAR ? rgb_planar_of(rows[0][k], rows[1][k], rows[2][k]) : rgb_of(rows[0][k], rows[1][k], rows[2][k]);
+			orow[k] = RgbOut<uint8_t, LAYOUT>::of(rows[0][k], rows[1][k], rows[2][k], 255);
 	}
 	store_rows(m1 - 1);
 }
@@ -2595,7 +2707,7 @@ struct PixGrid {
 	WinGrid grid;
 	int W, H, C, n;
 	long chan_stride;   // RGB: from a pixel's sample of one channel to the next one's — 1 interleaved, dwtx_pixels::channel_stride planar
-	int col_step;       // from a pixel to the next one of its row: C interleaved, 1 planar
+	int col_step;       // from a pixel to the next one of its row: C interleaved (dwtx_pixels::pixel_step where a view has one), 1 planar
 };
 
 constexpr int PX_LANES = 64, PX_ROWS = 4;   // a workgroup of the conversions: one wave per row, a lane per pixel
@@ -2615,7 +2727,7 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *
 		const P *row = pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
 		int *dst = planes + (long)win * g.C * npix + (long)y * g.W + x;
 		if (g.C == 1) {
-			dst[0] = row[x];
+			dst[0] = row[(long)x * g.col_step];
 		} else {
 			const P *p = row + (long)x * g.col_step;
 			const int r = p[0], gr = p[g.chan_stride], b = p[2 * g.chan_stride];
@@ -2636,7 +2748,8 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi)
 
 // image.h:39-50 ycocg2rgb (input clamps included) + pnm.h:108 output clamp, with M (the pixels' maxval) where the
 // reference has 255: Y and the output to [0, M], Co and Cg to [-M, M].  P = uint8_t (M = 255) or uint16_t.  Same grid as
-// above; only the W*C samples of a window's H rows are written.
+// above; only the C samples of the W pixels of a window's H rows are written — with a column step above C nothing between
+// the pixels is: no word is read, merged and written back (another stream may be writing the samples in between).
 template <class P>
 __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, int M)
 {
@@ -2649,7 +2762,7 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__
 		P *row = pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
 		const int *src = planes + (long)win * g.C * npix + (long)y * g.W + x;
 		if (g.C == 1) {
-			row[x] = (P)clampi(src[0], 0, M);
+			row[(long)x * g.col_step] = (P)clampi(src[0], 0, M);
 		} else {
 			const int yy = clampi(src[0], 0, M);
 			const int co = clampi(src[npix], -M, M);
@@ -2754,7 +2867,7 @@ static PixGrid pix_grid(const dwtx_pixels &px, int W, int H, int n, dim3 *grid)
 {
 	*grid = dim3((unsigned)dwtx_cdiv(W, PX_LANES), (unsigned)dwtx_cdiv(H, PX_ROWS), (unsigned)min(n, 65535));
 	return PixGrid{ (long)px.image_stride, (long)px.pitch(W), win_grid(px), W, H, px.channels, n, px.planar() ? (long)px.channel_stride : 1L,
-		px.planar() ? 1 : px.channels };
+		(int)px.step() };
 }
 
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
@@ -2880,6 +2993,8 @@ static WideKernel fwd_wide_kernel(const dwtx_pixels *px, bool hist, bool src16)
 		return hist ? k_fwd_pixels_w<RgbP8, true> : k_fwd_pixels_w<RgbP8, false>;
 	if (planar)
 		return k_fwd_level_w<false, SRC_RGBP16>;
+	if (px && px->rgbx8())
+		return hist ? k_fwd_pixels_w<Rgbx8, true> : k_fwd_pixels_w<Rgbx8, false>;
 	if (hist) {
 		if (channels8 == 3)
 			return k_fwd_pixels_w<Rgb8, true>;
@@ -3061,11 +3176,12 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 // Can the finest level of a W*H image read / write these pixels directly?  (wide kernel, not the LDS tail)
 // Windows of a frame too (dwtx_pixels: row pitch, bands): the kernels touch only the W * channels samples of a window's
 // rows, so all they ask is that every row of every window — of every plane of a planar window — starts on a quad (px.wide())
-// and that the pitch fits their int.
+// and that the pitch fits their int.  Pixels with a step (dwtx_pixels::pixel_step): only 8-bit RGB in 4-byte pixels, which the
+// Rgbx8 / PIX_STEP4 instances address with the constant 4; the others would be read and written with dense addressing.
 // Any other view goes through the general conversions (dwtx_pixels_to_planes / dwtx_planes_to_pixels).
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H)
 {
-	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide() && px.pitch(W) <= 0x7fffffffu;
+	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide() && px.pitch(W) <= 0x7fffffffu && (!px.stepped() || px.rgbx8());
 }
 
 unsigned dwtx_levels16(int W, int H, unsigned sq_levels)
@@ -3110,7 +3226,7 @@ using Inv2Kernel = void (*)(Inv2Args);
 static Inv2Kernel inv2_kernel(const dwtx_pixels *px, bool det16)
 {
 	if (px && px->channels == 3)
-		return px->planar() ? k_inv2_level_w_rgb<true, true> : k_inv2_level_w_rgb<true>;
+		return px->planar() ? k_inv2_level_w_rgb<true, PIX_PLANAR> : px->rgbx8() ? k_inv2_level_w_rgb<true, PIX_STEP4> : k_inv2_level_w_rgb<true>;
 	if (px)
 		return k_inv2_level_w<uint8_t, true>;
 	return det16 ? k_inv2_level_w<int, true> : k_inv2_level_w<int, false>;
@@ -3122,9 +3238,11 @@ static WideKernel inv_wide_kernel(const dwtx_pixels *px, bool det16)
 	const int channels8 = px && !px->deep() ? px->channels : 0;
 	if (px && px->channels == 3 && px->planar()) {
 		if (px->deep())
-			return k_inv_level_w_rgb<false, uint16_t, true>;
-		return det16 ? k_inv_level_w_rgb<true, uint8_t, true> : k_inv_level_w_rgb<false, uint8_t, true>;
+			return k_inv_level_w_rgb<false, uint16_t, PIX_PLANAR>;
+		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_PLANAR> : k_inv_level_w_rgb<false, uint8_t, PIX_PLANAR>;
 	}
+	if (px && px->rgbx8())
+		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_STEP4> : k_inv_level_w_rgb<false, uint8_t, PIX_STEP4>;
 	if (channels8 == 3)
 		return det16 ? k_inv_level_w_rgb<true> : k_inv_level_w_rgb<false>;
 	if (channels8)

@@ -384,6 +384,34 @@ int dwtx_decode_view(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_st
 	const unsigned long long *dev_lens, int W, int H, int n, int levels_max,
 	const dwtx_view *dst, dwtx_decode_info *host_info);
 
+/* ---- pixel step: pixels that lie further apart than their own samples ------------------------------------------------
+ * dwtx_encode_view / dwtx_decode_view for surfaces whose pixels are more than the coded channels: the RGB of an RGBA8 /
+ * RGBX8 render target (channels 3, pixel_step 4), its alpha (channels 1, dev + 3, pixel_step 4), one chroma plane of NV12
+ * (channels 1, pixel_step 2), one plane of a Bayer mosaic (channels 1, pixel_step 2, twice the frame's row pitch).
+ * pixel_step counts SAMPLES like every stride of a view: sample c of pixel x of a window's row lies x * pixel_step + c
+ * samples after the row's first sample.  Everything else the dwtx_view says keeps its meaning, so grids of tiles, stacks
+ * and deep samples work with a step; dwtx_view itself is unchanged.  pixel_step == 0 or == channels is the dense case:
+ * the call is then dwtx_encode_view / dwtx_decode_view in every respect.  The streams are those of the dense interleaved
+ * copy: the .dwt format knows nothing of the layout.  (An RGBA surface is an RGB stream and a gray stream, in two calls;
+ * the channel order is R, G, B as it lies.)
+ * With row = (W-1)*pixel_step + channels, the samples from a window row's first to behind its last, DWTX_ERR_ARG (with a
+ * dwtx_last_error() text, nothing written): pixel_step non-zero and below channels; a planar view (channels == 3,
+ * channel_stride != 0) with any step but 0 and 3 — the rows of a plane stay dense; row_pitch < row.
+ * Encode: only the windows' samples are read — the `channels` samples of each of the W pixels of a window's H rows.  One
+ * exception: 8-bit RGB in 4-byte pixels (sample_bytes 1, channels 3, pixel_step 4) whose dev, row_pitch, image_stride and
+ * band_stride are multiples of 4 — pictures with W % 4 == 0 and more than 64 pixels on a side are then read a pixel's four
+ * bytes at a time: the fourth byte of a window's OWN pixels is loaded and never used.  The pixel is 4-byte aligned there,
+ * so that byte is addressable whenever the pixel is.  Nothing else of the surface is read. */
+int dwtx_encode_view_step(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int W, int H, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
+/* Decode: the disjointness rules of dwtx_decode_view hold with that `row` in place of W*channels, in the stacked, the
+ * side-by-side and the band form alike (the bounds themselves are accepted).  The `channels` samples of each pixel of the
+ * ow x oh rectangle a stream supports are written and NO OTHER SAMPLE, in particular not the pixel_step - channels samples
+ * between two pixels — the alpha byte of an RGBA surface, the other planes of a mosaic: another stream may be writing
+ * those at the same moment, so nothing is read, merged and written back there. */
+int dwtx_decode_view_step(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, dwtx_decode_info *host_info);
+
 /* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
  * interior, right column, bottom row, corner, in that order, those that exist — each a cols x rows grid of W x H tiles
  * whose first tile's corner is (x0, y0): one dwtx_encode_view / dwtx_decode_view call per group.  Per axis, with
