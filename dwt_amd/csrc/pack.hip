@@ -468,32 +468,42 @@ struct HdrWriter {
 	long pos;
 	int order;
 	// What the reference's own counters would say if CAPACITY cut into this part of the stream: a refused
-	// byte makes write_bits()/put_vli() give up the field they are writing (bits.h:58-78, vli.h:67-84, the
-	// order then stays as it was) while encode_root() carries on with the next value (encode.c:97-110).
+	// byte makes write_bits()/put_vli() give up the field they are writing (bits.h:58-78, vli.h:67-84)
+	// while encode_root() carries on with the next value (encode.c:97-110).  put_vli() has by then raised
+	// its order once per zero it has put (vli.h:70-75) and lowers it only after a whole token (vli.h:80):
+	// a token given up part-way leaves the order raised, and the next token is coded from there.
 	// Only the statistics lines need this; the bytes are the prefix of the unlimited stream either way.
 	long rc_cap, rc_len;
 	int rc_n, rc_order;
-	__device__ bool rc_bits(int nb)   // false: a byte was refused
+	__device__ int rc_bits(int nb)   // how many of the nb bits went in: fewer than nb when a byte was refused
 	{
 		if (nb <= 0)
-			return true;
+			return 0;
+		const int before = rc_n;
 		rc_n += nb;
 		if (rc_cap <= 0)   // no limit: nothing is ever refused, rc_count() only needs the sum
-			return true;
-		while (rc_n >= 8) {
-			if (rc_cap > 0 && rc_len >= rc_cap) {
+			return nb;
+		for (int bytes = 1; rc_n >= 8; ++bytes) {
+			if (rc_len >= rc_cap) {
 				rc_n = 0;
-				return false;
+				return 8 * bytes - before - 1;   // the bit that filled the refused byte is not among them
 			}
 			++rc_len;
 			rc_n -= 8;
 		}
-		return true;
+		return nb;
 	}
 	__device__ void rc_vli(unsigned v)
 	{
 		const int top = vli_top(rc_order, v);
-		if (!rc_bits(top - rc_order) || !rc_bits(1) || !rc_bits(top))
+		const int zeros = top - rc_order;
+		const int took = rc_bits(zeros);
+		if (took < zeros) {   // refused among the leading zeros: the order stands where they left it
+			rc_order += took;
+			return;
+		}
+		rc_order = top;       // refused at the one or in the remainder: all the zeros are out, nothing lowered yet
+		if (rc_bits(1) < 1 || rc_bits(top) < top)
 			return;
 		rc_order = vli_next(top);
 	}

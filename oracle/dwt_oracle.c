@@ -348,6 +348,7 @@ typedef struct {
 	uint64_t acc;
 	int nacc;
 	int err;
+	int took;       /* bits of the last field that went in before a byte was refused */
 	int order;      /* vli.h:33  */
 	long run;       /* rle.h:33  */
 	long tokens, raw;
@@ -371,12 +372,15 @@ static int sink_bits(sink *s, uint32_t v, int n)
 		return 0;
 	if (n < 32)
 		v &= (1u << n) - 1u;
+	int before = s->nacc;
 	s->acc |= (uint64_t)v << s->nacc;
 	s->nacc += n;
-	while (s->nacc >= 8) {
+	s->took = n;
+	for (int bytes = 1; s->nacc >= 8; ++bytes) {
 		if (sink_byte(s, (int)(s->acc & 255))) {
 			s->acc = 0;
 			s->nacc = 0;
+			s->took = 8 * bytes - before - 1;   /* the bit that filled the refused byte is not among them */
 			return s->err;
 		}
 		s->acc >>= 8;
@@ -386,7 +390,11 @@ static int sink_bits(sink *s, uint32_t v, int n)
 }
 
 /* vli.h:67-84 in closed form: with order o and value v,
- * o* = ilog2(v + 2^o); (o*-o) zeros, a one, then v + 2^o - 2^o* in o* bits. */
+ * o* = ilog2(v + 2^o); (o*-o) zeros, a one, then v + 2^o - 2^o* in o* bits.
+ * vli.h:70-75 raises the order with every zero it has put and vli.h:80 lowers it only after the
+ * whole token: a token refused part-way leaves the order raised — by the zeros that went in when
+ * the refused bit is one of them, to o* when it is the one or a remainder bit — and the next
+ * token (encode.c:97-110 and 181-182 carry on after an error) is coded from there. */
 static int sink_vli(sink *s, long v)
 {
 	int o = s->order;
@@ -396,8 +404,11 @@ static int sink_vli(sink *s, long v)
 		++top;
 	int r;
 	++s->tokens;
-	if ((r = sink_bits(s, 0, top - o)))
+	if ((r = sink_bits(s, 0, top - o))) {
+		s->order = o + s->took;
 		return r;
+	}
+	s->order = top;
 	if ((r = sink_bits(s, 1, 1)))
 		return r;
 	if ((r = sink_bits(s, (uint32_t)(biased - (1L << top)), top)))

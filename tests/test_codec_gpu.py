@@ -316,8 +316,10 @@ def test_statistics_when_capacity_cuts_into_header_or_root(ctx):
     """encode.c:175-180,226-230 print the bit writer's own counters, and a refused byte makes the field being
     written give up (bits.h:58-78): with CAPACITY below the header + root image the three numbers are not the
     sizes of those parts.  Same numbers as the oracle (pinned on the reference in test_oracle.py)."""
-    for (W, H, Cn, seed) in ((53, 37, 3, 4), (64, 40, 1, 9)):
-        pix = orc.synth(W, H, Cn, seed, 0)
+    from refsweep import tiny_capacity_pictures
+
+    for pix in tiny_capacity_pictures():
+        H, W, Cn = pix.shape
         for cap in list(range(1, 20)) + [31, 47, 48, 60, 80, 85, 86, 87, 88, 90, 100, 120, 200]:
             data, st = ctx.encode(pix, cap)
             want, ost = orc.encode(pix, cap)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import orc
+from refsweep import corrupted_blobs, tiny_capacity_pictures   # noqa: F401 (other test modules take corrupted_blobs from here)
 
 G = json.load(open(os.path.join(orc.GOLDEN, "golden.json")))
 
@@ -142,30 +143,6 @@ def test_against_reference_binaries(tmp_path, shape):
                 assert (orc.read_pnm(dec) == back).all() and orc.read_pnm(dec).shape == back.shape
 
 
-def corrupted_blobs(good, n=40, seed=7):
-    """The corruptions tests/test_codec_gpu.py feeds the GPU decoder (bit flips, garbage runs, junk tails)."""
-    rng = np.random.default_rng(seed)
-    blobs = []
-    for case in range(n):
-        b = bytearray(good)
-        kind = case % 4
-        if kind == 0:
-            for _ in range(int(rng.integers(1, 4))):
-                i = int(rng.integers(6, len(b)))
-                b[i] ^= 1 << int(rng.integers(0, 8))
-        elif kind == 1:
-            i = int(rng.integers(6, len(b) - 40))
-            b[i:i + 32] = bytes(rng.integers(0, 256, 32, dtype=np.uint8))
-        elif kind == 2:
-            i = int(rng.integers(40, len(b)))
-            b[i:] = bytes(rng.integers(0, 256, len(b) - i, dtype=np.uint8))
-        else:
-            i = int(rng.integers(40, len(b)))
-            b[i:] = bytes([0 if case % 8 == 3 else 255]) * (len(b) - i)
-        blobs.append(bytes(b))
-    return blobs
-
-
 @pytest.mark.skipif(not orc.have_ref(), reason="oracle/_ref not built (no /root/reference here)")
 def test_corrupted_streams_against_reference_binary(tmp_path):
     """Pins the restatement's error paths (rle.h:58-61,95-101, vli.h, decode.c:204-239) on damaged streams."""
@@ -274,8 +251,7 @@ def test_damaged_streams_that_leave_the_range_of_the_shifts(tmp_path, case):
 def test_statistics_lines_under_tiny_capacities_against_reference_binary(tmp_path):
     """With CAPACITY below header + root image the reference's three stderr numbers are its bit writer's
     counters after fields were given up (bits.h:58-78); the restatement reproduces them."""
-    for (W, H, Cn, seed) in ((53, 37, 3, 4), (64, 40, 1, 9)):
-        pix = orc.synth(W, H, Cn, seed, 0)
+    for pix in tiny_capacity_pictures():
         orc.write_pnm(str(tmp_path / "in.pnm"), pix)
         for cap in list(range(1, 20)) + [31, 47, 48, 60, 80, 85, 86, 87, 88, 90, 100, 120, 200]:
             r = subprocess.run([os.path.join(orc.REF_DIR, "encode"), "in.pnm", "o.dwt", str(cap)], cwd=tmp_path, capture_output=True)

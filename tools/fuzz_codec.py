@@ -8,6 +8,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import orc
 import dwt_amd
+from refsweep import picture   # the nine picture kinds, shared with the reference-made record of tests/refsweep.py
 
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 cases = int(sys.argv[2]) if len(sys.argv) > 2 else 40
@@ -27,31 +28,7 @@ for case in range(cases):
         W, H = (long_side, short_side) if rng.integers(0, 2) else (short_side, long_side)
     Cn = 1 if rng.integers(0, 2) else 3
     n = int(rng.integers(1, 7))
-    def picture():
-        what = int(rng.integers(0, 9))
-        if what <= 2:
-            return orc.synth(W, H, Cn, int(rng.integers(0, 1 << 30)), int(rng.integers(0, 2)))
-        y, x = np.mgrid[0:H, 0:W]
-        if what == 3:     # flat
-            img = np.full((H, W, Cn), int(rng.integers(0, 256)))
-        elif what == 4:   # checkerboard of two levels, period 1..8
-            per = int(rng.integers(1, 9))
-            a, b = int(rng.integers(0, 256)), int(rng.integers(0, 256))
-            img = np.where((((x // per) + (y // per)) & 1)[..., None] == 0, a, b) * np.ones((1, 1, Cn), dtype=np.int64)
-        elif what == 5:   # white noise over the full range
-            img = rng.integers(0, 256, (H, W, Cn))
-        elif what == 6:   # a few impulses on black
-            img = np.zeros((H, W, Cn), dtype=np.int64)
-            k = int(rng.integers(1, 30))
-            img[rng.integers(0, H, k), rng.integers(0, W, k)] = rng.integers(1, 256, (k, Cn))
-        elif what == 7:   # ramps
-            img = ((x * int(rng.integers(1, 5)) + y * int(rng.integers(0, 5))) // int(rng.integers(1, 9)))[..., None] + np.arange(Cn) * 40
-        else:             # bars with hard edges plus one noisy channel
-            img = ((x * 8 // W) * 36)[..., None] + np.zeros((1, 1, Cn), dtype=np.int64)
-            img[..., Cn - 1] += rng.integers(0, 3, (H, W))
-        return np.ascontiguousarray(np.clip(img, 0, 255).astype(np.uint8).reshape(H, W, Cn))
-
-    pix = np.stack([picture() for _ in range(n)])
+    pix = np.stack([picture(rng, W, H, Cn) for _ in range(n)])
     want = [orc.encode(p) for p in pix]
     streams, stats = ctx.encode(pix)
     for i in range(n):
