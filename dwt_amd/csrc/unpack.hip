@@ -134,12 +134,12 @@ struct DWork {
 	int NT;
 	// speculative chunk parse (see k_link_first): per 128-bit chunk of every stream
 	unsigned short *exitX;          // [n*FAM][NCH] rel | order<<8: state in which the chunk's recorded path leaves it; 0xffff dead
-	unsigned short *entryE;         // [n*FAM][NCH] state in which that recorded path entered (valid if == exitX[chunk-1])
-	unsigned long long *cs;         // [n][NCH+1] exclusive prefix of symbols (run+1) along the arriving paths
-	unsigned *ct;                   // [n][NCH+1] exclusive prefix of tokens
-	unsigned *cg;                   // [n][NCH+1] exclusive prefix of "arriving path does not rejoin" flags
-	unsigned long long *part_s;     // [n][NB]
-	unsigned *part_t, *part_g;      // [n][NB]
+	unsigned long long *cs;         // [n*FAM][NCH+1] exclusive prefix of symbols (run+1) along the arriving paths; until k_scan_final, the chunk's link_record
+	unsigned *ct;                   // [n*FAM][NCH+1] exclusive prefix of tokens
+	unsigned *cg;                   // [n*FAM][NCH+1] exclusive prefix of "arriving path does not rejoin" flags
+	unsigned long long *part_s;     // [n*FAM][NB]
+	unsigned *part_t, *part_g;      // [n*FAM][NB]
+	unsigned short *part_x;         // [n*FAM][NB] exit state (13 bits, link_state13) of the chunk before the scan block's first (k_scan_reduce -> k_scan_final)
 	int *hop_seg;                   // [n][w.MAX_HOPS]
 	unsigned *hop_first, *hop_last, *hop_q0;   // [n][w.MAX_HOPS]
 	unsigned *hop_entry;            // [n][MAX_HOPS] 0xffffffff = stitched run (enter at exitX[first-1]); else off | order<<8
@@ -695,7 +695,26 @@ constexpr int LINK_SHARDS = 64;   // work lists are sharded: one counter would s
 constexpr int LINK_RUN = 8;       // chunks a thread of k_link_first parses one after the other (runs start at multiples of it)
 constexpr int RUN_W = 2 * LINK_RUN + 2;   // 64-bit LDS words per thread there
 
+// A chunk's record is one word, on its way through LDS and in the chunk's slot of `cs` until k_scan_final replaces it by the
+// prefix: symbols (31 bits, saturating: a count no segment can ask for — a ring has at most 2^30 coefficients — so such
+// a chunk is simply never hopped over), tokens (7 bits: at most 64 start in 128 bits), entry and exit state (13 bits
+// each: offset 7, order 5; all ones = dead).  All ones = no record.
+__device__ __forceinline__ unsigned link_state13(unsigned short s) { return s == 0xffff ? 0x1fffu : ((unsigned)s & 0x7fu) | ((unsigned)s >> 8) << 7; }
+__device__ __forceinline__ unsigned short link_state16(unsigned s) { return s == 0x1fffu ? (unsigned short)0xffff : (unsigned short)((s & 0x7fu) | (s >> 7) << 8); }
+__device__ __forceinline__ unsigned long long link_record(unsigned sym, unsigned tok, unsigned short in, unsigned short out)
+{
+	const unsigned long long s31 = sym < 0x7fffffffu ? sym : 0x7fffffffu;
+	return s31 | (unsigned long long)tok << 31 | (unsigned long long)link_state13(in) << 38 | (unsigned long long)link_state13(out) << 51;
+}
+__device__ __forceinline__ unsigned link_entry13(unsigned long long rec) { return (unsigned)(rec >> 38) & 0x1fffu; }
+__device__ __forceinline__ unsigned link_exit13(unsigned long long rec) { return (unsigned)(rec >> 51); }
+
 // Returns true if the chunk's exit moved (its successor must be re-parsed).
+// The predecessor's exit and the chunk's own old exit come out of their records, and one record goes back: aligned
+// 8-byte loads and stores are whole, so a reader in the same round sees the old record or the new one, never a mix,
+// and an exit that moved queues the successor either way.  The symbol count saturates at 2^31-1 here as in
+// k_link_first (it used to reach 2^32-1 in this kernel): no segment asks for 2^30 symbols, so a chunk at either
+// ceiling is never hopped over.
 // (Round 4 tried to go on with the successor in the same thread while the exit moves, up to the end of the run of
 // LINK_RUN chunks: fewer rounds for the same reach — but reach is what hurts: paths that come out of the raw refinement
 // blocks then run 8 times as far into the first-pass stretches and replace records that were right; the walker's hops
@@ -704,7 +723,7 @@ __device__ __forceinline__ bool link_parse(const DWork &w, const unsigned char *
 {
 	const int img = vs / FAM;
 	const long ci = vs * (w.NCH + 1) + ch;
-	const unsigned short in = w.exitX[vs * w.NCH + ch - 1];
+	const unsigned short in = link_state16(link_exit13(w.cs[ci - 1]));
 	unsigned sym = 0, tok = 0;
 	unsigned short out = 0xffff;
 	if (in != 0xffff) {
@@ -713,12 +732,9 @@ __device__ __forceinline__ bool link_parse(const DWork &w, const unsigned char *
 		if (chunk_count(c, off, o, tok, sym))
 			out = (unsigned short)((off - CH_BITS) | (o << 8));
 	}
-	const unsigned short old = w.exitX[vs * w.NCH + ch];
-	w.entryE[vs * w.NCH + ch] = in;
-	w.cs[ci] = sym;
-	w.ct[ci] = tok;
-	w.exitX[vs * w.NCH + ch] = out;
-	return out != old && ch + 1 < w.nch[img];
+	const unsigned old = link_exit13(w.cs[ci]);
+	w.cs[ci] = link_record(sym, tok, in, out);
+	return link_state13(out) != old && ch + 1 < w.nch[img];
 }
 
 // queue chunk `ch` for the next round; one atomic per (wave, shard) instead of one per lane.
@@ -755,21 +771,9 @@ __device__ __forceinline__ void link_push(const DWork &w, int vs, long ch, bool 
 // With two families the speculative start is the chunk's middle plus the family's parity: at order 0 every token has
 // even length (2z + o + 2), so two parses that start an odd number of bits apart cannot meet while the order stays 0.
 // A path that dies (no token this codec writes fits there) starts again from the speculative start in the next chunk;
-// the record's entry then differs from its predecessor's exit, which is what flags it (k_scan_local).
+// the record's entry then differs from its predecessor's exit, which is what flags it (scan_quad).
 // The workgroup's stretch of the stream (32 KB) is staged in LDS with coalesced loads, a thread's run 18 words apart
 // (two words of padding: the 64 lanes' 8-byte reads spread over all banks).
-// A chunk's record as one word on its way through LDS: symbols (31 bits, saturating: a count no segment can ask for — a
-// ring has at most 2^30 coefficients — so such a chunk is simply never hopped over), tokens (7 bits: at most 64 start in
-// 128 bits), entry and exit state (13 bits each: offset 7, order 5; all ones = dead).  All ones = no record.
-__device__ __forceinline__ unsigned link_state13(unsigned short s) { return s == 0xffff ? 0x1fffu : ((unsigned)s & 0x7fu) | ((unsigned)s >> 8) << 7; }
-__device__ __forceinline__ unsigned short link_state16(unsigned s) { return s == 0x1fffu ? (unsigned short)0xffff : (unsigned short)((s & 0x7fu) | (s >> 7) << 8); }
-__device__ __forceinline__ unsigned long long link_record(unsigned sym, unsigned tok, unsigned short in, unsigned short out)
-{
-	const unsigned long long s31 = sym < 0x7fffffffu ? sym : 0x7fffffffu;
-	return s31 | (unsigned long long)tok << 31 | (unsigned long long)link_state13(in) << 38 | (unsigned long long)link_state13(out) << 51;
-}
-
-
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(64), amdgpu_waves_per_eu(4))) void k_link_first(DWork w, const unsigned char *streams, long stream_stride)
 {
 	__shared__ unsigned long long words[256 * RUN_W + 4];
@@ -824,14 +828,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(64), amdgpu_wav
 			const int q = k * 256 + (int)threadIdx.x;
 			const long chunk = base + q;
 			const unsigned long long rec = words[(q / LINK_RUN) * RUN_W + 3 + q % LINK_RUN];
-			if (rec != ~0ull) {   // (a chunk past the stream's end has none)
-				if (chunk > 0) {
-					w.entryE[vs * w.NCH + chunk] = link_state16((unsigned)(rec >> 38) & 0x1fffu);
-					w.cs[vs * (w.NCH + 1) + chunk] = rec & 0x7fffffffull;
-					w.ct[vs * (w.NCH + 1) + chunk] = (unsigned)(rec >> 31) & 0x7fu;
-				}
-				w.exitX[vs * w.NCH + chunk] = link_state16((unsigned)(rec >> 51));
-			}
+			if (rec != ~0ull)   // (a chunk past the stream's end has none)
+				w.cs[vs * (w.NCH + 1) + chunk] = rec;
 		}
 		// the run's first chunk was parsed from the warm-up's exit: right only if that is what the run before recorded as its last exit
 		const bool redo = c0 > 0 && c0 < nch && (threadIdx.x == 0 || sx[threadIdx.x - 1] != wexit);
@@ -861,7 +859,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(64))) void k_li
 	}
 }
 
-// three-kernel exclusive scan of (cs, ct, cg) over the NCH+1 elements of every image
+// three-kernel exclusive scan of (symbols, tokens, flags) over the NCH+1 elements of every image -> cs, ct, cg
 struct Tri {
 	unsigned long long s;
 	unsigned t, g;
@@ -907,103 +905,76 @@ __device__ __forceinline__ Tri block_scan_tri(Tri v, Tri *wsum, Tri &total)
 	return ex;
 }
 
-// Four consecutive elements per thread (NCH+1 is a multiple of 4: whole vectors are in or out)
-struct Quad {
-	ulonglong2 s01, s23;
-	uint4 t, g;
+// Four consecutive elements per thread (NCH+1 is a multiple of 4: whole vectors are in or out).
+// A chunk's record is usable iff it was made from the state its predecessor now leaves in: g = 1 marks
+// the others (never hopped over; their counts are zeroed to keep the prefix sums small and monotone).  Chunk
+// 0 has no predecessor; element nch is the scan's sentinel; elements from nch on count as zeros.
+struct ScanQuad {
+	unsigned long long s[4];
+	unsigned t[4], g[4];
+	unsigned x[4];   // exit states (13 bits)
 };
 
-// (k_scan_local makes the flags itself: WITH_G = false leaves cg unread)
-template <bool WITH_G = true> __device__ __forceinline__ Quad quad_load(const DWork &w, long at)
+// the four records at row + i (i < nch + 1); prev = exit state of chunk i - 1 (anything for i = 0)
+__device__ __forceinline__ ScanQuad scan_quad(const unsigned long long *row, long i, long nch, unsigned prev)
 {
-	Quad q;
-	q.s01 = *reinterpret_cast<const ulonglong2 *>(w.cs + at);
-	q.s23 = *reinterpret_cast<const ulonglong2 *>(w.cs + at + 2);
-	q.t = *reinterpret_cast<const uint4 *>(w.ct + at);
-	q.g = WITH_G ? *reinterpret_cast<const uint4 *>(w.cg + at) : make_uint4(0u, 0u, 0u, 0u);
+	const ulonglong2 r01 = *reinterpret_cast<const ulonglong2 *>(row + i), r23 = *reinterpret_cast<const ulonglong2 *>(row + i + 2);
+	const unsigned long long rec[4] = { r01.x, r01.y, r23.x, r23.y };
+	ScanQuad q;
+#pragma unroll
+	for (int e = 0; e < 4; ++e) {
+		const long c = i + e;
+		const unsigned x = link_exit13(rec[e]);
+		const bool live = c > 0 && c < nch;
+		const bool bad = prev == 0x1fffu || link_entry13(rec[e]) != prev || x == 0x1fffu;
+		q.g[e] = c == 0 || (live && bad) ? 1u : 0u;
+		q.s[e] = live && !bad ? rec[e] & 0x7fffffffull : 0ull;
+		q.t[e] = live && !bad ? (unsigned)(rec[e] >> 31) & 0x7fu : 0u;
+		q.x[e] = x;
+		if (c < nch)
+			prev = x;
+	}
 	return q;
 }
 
-__device__ __forceinline__ void quad_store(const DWork &w, long at, const Quad &q)
+__device__ __forceinline__ Tri scan_quad_sum(const ScanQuad &q)
 {
-	*reinterpret_cast<ulonglong2 *>(w.cs + at) = q.s01;
-	*reinterpret_cast<ulonglong2 *>(w.cs + at + 2) = q.s23;
-	*reinterpret_cast<uint4 *>(w.ct + at) = q.t;
-	*reinterpret_cast<uint4 *>(w.cg + at) = q.g;
+	const Tri v = { q.s[0] + q.s[1] + q.s[2] + q.s[3], q.t[0] + q.t[1] + q.t[2] + q.t[3], q.g[0] + q.g[1] + q.g[2] + q.g[3] };
+	return v;
 }
 
-// A chunk's record is usable iff it was made from the state its predecessor now leaves in: cg = 1 marks
-// the others (never hopped over; their counts are zeroed to keep the prefix sums small and monotone).  Chunk
-// 0 has no predecessor; element nch is the scan's sentinel.  The flag is left in entryE for k_scan_add.
+// Reduce-then-scan over the records: k_scan_reduce sums every block of SCAN_BLOCK chunks, k_scan_parts scans the
+// block sums, k_scan_final scans inside the blocks from their bases and writes every table once — the prefixes over
+// the records, in place.  The flags are derived from the records in both passes and stored nowhere.
+// Hazard of the in-place pass: a block's first chunk needs the exit of the block before's last chunk, whose slot
+// another workgroup may have overwritten by then.  Mechanism: a saved edge state.  k_scan_reduce, which overwrites
+// nothing, files that one state per block in part_x, and k_scan_final takes it from there and never reads a slot of
+// `cs` outside its own block; inside the block every thread has loaded its records and its left-hand neighbour's
+// (scan_quad's results feed block_scan_tri) before the scan's barrier, and stores only after it.
 constexpr int SCAN_GRID = 1024;
 
-__global__ __launch_bounds__(256) void k_scan_local(DWork w)
+__global__ __launch_bounds__(256) void k_scan_reduce(DWork w)
 {
 	__shared__ Tri wsum[4];
 	const int vs = vstream(w, blockIdx.y);   // virtual stream
-	const long n = w.NCH + 1, nch = w.nch[vs / FAM], used = nch + 1;
-	unsigned short *exitX = w.exitX + (long)vs * w.NCH, *entryE = w.entryE + (long)vs * w.NCH;
+	const long nch = w.nch[vs / FAM], used = nch + 1;
+	const unsigned long long *row = w.cs + (long)vs * (w.NCH + 1);
 	for (long vb = blockIdx.x; vb * SCAN_BLOCK < used; vb += gridDim.x) {
 		const long i = vb * SCAN_BLOCK + 4 * threadIdx.x;
-		const bool in = i < used;
-		Quad q;
-		q.s01 = q.s23 = make_ulonglong2(0ull, 0ull);
-		q.t = q.g = make_uint4(0u, 0u, 0u, 0u);
-		if (in) {
-			q = quad_load<false>(w, vs * n + i);
-			unsigned long long *sv[4] = { &q.s01.x, &q.s01.y, &q.s23.x, &q.s23.y };
-			unsigned *tv[4] = { &q.t.x, &q.t.y, &q.t.z, &q.t.w }, *gv[4] = { &q.g.x, &q.g.y, &q.g.z, &q.g.w };
-			unsigned short prev = i >= 1 && i - 1 < nch ? exitX[i - 1] : (unsigned short)0xffff;
-#pragma unroll
-			for (int e = 0; e < 4; ++e) {
-				const long c = i + e;
-				unsigned flag;
-				if (c == 0 || c >= nch) {
-					flag = c == 0 ? 1u : 0u;
-					*sv[e] = 0;
-					*tv[e] = 0;
-				} else {
-					const unsigned short x = exitX[c];
-					const bool bad = prev == 0xffff || entryE[c] != prev || x == 0xffff;
-					flag = bad ? 1u : 0u;
-					if (bad) {
-						*sv[e] = 0;
-						*tv[e] = 0;
-					}
-					prev = x;
-				}
-				if (c == 0)
-					prev = nch > 0 ? exitX[0] : (unsigned short)0xffff;
-				*gv[e] = flag;
-				if (c < nch)
-					entryE[c] = (unsigned short)flag;
-			}
+		Tri mine = { 0, 0, 0 };
+		if (i < used) {
+			const unsigned prev = i >= 1 && i - 1 < nch ? link_exit13(row[i - 1]) : 0x1fffu;
+			mine = scan_quad_sum(scan_quad(row, i, nch, prev));
+			if (threadIdx.x == 0)
+				w.part_x[vs * w.NB + vb] = (unsigned short)prev;
 		}
-		const Tri mine = { q.s01.x + q.s01.y + q.s23.x + q.s23.y, q.t.x + q.t.y + q.t.z + q.t.w, q.g.x + q.g.y + q.g.z + q.g.w };
 		Tri total;
-		const Tri pre = block_scan_tri(mine, wsum, total);
-		if (in) {
-			Quad o;
-			o.s01.x = pre.s;
-			o.s01.y = o.s01.x + q.s01.x;
-			o.s23.x = o.s01.y + q.s01.y;
-			o.s23.y = o.s23.x + q.s23.x;
-			o.t.x = pre.t;
-			o.t.y = o.t.x + q.t.x;
-			o.t.z = o.t.y + q.t.y;
-			o.t.w = o.t.z + q.t.z;
-			o.g.x = pre.g;
-			o.g.y = o.g.x + q.g.x;
-			o.g.z = o.g.y + q.g.y;
-			o.g.w = o.g.z + q.g.z;
-			quad_store(w, vs * n + i, o);
-		}
+		block_scan_tri(mine, wsum, total);   // (its barriers also free wsum for the next virtual block)
 		if (threadIdx.x == 0) {
 			w.part_s[vs * w.NB + vb] = total.s;
 			w.part_t[vs * w.NB + vb] = total.t;
 			w.part_g[vs * w.NB + vb] = total.g;
 		}
-		__syncthreads();   // wsum is reused by the next virtual block
 	}
 }
 
@@ -1011,7 +982,7 @@ __global__ __launch_bounds__(256) void k_scan_parts(DWork w)
 {
 	__shared__ Tri wsum[4];
 	const int img = vstream(w, blockIdx.x);   // virtual stream
-	const long nb = (w.nch[img / FAM] + 1 + SCAN_BLOCK - 1) / SCAN_BLOCK;   // blocks k_scan_local ran
+	const long nb = (w.nch[img / FAM] + 1 + SCAN_BLOCK - 1) / SCAN_BLOCK;   // blocks k_scan_reduce ran
 	Tri carry = { 0, 0, 0 };
 	for (long b0 = 0; b0 < nb; b0 += 256) {
 		const long i = b0 + threadIdx.x;
@@ -1032,38 +1003,65 @@ __global__ __launch_bounds__(256) void k_scan_parts(DWork w)
 	}
 }
 
-// adds the block offsets and files the unjoined chunks: the one with rank r (= cg[i], exclusive prefix) goes to breaks[r]
-__global__ __launch_bounds__(256) void k_scan_add(DWork w)
+// the final tables of a block, and the unjoined chunks filed: the one with rank r (= cg[i], exclusive prefix) goes to breaks[r]
+__global__ __launch_bounds__(256) void k_scan_final(DWork w)
 {
+	__shared__ Tri wsum[4];
 	const int vs = vstream(w, blockIdx.y);   // virtual stream
 	const long n = w.NCH + 1, nch = w.nch[vs / FAM], used = nch + 1;
-	const unsigned short *flags = w.entryE + (long)vs * w.NCH;
+	unsigned long long *row = w.cs + (long)vs * n;
+	unsigned short *exitX = w.exitX + (long)vs * w.NCH;
 	unsigned *breaks = w.breaks + (long)vs * w.NCH;
 	for (long vb = blockIdx.x; vb * SCAN_BLOCK < used; vb += gridDim.x) {
 		const long i = vb * SCAN_BLOCK + 4 * threadIdx.x;
-		if (i >= used)
+		const bool in = i < used;
+		ScanQuad q = {};
+		if (in) {
+			const unsigned prev = threadIdx.x == 0 ? w.part_x[vs * w.NB + vb] : i - 1 < nch ? link_exit13(row[i - 1]) : 0x1fffu;
+			q = scan_quad(row, i, nch, prev);
+		}
+		Tri total;
+		const Tri pre = block_scan_tri(scan_quad_sum(q), wsum, total);   // (its barriers also free wsum for the next virtual block)
+		if (!in)
 			continue;
-		const unsigned long long ps = w.part_s[vs * w.NB + vb];
-		const unsigned pt = w.part_t[vs * w.NB + vb], pg = w.part_g[vs * w.NB + vb];
-		Quad q = quad_load(w, vs * n + i);
-		q.s01.x += ps;
-		q.s01.y += ps;
-		q.s23.x += ps;
-		q.s23.y += ps;
-		q.t.x += pt;
-		q.t.y += pt;
-		q.t.z += pt;
-		q.t.w += pt;
-		q.g.x += pg;
-		q.g.y += pg;
-		q.g.z += pg;
-		q.g.w += pg;
-		if (vb)   // the first block's prefixes are final already
-			quad_store(w, vs * n + i, q);
-		const unsigned g4[4] = { q.g.x, q.g.y, q.g.z, q.g.w };
+		ulonglong2 s01, s23;
+		uint4 t, g;
+		s01.x = w.part_s[vs * w.NB + vb] + pre.s;
+		s01.y = s01.x + q.s[0];
+		s23.x = s01.y + q.s[1];
+		s23.y = s23.x + q.s[2];
+		t.x = w.part_t[vs * w.NB + vb] + pre.t;
+		t.y = t.x + q.t[0];
+		t.z = t.y + q.t[1];
+		t.w = t.z + q.t[2];
+		g.x = w.part_g[vs * w.NB + vb] + pre.g;
+		g.y = g.x + q.g[0];
+		g.z = g.y + q.g[1];
+		g.w = g.z + q.g[2];
+		*reinterpret_cast<ulonglong2 *>(row + i) = s01;
+		*reinterpret_cast<ulonglong2 *>(row + i + 2) = s23;
+		*reinterpret_cast<uint4 *>(w.ct + vs * n + i) = t;
+		*reinterpret_cast<uint4 *>(w.cg + vs * n + i) = g;
+		// exitX has NCH elements per row, an odd number: a thread's four are side by side in one or two words where the
+		// row's parity allows (always with one family), and the quad with the sentinel goes one by one
+		const unsigned short x[4] = { link_state16(q.x[0]), link_state16(q.x[1]), link_state16(q.x[2]), link_state16(q.x[3]) };
+		const unsigned x01 = x[0] | (unsigned)x[1] << 16, x23 = x[2] | (unsigned)x[3] << 16;
+		const unsigned misalign = (unsigned)(size_t)(exitX + i) & 7u;
+		if (i + 4 <= nch && misalign == 0) {
+			*reinterpret_cast<uint2 *>(exitX + i) = make_uint2(x01, x23);
+		} else if (i + 4 <= nch && misalign == 4) {
+			*reinterpret_cast<unsigned *>(exitX + i) = x01;
+			*reinterpret_cast<unsigned *>(exitX + i + 2) = x23;
+		} else {
+#pragma unroll
+			for (int e = 0; e < 4; ++e)
+				if (i + e < nch)
+					exitX[i + e] = x[e];
+		}
+		const unsigned g4[4] = { g.x, g.y, g.z, g.w };
 #pragma unroll
 		for (int e = 0; e < 4; ++e)
-			if (i + e < nch && flags[i + e])
+			if (i + e < nch && q.g[e])
 				breaks[g4[e]] = (unsigned)(i + e);
 	}
 }
@@ -2427,13 +2425,13 @@ template <class F> static void dwork_tables(DWork &w, unsigned *&clear_words, in
 	t(SLOT_UP_TILES, w.tile_rank, (long)C * MAX_PLANES * w.NT);
 	t(SLOT_UP_TILES, w.count_base, (long)C * 16);
 	t(SLOT_UP_CHUNKS, w.exitX, FAM * w.NCH);
-	t(SLOT_UP_CHUNKS, w.entryE, FAM * w.NCH);
 	t(SLOT_UP_CHUNKS, w.cs, FAM * (w.NCH + 1));
 	t(SLOT_UP_CHUNKS, w.ct, FAM * (w.NCH + 1));
 	t(SLOT_UP_CHUNKS, w.cg, FAM * (w.NCH + 1));
 	t(SLOT_UP_CHUNKS, w.part_s, FAM * w.NB);
 	t(SLOT_UP_CHUNKS, w.part_t, FAM * w.NB);
 	t(SLOT_UP_CHUNKS, w.part_g, FAM * w.NB);
+	t(SLOT_UP_CHUNKS, w.part_x, FAM * w.NB);
 	t(SLOT_UP_CHUNKS, w.hop_seg, w.MAX_HOPS);
 	t(SLOT_UP_CHUNKS, w.hop_first, w.MAX_HOPS);
 	t(SLOT_UP_CHUNKS, w.hop_last, w.MAX_HOPS);
@@ -2584,9 +2582,9 @@ struct DecodeCall {
 			cur ^= 1;
 		}
 		const unsigned sblocks = (unsigned)(w.NB < SCAN_GRID ? w.NB : SCAN_GRID);
-		hipLaunchKernelGGL(k_scan_local, dim3(sblocks, count * h.fam), dim3(256), 0, st, h);
+		hipLaunchKernelGGL(k_scan_reduce, dim3(sblocks, count * h.fam), dim3(256), 0, st, h);
 		hipLaunchKernelGGL(k_scan_parts, dim3(count * h.fam), dim3(256), 0, st, h);
-		hipLaunchKernelGGL(k_scan_add, dim3(sblocks, count * h.fam), dim3(256), 0, st, h);
+		hipLaunchKernelGGL(k_scan_final, dim3(sblocks, count * h.fam), dim3(256), 0, st, h);
 		DWTX_LAUNCH_CHECK();
 		return DWTX_OK;
 	}
