@@ -369,35 +369,11 @@ __device__ __forceinline__ void hist_flush(HistAcc &h, const HistArgs &H, int pl
 	h.mx = 0;
 }
 
+// One row of the wave's strip, widened: what the int32 arithmetic lifts
 struct FwdRaw {
 	int4 x;
 	int xr;           // x[4q+4] for lane 63
 	int2 left;        // x[4q-2], x[4q-1] for lane 0
-};
-
-// Where the finest forward level may read its samples instead of int32 planes: 8-bit gray pixels (pnm.h:69-74 fused)
-// or 8-bit interleaved RGB pixels, of which each plane's launch takes its own YCoCg-R channel (image.h:52-65 fused).
-struct Rgb8 {};
-// or 8-bit planar RGB pixels (dwtx_pixels::channel_stride): three gray-style rows per row, one per plane, no unpacking
-struct RgbP8 {};
-// or 8-bit RGB in 4-byte pixels (dwtx_pixels::rgbx8(): RGBA / RGBX surfaces, pixel step 4): interleaved like Rgb8, a lane's
-// four pixels one 16-byte piece whose every fourth byte is loaded and never used
-struct Rgbx8 {};
-template <typename SrcT>
-struct SrcTag {};
-
-// (8-bit rows wait for their turn as they were loaded — four pixels in a word, the neighbours' in another — and are
-// widened when used)
-struct FwdRaw8 {
-	unsigned v;       // pixels 4q .. 4q+3
-	unsigned edge;    // the word after them (lane 63: its first byte is x[4q+4]) or before them (lane 0: its last two are x[4q-2], x[4q-1])
-};
-
-// (RGB rows too: the four pixels' three words and two words of neighbours; the colour transform of image.h:52-65
-// happens when the row is used)
-struct FwdRawRgb {
-	unsigned a, b, c;   // pixels 4q .. 4q+3
-	unsigned e0, e1;    // lane 63: e0 = the word with pixel 4q+4; lane 0: bytes 12q-8 .. 12q-1 (pixels 4q-2 and 4q-1 are the last six)
 };
 
 __device__ __forceinline__ void fwd_lift_w(const FwdRaw &r, int q, int lane, int nquads, I2 &lo, I2 &hi)
@@ -420,13 +396,15 @@ __device__ __forceinline__ void fwd_lift_w(const FwdRaw &r, int q, int lane, int
 	hi.b = d1;
 }
 
-__device__ __forceinline__ I2 i2_pred(I2 odd, I2 e0, I2 e2)
+// The lane's two column pairs of a row as the vertical step sees them, in the int32 arithmetic (the packed 16-bit one,
+// P2, is further down): the loop of fwd_level_body meets either through these overloads.
+__device__ __forceinline__ I2 lift_pred(I2 odd, I2 e0, I2 e2)   // cdf53.h:13 down the columns
 {
 	I2 r = { odd.a - tdiv2(e0.a + e2.a), odd.b - tdiv2(e0.b + e2.b) };
 	return r;
 }
 
-__device__ __forceinline__ I2 i2_upd(I2 even, I2 dprev, I2 d)
+__device__ __forceinline__ I2 lift_upd(I2 even, I2 dprev, I2 d)   // cdf53.h:20
 {
 	I2 r = { even.a + tdiv4(dprev.a + d.a), even.b + tdiv4(dprev.b + d.b) };
 	return r;
@@ -437,27 +415,19 @@ __device__ __forceinline__ void st2(int *p, I2 v)
 	*reinterpret_cast<int2 *>(p) = make_int2(v.a, v.b);
 }
 
+__device__ __forceinline__ void st2(short *p, I2 v)
+{
+	*reinterpret_cast<unsigned *>(p) = ((unsigned)v.a & 0xffffu) | ((unsigned)v.b << 16);
+}
 
-// first sample of the plane's source and the channel a launch extracts (RGB only)
-__device__ __forceinline__ const uint8_t *fwd_base(SrcTag<uint8_t>, const LevelArgs &a, int plane, int &ch)
+__device__ __forceinline__ void hist_add(HistAcc &h, I2 v)
 {
-	ch = 0;
-	return a.src8 + win_off(a.grid, a.src_ps, plane);
+	hist_add(h, v.a);
+	hist_add(h, v.b);
 }
-__device__ __forceinline__ const uint8_t *fwd_base(SrcTag<Rgb8>, const LevelArgs &a, int plane, int &ch)
-{
-	ch = plane % 3;
-	return a.src8 + win_off(a.grid, a.src_ps, plane / 3);   // src_ps = bytes from an interleaved image to the next, spitch = bytes per row
-}
-__device__ __forceinline__ const uint8_t *fwd_base(SrcTag<Rgbx8>, const LevelArgs &a, int plane, int &ch)
-{
-	return fwd_base(SrcTag<Rgb8>(), a, plane, ch);   // (spitch = bytes per row of 4-byte pixels)
-}
-__device__ __forceinline__ const uint8_t *fwd_base(SrcTag<RgbP8>, const LevelArgs &a, int plane, int &ch)
-{
-	ch = plane % 3;
-	return a.src8 + win_off(a.grid, a.src_ps, plane / 3);   // channel 0's plane of the window; spitch = bytes per row of a plane
-}
+
+// the OR of the magnitudes as hist_add(.., I2) left it in HistAcc::mx: what hist_flush takes
+__device__ __forceinline__ unsigned hist_mx(unsigned mx, I2) { return mx; }
 
 // Workgroups are dealt round-robin over the 8 XCDs (each with an L2 of its own): with the plain mapping the
 // strips left and right of a strip — whose edge sectors it also loads as halo — sit on other XCDs and those
@@ -496,25 +466,9 @@ __device__ __forceinline__ void xcd_strip_rgb(int &bx, int &by, int &c)
 	bx = s - by * gx;
 }
 
-template <typename SrcT>
-struct IsRgb {
-	static constexpr bool value = false;
-};
-template <>
-struct IsRgb<Rgb8> {
-	static constexpr bool value = true;
-};
-template <>
-struct IsRgb<RgbP8> {
-	static constexpr bool value = true;
-};
-template <>
-struct IsRgb<Rgbx8> {
-	static constexpr bool value = true;
-};
-
 // A row moves from the registers it was loaded into to the registers it is used from: a move the register allocator
-// cannot fold away, placed where the wave is to wait for the row (see the loop of k_fwd_level_w).
+// cannot fold away, placed where the wave is to wait for the row (see the loop of fwd_level_body).  Every kind of row
+// as it is loaded has its hold() below.
 __device__ __forceinline__ unsigned hold(unsigned v)
 {
 	unsigned o;
@@ -522,26 +476,32 @@ __device__ __forceinline__ unsigned hold(unsigned v)
 	return o;
 }
 __device__ __forceinline__ int hold(int v) { return (int)hold((unsigned)v); }
+__device__ __forceinline__ uint2 hold(uint2 v) { return make_uint2(hold(v.x), hold(v.y)); }
 
-// One int32 row of the wave's strip as it is loaded: every lane loads — lanes beyond the row from the row's last quad,
-// the edge pair from a clamped place — so that no load sits behind a branch or feeds a select (either would make the
-// wave wait for it at once); what the extra lanes get is never used.
+// Rows for the batched loop of fwd_level_body: every lane loads — lanes beyond the row from the row's last quad, the
+// edge piece from a clamped place — so that no load sits behind a branch or feeds a select (either would make the wave
+// wait for it at once); what the extra lanes get is never used.  Where a lane loads in a row, the same for every row, in
+// samples of the source: its quad, and the edge piece — before the quad for lane 0 (x[4q-2], x[4q-1] are its end),
+// after it for the others (x[4q+4] is its start).
+struct LaneAt {
+	int main, edge;
+};
+
+// per_quad: source samples in a lane's four pixels; reach: samples in an edge piece
+__device__ __forceinline__ LaneAt lane_at(int q, int lane, int nquads, int per_quad, int reach)
+{
+	const int m = per_quad * min(q, nquads - 1);
+	LaneAt o = { m, lane == 0 ? max(m - reach, 0) : min(m + per_quad, per_quad * nquads - reach) };
+	return o;
+}
+
+// an int32 row as it is loaded
 struct FwdRawI {
 	int4 x;           // x[4q .. 4q+3]
 	int2 e;           // lane 0: x[4q-2], x[4q-1]; the other lanes: e.x = x[4q+4]
 };
-struct LaneAtI {
-	int main, edge;   // offsets in a row, in samples
-};
 
-__device__ __forceinline__ LaneAtI lane_at_i(int q, int lane, int nquads)
-{
-	const int qa = min(q, nquads - 1);
-	LaneAtI o = { 4 * qa, lane == 0 ? max(4 * qa - 2, 0) : min(4 * qa + 4, 4 * nquads - 2) };
-	return o;
-}
-
-__device__ __forceinline__ FwdRawI fwd_load_i(const int *__restrict__ row, const LaneAtI &at)
+__device__ __forceinline__ FwdRawI fwd_load_i(const int *__restrict__ row, const LaneAt &at)
 {
 	FwdRawI r;
 	r.x = *reinterpret_cast<const int4 *>(row + at.main);
@@ -549,18 +509,12 @@ __device__ __forceinline__ FwdRawI fwd_load_i(const int *__restrict__ row, const
 	return r;
 }
 
-// the same row when the band is kept as 16-bit values (the levels of an 8-bit source whose range allows it)
-struct FwdRawS {
-	uint2 x;          // x[4q .. 4q+3]
-	unsigned e;       // lane 0: x[4q-2], x[4q-1]; the other lanes: its low half = x[4q+4]
-};
-
-__device__ __forceinline__ FwdRawS fwd_load_i(const short *__restrict__ row, const LaneAtI &at)
+__device__ __forceinline__ FwdRawI hold(const FwdRawI &r)
 {
-	FwdRawS r;
-	r.x = *reinterpret_cast<const uint2 *>(row + at.main);
-	r.e = *reinterpret_cast<const unsigned *>(row + at.edge);
-	return r;
+	FwdRawI o;
+	o.x = make_int4(hold(r.x.x), hold(r.x.y), hold(r.x.z), hold(r.x.w));
+	o.e = make_int2(hold(r.e.x), hold(r.e.y));
+	return o;
 }
 
 __device__ __forceinline__ FwdRaw widen(const FwdRawI &r)
@@ -572,7 +526,30 @@ __device__ __forceinline__ FwdRaw widen(const FwdRawI &r)
 	return o;
 }
 
-__device__ __forceinline__ FwdRaw widen(const FwdRawS &r)
+// A row of 16-bit samples as it is loaded — a lane's quad is 8 bytes: a band kept as 16-bit values (the levels of an
+// 8-bit source whose range allows it), widened with its sign, or deep gray pixels (uint16_t samples, include/dwtx.h),
+// widened without one (pnm.h:69-74).
+struct FwdRawS {
+	uint2 x;          // x[4q .. 4q+3]
+	unsigned e;       // lane 0: x[4q-2], x[4q-1]; the other lanes: its low half = x[4q+4]
+};
+
+__device__ __forceinline__ FwdRawS fwd_load_s(const void *row, const LaneAt &at)
+{
+	const uint16_t *p = static_cast<const uint16_t *>(row);
+	FwdRawS r;
+	r.x = *reinterpret_cast<const uint2 *>(p + at.main);
+	r.e = *reinterpret_cast<const unsigned *>(p + at.edge);
+	return r;
+}
+
+__device__ __forceinline__ FwdRawS hold(const FwdRawS &r)
+{
+	FwdRawS o = { hold(r.x), hold(r.e) };
+	return o;
+}
+
+__device__ __forceinline__ FwdRaw widen_s(const FwdRawS &r)
 {
 	FwdRaw o;
 	o.x = make_int4((int)(short)(r.x.x & 0xffffu), (int)r.x.x >> 16, (int)(short)(r.x.y & 0xffffu), (int)r.x.y >> 16);
@@ -581,35 +558,7 @@ __device__ __forceinline__ FwdRaw widen(const FwdRawS &r)
 	return o;
 }
 
-__device__ __forceinline__ FwdRaw hold(const FwdRawS &r)
-{
-	FwdRawS h;
-	h.x = make_uint2(hold(r.x.x), hold(r.x.y));
-	h.e = hold(r.e);
-	return widen(h);
-}
-
-__device__ __forceinline__ void st2(short *p, I2 v)
-{
-	*reinterpret_cast<unsigned *>(p) = ((unsigned)v.a & 0xffffu) | ((unsigned)v.b << 16);
-}
-
-__device__ __forceinline__ FwdRaw hold(const FwdRawI &r)
-{
-	FwdRaw o;
-	o.x = make_int4(hold(r.x.x), hold(r.x.y), hold(r.x.z), hold(r.x.w));
-	o.xr = hold(r.e.x);
-	o.left = make_int2(o.xr, hold(r.e.y));
-	return o;
-}
-
-// Deep pixels (uint16_t samples, include/dwtx.h) as the finest level's source.  Gray: the row is loaded like a 16-bit
-// band — a lane's quad is 8 bytes — and widened without a sign (pnm.h:69-74).
-struct FwdRawU {
-	uint2 x;          // x[4q .. 4q+3]
-	unsigned e;       // lane 0: x[4q-2], x[4q-1]; the other lanes: its low half = x[4q+4]
-};
-__device__ __forceinline__ FwdRaw widen(const FwdRawU &r)
+__device__ __forceinline__ FwdRaw widen_u(const FwdRawS &r)
 {
 	FwdRaw o;
 	o.x = make_int4((int)(r.x.x & 0xffffu), (int)(r.x.x >> 16), (int)(r.x.y & 0xffffu), (int)(r.x.y >> 16));
@@ -617,13 +566,7 @@ __device__ __forceinline__ FwdRaw widen(const FwdRawU &r)
 	o.left = make_int2(o.xr, (int)(r.e >> 16));
 	return o;
 }
-// Interleaved RGB16: a lane's four pixels are 24 bytes (three 8-byte loads; rows of W % 4 == 0 pixels are multiples of
-// 24 bytes, so they stay 8-byte aligned), the neighbours' pixels three words: lane 0 pixels 4q-2 and 4q-1, the other lanes
-// pixel 4q+4 in the first three samples.  Every plane's launch takes its own channel of image.h:52-65 when the row is used.
-struct FwdRawRgb16 {
-	uint2 a, b, c;
-	unsigned e0, e1, e2;
-};
+
 __device__ __forceinline__ int ycocg_ch(int r, int g, int b, int ch)   // image.h:52-65, channel ch (uniform)
 {
 	const int co = r - b;
@@ -633,6 +576,21 @@ __device__ __forceinline__ int ycocg_ch(int r, int g, int b, int ch)   // image.
 	const int cg = g - t;
 	return ch == 2 ? cg : t + tdiv2(cg);
 }
+
+// Interleaved RGB16: a lane's four pixels are 24 bytes (three 8-byte loads; rows of W % 4 == 0 pixels are multiples of
+// 24 bytes, so they stay 8-byte aligned), the neighbours' pixels three words: lane 0 pixels 4q-2 and 4q-1, the other lanes
+// pixel 4q+4 in the first three samples.  Every plane's launch takes its own channel of image.h:52-65 when the row is used.
+struct FwdRawRgb16 {
+	uint2 a, b, c;
+	unsigned e0, e1, e2;
+};
+
+__device__ __forceinline__ FwdRawRgb16 hold(const FwdRawRgb16 &r)
+{
+	FwdRawRgb16 o = { hold(r.a), hold(r.b), hold(r.c), hold(r.e0), hold(r.e1), hold(r.e2) };
+	return o;
+}
+
 __device__ __forceinline__ FwdRaw widen(const FwdRawRgb16 &r, int ch)
 {
 	auto lo = [](unsigned w) { return (int)(w & 0xffffu); };
@@ -647,102 +605,21 @@ __device__ __forceinline__ FwdRaw widen(const FwdRawRgb16 &r, int ch)
 	return o;
 }
 
-// the band a forward level reads, as the kernel variant sees it: int32 planes, 16-bit planes (dwtx_p16: the detail bands
-// go out as 16-bit values too), or — the finest level of a deep picture — uint16_t pixels, gray, interleaved RGB or planar RGB
-// (load()'s last argument: the planar pixels' channel stride, LevelArgsW::cstride; the others have no use for it)
-enum { SRC_I32 = 0, SRC_I16 = 1, SRC_U16 = 2, SRC_RGB16 = 3, SRC_RGBP16 = 4 };
-template <int SRC>
-struct SrcBand {
-	typedef const int *ptr;
-	typedef FwdRawI raw;
-	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &) { return a.src + plane * a.src_ps; }
-	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads) { return lane_at_i(q, lane, nquads); }
-	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at, long) { return fwd_load_i(row, at); }
-	static __device__ __forceinline__ FwdRaw wide(const raw &r, int) { return widen(r); }
-	static __device__ __forceinline__ FwdRaw held(const raw &r, int) { return hold(r); }
-};
-template <>
-struct SrcBand<SRC_I16> {
-	typedef const short *ptr;
-	typedef FwdRawS raw;
-	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &) { return a.src16 + plane * a.src_ps; }
-	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads) { return lane_at_i(q, lane, nquads); }
-	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at, long) { return fwd_load_i(row, at); }
-	static __device__ __forceinline__ FwdRaw wide(const raw &r, int) { return widen(r); }
-	static __device__ __forceinline__ FwdRaw held(const raw &r, int) { return hold(r); }
-};
-template <>
-struct SrcBand<SRC_U16> {
-	typedef const uint16_t *ptr;
-	typedef FwdRawU raw;
-	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &) { return reinterpret_cast<const uint16_t *>(a.src8) + win_off(a.grid, a.src_ps, (int)plane); }
-	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads) { return lane_at_i(q, lane, nquads); }
-	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at, long = 0)
-	{
-		raw r;
-		r.x = *reinterpret_cast<const uint2 *>(row + at.main);
-		r.e = *reinterpret_cast<const unsigned *>(row + at.edge);
-		return r;
-	}
-	static __device__ __forceinline__ FwdRaw wide(const raw &r, int) { return widen(r); }
-	static __device__ __forceinline__ FwdRaw held(const raw &r, int)
-	{
-		raw h;
-		h.x = make_uint2(hold(r.x.x), hold(r.x.y));
-		h.e = hold(r.e);
-		return widen(h);
-	}
-};
-template <>
-struct SrcBand<SRC_RGB16> {
-	typedef const uint16_t *ptr;
-	typedef FwdRawRgb16 raw;
-	// plane p = channel p % 3 of image p / 3; src_ps = samples per interleaved image, spitch = samples per row
-	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &ch)
-	{
-		ch = (int)(plane % 3);
-		return reinterpret_cast<const uint16_t *>(a.src8) + win_off(a.grid, a.src_ps, (int)(plane / 3));
-	}
-	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads)
-	{
-		const int qa = min(q, nquads - 1);
-		LaneAtI o = { 12 * qa, lane == 0 ? max(12 * qa - 6, 0) : min(12 * qa + 12, 12 * nquads - 6) };
-		return o;
-	}
-	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at, long)
-	{
-		raw r;
-		const uint2 *m = reinterpret_cast<const uint2 *>(row + at.main);
-		const unsigned *e = reinterpret_cast<const unsigned *>(row + at.edge);
-		r.a = m[0];
-		r.b = m[1];
-		r.c = m[2];
-		r.e0 = e[0];
-		r.e1 = e[1];
-		r.e2 = e[2];
-		return r;
-	}
-	static __device__ __forceinline__ FwdRaw wide(const raw &r, int ch) { return widen(r, ch); }
-	static __device__ __forceinline__ FwdRaw held(const raw &r, int ch)
-	{
-		raw h;
-		h.a = make_uint2(hold(r.a.x), hold(r.a.y));
-		h.b = make_uint2(hold(r.b.x), hold(r.b.y));
-		h.c = make_uint2(hold(r.c.x), hold(r.c.y));
-		h.e0 = hold(r.e0);
-		h.e1 = hold(r.e1);
-		h.e2 = hold(r.e2);
-		return widen(h, ch);
-	}
-};
 // Planar RGB16: the same row of the window's three planes, each loaded as a gray deep row is (8 bytes for the lane's quad, a
 // word of neighbours, inside the row's own W samples of that plane); the plane's launch takes its channel of image.h:52-65
-struct FwdRawRgbU3 {
-	FwdRawU r, g, b;
+struct FwdRawRgbS3 {
+	FwdRawS r, g, b;
 };
-__device__ __forceinline__ FwdRaw widen(const FwdRawRgbU3 &p, int ch)
+
+__device__ __forceinline__ FwdRawRgbS3 hold(const FwdRawRgbS3 &p)
 {
-	const FwdRaw r = widen(p.r), g = widen(p.g), b = widen(p.b);
+	FwdRawRgbS3 o = { hold(p.r), hold(p.g), hold(p.b) };
+	return o;
+}
+
+__device__ __forceinline__ FwdRaw widen(const FwdRawRgbS3 &p, int ch)
+{
+	const FwdRaw r = widen_u(p.r), g = widen_u(p.g), b = widen_u(p.b);
 	FwdRaw o;
 	o.x.x = ycocg_ch(r.x.x, g.x.x, b.x.x, ch);
 	o.x.y = ycocg_ch(r.x.y, g.x.y, b.x.y, ch);
@@ -751,177 +628,6 @@ __device__ __forceinline__ FwdRaw widen(const FwdRawRgbU3 &p, int ch)
 	o.xr = ycocg_ch(r.xr, g.xr, b.xr, ch);
 	o.left = make_int2(o.xr, ycocg_ch(r.left.y, g.left.y, b.left.y, ch));
 	return o;
-}
-template <>
-struct SrcBand<SRC_RGBP16> {
-	typedef const uint16_t *ptr;
-	typedef FwdRawRgbU3 raw;
-	typedef SrcBand<SRC_U16> Gray;
-	// plane p = channel p % 3 of image p / 3; the pointer is channel 0's plane of the window, spitch = samples per row of a plane
-	static __device__ __forceinline__ ptr of(const LevelArgs &a, long plane, int &ch) { return SrcBand<SRC_RGB16>::of(a, plane, ch); }
-	static __device__ __forceinline__ LaneAtI at(int q, int lane, int nquads) { return lane_at_i(q, lane, nquads); }
-	static __device__ __forceinline__ raw load(ptr row, const LaneAtI &at, long cs)
-	{
-		raw r = { Gray::load(row, at), Gray::load(row + cs, at), Gray::load(row + 2 * cs, at) };
-		return r;
-	}
-	static __device__ __forceinline__ FwdRaw wide(const raw &r, int ch) { return widen(r, ch); }
-	static __device__ __forceinline__ FwdRaw held(const raw &r, int ch)
-	{
-		auto h = [](const FwdRawU &u) {
-			FwdRawU o;
-			o.x = make_uint2(hold(u.x.x), hold(u.x.y));
-			o.e = hold(u.e);
-			return o;
-		};
-		const raw k = { h(r.r), h(r.g), h(r.b) };
-		return widen(k, ch);
-	}
-};
-
-// Forward level on int32 planes (every level of dwtx_transformation_fwd; the levels below the finest in the codec).
-// Memory operations retire in order on this part (one counter for loads and stores): a wave that waits for rows it
-// loaded also waits for everything it issued before them, and a wait the compiler cannot count exactly waits for
-// everything.  So the loop works in batches of S row pairs: wait once (where the rows are moved to the registers they
-// are used from), send the previous batch's results out, ask for the next batch's rows, then compute S row pairs
-// without touching memory — by the next wait both the stores and the loads are a whole batch of arithmetic old.
-// P16: the level's input band and its detail bands are 16-bit values (levels 2..5 of an 8-bit source in the codec: with
-// |x| <= 255 a sample of level k's input stays below 255 * 2.25^(k-1) and its details below four times that — the
-// low-pass of cdf53.h:9-34 has an l1 norm of 1.5 per direction, the high-pass of 2 — i.e. 26 142 on the fifth level;
-// that bound is loose: the composed five-level response has an l1 norm of 7.95, 2 028 for 8-bit samples, and
-// tests/test_codec_gpu.py builds the picture that gets there); the arithmetic is int32 either way.
-// SRC_U16 / SRC_RGB16 / SRC_RGBP16: the finest level of a deep picture reads its uint16_t pixels itself (widening and YCoCg-R fused);
-// everything it writes is int32.
-template <bool HIST, int SRC>
-__global__ __launch_bounds__(64 * WAVES) void k_fwd_level_w(LevelArgsW A)
-{
-	const LevelArgs &a = A.a;
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	int bx, by;
-	xcd_strip(bx, by);
-	const int sx = (bx << A.wx_log2) + (wv & ((1 << A.wx_log2) - 1));   // the wave's strip of 64 quads
-	const int q = sx * 64 + lane;
-	const int j0 = (by * (WAVES >> A.wx_log2) + (wv >> A.wx_log2)) * a.rpw;
-	if (j0 >= a.h2 || sx * 64 >= A.nquads)
-		return;
-	const int j1 = min(j0 + a.rpw, a.h2);
-	const int plane = blockIdx.z;
-	const bool valid = q < A.nquads;
-	constexpr bool P16 = SRC == SRC_I16;
-	typedef SrcBand<SRC> Band;
-	int ch = 0;   // (the RGB16 source: the plane's channel; uniform)
-	const typename Band::ptr src = Band::of(a, plane, ch);
-	int *ll = a.ll + plane * a.ll_ps;
-	short *ll16 = a.ll16 ? a.ll16 + plane * a.ll_ps : nullptr;   // (uniform)
-	int *det = a.det + plane * a.det_ps;
-	short *det16 = P16 ? a.det16 + plane * a.det_ps : nullptr;
-
-	constexpr int S = 2;
-	const int jfirst = j0 > 0 ? j0 - 1 : 0;
-	const LaneAtI at = Band::at(q, lane, A.nquads);
-	I2 l0, h0, pl = { 0, 0 }, ph = { 0, 0 };
-	fwd_lift_w(Band::wide(Band::load(src + (long)(2 * jfirst) * a.spitch, at, A.cstride), ch), q, lane, A.nquads, l0, h0);
-	auto rowp = [&](int r) { return src + (long)min(r, a.h - 1) * a.spitch; };
-	FwdRaw cur[2 * S];
-	typename Band::raw nxt[2 * S];
-#pragma unroll
-	for (int k = 0; k < 2 * S; ++k)
-		nxt[k] = Band::load(rowp(2 * jfirst + 1 + k), at, A.cstride);
-	I2 osl[S], osh[S], odl[S], odh[S];   // a batch's results wait here for the next iteration's stores
-	auto store_batch = [&](int jb) {
-#pragma unroll
-		for (int s = 0; s < S; ++s) {
-			const int j = jb + s;
-			if (j >= j0 && j < j1 && valid) {
-				if (ll16)
-					st2(ll16 + (long)j * a.llpitch + 2 * q, osl[s]);
-				else
-					st2(ll + (long)j * a.llpitch + 2 * q, osl[s]);
-				if (P16) {
-					st2(det16 + (long)j * a.dpitch + a.w2 + 2 * q, osh[s]);
-					if (2 * j + 1 < a.h) {
-						st2(det16 + (long)(a.h2 + j) * a.dpitch + 2 * q, odl[s]);
-						st2(det16 + (long)(a.h2 + j) * a.dpitch + a.w2 + 2 * q, odh[s]);
-					}
-				} else {
-					st2(det + (long)j * a.dpitch + a.w2 + 2 * q, osh[s]);
-					if (2 * j + 1 < a.h) {
-						st2(det + (long)(a.h2 + j) * a.dpitch + 2 * q, odl[s]);
-						st2(det + (long)(a.h2 + j) * a.dpitch + a.w2 + 2 * q, odh[s]);
-					}
-				}
-			}
-		}
-	};
-	HistAcc hHL = { 0, 0, 0, 0 }, hLH = { 0, 0, 0, 0 }, hHH = { 0, 0, 0, 0 };
-	for (int jb = jfirst; jb < j1; jb += S) {
-#pragma unroll
-		for (int k = 0; k < 2 * S; ++k)
-			cur[k] = Band::held(nxt[k], ch);   // the one wait of the iteration: everything outstanding is a batch old
-		if (jb > jfirst)
-			store_batch(jb - S);
-		if (jb + S < j1) {
-#pragma unroll
-			for (int k = 0; k < 2 * S; ++k)
-				nxt[k] = Band::load(rowp(2 * (jb + S) + 1 + k), at, A.cstride);
-		}
-#pragma unroll
-		for (int s = 0; s < S; ++s) {
-			const int jj = jb + s;
-			if (jj >= j1)
-				break;
-			const int r1 = 2 * jj + 1, r2 = r1 + 1;
-			const bool odd_in = r1 < a.h;
-			I2 l1 = { 0, 0 }, h1 = { 0, 0 }, l2 = l0, h2v = h0;
-			if (odd_in)
-				fwd_lift_w(cur[2 * s], q, lane, A.nquads, l1, h1);
-			if (r2 < a.h)
-				fwd_lift_w(cur[2 * s + 1], q, lane, A.nquads, l2, h2v);
-			const I2 dl = i2_pred(l1, l0, l2);
-			const I2 dh = i2_pred(h1, h0, h2v);
-			I2 sl = l0, sh = h0;
-			if (odd_in) {
-				sl = i2_upd(l0, jj ? pl : dl, dl);
-				sh = i2_upd(h0, jj ? ph : dh, dh);
-			}
-			osl[s] = sl;
-			osh[s] = sh;
-			odl[s] = dl;
-			odh[s] = dh;
-			if (HIST && jj >= j0) {
-				// the detail coefficients of this row pair (cdf53.h:9-34 output): HL row jj, LH and HH row h2 + jj
-				if (valid) {
-					hist_add(hHL, sh.a);
-					hist_add(hHL, sh.b);
-					if (odd_in) {
-						hist_add(hLH, dl.a);
-						hist_add(hLH, dl.b);
-						hist_add(hHH, dh.a);
-						hist_add(hHH, dh.b);
-					}
-				}
-				if ((jj & 3) == 3) {   // eight coefficients per subband since the last fold: a nibble holds fifteen
-					hist_fold(hHL);
-					hist_fold(hLH);
-					hist_fold(hHH);
-				}
-				// a block ends where its 32 rows end (or the strip does): the rows of HL are jj, those of LH / HH h2 + jj
-				const bool last = jj == j1 - 1;
-				const int bxl = (2 * q) >> 5, bxh = (a.w2 + 2 * q) >> 5;
-				if (last || ((jj + 1) & 31) == 0)
-					hist_flush(hHL, A.hist, plane, bxh, jj >> 5, lane);
-				if (last || ((a.h2 + jj + 1) & 31) == 0) {
-					hist_flush(hLH, A.hist, plane, bxl, (a.h2 + jj) >> 5, lane);
-					hist_flush(hHH, A.hist, plane, bxh, (a.h2 + jj) >> 5, lane);
-				}
-			}
-			pl = dl;
-			ph = dh;
-			l0 = l2;
-			h0 = h2v;
-		}
-	}
-	store_batch(jfirst + (j1 - 1 - jfirst) / S * S);   // the last batch (a strip has at least one row pair)
 }
 
 // ---- two levels per pass (forward, int32 planes) ----
@@ -1065,7 +771,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_fwd2_level_w(Level2Args a)
 	for (int jb = jfirst; jb <= r_hi; jb += S) {
 #pragma unroll
 		for (int k = 0; k < 2 * S; ++k)
-			cur[k] = hold(nxt[k]);   // the one wait of the iteration (see k_fwd_level_w)
+			cur[k] = hold(nxt[k]);   // the one wait of the iteration (see fwd_level_body)
 		if (jb > jfirst)
 			store_batch(jb - S);
 		if (jb + S <= r_hi) {
@@ -1082,10 +788,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_fwd2_level_w(Level2Args a)
 			fwd_lift_q(cur[2 * s], q, a.nquads, l1, h1);
 			if (2 * jj + 2 < a.h)
 				fwd_lift_q(cur[2 * s + 1], q, a.nquads, l2, h2v);
-			const I2 dl = i2_pred(l1, l0, l2);
-			const I2 dh = i2_pred(h1, h0, h2v);
-			const I2 sl = i2_upd(l0, jj ? pl : dl, dl);
-			osh[s] = i2_upd(h0, jj ? ph : dh, dh);
+			const I2 dl = lift_pred(l1, l0, l2);
+			const I2 dh = lift_pred(h1, h0, h2v);
+			const I2 sl = lift_upd(l0, jj ? pl : dl, dl);
+			osh[s] = lift_upd(h0, jj ? ph : dh, dh);
 			odl[s] = dl;
 			odh[s] = dh;
 			pl = dl;
@@ -1122,13 +828,32 @@ __global__ __launch_bounds__(64 * WAVES) void k_fwd2_level_w(Level2Args a)
 // Samples of magnitude <= 255 cannot leave 16 bits anywhere in one level of cdf53.h:9-34 (|d| <= 510 after the row
 // pass, <= 1020 after the column pass; every intermediate sum stays below 2^12): the lane's two column pairs ride in
 // the halves of one register and every add / shift / subtract is a v_pk_* instruction on both.  Same results as
-// the int32 arithmetic of k_fwd_level_w, with about half the vector instructions.
+// the int32 arithmetic, with about half the vector instructions.
 typedef short P2 __attribute__((ext_vector_type(2)));
 typedef unsigned short U2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ P2 p2_of(unsigned u) { return __builtin_bit_cast(P2, u); }
 __device__ __forceinline__ unsigned bits_of(P2 v) { return __builtin_bit_cast(unsigned, v); }
 __device__ __forceinline__ P2 tdiv2p(P2 a) { return (a + (P2)((U2)a >> (U2)15)) >> (P2)1; }
 __device__ __forceinline__ P2 tdiv4p(P2 a) { return (a + ((a >> (P2)15) & (P2)3)) >> (P2)2; }
+
+// what the loop of fwd_level_body asks of an arithmetic (the int32 one: I2 above)
+__device__ __forceinline__ P2 lift_pred(P2 odd, P2 e0, P2 e2) { return odd - tdiv2p(e0 + e2); }
+__device__ __forceinline__ P2 lift_upd(P2 even, P2 dprev, P2 d) { return even + tdiv4p(dprev + d); }
+__device__ __forceinline__ void st2(int *p, P2 v) { *reinterpret_cast<int2 *>(p) = make_int2((int)v.x, (int)v.y); }
+__device__ __forceinline__ void st2(short *p, P2 v) { *reinterpret_cast<unsigned *>(p) = bits_of(v); }
+
+// (no clamp at 15 bits as in hist_add(.., int): the magnitudes of a level from 8-bit samples are below 2^12)
+__device__ __forceinline__ void hist_add(HistAcc &h, P2 v)
+{
+	const unsigned a = bits_of(__builtin_elementwise_max(v, -v));   // both magnitudes
+	h.mx |= a;
+	const unsigned t0 = 32u - (unsigned)__clz((int)(a & 0xffffu)), t1 = 32u - (unsigned)__clz((int)(a >> 16));
+	h.R += 0x1111111111111111ull << (4u * t0);
+	h.R += 0x1111111111111111ull << (4u * t1);
+}
+
+// (HistAcc::mx gathered both halves: one OR more before a flush)
+__device__ __forceinline__ unsigned hist_mx(unsigned mx, P2) { return (mx | (mx >> 16)) & 0xffffu; }
 
 // image.h:52-65 on two pixels at once: channel ch of (R, G, B) pairs
 __device__ __forceinline__ P2 ycocg_p(P2 r, P2 g, P2 b, int ch)
@@ -1144,31 +869,6 @@ __device__ __forceinline__ P2 ycocg_p(P2 r, P2 g, P2 b, int ch)
 struct RowP {
 	P2 E, O, xr, left;
 };
-
-__device__ __forceinline__ RowP row_p(const FwdRaw8 &r, int)
-{
-	RowP o;
-	o.E = p2_of(r.v & 0x00ff00ffu);
-	o.O = p2_of((r.v >> 8) & 0x00ff00ffu);
-	o.xr = p2_of(r.edge & 255u);
-	o.left = p2_of(__builtin_amdgcn_perm(0u, r.edge, 0x0c030c02u));   // the last two bytes of the word before
-	return o;
-}
-
-__device__ __forceinline__ RowP row_p(const FwdRawRgb &r, int ch)
-{
-	// a = R0 G0 B0 R1, b = G1 B1 R2 G2, c = B2 R3 G3 B3 (v_perm_b32: selector bytes 0-3 pick from the second operand, 4-7 from the first, 0x0c is zero)
-	RowP o;
-	o.E = ycocg_p(p2_of(__builtin_amdgcn_perm(r.b, r.a, 0x0c060c00u)), p2_of(__builtin_amdgcn_perm(r.b, r.a, 0x0c070c01u)),
-		p2_of(__builtin_amdgcn_perm(r.c, r.a, 0x0c040c02u)), ch);
-	o.O = ycocg_p(p2_of(__builtin_amdgcn_perm(r.c, r.a, 0x0c050c03u)), p2_of(__builtin_amdgcn_perm(r.c, r.b, 0x0c060c00u)),
-		p2_of(__builtin_amdgcn_perm(r.c, r.b, 0x0c070c01u)), ch);
-	// lane 63: e0 = R4 G4 B4 ..; lane 0: e0, e1 = bytes 12q-8 .. 12q-1, pixels 4q-2 and 4q-1 are the last six
-	o.xr = ycocg_p(p2_of(r.e0 & 255u), p2_of((r.e0 >> 8) & 255u), p2_of((r.e0 >> 16) & 255u), ch);
-	o.left = ycocg_p(p2_of(__builtin_amdgcn_perm(r.e1, r.e0, 0x0c050c02u)), p2_of(__builtin_amdgcn_perm(r.e1, r.e0, 0x0c060c03u)),
-		p2_of(__builtin_amdgcn_perm(r.e1, r.e0, 0x0c070c04u)), ch);
-	return o;
-}
 
 // cdf53.h:9-34 along the row for the lane's two pairs: L = (s[2q], s[2q+1]), Hh = (d[2q], d[2q+1])
 __device__ __forceinline__ void fwd_lift_p(const RowP &r, int q, int lane, int nquads, P2 &L, P2 &Hh)
@@ -1194,62 +894,18 @@ __device__ __forceinline__ void fwd_lift_p(const RowP &r, int q, int lane, int n
 	Hh = D;
 }
 
-__device__ __forceinline__ void hist_add2(HistAcc &h, P2 v)
-{
-	const unsigned a = bits_of(__builtin_elementwise_max(v, -v));   // both magnitudes (below 2^12)
-	h.mx |= a;
-	const unsigned t0 = 32u - (unsigned)__clz((int)(a & 0xffffu)), t1 = 32u - (unsigned)__clz((int)(a >> 16));
-	h.R += 0x1111111111111111ull << (4u * t0);
-	h.R += 0x1111111111111111ull << (4u * t1);
-}
-
-__device__ __forceinline__ void st2(int *p, P2 v) { *reinterpret_cast<int2 *>(p) = make_int2((int)v.x, (int)v.y); }
-__device__ __forceinline__ void st2(short *p, P2 v) { *reinterpret_cast<unsigned *>(p) = bits_of(v); }
-
-// Rows for the batched loop below: every lane loads — lanes beyond the row from the row's last quad, the edge word from
-// a clamped place — so that no load sits behind a branch or feeds a select (either would make the wave wait for it at
-// once); what the extra lanes get is never used.  e8: byte offset of the lane's edge word in a row (the word before the
-// lane's pixels for lane 0, the word after them for the others), the same for every row.
-struct LaneAt {
-	int main, edge;   // byte offsets in a source row
+// 8-bit rows wait for their turn as they were loaded and become a RowP — widened, RGB through the colour transform of
+// image.h:52-65 — when they are used.  Gray: four pixels in a word, the neighbours' in another.
+struct FwdRaw8 {
+	unsigned v;       // pixels 4q .. 4q+3
+	unsigned edge;    // the word after them (lane 63: its first byte is x[4q+4]) or before them (lane 0: its last two are x[4q-2], x[4q-1])
 };
 
-__device__ __forceinline__ LaneAt lane_at(SrcTag<uint8_t>, int q, int lane, int nquads)
-{
-	const int qa = min(q, nquads - 1);
-	LaneAt o = { 4 * qa, lane == 0 ? max(4 * qa - 4, 0) : min(4 * qa + 4, 4 * (nquads - 1)) };
-	return o;
-}
-
-__device__ __forceinline__ LaneAt lane_at(SrcTag<Rgb8>, int q, int lane, int nquads)
-{
-	const int qa = min(q, nquads - 1);
-	LaneAt o = { 12 * qa, lane == 0 ? max(12 * qa - 8, 0) : min(12 * qa + 12, 12 * nquads - 8) };
-	return o;
-}
-
-__device__ __forceinline__ FwdRaw8 fwd_load_p(SrcTag<uint8_t>, const uint8_t *__restrict__ row, const LaneAt &at, long = 0, int = 0)
+__device__ __forceinline__ FwdRaw8 fwd_load_8(const uint8_t *__restrict__ row, const LaneAt &at)
 {
 	FwdRaw8 r;
 	r.v = *reinterpret_cast<const unsigned *>(row + at.main);
 	r.edge = *reinterpret_cast<const unsigned *>(row + at.edge);
-	return r;
-}
-
-// (the RGB row as the two loads deliver it — three words and two words in consecutive registers; taking single words
-// out of them at load time would be a use of the load)
-typedef unsigned U32x3 __attribute__((ext_vector_type(3)));
-typedef unsigned U32x2 __attribute__((ext_vector_type(2)));
-struct FwdRawRgbP {
-	U32x3 abc;   // pixels 4q .. 4q+3
-	U32x2 e;     // lane 63: e.x = the word with pixel 4q+4; lane 0: bytes 12q-8 .. 12q-1
-};
-
-__device__ __forceinline__ FwdRawRgbP fwd_load_p(SrcTag<Rgb8>, const uint8_t *__restrict__ row, const LaneAt &at, long, int)
-{
-	FwdRawRgbP r;
-	r.abc = *reinterpret_cast<const U32x3 *>(row + at.main);
-	r.e = *reinterpret_cast<const U32x2 *>(row + at.edge);
 	return r;
 }
 
@@ -1258,39 +914,63 @@ __device__ __forceinline__ FwdRaw8 hold(const FwdRaw8 &r)
 	FwdRaw8 o = { hold(r.v), hold(r.edge) };
 	return o;
 }
-__device__ __forceinline__ FwdRawRgb hold(const FwdRawRgbP &r)
+
+__device__ __forceinline__ RowP row_p(const FwdRaw8 &r, int)
 {
-	FwdRawRgb o = { hold(r.abc.x), hold(r.abc.y), hold(r.abc.z), hold(r.e.x), hold(r.e.y) };
+	RowP o;
+	o.E = p2_of(r.v & 0x00ff00ffu);
+	o.O = p2_of((r.v >> 8) & 0x00ff00ffu);
+	o.xr = p2_of(r.edge & 255u);
+	o.left = p2_of(__builtin_amdgcn_perm(0u, r.edge, 0x0c030c02u));   // the last two bytes of the word before
 	return o;
 }
-__device__ __forceinline__ FwdRawRgb as_used(const FwdRawRgbP &r)
+
+// Interleaved RGB: the row as the two loads deliver it — the four pixels' three words and two words of neighbours in
+// consecutive registers; taking single words out of them at load time would be a use of the load.
+typedef unsigned U32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned U32x3 __attribute__((ext_vector_type(3)));
+typedef unsigned U32x4 __attribute__((ext_vector_type(4)));
+struct FwdRawRgb {
+	U32x3 abc;   // pixels 4q .. 4q+3
+	U32x2 e;     // lane 63: e.x = the word with pixel 4q+4; lane 0: bytes 12q-8 .. 12q-1 (pixels 4q-2 and 4q-1 are the last six)
+};
+
+__device__ __forceinline__ FwdRawRgb hold(const FwdRawRgb &r)
 {
-	FwdRawRgb o = { r.abc.x, r.abc.y, r.abc.z, r.e.x, r.e.y };
+	FwdRawRgb o = { { hold(r.abc.x), hold(r.abc.y), hold(r.abc.z) }, { hold(r.e.x), hold(r.e.y) } };
 	return o;
 }
-__device__ __forceinline__ FwdRaw8 as_used(const FwdRaw8 &r) { return r; }
+
+__device__ __forceinline__ RowP row_p(const FwdRawRgb &r, int ch)
+{
+	// a = R0 G0 B0 R1, b = G1 B1 R2 G2, c = B2 R3 G3 B3 (v_perm_b32: selector bytes 0-3 pick from the second operand, 4-7 from the first, 0x0c is zero)
+	const unsigned a = r.abc.x, b = r.abc.y, c = r.abc.z, e0 = r.e.x, e1 = r.e.y;
+	RowP o;
+	o.E = ycocg_p(p2_of(__builtin_amdgcn_perm(b, a, 0x0c060c00u)), p2_of(__builtin_amdgcn_perm(b, a, 0x0c070c01u)),
+		p2_of(__builtin_amdgcn_perm(c, a, 0x0c040c02u)), ch);
+	o.O = ycocg_p(p2_of(__builtin_amdgcn_perm(c, a, 0x0c050c03u)), p2_of(__builtin_amdgcn_perm(c, b, 0x0c060c00u)),
+		p2_of(__builtin_amdgcn_perm(c, b, 0x0c070c01u)), ch);
+	// lane 63: e0 = R4 G4 B4 ..; lane 0: e0, e1 = bytes 12q-8 .. 12q-1, pixels 4q-2 and 4q-1 are the last six
+	o.xr = ycocg_p(p2_of(e0 & 255u), p2_of((e0 >> 8) & 255u), p2_of((e0 >> 16) & 255u), ch);
+	o.left = ycocg_p(p2_of(__builtin_amdgcn_perm(e1, e0, 0x0c050c02u)), p2_of(__builtin_amdgcn_perm(e1, e0, 0x0c060c03u)),
+		p2_of(__builtin_amdgcn_perm(e1, e0, 0x0c070c04u)), ch);
+	return o;
+}
 
 // Planar RGB rows: the same row of the window's three planes, each as a gray row is loaded — the lane's quad is one aligned
-// word per channel and the neighbours' another, both inside the row's own W bytes of that plane (lane_at of gray rows).
+// word per channel and the neighbours' another, both inside the row's own W bytes of that plane.
 // Nothing is unpacked: the bytes of a word are four pixels of ONE channel, so the even / odd pairs of row_p(FwdRaw8) feed
 // the packed colour transform as they are (against six v_perm_b32 per row and two for the edges from interleaved pixels).
 struct FwdRawRgb3 {
 	FwdRaw8 r, g, b;
 };
-__device__ __forceinline__ LaneAt lane_at(SrcTag<RgbP8>, int q, int lane, int nquads) { return lane_at(SrcTag<uint8_t>(), q, lane, nquads); }
-// (ch: the channel the workgroup extracts, a constant where this is inlined: Co is R - B and leaves the G plane unloaded)
-__device__ __forceinline__ FwdRawRgb3 fwd_load_p(SrcTag<RgbP8>, const uint8_t *__restrict__ row, const LaneAt &at, long cs, int ch)
-{
-	const FwdRaw8 r = fwd_load_p(SrcTag<uint8_t>(), row, at), b = fwd_load_p(SrcTag<uint8_t>(), row + 2 * cs, at);
-	FwdRawRgb3 o = { r, ch == 1 ? r : fwd_load_p(SrcTag<uint8_t>(), row + cs, at), b };
-	return o;
-}
+
 __device__ __forceinline__ FwdRawRgb3 hold(const FwdRawRgb3 &r)
 {
 	FwdRawRgb3 o = { hold(r.r), hold(r.g), hold(r.b) };
 	return o;
 }
-__device__ __forceinline__ FwdRawRgb3 as_used(const FwdRawRgb3 &r) { return r; }
+
 __device__ __forceinline__ RowP row_p(const FwdRawRgb3 &r, int ch)
 {
 	const RowP R = row_p(r.r, 0), G = row_p(r.g, 0), B = row_p(r.b, 0);
@@ -1301,124 +981,266 @@ __device__ __forceinline__ RowP row_p(const FwdRawRgb3 &r, int ch)
 // RGB in 4-byte pixels: the lane's four pixels are one 16-byte load (rows and window origins are multiples of 4 bytes:
 // dwtx_pixels::wide()), a word per pixel, the fourth byte of each never used; the edge is the neighbours' two words — lane 0:
 // pixels 4q-2 and 4q-1, the others: pixel 4q+4 first — clamped into the row's own 4*W bytes like every edge here.
-typedef unsigned U32x4 __attribute__((ext_vector_type(4)));
-struct FwdRawRgbxP {
+struct FwdRawRgbx {
 	U32x4 px;    // pixels 4q .. 4q+3
 	U32x2 e;
 };
-struct FwdRawRgbx {
-	unsigned a, b, c, d;   // pixels 4q .. 4q+3
-	unsigned e0, e1;
-};
-__device__ __forceinline__ LaneAt lane_at(SrcTag<Rgbx8>, int q, int lane, int nquads)
+
+__device__ __forceinline__ FwdRawRgbx hold(const FwdRawRgbx &r)
 {
-	const int qa = min(q, nquads - 1);
-	LaneAt o = { 16 * qa, lane == 0 ? max(16 * qa - 8, 0) : min(16 * qa + 16, 16 * nquads - 8) };
+	FwdRawRgbx o = { { hold(r.px.x), hold(r.px.y), hold(r.px.z), hold(r.px.w) }, { hold(r.e.x), hold(r.e.y) } };
 	return o;
 }
-__device__ __forceinline__ FwdRawRgbxP fwd_load_p(SrcTag<Rgbx8>, const uint8_t *__restrict__ row, const LaneAt &at, long, int)
-{
-	FwdRawRgbxP r;
-	r.px = *reinterpret_cast<const U32x4 *>(row + at.main);
-	r.e = *reinterpret_cast<const U32x2 *>(row + at.edge);
-	return r;
-}
-__device__ __forceinline__ FwdRawRgbx hold(const FwdRawRgbxP &r)
-{
-	FwdRawRgbx o = { hold(r.px.x), hold(r.px.y), hold(r.px.z), hold(r.px.w), hold(r.e.x), hold(r.e.y) };
-	return o;
-}
-__device__ __forceinline__ FwdRawRgbx as_used(const FwdRawRgbxP &r)
-{
-	FwdRawRgbx o = { r.px.x, r.px.y, r.px.z, r.px.w, r.e.x, r.e.y };
-	return o;
-}
+
 // channel ch of the pixels in the words lo and hi, as a packed pair (v_perm_b32 as in row_p(FwdRawRgb): a word is R G B x)
 __device__ __forceinline__ P2 rgbx_pair(unsigned lo, unsigned hi, int ch)
 {
 	return ycocg_p(p2_of(__builtin_amdgcn_perm(hi, lo, 0x0c040c00u)), p2_of(__builtin_amdgcn_perm(hi, lo, 0x0c050c01u)),
 		p2_of(__builtin_amdgcn_perm(hi, lo, 0x0c060c02u)), ch);
 }
+
 __device__ __forceinline__ RowP row_p(const FwdRawRgbx &r, int ch)
 {
-	RowP o = { rgbx_pair(r.a, r.c, ch), rgbx_pair(r.b, r.d, ch),
-		ycocg_p(p2_of(r.e0 & 255u), p2_of((r.e0 >> 8) & 255u), p2_of((r.e0 >> 16) & 255u), ch),   // lane 63: e0 = pixel 4q+4
-		rgbx_pair(r.e0, r.e1, ch) };                                                              // lane 0: e0, e1 = pixels 4q-2, 4q-1
+	const unsigned e0 = r.e.x, e1 = r.e.y;
+	RowP o = { rgbx_pair(r.px.x, r.px.z, ch), rgbx_pair(r.px.y, r.px.w, ch),
+		ycocg_p(p2_of(e0 & 255u), p2_of((e0 >> 8) & 255u), p2_of((e0 >> 16) & 255u), ch),   // lane 63: e0 = pixel 4q+4
+		rgbx_pair(e0, e1, ch) };                                                          // lane 0: e0, e1 = pixels 4q-2, 4q-1
 	return o;
 }
 
-// the row as it is loaded / as it is used
-template <typename SrcT>
-struct RowRegs {
-	typedef FwdRaw8 Loaded;
-	typedef FwdRaw8 Used;
-	static constexpr int S = 2;   // row pairs per batch of fwd_pixels_body's loop
-};
-template <>
-struct RowRegs<Rgb8> {
-	typedef FwdRawRgbP Loaded;
-	typedef FwdRawRgb Used;
+// ---- the sources of a wide forward level ----
+// FwdSrc<Src>: what the one loop below needs to know about where its samples come from.
+//   Pair        the arithmetic the level is lifted in: I2 (int32) or P2 (packed 16-bit: 8-bit pixels only, see above)
+//   Loaded      a row as it is loaded, and as it waits for its turn
+//   Used        a row in cur[], as a batch's arithmetic takes it: the int32 sources widen it there (FwdRaw), the packed
+//               ones leave it as loaded and make a RowP of it in lift()
+//   S           row pairs per batch of the loop
+//   RGB_GRID    the three channels of a strip are three workgroups side by side (xcd_strip_rgb) and the channel a
+//               compile-time constant of the body; otherwise a workgroup column per plane and base() says the channel
+//   det16(a, plane), details16(p)   the plane's 16-bit detail bands, and whether the details go there: always for
+//               16-bit bands, never for int32 and deep sources, where the pointer is set for 8-bit pixels
+//   base(a, plane, ch)   the plane's first sample (RGB: of its window; the planar ones: in channel 0's plane) and its channel
+//   at(q, lane, nquads)  where the lane loads in every row
+//   load(row, at, cstride, ch), used(loaded, ch), lift(used, ch, q, lane, nquads, lo, hi)
+// (the pitch, the strides and `at` count samples of the source — bytes for 8-bit pixels.)
+template <typename Src>
+struct FwdSrc;
+
+// the band a level of k_fwd_level_w reads: int32 planes, 16-bit planes (dwtx_p16: the detail bands go out as 16-bit values
+// too), or — the finest level of a deep picture — uint16_t pixels, gray, interleaved RGB or planar RGB; and the pixels
+// k_fwd_pixels_w reads (the host's names for Band<>'s five and for uint8_t, Rgb8, RgbP8 and Rgbx8)
+enum { SRC_I32 = 0, SRC_I16, SRC_U16, SRC_RGB16, SRC_RGBP16, SRC_U8, SRC_RGB8, SRC_RGBP8, SRC_RGBX8, SRC_COUNT };
+template <int SRC>
+struct Band {};
+// 8-bit interleaved RGB pixels, of which each plane's workgroup takes its own YCoCg-R channel (image.h:52-65 fused; 8-bit
+// gray pixels — pnm.h:69-74 fused — are FwdSrc<uint8_t>)
+struct Rgb8 {};
+// 8-bit planar RGB pixels (dwtx_pixels::channel_stride): three gray-style rows per row, one per plane, no unpacking
+struct RgbP8 {};
+// 8-bit RGB in 4-byte pixels (dwtx_pixels::rgbx8(): RGBA / RGBX surfaces, pixel step 4): interleaved like Rgb8, a lane's
+// four pixels one 16-byte piece whose every fourth byte is loaded and never used
+struct Rgbx8 {};
+
+// plane p of an RGB picture = channel p % 3 of window p / 3 (src_ps from a window to the next)
+__device__ __forceinline__ long rgb_window(const LevelArgs &a, int plane, int &ch)
+{
+	ch = plane % 3;
+	return win_off(a.grid, a.src_ps, plane / 3);
+}
+
+struct FwdInt32 {
+	typedef I2 Pair;
+	typedef FwdRaw Used;
 	static constexpr int S = 2;
-};
-template <>
-struct RowRegs<Rgbx8> {
-	typedef FwdRawRgbxP Loaded;
-	typedef FwdRawRgbx Used;
-	static constexpr int S = 2;
-};
-template <>
-struct RowRegs<RgbP8> {
-	typedef FwdRawRgb3 Loaded;
-	typedef FwdRawRgb3 Used;
-	static constexpr int S = 1;   // (a row is six registers: batches of two pairs took the kernel with histograms to 133, three waves per SIMD)
+	static constexpr bool RGB_GRID = false;
+	static __device__ __forceinline__ short *det16(const LevelArgs &, int) { return nullptr; }
+	static __device__ __forceinline__ bool details16(const short *) { return false; }
+	static __device__ __forceinline__ void lift(const FwdRaw &r, int, int q, int lane, int nquads, I2 &lo, I2 &hi) { fwd_lift_w(r, q, lane, nquads, lo, hi); }
 };
 
-// CH: the YCoCg-R channel the launch's workgroup extracts, as a compile-time constant (RGB; the kernel below branches —
-// uniformly — into the three instances: Co is one subtraction per pixel pair, and neither it nor Cg needs what only Y needs;
-// with the channel as a run-time value every workgroup computed all three and selected: 1.84 -> 1.6 ms per 256 frames of 1080p)
-template <typename SrcT, bool HIST, int CH>
-__device__ __forceinline__ void fwd_pixels_body(const LevelArgsW &A, int bx, int by)
+struct FwdPacked {
+	typedef P2 Pair;
+	static constexpr int S = 2;
+	static constexpr bool RGB_GRID = false;
+	static __device__ __forceinline__ short *det16(const LevelArgs &a, int plane) { return a.det16 ? a.det16 + plane * a.det_ps : nullptr; }   // (uniform)
+	static __device__ __forceinline__ bool details16(const short *p) { return p != nullptr; }
+	template <typename Row>
+	static __device__ __forceinline__ Row used(const Row &r, int) { return r; }
+	template <typename Row>
+	static __device__ __forceinline__ void lift(const Row &r, int ch, int q, int lane, int nquads, P2 &lo, P2 &hi) { fwd_lift_p(row_p(r, ch), q, lane, nquads, lo, hi); }
+};
+
+template <>
+struct FwdSrc<Band<SRC_I32>> : FwdInt32 {
+	typedef FwdRawI Loaded;
+	static __device__ __forceinline__ const int *base(const LevelArgs &a, int plane, int &) { return a.src + plane * a.src_ps; }
+	static __device__ __forceinline__ LaneAt at(int q, int lane, int nquads) { return lane_at(q, lane, nquads, 4, 2); }
+	static __device__ __forceinline__ Loaded load(const int *row, const LaneAt &at, long, int) { return fwd_load_i(row, at); }
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int) { return widen(r); }
+};
+
+// The level's input band and its detail bands are 16-bit values (levels 2..5 of an 8-bit source in the codec: with
+// |x| <= 255 a sample of level k's input stays below 255 * 2.25^(k-1) and its details below four times that — the
+// low-pass of cdf53.h:9-34 has an l1 norm of 1.5 per direction, the high-pass of 2 — i.e. 26 142 on the fifth level;
+// that bound is loose: the composed five-level response has an l1 norm of 7.95, 2 028 for 8-bit samples, and
+// tests/test_codec_gpu.py builds the picture that gets there); the arithmetic is int32 either way.
+template <>
+struct FwdSrc<Band<SRC_I16>> : FwdInt32 {
+	typedef FwdRawS Loaded;
+	static __device__ __forceinline__ short *det16(const LevelArgs &a, int plane) { return a.det16 + plane * a.det_ps; }
+	static __device__ __forceinline__ bool details16(const short *) { return true; }
+	static __device__ __forceinline__ const short *base(const LevelArgs &a, int plane, int &) { return a.src16 + plane * a.src_ps; }
+	static __device__ __forceinline__ LaneAt at(int q, int lane, int nquads) { return lane_at(q, lane, nquads, 4, 2); }
+	static __device__ __forceinline__ Loaded load(const short *row, const LaneAt &at, long, int) { return fwd_load_s(row, at); }
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int) { return widen_s(r); }
+};
+
+// Deep pixels: the finest level reads the uint16_t samples itself (widening and YCoCg-R fused); everything it writes is
+// int32, and it leaves every histogram to k_hist (hist_add(.., int))
+template <>
+struct FwdSrc<Band<SRC_U16>> : FwdInt32 {
+	typedef FwdRawS Loaded;
+	static __device__ __forceinline__ const uint16_t *base(const LevelArgs &a, int plane, int &)
+	{
+		return reinterpret_cast<const uint16_t *>(a.src8) + win_off(a.grid, a.src_ps, plane);
+	}
+	static __device__ __forceinline__ LaneAt at(int q, int lane, int nquads) { return lane_at(q, lane, nquads, 4, 2); }
+	static __device__ __forceinline__ Loaded load(const uint16_t *row, const LaneAt &at, long, int) { return fwd_load_s(row, at); }
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int) { return widen_u(r); }
+};
+
+template <>
+struct FwdSrc<Band<SRC_RGB16>> : FwdInt32 {
+	typedef FwdRawRgb16 Loaded;
+	static __device__ __forceinline__ const uint16_t *base(const LevelArgs &a, int plane, int &ch)
+	{
+		return reinterpret_cast<const uint16_t *>(a.src8) + rgb_window(a, plane, ch);
+	}
+	static __device__ __forceinline__ LaneAt at(int q, int lane, int nquads) { return lane_at(q, lane, nquads, 12, 6); }
+	static __device__ __forceinline__ Loaded load(const uint16_t *row, const LaneAt &at, long, int)
+	{
+		const uint2 *m = reinterpret_cast<const uint2 *>(row + at.main);
+		const unsigned *e = reinterpret_cast<const unsigned *>(row + at.edge);
+		Loaded r = { m[0], m[1], m[2], e[0], e[1], e[2] };
+		return r;
+	}
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int ch) { return widen(r, ch); }
+};
+
+template <>
+struct FwdSrc<Band<SRC_RGBP16>> : FwdInt32 {
+	typedef FwdRawRgbS3 Loaded;
+	static __device__ __forceinline__ const uint16_t *base(const LevelArgs &a, int plane, int &ch) { return FwdSrc<Band<SRC_RGB16>>::base(a, plane, ch); }
+	static __device__ __forceinline__ LaneAt at(int q, int lane, int nquads) { return lane_at(q, lane, nquads, 4, 2); }
+	static __device__ __forceinline__ Loaded load(const uint16_t *row, const LaneAt &at, long cs, int)
+	{
+		Loaded r = { fwd_load_s(row, at), fwd_load_s(row + cs, at), fwd_load_s(row + 2 * cs, at) };
+		return r;
+	}
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int ch) { return widen(r, ch); }
+};
+
+template <>
+struct FwdSrc<uint8_t> : FwdPacked {
+	typedef FwdRaw8 Loaded;
+	typedef FwdRaw8 Used;
+	static __device__ __forceinline__ const uint8_t *base(const LevelArgs &a, int plane, int &) { return a.src8 + win_off(a.grid, a.src_ps, plane); }
+	static __device__ __forceinline__ LaneAt at(int q, int lane, int nquads) { return lane_at(q, lane, nquads, 4, 4); }
+	static __device__ __forceinline__ Loaded load(const uint8_t *row, const LaneAt &at, long, int) { return fwd_load_8(row, at); }
+};
+
+template <>
+struct FwdSrc<Rgb8> : FwdPacked {
+	typedef FwdRawRgb Loaded;
+	typedef FwdRawRgb Used;
+	static constexpr bool RGB_GRID = true;
+	static __device__ __forceinline__ const uint8_t *base(const LevelArgs &a, int plane, int &ch) { return a.src8 + rgb_window(a, plane, ch); }
+	static __device__ __forceinline__ LaneAt at(int q, int lane, int nquads) { return lane_at(q, lane, nquads, 12, 8); }
+	static __device__ __forceinline__ Loaded load(const uint8_t *__restrict__ row, const LaneAt &at, long, int)
+	{
+		Loaded r = { *reinterpret_cast<const U32x3 *>(row + at.main), *reinterpret_cast<const U32x2 *>(row + at.edge) };
+		return r;
+	}
+};
+
+template <>
+struct FwdSrc<RgbP8> : FwdPacked {
+	typedef FwdRawRgb3 Loaded;
+	typedef FwdRawRgb3 Used;
+	static constexpr bool RGB_GRID = true;
+	static constexpr int S = 1;   // (a row is six registers: batches of two pairs took the kernel with histograms to 133, three waves per SIMD)
+	static __device__ __forceinline__ const uint8_t *base(const LevelArgs &a, int plane, int &ch) { return a.src8 + rgb_window(a, plane, ch); }
+	static __device__ __forceinline__ LaneAt at(int q, int lane, int nquads) { return lane_at(q, lane, nquads, 4, 4); }
+	// (ch: the channel the workgroup extracts, a constant where this is inlined: Co is R - B and leaves the G plane unloaded)
+	static __device__ __forceinline__ Loaded load(const uint8_t *__restrict__ row, const LaneAt &at, long cs, int ch)
+	{
+		const FwdRaw8 r = fwd_load_8(row, at), b = fwd_load_8(row + 2 * cs, at);
+		Loaded o = { r, ch == 1 ? r : fwd_load_8(row + cs, at), b };
+		return o;
+	}
+};
+
+template <>
+struct FwdSrc<Rgbx8> : FwdPacked {
+	typedef FwdRawRgbx Loaded;
+	typedef FwdRawRgbx Used;
+	static constexpr bool RGB_GRID = true;
+	static __device__ __forceinline__ const uint8_t *base(const LevelArgs &a, int plane, int &ch) { return a.src8 + rgb_window(a, plane, ch); }
+	static __device__ __forceinline__ LaneAt at(int q, int lane, int nquads) { return lane_at(q, lane, nquads, 16, 8); }
+	static __device__ __forceinline__ Loaded load(const uint8_t *__restrict__ row, const LaneAt &at, long, int)
+	{
+		Loaded r = { *reinterpret_cast<const U32x4 *>(row + at.main), *reinterpret_cast<const U32x2 *>(row + at.edge) };
+		return r;
+	}
+};
+
+// One wide forward level of the wave's strip, for every source (FwdSrc above): int32 planes on every level of
+// dwtx_transformation_fwd and below the finest in the codec, pixels on the codec's finest.
+// Memory operations retire in order on this part (one counter for loads and stores): a wave that waits for rows it
+// loaded also waits for everything it issued before them, and a wait the compiler cannot count exactly waits for
+// everything.  So the loop works in batches of S row pairs: wait once (where the rows are moved to the registers they
+// are used from), send the previous batch's results out, ask for the next batch's rows, then compute S row pairs
+// without touching memory — by the next wait both the stores and the loads are a whole batch of arithmetic old.
+// CH: the YCoCg-R channel the workgroup extracts as a compile-time constant (the 8-bit RGB sources, whose kernel branches
+// — uniformly — into the three instances: Co is one subtraction per pixel pair, and neither it nor Cg needs what only Y needs;
+// with the channel as a run-time value every workgroup computed all three and selected: 1.84 -> 1.6 ms per 256 frames of
+// 1080p); below 0: whatever base() says, a run-time uniform.
+template <typename Src, bool HIST, int CH>
+__device__ __forceinline__ void fwd_level_body(const LevelArgsW &A, int bx, int by)
 {
+	typedef FwdSrc<Src> T;
+	typedef typename T::Pair Pair;
 	const LevelArgs &a = A.a;
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	const int chan = CH;
-	const int sx = (bx << A.wx_log2) + (wv & ((1 << A.wx_log2) - 1));
+	const int sx = (bx << A.wx_log2) + (wv & ((1 << A.wx_log2) - 1));   // the wave's strip of 64 quads
 	const int q = sx * 64 + lane;
 	const int j0 = (by * (WAVES >> A.wx_log2) + (wv >> A.wx_log2)) * a.rpw;
 	if (j0 >= a.h2 || sx * 64 >= A.nquads)
 		return;
 	const int j1 = min(j0 + a.rpw, a.h2);
-	const int plane = IsRgb<SrcT>::value ? (int)blockIdx.z * 3 + chan : (int)blockIdx.z;
+	const int plane = T::RGB_GRID ? (int)blockIdx.z * 3 + CH : (int)blockIdx.z;
 	const bool valid = q < A.nquads;
-	int ch_rt;
-	const uint8_t *src = fwd_base(SrcTag<SrcT>(), a, plane, ch_rt);
-	const int ch = CH;   // (== ch_rt)
+	int ch_rt = 0;
+	const auto src = T::base(a, plane, ch_rt);
+	const int ch = CH >= 0 ? CH : ch_rt;   // (uniform)
 	int *ll = a.ll + plane * a.ll_ps;
-	short *ll16 = a.ll16 ? a.ll16 + plane * a.ll_ps : nullptr;      // (uniform)
+	short *ll16 = a.ll16 ? a.ll16 + plane * a.ll_ps : nullptr;   // (uniform)
 	int *det = a.det + plane * a.det_ps;
-	short *det16 = a.det16 ? a.det16 + plane * a.det_ps : nullptr;   // (uniform)
+	short *det16 = T::det16(a, plane);
 
-	// Memory operations retire in order on this part (one counter for loads and stores): a wave that waits for rows it
-	// loaded also waits for everything it issued before them, and a wait the compiler cannot count exactly waits for
-	// everything.  So the loop works in batches of S row pairs: wait once, send the previous batch's results out, ask
-	// for the next batch's rows, then compute S row pairs without touching memory — by the next wait both the stores
-	// and the loads are a whole batch of arithmetic old.
-	constexpr int S = RowRegs<SrcT>::S;
+	constexpr int S = T::S;
 	const int jfirst = j0 > 0 ? j0 - 1 : 0;
-	const P2 zero = p2_of(0u);
-	P2 l0, h0, pl = zero, ph = zero;
-	const LaneAt at = lane_at(SrcTag<SrcT>(), q, lane, A.nquads);
-	{
-		const typename RowRegs<SrcT>::Loaded r0 = fwd_load_p(SrcTag<SrcT>(), src + (long)(2 * jfirst) * a.spitch, at, A.cstride, CH);
-		fwd_lift_p(row_p(as_used(r0), ch), q, lane, A.nquads, l0, h0);
-	}
+	const LaneAt at = T::at(q, lane, A.nquads);
+	const Pair zero = {};
+	Pair l0, h0, pl = zero, ph = zero;
+	T::lift(T::used(T::load(src + (long)(2 * jfirst) * a.spitch, at, A.cstride, ch), ch), ch, q, lane, A.nquads, l0, h0);
 	auto rowp = [&](int r) { return src + (long)min(r, a.h - 1) * a.spitch; };
-	typename RowRegs<SrcT>::Used cur[2 * S];
-	typename RowRegs<SrcT>::Loaded nxt[2 * S];
+	typename T::Used cur[2 * S];
+	typename T::Loaded nxt[2 * S];
 #pragma unroll
 	for (int k = 0; k < 2 * S; ++k)
-		nxt[k] = fwd_load_p(SrcTag<SrcT>(), rowp(2 * jfirst + 1 + k), at, A.cstride, CH);
-	P2 osl[S], osh[S], odl[S], odh[S];   // a batch's results wait here for the next iteration's stores
+		nxt[k] = T::load(rowp(2 * jfirst + 1 + k), at, A.cstride, ch);
+	Pair osl[S], osh[S], odl[S], odh[S];   // a batch's results wait here for the next iteration's stores
 	auto store_batch = [&](int jb) {
 #pragma unroll
 		for (int s = 0; s < S; ++s) {
@@ -1429,7 +1251,7 @@ __device__ __forceinline__ void fwd_pixels_body(const LevelArgsW &A, int bx, int
 					st2(ll16 + (long)j * a.llpitch + 2 * q, osl[s]);
 				else
 					st2(ll + (long)j * a.llpitch + 2 * q, osl[s]);
-				if (det16) {
+				if (T::details16(det16)) {
 					st2(det16 + (long)j * a.dpitch + a.w2 + 2 * q, osh[s]);
 					if (odd_in) {
 						st2(det16 + (long)(a.h2 + j) * a.dpitch + 2 * q, odl[s]);
@@ -1446,16 +1268,20 @@ __device__ __forceinline__ void fwd_pixels_body(const LevelArgsW &A, int bx, int
 		}
 	};
 	HistAcc hHL = { 0, 0, 0, 0 }, hLH = { 0, 0, 0, 0 }, hHH = { 0, 0, 0, 0 };
+	auto flush = [&](HistAcc &h, int hbx, int hby) {
+		h.mx = hist_mx(h.mx, Pair());
+		hist_flush(h, A.hist, plane, hbx, hby, lane);
+	};
 	for (int jb = jfirst; jb < j1; jb += S) {
 #pragma unroll
 		for (int k = 0; k < 2 * S; ++k)
-			cur[k] = hold(nxt[k]);   // the one wait of the iteration: everything outstanding is a batch old
+			cur[k] = T::used(hold(nxt[k]), ch);   // the one wait of the iteration: everything outstanding is a batch old
 		if (jb > jfirst)
 			store_batch(jb - S);
 		if (jb + S < j1) {
 #pragma unroll
 			for (int k = 0; k < 2 * S; ++k)
-				nxt[k] = fwd_load_p(SrcTag<SrcT>(), rowp(2 * (jb + S) + 1 + k), at, A.cstride, CH);
+				nxt[k] = T::load(rowp(2 * (jb + S) + 1 + k), at, A.cstride, ch);
 		}
 #pragma unroll
 		for (int s = 0; s < S; ++s) {
@@ -1464,17 +1290,17 @@ __device__ __forceinline__ void fwd_pixels_body(const LevelArgsW &A, int bx, int
 				break;
 			const int r1 = 2 * jj + 1, r2 = r1 + 1;
 			const bool odd_in = r1 < a.h;
-			P2 l1 = zero, h1 = zero, l2 = l0, h2v = h0;
+			Pair l1 = zero, h1 = zero, l2 = l0, h2v = h0;
 			if (odd_in)
-				fwd_lift_p(row_p(cur[2 * s], ch), q, lane, A.nquads, l1, h1);
+				T::lift(cur[2 * s], ch, q, lane, A.nquads, l1, h1);
 			if (r2 < a.h)
-				fwd_lift_p(row_p(cur[2 * s + 1], ch), q, lane, A.nquads, l2, h2v);
-			const P2 dl = l1 - tdiv2p(l0 + l2);     // cdf53.h:13 down the columns
-			const P2 dh = h1 - tdiv2p(h0 + h2v);
-			P2 sl = l0, sh = h0;
-			if (odd_in) {
-				sl = l0 + tdiv4p((jj ? pl : dl) + dl);   // cdf53.h:20
-				sh = h0 + tdiv4p((jj ? ph : dh) + dh);
+				T::lift(cur[2 * s + 1], ch, q, lane, A.nquads, l2, h2v);
+			const Pair dl = lift_pred(l1, l0, l2);
+			const Pair dh = lift_pred(h1, h0, h2v);
+			Pair sl = l0, sh = h0;
+			if (odd_in) {    // an odd-height plane leaves its last even row untouched
+				sl = lift_upd(l0, jj ? pl : dl, dl);
+				sh = lift_upd(h0, jj ? ph : dh, dh);
 			}
 			osl[s] = sl;
 			osh[s] = sh;
@@ -1483,10 +1309,10 @@ __device__ __forceinline__ void fwd_pixels_body(const LevelArgsW &A, int bx, int
 			if (HIST && jj >= j0) {
 				// the detail coefficients of this row pair (cdf53.h:9-34 output): HL row jj, LH and HH row h2 + jj
 				if (valid) {
-					hist_add2(hHL, sh);
+					hist_add(hHL, sh);
 					if (odd_in) {
-						hist_add2(hLH, dl);
-						hist_add2(hHH, dh);
+						hist_add(hLH, dl);
+						hist_add(hHH, dh);
 					}
 				}
 				if ((jj & 3) == 3) {   // eight coefficients per subband since the last fold: a nibble holds fifteen
@@ -1497,15 +1323,11 @@ __device__ __forceinline__ void fwd_pixels_body(const LevelArgsW &A, int bx, int
 				// a block ends where its 32 rows end (or the strip does): the rows of HL are jj, those of LH / HH h2 + jj
 				const bool last = jj == j1 - 1;
 				const int bxl = (2 * q) >> 5, bxh = (a.w2 + 2 * q) >> 5;
-				if (last || ((jj + 1) & 31) == 0) {
-					hHL.mx = (hHL.mx | (hHL.mx >> 16)) & 0xffffu;
-					hist_flush(hHL, A.hist, plane, bxh, jj >> 5, lane);
-				}
+				if (last || ((jj + 1) & 31) == 0)
+					flush(hHL, bxh, jj >> 5);
 				if (last || ((a.h2 + jj + 1) & 31) == 0) {
-					hLH.mx = (hLH.mx | (hLH.mx >> 16)) & 0xffffu;
-					hHH.mx = (hHH.mx | (hHH.mx >> 16)) & 0xffffu;
-					hist_flush(hLH, A.hist, plane, bxl, (a.h2 + jj) >> 5, lane);
-					hist_flush(hHH, A.hist, plane, bxh, (a.h2 + jj) >> 5, lane);
+					flush(hLH, bxl, (a.h2 + jj) >> 5);
+					flush(hHH, bxh, (a.h2 + jj) >> 5);
 				}
 			}
 			pl = dl;
@@ -1514,25 +1336,34 @@ __device__ __forceinline__ void fwd_pixels_body(const LevelArgsW &A, int bx, int
 			h0 = h2v;
 		}
 	}
-	// the last batch (a strip has at least one row pair)
-	store_batch(jfirst + (j1 - 1 - jfirst) / S * S);
+	store_batch(jfirst + (j1 - 1 - jfirst) / S * S);   // the last batch (a strip has at least one row pair)
+}
+
+// The two entry points pick the strip mapping and the channel dispatch.  k_fwd_level_w: bands and deep pixels, a workgroup
+// column per plane.  k_fwd_pixels_w: 8-bit pixels.
+template <bool HIST, int SRC>
+__global__ __launch_bounds__(64 * WAVES) void k_fwd_level_w(LevelArgsW A)
+{
+	int bx, by;
+	xcd_strip(bx, by);
+	fwd_level_body<Band<SRC>, HIST, -1>(A, bx, by);
 }
 
 template <typename SrcT, bool HIST>
 __global__ __launch_bounds__(64 * WAVES) void k_fwd_pixels_w(LevelArgsW A)
 {
 	int bx, by, chan = 0;
-	if (IsRgb<SrcT>::value) {
+	if (FwdSrc<SrcT>::RGB_GRID) {
 		xcd_strip_rgb(bx, by, chan);
 		if (chan == 0)
-			fwd_pixels_body<SrcT, HIST, 0>(A, bx, by);
+			fwd_level_body<SrcT, HIST, 0>(A, bx, by);
 		else if (chan == 1)
-			fwd_pixels_body<SrcT, HIST, 1>(A, bx, by);
+			fwd_level_body<SrcT, HIST, 1>(A, bx, by);
 		else
-			fwd_pixels_body<SrcT, HIST, 2>(A, bx, by);
+			fwd_level_body<SrcT, HIST, 2>(A, bx, by);
 	} else {
 		xcd_strip(bx, by);
-		fwd_pixels_body<SrcT, HIST, 0>(A, bx, by);
+		fwd_level_body<SrcT, HIST, 0>(A, bx, by);
 	}
 }
 
@@ -2116,7 +1947,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w(Inv2Args a)
 		ceh = neh;
 	};
 	for (int m = m0; m < m1; ++m) {
-		c2 = hold(n2);   // the one wait of the iteration (see k_fwd_level_w)
+		c2 = hold(n2);   // the one wait of the iteration (see fwd_level_body)
 		c1a = hold(n1a);
 		c1b = hold(n1b);
 		if (m > m0)
@@ -2496,7 +2327,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 	for (int m = m0; m < m1; ++m) {
 #pragma unroll
 		for (int ch = 0; ch < 3; ++ch) {
-			c2[ch] = hold(n2[ch]);   // the one wait of the iteration (see k_fwd_level_w)
+			c2[ch] = hold(n2[ch]);   // the one wait of the iteration (see fwd_level_body)
 			c1a[ch] = hold(n1a[ch]);
 			c1b[ch] = hold(n1b[ch]);
 		}
@@ -2983,32 +2814,40 @@ static TailArgs tail_args(const LiftLayout &L, int *pyr)
 
 using WideKernel = void (*)(LevelArgsW);
 
-// The wide kernel of a forward step.  px: the step reads these pixels (gray or RGB; deep ones leave no histograms); null:
-// int32 planes, or src16 the 16-bit bands of the level before
-static WideKernel fwd_wide_kernel(const dwtx_pixels *px, bool hist, bool src16)
+// What a wide forward step reads.  px: these pixels; null: int32 planes, or (src16) the 16-bit bands of the level before.
+// The one place that looks at the pixels' layout: the kernel, the launch's grid and LevelArgsW::cstride follow from it.
+struct FwdSource {
+	int src;          // SRC_*
+	bool rgb_grid;    // FwdSrc<>::RGB_GRID: three workgroups per strip and nplanes / 3 in z, against one per plane
+	long cstride;
+};
+
+static FwdSource fwd_source(const dwtx_pixels *px, bool src16)
 {
-	const int channels8 = px && !px->deep() ? px->channels : 0;
-	const bool planar = px && px->channels == 3 && px->planar();
-	if (planar && channels8)
-		return hist ? k_fwd_pixels_w<RgbP8, true> : k_fwd_pixels_w<RgbP8, false>;
-	if (planar)
-		return k_fwd_level_w<false, SRC_RGBP16>;
-	if (px && px->rgbx8())
-		return hist ? k_fwd_pixels_w<Rgbx8, true> : k_fwd_pixels_w<Rgbx8, false>;
-	if (hist) {
-		if (channels8 == 3)
-			return k_fwd_pixels_w<Rgb8, true>;
-		if (channels8)
-			return k_fwd_pixels_w<uint8_t, true>;
-		return src16 ? k_fwd_level_w<true, SRC_I16> : k_fwd_level_w<true, SRC_I32>;
-	}
-	if (channels8 == 3)
-		return k_fwd_pixels_w<Rgb8, false>;
-	if (channels8)
-		return k_fwd_pixels_w<uint8_t, false>;
 	if (!px)
-		return src16 ? k_fwd_level_w<false, SRC_I16> : k_fwd_level_w<false, SRC_I32>;
-	return px->channels == 3 ? k_fwd_level_w<false, SRC_RGB16> : k_fwd_level_w<false, SRC_U16>;
+		return { src16 ? SRC_I16 : SRC_I32, false, 0 };
+	const bool deep = px->deep();
+	if (px->channels != 3)
+		return { deep ? SRC_U16 : SRC_U8, false, 0 };
+	const int src = px->planar() ? (deep ? SRC_RGBP16 : SRC_RGBP8) : px->rgbx8() ? SRC_RGBX8 : deep ? SRC_RGB16 : SRC_RGB8;
+	return { src, !deep, (long)px->channel_stride };
+}
+
+// the wide kernel of a source, without and with histograms (deep pixels leave none: lift_fwd refuses the call)
+static WideKernel fwd_wide_kernel(int src, bool hist)
+{
+	static const WideKernel K[SRC_COUNT][2] = {
+		{ k_fwd_level_w<false, SRC_I32>, k_fwd_level_w<true, SRC_I32> },
+		{ k_fwd_level_w<false, SRC_I16>, k_fwd_level_w<true, SRC_I16> },
+		{ k_fwd_level_w<false, SRC_U16>, nullptr },
+		{ k_fwd_level_w<false, SRC_RGB16>, nullptr },
+		{ k_fwd_level_w<false, SRC_RGBP16>, nullptr },
+		{ k_fwd_pixels_w<uint8_t, false>, k_fwd_pixels_w<uint8_t, true> },
+		{ k_fwd_pixels_w<Rgb8, false>, k_fwd_pixels_w<Rgb8, true> },
+		{ k_fwd_pixels_w<RgbP8, false>, k_fwd_pixels_w<RgbP8, true> },
+		{ k_fwd_pixels_w<Rgbx8, false>, k_fwd_pixels_w<Rgbx8, true> },
+	};
+	return K[src][hist];
 }
 
 // px != nullptr (`in` is then not read): the source is pixels, gray (plane p = image p) or RGB, interleaved or planar (plane p =
@@ -3113,7 +2952,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 		a.dpitch = W;
 		// 16-bit bands (dwtx_p16): the levels in the mask write their details there; between two such levels the LL
 		// band travels as 16-bit values too (in the scratch planes, which are sized for int32).  Only from 8-bit pixels:
-		// that is what bounds the magnitudes (see k_fwd_level_w).
+		// that is what bounds the magnitudes (see fwd_level_body).
 		auto in_mask = [&](int step) { return p16.planes && step < tail_from && ((p16.levels >> (T - 1 - step)) & 1u); };
 		if (in_mask(t)) {
 			if (!px || t >= LEVELS16_MAX || (t > 0 && !in_mask(t - 1)) || !aligned_to(p16.planes, 16))
@@ -3141,7 +2980,8 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			a.rpw = pick_rpw(strips, a.h2, nplanes, forced);
 			A.wx_log2 = strips >= 4 ? 2 : strips >= 2 ? 1 : 0;
 			A.a = a;
-			A.cstride = pix_in && px->channels == 3 ? (long)px->channel_stride : 0;
+			const FwdSource from = fwd_source(pix_in, a.src16 != nullptr);
+			A.cstride = from.cstride;
 			if (hist_here) {
 				A.hist = HistArgs{ sink->cum32, sink->tile_mx, sink->tiles.xy2tile + sink->tiles.xy_first[level], sink->NT, sink->NTP,
 					sink->tiles.nbs[level] };
@@ -3149,9 +2989,11 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			}
 			const int sx = dwtx_cdiv(strips, 1 << A.wx_log2), gy = dwtx_cdiv(a.h2, (WAVES >> A.wx_log2) * a.rpw);
 			// (8-bit RGB: the three channels of a strip side by side, xcd_strip_rgb; deep RGB: a block per plane, each taking its channel)
-			const bool rgb8 = pix_in && !px->deep() && px->channels == 3;
-			const dim3 grid = rgb8 ? dim3(sx * 3, gy, nplanes / 3) : dim3(sx, gy, nplanes);
-			hipLaunchKernelGGL(fwd_wide_kernel(pix_in, hist_here, a.src16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
+			const dim3 grid = from.rgb_grid ? dim3(sx * 3, gy, nplanes / 3) : dim3(sx, gy, nplanes);
+			const WideKernel kernel = fwd_wide_kernel(from.src, hist_here);
+			if (!kernel)
+				return DWTX_ERR_ARG;
+			hipLaunchKernelGGL(kernel, grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {
 			const int sx = dwtx_cdiv(a.w2, 64);
 			a.rpw = pick_rpw(sx, a.h2, nplanes, forced);

@@ -122,6 +122,21 @@ def test_planar_under_the_switches(ctx, opts, wh, name, value, is16):
         V.check_decode(ctx, L, W, H, 3, is16, rows, pixels_max)
 
 
+# 128 wide: the histograms ride along on the finest level; 260: one lane into a second strip; heights 131 and 514: a last row
+# pair without its odd row, and under lift_rows 16 / 64 strips of a single row pair (the batches of the 8-bit planar
+# kernel are one row pair, the others' two: their last batch ends differently)
+STRIP_EDGES = [(128, 130), (260, 131), (68, 514)]
+
+
+@pytest.mark.parametrize("rows", [16, 64])
+@depths
+@pytest.mark.parametrize("wh", STRIP_EDGES, ids=lambda wh: "%dx%d" % wh)
+def test_planar_rows_per_wave_at_the_strip_edges(ctx, opts, wh, is16, rows):
+    W, H = wh
+    opts.set("lift_rows", rows)
+    V.check_encode(ctx, nchw(W, H), W, H, 3, is16, capacities=(0,))
+
+
 # ---- parts -------------------------------------------------------------------------------------------------------------
 
 def test_planar_encoder_parts_start_mid_grid(ctx):

@@ -184,6 +184,16 @@ def test_step4_rgb_under_the_switches(sctx, opts, wh, name, value):
     check_both(sctx, sstack(W, H, 3, 4), W, H, 3, False)
 
 
+@pytest.mark.parametrize("rows", [16, 64])
+@pytest.mark.parametrize("wh", [(128, 130), (260, 131), (68, 514)], ids=lambda wh: "%dx%d" % wh)
+def test_step4_rgb_rows_per_wave_at_the_strip_edges(sctx, opts, wh, rows):
+    """The 4-byte RGB surface at the strip-edge shapes of tests/test_planar_gpu.py: histograms on the finest level (128
+    wide), one lane into a second strip (260), a last row pair without its odd row and strips of one row pair (131, 514)."""
+    W, H = wh
+    opts.set("lift_rows", rows)
+    V.check_encode(sctx, sstack(W, H, 3, 4), W, H, 3, False, capacities=(0,))
+
+
 # ---- parts ---------------------------------------------------------------------------------------------------------------
 
 def test_step4_encoder_parts_start_mid_grid(sctx):
