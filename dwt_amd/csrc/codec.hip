@@ -208,6 +208,8 @@ static int encode_device(dwtx_ctx *ctx, const dwtx_pixels &px, int W, int H, int
 	const int C = px.channels;
 	if (!ctx || !px.base || !dev_out || !dev_info || (C != 1 && C != 3) || n < 1 || !px.sample_aligned())
 		return DWTX_ERR_ARG;
+	if (!dwtx_count_ok((long)n * C, DWTX_MAX_PLANES_PER_CALL, "planes"))   // (before any scratch is asked for)
+		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
 	// (parts pay from about 32 images each: measured at the end of round 3, when the transform no longer waits on memory
@@ -266,7 +268,7 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 	const int C = px.channels;
 	if (!ctx || !dev_streams || !dev_lens || !px.base || !host_info || n < 1 || !px.sample_aligned())
 		return DWTX_ERR_ARG;
-	if (!dwtx_maxval_ok(px.maxval))
+	if (!dwtx_maxval_ok(px.maxval) || !dwtx_count_ok(n, DWTX_MAX_PLANES_PER_CALL / 3, "streams to decode"))   // (before any scratch is asked for)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
@@ -569,8 +571,8 @@ __global__ __launch_bounds__(PK_THREADS) void k_pack_streams(uint8_t *out, unsig
 extern "C" int dwtx_pack_streams(dwtx_ctx *ctx, uint8_t *dev_out, size_t out_bytes, unsigned long long *dev_offsets,
 	const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens, int n)
 {
-	if (!ctx || !dev_out || !dev_streams || !dev_lens || n < 1 || n > 65535 || (stream_stride & 7) || !stream_stride ||
-		((uintptr_t)dev_out & 7) || ((uintptr_t)dev_streams & 7))
+	if (!ctx || !dev_out || !dev_streams || !dev_lens || n < 1 || (stream_stride & 7) || !stream_stride ||
+		((uintptr_t)dev_out & 7) || ((uintptr_t)dev_streams & 7) || !dwtx_count_ok(n, DWTX_MAX_PLANES_PER_CALL, "streams to pack"))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	const unsigned pieces = (unsigned)((stream_stride + PK_PIECE - 1) / PK_PIECE);

@@ -108,6 +108,19 @@ static inline bool dwtx_maxval_ok(int maxval)
 	return false;
 }
 
+// The planes (images * channels) of one call: a dimension of most launches' grids (blockIdx.y / .z), which holds 65535, and
+// what WinGrid's unsigned `first + i` (lift.hip) and the kernels' int plane indices count.  32-bit by design (DESIGN.md
+// section 4.13): every entry point that takes a count refuses more, before it allocates or launches anything.  The
+// decoder takes a third of it whatever the channels (its launches are sized for three planes per image).
+#define DWTX_MAX_PLANES_PER_CALL 65535
+static inline bool dwtx_count_ok(long count, long most, const char *what)
+{
+	if (count <= most)
+		return true;
+	dwtx_set_error("%ld %s in one call: at most %ld (the planes of a call are a grid dimension of its launches); split the batch", count, what, most);
+	return false;
+}
+
 // Image sizes: sides of 8..DWTX_MAX_SIDE (above it the reference's own arithmetic overflows, include/dwtx.h), and the
 // kernels' int indices want one plane (W*H) below 2^31 — which 32768 x 32768 = 2^30 always is; the check stays for
 // whoever raises DWTX_MAX_SIDE (the reference itself indexes with int, encode.c:40 `channels*(width*y+x)`).

@@ -47,7 +47,7 @@ __device__ __forceinline__ long win_off(const WinGrid &g, long ps, int image)
 {
 	if (g.cols == 0)
 		return image * ps;
-	const unsigned i = (unsigned)__builtin_amdgcn_readfirstlane(image) + g.first;
+	const unsigned i = (unsigned)__builtin_amdgcn_readfirstlane(image) + g.first;   // (both below 65536: a call's windows, dwtx_count_ok)
 	const unsigned band = i / g.cols;
 	return (long)band * g.band_ps + (long)(i - band * g.cols) * ps;
 }
@@ -2649,6 +2649,8 @@ struct LiftLayout {
 	int *level1, *small;   // null where no step needs them
 };
 
+// (cols and first in 32 bits: both are window counts of one call, at most DWTX_MAX_PLANES_PER_CALL — dwtx_count_ok — so that
+// win_off's unsigned `i + first` cannot wrap)
 WinGrid win_grid(const dwtx_pixels &px) { return WinGrid{ (unsigned)px.cols, (unsigned)px.first, (long)px.band_stride }; }
 
 // ctx null: the sizes only
@@ -2860,7 +2862,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 		return DWTX_ERR_ARG;
 	if (hist_levels)
 		*hist_levels = 0u;
-	if (!ctx || !out || (!in && !px) || W < 2 || H < 2 || nplanes < 1 || nplanes > 65535)
+	if (!ctx || !out || (!in && !px) || W < 2 || H < 2 || nplanes < 1 || !dwtx_count_ok(nplanes, DWTX_MAX_PLANES_PER_CALL, "planes"))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	int forced;
@@ -3100,7 +3102,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 {
 	if (px && px->deep() && p16 && p16->planes)
 		return DWTX_ERR_ARG;
-	if (!ctx || (!out && !px) || !in || W < 2 || H < 2 || nplanes < 1 || nplanes > 65535)
+	if (!ctx || (!out && !px) || !in || W < 2 || H < 2 || nplanes < 1 || !dwtx_count_ok(nplanes, DWTX_MAX_PLANES_PER_CALL, "planes"))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	int forced;

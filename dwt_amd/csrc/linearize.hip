@@ -554,7 +554,7 @@ extern "C" int dwtx_linearization(dwtx_ctx *ctx, int32_t *lin, const int32_t *py
 int dwtx_linearization_ex(dwtx_ctx *ctx, int32_t *lin, const int32_t *pyr, int W, int H, int nplanes, unsigned skip_levels,
 	dwtx_p16 p16)
 {
-	if (!ctx || !lin || !pyr || nplanes < 1 || nplanes > 65535)
+	if (!ctx || !lin || !pyr || nplanes < 1 || !dwtx_count_ok(nplanes, DWTX_MAX_PLANES_PER_CALL, "planes"))
 		return DWTX_ERR_ARG;
 	DWTX_CHECK_DIMS(W, H);
 	DWTX_ENTER(ctx);
@@ -589,7 +589,7 @@ extern "C" int dwtx_reconstruction(dwtx_ctx *ctx, int32_t *pyr, const int32_t *l
 int dwtx_reconstruction_ex(dwtx_ctx *ctx, int32_t *pyr, const int32_t *lin, const int *dev_missing,
 	int levels_out, int W, int H, int C, int n, unsigned skip_levels, dwtx_p16 p16)
 {
-	if (!ctx || !lin || !pyr || (C != 1 && C != 3) || n < 1 || n * C > 65535)
+	if (!ctx || !lin || !pyr || (C != 1 && C != 3) || n < 1 || !dwtx_count_ok((long)n * C, DWTX_MAX_PLANES_PER_CALL, "planes"))
 		return DWTX_ERR_ARG;
 	DWTX_CHECK_DIMS(W, H);
 	DWTX_ENTER(ctx);

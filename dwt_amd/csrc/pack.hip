@@ -2619,7 +2619,7 @@ static int pack_geometry(dwtx_ctx *ctx, int W, int H, int C, int n, PackGeom &g,
 // levels it can take to these records (lift.hip); dwtx_encode_planes_ex is then told which levels are done.
 int dwtx_hist_begin(dwtx_ctx *ctx, int W, int H, int C, int n, dwtx_hist_sink *sink)
 {
-	if (!ctx || !sink || (C != 1 && C != 3) || n < 1 || n > 65535)
+	if (!ctx || !sink || (C != 1 && C != 3) || n < 1 || !dwtx_count_ok((long)n * C, DWTX_MAX_PLANES_PER_CALL, "planes"))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
@@ -2668,7 +2668,8 @@ extern "C" int dwtx_debug_hist_copy(dwtx_ctx *ctx, int W, int H, int C, int n, u
 int dwtx_encode_planes_ex(dwtx_ctx *ctx, const int32_t *lin, const int32_t *pyr, unsigned sq_levels, unsigned hist_levels, int W, int H, int C,
 	int n, long capacity, uint8_t *out, size_t out_stride, dwtx_stream_info *dev_info, dwtx_p16 p16, dwtx_index *dev_index)
 {
-	if (!ctx || !lin || !out || !dev_info || (C != 1 && C != 3) || n < 1 || n > 65535 || (out_stride & 3) || out_stride < 8)
+	if (!ctx || !lin || !out || !dev_info || (C != 1 && C != 3) || n < 1 || (out_stride & 3) || out_stride < 8 ||
+		!dwtx_count_ok((long)n * C, DWTX_MAX_PLANES_PER_CALL, "planes"))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);

@@ -2794,8 +2794,8 @@ int dwtx_decode_planes_ex(dwtx_ctx *ctx, int32_t *lin, int32_t *pyr, const uint8
 	const unsigned long long *dev_lens, int W, int H, int C, int n, int levels_max, dwtx_decode_info *host_info,
 	int (*done)(void *user, int first, int count, unsigned fused_levels), void *user, dwtx_p16 p16)
 {
-	if (!ctx || !lin || !streams || !dev_lens || !host_info || (C != 1 && C != 3) || n < 1 || n > 65535 / 3 ||
-		(stream_stride & 7) || stream_stride < 64)
+	if (!ctx || !lin || !streams || !dev_lens || !host_info || (C != 1 && C != 3) || n < 1 || (stream_stride & 7) || stream_stride < 64 ||
+		!dwtx_count_ok(n, DWTX_MAX_PLANES_PER_CALL / 3, "streams to decode"))
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
