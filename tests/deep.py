@@ -11,8 +11,10 @@ depth-agnostic stages, each of which is pinned on the reference by tests/test_or
 tests/test_deep_cpu.py checks that the composition equals the whole-file oracle (orc.encode / orc.decode) on 8-bit
 pictures and the reference binary's own bytes (tests/golden/smpte*.dwt).
 
-Also here: seeded integer-only generators of deep pictures, and the linear gain model of the transform that says
-which depths can never need more than the coder's 16 bit planes."""
+Also here: seeded integer-only generators of deep pictures, the pictures, streams and batches of
+tests/test_foreign_depth_gpu.py (deep streams through the 8-bit decoders) with the conditions its inputs must meet, and
+the linear gain model of the transform that says which depths can never need more than the coder's 16 bit planes
+(DESIGN.md section 4.8)."""
 import numpy as np
 
 import orc
@@ -55,18 +57,31 @@ def deep_encode(pix, capacity=0):
     return orc.encode_lin(orc.linearize(orc.forward(a)), W, H, capacity)
 
 
-def deep_decode(data, W, H, C, M, pixels_max=-1, clamp=True):
-    """.dwt bytes (or a prefix) -> uint16 [h, w, C] with the clamps at M, or None where decode.c would exit 1.
-    clamp=False: int64 samples as the arithmetic leaves them, no clamp anywhere."""
+def decoded(data, W, H, C, pixels_max=-1):
+    """.dwt bytes (or a prefix) -> (level, missing, plane counts, int32 [h, w, C]: the inverse transform's output before the
+    colour transform and every clamp — Y, Co, Cg for C == 3), or None where decode.c would exit 1."""
     r = orc.decode_stage(data, W, H, C, pixels_max)
     if r is None:
         return None
     lin, level, missing, planes = r
-    img = orc.inverse(orc.reconstruct(lin, W, H, level + 1, missing))
+    return level, missing, planes, orc.inverse(orc.reconstruct(lin, W, H, level + 1, missing))
+
+
+def to_pixels(img, C, M):
+    """image.h:39-51 and pnm.h:108 with M where they have 255 on the inverse transform's output -> uint16 [h, w, C]."""
+    return (ycocg2rgb(img, M) if C == 3 else np.clip(img, 0, M)).astype(np.uint16)
+
+
+def deep_decode(data, W, H, C, M, pixels_max=-1, clamp=True):
+    """.dwt bytes (or a prefix) -> uint16 [h, w, C] with the clamps at M, or None where decode.c would exit 1.
+    clamp=False: int64 samples as the arithmetic leaves them, no clamp anywhere."""
+    r = decoded(data, W, H, C, pixels_max)
+    if r is None:
+        return None
+    img = r[3]
     if not clamp:
         return ycocg2rgb(img, None) if C == 3 else img.astype(np.int64)
-    out = ycocg2rgb(img, M) if C == 3 else np.clip(img, 0, M)
-    return out.astype(np.uint16)
+    return to_pixels(img, C, M)
 
 
 def levels_max(W, H, pixels_max):
@@ -111,6 +126,191 @@ def blocks(W, H, C, M, seed=0):
     rng = np.random.default_rng(seed)
     bits = rng.integers(0, 2, ((H + 2) // 3, (W + 4) // 5, C), dtype=np.int64)
     return (np.repeat(np.repeat(bits, 3, axis=0), 5, axis=1)[:H, :W] * M).astype(np.uint16)
+
+
+def impulses(W, H, C, V, seed, base=511, share=0.004):
+    """Uniform noise in [0, base] with a `share` of the pixels set to V (of three channels R and B get V and G gets 0,
+    so that Cg carries the impulse as well as Y).  The isolated samples make coefficients of about 2 * V on the finest
+    levels, so V picks the plane count, while most of the picture stays small: an 8-bit decode of such a stream has
+    about half of its samples inside [0, 255] and the rest cut by every clamp.  (Plain deep noise saturates nearly
+    everywhere.)"""
+    rng = np.random.default_rng(seed)
+    pix = rng.integers(0, base + 1, (H, W, C), dtype=np.int64)
+    at = rng.choice(W * H, max(1, round(share * W * H)), replace=False)
+    flat = pix.reshape(W * H, C)
+    flat[at] = (V, 0, V) if C == 3 else (V,)
+    return pix.astype(np.uint16)
+
+
+# The pictures of tests/test_foreign_depth_gpu.py: impulses(W, H, C, V, FOREIGN_SEED) with, per (W, H, C), the largest V
+# that needs 15 bit planes — its largest coefficient is then 32767 in magnitude, the last value an int16 holds — and that
+# V + 6000, which needs 16.  tests/test_deep_cpu.py holds every one of them to what the GPU tests rely on.
+FOREIGN_SEED = 3
+FOREIGN_WIDE = [(132, 72), (516, 260), (1088, 320)]   # W, H: the fused inverse kernels; 1088x320 has five 16-bit ring levels
+FOREIGN_GENERAL = [(131, 77), (64, 48)]               # W % 4 != 0; nothing above the LDS tail
+FOREIGN_V = {(132, 72, 1): 32678, (132, 72, 3): 32217, (516, 260, 1): 26482, (516, 260, 3): 26310, (1088, 320, 1): 26384,
+             (1088, 320, 3): 26029, (131, 77, 1): 32714, (131, 77, 3): 32650, (64, 48, 1): 33067, (64, 48, 3): 32779}
+_foreign = {}
+
+
+def foreign_picture(W, H, C, planes, seed=FOREIGN_SEED):
+    """The 15- or 16-plane picture of a geometry; another seed: 15 planes with room to spare (V = 24000), or 16."""
+    if seed == FOREIGN_SEED:
+        return impulses(W, H, C, FOREIGN_V[W, H, C] + (6000 if planes == 16 else 0), seed)
+    return impulses(W, H, C, 24000 if planes == 15 else 40000, seed)
+
+
+def foreign_stream(W, H, C, planes, seed=FOREIGN_SEED):
+    """-> (.dwt bytes, Stats) of foreign_picture, made once."""
+    key = (W, H, C, planes, seed)
+    if key not in _foreign:
+        _foreign[key] = deep_encode(foreign_picture(W, H, C, planes, seed))
+    return _foreign[key]
+
+
+def foreign_cuts(data):
+    """The two prefixes that still reach the finest level (tests/test_deep_cpu.py), so that the dequantisation bias of
+    decode.c:32-65 is added to coefficients of every size."""
+    return [data[:len(data) * 3 // 4], data[:len(data) // 2]]
+
+
+def level_early_cut(data, W, H, C):
+    """The longest prefix whose decode stops one level short of the whole picture (or earlier)."""
+    key = (data, "early")
+    if key not in _foreign:
+        levels = orc.geometry(W, H).levels
+        lo, hi = 6, len(data)   # (6 bytes are unreadable; the whole stream reaches the last level)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            r = orc.decode_stage(data[:mid], W, H, C)
+            if r is None or r[1] < levels - 1:
+                lo = mid
+            else:
+                hi = mid
+        _foreign[key] = data[:lo]
+    return _foreign[key]
+
+
+REFUSED = "17 planes"   # the name of the row every decoder must answer with status 2
+
+
+def foreign_rows(W, H, C):
+    """[(name, .dwt bytes)]: what no 8-bit picture makes — whole 15- and 16-plane streams, their cuts — beside what one
+    does, and a stream that claims 17 planes."""
+    s15, s16 = foreign_stream(W, H, C, 15)[0], foreign_stream(W, H, C, 16)[0]
+    c15, c16 = foreign_cuts(s15), foreign_cuts(s16)
+    return [("15 planes", s15), ("16 planes", s16), ("15 planes, 3/4", c15[0]), ("16 planes, 3/4", c16[0]),
+            ("15 planes, 1/2", c15[1]), ("16 planes, 1/2", c16[1]), ("15 planes, a level early", level_early_cut(s15, W, H, C)),
+            ("8-bit picture", orc.encode(orc.synth(W, H, C, 7, 0))[0]), (REFUSED, orc.many_plane_stream(W, H, C, [17, 3, 3]))]
+
+
+def foreign_clean_rows(W, H, C):
+    """Six rows that every decoder part takes whole and with at most 15 planes, so that the 16-bit ring planes carry
+    them wherever the shape has any: the stream that reaches 32767, its two cuts, an 8-bit picture's and two more seeds."""
+    s15 = foreign_stream(W, H, C, 15)[0]
+    c15 = foreign_cuts(s15)
+    return [("15 planes", s15), ("15 planes, 3/4", c15[0]), ("15 planes, 1/2", c15[1]), ("8-bit picture", orc.encode(orc.synth(W, H, C, 7, 0))[0]),
+            ("15 planes, seed 11", foreign_stream(W, H, C, 15, 11)[0]), ("15 planes, seed 12", foreign_stream(W, H, C, 15, 12)[0])]
+
+
+def decoder_parts(n, K=0):
+    """The ranges of rows dwtx_decode_planes_ex cuts a batch of n into under DWTX_OPT_DECODE_PARTS = K (0: automatic;
+    K = 1 stands for DWTX_OPT_ONE_STREAM): unpack.hip, "Parts"."""
+    if n < 4 or K == 1:
+        K = 1
+    elif K == 0:
+        K = 4 if n >= 24 else 2
+    K = min(max(K, 1), 4)
+    return [range(n * k // K, n * (k + 1) // K) for k in range(K)]
+
+
+def clean_parts(rows, W, H, C, K=0):
+    """The parts of a batch (decoder_parts) that scatter() of unpack.hip sends through the 16-bit ring planes: every row
+    readable, decoded to the last level, and none with more than 15 planes."""
+    levels = orc.geometry(W, H).levels
+
+    def clean(row):
+        key = (row[1], "clean")
+        if key not in _foreign:
+            r = None if row[0] == REFUSED else orc.decode_stage(row[1], W, H, C)
+            _foreign[key] = r is not None and r[1] == levels - 1 and max(r[3]) <= 15
+        return _foreign[key]
+    flags = [clean(row) for row in rows]
+    return [p for p in decoder_parts(len(rows), K) if all(flags[i] for i in p)]
+
+
+def levels16(W, H):
+    """The mask of ring levels that dwtx_transformation_fwd_pixels reports as 16-bit for a W x H picture (lift.hip,
+    dwtx_levels16 over linearize.hip's dwtx_square_levels), restated: from the finest level down, at most five, while
+    the step is above the 64 x 64 LDS tail, its width a multiple of 4 and the level's Hilbert square at least 64 wide.
+    tests/test_foreign_depth_gpu.py compares it with what the library reports."""
+    g = orc.geometry(W, H)
+    if W % 4:
+        return 0
+    mask, w, h = 0, W, H
+    for t in range(min(5, g.levels)):
+        l = g.levels - 1 - t
+        if (w <= 64 and h <= 64) or w % 4 or g.lengths[l + 1] < 64:
+            break
+        mask |= 1 << l
+        w, h = (w + 1) >> 1, (h + 1) >> 1
+    return mask
+
+
+def ring_level_tops(pic):
+    """The largest |coefficient| of a picture on every ring level, finest last (the oracle's linearised planes)."""
+    H, W, C = pic.shape
+    g = orc.geometry(W, H)
+    lin = np.abs(orc.linearize(orc.forward(rgb2ycocg(pic) if C == 3 else pic.astype(np.int32))))
+    return [int(lin[:, g.pixels[l]:g.pixels[l + 1]].max()) for l in range(g.levels)]
+
+
+FOREIGN_BATCH_16 = 5   # where the 16-plane stream of foreign_batch stands
+
+
+def foreign_batch(W, H, C):
+    """Twelve rows around one 16-plane stream.  The decoder cuts a batch of n into K parts [n*k/K, n*(k+1)/K) and asks
+    of each part whether any of its streams has more than 15 planes: at index 5 the 16-plane stream shares a part with
+    rows 0-4 (K = 2), with 4, 6 and 7 (K = 3), with 3 and 4 (K = 4) and with all (K = 1).  The refused row stands in the
+    first part of every K, so the rows from 6 on (K = 2), 8 on (K = 3) and 6 on (K = 4) are parts of whole streams of at most
+    15 planes, which take the 16-bit planes beside the part that may not; the stream whose coefficients reach 32767 is
+    row 9, in such a part for every K above 1 (clean_parts; tests/test_deep_cpu.py)."""
+    w15 = lambda seed: foreign_stream(W, H, C, 15, seed)[0]   # noqa: E731
+    s15, s16 = foreign_stream(W, H, C, 15)[0], foreign_stream(W, H, C, 16)[0]
+    rows = [("15 planes, seed 11", w15(11)), ("8-bit picture", orc.encode(orc.synth(W, H, C, 8, 1))[0]), (REFUSED, orc.many_plane_stream(W, H, C, [17, 3, 3])),
+            ("15 planes, seed 14", w15(14)), ("15 planes, seed 12", w15(12)), ("16 planes", s16), ("15 planes, seed 13", w15(13)),
+            ("8-bit picture", orc.encode(orc.synth(W, H, C, 9, 0))[0]), ("15 planes, 1/2", foreign_cuts(s15)[1]), ("15 planes", s15),
+            ("15 planes, 3/4", foreign_cuts(s15)[0]), ("15 planes, seed 15", w15(15))]
+    assert rows[FOREIGN_BATCH_16][0] == "16 planes"
+    return rows
+
+
+FOREIGN_BATCH_SHAPES = [(132, 72, 1), (132, 72, 3), (516, 260, 3), (1088, 320, 3)]   # W, H, C of the batches
+FOREIGN_SEEDS = (FOREIGN_SEED, 11, 12, 13, 14, 15)
+
+
+def foreign_uniform(W, H, C, planes):
+    """Six whole streams that all need `planes` bit planes."""
+    return [("%d planes, seed %d" % (planes, s), foreign_stream(W, H, C, planes, s)[0]) for s in FOREIGN_SEEDS]
+
+
+def clamp_shares(img, C):
+    """What the clamps of image.h:39-51 / pnm.h:108 at 255 find in an inverse transform's output [..., C] (int, before
+    any clamp): (share of the final samples inside [0, 255], [share of Y outside [0, 255], of Co and of Cg outside
+    [-255, 255]]) — the list is empty for gray."""
+    a = img.astype(np.int64)
+    if C == 1:
+        return float(((a >= 0) & (a <= 255)).mean()), []
+    out = ycocg2rgb(a, None)
+    return (float(((out >= 0) & (out <= 255)).mean()),
+            [float(((a[..., 0] < 0) | (a[..., 0] > 255)).mean())] + [float((np.abs(a[..., c]) > 255).mean()) for c in (1, 2)])
+
+
+def clamps_are_at_work(img, C):
+    """The condition every 8-bit clamp test here asserts of its input: between 25 % and 75 % of the samples end inside
+    [0, 255], and each of Y, Co and Cg leaves its clamp on 10 % to 90 % of the samples."""
+    inside, outside = clamp_shares(img, C)
+    return 0.25 <= inside <= 0.75 and all(0.10 <= s <= 0.90 for s in outside)
 
 
 # ---- the transform's gain ----------------------------------------------------------------------------------------

@@ -101,6 +101,18 @@ def test_without_the_variables_both_behave_as_before(tmp_path):
         assert run(DEC, dwt, pnm, env={"DWTX_MAXVAL": bad}).returncode == 1
 
 
+def test_decode_without_maxval_clamps_a_15_plane_stream_at_255(tmp_path):
+    """The documented use at a size where it matters: 132x72 RGB takes the fused inverse kernel and the 16-bit ring planes,
+    the stream's coefficients reach 32767 and the clamps cut about half of the samples (tests/test_deep_cpu.py)."""
+    W, H, Cn = 132, 72, 3
+    data = deep.foreign_stream(W, H, Cn, 15)[0]
+    dwt, pnm = str(tmp_path / "a.dwt"), str(tmp_path / "o.pnm")
+    open(dwt, "wb").write(data)
+    r = run(DEC, dwt, pnm)
+    assert r.returncode == 0, r.stderr
+    assert open(pnm, "rb").read().startswith(b"P6 132 72 255\n") and (orc.read_pnm(pnm) == orc.decode(data)).all()
+
+
 def test_a_picture_with_too_many_planes_is_refused(tmp_path):
     src, dwt = str(tmp_path / "i.pnm"), str(tmp_path / "a.dwt")
     open(src, "wb").write(pnm16(deep.noise(128, 96, 3, 65535, 1), 65535))

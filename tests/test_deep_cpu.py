@@ -133,3 +133,109 @@ def test_deep_entry_points_are_declared_typed_and_exported():
     for m in ("planes_from_pixels16", "pixels16_from_planes", "transformation_fwd_pixels16", "transformation_inv_pixels16",
               "encode16", "decode16", "encode_device16", "decode_device16"):
         assert callable(getattr(dwt_amd.Context, m))
+
+
+# ---- the streams no 8-bit picture makes (tests/test_foreign_depth_gpu.py) -----------------------------------------
+
+FOREIGN = [(W, H, C) for W, H in deep.FOREIGN_WIDE + deep.FOREIGN_GENERAL for C in (1, 3)]
+_checked = {}
+
+
+def _plane_max(st, C):
+    return max(list(st.planes)[:C])
+
+
+def _decoded(row, W, H, C):
+    """One row through both oracles, once: orc.decode must equal deep.deep_decode(row, W, H, C, 255), which is to_pixels of
+    decoded (tests/deep.py).  -> decoded's (level, missing, plane counts, Y / Co / Cg before the clamps)"""
+    if row not in _checked:
+        r = deep.decoded(row, W, H, C)
+        composed, ref = deep.to_pixels(r[3], C, 255), orc.decode(row)
+        assert ref is not None and ref.shape == composed.shape and (ref == composed).all()
+        _checked[row] = r
+    return _checked[row]
+
+
+def _the_32767_stream_is_in(part, rows, W, H, C):
+    return any(rows[i][1] == deep.foreign_stream(W, H, C, 15)[0] for i in part)
+
+
+@pytest.mark.parametrize("whc", FOREIGN, ids=lambda v: "%dx%dx%d" % v)
+def test_foreign_depth_pictures_are_what_the_gpu_tests_take_them_for(whc):
+    """Without these conditions the 8-bit decode tests of deep streams could pass for the wrong reason.
+    Plane count: exactly 15 and 16.  Size: the 15-plane picture's largest coefficient is 32767 in magnitude, the last value
+    an int16 holds, and it lies on the finest ring level — a 16-bit one wherever the shape has any; the other 16-bit levels
+    of 1088x320 hold more than the 11 bits of an 8-bit source as well.  Clamp shares: in the 8-bit decode of the whole streams
+    and of the two cuts, which still reach the finest level, 25 % to 75 % of the samples end inside [0, 255] and Y, Co and Cg
+    each leave their clamp on 10 % to 90 % of them.  Oracle agreement: orc.decode equals the composed deep_decode(..., 255)
+    on every row.  Parts: the clean batch goes through the 16-bit planes in every part, the 32767 stream among them; the
+    mixed nine rows in none (a 16-plane stream in one part, an early cut and the refused row in the other)."""
+    W, H, C = whc
+    g = orc.geometry(W, H)
+    mask = deep.levels16(W, H)
+    assert (mask != 0) == ((W, H) in deep.FOREIGN_WIDE)
+    for planes in (15, 16):
+        pic = deep.foreign_picture(W, H, C, planes)
+        data, st = deep.foreign_stream(W, H, C, planes)
+        assert _plane_max(st, C) == planes
+        tops = deep.ring_level_tops(pic)
+        print(f"{W}x{H}x{C} {planes} planes: V {int(pic.max())}, largest |coefficient| per ring level {tops}, {len(data)} bytes")
+        if planes == 15:
+            assert max(tops) == tops[-1] == 32767
+            assert all(tops[l] > 2047 for l in range(g.levels) if (mask >> l) & 1 and l >= 2)
+        else:
+            assert 1 << 15 <= max(tops) < 1 << 16
+        for row in [data] + deep.foreign_cuts(data):
+            level, missing, _, img = _decoded(row, W, H, C)
+            inside, outside = deep.clamp_shares(img, C)
+            print(f"  {len(row)} bytes: level {level}, max(missing) {int(missing.max())}, inside {inside:.3f}, outside {outside}")
+            assert level == g.levels - 1 and img.shape == (H, W, C)
+            assert (len(row) == len(data)) == (int(missing.max()) == 0)
+            assert deep.clamps_are_at_work(img, C)
+    rows = deep.foreign_rows(W, H, C)
+    assert len(rows) == 9 and len({r for _, r in rows}) == 9
+    for name, row in rows:
+        if name != deep.REFUSED:
+            level = _decoded(row, W, H, C)[0]
+            assert (level < g.levels - 1) == (name == "15 planes, a level early"), name
+    assert deep.clean_parts(rows, W, H, C) == []
+    clean = deep.foreign_clean_rows(W, H, C)
+    for name, row in clean:
+        level, _, planes, img = _decoded(row, W, H, C)
+        assert level == g.levels - 1 and max(planes) == (15 if name[:2] == "15" else max(planes)) and max(planes) <= 15, name
+        assert name == "8-bit picture" or deep.clamps_are_at_work(img, C), name
+    parts = deep.decoder_parts(len(clean))
+    assert len(parts) == 2 and deep.clean_parts(clean, W, H, C) == parts and _the_32767_stream_is_in(parts[0], clean, W, H, C)
+
+
+@pytest.mark.parametrize("whc", deep.FOREIGN_BATCH_SHAPES, ids=lambda v: "%dx%dx%d" % v)
+def test_foreign_depth_batches_are_what_the_gpu_tests_take_them_for(whc):
+    """The pictures of the other seeds: plane counts, clamp shares and oracle agreement as above.  The mixed batch has its
+    16-plane stream where the parts of 2, 3 and 4 give it different neighbours, and for each of those cuts a part that goes
+    through the 16-bit planes and holds the 32767 stream; as one part it has none.  Every part of the uniform 15-plane batch
+    goes through them, no part of the 16-plane one."""
+    W, H, C = whc
+    for planes in (15, 16):
+        rows = deep.foreign_uniform(W, H, C, planes)
+        for name, row in rows:
+            _, _, counts, img = _decoded(row, W, H, C)
+            assert max(counts) == planes, name
+            assert deep.clamps_are_at_work(img, C), name
+        for K in (0, 3):
+            parts = deep.decoder_parts(len(rows), K)
+            assert len(parts) == (K or 2)
+            assert deep.clean_parts(rows, W, H, C, K) == (parts if planes == 15 else []), (planes, K)
+            assert planes == 16 or any(_the_32767_stream_is_in(p, rows, W, H, C) for p in parts)
+    rows = deep.foreign_batch(W, H, C)
+    n, at = len(rows), deep.FOREIGN_BATCH_16
+    assert n == 12 and deep.decoder_parts(n, 0) == deep.decoder_parts(n, 2)
+    for K, mates in ((1, set(range(12)) - {5}), (2, {0, 1, 2, 3, 4}), (3, {4, 6, 7}), (4, {3, 4})):
+        parts = deep.decoder_parts(n, K)
+        mine = [set(p) for p in parts if at in p]
+        assert len(parts) == K and len(mine) == 1 and mine[0] - {at} == mates, K
+        clean = deep.clean_parts(rows, W, H, C, K)
+        assert (len(clean) >= 1) == (K > 1), K
+        assert K == 1 or any(_the_32767_stream_is_in(p, rows, W, H, C) for p in clean), K
+    for name, row in rows:
+        if name != deep.REFUSED:
+            _decoded(row, W, H, C)

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import deep
 import orc
 
 pytestmark = pytest.mark.gpu
@@ -133,6 +134,103 @@ def test_pixel_transforms_as_the_pipelines_run_them(ctx, shape, rings16):
     assert (got == want).all()
     back = ctx.transformation_inv_pixels(pyr, r16, mask, Cn)
     assert torch.equal(back, t)
+
+
+def ring_bands(g, l):
+    """(rows, columns) of the three detail bands of ring level l in a pyramid plane: HL, LH, HH"""
+    w0, h0, w1, h1 = g.widths[l], g.heights[l], g.widths[l + 1], g.heights[l + 1]
+    return [((0, h0), (w0, w1)), ((h0, h1), (0, w0)), ((h0, h1), (w0, w1))]
+
+
+def arbitrary_pyramid(rng, P, H, W, Cn, mask):
+    """-> (int32 pyramid [P,H,W], int16 ring planes [P,H,W] or None, the merged pyramid): coefficients no transform made.
+    Uniform in +-150 (gray, Y) or +-400 (Co, Cg) with one in two thousand anywhere in +-2^20 (int32) or in all of int16 (the ring levels in `mask`, which
+    the int32 array then does not hold: it has a sentinel there), 128 added to the root band of gray / Y — so that about half
+    of the inverse's samples fall inside [0, 255] and the rest leave it on either side.  Every band of a 16-bit ring has
+    -32768 and 32767 in its corners and in the middle of its first and last row and column."""
+    g = orc.geometry(W, H)
+    amp = np.array([150 if p % Cn == 0 else 400 for p in range(P)], dtype=np.int32)[:, None, None]   # gray / Y; Co, Cg
+    pyr = rng.integers(-1000, 1001, size=(P, H, W), dtype=np.int32) * amp // 1000
+    rare = rng.random((P, H, W)) < 0.0005
+    pyr[rare] = rng.integers(-(1 << 20), (1 << 20) + 1, size=int(rare.sum()), dtype=np.int32)
+    pyr[::Cn, :g.heights[0], :g.widths[0]] += 128
+    if not mask:
+        return pyr, None, pyr
+    r16 = (rng.integers(-1000, 1001, size=(P, H, W), dtype=np.int32) * amp // 1000).astype(np.int16)
+    r16[rare] = rng.integers(-32768, 32768, size=int(rare.sum()), dtype=np.int16)
+    for l in range(g.levels):
+        if (mask >> l) & 1:
+            for k, ((y0, y1), (x0, x1)) in enumerate(ring_bands(g, l)):
+                pyr[:, y0:y1, x0:x1] = -(1 << 30)   # not read
+                ys, xs = (y0, (y0 + y1) // 2, y1 - 1), (x0, (x0 + x1) // 2, x1 - 1)
+                edge = [(y, x) for y in ys for x in xs if y != ys[1] or x != xs[1]]
+                for i, (y, x) in enumerate(edge):
+                    r16[:, y, x] = 32767 if (i + k) & 1 else -32768
+    return pyr, r16, merge_rings(pyr, r16, mask, W, H)
+
+
+def popcount(v):
+    return bin(v).count("1")
+
+
+INV_PIXELS_SHAPES = [(72, 132, 1), (72, 132, 3), (260, 516, 1), (260, 516, 3), (1024, 1024, 1), (320, 1088, 1), (320, 1088, 3)]
+
+
+@pytest.mark.parametrize("shape", INV_PIXELS_SHAPES)
+@pytest.mark.parametrize("rings16", [False, True], ids=["int32", "rings16"])
+def test_inverse_to_8_bit_pixels_of_arbitrary_pyramids(ctx, shape, rings16):
+    """dwtx_transformation_inv_pixels on pyramids that no 8-bit picture makes: the clamps of the fused kernels (image.h:39-51,
+    pnm.h:108 — Y to [0,255], Co and Cg to [-255,255], then R, G, B to [0,255]) cut about half of the samples, which the
+    test asserts of its own input, and the 16-bit rings hold all of int16.  72x132: one wide level above the LDS tail;
+    1024x1024: four 16-bit ring levels, two two-level passes; 320x1088: five of its six ring levels are 16-bit, so
+    k_inv2_level_w* reads 16-bit rings on both of its levels and the step below them an int32 ring.  Everything in int32
+    (no ring planes) and with the rings of the reported mask in int16; against orc.inverse of the merged pyramid and numpy's
+    colour transform and clamps."""
+    import torch
+
+    H, W, Cn = shape
+    n = 2
+    g = orc.geometry(W, H)
+    reported = ctx.transformation_fwd_pixels(torch.zeros((1, H, W, Cn), dtype=torch.uint8, device=ctx.device))[2]
+    assert reported & (1 << (g.levels - 1))
+    assert popcount(reported) == {1024: 4, 1088: 5}.get(W, 1)
+    if W == 1088:
+        assert g.levels == 6 and not reported & 1   # ring level 0 stays int32: the boundary is inside the picture
+    mask = reported if rings16 else 0
+    pyr, r16, merged = arbitrary_pyramid(np.random.default_rng(H + W + Cn), n * Cn, H, W, Cn, mask)
+    assert np.abs(merged).max() <= 1 << 20
+    if rings16:
+        assert r16.min() == -32768 and r16.max() == 32767
+    inv = [orc.inverse(np.moveaxis(merged[i * Cn:(i + 1) * Cn], 0, 2)) for i in range(n)]
+    for a in inv:
+        print(shape, "mask 0x%x" % mask, "inside, outside:", deep.clamp_shares(a, Cn))
+        assert deep.clamps_are_at_work(a, Cn)
+    want = np.stack([deep.ycocg2rgb(a, 255) if Cn == 3 else np.clip(a, 0, 255) for a in inv]).astype(np.uint8)
+    got = ctx.transformation_inv_pixels(torch.from_numpy(pyr).to(ctx.device), torch.from_numpy(r16).to(ctx.device) if rings16 else None,
+                                        mask, Cn)
+    assert (got.cpu().numpy() == want).all()
+
+
+@pytest.mark.parametrize("shape", [(53, 37, 1), (77, 131, 3), (100, 258, 3), (66, 1030, 1), (9, 10, 3)])
+def test_8_bit_pixels_from_planes_that_the_clamps_cut(ctx, shape):
+    """dwtx_pixels_from_planes (k_pixels_from_planes<uint8_t>) on planes in about +-2000, widths that are no multiple of 4:
+    most of gray / Y in [-150, 400] and of Co, Cg in [-400, 400], one sample in seven anywhere in +-2000."""
+    import torch
+
+    H, W, Cn = shape
+    n = 2
+    rng = np.random.default_rng(H * W + Cn)
+    a = rng.integers(-400, 401, size=(n, H, W, Cn), dtype=np.int32)
+    a[..., 0] = rng.integers(-150, 401, size=(n, H, W), dtype=np.int32)
+    far = rng.random(a.shape) < 1 / 7
+    a[far] = rng.integers(-2000, 2001, size=int(far.sum()), dtype=np.int32)
+    assert W % 4 != 0
+    for img in a:
+        print(shape, "inside, outside:", deep.clamp_shares(img, Cn))
+        assert deep.clamps_are_at_work(img, Cn)
+    want = np.stack([deep.ycocg2rgb(img, 255) if Cn == 3 else np.clip(img, 0, 255) for img in a]).astype(np.uint8)
+    planes = torch.from_numpy(np.ascontiguousarray(a.transpose(0, 3, 1, 2)).reshape(n * Cn, H, W)).to(ctx.device)
+    assert (ctx.pixels_from_planes(planes, Cn).cpu().numpy() == want).all()
 
 
 def test_pixel_transforms_refuse_shapes_their_kernels_do_not_take(ctx):
