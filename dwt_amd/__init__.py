@@ -12,7 +12,7 @@ import ctypes as C
 from . import _lib
 from ._lib import Geom, Stats, StreamInfo, DecodeInfo, Index, SegIndex, View, TileGroup, INDEX_MAGIC, INDEX_MAX_SEGS, LIB_PATH  # noqa: F401
 
-__all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "tile_groups", "view_fields", "Geom", "Stats", "View",
+__all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "tile_groups", "view_fields", "view_order", "Geom", "Stats", "View",
            "TileGroup"]
 
 
@@ -50,6 +50,17 @@ def tile_groups(W, H, tile):
     if k < 0:
         raise DwtxError(k, "dwtx_tile_groups")
     return [TileGroup.from_buffer_copy(bytes(out[i])) for i in range(k)]
+
+
+ORDERS = {"rgb": 0, "bgr": 1}   # enum DWTX_ORDER_* (include/dwtx.h)
+
+
+def view_order(order):
+    """The `order` keyword of encode_view / decode_view -> DWTX_ORDER_*: "rgb", or "bgr" for pixels (or planes) that lie as
+    B, G, R.  Anything else is a ValueError — raised here, before any device call."""
+    if not isinstance(order, str) or order not in ORDERS:
+        raise ValueError(f"order {order!r}: a view's channels lie as 'rgb' or as 'bgr'")
+    return ORDERS[order]
 
 
 def view_fields(shape, strides, stepped=False):
@@ -501,11 +512,14 @@ class Context:
                  f["channel_stride"])
         return v, f["W"], f["H"], f["channels"], f["n"], f["pixel_step"]
 
-    def encode_view(self, t, capacity=0, out=None, info=None, stepped=False):
+    def encode_view(self, t, capacity=0, out=None, info=None, stepped=False, order="rgb"):
         """dwtx_encode_view: the windows of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (a slice, a crop, a
         grid of tiles, a channel-first batch permuted to channel-last: see _view) -> (streams uint8 [n,stride], info uint8
         [n,sizeof(StreamInfo)]) on device, as encode_device / encode_device16 give for the contiguous copy; async.
-        stepped=True: dwtx_encode_view_step — `rgba[..., :3]`, `rgba[..., 3:]` and `uv[:, :, 0::2]` are views as they lie."""
+        stepped=True: dwtx_encode_view_step — `rgba[..., :3]`, `rgba[..., 3:]` and `uv[:, :, 0::2]` are views as they lie.
+        order="bgr": dwtx_encode_view_order — the channels lie as B, G, R (`bgra[..., :3]` with stepped=True, an OpenCV
+        frame, planar B, G, R planes); the streams are those of the R, G, B picture."""
+        order = view_order(order)
         torch = self.torch
         v, W, H, Cn, n, step = self._view(t, None, stepped)
         bound = self.lib.dwtx_encode_bound16 if v.sample_bytes == 2 else self.lib.dwtx_encode_bound
@@ -514,25 +528,33 @@ class Context:
             out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         if info is None:
             info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
-        if stepped:
+        if order:
+            _check(self.lib.dwtx_encode_view_order(self.h, C.byref(v), step, order, W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
+                   "dwtx_encode_view_order")
+        elif stepped:
             _check(self.lib.dwtx_encode_view_step(self.h, C.byref(v), step, W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
                    "dwtx_encode_view_step")
         else:
             _check(self.lib.dwtx_encode_view(self.h, C.byref(v), W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view")
         return out, info
 
-    def decode_view(self, streams, lens, into, maxval=None, levels_max=-1, stepped=False):
+    def decode_view(self, streams, lens, into, maxval=None, levels_max=-1, stepped=False, order="rgb"):
         """dwtx_decode_view: device streams [n,stride] + int64 lens -> the windows of the strided device tensor `into`
         ([n,H,W,C] or [bands,cols,H,W,C]), each picture in its window's top-left corner at the size its stream supports;
         nothing else of `into`'s storage is written.  maxval: the deep pictures' (default 65535).  Returns the list of
         DecodeInfo; syncs once.  stepped=True: dwtx_decode_view_step, for the tensors encode_view takes with it; the
-        samples between the pixels (an RGBA surface's alpha) are not written either."""
+        samples between the pixels (an RGBA surface's alpha) are not written either.  order="bgr": dwtx_decode_view_order —
+        R and B are written at each other's places."""
+        order = view_order(order)
         torch = self.torch
         v, W, H, Cn, n, step = self._view(into, maxval, stepped)
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
         assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
         infos = (DecodeInfo * n)()
-        if stepped:
+        if order:
+            _check(self.lib.dwtx_decode_view_order(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step,
+                                                   order, C.cast(infos, C.c_void_p)), "dwtx_decode_view_order")
+        elif stepped:
             _check(self.lib.dwtx_decode_view_step(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step,
                                                   C.cast(infos, C.c_void_p)), "dwtx_decode_view_step")
         else:

@@ -137,6 +137,8 @@ SYMBOLS = {
     "dwtx_decode_view": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _vp]),
     "dwtx_encode_view_step": (_i, [_vp, C.POINTER(View), _sz, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
     "dwtx_decode_view_step": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _vp]),
+    "dwtx_encode_view_order": (_i, [_vp, C.POINTER(View), _sz, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
+    "dwtx_decode_view_order": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, _vp]),
     "dwtx_tile_groups": (_i, [_i, _i, _i, C.POINTER(TileGroup)]),
     "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }

@@ -367,8 +367,13 @@ extern "C" int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, s
 // dwtx_view -> dwtx_pixels for n windows of W x H, checked; `dst`: the view will be written (maxval, disjoint windows).
 // pixel_step (the *_view_step calls; the plain ones pass 0): samples from a pixel to the next one of its row; 0 and
 // `channels` are both the dense case and leave px->pixel_step 0, so that everything downstream is the plain call's.
-static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int W, int H, int n, bool dst, dwtx_pixels *px)
+// order (the *_view_order calls; the others pass DWTX_ORDER_RGB): kept for RGB views and checked first, nothing else here looks at it.
+static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, dwtx_pixels *px)
 {
+	if (order != DWTX_ORDER_RGB && order != DWTX_ORDER_BGR) {
+		dwtx_set_error("view: channel order %d (DWTX_ORDER_RGB = 0 or DWTX_ORDER_BGR = 1)", order);
+		return DWTX_ERR_ARG;
+	}
 	if (!v || !v->dev || n < 1) {
 		dwtx_set_error("no view, no pixels or no windows");
 		return DWTX_ERR_ARG;
@@ -437,6 +442,7 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int W, int H, i
 	px->row_pitch = v->row_pitch;
 	px->channel_stride = cs;
 	px->pixel_step = step;
+	px->order = v->channels == 3 ? order : DWTX_ORDER_RGB;
 	if (bands) {
 		px->cols = (int)cols;
 		px->band_stride = v->band_stride;
@@ -448,7 +454,7 @@ extern "C" int dwtx_encode_view(dwtx_ctx *ctx, const dwtx_view *src, int W, int 
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
 {
 	dwtx_pixels px;
-	if (const int rc = pixels_of_view(src, 0, W, H, n, false, &px))
+	if (const int rc = pixels_of_view(src, 0, DWTX_ORDER_RGB, W, H, n, false, &px))
 		return rc;
 	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
 }
@@ -457,7 +463,7 @@ extern "C" int dwtx_encode_view_step(dwtx_ctx *ctx, const dwtx_view *src, size_t
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
 {
 	dwtx_pixels px;
-	if (const int rc = pixels_of_view(src, pixel_step, W, H, n, false, &px))
+	if (const int rc = pixels_of_view(src, pixel_step, DWTX_ORDER_RGB, W, H, n, false, &px))
 		return rc;
 	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
 }
@@ -466,7 +472,7 @@ extern "C" int dwtx_decode_view(dwtx_ctx *ctx, const uint8_t *dev_streams, size_
 	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, dwtx_decode_info *host_info)
 {
 	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, 0, W, H, n, true, &px))
+	if (const int rc = pixels_of_view(dst, 0, DWTX_ORDER_RGB, W, H, n, true, &px))
 		return rc;
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
 }
@@ -475,7 +481,26 @@ extern "C" int dwtx_decode_view_step(dwtx_ctx *ctx, const uint8_t *dev_streams, 
 	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, dwtx_decode_info *host_info)
 {
 	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, pixel_step, W, H, n, true, &px))
+	if (const int rc = pixels_of_view(dst, pixel_step, DWTX_ORDER_RGB, W, H, n, true, &px))
+		return rc;
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
+}
+
+extern "C" int dwtx_encode_view_order(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, int W, int H, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	dwtx_pixels px;
+	if (const int rc = pixels_of_view(src, pixel_step, order, W, H, n, false, &px))
+		return rc;
+	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
+}
+
+extern "C" int dwtx_decode_view_order(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
+	dwtx_decode_info *host_info)
+{
+	dwtx_pixels px;
+	if (const int rc = pixels_of_view(dst, pixel_step, order, W, H, n, true, &px))
 		return rc;
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
 }

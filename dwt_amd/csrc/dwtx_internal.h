@@ -184,6 +184,9 @@ template <class F> char *carve(dwtx_ctx *ctx, int slot, F &&fn)
 // Interleaved and gray pixels may lie further apart than their own samples (pixel_step, the *_view_step calls only): the
 // RGB of an RGBA surface, its alpha, one plane of a mosaic — what lies between a pixel's samples and the next pixel is
 // never written, and read only by lift.hip's Rgbx8 source (the fourth byte of a window's own 4-byte pixels, never used).
+// The three channels may lie as B, G, R (order, the *_view_order calls only): base and every stride stay what they are — base
+// is the lowest-addressed channel's first sample — and only lift.hip's last step to the kernels (red(), colour_stride())
+// knows: no check and no choice of path looks at the order.
 struct dwtx_pixels {
 	void *base;            // the grid's window 0, first sample
 	int sample_bytes;      // 1 or 2
@@ -196,6 +199,7 @@ struct dwtx_pixels {
 	size_t first = 0;      // the view's first window in the grid (parts of a batch start anywhere in it)
 	size_t channel_stride = 0;   // 0: interleaved; else planar RGB: from a window's plane of one channel to the next one's (image() and moved() keep it)
 	size_t pixel_step = 0;       // 0: dense (a pixel is its channels); else from a pixel to the next one of its row, above channels (image() and moved() keep it)
+	int order = DWTX_ORDER_RGB;  // which colour the three channels are as they lie (DWTX_ORDER_*; image() and moved() keep it); gray pixels have none
 
 	bool deep() const { return sample_bytes == 2; }
 	size_t bytes(size_t samples) const { return samples * (size_t)sample_bytes; }
@@ -207,6 +211,16 @@ struct dwtx_pixels {
 	bool one_band() const { return cols == 0; }
 	bool planar() const { return channel_stride != 0; }
 	bool stepped() const { return pixel_step != 0; }
+	bool bgr() const { return order == DWTX_ORDER_BGR && channels == 3; }
+	// The colours of a pixel for kernels that walk R, G, B through a signed stride (planar pixels, and the general
+	// conversions' interleaved ones): from a colour's sample to the next colour's, and the R sample of the grid's first pixel —
+	// B, G, R pixels are walked down from their highest-addressed channel
+	long colour_stride() const
+	{
+		const long cs = planar() ? (long)channel_stride : 1L;
+		return bgr() ? -cs : cs;
+	}
+	void *red() const { return bgr() ? at(2 * (planar() ? channel_stride : (size_t)1)) : base; }
 	// from a pixel to the next one of its row
 	size_t step() const { return planar() ? 1 : pixel_step ? pixel_step : (size_t)channels; }
 	// 8-bit RGB in 4-byte pixels (RGBA / RGBX surfaces): the one stepped layout lift.hip's wide kernels take

@@ -294,7 +294,8 @@ struct LevelArgsW {
 	int nquads;       // w / 4
 	int wx_log2;      // forward: 1 << wx_log2 waves of a block side by side
 	HistArgs hist;
-	long cstride;     // planar RGB pixels behind src8 / dst8 (dwtx_pixels::channel_stride, in samples): from a window's plane to its next; 0: interleaved.
+	long cstride;     // planar RGB pixels behind src8 / dst8 (dwtx_pixels::colour_stride(), in samples): from a window's R plane to its G plane, from G to B — negative
+	                  // where the planes lie as B, G, R (src8 / dst8 is then the R plane all the same); 0: interleaved.
 	                  // (Last, so that the interleaved kernels find their arguments where they were.)
 };
 
@@ -577,6 +578,16 @@ __device__ __forceinline__ int ycocg_ch(int r, int g, int b, int ch)   // image.
 	return ch == 2 ? cg : t + tdiv2(cg);
 }
 
+// The colour transform on a pixel's three samples AS THEY LIE (s0 the lowest-addressed): R, G, B, or — BGR, dwtx_pixels::order —
+// B, G, R, where the triple handed on takes R from the third sample and B from the first.  Which is which is decided when
+// the kernel is compiled: the interleaved sources below exist once per order, and the two differ in no instruction but
+// the operands of the transform.  (Planar pixels need none of it: the host hands their kernels the R plane and a negative stride.)
+template <bool BGR>
+__device__ __forceinline__ int ycocg_lies(int s0, int s1, int s2, int ch)
+{
+	return BGR ? ycocg_ch(s2, s1, s0, ch) : ycocg_ch(s0, s1, s2, ch);
+}
+
 // Interleaved RGB16: a lane's four pixels are 24 bytes (three 8-byte loads; rows of W % 4 == 0 pixels are multiples of
 // 24 bytes, so they stay 8-byte aligned), the neighbours' pixels three words: lane 0 pixels 4q-2 and 4q-1, the other lanes
 // pixel 4q+4 in the first three samples.  Every plane's launch takes its own channel of image.h:52-65 when the row is used.
@@ -591,17 +602,18 @@ __device__ __forceinline__ FwdRawRgb16 hold(const FwdRawRgb16 &r)
 	return o;
 }
 
+template <bool BGR = false>
 __device__ __forceinline__ FwdRaw widen(const FwdRawRgb16 &r, int ch)
 {
 	auto lo = [](unsigned w) { return (int)(w & 0xffffu); };
 	auto hi = [](unsigned w) { return (int)(w >> 16); };
 	FwdRaw o;
-	o.x.x = ycocg_ch(lo(r.a.x), hi(r.a.x), lo(r.a.y), ch);
-	o.x.y = ycocg_ch(hi(r.a.y), lo(r.b.x), hi(r.b.x), ch);
-	o.x.z = ycocg_ch(lo(r.b.y), hi(r.b.y), lo(r.c.x), ch);
-	o.x.w = ycocg_ch(hi(r.c.x), lo(r.c.y), hi(r.c.y), ch);
-	o.xr = ycocg_ch(lo(r.e0), hi(r.e0), lo(r.e1), ch);
-	o.left = make_int2(o.xr, ycocg_ch(hi(r.e1), lo(r.e2), hi(r.e2), ch));
+	o.x.x = ycocg_lies<BGR>(lo(r.a.x), hi(r.a.x), lo(r.a.y), ch);
+	o.x.y = ycocg_lies<BGR>(hi(r.a.y), lo(r.b.x), hi(r.b.x), ch);
+	o.x.z = ycocg_lies<BGR>(lo(r.b.y), hi(r.b.y), lo(r.c.x), ch);
+	o.x.w = ycocg_lies<BGR>(hi(r.c.x), lo(r.c.y), hi(r.c.y), ch);
+	o.xr = ycocg_lies<BGR>(lo(r.e0), hi(r.e0), lo(r.e1), ch);
+	o.left = make_int2(o.xr, ycocg_lies<BGR>(hi(r.e1), lo(r.e2), hi(r.e2), ch));
 	return o;
 }
 
@@ -925,6 +937,13 @@ __device__ __forceinline__ RowP row_p(const FwdRaw8 &r, int)
 	return o;
 }
 
+// ycocg_lies for packed pairs
+template <bool BGR>
+__device__ __forceinline__ P2 ycocg_lies_p(P2 s0, P2 s1, P2 s2, int ch)
+{
+	return BGR ? ycocg_p(s2, s1, s0, ch) : ycocg_p(s0, s1, s2, ch);
+}
+
 // Interleaved RGB: the row as the two loads deliver it — the four pixels' three words and two words of neighbours in
 // consecutive registers; taking single words out of them at load time would be a use of the load.
 typedef unsigned U32x2 __attribute__((ext_vector_type(2)));
@@ -941,18 +960,19 @@ __device__ __forceinline__ FwdRawRgb hold(const FwdRawRgb &r)
 	return o;
 }
 
+template <bool BGR = false>
 __device__ __forceinline__ RowP row_p(const FwdRawRgb &r, int ch)
 {
-	// a = R0 G0 B0 R1, b = G1 B1 R2 G2, c = B2 R3 G3 B3 (v_perm_b32: selector bytes 0-3 pick from the second operand, 4-7 from the first, 0x0c is zero)
+	// a = R0 G0 B0 R1, b = G1 B1 R2 G2, c = B2 R3 G3 B3 — BGR: R and B the other way round, here and in the edge words — (v_perm_b32: selector bytes 0-3 pick from the second operand, 4-7 from the first, 0x0c is zero)
 	const unsigned a = r.abc.x, b = r.abc.y, c = r.abc.z, e0 = r.e.x, e1 = r.e.y;
 	RowP o;
-	o.E = ycocg_p(p2_of(__builtin_amdgcn_perm(b, a, 0x0c060c00u)), p2_of(__builtin_amdgcn_perm(b, a, 0x0c070c01u)),
+	o.E = ycocg_lies_p<BGR>(p2_of(__builtin_amdgcn_perm(b, a, 0x0c060c00u)), p2_of(__builtin_amdgcn_perm(b, a, 0x0c070c01u)),
 		p2_of(__builtin_amdgcn_perm(c, a, 0x0c040c02u)), ch);
-	o.O = ycocg_p(p2_of(__builtin_amdgcn_perm(c, a, 0x0c050c03u)), p2_of(__builtin_amdgcn_perm(c, b, 0x0c060c00u)),
+	o.O = ycocg_lies_p<BGR>(p2_of(__builtin_amdgcn_perm(c, a, 0x0c050c03u)), p2_of(__builtin_amdgcn_perm(c, b, 0x0c060c00u)),
 		p2_of(__builtin_amdgcn_perm(c, b, 0x0c070c01u)), ch);
 	// lane 63: e0 = R4 G4 B4 ..; lane 0: e0, e1 = bytes 12q-8 .. 12q-1, pixels 4q-2 and 4q-1 are the last six
-	o.xr = ycocg_p(p2_of(e0 & 255u), p2_of((e0 >> 8) & 255u), p2_of((e0 >> 16) & 255u), ch);
-	o.left = ycocg_p(p2_of(__builtin_amdgcn_perm(e1, e0, 0x0c050c02u)), p2_of(__builtin_amdgcn_perm(e1, e0, 0x0c060c03u)),
+	o.xr = ycocg_lies_p<BGR>(p2_of(e0 & 255u), p2_of((e0 >> 8) & 255u), p2_of((e0 >> 16) & 255u), ch);
+	o.left = ycocg_lies_p<BGR>(p2_of(__builtin_amdgcn_perm(e1, e0, 0x0c050c02u)), p2_of(__builtin_amdgcn_perm(e1, e0, 0x0c060c03u)),
 		p2_of(__builtin_amdgcn_perm(e1, e0, 0x0c070c04u)), ch);
 	return o;
 }
@@ -992,19 +1012,21 @@ __device__ __forceinline__ FwdRawRgbx hold(const FwdRawRgbx &r)
 	return o;
 }
 
-// channel ch of the pixels in the words lo and hi, as a packed pair (v_perm_b32 as in row_p(FwdRawRgb): a word is R G B x)
+// channel ch of the pixels in the words lo and hi, as a packed pair (v_perm_b32 as in row_p(FwdRawRgb): a word is R G B x, or B G R x)
+template <bool BGR>
 __device__ __forceinline__ P2 rgbx_pair(unsigned lo, unsigned hi, int ch)
 {
-	return ycocg_p(p2_of(__builtin_amdgcn_perm(hi, lo, 0x0c040c00u)), p2_of(__builtin_amdgcn_perm(hi, lo, 0x0c050c01u)),
+	return ycocg_lies_p<BGR>(p2_of(__builtin_amdgcn_perm(hi, lo, 0x0c040c00u)), p2_of(__builtin_amdgcn_perm(hi, lo, 0x0c050c01u)),
 		p2_of(__builtin_amdgcn_perm(hi, lo, 0x0c060c02u)), ch);
 }
 
+template <bool BGR = false>
 __device__ __forceinline__ RowP row_p(const FwdRawRgbx &r, int ch)
 {
 	const unsigned e0 = r.e.x, e1 = r.e.y;
-	RowP o = { rgbx_pair(r.px.x, r.px.z, ch), rgbx_pair(r.px.y, r.px.w, ch),
-		ycocg_p(p2_of(e0 & 255u), p2_of((e0 >> 8) & 255u), p2_of((e0 >> 16) & 255u), ch),   // lane 63: e0 = pixel 4q+4
-		rgbx_pair(e0, e1, ch) };                                                          // lane 0: e0, e1 = pixels 4q-2, 4q-1
+	RowP o = { rgbx_pair<BGR>(r.px.x, r.px.z, ch), rgbx_pair<BGR>(r.px.y, r.px.w, ch),
+		ycocg_lies_p<BGR>(p2_of(e0 & 255u), p2_of((e0 >> 8) & 255u), p2_of((e0 >> 16) & 255u), ch),   // lane 63: e0 = pixel 4q+4
+		rgbx_pair<BGR>(e0, e1, ch) };                                                          // lane 0: e0, e1 = pixels 4q-2, 4q-1
 	return o;
 }
 
@@ -1028,8 +1050,9 @@ struct FwdSrc;
 
 // the band a level of k_fwd_level_w reads: int32 planes, 16-bit planes (dwtx_p16: the detail bands go out as 16-bit values
 // too), or — the finest level of a deep picture — uint16_t pixels, gray, interleaved RGB or planar RGB; and the pixels
-// k_fwd_pixels_w reads (the host's names for Band<>'s five and for uint8_t, Rgb8, RgbP8 and Rgbx8)
-enum { SRC_I32 = 0, SRC_I16, SRC_U16, SRC_RGB16, SRC_RGBP16, SRC_U8, SRC_RGB8, SRC_RGBP8, SRC_RGBX8, SRC_COUNT };
+// k_fwd_pixels_w reads (the host's names for Band<>'s five and for uint8_t, Rgb8, RgbP8 and Rgbx8, then the
+// three B, G, R twins: Band<SRC_BGR16>, Bgr8, Bgrx8)
+enum { SRC_I32 = 0, SRC_I16, SRC_U16, SRC_RGB16, SRC_RGBP16, SRC_U8, SRC_RGB8, SRC_RGBP8, SRC_RGBX8, SRC_BGR16, SRC_BGR8, SRC_BGRX8, SRC_COUNT };
 template <int SRC>
 struct Band {};
 // 8-bit interleaved RGB pixels, of which each plane's workgroup takes its own YCoCg-R channel (image.h:52-65 fused; 8-bit
@@ -1040,6 +1063,10 @@ struct RgbP8 {};
 // 8-bit RGB in 4-byte pixels (dwtx_pixels::rgbx8(): RGBA / RGBX surfaces, pixel step 4): interleaved like Rgb8, a lane's
 // four pixels one 16-byte piece whose every fourth byte is loaded and never used
 struct Rgbx8 {};
+// The interleaved sources for pixels that lie as B, G, R (dwtx_pixels::order): Band<SRC_BGR16>, and these two.  Each is its RGB
+// twin — loads, addresses, registers — with the colour triple taken the other way round where the row is used.
+struct Bgr8 {};
+struct Bgrx8 {};
 
 // plane p of an RGB picture = channel p % 3 of window p / 3 (src_ps from a window to the next)
 __device__ __forceinline__ long rgb_window(const LevelArgs &a, int plane, int &ch)
@@ -1128,6 +1155,11 @@ struct FwdSrc<Band<SRC_RGB16>> : FwdInt32 {
 };
 
 template <>
+struct FwdSrc<Band<SRC_BGR16>> : FwdSrc<Band<SRC_RGB16>> {
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int ch) { return widen<true>(r, ch); }
+};
+
+template <>
 struct FwdSrc<Band<SRC_RGBP16>> : FwdInt32 {
 	typedef FwdRawRgbS3 Loaded;
 	static __device__ __forceinline__ const uint16_t *base(const LevelArgs &a, int plane, int &ch) { return FwdSrc<Band<SRC_RGB16>>::base(a, plane, ch); }
@@ -1192,6 +1224,16 @@ struct FwdSrc<Rgbx8> : FwdPacked {
 		Loaded r = { *reinterpret_cast<const U32x4 *>(row + at.main), *reinterpret_cast<const U32x2 *>(row + at.edge) };
 		return r;
 	}
+};
+
+template <>
+struct FwdSrc<Bgr8> : FwdSrc<Rgb8> {
+	static __device__ __forceinline__ void lift(const FwdRawRgb &r, int ch, int q, int lane, int nquads, P2 &lo, P2 &hi) { fwd_lift_p(row_p<true>(r, ch), q, lane, nquads, lo, hi); }
+};
+
+template <>
+struct FwdSrc<Bgrx8> : FwdSrc<Rgbx8> {
+	static __device__ __forceinline__ void lift(const FwdRawRgbx &r, int ch, int q, int lane, int nquads, P2 &lo, P2 &hi) { fwd_lift_p(row_p<true>(r, ch), q, lane, nquads, lo, hi); }
 };
 
 // One wide forward level of the wave's strip, for every source (FwdSrc above): int32 planes on every level of
@@ -1773,7 +1815,7 @@ struct Inv2Args {
 	const short *det16;   // F16: the detail bands of BOTH levels as 16-bit values (positions, pitch and plane stride of det)
 	uint8_t *dst8;        // 8-bit output (the finest level of a gray picture: pnm.h:108's clamp fused), dst_ps / opitch in bytes
 	WinGrid grid;         // the windows behind dst8 (dst_ps apart in a band)
-	long cstride;         // planar RGB pixels behind dst8: from a window's plane to its next (bytes); 0: interleaved.  (Last, as in LevelArgsW.)
+	long cstride;         // planar RGB pixels behind dst8: from a window's R plane to G, from G to B (bytes; signed as in LevelArgsW); 0: interleaved.  (Last, as in LevelArgsW.)
 };
 constexpr int V2_FIRST = 4, V2_OWN = 56;
 
@@ -1993,6 +2035,9 @@ struct Rgb24 {
 };
 
 // the same for deep pixels: the clamps at the picture's maxval M
+// (BGR, here and in rgbx_of and rgb_of: the pixels lie as B, G, R — dwtx_pixels::order — so R and B trade places AFTER the
+// clamps, which act on the colours)
+template <bool BGR = false>
 __device__ __forceinline__ Rgb24 rgb16_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M)
 {
 	unsigned px[12];
@@ -2003,9 +2048,9 @@ __device__ __forceinline__ Rgb24 rgb16_of(const Quad4 &y, const Quad4 &co, const
 		const int g = c1 + t;
 		const int b = t - tdiv2(c0);
 		const int r = b + c0;
-		px[3 * k] = (unsigned)clamp_to(r, 0, M);
+		px[3 * k + (BGR ? 2 : 0)] = (unsigned)clamp_to(r, 0, M);
 		px[3 * k + 1] = (unsigned)clamp_to(g, 0, M);
-		px[3 * k + 2] = (unsigned)clamp_to(b, 0, M);
+		px[3 * k + (BGR ? 0 : 2)] = (unsigned)clamp_to(b, 0, M);
 	}
 	Rgb24 o;
 #pragma unroll
@@ -2060,9 +2105,11 @@ __device__ __forceinline__ Rgb24 rgb16_planar_of(const Quad4 &y, const Quad4 &co
 // 8 of deep pixels, or (PIX_STEP4: 8-bit RGB in 4-byte pixels, dwtx_pixels::rgbx8()) the three colour bytes of each of the four
 // pixels and NOT the fourth: a halfword and a byte per pixel, nothing read, merged and written back (include/dwtx.h: another
 // stream may be writing the fourth bytes at the same moment)
-enum PixLayout { PIX_PACKED = 0, PIX_PLANAR = 1, PIX_STEP4 = 2 };
+// PIX_PACKED_BGR, PIX_STEP4_BGR: the two interleaved layouts for pixels that lie as B, G, R: the same stores of the same bytes,
+// R and B at each other's places in what is stored.  (Planar pixels have no such twin: the host gives cs a sign.)
+enum PixLayout { PIX_PACKED = 0, PIX_PLANAR = 1, PIX_STEP4 = 2, PIX_PACKED_BGR = 3, PIX_STEP4_BGR = 4 };
 struct Rgbx16 {
-	unsigned w[4];   // four pixels: R | G << 8 | B << 16
+	unsigned w[4];   // four pixels: R | G << 8 | B << 16 (PIX_STEP4_BGR: B | G << 8 | R << 16)
 };
 template <bool NT>
 __device__ __forceinline__ void rgbx_store(uint8_t *p, const Rgbx16 &v)
@@ -2126,6 +2173,7 @@ struct RgbOut<uint16_t, PIX_PLANAR> {
 			*reinterpret_cast<uint2 *>(p + c * cs) = make_uint2(v.w[2 * c], v.w[2 * c + 1]);
 	}
 };
+template <bool BGR = false>
 __device__ __forceinline__ Rgbx16 rgbx_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg)
 {
 	unsigned px[3][4];
@@ -2133,7 +2181,7 @@ __device__ __forceinline__ Rgbx16 rgbx_of(const Quad4 &y, const Quad4 &co, const
 	Rgbx16 o;
 #pragma unroll
 	for (int k = 0; k < 4; ++k)
-		o.w[k] = px[0][k] | (px[1][k] << 8) | (px[2][k] << 16);
+		o.w[k] = px[BGR ? 2 : 0][k] | (px[1][k] << 8) | (px[BGR ? 0 : 2][k] << 16);
 	return o;
 }
 template <>
@@ -2146,6 +2194,7 @@ struct RgbOut<uint8_t, PIX_STEP4> {
 	}
 };
 
+template <bool BGR = false>
 __device__ __forceinline__ Rgb12 rgb_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg)
 {
 	unsigned char px[12];
@@ -2156,9 +2205,9 @@ __device__ __forceinline__ Rgb12 rgb_of(const Quad4 &y, const Quad4 &co, const Q
 		const int g = c1 + t;
 		const int b = t - tdiv2(c0);
 		const int r = b + c0;
-		px[3 * k] = (unsigned char)clamp_to(r, 0, 255);
+		px[3 * k + (BGR ? 2 : 0)] = (unsigned char)clamp_to(r, 0, 255);
 		px[3 * k + 1] = (unsigned char)clamp_to(g, 0, 255);
-		px[3 * k + 2] = (unsigned char)clamp_to(b, 0, 255);
+		px[3 * k + (BGR ? 0 : 2)] = (unsigned char)clamp_to(b, 0, 255);
 	}
 	Rgb12 o;
 #pragma unroll
@@ -2170,8 +2219,22 @@ __device__ __forceinline__ Rgb12 rgb_of(const Quad4 &y, const Quad4 &co, const Q
 template <typename PixT, PixLayout LAYOUT>
 __device__ __forceinline__ typename RgbOut<PixT, LAYOUT>::row RgbOut<PixT, LAYOUT>::of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgb_of(y, co, cg); }
 
+// the B, G, R twins: their RGB layout's row and store, R and B swapped in the row
+template <>
+struct RgbOut<uint8_t, PIX_PACKED_BGR> : RgbOut<uint8_t, PIX_PACKED> {
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgb_of<true>(y, co, cg); }
+};
+template <>
+struct RgbOut<uint16_t, PIX_PACKED_BGR> : RgbOut<uint16_t, PIX_PACKED> {
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M) { return rgb16_of<true>(y, co, cg, M); }
+};
+template <>
+struct RgbOut<uint8_t, PIX_STEP4_BGR> : RgbOut<uint8_t, PIX_STEP4> {
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgbx_of<true>(y, co, cg); }
+};
+
 // PixT = uint16_t: deep pixels (dst8 points to uint16_t samples, ll_ps / llpitch count samples, clamps at a.maxval)
-// PIX_PLANAR: dst8 is channel 0's plane of the window, the others A.cstride samples apart, llpitch the pitch of a plane's rows
+// PIX_PLANAR: dst8 is the R plane of the window, G and B A.cstride samples apart each (signed), llpitch the pitch of a plane's rows
 // PIX_STEP4: llpitch is the pitch of rows of 4-byte pixels; the step is the constant 4 here, no argument carries it
 template <bool F16, typename PixT = uint8_t, PixLayout LAYOUT = PIX_PACKED>
 __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
@@ -2311,7 +2374,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 			return;
 #pragma unroll
 		for (int k = 0; k < 4; ++k) {
-			if constexpr (LAYOUT == PIX_STEP4) {
+			if constexpr (LAYOUT == PIX_STEP4 || LAYOUT == PIX_STEP4_BGR) {
 				rgbx_store<true>(dst + (long)(4 * m + k) * a.opitch + 16 * q, orow[k]);
 			} else if constexpr (LAYOUT == PIX_PLANAR) {
 				uint8_t *p = dst + (long)(4 * m + k) * a.opitch + 4 * q;
@@ -2537,7 +2600,7 @@ struct PixGrid {
 	long image_stride, row_pitch;
 	WinGrid grid;
 	int W, H, C, n;
-	long chan_stride;   // RGB: from a pixel's sample of one channel to the next one's — 1 interleaved, dwtx_pixels::channel_stride planar
+	long chan_stride;   // RGB: from a pixel's R sample to its G, from G to B (dwtx_pixels::colour_stride()) — 1 interleaved, the channel stride planar, negative where the pixels lie as B, G, R
 	int col_step;       // from a pixel to the next one of its row: C interleaved (dwtx_pixels::pixel_step where a view has one), 1 planar
 };
 
@@ -2695,12 +2758,12 @@ extern "C" int dwtx_synth_pixels(dwtx_ctx *ctx, uint8_t *pix, int W, int H, int 
 	return DWTX_OK;
 }
 
-// the conversions' view of px and their launch grid
+// the conversions' view of px and their launch grid; the kernels' `pix` is px.red(): the R sample of the grid's first pixel,
+// from which chan_stride leads to G and B — upwards, or down to the base for B, G, R pixels
 static PixGrid pix_grid(const dwtx_pixels &px, int W, int H, int n, dim3 *grid)
 {
 	*grid = dim3((unsigned)dwtx_cdiv(W, PX_LANES), (unsigned)dwtx_cdiv(H, PX_ROWS), (unsigned)min(n, 65535));
-	return PixGrid{ (long)px.image_stride, (long)px.pitch(W), win_grid(px), W, H, px.channels, n, px.planar() ? (long)px.channel_stride : 1L,
-		(int)px.step() };
+	return PixGrid{ (long)px.image_stride, (long)px.pitch(W), win_grid(px), W, H, px.channels, n, px.colour_stride(), (int)px.step() };
 }
 
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
@@ -2712,9 +2775,9 @@ int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px,
 	dim3 grid;
 	const PixGrid g = pix_grid(px, W, H, n, &grid);
 	if (!px.deep())
-		hipLaunchKernelGGL(k_planes_from_pixels<uint8_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, px.u8(), g);
+		hipLaunchKernelGGL(k_planes_from_pixels<uint8_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, static_cast<const uint8_t *>(px.red()), g);
 	else
-		hipLaunchKernelGGL(k_planes_from_pixels<uint16_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, px.u16(), g);
+		hipLaunchKernelGGL(k_planes_from_pixels<uint16_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, static_cast<const uint16_t *>(px.red()), g);
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
@@ -2730,9 +2793,9 @@ int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *p
 	dim3 grid;
 	const PixGrid g = pix_grid(px, W, H, n, &grid);
 	if (!px.deep())
-		hipLaunchKernelGGL(k_pixels_from_planes<uint8_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, px.u8(), planes, g, px.maxval);
+		hipLaunchKernelGGL(k_pixels_from_planes<uint8_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<uint8_t *>(px.red()), planes, g, px.maxval);
 	else
-		hipLaunchKernelGGL(k_pixels_from_planes<uint16_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, px.u16(), planes, g, px.maxval);
+		hipLaunchKernelGGL(k_pixels_from_planes<uint16_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<uint16_t *>(px.red()), planes, g, px.maxval);
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
@@ -2824,15 +2887,24 @@ struct FwdSource {
 	long cstride;
 };
 
+// The order of the channels (dwtx_pixels::order) changes no path: interleaved B, G, R pixels run their layout's twin kernel on
+// the same base, planar ones the same kernel from their R plane with a negative channel stride.  What the wide kernels get as
+// src8 / dst8 and as cstride:
+static const uint8_t *wide_base(const dwtx_pixels &px) { return px.planar() ? static_cast<const uint8_t *>(px.red()) : px.u8(); }
+static long wide_cstride(const dwtx_pixels &px) { return px.channels == 3 && px.planar() ? px.colour_stride() : 0; }
+
 static FwdSource fwd_source(const dwtx_pixels *px, bool src16)
 {
 	if (!px)
 		return { src16 ? SRC_I16 : SRC_I32, false, 0 };
-	const bool deep = px->deep();
+	const bool deep = px->deep(), bgr = px->bgr();
 	if (px->channels != 3)
 		return { deep ? SRC_U16 : SRC_U8, false, 0 };
-	const int src = px->planar() ? (deep ? SRC_RGBP16 : SRC_RGBP8) : px->rgbx8() ? SRC_RGBX8 : deep ? SRC_RGB16 : SRC_RGB8;
-	return { src, !deep, (long)px->channel_stride };
+	const int src = px->planar() ? (deep ? SRC_RGBP16 : SRC_RGBP8)
+		: px->rgbx8()            ? (bgr ? SRC_BGRX8 : SRC_RGBX8)
+		: deep                   ? (bgr ? SRC_BGR16 : SRC_RGB16)
+		                         : (bgr ? SRC_BGR8 : SRC_RGB8);
+	return { src, !deep, wide_cstride(*px) };
 }
 
 // the wide kernel of a source, without and with histograms (deep pixels leave none: lift_fwd refuses the call)
@@ -2848,6 +2920,9 @@ static WideKernel fwd_wide_kernel(int src, bool hist)
 		{ k_fwd_pixels_w<Rgb8, false>, k_fwd_pixels_w<Rgb8, true> },
 		{ k_fwd_pixels_w<RgbP8, false>, k_fwd_pixels_w<RgbP8, true> },
 		{ k_fwd_pixels_w<Rgbx8, false>, k_fwd_pixels_w<Rgbx8, true> },
+		{ k_fwd_level_w<false, SRC_BGR16>, nullptr },
+		{ k_fwd_pixels_w<Bgr8, false>, k_fwd_pixels_w<Bgr8, true> },
+		{ k_fwd_pixels_w<Bgrx8, false>, k_fwd_pixels_w<Bgrx8, true> },
 	};
 	return K[src][hist];
 }
@@ -2939,7 +3014,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 		a.h2 = hs[t + 1];
 		const dwtx_pixels *pix_in = t == 0 ? px : nullptr;   // this step reads the pixels
 		if (pix_in) {   // (deep pixels: uint16_t samples behind src8; src_ps and spitch count samples either way)
-			a.src8 = px->u8();
+			a.src8 = wide_base(*px);
 			a.src_ps = (long)px->image_stride;
 			a.spitch = (int)px->pitch(W);
 			a.grid = win_grid(*px);
@@ -3069,8 +3144,13 @@ using Inv2Kernel = void (*)(Inv2Args);
 // px: the pair writes these pixels (8-bit ones, gray or RGB), which it does from 16-bit bands only
 static Inv2Kernel inv2_kernel(const dwtx_pixels *px, bool det16)
 {
-	if (px && px->channels == 3)
-		return px->planar() ? k_inv2_level_w_rgb<true, PIX_PLANAR> : px->rgbx8() ? k_inv2_level_w_rgb<true, PIX_STEP4> : k_inv2_level_w_rgb<true>;
+	if (px && px->channels == 3) {
+		if (px->planar())
+			return k_inv2_level_w_rgb<true, PIX_PLANAR>;
+		if (px->bgr())
+			return px->rgbx8() ? k_inv2_level_w_rgb<true, PIX_STEP4_BGR> : k_inv2_level_w_rgb<true, PIX_PACKED_BGR>;
+		return px->rgbx8() ? k_inv2_level_w_rgb<true, PIX_STEP4> : k_inv2_level_w_rgb<true>;
+	}
 	if (px)
 		return k_inv2_level_w<uint8_t, true>;
 	return det16 ? k_inv2_level_w<int, true> : k_inv2_level_w<int, false>;
@@ -3084,6 +3164,13 @@ static WideKernel inv_wide_kernel(const dwtx_pixels *px, bool det16)
 		if (px->deep())
 			return k_inv_level_w_rgb<false, uint16_t, PIX_PLANAR>;
 		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_PLANAR> : k_inv_level_w_rgb<false, uint8_t, PIX_PLANAR>;
+	}
+	if (px && px->bgr()) {   // (interleaved: the layouts' B, G, R twins)
+		if (px->rgbx8())
+			return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_STEP4_BGR> : k_inv_level_w_rgb<false, uint8_t, PIX_STEP4_BGR>;
+		if (px->deep())
+			return k_inv_level_w_rgb<false, uint16_t, PIX_PACKED_BGR>;
+		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_PACKED_BGR> : k_inv_level_w_rgb<false, uint8_t, PIX_PACKED_BGR>;
 	}
 	if (px && px->rgbx8())
 		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_STEP4> : k_inv_level_w_rgb<false, uint8_t, PIX_STEP4>;
@@ -3202,11 +3289,11 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 			f.det16 = in16(t) ? p16->planes : nullptr;
 			const dwtx_pixels *pix_out = t - 1 == 0 ? px : nullptr;   // the pair writes the pixels
 			if (pix_out) {
-				f.dst8 = px->u8();
+				f.dst8 = const_cast<uint8_t *>(wide_base(*px));
 				f.dst_ps = (long)px->image_stride;
 				f.opitch = (int)px->pitch(W);
 				f.grid = win_grid(*px);
-				f.cstride = px->channels == 3 ? (long)px->channel_stride : 0;
+				f.cstride = wide_cstride(*px);
 			} else if (t - 1 == 0) {
 				f.dst = out;
 				f.dst_ps = full_ps;
@@ -3242,7 +3329,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 		a.spitch = cur_pitch;
 		const dwtx_pixels *pix_out = t == 0 ? px : nullptr;   // this step writes the pixels
 		if (pix_out) {   // (deep pixels: uint16_t samples behind dst8; ll_ps and llpitch count samples either way)
-			a.dst8 = px->u8();
+			a.dst8 = const_cast<uint8_t *>(wide_base(*px));
 			a.ll_ps = (long)px->image_stride;
 			a.llpitch = (int)px->pitch(W);
 			a.grid = win_grid(*px);
@@ -3277,7 +3364,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 			const int sx = dwtx_cdiv(A.nquads, rgb ? INV_QUADS : 64);   // (the RGB kernel's waves overlap by a lane on each side)
 			a.rpw = pick_rpw(sx, a.h2, nplanes, forced);
 			A.a = a;
-			A.cstride = rgb ? (long)px->channel_stride : 0;
+			A.cstride = rgb ? wide_cstride(*px) : 0;
 			const dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), rgb ? nplanes / 3 : nplanes);
 			hipLaunchKernelGGL(inv_wide_kernel(pix_out, a.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {

@@ -15,19 +15,20 @@ def group_view(frame, g):
                             frame.storage_offset() + g.y0 * sh + g.x0 * sw)
 
 
-def encode_frame(ctx, frame, tile, capacity=0, stepped=False):
+def encode_frame(ctx, frame, tile, capacity=0, stepped=False, order="rgb"):
     """frame: device tensor [H,W,C] (uint8, or uint16 / int16; interleaved, or a planar [C,H,W] frame permuted) -> one (TileGroup, streams, lens, info) per group of
     tile_groups(W, H, tile); a group's stream i is its tile (i // cols, i % cols).  Async, like encode_view.
-    stepped: encode_view's keyword — the frame may be `rgba[..., :3]` or `rgba[..., 3:]` of an RGBA surface [H,W,4]."""
+    stepped: encode_view's keyword — the frame may be `rgba[..., :3]` or `rgba[..., 3:]` of an RGBA surface [H,W,4].
+    order: encode_view's keyword — "bgr" for `bgra[..., :3]` of a BGRA surface, or a BGR frame."""
     out = []
     for g in tile_groups(frame.shape[1], frame.shape[0], tile):
-        streams, info = ctx.encode_view(group_view(frame, g), capacity, stepped=stepped)
+        streams, info = ctx.encode_view(group_view(frame, g), capacity, stepped=stepped, order=order)
         out.append((g, streams, ctx.stream_lengths(info), info))
     return out
 
 
-def decode_frame(ctx, groups, into, maxval=None, levels_max=-1, stepped=False):
+def decode_frame(ctx, groups, into, maxval=None, levels_max=-1, stepped=False, order="rgb"):
     """groups: what encode_frame returned (or (TileGroup, streams, lens) triples) -> every tile decoded in place in the
     device tensor `into` [H,W,C]; a tile whose stream was cut comes out reduced in its own corner.  Returns the lists of
-    DecodeInfo, one per group.  stepped: decode_view's keyword."""
-    return [ctx.decode_view(g[1], g[2], group_view(into, g[0]), maxval, levels_max, stepped=stepped) for g in groups]
+    DecodeInfo, one per group.  stepped, order: decode_view's keywords."""
+    return [ctx.decode_view(g[1], g[2], group_view(into, g[0]), maxval, levels_max, stepped=stepped, order=order) for g in groups]

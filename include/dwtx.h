@@ -393,7 +393,7 @@ int dwtx_decode_view(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_st
  * and deep samples work with a step; dwtx_view itself is unchanged.  pixel_step == 0 or == channels is the dense case:
  * the call is then dwtx_encode_view / dwtx_decode_view in every respect.  The streams are those of the dense interleaved
  * copy: the .dwt format knows nothing of the layout.  (An RGBA surface is an RGB stream and a gray stream, in two calls;
- * the channel order is R, G, B as it lies.)
+ * the channel order is R, G, B as it lies; B, G, R surfaces: dwtx_*_view_order below.)
  * With row = (W-1)*pixel_step + channels, the samples from a window row's first to behind its last, DWTX_ERR_ARG (with a
  * dwtx_last_error() text, nothing written): pixel_step non-zero and below channels; a planar view (channels == 3,
  * channel_stride != 0) with any step but 0 and 3 — the rows of a plane stay dense; row_pitch < row.
@@ -411,6 +411,29 @@ int dwtx_encode_view_step(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step
  * those at the same moment, so nothing is read, merged and written back there. */
 int dwtx_decode_view_step(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
 	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, dwtx_decode_info *host_info);
+
+/* ---- channel order: B, G, R pixels coded where they lie --------------------------------------------------------------
+ * dwtx_encode_view_step / dwtx_decode_view_step for surfaces whose three channels lie the other way round: B8G8R8A8 / BGRX
+ * swap-chain and capture surfaces (channels 3, pixel_step 4), video decoders' RGB outputs, OpenCV's BGR Mat (channels 3,
+ * pixel_step 0).  `order` says which colour the three channels of a pixel are AS THEY LIE IN MEMORY: with DWTX_ORDER_BGR,
+ * memory sample 0 of an interleaved pixel is B and sample 2 is R; of a planar view (channel_stride != 0) the plane at dev
+ * is B and the plane at dev + 2*channel_stride is R.  dev stays the lowest-addressed channel's first sample, and every
+ * stride keeps its meaning.  Every rule of the calls above holds word for word as it does for RGB: row length and
+ * alignment, the disjointness of destinations, "no other sample written", and the one documented read of a pixel's own
+ * fourth byte (8-bit pixels on the 4-byte grid are read and written by the same wide kernels in either order; a view
+ * takes the same path whatever its order).
+ * The streams are those of the dense interleaved R, G, B copy: a BGR view and the channel-reversed copy of it encode to the
+ * same bytes, and a decode writes what the RGB decode would, with R and B at each other's places.  The clamps of a
+ * truncated stream's decode (image.h:41-43, pnm.h:108) act on the colours, not on memory positions.
+ * DWTX_ORDER_RGB is dwtx_*_view_step in every respect.  Any other value is DWTX_ERR_ARG (with a dwtx_last_error() text,
+ * nothing written).  `order` is ignored when channels == 1, as channel_stride is.
+ * Alpha-first surfaces (A8R8G8B8: DWTX_ORDER_RGB, A8B8G8R8: DWTX_ORDER_BGR) are the same calls with dev + 1 and pixel_step 4.
+ * Their pixels leave the 4-byte grid, so they take the general conversions, not the wide kernels: correct, and slower. */
+enum { DWTX_ORDER_RGB = 0, DWTX_ORDER_BGR = 1 };
+int dwtx_encode_view_order(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, int W, int H, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
+int dwtx_decode_view_order(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, dwtx_decode_info *host_info);
 
 /* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
  * interior, right column, bottom row, corner, in that order, those that exist — each a cols x rows grid of W x H tiles

@@ -1,4 +1,4 @@
-"""Encode + decode of the RGB of RGBA surfaces (4-byte pixels, of which three are colour), four routes (development aid):
+"""Encode + decode of the RGB of RGBA surfaces (4-byte pixels, of which three are colour), six routes (development aid):
   step         encode_view(rgba[..., :3], stepped=True) / decode_view into the surface: the pixels are coded where they lie
                (8-bit, step 4, everything on the 4-byte grid: lift.hip's Rgbx8 / PIX_STEP4 kernels)
   general      the same calls on the same surface kept one byte off the 4-byte grid: the general conversions
@@ -6,6 +6,10 @@
   copies       what the holder had to do before views knew a pixel step: rgba[..., :3].contiguous(), encode_device,
                decode_device and a scattering copy back into the surface
   interleaved  the view of the same pictures kept as dense RGB (what the codec had all along), for scale
+  step_bgr     `step` with the same surfaces declared BGRA (order="bgr": the kernels' B, G, R twins); its streams are those of
+               the channel-reversed pictures
+  copies_bgr   what the holder of a BGRA surface had to do before views knew a channel order: bgra[..., :3].flip(-1) (a
+               channel-reversing contiguous copy), encode_device, decode_device and a reversing scatter back
 Encode and decode are timed apart, `reps` times, the routes taking turns; every timed call runs under an alarm of its own
 (LIMIT seconds: a call that hangs ends the process).  Two workloads: 64 surfaces of 1920 x 1080, and one 4096 x 4096
 surface as a 4 x 4 grid of 1024 x 1024 tiles.  Prints one JSON line and, with an argument, writes it there too ("-":
@@ -74,10 +78,10 @@ def workload(name, rgb, windows):
     def lens():
         return ctx.stream_lengths(info)
 
-    def stepped(route):
+    def stepped(route, **kw):
         s, b = windows(src[route][..., :3]), windows(back[route][..., :3])
-        return (lambda: ctx.encode_view(s, out=streams, info=info, stepped=True),
-                lambda: ctx.decode_view(streams, lens(), b, stepped=True))
+        return (lambda: ctx.encode_view(s, out=streams, info=info, stepped=True, **kw),
+                lambda: ctx.decode_view(streams, lens(), b, stepped=True, **kw))
 
     def copies_enc():
         dense.view(iview.shape).copy_(windows(src["copies"][..., :3]))      # rgba[..., :3].contiguous()
@@ -87,8 +91,17 @@ def workload(name, rgb, windows):
         ctx.decode_device(streams, lens(), W, H, 3, out=dback)
         windows(back["copies"][..., :3]).copy_(dback.view(iview.shape))     # and back into the surface
 
+    def copies_bgr_enc():
+        ctx.encode_device(windows(src["copies"][..., :3]).flip(-1).contiguous().view(n, H, W, 3), out=streams, info=info)
+
+    def copies_bgr_dec():
+        ctx.decode_device(streams, lens(), W, H, 3, out=dback)
+        windows(back["copies"][..., :3]).copy_(dback.view(iview.shape).flip(-1))
+
     routes = {"step": stepped("step"), "general": stepped("general"), "copies": (copies_enc, copies_dec),
-              "interleaved": (lambda: ctx.encode_view(iview, out=streams, info=info), lambda: ctx.decode_view(streams, lens(), windows(iback)))}
+              "interleaved": (lambda: ctx.encode_view(iview, out=streams, info=info), lambda: ctx.decode_view(streams, lens(), windows(iback))),
+              "step_bgr": stepped("step", order="bgr"), "copies_bgr": (copies_bgr_enc, copies_bgr_dec)}
+    surface_of = {"step_bgr": "step", "copies_bgr": "copies"}   # the BGR routes run on their RGB twins' surfaces
     if only:
         routes = {only: routes[only]}
     for enc, dec in routes.values():   # warm-up: scratch, streams, caches
@@ -102,17 +115,22 @@ def workload(name, rgb, windows):
     out = {"pictures": n, "W": W, "H": H, "ms_per_call": res}
     if only:
         return out
-    keep = None
-    for k, (enc, dec) in routes.items():   # every route: the same streams, a lossless round trip, the fourth bytes untouched
+    keep = {}
+    for k, (enc, dec) in routes.items():   # every route: its order's streams, a lossless round trip, the fourth bytes untouched
+        b = back.get(surface_of.get(k, k))
+        if b is not None:
+            b[...] = 0xA5
         enc()
         dec()
         torch.cuda.synchronize()
-        keep = streams.clone() if keep is None else keep
-        assert torch.equal(streams, keep), name + ": " + k + " gives other streams"
+        order = "bgr" if k in surface_of else "rgb"
+        keep.setdefault(order, streams.clone())
+        assert torch.equal(streams, keep[order]), name + ": " + k + " gives other streams"
         if k == "interleaved":
             assert torch.equal(iback, rgb), name + ": interleaved round trip"
         else:
-            assert torch.equal(back[k][..., :3], rgb) and bool((back[k][..., 3] == 0xA5).all()), name + ": " + k + " round trip"
+            assert torch.equal(b[..., :3], rgb) and bool((b[..., 3] == 0xA5).all()), name + ": " + k + " round trip"
+    assert not torch.equal(keep["rgb"], keep["bgr"]), name + ": the order made no difference"
     med = lambda v: sorted(v)[len(v) // 2]
     out["median_ms"] = {k: {"encode": med(r["encode"]), "decode": med(r["decode"]), "both": round(med(r["encode"]) + med(r["decode"]), 3)}
                         for k, r in res.items()}
