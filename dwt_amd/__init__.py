@@ -10,10 +10,10 @@ raise.
 import ctypes as C
 
 from . import _lib
-from ._lib import Geom, Stats, StreamInfo, DecodeInfo, Index, SegIndex, View, TileGroup, INDEX_MAGIC, INDEX_MAX_SEGS, LIB_PATH  # noqa: F401
+from ._lib import Geom, Stats, StreamInfo, DecodeInfo, Index, SegIndex, View, TileGroup, FloatFormat, INDEX_MAGIC, INDEX_MAX_SEGS, LIB_PATH  # noqa: F401
 
-__all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "tile_groups", "view_fields", "view_order", "Geom", "Stats", "View",
-           "TileGroup"]
+__all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "tile_groups", "view_fields", "view_order", "float_format",
+           "Geom", "Stats", "View", "TileGroup", "FloatFormat"]
 
 
 class DwtxError(RuntimeError):
@@ -61,6 +61,39 @@ def view_order(order):
     if not isinstance(order, str) or order not in ORDERS:
         raise ValueError(f"order {order!r}: a view's channels lie as 'rgb' or as 'bgr'")
     return ORDERS[order]
+
+
+FLOAT_TYPES = {"float32": 0, "float16": 1, "bfloat16": 2}   # enum DWTX_FLOAT32 / _FLOAT16 / _BFLOAT16 (include/dwtx.h)
+
+
+def float_format(dtype, scale=1.0, bias=0.0):
+    """The dtype, `scale` and `bias` keywords of decode_view_float -> FloatFormat.  dtype: torch.float32 / float16 / bfloat16
+    (or their names); scale and bias: a number, or three — one per COLOUR, R, G, B, whatever order the channels lie in.  The
+    values are rounded to float32 here, as the library holds them.  Anything else — another dtype, another length, a value
+    that is not finite (before or after that rounding) — is a ValueError, raised here, before any device call."""
+    import math
+    import struct
+
+    name = str(dtype).replace("torch.", "")
+    if name not in FLOAT_TYPES:
+        raise ValueError(f"dtype {dtype}: a float view holds float32, float16 or bfloat16 samples")
+    fmt = FloatFormat(FLOAT_TYPES[name])
+    for what, arg, dst in (("scale", scale, fmt.scale), ("bias", bias, fmt.bias)):
+        try:
+            vals = [float(v) for v in arg]
+        except TypeError:
+            vals = [float(arg)] * 3
+        if len(vals) != 3:
+            raise ValueError(f"{what}: one value or three (R, G, B), not {len(vals)}")
+        for c, v in enumerate(vals):
+            try:
+                v32 = struct.unpack("f", struct.pack("f", v))[0]
+            except OverflowError:
+                v32 = math.inf
+            if not math.isfinite(v32):
+                raise ValueError(f"{what}[{c}] = {v!r} is not a finite float32")
+            dst[c] = v32
+    return fmt
 
 
 def view_fields(shape, strides, stepped=False):
@@ -496,19 +529,22 @@ class Context:
 
     # -- strided views: windows and tile grids of a larger frame (dwtx_encode_view / dwtx_decode_view) -----------
 
-    def _view(self, t, maxval, stepped=False):
+    def _view(self, t, maxval, stepped=False, floats=False):
         """View of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (uint8, or uint16 / int16 for deep pixels):
         the windows stay where they are.  RGB pixels are interleaved (channel stride 1, column stride 3) or planar (column
         stride 1, any channel stride): `nchw.permute(0, 2, 3, 1)` and `chw.permute(1, 2, 0)` are views as they are.
         stepped: pixels further apart than their samples too (view_fields); the last value returned is their pixel step."""
         torch = self.torch
-        if t.dtype not in (torch.uint8, torch.uint16, torch.int16) or t.device != self.device or t.dim() not in (4, 5):
+        if floats:   # (decode_view_float: the same views of float32 / float16 / bfloat16 samples)
+            if t.dtype not in (torch.float32, torch.float16, torch.bfloat16) or t.device != self.device or t.dim() not in (4, 5):
+                raise ValueError("a float view needs a float32 / float16 / bfloat16 tensor [n,H,W,C] or [bands,cols,H,W,C] on the context's device")
+        elif t.dtype not in (torch.uint8, torch.uint16, torch.int16) or t.device != self.device or t.dim() not in (4, 5):
             raise ValueError("a view needs a uint8 / uint16 / int16 tensor [n,H,W,C] or [bands,cols,H,W,C] on the context's device")
         f = view_fields(tuple(t.shape), tuple(t.stride()), stepped)
         deep = t.dtype != torch.uint8
         if maxval is None:
             maxval = 65535 if deep else 255
-        v = View(t.data_ptr(), 2 if deep else 1, f["channels"], maxval, f["cols"], f["row_pitch"], f["image_stride"], f["band_stride"],
+        v = View(t.data_ptr(), t.element_size(), f["channels"], maxval, f["cols"], f["row_pitch"], f["image_stride"], f["band_stride"],
                  f["channel_stride"])
         return v, f["W"], f["H"], f["channels"], f["n"], f["pixel_step"]
 
@@ -560,4 +596,25 @@ class Context:
         else:
             _check(self.lib.dwtx_decode_view(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
                                              C.cast(infos, C.c_void_p)), "dwtx_decode_view")
+        return list(infos)
+
+    def decode_view_float(self, streams, lens, into, maxval=255, scale=1.0, bias=0.0, levels_max=-1, stepped=False, order="rgb"):
+        """dwtx_decode_view_float: decode_view into a float32 / float16 / bfloat16 strided device tensor `into` (the shapes
+        and strides decode_view takes, stepped and order="bgr" included): every sample decode_view would write becomes
+        `v * scale + bias` — two float32 roundings, then the tensor's dtype, bit for bit torch's unfused
+        `x.float() * scale + bias` (and `.to(dtype)`) of the integer decode — and nothing else of `into`'s storage is
+        written.  maxval: what the streams were encoded from (255, or a deep picture's).  scale, bias: a number, or three,
+        per colour R, G, B.  Returns the list of DecodeInfo; syncs once.  A wrong dtype, a wrong length of scale or bias
+        and values that are not finite raise ValueError before any device call."""
+        order = view_order(order)
+        torch = self.torch
+        if not hasattr(into, "dtype") or into.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError(f"decode_view_float writes float32, float16 or bfloat16 tensors, not {getattr(into, 'dtype', type(into))}")
+        fmt = float_format(into.dtype, scale, bias)
+        v, W, H, Cn, n, step = self._view(into, int(maxval), stepped, floats=True)
+        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
+        assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
+        infos = (DecodeInfo * n)()
+        _check(self.lib.dwtx_decode_view_float(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step,
+                                               order, C.byref(fmt), C.cast(infos, C.c_void_p)), "dwtx_decode_view_float")
         return list(infos)

@@ -62,6 +62,11 @@ class View(C.Structure):
                 ("row_pitch", C.c_size_t), ("image_stride", C.c_size_t), ("band_stride", C.c_size_t), ("channel_stride", C.c_size_t)]
 
 
+class FloatFormat(C.Structure):
+    """dwtx_float_format: the float type of a dwtx_decode_view_float destination, scale and bias per colour (R, G, B)."""
+    _fields_ = [("type", C.c_int), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
 class TileGroup(C.Structure):
     """dwtx_tile_group: a cols x rows grid of W x H tiles whose first tile's corner is (x0, y0)."""
     _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("W", C.c_int), ("H", C.c_int), ("cols", C.c_int), ("rows", C.c_int)]
@@ -139,6 +144,7 @@ SYMBOLS = {
     "dwtx_decode_view_step": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _vp]),
     "dwtx_encode_view_order": (_i, [_vp, C.POINTER(View), _sz, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
     "dwtx_decode_view_order": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, _vp]),
+    "dwtx_decode_view_float": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), _vp]),
     "dwtx_tile_groups": (_i, [_i, _i, _i, C.POINTER(TileGroup)]),
     "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }

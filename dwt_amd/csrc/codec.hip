@@ -3,6 +3,7 @@
 // for batches of same-geometry images.
 #include "dwtx_internal.h"
 
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -368,7 +369,9 @@ extern "C" int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, s
 // pixel_step (the *_view_step calls; the plain ones pass 0): samples from a pixel to the next one of its row; 0 and
 // `channels` are both the dense case and leave px->pixel_step 0, so that everything downstream is the plain call's.
 // order (the *_view_order calls; the others pass DWTX_ORDER_RGB): kept for RGB views and checked first, nothing else here looks at it.
-static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, dwtx_pixels *px)
+// kind (dwtx_decode_view_float; the others pass none): the float samples the view must hold — its sample_bytes their size,
+// any maxval a deep picture may have; every stride counts those samples, and every rule below holds as it stands.
+static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, dwtx_pixels *px, int kind = -1)
 {
 	if (order != DWTX_ORDER_RGB && order != DWTX_ORDER_BGR) {
 		dwtx_set_error("view: channel order %d (DWTX_ORDER_RGB = 0 or DWTX_ORDER_BGR = 1)", order);
@@ -379,7 +382,11 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 		return DWTX_ERR_ARG;
 	}
 	DWTX_CHECK_DIMS(W, H);
-	if ((v->sample_bytes != 1 && v->sample_bytes != 2) || (v->channels != 1 && v->channels != 3) || v->cols < 0) {
+	if (kind >= 0 && v->sample_bytes != (kind == DWTX_SAMPLE_F32 ? 4 : 2)) {
+		dwtx_set_error("view: sample_bytes %d does not match the float type (%d bytes a sample)", v->sample_bytes, kind == DWTX_SAMPLE_F32 ? 4 : 2);
+		return DWTX_ERR_ARG;
+	}
+	if ((kind < 0 && v->sample_bytes != 1 && v->sample_bytes != 2) || (v->channels != 1 && v->channels != 3) || v->cols < 0) {
 		dwtx_set_error("view: sample_bytes %d (1 or 2), channels %d (1 or 3), cols %d (>= 0)", v->sample_bytes, v->channels, v->cols);
 		return DWTX_ERR_ARG;
 	}
@@ -437,8 +444,9 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 			}
 		}
 	}
-	*px = v->sample_bytes == 1 ? dwtx_pixels8((const uint8_t *)v->dev, v->channels, v->image_stride)
-		: dwtx_pixels16((const uint16_t *)v->dev, v->channels, v->image_stride, dst ? v->maxval : 65535);
+	*px = kind >= 0            ? dwtx_pixels_float(v->dev, kind, v->channels, v->image_stride, v->maxval)
+		: v->sample_bytes == 1 ? dwtx_pixels8((const uint8_t *)v->dev, v->channels, v->image_stride)
+		                       : dwtx_pixels16((const uint16_t *)v->dev, v->channels, v->image_stride, dst ? v->maxval : 65535);
 	px->row_pitch = v->row_pitch;
 	px->channel_stride = cs;
 	px->pixel_step = step;
@@ -502,6 +510,34 @@ extern "C" int dwtx_decode_view_order(dwtx_ctx *ctx, const uint8_t *dev_streams,
 	dwtx_pixels px;
 	if (const int rc = pixels_of_view(dst, pixel_step, order, W, H, n, true, &px))
 		return rc;
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
+}
+
+extern "C" int dwtx_decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
+	const dwtx_float_format *fmt, dwtx_decode_info *host_info)
+{
+	if (!fmt) {
+		dwtx_set_error("float view: no dwtx_float_format");
+		return DWTX_ERR_ARG;
+	}
+	if (fmt->type != DWTX_FLOAT32 && fmt->type != DWTX_FLOAT16 && fmt->type != DWTX_BFLOAT16) {
+		dwtx_set_error("float view: type %d (DWTX_FLOAT32 = 0, DWTX_FLOAT16 = 1 or DWTX_BFLOAT16 = 2)", fmt->type);
+		return DWTX_ERR_ARG;
+	}
+	for (int c = 0; c < 3; ++c)
+		if (!isfinite(fmt->scale[c]) || !isfinite(fmt->bias[c])) {
+			dwtx_set_error("float view: scale[%d] = %g, bias[%d] = %g: both must be finite", c, (double)fmt->scale[c], c, (double)fmt->bias[c]);
+			return DWTX_ERR_ARG;
+		}
+	const int kind = fmt->type == DWTX_FLOAT32 ? DWTX_SAMPLE_F32 : fmt->type == DWTX_FLOAT16 ? DWTX_SAMPLE_F16 : DWTX_SAMPLE_BF16;
+	dwtx_pixels px;
+	if (const int rc = pixels_of_view(dst, pixel_step, order, W, H, n, true, &px, kind))
+		return rc;
+	for (int c = 0; c < 3; ++c) {
+		px.scale[c] = fmt->scale[c];
+		px.bias[c] = fmt->bias[c];
+	}
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
 }
 

@@ -187,9 +187,14 @@ template <class F> char *carve(dwtx_ctx *ctx, int slot, F &&fn)
 // The three channels may lie as B, G, R (order, the *_view_order calls only): base and every stride stay what they are — base
 // is the lowest-addressed channel's first sample — and only lift.hip's last step to the kernels (red(), colour_stride())
 // knows: no check and no choice of path looks at the order.
+// A destination may hold floating-point samples (kind, dwtx_decode_view_float only): what the integer sinks would write
+// there, times scale plus bias per COLOUR, converted.  sample_bytes stays the addressing unit (4, or 2 for the half types);
+// a float view takes the 8-bit pixels' route through the pipelines whatever its maxval (deep() is false: 16-bit ring planes
+// where the streams' plane counts allow them), with the clamp bound always passed along.
+enum dwtx_sample_kind { DWTX_SAMPLE_U8 = 0, DWTX_SAMPLE_U16, DWTX_SAMPLE_F32, DWTX_SAMPLE_F16, DWTX_SAMPLE_BF16 };
 struct dwtx_pixels {
 	void *base;            // the grid's window 0, first sample
-	int sample_bytes;      // 1 or 2
+	int sample_bytes;      // 1 or 2; a float destination's 4 or 2 (kind says which samples they are)
 	int channels;          // 1 gray, 3 RGB (interleaved unless channel_stride says otherwise)
 	size_t image_stride;   // from a window to the next one of its band
 	int maxval;            // 255 for bytes; a deep picture's own (what the inverse direction clamps at)
@@ -200,8 +205,12 @@ struct dwtx_pixels {
 	size_t channel_stride = 0;   // 0: interleaved; else planar RGB: from a window's plane of one channel to the next one's (image() and moved() keep it)
 	size_t pixel_step = 0;       // 0: dense (a pixel is its channels); else from a pixel to the next one of its row, above channels (image() and moved() keep it)
 	int order = DWTX_ORDER_RGB;  // which colour the three channels are as they lie (DWTX_ORDER_*; image() and moved() keep it); gray pixels have none
+	int kind = DWTX_SAMPLE_U8;   // dwtx_sample_kind (dwtx_pixels8 / dwtx_pixels16 / dwtx_pixels_float set it with sample_bytes)
+	float scale[3] = { 1.f, 1.f, 1.f }, bias[3] = { 0.f, 0.f, 0.f };   // float samples: per colour R, G, B (gray: [0])
 
-	bool deep() const { return sample_bytes == 2; }
+	// uint16_t samples — and with them the kernel family that clamps at maxval and keeps no 16-bit ring planes
+	bool deep() const { return kind == DWTX_SAMPLE_U16; }
+	bool is_float() const { return kind >= DWTX_SAMPLE_F32; }
 	size_t bytes(size_t samples) const { return samples * (size_t)sample_bytes; }
 	void *at(size_t sample) const { return static_cast<char *>(base) + bytes(sample); }
 	// typed for the kernels: u16() for deep pixels; u8() for bytes — and for the fields that carry either kind as bytes
@@ -246,8 +255,8 @@ struct dwtx_pixels {
 	bool aligned(size_t a) const { return ((uintptr_t)base & (a - 1)) == 0; }
 	bool sample_aligned() const { return aligned((size_t)sample_bytes); }
 	// What lift.hip's wide kernels ask of the buffer when the finest level reads / writes the pixels itself: a lane's
-	// quad of samples — 4 bytes, 8 of a deep picture (gray, and each plane of planar RGB; interleaved RGB lanes take three) — is
-	// one aligned access in every row of every image
+	// quad of samples — 4 bytes, 8 of a deep picture or of half floats, 16 of fp32 (gray, and each plane of planar RGB;
+	// interleaved RGB lanes take three) — is one aligned access in every row of every image
 	bool wide() const
 	{
 		return image_stride % 4 == 0 && row_pitch % 4 == 0 && band_stride % 4 == 0 && channel_stride % 4 == 0 && aligned(4 * (size_t)sample_bytes);
@@ -259,7 +268,16 @@ static inline dwtx_pixels dwtx_pixels8(const uint8_t *pix, int channels, size_t 
 }
 static inline dwtx_pixels dwtx_pixels16(const uint16_t *pix, int channels, size_t image_stride, int maxval = 65535)
 {
-	return dwtx_pixels{ const_cast<uint16_t *>(pix), 2, channels, image_stride, maxval };
+	dwtx_pixels p{ const_cast<uint16_t *>(pix), 2, channels, image_stride, maxval };
+	p.kind = DWTX_SAMPLE_U16;
+	return p;
+}
+// a float destination (kind: DWTX_SAMPLE_F32 / _F16 / _BF16); the caller fills scale and bias
+static inline dwtx_pixels dwtx_pixels_float(void *pix, int kind, int channels, size_t image_stride, int maxval)
+{
+	dwtx_pixels p{ pix, kind == DWTX_SAMPLE_F32 ? 4 : 2, channels, image_stride, maxval };
+	p.kind = kind;
+	return p;
 }
 
 // lift.hip: the finest lifting level reads / writes pixels itself (the widening of pnm.h:69-74, the clamp of pnm.h:108
@@ -267,6 +285,7 @@ static inline dwtx_pixels dwtx_pixels16(const uint16_t *pix, int channels, size_
 // the buffer allow it: W % 4 == 0, more than 64 pixels on a side (the wide kernel, not the LDS tail), px.wide() (a planar
 // picture's channel stride on the quad grid too), and windows the kernels can address (lift.hip).  Of the stepped views
 // (dwtx_pixels::pixel_step) only 8-bit RGB in 4-byte pixels qualifies: every other one takes the general conversions.
+// Of float destinations gray and planar RGB qualify (the inverse direction only); interleaved float RGB takes the general way.
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H);
 // lift.hip: asks for the scratch planes every lifting call of a W*H transform over nplanes planes asks for
 int dwtx_lift_scratch(dwtx_ctx *ctx, int W, int H, int nplanes);

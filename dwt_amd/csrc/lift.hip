@@ -67,6 +67,13 @@ struct LevelArgs {
 	WinGrid grid;          // the windows behind src8 / dst8 (src_ps / ll_ps apart in a band)
 };
 
+// A float destination (dwtx_pixels::kind): scale and bias per COLOUR — R, G, B, whatever the order the channels lie in; gray
+// uses [0] — and which of the two 16-bit types a Half16 sink writes (the two differ in the convert only: one kernel for both)
+struct FloatFmt {
+	float scale[3], bias[3];
+	int bf16;
+};
+
 // ---------------------------------------------------------------- forward ---
 
 struct FwdLane {
@@ -296,7 +303,8 @@ struct LevelArgsW {
 	HistArgs hist;
 	long cstride;     // planar RGB pixels behind src8 / dst8 (dwtx_pixels::colour_stride(), in samples): from a window's R plane to its G plane, from G to B — negative
 	                  // where the planes lie as B, G, R (src8 / dst8 is then the R plane all the same); 0: interleaved.
-	                  // (Last, so that the interleaved kernels find their arguments where they were.)
+	                  // (After everything else, so that the interleaved kernels find their arguments where they were.)
+	FloatFmt fmt;     // inverse, float pixels behind dst8 (only the float sinks read it)
 };
 
 // Per lane and subband: counts of "magnitude below 2^q" for q = 0..15 — nibbles of R for the last few coefficients
@@ -1611,6 +1619,67 @@ struct OutRow<uint8_t> {
 	static __device__ __forceinline__ void store(uint8_t *__restrict__ row, int qd, const type &v) { *reinterpret_cast<unsigned *>(row + 4 * qd) = v; }
 };
 
+// ---- float sinks: the value an integer sink would write, as a float: v * scale + bias in fp32, then the sample's type ----
+// Two roundings, as torch's unfused `x.float() * scale + bias` has them.  hipcc contracts a * b + c into an fma by default, and
+// __fmul_rn / __fadd_rn are plain operators in a header compiled that way — they fuse all the same (v_fma_f32, and
+// v_fma_mixlo_f16 straight into the half) — so the two operations stand here, under a pragma that forbids it.
+__device__ __forceinline__ float float_of(int v, float scale, float bias)
+{
+#pragma clang fp contract(off)
+	const float m = (float)v * scale;
+	return m + bias;
+}
+// round to nearest even, overflow to infinity, subnormals kept: v_cvt_f16_f32 / v_cvt_pk_f16_f32 and v_cvt_pk_bf16_f32 under the
+// default rounding mode (the compiler picks the packed forms itself; never v_cvt_pkrtz_f16_f32, which truncates)
+__device__ __forceinline__ unsigned f16_bits(float f) { return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)f); }
+__device__ __forceinline__ unsigned bf16_bits(float f) { return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)f); }
+// four 16-bit floats of either type (uniform choice: a scalar branch)
+__device__ __forceinline__ uint2 half_quad(const float (&f)[4], int bf16)
+{
+	if (bf16)
+		return make_uint2(bf16_bits(f[0]) | (bf16_bits(f[1]) << 16), bf16_bits(f[2]) | (bf16_bits(f[3]) << 16));
+	return make_uint2(f16_bits(f[0]) | (f16_bits(f[1]) << 16), f16_bits(f[2]) | (f16_bits(f[3]) << 16));
+}
+// the sample type of the wide kernels' 16-bit float sinks: fp16 or bf16, FloatFmt::bf16 says which
+struct Half16 {
+	uint16_t bits;
+};
+// value: a float sink, whose of() takes the conversion; AT_STORE: its RGB sink converts in store() instead (see RgbOut<float, PIX_PLANAR>)
+template <typename T>
+struct FloatSample {
+	static constexpr bool value = false, AT_STORE = false;
+};
+template <>
+struct FloatSample<float> {
+	static constexpr bool value = true, AT_STORE = true;
+};
+template <>
+struct FloatSample<Half16> {
+	static constexpr bool value = true, AT_STORE = false;
+};
+// four gray pixels clamped to [0, M] (pnm.h:108 at the picture's maxval) as floats: 16 bytes per lane, 8 of the half types
+template <>
+struct OutRow<float> {
+	typedef float4 type;
+	static __device__ __forceinline__ type of(const Quad4 &v, int M, const FloatFmt &f)
+	{
+		auto c = [M, &f](int x) { return float_of(x < 0 ? 0 : x > M ? M : x, f.scale[0], f.bias[0]); };
+		return make_float4(c(v.v[0]), c(v.v[1]), c(v.v[2]), c(v.v[3]));
+	}
+	static __device__ __forceinline__ void store(float *__restrict__ row, int qd, const type &v) { *reinterpret_cast<float4 *>(row + 4 * qd) = v; }
+};
+template <>
+struct OutRow<Half16> {
+	typedef uint2 type;
+	static __device__ __forceinline__ type of(const Quad4 &v, int M, const FloatFmt &f)
+	{
+		auto c = [M, &f](int x) { return float_of(x < 0 ? 0 : x > M ? M : x, f.scale[0], f.bias[0]); };
+		const float q[4] = { c(v.v[0]), c(v.v[1]), c(v.v[2]), c(v.v[3]) };
+		return half_quad(q, f.bf16);
+	}
+	static __device__ __forceinline__ void store(Half16 *__restrict__ row, int qd, const type &v) { *reinterpret_cast<uint2 *>(row + 4 * qd) = v; }
+};
+
 template <typename DstT>
 __device__ __forceinline__ DstT *inv_dst(const LevelArgs &a);
 template <>
@@ -1619,6 +1688,10 @@ template <>
 __device__ __forceinline__ uint8_t *inv_dst<uint8_t>(const LevelArgs &a) { return a.dst8; }
 template <>
 __device__ __forceinline__ uint16_t *inv_dst<uint16_t>(const LevelArgs &a) { return reinterpret_cast<uint16_t *>(a.dst8); }   // (ll_ps, llpitch in samples)
+template <>
+__device__ __forceinline__ float *inv_dst<float>(const LevelArgs &a) { return reinterpret_cast<float *>(a.dst8); }
+template <>
+__device__ __forceinline__ Half16 *inv_dst<Half16>(const LevelArgs &a) { return reinterpret_cast<Half16 *>(a.dst8); }
 // (planes lie one after the other; pixels may be windows of a frame)
 template <typename DstT>
 __device__ __forceinline__ long inv_dst_off(const LevelArgs &a, int plane) { return win_off(a.grid, a.ll_ps, plane); }
@@ -1722,7 +1795,8 @@ __device__ __forceinline__ Quad4 inv_row_vals_h(int qd, int nquads, int lane, co
 }
 
 // Inverse level: int32 planes, or — the finest level of a gray image — clamped 8-bit pixels out (and, F16, the detail
-// bands in as 16-bit values).  The loop is batched like the forward kernel's (see there): one wait per S row pairs.
+// bands in as 16-bit values); DstT = float / Half16: the clamped pixels (at a.maxval, whatever it is) as floats, A.fmt.
+// The loop is batched like the forward kernel's (see there): one wait per S row pairs.
 template <typename DstT, bool F16>
 __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 {
@@ -1791,8 +1865,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 			RowLH e, o, ex, ox;
 			inv_cols(a, jj, c, cur[s], e, o);
 			inv_cols(a, jj, cx, curx[s], ex, ox);
-			orow[2 * s] = Out::of(inv_row_vals_h(qd, A.nquads, lane, e, ex), a.maxval);
-			orow[2 * s + 1] = Out::of(inv_row_vals_h(qd, A.nquads, lane, o, ox), a.maxval);
+			if constexpr (FloatSample<DstT>::value) {
+				orow[2 * s] = Out::of(inv_row_vals_h(qd, A.nquads, lane, e, ex), a.maxval, A.fmt);
+				orow[2 * s + 1] = Out::of(inv_row_vals_h(qd, A.nquads, lane, o, ox), a.maxval, A.fmt);
+			} else {
+				orow[2 * s] = Out::of(inv_row_vals_h(qd, A.nquads, lane, e, ex), a.maxval);
+				orow[2 * s + 1] = Out::of(inv_row_vals_h(qd, A.nquads, lane, o, ox), a.maxval);
+			}
 		}
 	}
 	store_batch(j0 + (j1 - 1 - j0) / S * S);
@@ -2173,6 +2252,43 @@ struct RgbOut<uint16_t, PIX_PLANAR> {
 			*reinterpret_cast<uint2 *>(p + c * cs) = make_uint2(v.w[2 * c], v.w[2 * c + 1]);
 	}
 };
+// planar float pixels: the colour transform and its clamps at M, then each plane's quad through its own colour's scale and
+// bias (px[c] is colour c wherever its plane lies: B, G, R planes come with a negative cs): 16 bytes per plane and lane, or 8.
+// fp32 rows wait for their store as the deep sink's clamped integers — six registers, not twelve, which keeps the kernel
+// below 128 — and become floats in store(), which takes the conversion (FloatSample<float>::AT_STORE)
+template <>
+struct RgbOut<float, PIX_PLANAR> {
+	typedef Rgb24 row;
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M, const FloatFmt &) { return rgb16_planar_of(y, co, cg, M); }
+	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long cs, const FloatFmt &f)
+	{
+		float *p = reinterpret_cast<float *>(dst) + r * pitch + 4 * qd;
+#pragma unroll
+		for (int c = 0; c < 3; ++c) {
+			const unsigned lo = v.w[2 * c], hi = v.w[2 * c + 1];
+			*reinterpret_cast<float4 *>(p + c * cs) = make_float4(float_of((int)(lo & 0xffffu), f.scale[c], f.bias[c]), float_of((int)(lo >> 16), f.scale[c], f.bias[c]),
+				float_of((int)(hi & 0xffffu), f.scale[c], f.bias[c]), float_of((int)(hi >> 16), f.scale[c], f.bias[c]));
+		}
+	}
+};
+template <>
+struct RgbOut<Half16, PIX_PLANAR> : RgbOut<uint16_t, PIX_PLANAR> {   // (the deep planar sink's row and store: the same 8 bytes per plane)
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M, const FloatFmt &f)
+	{
+		unsigned px[3][4];
+		rgb_planes_of(y, co, cg, M, px);
+		row o;
+#pragma unroll
+		for (int c = 0; c < 3; ++c) {
+			const float q[4] = { float_of((int)px[c][0], f.scale[c], f.bias[c]), float_of((int)px[c][1], f.scale[c], f.bias[c]),
+				float_of((int)px[c][2], f.scale[c], f.bias[c]), float_of((int)px[c][3], f.scale[c], f.bias[c]) };
+			const uint2 h = half_quad(q, f.bf16);
+			o.w[2 * c] = h.x;
+			o.w[2 * c + 1] = h.y;
+		}
+		return o;
+	}
+};
 template <bool BGR = false>
 __device__ __forceinline__ Rgbx16 rgbx_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg)
 {
@@ -2236,6 +2352,7 @@ struct RgbOut<uint8_t, PIX_STEP4_BGR> : RgbOut<uint8_t, PIX_STEP4> {
 // PixT = uint16_t: deep pixels (dst8 points to uint16_t samples, ll_ps / llpitch count samples, clamps at a.maxval)
 // PIX_PLANAR: dst8 is the R plane of the window, G and B A.cstride samples apart each (signed), llpitch the pitch of a plane's rows
 // PIX_STEP4: llpitch is the pitch of rows of 4-byte pixels; the step is the constant 4 here, no argument carries it
+// PixT = float / Half16 (PIX_PLANAR only): float samples, strides in samples, clamps at a.maxval, the conversion in A.fmt
 template <bool F16, typename PixT = uint8_t, PixLayout LAYOUT = PIX_PACKED>
 __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 {
@@ -2274,9 +2391,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 	typename Out::row orow[2];
 	auto store_pair = [&](int j) {
 		if (writes) {   // twelve bytes per lane in one store: the wave's 56 lanes write 672 consecutive bytes (deep pixels: twice that; planar: a third of it to each plane)
-			Out::store(dst, a.llpitch, 2 * j, qd, orow[0], A.cstride);
-			if (2 * j + 1 < a.h)
-				Out::store(dst, a.llpitch, 2 * j + 1, qd, orow[1], A.cstride);
+			if constexpr (FloatSample<PixT>::AT_STORE) {
+				Out::store(dst, a.llpitch, 2 * j, qd, orow[0], A.cstride, A.fmt);
+				if (2 * j + 1 < a.h)
+					Out::store(dst, a.llpitch, 2 * j + 1, qd, orow[1], A.cstride, A.fmt);
+			} else {
+				Out::store(dst, a.llpitch, 2 * j, qd, orow[0], A.cstride);
+				if (2 * j + 1 < a.h)
+					Out::store(dst, a.llpitch, 2 * j + 1, qd, orow[1], A.cstride);
+			}
 		}
 	};
 	for (int jj = j0; jj < j1; ++jj) {
@@ -2294,8 +2417,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 #pragma unroll
 		for (int ch = 0; ch < 3; ++ch)
 			inv_pair(a, jj, qd, A.nquads, c[ch], cur[ch], even[ch], odd[ch]);
-		orow[0] = Out::of(even[0], even[1], even[2], a.maxval);
-		orow[1] = Out::of(odd[0], odd[1], odd[2], a.maxval);
+		if constexpr (FloatSample<PixT>::value) {
+			orow[0] = Out::of(even[0], even[1], even[2], a.maxval, A.fmt);
+			orow[1] = Out::of(odd[0], odd[1], odd[2], a.maxval, A.fmt);
+		} else {
+			orow[0] = Out::of(even[0], even[1], even[2], a.maxval);
+			orow[1] = Out::of(odd[0], odd[1], odd[2], a.maxval);
+		}
 	}
 	store_pair(j1 - 1);
 }
@@ -2644,8 +2772,19 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi)
 // reference has 255: Y and the output to [0, M], Co and Cg to [-M, M].  P = uint8_t (M = 255) or uint16_t.  Same grid as
 // above; only the C samples of the W pixels of a window's H rows are written — with a column step above C nothing between
 // the pixels is: no word is read, merged and written back (another stream may be writing the samples in between).
+// P = float, _Float16 or __bf16: the same clamped integers through float_of with colour c's scale and bias (f; the integer
+// instances do not read it), any layout the integer instances take.
 template <class P>
-__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, int M)
+__device__ __forceinline__ P sample_of(int v, const FloatFmt &, int) { return (P)v; }
+template <>
+__device__ __forceinline__ float sample_of<float>(int v, const FloatFmt &f, int c) { return float_of(v, f.scale[c], f.bias[c]); }
+template <>
+__device__ __forceinline__ _Float16 sample_of<_Float16>(int v, const FloatFmt &f, int c) { return (_Float16)float_of(v, f.scale[c], f.bias[c]); }
+template <>
+__device__ __forceinline__ __bf16 sample_of<__bf16>(int v, const FloatFmt &f, int c) { return (__bf16)float_of(v, f.scale[c], f.bias[c]); }
+
+template <class P>
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, int M, FloatFmt f)
 {
 	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
 	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
@@ -2656,7 +2795,7 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__
 		P *row = pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
 		const int *src = planes + (long)win * g.C * npix + (long)y * g.W + x;
 		if (g.C == 1) {
-			row[(long)x * g.col_step] = (P)clampi(src[0], 0, M);
+			row[(long)x * g.col_step] = sample_of<P>(clampi(src[0], 0, M), f, 0);
 		} else {
 			const int yy = clampi(src[0], 0, M);
 			const int co = clampi(src[npix], -M, M);
@@ -2666,9 +2805,9 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__
 			const int b = t - tdiv2(co);
 			const int r = b + co;
 			P *p = row + (long)x * g.col_step;
-			p[0] = (P)clampi(r, 0, M);
-			p[g.chan_stride] = (P)clampi(gr, 0, M);
-			p[2 * g.chan_stride] = (P)clampi(b, 0, M);
+			p[0] = sample_of<P>(clampi(r, 0, M), f, 0);
+			p[g.chan_stride] = sample_of<P>(clampi(gr, 0, M), f, 1);
+			p[2 * g.chan_stride] = sample_of<P>(clampi(b, 0, M), f, 2);
 		}
 	}
 }
@@ -2766,10 +2905,22 @@ static PixGrid pix_grid(const dwtx_pixels &px, int W, int H, int n, dim3 *grid)
 	return PixGrid{ (long)px.image_stride, (long)px.pitch(W), win_grid(px), W, H, px.channels, n, px.colour_stride(), (int)px.step() };
 }
 
+// the kernels' copy of a float destination's conversion (integer pixels: the identity, which nothing reads)
+static FloatFmt float_fmt(const dwtx_pixels &px)
+{
+	FloatFmt f;
+	for (int c = 0; c < 3; ++c) {
+		f.scale[c] = px.scale[c];
+		f.bias[c] = px.bias[c];
+	}
+	f.bf16 = px.kind == DWTX_SAMPLE_BF16;
+	return f;
+}
+
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
 {
 	const int C = px.channels;
-	if (!ctx || !planes || !px.base || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || !px.sample_aligned())
+	if (!ctx || !planes || !px.base || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || !px.sample_aligned() || px.is_float())   // (a float source has no lossless meaning)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	dim3 grid;
@@ -2792,10 +2943,27 @@ int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *p
 	DWTX_ENTER(ctx);
 	dim3 grid;
 	const PixGrid g = pix_grid(px, W, H, n, &grid);
-	if (!px.deep())
-		hipLaunchKernelGGL(k_pixels_from_planes<uint8_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<uint8_t *>(px.red()), planes, g, px.maxval);
-	else
-		hipLaunchKernelGGL(k_pixels_from_planes<uint16_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<uint16_t *>(px.red()), planes, g, px.maxval);
+	const FloatFmt f = float_fmt(px);
+	const dim3 block(PX_LANES * PX_ROWS);
+	switch (px.kind) {
+	case DWTX_SAMPLE_U8:
+		hipLaunchKernelGGL(k_pixels_from_planes<uint8_t>, grid, block, 0, ctx->stream, static_cast<uint8_t *>(px.red()), planes, g, px.maxval, f);
+		break;
+	case DWTX_SAMPLE_U16:
+		hipLaunchKernelGGL(k_pixels_from_planes<uint16_t>, grid, block, 0, ctx->stream, static_cast<uint16_t *>(px.red()), planes, g, px.maxval, f);
+		break;
+	case DWTX_SAMPLE_F32:
+		hipLaunchKernelGGL(k_pixels_from_planes<float>, grid, block, 0, ctx->stream, static_cast<float *>(px.red()), planes, g, px.maxval, f);
+		break;
+	case DWTX_SAMPLE_F16:
+		hipLaunchKernelGGL(k_pixels_from_planes<_Float16>, grid, block, 0, ctx->stream, static_cast<_Float16 *>(px.red()), planes, g, px.maxval, f);
+		break;
+	case DWTX_SAMPLE_BF16:
+		hipLaunchKernelGGL(k_pixels_from_planes<__bf16>, grid, block, 0, ctx->stream, static_cast<__bf16 *>(px.red()), planes, g, px.maxval, f);
+		break;
+	default:
+		return DWTX_ERR_ARG;
+	}
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
@@ -2933,7 +3101,7 @@ static WideKernel fwd_wide_kernel(int src, bool hist)
 static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_pixels *px, int W, int H, int nplanes,
 	const dwtx_hist_sink *sink = nullptr, unsigned *hist_levels = nullptr, dwtx_p16 p16 = dwtx_p16{ nullptr, 0u })
 {
-	if (px && px->deep() && (sink || p16.planes))
+	if (px && (px->is_float() || (px->deep() && (sink || p16.planes))))
 		return DWTX_ERR_ARG;
 	if (hist_levels)
 		*hist_levels = 0u;
@@ -3100,7 +3268,8 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 // Any other view goes through the general conversions (dwtx_pixels_to_planes / dwtx_planes_to_pixels).
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H)
 {
-	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide() && px.pitch(W) <= 0x7fffffffu && (!px.stepped() || px.rgbx8());
+	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide() && px.pitch(W) <= 0x7fffffffu && (!px.stepped() || px.rgbx8()) &&
+		(!px.is_float() || px.channels == 1 || px.planar());   // (float sinks: OutRow<F> and RgbOut<F, PIX_PLANAR>; interleaved float RGB has none)
 }
 
 unsigned dwtx_levels16(int W, int H, unsigned sq_levels)
@@ -3159,6 +3328,14 @@ static Inv2Kernel inv2_kernel(const dwtx_pixels *px, bool det16)
 // The wide kernel of an inverse step.  px: the step writes these pixels (gray or RGB; deep ones never from 16-bit bands)
 static WideKernel inv_wide_kernel(const dwtx_pixels *px, bool det16)
 {
+	if (px && px->is_float()) {   // gray, or planar RGB in either order (dwtx_pixels_ok); from int32 and from 16-bit bands
+		const bool f32 = px->kind == DWTX_SAMPLE_F32;
+		if (px->channels == 3)
+			return f32 ? (det16 ? k_inv_level_w_rgb<true, float, PIX_PLANAR> : k_inv_level_w_rgb<false, float, PIX_PLANAR>)
+			           : (det16 ? k_inv_level_w_rgb<true, Half16, PIX_PLANAR> : k_inv_level_w_rgb<false, Half16, PIX_PLANAR>);
+		return f32 ? (det16 ? k_inv_level_w<float, true> : k_inv_level_w<float, false>)
+		           : (det16 ? k_inv_level_w<Half16, true> : k_inv_level_w<Half16, false>);
+	}
 	const int channels8 = px && !px->deep() ? px->channels : 0;
 	if (px && px->channels == 3 && px->planar()) {
 		if (px->deep())
@@ -3215,8 +3392,8 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 	auto can_fuse = [&](int t) {   // (t == T - 1 reads the root LL in the pyramid itself: no pair there)
 		if (!fusing || t < 1 || t == T - 1 || ws[t - 1] % 4 != 0 || hs[t - 1] % 4 != 0 || in16(t) != in16(t - 1))
 			return false;
-		if (t - 1 == 0 && px)   // (the 8-bit variants exist for 16-bit bands only: what the pipelines run; RGB: three planes per wave)
-			return in16(0) && (px->channels == 1 || (px->channels == 3 && nplanes % 3 == 0));
+		if (t - 1 == 0 && px)   // (the 8-bit variants exist for 16-bit bands only: what the pipelines run; RGB: three planes per wave; no float ones)
+			return !px->is_float() && in16(0) && (px->channels == 1 || (px->channels == 3 && nplanes % 3 == 0));
 		return true;
 	};
 	// Steps t .. 0 with the planes from here on assigned with `fl`: the most samples that can go through two-level steps (a pair is
@@ -3333,7 +3510,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 			a.ll_ps = (long)px->image_stride;
 			a.llpitch = (int)px->pitch(W);
 			a.grid = win_grid(*px);
-			a.maxval = px->deep() ? px->maxval : 0;
+			a.maxval = px->deep() || px->is_float() ? px->maxval : 0;   // (float sinks clamp at whatever the maxval is, 255 included)
 		} else if (t == 0) {
 			a.ll = out;
 			a.ll_ps = full_ps;
@@ -3365,6 +3542,8 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 			a.rpw = pick_rpw(sx, a.h2, nplanes, forced);
 			A.a = a;
 			A.cstride = rgb ? wide_cstride(*px) : 0;
+			if (pix_out)
+				A.fmt = float_fmt(*px);
 			const dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), rgb ? nplanes / 3 : nplanes);
 			hipLaunchKernelGGL(inv_wide_kernel(pix_out, a.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {

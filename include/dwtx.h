@@ -435,6 +435,38 @@ int dwtx_encode_view_order(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_ste
 int dwtx_decode_view_order(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
 	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, dwtx_decode_info *host_info);
 
+/* ---- float destinations: decode straight into fp32, fp16 and bf16 tensors ---------------------------------------------
+ * dwtx_decode_view_order for destinations that hold floating-point samples: what a training or inference pipeline does
+ * with a decoded batch on its next line — `x.float() * scale + bias`, or `.half()` — without the integer frame in between,
+ * its second pass and its memory.  Decode only: a float source has no lossless meaning.
+ * Destination: dst->sample_bytes must equal the size of fmt->type (4, or 2 for the two half types); every stride of the
+ * view, and pixel_step, count samples of that type; dev is aligned to the sample.  dst->maxval is what the streams were
+ * encoded from, 1..65535: the same call covers 8-bit and deep streams.
+ * Value written: for colour c of a pixel, with v the integer that dwtx_decode_view_order would write there with that maxval
+ * (all clamps of image.h:41-43 and pnm.h:108 applied, on colours): f = (float)v * scale[c], rounded to fp32, then
+ * f + bias[c], rounded to fp32 — two roundings, no fused multiply-add: bit for bit the unfused line above — then converted
+ * to fmt->type, round to nearest even.  fp16 overflow goes to infinity and fp16 subnormals are kept, as torch's conversion
+ * does; what becomes of an fp32-subnormal intermediate is not pinned.  scale and bias belong to COLOURS (R, G, B), not to
+ * memory positions: with DWTX_ORDER_BGR the sample at the lowest address gets scale[2] and bias[2].  Gray uses [0].
+ * Everything the integer views guarantee holds word for word: only the `channels` samples of the pixels of the ow x oh
+ * rectangle a stream supports are written, nothing between pixels, nothing of the frame around the windows; the
+ * disjointness rules apply with the same formulas; planar, stacked, side-by-side and band forms are accepted; pixel_step
+ * and order keep their meaning; the windows of streams with status 1 or 2 are left untouched.
+ * Gray and planar RGB windows with W % 4 == 0, more than 64 pixels on a side and every row on the quad grid of the float
+ * sample (16 bytes for fp32, 8 for the half types) are written by the inverse transform's last level itself; every other
+ * view (interleaved float RGB among them) through int32 planes and the general conversion — the same bits, one pass more.
+ * DWTX_ERR_ARG (with a dwtx_last_error() text, nothing written): fmt == NULL, an unknown type, a sample_bytes that does not
+ * match the type, a scale or bias that is not finite, and everything dwtx_decode_view_order refuses. */
+enum { DWTX_FLOAT32 = 0, DWTX_FLOAT16 = 1, DWTX_BFLOAT16 = 2 };
+typedef struct dwtx_float_format {
+	int   type;       /* DWTX_FLOAT32 / _FLOAT16 / _BFLOAT16 */
+	float scale[3];   /* per COLOUR (R, G, B — not memory position); gray uses [0] */
+	float bias[3];
+} dwtx_float_format;
+int dwtx_decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
+	const dwtx_float_format *fmt, dwtx_decode_info *host_info);
+
 /* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
  * interior, right column, bottom row, corner, in that order, those that exist — each a cols x rows grid of W x H tiles
  * whose first tile's corner is (x0, y0): one dwtx_encode_view / dwtx_decode_view call per group.  Per axis, with
