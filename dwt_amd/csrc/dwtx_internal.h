@@ -402,6 +402,14 @@ int dwtx_decode_planes_ex(dwtx_ctx *ctx, int32_t *lin, int32_t *pyr, const uint8
 // into 0/1 in a register and compared again — two extra instructions per use in the ballot-heavy kernels.)
 __device__ __forceinline__ unsigned long long ballot64(bool pred) { return __builtin_amdgcn_ballot_w64(pred); }
 
+// The wave's index inside its workgroup, as a SCALAR.  The compiler takes threadIdx.x >> 6 for a per-lane value, so what a
+// wave-per-item kernel derives from it (its tile, its LDS slice, every branch and table look-up on them) would stay in vector
+// registers under exec masks although no lane differs; readfirstlane says that it is one value.  That rests on one-dimensional
+// workgroups (threadIdx.y == threadIdx.z == 0) and wave64: lanes 64k .. 64k+63 of a workgroup are one wave, so all the lanes
+// of a wave share threadIdx.x >> 6, whichever of them are active and however long the workgroup's last wave is.  Every launch
+// of a kernel that calls this is dim3(N) or a plain thread count.
+__device__ __forceinline__ int wave_in_block() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
 // C truncating division by 2 and 4 on the device (cdf53.h:13,20 use `/`)
 __device__ __forceinline__ int tdiv2(int a) { return (a + (int)((unsigned)a >> 31)) >> 1; }
 __device__ __forceinline__ int tdiv4(int a) { return (a + ((a >> 31) & 3)) >> 2; }

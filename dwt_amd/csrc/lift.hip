@@ -111,7 +111,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_fwd_level(LevelArgs a)
 {
 	FwdLane L;
 	L.lane = threadIdx.x & 63;
-	const int wv = threadIdx.x >> 6;
+	const int wv = wave_in_block();
 	L.k = blockIdx.x * 64 + L.lane;
 	const int j0 = (blockIdx.y * WAVES + wv) * a.rpw;
 	if (j0 >= a.h2)
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level(LevelArgs a)
 {
 	InvLane L;
 	const int lane = threadIdx.x & 63;
-	const int wv = threadIdx.x >> 6;
+	const int wv = wave_in_block();
 	L.k = blockIdx.x * INV_PAIRS - 1 + lane;
 	const int j0 = (blockIdx.y * WAVES + wv) * a.rpw;
 	if (j0 >= a.h2)
@@ -722,7 +722,7 @@ __device__ __forceinline__ void st2nt(int *p, I2 v)
 
 __global__ __launch_bounds__(64 * WAVES) void k_fwd2_level_w(Level2Args a)
 {
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const int lane = threadIdx.x & 63, wv = wave_in_block();
 	int bx, by;
 	xcd_strip(bx, by);
 	const int strip = bx * WAVES + wv;                      // the block's waves side by side
@@ -1261,7 +1261,8 @@ __device__ __forceinline__ void fwd_level_body(const LevelArgsW &A, int bx, int 
 	typedef FwdSrc<Src> T;
 	typedef typename T::Pair Pair;
 	const LevelArgs &a = A.a;
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	// (the RGB sources' histogram kernels hold three bodies and spill scalar registers already: there the index stays per lane)
+	const int lane = threadIdx.x & 63, wv = HIST && T::RGB_GRID ? (int)(threadIdx.x >> 6) : wave_in_block();
 	const int sx = (bx << A.wx_log2) + (wv & ((1 << A.wx_log2) - 1));   // the wave's strip of 64 quads
 	const int q = sx * 64 + lane;
 	const int j0 = (by * (WAVES >> A.wx_log2) + (wv >> A.wx_log2)) * a.rpw;
@@ -1801,7 +1802,7 @@ template <typename DstT, bool F16>
 __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 {
 	const LevelArgs &a = A.a;
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const int lane = threadIdx.x & 63, wv = wave_in_block();
 	int bx, by;
 	xcd_strip(bx, by);
 	const int qd = bx * 64 + lane;   // all 64 lanes write: the halo columns ride along (InvHalo)
@@ -2357,7 +2358,7 @@ template <bool F16, typename PixT = uint8_t, PixLayout LAYOUT = PIX_PACKED>
 __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 {
 	const LevelArgs &a = A.a;
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const int lane = threadIdx.x & 63, wv = wave_in_block();
 	int bx, by;
 	xcd_strip(bx, by);
 	const int qd = bx * INV_QUADS - 1 + lane;

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(1024) void k_block_scan(LinGeom g, int *__restrict_
 {
 	__shared__ int wsum[16];
 	__shared__ int carry;
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;   // (one workgroup, once per geometry; as a scalar it costs instructions here)
 	for (int l = 0; l < g.levels; ++l) {
 		const int first = g.blk_first[l], nb = g.blk_first[l + 1] - first;
 		if (threadIdx.x == 0)
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(THREADS) void k_ring_copy(LinGeom g, const int *__r
 	if (((skip_levels >> l) & 1u) && full)
 		return;   // on these levels the entropy stage reads / writes whole squares in the pyramid itself
 	const int w0 = g.widths[l], h0 = g.heights[l], w1 = g.widths[l + 1], h1 = g.heights[l + 1];
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const int lane = threadIdx.x & 63, wv = wave_in_block();
 	const SquareMap smap = square_map(n, (unsigned)lb);   // uniform
 	int slot[PTS], lidx[PTS];
 	long offs[PTS], sq = 0;

@@ -421,7 +421,7 @@ __global__ __launch_bounds__(256) void k_hist_init(PackGeom g, Work w)
 __global__ __launch_bounds__(256) void k_hist(PackGeom g, const int *__restrict__ lin, Work w, unsigned done_levels)
 {
 	const int lane = threadIdx.x & 63;
-	const int tile0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * HIST_TPW;
+	const int tile0 = (blockIdx.x * 4 + wave_in_block()) * HIST_TPW;
 	const int plane = blockIdx.y;
 	if (tile0 >= w.NT)
 		return;
@@ -916,9 +916,6 @@ struct alignas(16) CodeLds {
 	};
 	unsigned short cum[MAX_PLANES + 2];   // the tile's histogram: #(t <= q), q = 0..16
 	unsigned short slot0[MAX_PLANES];     // plane p's first token slot
-	unsigned gb[MAX_PLANES];         // (16-plane variant) plane p: token index of the entry's first token; ~0: plane not coded
-	unsigned long long rb[MAX_PLANES];    // plane p: bit position of the entry's refinement bits in the staging buffer
-	int ent[MAX_PLANES];             // plane p: entry index, -1 = the plane is not coded for this tile
 };
 
 // NQ = number of count fields q = 0 .. NQ-1 (one nibble each): 8 when the channel has at most 8 bit planes (the
@@ -1063,15 +1060,19 @@ __device__ __forceinline__ void code_tile(CodeLds &L, const unsigned char *pext4
 	}
 	wave_sync();
 
-	// per-plane facts of the tile for the plane loops below (lane p holds plane p's)
-	if (lane < MAX_PLANES) {
-		L.gb[lane] = my_ent >= 0 ? my_tokbase : ~0u;
-		L.ent[lane] = my_ent;
-		L.rb[lane] = my_rb;
-	}
-	wave_sync();
-
 	auto cq = [&](int q) -> unsigned { return q < P && q < NQ ? CT(q) : (unsigned)nvalid; };   // q a constant
+	// The plane loops below run over a run-time p: what they need of plane p they take from lane p's registers with one
+	// v_readlane each, as scalars (read back from LDS, every fact was a vector load and its tests vector compares):
+	// my_ent (entry index, -1 = the plane is not coded for this tile), my_rb (bit position of the entry's refinement bits
+	// in the staging buffer), my_tokbase (token index of the entry's first token), and the tile's histogram and slots
+	const unsigned my_cum = L.cum[lane < MAX_PLANES + 2 ? lane : 0];   // lane q: #(t <= q)
+	const unsigned my_slot0 = L.slot0[lane < MAX_PLANES ? lane : 0];   // lane p: plane p's first token slot
+	auto cum_s = [&](int q) -> unsigned { return (unsigned)__builtin_amdgcn_readlane((int)my_cum, q); };
+	auto ent_s = [&](int p) -> int { return __builtin_amdgcn_readlane(my_ent, p); };
+	auto rb_lo_s = [&](int p) -> unsigned { return (unsigned)__builtin_amdgcn_readlane((int)(unsigned)my_rb, p); };
+	auto rb_s = [&](int p) -> unsigned long long {
+		return (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(my_rb >> 32), p) << 32 | rb_lo_s(p);
+	};
 
 	// The refinement bits go first: their last step adds the rows' edge words to the staging buffer with global atomics
 	// (the neighbouring tiles share those words), which take long to come back — issued here, they have the
@@ -1113,8 +1114,8 @@ __device__ __forceinline__ void code_tile(CodeLds &L, const unsigned char *pext4
 		const unsigned SA0 = (A0 >> 8) | (A0 >> 16) | (A0 >> 24) | ((SA1 | A1) & 0xffu) * 0x01010101u;
 		const unsigned SB0 = (B0 >> 8) | (B0 >> 16) | (B0 >> 24) | ((SB1 | B1) & 0xffu) * 0x01010101u;
 		auto plane_string = [&](int p, unsigned Aw, unsigned SAw, unsigned Bw, unsigned SBw) {
-			const int refs = nvalid - (int)L.cum[p + 1];
-			if (refs <= 0 || L.ent[p] < 0)
+			const int refs = nvalid - (int)cum_s(p + 1);
+			if (refs <= 0 || ent_s(p) < 0)
 				return;   // uniform
 			const unsigned sh8 = 8u * ((unsigned)p & 3u);
 			const unsigned nA = (Aw >> sh8) & 0xffu, sA = (SAw >> sh8) & 0xffu, nB = (Bw >> sh8) & 0xffu, sB = (SBw >> sh8) & 0xffu;
@@ -1122,7 +1123,7 @@ __device__ __forceinline__ void code_tile(CodeLds &L, const unsigned char *pext4
 			const unsigned e2 = pext4[((sB & 15u) << 4) | (nB & 15u)], e3 = pext4[(sB & 0xf0u) | (nB >> 4)];
 			const unsigned c0 = (unsigned)__builtin_popcount(sA & 15u), c1 = (unsigned)__builtin_popcount(sA);
 			const unsigned c2 = c1 + (unsigned)__builtin_popcount(sB & 15u), c3 = c1 + (unsigned)__builtin_popcount(sB);
-			deposit(p, e0 | e1 << c0 | e2 << c1 | e3 << c2, c3, L.tab[tab8(lane, p + 1)] & 0x3ffu, (unsigned)L.rb[p]);
+			deposit(p, e0 | e1 << c0 | e2 << c1 | e3 << c2, c3, L.tab[tab8(lane, p + 1)] & 0x3ffu, rb_lo_s(p));
 		};
 		for (int p = P - 2; p >= 4; --p)
 			plane_string(p, A1, SA1, B1, SB1);
@@ -1130,15 +1131,15 @@ __device__ __forceinline__ void code_tile(CodeLds &L, const unsigned char *pext4
 			plane_string(p, A0, SA0, B0, SB0);
 		wave_sync();
 		for (int p = P - 2; p >= 0; --p) {
-			const int refs = nvalid - (int)L.cum[p + 1];
-			if (refs <= 0 || L.ent[p] < 0)
+			const int refs = nvalid - (int)cum_s(p + 1);
+			if (refs <= 0 || ent_s(p) < 0)
 				continue;
-			row_out(p, refs, L.rb[p]);
+			row_out(p, refs, rb_s(p));
 		}
 	} else {
 		for (int p = P - 2; p >= 0; --p) {
-			const int refs = nvalid - (int)L.cum[p + 1];
-			if (refs <= 0 || L.ent[p] < 0)
+			const int refs = nvalid - (int)cum_s(p + 1);
+			if (refs <= 0 || ent_s(p) < 0)
 				continue;   // uniform
 			const unsigned thr = 2u << p;
 			unsigned acc = 0, cnt = 0;
@@ -1148,14 +1149,14 @@ __device__ __forceinline__ void code_tile(CodeLds &L, const unsigned char *pext4
 				acc |= (isref ? (mag[i] >> p) & 1u : 0u) << cnt;
 				cnt += isref ? 1u : 0u;
 			}
-			deposit(p, acc, cnt, L.tab[tab16(lane, p + 1)] & 0x3ffu, (unsigned)L.rb[p]);
+			deposit(p, acc, cnt, L.tab[tab16(lane, p + 1)] & 0x3ffu, rb_lo_s(p));
 		}
 		wave_sync();
 		for (int p = P - 2; p >= 0; --p) {
-			const int refs = nvalid - (int)L.cum[p + 1];
-			if (refs <= 0 || L.ent[p] < 0)
+			const int refs = nvalid - (int)cum_s(p + 1);
+			if (refs <= 0 || ent_s(p) < 0)
 				continue;
-			row_out(p, refs, L.rb[p]);
+			row_out(p, refs, rb_s(p));
 		}
 	}
 	wave_sync();   // the rows have been read: the token slots take their place
@@ -1202,8 +1203,8 @@ __device__ __forceinline__ void code_tile(CodeLds &L, const unsigned char *pext4
 		int first_slot = -1;
 		if (lane < MAX_PLANES) {
 			const int p = lane;
-			const unsigned c0 = L.cum[p], c1 = L.cum[p + 1];
-			const unsigned ones = c1 - c0, slot0 = L.slot0[p];
+			const unsigned c0 = my_cum, c1 = L.cum[p + 1];
+			const unsigned ones = c1 - c0, slot0 = my_slot0;
 			if (ones) {
 				first_slot = (int)slot0;
 				first_tok = L.zs[slot0];
@@ -1247,12 +1248,11 @@ __device__ __forceinline__ void code_tile(CodeLds &L, const unsigned char *pext4
 				*reinterpret_cast<uint4 *>(dst + head + 8 * c) = *reinterpret_cast<const uint4 *>(src + head + 8 * c);
 		};
 		for (int p = P > 0 ? P - 1 : 0; p >= 0; --p) {
-			const unsigned c0 = (unsigned)__builtin_amdgcn_readfirstlane((int)L.cum[p]), c1 = (unsigned)__builtin_amdgcn_readfirstlane((int)L.cum[p + 1]);
-			const int ones = (int)(c1 - c0);
-			const unsigned gb = (unsigned)__builtin_amdgcn_readfirstlane((int)L.gb[p]);
+			const int ones = (int)(cum_s(p + 1) - cum_s(p));
+			const unsigned gb = ent_s(p) >= 0 ? (unsigned)__builtin_amdgcn_readlane((int)my_tokbase, p) : ~0u;
 			if (ones <= 0 || gb == ~0u)
 				continue;   // uniform
-			plane_out(gb, (unsigned)__builtin_amdgcn_readfirstlane((int)L.slot0[p]), ones);
+			plane_out(gb, (unsigned)__builtin_amdgcn_readlane((int)my_slot0, p), ones);
 		}
 	}
 
@@ -1332,7 +1332,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
 {
 	__shared__ CodeLds lds[4];
 	__shared__ unsigned char pext4[256];
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	// (the deep planes' kernel keeps the index per lane: as a scalar it would push more scalar registers into spills there)
+	const int lane = threadIdx.x & 63, wv = WIDE ? (int)(threadIdx.x >> 6) : wave_in_block();
 	const int plane = blockIdx.y;
 	const int img = plane / g.C, c = plane - img * g.C;
 	if ((w.info[img].planes[c] > 8) != WIDE)
@@ -2083,7 +2084,7 @@ struct EmitLds {
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_emit(Work w, unsigned *out, long out_words)
 {
 	__shared__ EmitLds lds[4];
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;   // (not wave_in_block(): no fewer vector instructions here, and scalar registers spill)
 	const long wave = (long)blockIdx.x * 4 + wv;
 	const int img = blockIdx.y;
 	const ImgInfo &I = w.info[img];
@@ -2487,7 +2488,7 @@ __global__ __launch_bounds__(IDX_THREADS) void k_index(PackGeom g, Work w, dwtx_
 		}
 		return;
 	}
-	const int k = threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const int k = threadIdx.x, lane = threadIdx.x & 63, wv = wave_in_block();
 	const int *sd = w.seg_desc + (long)img * MAX_SEGS;
 	int num = 0;
 	if (k < K) {

@@ -2136,8 +2136,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
 	dep[4096 + threadIdx.x] = DEPOSIT.ref[threadIdx.x];
 	__syncthreads();
 	const unsigned char *dsym = dep, *dref = dep + 4096;
-	const int lane = threadIdx.x & 63;
-	const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
+	const int lane = threadIdx.x & 63, wv = wave_in_block();
+	const int tile = blockIdx.x * 4 + wv;   // scalar: the level search, the square's map and every table read below are scalar work
 	const int plane = blockIdx.y;
 	if (tile >= w.NT)
 		return;
@@ -2194,10 +2194,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
 	// the store: 20 KB per workgroup instead of 34, six waves per SIMD instead of four)
 	static_assert(AP_BATCH * (SYMW + REFW) <= SQ_WORDS, "the plane slices share the wave's square staging area");
 	__shared__ __attribute__((aligned(16))) unsigned ap_mem[4][SQ_WORDS];
-	unsigned (*ap_sym)[SYMW] = reinterpret_cast<unsigned (*)[SYMW]>(ap_mem[threadIdx.x >> 6]);
-	unsigned (*ap_ref)[REFW] = reinterpret_cast<unsigned (*)[REFW]>(ap_mem[threadIdx.x >> 6] + AP_BATCH * SYMW);
-	__shared__ unsigned ap_rank[4][MAX_PLANES], ap_n2[4][MAX_PLANES], ap_refbit[4][MAX_PLANES];
-	const int wv = threadIdx.x >> 6;
+	unsigned (*ap_sym)[SYMW] = reinterpret_cast<unsigned (*)[SYMW]>(ap_mem[wv]);
+	unsigned (*ap_ref)[REFW] = reinterpret_cast<unsigned (*)[REFW]>(ap_mem[wv] + AP_BATCH * SYMW);
 	unsigned my_tr = 0, my_n2 = 0;
 	unsigned long long my_sb = 0, my_b2 = 0;
 	bool my_live = false;
@@ -2245,11 +2243,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
 			const long rw = (long)(rbit >> 5) + lane;
 			if (lane < REFW && r2t < n2 && rw < stream_words)
 				rv[q] = stream[rw];
-			if (lane == 0) {
-				ap_rank[wv][pl[q]] = rank;
-				ap_n2[wv][pl[q]] = n2;
-				ap_refbit[wv][pl[q]] = (unsigned)(rbit & 31);
-			}
 		}
 #pragma unroll
 		for (int q = 0; q < AP_BATCH; ++q) {
@@ -2268,7 +2261,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
 		for (int q = 0; q < nbatch; ++q) {
 			const int p = 63 - __builtin_clzll(todo);
 			todo &= ~(1ull << p);
-			const unsigned rank = ap_rank[wv][p], n2done = ap_n2[wv][p];
+			// (the plane's facts, from lane p's registers as the fetch above took them: scalars, and so is what hangs on them alone)
+			const unsigned rank = (unsigned)__builtin_amdgcn_readlane((int)my_tr, p) & 0x7fffffffu, n2done = (unsigned)__builtin_amdgcn_readlane((int)my_n2, p);
+			const unsigned refbit = ((unsigned)__builtin_amdgcn_readlane((int)my_b2, p) + (tbase - rank)) & 31u;   // of the tile's first refinement bit
 			const unsigned ci = (unsigned)__builtin_popcount(ins);
 			const unsigned nb = wave_incl_add_u(ci) - ci;                 // insignificant coefficients in the lanes before
 			// symbols: two bits each (one flag, sign), this lane's start `nb` symbols after the tile's
@@ -2280,7 +2275,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
 			const unsigned r2 = tbase - rank + sb4;                          // refinement index of this lane's first significant one
 			const unsigned cs = (unsigned)nv - ci;
 			const unsigned avail = r2 < n2done ? (n2done - r2 < cs ? n2done - r2 : cs) : 0u;
-			const unsigned rrel = ap_refbit[wv][p] + sb4;
+			const unsigned rrel = refbit + sb4;
 			const unsigned *rwp = ap_ref[q] + (rrel >> 5);
 			unsigned r16 = __builtin_amdgcn_alignbit(rwp[1], rwp[0], rrel & 31u) & bfm(avail, 0u);   // avail <= 16
 			// four coefficients per look-up: symbols to the insignificant ones, refinement bits to the others, in order
@@ -2353,9 +2348,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
 			val[i] = v;
 		}
 		if ((g.lv16 >> l) & 1u)
-			store_square16(g.fine16 + (long)plane * g.lin_stride, g.W, g.side[l], g.tile_blk[tile], lane, ap_mem[threadIdx.x >> 6], val);
+			store_square16(g.fine16 + (long)plane * g.lin_stride, g.W, g.side[l], g.tile_blk[tile], lane, ap_mem[wv], val);
 		else
-			store_square16(g.pyr + (long)plane * g.lin_stride, g.W, g.side[l], g.tile_blk[tile], lane, ap_mem[threadIdx.x >> 6], val);
+			store_square16(g.pyr + (long)plane * g.lin_stride, g.W, g.side[l], g.tile_blk[tile], lane, ap_mem[wv], val);
 		return;
 	}
 	int *dst = lin + (long)plane * g.lin_stride + base + first;
