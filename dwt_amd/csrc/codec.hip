@@ -318,6 +318,11 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 		}
 		int *lin = a + plane_ints * C * first;
 		int *pyr = b + plane_ints * C * first;
+		// A reduced pyramid (pitch ow) may go through the wide inverse kernels where the whole picture does not: 263x135 at
+		// 132x68.  They read it 8 and 16 bytes at a time, and image `first` of odd-sized pictures starts on an odd int: the
+		// reduced planes, little more than a quarter of the slot, start on the next 16 bytes instead.
+		if (lo < g.levels)
+			pyr += (4 - ((size_t)(pyr - b) & 3)) & 3;
 		int *img = a + plane_ints * C * first;   // lin is dead once reconstructed
 		dwtx_p16 f16 = { nullptr, 0u };
 		if (fused & DWTX_FUSED_FINE16) {   // the decoder put the part's finest rings there

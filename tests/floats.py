@@ -6,6 +6,8 @@ float32: numpy, as two separate operations — `(v.astype(np.float32) * s).astyp
 fuse them.  float16 / bfloat16: that float32 through torch ON THE CPU, `.to(torch.float16 / torch.bfloat16)`: round to
 nearest even, overflow to infinity, subnormals kept.  Never the library's own integer decode, and nothing here needs a
 device.  tests/test_float_cpu.py holds this helper to hand-computed cases."""
+import functools
+
 import numpy as np
 
 KINDS = ("float32", "float16", "bfloat16")
@@ -55,7 +57,12 @@ def reference(v, kind, scale=1.0, bias=0.0, order="rgb"):
 
 def fill_bits(samples, kind):
     """A frame's fill, as bit patterns: every value of the type turns up, NaNs and infinities among them, and no two
-    neighbours are equal."""
+    neighbours are equal.  (A copy of its own for every caller: the same sizes come again and again.)"""
+    return _fill_bits(samples, kind).copy()
+
+
+@functools.lru_cache(maxsize=8)
+def _fill_bits(samples, kind):
     i = np.arange(samples, dtype=np.uint64)
     if kind == "float32":
         return ((i * np.uint64(2654435761) + (i >> np.uint64(7))) & np.uint64(0xFFFFFFFF)).astype(np.uint32)

@@ -6,6 +6,7 @@ samples (maxval 4095).  Every comparison is exact.  A layout is a flat buffer of
 strides (in samples): numpy and torch take the same strided view of it, so the expectation of a decode — the oracle's
 picture in each window's corner, the prefilled pattern in every other sample of the buffer — is built with numpy alone."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -104,9 +105,15 @@ def grid(W, H, Cn, variant="quad", rows=3, cols=4):
 LAYOUTS = {"stack": stack, "band": band, "grid": grid}
 
 
-def pattern(samples, is16):
+@functools.lru_cache(maxsize=8)
+def _pattern(samples, is16):
     i = np.arange(samples, dtype=np.int64)
     return ((i * 7 + (i >> 9) * 13 + 1) % (4093 if is16 else 251)).astype(np.uint16 if is16 else np.uint8)
+
+
+def pattern(samples, is16):
+    """A buffer's fill (a copy of its own for every caller: the same sizes come again and again)."""
+    return _pattern(samples, is16).copy()
 
 
 def to_device(ctx, buf):
