@@ -67,8 +67,8 @@ FLOAT_TYPES = {"float32": 0, "float16": 1, "bfloat16": 2}   # enum DWTX_FLOAT32 
 
 
 def float_format(dtype, scale=1.0, bias=0.0):
-    """The dtype, `scale` and `bias` keywords of decode_view_float -> FloatFormat.  dtype: torch.float32 / float16 / bfloat16
-    (or their names); scale and bias: a number, or three — one per COLOUR, R, G, B, whatever order the channels lie in.  The
+    """The dtype, `scale` and `bias` keywords of decode_view_float and encode_view_float -> FloatFormat.  dtype:
+    torch.float32 / float16 / bfloat16 (or their names); scale and bias: a number, or three — one per COLOUR, R, G, B, whatever order the channels lie in.  The
     values are rounded to float32 here, as the library holds them.  Anything else — another dtype, another length, a value
     that is not finite (before or after that rounding) — is a ValueError, raised here, before any device call."""
     import math
@@ -535,7 +535,7 @@ class Context:
         stride 1, any channel stride): `nchw.permute(0, 2, 3, 1)` and `chw.permute(1, 2, 0)` are views as they are.
         stepped: pixels further apart than their samples too (view_fields); the last value returned is their pixel step."""
         torch = self.torch
-        if floats:   # (decode_view_float: the same views of float32 / float16 / bfloat16 samples)
+        if floats:   # (decode_view_float, encode_view_float: the same views of float32 / float16 / bfloat16 samples)
             if t.dtype not in (torch.float32, torch.float16, torch.bfloat16) or t.device != self.device or t.dim() not in (4, 5):
                 raise ValueError("a float view needs a float32 / float16 / bfloat16 tensor [n,H,W,C] or [bands,cols,H,W,C] on the context's device")
         elif t.dtype not in (torch.uint8, torch.uint16, torch.int16) or t.device != self.device or t.dim() not in (4, 5):
@@ -572,6 +572,29 @@ class Context:
                    "dwtx_encode_view_step")
         else:
             _check(self.lib.dwtx_encode_view(self.h, C.byref(v), W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view")
+        return out, info
+
+    def encode_view_float(self, t, maxval=255, scale=1.0, bias=0.0, capacity=0, out=None, info=None, stepped=False, order="rgb"):
+        """dwtx_encode_view_float: encode_view of a float32 / float16 / bfloat16 strided device tensor (the shapes and
+        strides encode_view takes, stepped and order="bgr" included).  The picture that is coded is, per sample,
+        `(x.float() * scale + bias).round().clamp(0, maxval)` — two float32 roundings, ties to even, NaN -> 0 — and the
+        streams are those of encode_device (maxval <= 255) or encode_device16 (above) on that picture; async.  scale,
+        bias: a number, or three, per colour R, G, B.  Returns (streams, info) like encode_view.  A tensor that holds no
+        floats, a wrong length of scale or bias and values that are not finite raise ValueError before any device call."""
+        order = view_order(order)
+        torch = self.torch
+        if not hasattr(t, "dtype") or t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError(f"encode_view_float reads float32, float16 or bfloat16 tensors, not {getattr(t, 'dtype', type(t))}")
+        fmt = float_format(t.dtype, scale, bias)
+        v, W, H, Cn, n, step = self._view(t, int(maxval), stepped, floats=True)
+        bound = self.lib.dwtx_encode_bound16 if int(maxval) > 255 else self.lib.dwtx_encode_bound
+        stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
+        if out is None:
+            out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
+        if info is None:
+            info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
+        _check(self.lib.dwtx_encode_view_float(self.h, C.byref(v), step, order, C.byref(fmt), W, H, n, capacity, _ptr(out), out.shape[1],
+                                               _ptr(info)), "dwtx_encode_view_float")
         return out, info
 
     def decode_view(self, streams, lens, into, maxval=None, levels_max=-1, stepped=False, order="rgb"):

@@ -63,7 +63,8 @@ class View(C.Structure):
 
 
 class FloatFormat(C.Structure):
-    """dwtx_float_format: the float type of a dwtx_decode_view_float destination, scale and bias per colour (R, G, B)."""
+    """dwtx_float_format: the float type of a dwtx_decode_view_float destination or a dwtx_encode_view_float source,
+    scale and bias per colour (R, G, B)."""
     _fields_ = [("type", C.c_int), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
 
 
@@ -145,6 +146,7 @@ SYMBOLS = {
     "dwtx_encode_view_order": (_i, [_vp, C.POINTER(View), _sz, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
     "dwtx_decode_view_order": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, _vp]),
     "dwtx_decode_view_float": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), _vp]),
+    "dwtx_encode_view_float": (_i, [_vp, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), _i, _i, _i, C.c_long, _vp, _sz, _vp]),
     "dwtx_tile_groups": (_i, [_i, _i, _i, C.POINTER(TileGroup)]),
     "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }

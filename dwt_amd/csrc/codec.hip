@@ -68,12 +68,13 @@ static int pyramid_from_pixels(dwtx_ctx *ctx, int32_t *pyr, int32_t *tmp, const 
 	const int C = px.channels;
 	int rc;
 	dwtx_hist_sink sink;
-	const dwtx_hist_sink *hist = px.deep() ? nullptr : &sink;
+	// (deep_source(): deep pixels, and float pixels that quantise beyond 255 — dwtx_encode_view_float — which take their route)
+	const dwtx_hist_sink *hist = px.deep_source() ? nullptr : &sink;
 	*hist_levels = 0u;
 	*fine16 = dwtx_p16{ nullptr, 0u };
 	if (hist && (rc = dwtx_hist_begin(ctx, W, H, C, n, &sink)))
 		return rc;
-	if ((rc = rings16(ctx, px, W, H, n, sq16, own16, fine16)))
+	if ((rc = rings16(ctx, px, W, H, n, px.deep_source() ? 0u : sq16, own16, fine16)))
 		return rc;
 	if (dwtx_pixels_ok(px, W, H) && !(px.deep() && ctx->opt[DWTX_OPT_NO_PIXELS16]))
 		return dwtx_fwd_pixels(ctx, pyr, px, W, H, n, hist, hist_levels, *fine16);             // encode.c:155-159 in one pass
@@ -374,7 +375,7 @@ extern "C" int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, s
 // pixel_step (the *_view_step calls; the plain ones pass 0): samples from a pixel to the next one of its row; 0 and
 // `channels` are both the dense case and leave px->pixel_step 0, so that everything downstream is the plain call's.
 // order (the *_view_order calls; the others pass DWTX_ORDER_RGB): kept for RGB views and checked first, nothing else here looks at it.
-// kind (dwtx_decode_view_float; the others pass none): the float samples the view must hold — its sample_bytes their size,
+// kind (dwtx_decode_view_float, dwtx_encode_view_float; the others pass none): the float samples the view must hold — its sample_bytes their size,
 // any maxval a deep picture may have; every stride counts those samples, and every rule below holds as it stands.
 static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, dwtx_pixels *px, int kind = -1)
 {
@@ -518,9 +519,8 @@ extern "C" int dwtx_decode_view_order(dwtx_ctx *ctx, const uint8_t *dev_streams,
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
 }
 
-extern "C" int dwtx_decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
-	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
-	const dwtx_float_format *fmt, dwtx_decode_info *host_info)
+// dwtx_float_format -> the sample kind of dwtx_pixels, checked (what both float calls refuse alike)
+static int float_kind(const dwtx_float_format *fmt, int *kind)
 {
 	if (!fmt) {
 		dwtx_set_error("float view: no dwtx_float_format");
@@ -535,15 +535,48 @@ extern "C" int dwtx_decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams,
 			dwtx_set_error("float view: scale[%d] = %g, bias[%d] = %g: both must be finite", c, (double)fmt->scale[c], c, (double)fmt->bias[c]);
 			return DWTX_ERR_ARG;
 		}
-	const int kind = fmt->type == DWTX_FLOAT32 ? DWTX_SAMPLE_F32 : fmt->type == DWTX_FLOAT16 ? DWTX_SAMPLE_F16 : DWTX_SAMPLE_BF16;
+	*kind = fmt->type == DWTX_FLOAT32 ? DWTX_SAMPLE_F32 : fmt->type == DWTX_FLOAT16 ? DWTX_SAMPLE_F16 : DWTX_SAMPLE_BF16;
+	return DWTX_OK;
+}
+
+static void set_float_format(dwtx_pixels *px, const dwtx_float_format *fmt)
+{
+	for (int c = 0; c < 3; ++c) {
+		px->scale[c] = fmt->scale[c];
+		px->bias[c] = fmt->bias[c];
+	}
+}
+
+extern "C" int dwtx_decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
+	const dwtx_float_format *fmt, dwtx_decode_info *host_info)
+{
+	int kind;
+	if (const int rc = float_kind(fmt, &kind))
+		return rc;
 	dwtx_pixels px;
 	if (const int rc = pixels_of_view(dst, pixel_step, order, W, H, n, true, &px, kind))
 		return rc;
-	for (int c = 0; c < 3; ++c) {
-		px.scale[c] = fmt->scale[c];
-		px.bias[c] = fmt->bias[c];
-	}
+	set_float_format(&px, fmt);
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
+}
+
+// The source's maxval is the quantiser's clamp (the one encode that reads it): up to 255 the picture is one of bytes and takes
+// their route, beyond it a deep picture's (dwtx_pixels::deep_source()); the streams are those of dwtx_encode_device /
+// dwtx_encode_device16 on the quantised picture either way.
+extern "C" int dwtx_encode_view_float(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	int kind;
+	if (const int rc = float_kind(fmt, &kind))
+		return rc;
+	dwtx_pixels px;
+	if (const int rc = pixels_of_view(src, pixel_step, order, W, H, n, false, &px, kind))
+		return rc;
+	if (!dwtx_maxval_ok(src->maxval))
+		return DWTX_ERR_ARG;
+	set_float_format(&px, fmt);
+	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
 }
 
 // one axis of dwtx_tile_groups: `full` tiles of `tile`, then one of `last` (0: none)

@@ -187,10 +187,13 @@ template <class F> char *carve(dwtx_ctx *ctx, int slot, F &&fn)
 // The three channels may lie as B, G, R (order, the *_view_order calls only): base and every stride stay what they are — base
 // is the lowest-addressed channel's first sample — and only lift.hip's last step to the kernels (red(), colour_stride())
 // knows: no check and no choice of path looks at the order.
-// A destination may hold floating-point samples (kind, dwtx_decode_view_float only): what the integer sinks would write
+// A destination may hold floating-point samples (kind, dwtx_decode_view_float): what the integer sinks would write
 // there, times scale plus bias per COLOUR, converted.  sample_bytes stays the addressing unit (4, or 2 for the half types);
-// a float view takes the 8-bit pixels' route through the pipelines whatever its maxval (deep() is false: 16-bit ring planes
-// where the streams' plane counts allow them), with the clamp bound always passed along.
+// a float destination takes the 8-bit pixels' route through the pipelines whatever its maxval (deep() is false: 16-bit ring
+// planes where the streams' plane counts allow them), with the clamp bound always passed along.
+// A source may hold them too (dwtx_encode_view_float): the picture that is coded is rint(x * scale + bias) per COLOUR, two
+// fp32 roundings, clamped to [0, maxval] (NaN: 0) — lift.hip's quant_of.  Up to a maxval of 255 those integers meet every
+// bound of 8-bit samples and the source takes their route; above it the deep pictures' (deep_source()).
 enum dwtx_sample_kind { DWTX_SAMPLE_U8 = 0, DWTX_SAMPLE_U16, DWTX_SAMPLE_F32, DWTX_SAMPLE_F16, DWTX_SAMPLE_BF16 };
 struct dwtx_pixels {
 	void *base;            // the grid's window 0, first sample
@@ -211,6 +214,9 @@ struct dwtx_pixels {
 	// uint16_t samples — and with them the kernel family that clamps at maxval and keeps no 16-bit ring planes
 	bool deep() const { return kind == DWTX_SAMPLE_U16; }
 	bool is_float() const { return kind >= DWTX_SAMPLE_F32; }
+	// as a SOURCE: the family whose forward transform keeps no histograms and no 16-bit ring planes (both bounds are for samples
+	// of at most 255): uint16_t samples, and floats that quantise to more than 255
+	bool deep_source() const { return deep() || (is_float() && maxval > 255); }
 	size_t bytes(size_t samples) const { return samples * (size_t)sample_bytes; }
 	void *at(size_t sample) const { return static_cast<char *>(base) + bytes(sample); }
 	// typed for the kernels: u16() for deep pixels; u8() for bytes — and for the fields that carry either kind as bytes
@@ -272,7 +278,7 @@ static inline dwtx_pixels dwtx_pixels16(const uint16_t *pix, int channels, size_
 	p.kind = DWTX_SAMPLE_U16;
 	return p;
 }
-// a float destination (kind: DWTX_SAMPLE_F32 / _F16 / _BF16); the caller fills scale and bias
+// a float destination or source (kind: DWTX_SAMPLE_F32 / _F16 / _BF16); the caller fills scale and bias
 static inline dwtx_pixels dwtx_pixels_float(void *pix, int kind, int channels, size_t image_stride, int maxval)
 {
 	dwtx_pixels p{ pix, kind == DWTX_SAMPLE_F32 ? 4 : 2, channels, image_stride, maxval };
@@ -285,7 +291,7 @@ static inline dwtx_pixels dwtx_pixels_float(void *pix, int kind, int channels, s
 // the buffer allow it: W % 4 == 0, more than 64 pixels on a side (the wide kernel, not the LDS tail), px.wide() (a planar
 // picture's channel stride on the quad grid too), and windows the kernels can address (lift.hip).  Of the stepped views
 // (dwtx_pixels::pixel_step) only 8-bit RGB in 4-byte pixels qualifies: every other one takes the general conversions.
-// Of float destinations gray and planar RGB qualify (the inverse direction only); interleaved float RGB takes the general way.
+// Of float views gray and planar RGB qualify, in both directions; interleaved float RGB takes the general way.
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H);
 // lift.hip: asks for the scratch planes every lifting call of a W*H transform over nplanes planes asks for
 int dwtx_lift_scratch(dwtx_ctx *ctx, int W, int H, int nplanes);
@@ -336,7 +342,8 @@ struct dwtx_p16 {
 };
 // The transforms whose finest level reads / writes the pixels itself; both need dwtx_pixels_ok(px, W, H), and image i of
 // the inverse is written at px.image(i).  Deep pixels: int32 arithmetic and int32 bands; no histograms ride along
-// (lift.hip hist_add) and no 16-bit ring planes — both bounds are for 8-bit sources, and a deep view with either is DWTX_ERR_ARG.
+// (lift.hip hist_add) and no 16-bit ring planes — both bounds are for 8-bit sources, and a deep view with either is DWTX_ERR_ARG
+// (dwtx_pixels::deep_source(): float sources that quantise beyond 255 among them).
 int dwtx_fwd_pixels(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels &px, int W, int H, int n, const dwtx_hist_sink *sink = nullptr,
 	unsigned *hist_levels = nullptr, dwtx_p16 p16 = dwtx_p16{ nullptr, 0u });
 int dwtx_inv_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *in, int W, int H, int n, const dwtx_p16 *p16 = nullptr);

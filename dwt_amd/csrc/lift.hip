@@ -19,6 +19,7 @@
 //   update at sample 0: d[-1] := d[0]      (tdiv(2a,4) == tdiv(a,2))
 //   odd-length line: the last even sample is NOT updated (not symmetric!)
 #include "dwtx_internal.h"
+#include <type_traits>
 
 #include <stdlib.h>
 
@@ -1060,7 +1061,9 @@ struct FwdSrc;
 // too), or — the finest level of a deep picture — uint16_t pixels, gray, interleaved RGB or planar RGB; and the pixels
 // k_fwd_pixels_w reads (the host's names for Band<>'s five and for uint8_t, Rgb8, RgbP8 and Rgbx8, then the
 // three B, G, R twins: Band<SRC_BGR16>, Bgr8, Bgrx8)
-enum { SRC_I32 = 0, SRC_I16, SRC_U16, SRC_RGB16, SRC_RGBP16, SRC_U8, SRC_RGB8, SRC_RGBP8, SRC_RGBX8, SRC_BGR16, SRC_BGR8, SRC_BGRX8, SRC_COUNT };
+enum { SRC_I32 = 0, SRC_I16, SRC_U16, SRC_RGB16, SRC_RGBP16, SRC_U8, SRC_RGB8, SRC_RGBP8, SRC_RGBX8, SRC_BGR16, SRC_BGR8, SRC_BGRX8,
+	// float pixels (FloatPix<> below), gray and planar (P) fp32 and fp16 / bf16: quantised to at most 255, and (D) beyond
+	SRC_F32, SRC_H16, SRC_F32P, SRC_H16P, SRC_F32D, SRC_H16D, SRC_F32PD, SRC_H16PD, SRC_COUNT };
 template <int SRC>
 struct Band {};
 // 8-bit interleaved RGB pixels, of which each plane's workgroup takes its own YCoCg-R channel (image.h:52-65 fused; 8-bit
@@ -1084,6 +1087,7 @@ __device__ __forceinline__ long rgb_window(const LevelArgs &a, int plane, int &c
 }
 
 struct FwdInt32 {
+	static constexpr bool FLOAT = false;   // (the float sources' used() takes the launch's arguments as well)
 	typedef I2 Pair;
 	typedef FwdRaw Used;
 	static constexpr int S = 2;
@@ -1094,6 +1098,7 @@ struct FwdInt32 {
 };
 
 struct FwdPacked {
+	static constexpr bool FLOAT = false;
 	typedef P2 Pair;
 	static constexpr int S = 2;
 	static constexpr bool RGB_GRID = false;
@@ -1244,6 +1249,189 @@ struct FwdSrc<Bgrx8> : FwdSrc<Rgbx8> {
 	static __device__ __forceinline__ void lift(const FwdRawRgbx &r, int ch, int q, int lane, int nquads, P2 &lo, P2 &hi) { fwd_lift_p(row_p<true>(r, ch), q, lane, nquads, lo, hi); }
 };
 
+// ---- float sources (dwtx_encode_view_float): the finest level reads fp32, fp16 or bf16 samples and quantises them itself ----
+// The picture that is coded, per sample x of colour c: m = fl32(x * scale[c]), r = fl32(m + bias[c]) — two roundings, as the
+// line a caller would otherwise write in torch has them, under the pragma float_of() (below, the inverse direction) stands
+// under for the same reason —, q = rint(r) (v_rndne_f32: ties to even), clamped to [0, M] with NaN -> 0: both compares are
+// false for a NaN, which therefore takes the 0; +inf takes M, -inf and -0.0 become 0.
+__device__ __forceinline__ int quant_of(float x, float scale, float bias, float M)
+{
+#pragma clang fp contract(off)
+	const float m = x * scale;
+	const float r = m + bias;
+	const float q = __builtin_rintf(r);
+	const float lo = q >= 0.f ? q : 0.f;
+	return (int)(lo > M ? M : lo);
+}
+
+// the 16-bit float types widen exactly (fp16 subnormals kept): which of the two the bits are is uniform (FloatFmt::bf16)
+__device__ __forceinline__ float half_float(unsigned bits16, int bf16)
+{
+	return bf16 ? __builtin_bit_cast(float, bits16 << 16) : (float)__builtin_bit_cast(_Float16, (unsigned short)bits16);
+}
+
+struct Half16;   // (the sample type of the 16-bit float sinks, further down: here the tag of the sources that read either type)
+
+// A row of one plane as it is loaded, F = float: the lane's quad is 16 bytes, its neighbours' two samples 8 (lane 0: x[4q-2],
+// x[4q-1]; the other lanes: the first is x[4q+4]); F = Half16: the 8 and 4 bytes of a deep gray row (FwdRawS).  Both inside
+// the row's own W samples, as every source's.
+template <typename F>
+struct FwdRawF {
+	uint4 x;
+	uint2 e;
+};
+template <>
+struct FwdRawF<Half16> : FwdRawS {};
+
+__device__ __forceinline__ FwdRawF<float> fwd_load_f(const float *__restrict__ row, const LaneAt &at)
+{
+	FwdRawF<float> r = { *reinterpret_cast<const uint4 *>(row + at.main), *reinterpret_cast<const uint2 *>(row + at.edge) };
+	return r;
+}
+__device__ __forceinline__ FwdRawF<Half16> fwd_load_f(const uint16_t *__restrict__ row, const LaneAt &at)
+{
+	FwdRawF<Half16> r;
+	static_cast<FwdRawS &>(r) = fwd_load_s(row, at);
+	return r;
+}
+__device__ __forceinline__ FwdRawF<float> hold(const FwdRawF<float> &r)
+{
+	FwdRawF<float> o = { make_uint4(hold(r.x.x), hold(r.x.y), hold(r.x.z), hold(r.x.w)), hold(r.e) };
+	return o;
+}
+__device__ __forceinline__ FwdRawF<Half16> hold(const FwdRawF<Half16> &r)
+{
+	FwdRawF<Half16> o;
+	static_cast<FwdRawS &>(o) = hold(static_cast<const FwdRawS &>(r));
+	return o;
+}
+
+// the six samples of a loaded row, quantised with colour c's scale and bias (c: uniform)
+struct Quant6 {
+	int x0, x1, x2, x3, e0, e1;
+};
+__device__ __forceinline__ Quant6 quant_row(const FwdRawF<float> &r, const LevelArgsW &A, int c)
+{
+	const float s = A.fmt.scale[c], b = A.fmt.bias[c], M = (float)A.a.maxval;
+	auto q = [s, b, M](unsigned bits) { return quant_of(__builtin_bit_cast(float, bits), s, b, M); };
+	Quant6 o = { q(r.x.x), q(r.x.y), q(r.x.z), q(r.x.w), q(r.e.x), q(r.e.y) };
+	return o;
+}
+__device__ __forceinline__ Quant6 quant_row(const FwdRawF<Half16> &r, const LevelArgsW &A, int c)
+{
+	const float s = A.fmt.scale[c], b = A.fmt.bias[c], M = (float)A.a.maxval;
+	const int bf16 = A.fmt.bf16;
+	auto q = [s, b, M, bf16](unsigned bits16) { return quant_of(half_float(bits16, bf16), s, b, M); };
+	Quant6 o = { q(r.x.x & 0xffffu), q(r.x.x >> 16), q(r.x.y & 0xffffu), q(r.x.y >> 16), q(r.e & 0xffffu), q(r.e >> 16) };
+	return o;
+}
+// ... as the row an 8-bit gray source loads (M <= 255: every value is a byte): everything after the load is that source's
+__device__ __forceinline__ FwdRaw8 raw8_of(const Quant6 &v)
+{
+	FwdRaw8 o = { (unsigned)v.x0 | ((unsigned)v.x1 << 8) | ((unsigned)v.x2 << 16) | ((unsigned)v.x3 << 24),
+		(unsigned)v.e0 | ((unsigned)v.e0 << 16) | ((unsigned)v.e1 << 24) };   // (byte 0: x[4q+4]; bytes 2, 3 — lane 0 —: x[4q-2], x[4q-1])
+	return o;
+}
+// ... and as the widened row of the int32 arithmetic (deep quantised values)
+__device__ __forceinline__ FwdRaw raw_of(const Quant6 &v)
+{
+	FwdRaw o;
+	o.x = make_int4(v.x0, v.x1, v.x2, v.x3);
+	o.xr = v.e0;
+	o.left = make_int2(v.e0, v.e1);
+	return o;
+}
+
+// The sources' names: F = float or Half16 (fp16 and bf16 share a kernel, as in the sinks), gray or planar RGB (in either
+// order: the host hands the R plane and a signed stride, as to RgbP8), and the route.  DEEP false — maxval <= 255 —: the row
+// becomes the packed row of the 8-bit source of its layout when it is used (FwdRaw8 / FwdRawRgb3: cur[] holds two / six
+// registers a row, only nxt[] the floats) and the level is that source's: packed arithmetic, histograms, 16-bit bands, the
+// three channels of a strip side by side.  DEEP true: the int32 arithmetic of the deep sources, no histograms, a workgroup
+// column per plane.  used() takes the launch's arguments for the format (FLOAT: fwd_level_body calls it that way).
+template <typename F, bool PLANAR, bool DEEP>
+struct FloatPix {};
+
+// a planar window's three rows
+template <typename F>
+struct FwdRawF3 {
+	FwdRawF<F> r, g, b;
+};
+template <typename F>
+__device__ __forceinline__ FwdRawF3<F> hold(const FwdRawF3<F> &p)
+{
+	FwdRawF3<F> o = { hold(p.r), hold(p.g), hold(p.b) };
+	return o;
+}
+
+template <typename F>
+struct FwdFloatRows {
+	typedef typename std::conditional<std::is_same<F, float>::value, float, uint16_t>::type Sample;
+	static __device__ __forceinline__ LaneAt at(int q, int lane, int nquads) { return lane_at(q, lane, nquads, 4, 2); }
+	static __device__ __forceinline__ const Sample *pixels(const LevelArgs &a) { return reinterpret_cast<const Sample *>(a.src8); }
+	// (ch: a constant where this is inlined for the 8-bit route: Co is R - B and leaves the G plane unloaded; below 0: all three)
+	static __device__ __forceinline__ FwdRawF3<F> load3(const Sample *__restrict__ row, const LaneAt &at, long cs, int ch)
+	{
+		const FwdRawF<F> r = fwd_load_f(row, at), b = fwd_load_f(row + 2 * cs, at);
+		FwdRawF3<F> o = { r, ch == 1 ? r : fwd_load_f(row + cs, at), b };
+		return o;
+	}
+};
+
+template <typename F>
+struct FwdSrc<FloatPix<F, false, false>> : FwdPacked, FwdFloatRows<F> {
+	static constexpr bool FLOAT = true;
+	typedef FwdRawF<F> Loaded;
+	typedef FwdRaw8 Used;
+	using typename FwdFloatRows<F>::Sample;
+	static __device__ __forceinline__ const Sample *base(const LevelArgs &a, int plane, int &) { return FwdFloatRows<F>::pixels(a) + win_off(a.grid, a.src_ps, plane); }
+	static __device__ __forceinline__ Loaded load(const Sample *row, const LaneAt &at, long, int) { return fwd_load_f(row, at); }
+	static __device__ __forceinline__ Used used(const Loaded &r, int, const LevelArgsW &A) { return raw8_of(quant_row(r, A, 0)); }
+};
+
+template <typename F>
+struct FwdSrc<FloatPix<F, true, false>> : FwdPacked, FwdFloatRows<F> {
+	static constexpr bool FLOAT = true;
+	typedef FwdRawF3<F> Loaded;
+	typedef FwdRawRgb3 Used;
+	using typename FwdFloatRows<F>::Sample;
+	static constexpr bool RGB_GRID = true;
+	static constexpr int S = 1;   // (as RgbP8)
+	static __device__ __forceinline__ const Sample *base(const LevelArgs &a, int plane, int &ch) { return FwdFloatRows<F>::pixels(a) + rgb_window(a, plane, ch); }
+	static __device__ __forceinline__ Loaded load(const Sample *row, const LaneAt &at, long cs, int ch) { return FwdFloatRows<F>::load3(row, at, cs, ch); }
+	static __device__ __forceinline__ Used used(const Loaded &p, int ch, const LevelArgsW &A)
+	{
+		const FwdRaw8 r = raw8_of(quant_row(p.r, A, 0)), b = raw8_of(quant_row(p.b, A, 2));
+		Used o = { r, ch == 1 ? r : raw8_of(quant_row(p.g, A, 1)), b };
+		return o;
+	}
+};
+
+template <typename F>
+struct FwdSrc<FloatPix<F, false, true>> : FwdInt32, FwdFloatRows<F> {
+	static constexpr bool FLOAT = true;
+	typedef FwdRawF<F> Loaded;
+	using typename FwdFloatRows<F>::Sample;
+	static __device__ __forceinline__ const Sample *base(const LevelArgs &a, int plane, int &) { return FwdFloatRows<F>::pixels(a) + win_off(a.grid, a.src_ps, plane); }
+	static __device__ __forceinline__ Loaded load(const Sample *row, const LaneAt &at, long, int) { return fwd_load_f(row, at); }
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int, const LevelArgsW &A) { return raw_of(quant_row(r, A, 0)); }
+};
+
+template <typename F>
+struct FwdSrc<FloatPix<F, true, true>> : FwdInt32, FwdFloatRows<F> {
+	static constexpr bool FLOAT = true;
+	typedef FwdRawF3<F> Loaded;
+	using typename FwdFloatRows<F>::Sample;
+	static __device__ __forceinline__ const Sample *base(const LevelArgs &a, int plane, int &ch) { return FwdFloatRows<F>::pixels(a) + rgb_window(a, plane, ch); }
+	static __device__ __forceinline__ Loaded load(const Sample *row, const LaneAt &at, long cs, int) { return FwdFloatRows<F>::load3(row, at, cs, -1); }
+	static __device__ __forceinline__ FwdRaw used(const Loaded &p, int ch, const LevelArgsW &A)
+	{
+		const Quant6 r = quant_row(p.r, A, 0), g = quant_row(p.g, A, 1), b = quant_row(p.b, A, 2);
+		const Quant6 o = { ycocg_ch(r.x0, g.x0, b.x0, ch), ycocg_ch(r.x1, g.x1, b.x1, ch), ycocg_ch(r.x2, g.x2, b.x2, ch), ycocg_ch(r.x3, g.x3, b.x3, ch),
+			ycocg_ch(r.e0, g.e0, b.e0, ch), ycocg_ch(r.e1, g.e1, b.e1, ch) };
+		return raw_of(o);
+	}
+};
+
 // One wide forward level of the wave's strip, for every source (FwdSrc above): int32 planes on every level of
 // dwtx_transformation_fwd and below the finest in the codec, pixels on the codec's finest.
 // Memory operations retire in order on this part (one counter for loads and stores): a wave that waits for rows it
@@ -1284,7 +1472,13 @@ __device__ __forceinline__ void fwd_level_body(const LevelArgsW &A, int bx, int 
 	const LaneAt at = T::at(q, lane, A.nquads);
 	const Pair zero = {};
 	Pair l0, h0, pl = zero, ph = zero;
-	T::lift(T::used(T::load(src + (long)(2 * jfirst) * a.spitch, at, A.cstride, ch), ch), ch, q, lane, A.nquads, l0, h0);
+	auto use = [&](const typename T::Loaded &r) {
+		if constexpr (T::FLOAT)
+			return T::used(r, ch, A);
+		else
+			return T::used(r, ch);
+	};
+	T::lift(use(T::load(src + (long)(2 * jfirst) * a.spitch, at, A.cstride, ch)), ch, q, lane, A.nquads, l0, h0);
 	auto rowp = [&](int r) { return src + (long)min(r, a.h - 1) * a.spitch; };
 	typename T::Used cur[2 * S];
 	typename T::Loaded nxt[2 * S];
@@ -1326,7 +1520,7 @@ __device__ __forceinline__ void fwd_level_body(const LevelArgsW &A, int bx, int 
 	for (int jb = jfirst; jb < j1; jb += S) {
 #pragma unroll
 		for (int k = 0; k < 2 * S; ++k)
-			cur[k] = T::used(hold(nxt[k]), ch);   // the one wait of the iteration: everything outstanding is a batch old
+			cur[k] = use(hold(nxt[k]));   // the one wait of the iteration: everything outstanding is a batch old
 		if (jb > jfirst)
 			store_batch(jb - S);
 		if (jb + S < j1) {
@@ -1415,6 +1609,26 @@ __global__ __launch_bounds__(64 * WAVES) void k_fwd_pixels_w(LevelArgsW A)
 	} else {
 		xcd_strip(bx, by);
 		fwd_level_body<SrcT, HIST, 0>(A, bx, by);
+	}
+}
+
+// k_fwd_float_w: float pixels (FloatPix<>).  The 8-bit route's planar RGB as k_fwd_pixels_w runs RgbP8; gray and the deep
+// route a workgroup column per plane, the channel whatever base() says.
+template <typename SrcT, bool HIST>
+__global__ __launch_bounds__(64 * WAVES) void k_fwd_float_w(LevelArgsW A)
+{
+	int bx, by, chan = 0;
+	if (FwdSrc<SrcT>::RGB_GRID) {
+		xcd_strip_rgb(bx, by, chan);
+		if (chan == 0)
+			fwd_level_body<SrcT, HIST, 0>(A, bx, by);
+		else if (chan == 1)
+			fwd_level_body<SrcT, HIST, 1>(A, bx, by);
+		else
+			fwd_level_body<SrcT, HIST, 2>(A, bx, by);
+	} else {
+		xcd_strip(bx, by);
+		fwd_level_body<SrcT, HIST, -1>(A, bx, by);
 	}
 }
 
@@ -2738,8 +2952,19 @@ constexpr int PX_LANES = 64, PX_ROWS = 4;   // a workgroup of the conversions: o
 // pnm.h:69-74 (byte -> int) fused with image.h:52-65 rgb2ycocg.  P = uint8_t, or uint16_t for deep pixels (the same
 // arithmetic: nothing in it knows the depth).  grid: (64 pixels of a row, 4 rows, window): a wave reads 64 neighbouring
 // pixels of one row, and nothing divides per sample.  Planar RGB: the wave reads 64 neighbouring samples of each plane.
+// P = float, _Float16 or __bf16 (dwtx_encode_view_float): the integers the samples quantise to — quant_of with colour c's scale
+// and bias, clamped at M — in any layout the integer instances take; those read neither f nor M.
 template <class P>
-__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *__restrict__ planes, const P *__restrict__ pix, PixGrid g)
+__device__ __forceinline__ int sample_in(P v, const FloatFmt &, int, int) { return (int)v; }
+template <>
+__device__ __forceinline__ int sample_in<float>(float v, const FloatFmt &f, int c, int M) { return quant_of(v, f.scale[c], f.bias[c], (float)M); }
+template <>
+__device__ __forceinline__ int sample_in<_Float16>(_Float16 v, const FloatFmt &f, int c, int M) { return quant_of((float)v, f.scale[c], f.bias[c], (float)M); }
+template <>
+__device__ __forceinline__ int sample_in<__bf16>(__bf16 v, const FloatFmt &f, int c, int M) { return quant_of((float)v, f.scale[c], f.bias[c], (float)M); }
+
+template <class P>
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *__restrict__ planes, const P *__restrict__ pix, PixGrid g, int M, FloatFmt f)
 {
 	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
 	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
@@ -2750,10 +2975,10 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *
 		const P *row = pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
 		int *dst = planes + (long)win * g.C * npix + (long)y * g.W + x;
 		if (g.C == 1) {
-			dst[0] = row[(long)x * g.col_step];
+			dst[0] = sample_in<P>(row[(long)x * g.col_step], f, 0, M);
 		} else {
 			const P *p = row + (long)x * g.col_step;
-			const int r = p[0], gr = p[g.chan_stride], b = p[2 * g.chan_stride];
+			const int r = sample_in<P>(p[0], f, 0, M), gr = sample_in<P>(p[g.chan_stride], f, 1, M), b = sample_in<P>(p[2 * g.chan_stride], f, 2, M);
 			const int co = r - b;
 			const int t = b + tdiv2(co);
 			const int cg = gr - t;
@@ -2921,15 +3146,34 @@ static FloatFmt float_fmt(const dwtx_pixels &px)
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
 {
 	const int C = px.channels;
-	if (!ctx || !planes || !px.base || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || !px.sample_aligned() || px.is_float())   // (a float source has no lossless meaning)
+	if (!ctx || !planes || !px.base || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || !px.sample_aligned())
+		return DWTX_ERR_ARG;
+	if (px.is_float() && !dwtx_maxval_ok(px.maxval))   // (the quantiser's clamp; integer sources have no use for a maxval)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	dim3 grid;
 	const PixGrid g = pix_grid(px, W, H, n, &grid);
-	if (!px.deep())
-		hipLaunchKernelGGL(k_planes_from_pixels<uint8_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, static_cast<const uint8_t *>(px.red()), g);
-	else
-		hipLaunchKernelGGL(k_planes_from_pixels<uint16_t>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, static_cast<const uint16_t *>(px.red()), g);
+	const FloatFmt f = float_fmt(px);
+	const dim3 block(PX_LANES * PX_ROWS);
+	switch (px.kind) {
+	case DWTX_SAMPLE_U8:
+		hipLaunchKernelGGL(k_planes_from_pixels<uint8_t>, grid, block, 0, ctx->stream, planes, static_cast<const uint8_t *>(px.red()), g, px.maxval, f);
+		break;
+	case DWTX_SAMPLE_U16:
+		hipLaunchKernelGGL(k_planes_from_pixels<uint16_t>, grid, block, 0, ctx->stream, planes, static_cast<const uint16_t *>(px.red()), g, px.maxval, f);
+		break;
+	case DWTX_SAMPLE_F32:
+		hipLaunchKernelGGL(k_planes_from_pixels<float>, grid, block, 0, ctx->stream, planes, static_cast<const float *>(px.red()), g, px.maxval, f);
+		break;
+	case DWTX_SAMPLE_F16:
+		hipLaunchKernelGGL(k_planes_from_pixels<_Float16>, grid, block, 0, ctx->stream, planes, static_cast<const _Float16 *>(px.red()), g, px.maxval, f);
+		break;
+	case DWTX_SAMPLE_BF16:
+		hipLaunchKernelGGL(k_planes_from_pixels<__bf16>, grid, block, 0, ctx->stream, planes, static_cast<const __bf16 *>(px.red()), g, px.maxval, f);
+		break;
+	default:
+		return DWTX_ERR_ARG;
+	}
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
@@ -3067,6 +3311,11 @@ static FwdSource fwd_source(const dwtx_pixels *px, bool src16)
 	if (!px)
 		return { src16 ? SRC_I16 : SRC_I32, false, 0 };
 	const bool deep = px->deep(), bgr = px->bgr();
+	if (px->is_float()) {   // gray, or planar RGB in either order (dwtx_pixels_ok): by sample size, layout and route
+		const bool rgb = px->channels == 3, far = px->deep_source();
+		const int src = (px->kind == DWTX_SAMPLE_F32 ? SRC_F32 : SRC_H16) + (rgb ? SRC_F32P - SRC_F32 : 0) + (far ? SRC_F32D - SRC_F32 : 0);
+		return { src, rgb && !far, wide_cstride(*px) };
+	}
 	if (px->channels != 3)
 		return { deep ? SRC_U16 : SRC_U8, false, 0 };
 	const int src = px->planar() ? (deep ? SRC_RGBP16 : SRC_RGBP8)
@@ -3092,17 +3341,26 @@ static WideKernel fwd_wide_kernel(int src, bool hist)
 		{ k_fwd_level_w<false, SRC_BGR16>, nullptr },
 		{ k_fwd_pixels_w<Bgr8, false>, k_fwd_pixels_w<Bgr8, true> },
 		{ k_fwd_pixels_w<Bgrx8, false>, k_fwd_pixels_w<Bgrx8, true> },
+		{ k_fwd_float_w<FloatPix<float, false, false>, false>, k_fwd_float_w<FloatPix<float, false, false>, true> },
+		{ k_fwd_float_w<FloatPix<Half16, false, false>, false>, k_fwd_float_w<FloatPix<Half16, false, false>, true> },
+		{ k_fwd_float_w<FloatPix<float, true, false>, false>, k_fwd_float_w<FloatPix<float, true, false>, true> },
+		{ k_fwd_float_w<FloatPix<Half16, true, false>, false>, k_fwd_float_w<FloatPix<Half16, true, false>, true> },
+		{ k_fwd_float_w<FloatPix<float, false, true>, false>, nullptr },
+		{ k_fwd_float_w<FloatPix<Half16, false, true>, false>, nullptr },
+		{ k_fwd_float_w<FloatPix<float, true, true>, false>, nullptr },
+		{ k_fwd_float_w<FloatPix<Half16, true, true>, false>, nullptr },
 	};
 	return K[src][hist];
 }
 
 // px != nullptr (`in` is then not read): the source is pixels, gray (plane p = image p) or RGB, interleaved or planar (plane p =
 // channel p%3 of image p/3 after YCoCg-R), image i at px->image(i); needs a finest level the wide kernel takes
-// (dwtx_pixels_ok).  Deep pixels: no histograms, no 16-bit bands (their bounds are for 8-bit sources).
+// (dwtx_pixels_ok).  Deep pixels: no histograms, no 16-bit bands (their bounds are for 8-bit sources).  Float pixels: the
+// integers they quantise to (quant_of) by the same rule, dwtx_pixels::deep_source().
 static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_pixels *px, int W, int H, int nplanes,
 	const dwtx_hist_sink *sink = nullptr, unsigned *hist_levels = nullptr, dwtx_p16 p16 = dwtx_p16{ nullptr, 0u })
 {
-	if (px && (px->is_float() || (px->deep() && (sink || p16.planes))))
+	if (px && ((px->deep_source() && (sink || p16.planes)) || (px->is_float() && !dwtx_maxval_ok(px->maxval))))
 		return DWTX_ERR_ARG;
 	if (hist_levels)
 		*hist_levels = 0u;
@@ -3187,6 +3445,8 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			a.src_ps = (long)px->image_stride;
 			a.spitch = (int)px->pitch(W);
 			a.grid = win_grid(*px);
+			if (px->is_float())
+				a.maxval = px->maxval;   // (what the quantiser clamps at; no other forward source reads it)
 		} else {
 			a.src = src;
 			a.src_ps = src_ps;
@@ -3228,6 +3488,8 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			A.a = a;
 			const FwdSource from = fwd_source(pix_in, a.src16 != nullptr);
 			A.cstride = from.cstride;
+			if (pix_in && px->is_float())
+				A.fmt = float_fmt(*px);
 			if (hist_here) {
 				A.hist = HistArgs{ sink->cum32, sink->tile_mx, sink->tiles.xy2tile + sink->tiles.xy_first[level], sink->NT, sink->NTP,
 					sink->tiles.nbs[level] };
@@ -3270,7 +3532,7 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H)
 {
 	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide() && px.pitch(W) <= 0x7fffffffu && (!px.stepped() || px.rgbx8()) &&
-		(!px.is_float() || px.channels == 1 || px.planar());   // (float sinks: OutRow<F> and RgbOut<F, PIX_PLANAR>; interleaved float RGB has none)
+		(!px.is_float() || px.channels == 1 || px.planar());   // (float sinks: OutRow<F> and RgbOut<F, PIX_PLANAR>, float sources: FloatPix<>; interleaved float RGB has neither)
 }
 
 unsigned dwtx_levels16(int W, int H, unsigned sq_levels)

@@ -349,7 +349,7 @@ typedef struct dwtx_view {
 	void  *dev;            /* first sample of window 0 */
 	int    sample_bytes;   /* 1: uint8_t, 2: native-endian uint16_t (deep pixels) */
 	int    channels;       /* 1 or 3 (interleaved, or planar: channel_stride) */
-	int    maxval;         /* decode: clamp bound (255 required when sample_bytes == 1); encode ignores it */
+	int    maxval;         /* decode: clamp bound (255 required when sample_bytes == 1); encode ignores it (but dwtx_encode_view_float: the quantiser's clamp) */
 	int    cols;           /* windows per band; 0 or >= n: all n windows in one band */
 	size_t row_pitch;      /* samples from a window's row to its next row, >= W*channels (planar: >= W) */
 	size_t image_stride;   /* samples from a window to the next one of its band */
@@ -435,10 +435,10 @@ int dwtx_encode_view_order(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_ste
 int dwtx_decode_view_order(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
 	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, dwtx_decode_info *host_info);
 
-/* ---- float destinations: decode straight into fp32, fp16 and bf16 tensors ---------------------------------------------
+/* ---- float views: decode straight into, and encode straight from, fp32, fp16 and bf16 tensors ------------------------
  * dwtx_decode_view_order for destinations that hold floating-point samples: what a training or inference pipeline does
  * with a decoded batch on its next line — `x.float() * scale + bias`, or `.half()` — without the integer frame in between,
- * its second pass and its memory.  Decode only: a float source has no lossless meaning.
+ * its second pass and its memory.  (Float sources: dwtx_encode_view_float below, whose quantiser is part of its contract.)
  * Destination: dst->sample_bytes must equal the size of fmt->type (4, or 2 for the two half types); every stride of the
  * view, and pixel_step, count samples of that type; dev is aligned to the sample.  dst->maxval is what the streams were
  * encoded from, 1..65535: the same call covers 8-bit and deep streams.
@@ -466,6 +466,37 @@ typedef struct dwtx_float_format {
 int dwtx_decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
 	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
 	const dwtx_float_format *fmt, dwtx_decode_info *host_info);
+
+/* dwtx_encode_view_order for sources that hold floating-point samples: a model's output in [-1, 1], a renderer's tone-mapped
+ * frame — without the line `(x.float() * s + b).round().clamp(0, maxval).to(uint8)`, its launches, its temporaries and the
+ * integer copy of the batch in between.  The quantiser is part of the contract, so the stream is the lossless code of a
+ * picture that is defined bit for bit.
+ * Source: src->sample_bytes must equal the size of fmt->type (4, or 2 for the two half types); every stride of the view,
+ * and pixel_step, count samples of that type; dev is aligned to the sample.  Asynchronous on the context's stream.
+ * The picture that is coded: for colour c of a pixel holding the sample x, widened exactly to fp32 (fp16 subnormals kept):
+ *   m = x * scale[c], rounded to fp32;  r = m + bias[c], rounded to fp32 — two roundings, no fused multiply-add —;
+ *   q = rint(r): to nearest, ties to even (torch.round, np.rint);  v = min(max(q, 0), maxval),
+ * with NaN -> 0, +inf -> maxval, -inf -> 0 and -0.0 -> 0.  What becomes of an fp32-subnormal m or r is not pinned (it
+ * quantises to 0 or to the same integer either way).  src->maxval is the clamp bound, 1..65535: the one encode that reads
+ * it.  scale and bias belong to COLOURS (R, G, B), not to memory positions: with DWTX_ORDER_BGR the sample at the lowest
+ * address takes scale[2] and bias[2].  Gray uses [0].
+ * Stream i and dev_info[i] are byte for byte those of dwtx_encode_device (maxval <= 255) or dwtx_encode_device16 (maxval
+ * above) on the dense interleaved R, G, B picture of those v; capacity, out_stride, the zero padding after a stream and
+ * the encode index (dwtx_ctx_set_encode_index) keep their meaning, and so does the refusal of a picture that needs more
+ * than 16 bit planes (dev_info[i].error = 1, the others of its batch are coded): with maxval <= 4095 none is refused.
+ * dwtx_encode_bound (maxval <= 255) and dwtx_encode_bound16 (maxval > 255) are the safe out_strides.
+ * Only the `channels` samples of the W pixels of a window's H rows are read (planar: the W samples of the H rows of its
+ * three planes): nothing between stepped pixels, nothing of the frame around the windows — there is no counterpart of the
+ * 8-bit RGBX path's read of a pixel's own fourth byte.  Windows and planes may overlap, as for any encode.
+ * Gray and planar RGB windows with W % 4 == 0, more than 64 pixels on a side and every row on the quad grid of the float
+ * sample (16 bytes for fp32, 8 for the half types) are read and quantised by the forward transform's finest level itself;
+ * every other view (interleaved float RGB among them) through the general conversion into int32 planes — the same bytes.
+ * DWTX_ERR_ARG (with a dwtx_last_error() text, nothing written to dev_out or dev_info): fmt == NULL, an unknown type, a
+ * sample_bytes that does not match the type, a scale or bias that is not finite, a maxval outside 1..65535, and everything
+ * dwtx_encode_view_order refuses. */
+int dwtx_encode_view_float(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order,
+	const dwtx_float_format *fmt, int W, int H, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
 
 /* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
  * interior, right column, bottom row, corner, in that order, those that exist — each a cols x rows grid of W x H tiles
