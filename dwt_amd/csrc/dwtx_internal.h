@@ -306,12 +306,24 @@ int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *p
 // encode.c:46-56, are the blocks' points one block after the other.  A tile is one non-empty curve block: `base` =
 // ring index of its first coefficient, `cnt` = its coefficients (1024 for a block that lies wholly inside the ring),
 // `blk` = the block's index on the curve.  Levels below 32x32 are one block each.  Tiles are numbered level by level.
+// What the kernels read of a tile is one 16-byte record (built with the plan, once per geometry): everything that follows
+// from (W, H, tile) alone, so that a wave finds its tile's facts with one load instead of a search over tile_first[], three
+// table reads and the curve's recursion for the block (hilbert_dev.h square_map; unpacked by tile_rec there).
+//   x: base    y: pixels[l] + base, the coefficient's place in a linearised plane (< 2^30)
+//   z: cnt | l << DWTX_REC_LEVEL_SHIFT | swap << DWTX_REC_SWAP_SHIFT    w: mx | my << 16, square_map(lengths[l+1], blk)
+struct dwtx_tile_rec {
+	int base, at;
+	unsigned info, masks;
+};
+static_assert(sizeof(dwtx_tile_rec) == 16, "a tile's record is one 16-byte load");
+constexpr int DWTX_REC_LEVEL_SHIFT = 16, DWTX_REC_SWAP_SHIFT = 31;
+static_assert(DWTX_MAX_SIDE <= (1 << 15), "a square map's XOR mask is below the curve's side: 16 bits each hold it");
+static_assert(DWTX_MAX_LEVELS <= 16, "the record keeps the level in four bits");
 struct dwtx_tiles {
 	int NT;
 	int tile_first[DWTX_MAX_LEVELS + 1];
-	const int *base;              // device, [NT]
-	const unsigned short *cnt;    // device, [NT]
-	const int *blk;               // device, [NT]
+	const dwtx_tile_rec *rec;     // device, [NT], 16-byte aligned
+	const unsigned short *cnt;    // device, [NT]: the counts once more, dense (k_entries_count: a thread per entry reads nothing else of a tile)
 	// block (bx, by) of level l's curve square (32x32 pyramid positions each, lengths[l+1] / 32 = nbs[l] blocks per side)
 	// -> its tile, -1 for a block without ring coefficients: xy2tile[xy_first[l] + by * nbs[l] + bx]; levels below 64 have none
 	const int *xy2tile;           // device
@@ -357,10 +369,8 @@ template <class G> int dwtx_fill_geom(dwtx_ctx *ctx, int W, int H, int C, G &g, 
 {
 	int lengths[DWTX_MAX_LEVELS], pixels[DWTX_MAX_LEVELS], widths[DWTX_MAX_LEVELS], heights[DWTX_MAX_LEVELS];
 	g.levels = dwtx_compute_lengths(lengths, pixels, widths, heights, W, H, DWTX_MIN_LEN);
-	for (int l = 0; l <= g.levels; ++l) {
+	for (int l = 0; l <= g.levels; ++l)
 		g.pixels[l] = pixels[l];
-		g.side[l] = l < g.levels ? lengths[l + 1] : 0;
-	}
 	g.C = C;
 	g.W = W;
 	g.H = H;
@@ -374,9 +384,7 @@ template <class G> int dwtx_fill_geom(dwtx_ctx *ctx, int W, int H, int C, G &g, 
 		return rc;
 	for (int l = 0; l <= g.levels; ++l)
 		g.tile_first[l] = tiles.tile_first[l];
-	g.tile_base = tiles.base;
-	g.tile_cnt = tiles.cnt;
-	g.tile_blk = tiles.blk;
+	g.tile_rec = tiles.rec;
 	return DWTX_OK;
 }
 

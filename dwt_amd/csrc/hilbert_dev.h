@@ -58,7 +58,7 @@ struct SquareMap {
 	unsigned mx, my;
 };
 
-__device__ __forceinline__ SquareMap square_map(int n, unsigned sq)   // square index = curve index >> 10, n >= 32
+__host__ __device__ __forceinline__ SquareMap square_map(int n, unsigned sq)   // square index = curve index >> 10; n <= 32: the empty map
 {
 	SquareMap m = { false, 0u, 0u };
 	for (unsigned s = 1u << BLK_LOG2; s < (unsigned)n; s <<= 1) {
@@ -79,6 +79,41 @@ __device__ __forceinline__ SquareMap square_map(int n, unsigned sq)   // square 
 		sq >>= 2;
 	}
 	return m;
+}
+
+// A tile's record (dwtx_tile_rec, built with the plan from square_map above) and what a kernel sees of it.  With a scalar
+// tile index — blockIdx.x * 4 + wave_in_block() — the record comes by scalar loads and every field is a scalar: one
+// s_load_dwordx4 where all of it is used at once (k_apply_all), the words each branch uses where the compiler can tell
+// (k_code, k_hist: DESIGN.md 4.5).  With a tile per lane it is a vector load of the words the caller uses.
+struct TileRec {
+	int base;        // ring index of the tile's first coefficient
+	int at;          // the same coefficient in a linearised plane: pixels[l] + base
+	int cnt, l;      // coefficients (1024: a whole 32x32 square), ring level
+	SquareMap map;   // of the tile's block on the level's curve
+};
+
+__host__ __device__ __forceinline__ dwtx_tile_rec tile_rec_pack(int base, int at, int cnt, int l, const SquareMap &m)
+{
+	dwtx_tile_rec r;
+	r.base = base;
+	r.at = at;
+	r.info = (unsigned)cnt | (unsigned)l << DWTX_REC_LEVEL_SHIFT | (m.sw ? 1u : 0u) << DWTX_REC_SWAP_SHIFT;
+	r.masks = m.mx | m.my << 16;
+	return r;
+}
+
+__device__ __forceinline__ TileRec tile_rec(const dwtx_tile_rec *__restrict__ recs, int tile)
+{
+	const uint4 r = reinterpret_cast<const uint4 *>(recs)[tile];
+	TileRec t;
+	t.base = (int)r.x;
+	t.at = (int)r.y;
+	t.cnt = (int)(r.z & 0xffffu);
+	t.l = (int)((r.z >> DWTX_REC_LEVEL_SHIFT) & 15u);
+	t.map.sw = (r.z >> DWTX_REC_SWAP_SHIFT) != 0u;
+	t.map.mx = r.w & 0xffffu;
+	t.map.my = r.w >> 16;
+	return t;
 }
 
 __device__ __forceinline__ void hilbert_in_square(const SquareMap &m, int i, int &xo, int &yo)
@@ -138,12 +173,11 @@ __device__ __forceinline__ void square_positions16(const SquareMap &m, int lane,
 	}
 }
 
-// Curve block `blk` of a ring level (outer side n) of one plane, a whole square: the wave reads it as whole
+// The curve block that `m` maps (a tile's record, or square_map(n, blk)) of one plane, a whole square: the wave reads it as whole
 // 128-byte rows, stages it in LDS (SQ_WORDS words, 16-byte aligned) and every lane picks up its 16 consecutive curve points.
-__device__ __forceinline__ void load_square16(const int *__restrict__ plane_pyr, int ppitch, int n, int blk, int lane,
+__device__ __forceinline__ void load_square16(const int *__restrict__ plane_pyr, int ppitch, const SquareMap &m, int lane,
 	unsigned *lds, int (&val)[16])
 {
-	const SquareMap m = square_map(n, (unsigned)blk);
 	const unsigned X0 = m.mx & ~31u, Y0 = m.my & ~31u;
 #pragma unroll
 	for (int it = 0; it < 4; ++it) {
@@ -162,10 +196,9 @@ __device__ __forceinline__ void load_square16(const int *__restrict__ plane_pyr,
 }
 
 // the inverse: 16 consecutive curve points per lane -> the pyramid's 32x32 square
-__device__ __forceinline__ void store_square16(int *__restrict__ plane_pyr, int ppitch, int n, int blk, int lane, unsigned *lds,
+__device__ __forceinline__ void store_square16(int *__restrict__ plane_pyr, int ppitch, const SquareMap &m, int lane, unsigned *lds,
 	const int (&val)[16])
 {
-	const SquareMap m = square_map(n, (unsigned)blk);
 	const unsigned X0 = m.mx & ~31u, Y0 = m.my & ~31u;
 	unsigned pos[16];
 	square_positions16(m, lane, pos);
@@ -185,10 +218,9 @@ __device__ __forceinline__ void store_square16(int *__restrict__ plane_pyr, int 
 
 // The same for a plane kept as 16-bit coefficients (the finest ring of an 8-bit source, lift.hip): 64-byte rows,
 // widened on the way into LDS / narrowed on the way out, so that the staged square is the one above.
-__device__ __forceinline__ void load_square16(const short *__restrict__ plane_pyr, int ppitch, int n, int blk, int lane,
+__device__ __forceinline__ void load_square16(const short *__restrict__ plane_pyr, int ppitch, const SquareMap &m, int lane,
 	unsigned *lds, int (&val)[16])
 {
-	const SquareMap m = square_map(n, (unsigned)blk);
 	const unsigned X0 = m.mx & ~31u, Y0 = m.my & ~31u;
 #pragma unroll
 	for (int it = 0; it < 2; ++it) {
@@ -212,10 +244,9 @@ __device__ __forceinline__ void load_square16(const short *__restrict__ plane_py
 	sq_wave_sync();
 }
 
-__device__ __forceinline__ void store_square16(short *__restrict__ plane_pyr, int ppitch, int n, int blk, int lane, unsigned *lds,
+__device__ __forceinline__ void store_square16(short *__restrict__ plane_pyr, int ppitch, const SquareMap &m, int lane, unsigned *lds,
 	const int (&val)[16])
 {
-	const SquareMap m = square_map(n, (unsigned)blk);
 	const unsigned X0 = m.mx & ~31u, Y0 = m.my & ~31u;
 	unsigned pos[16];
 	square_positions16(m, lane, pos);

@@ -299,7 +299,7 @@ struct dwtx_linplan {
 	LinGeom g;
 	int nblocks;
 	int *d_blockbase;
-	dwtx_tiles tiles;     // the non-empty blocks as the entropy stage's tiles (device arrays in one allocation at tiles.base)
+	dwtx_tiles tiles;     // the non-empty blocks as the entropy stage's tiles (tiles.rec and tiles.xy2tile are device allocations of the plan)
 	// the blocks that are copied when the entropy stage takes the whole squares of every level it can (dwtx_square_levels):
 	// blocks the ring's edges cut, and the small levels — global block ids, ascending; copy_upto[l] = how many lie below level l
 	int *d_copy_list;
@@ -310,7 +310,7 @@ struct dwtx_linplan {
 static void plan_destroy(dwtx_linplan *p)
 {
 	(void)hipFree(p->d_blockbase);
-	(void)hipFree(const_cast<int *>(p->tiles.base));
+	(void)hipFree(const_cast<dwtx_tile_rec *>(p->tiles.rec));
 	(void)hipFree(p->d_copy_list);
 	(void)hipFree(const_cast<int *>(p->tiles.xy2tile));
 	free(p);
@@ -367,11 +367,8 @@ static int build_plan(dwtx_ctx *ctx, dwtx_linplan *p, int W, int H)
 		for (int bb = g.blk_first[l]; bb < g.blk_first[l + 1]; ++bb)
 			nt += in_ring(l, bb) > 0;
 	{
-		const size_t o_blk = sizeof(int) * (size_t)nt, o_cnt = 2 * sizeof(int) * (size_t)nt;
-		const size_t bytes = o_cnt + sizeof(unsigned short) * (size_t)nt + 64;
-		std::vector<char> host(bytes);
-		int *tb = (int *)host.data(), *tk = (int *)(host.data() + o_blk);
-		unsigned short *tc = (unsigned short *)(host.data() + o_cnt);
+		// a record per tile (dwtx_tile_rec): what the entropy stage's kernels would otherwise work out per wave
+		std::vector<dwtx_tile_rec> host((size_t)(nt > 0 ? nt : 1));
 		int t = 0;
 		for (int l = 0; l < g.levels; ++l) {
 			p->tiles.tile_first[l] = t;
@@ -379,23 +376,27 @@ static int build_plan(dwtx_ctx *ctx, dwtx_linplan *p, int W, int H)
 				const int c = in_ring(l, bb);
 				if (c <= 0)
 					continue;
-				tb[t] = hb[(size_t)bb];
-				tk[t] = bb - g.blk_first[l];
-				tc[t] = (unsigned short)c;
-				++t;
+				const int base = hb[(size_t)bb];
+				host[(size_t)t++] = tile_rec_pack(base, g.pixels[l] + base, c, l, square_map(g.lengths[l + 1], (unsigned)(bb - g.blk_first[l])));
 			}
 		}
 		p->tiles.tile_first[g.levels] = t;
 		p->tiles.NT = t;
+		// one allocation (plan_destroy frees it through tiles.rec): the records, which hipMalloc aligns far beyond their 16 bytes,
+		// then the counts once more as a dense array
+		const size_t rec_bytes = sizeof(dwtx_tile_rec) * host.size();
+		std::vector<unsigned short> cnt(host.size());
+		for (int i = 0; i < t; ++i)
+			cnt[(size_t)i] = (unsigned short)(host[(size_t)i].info & 0xffffu);
 		char *dev = nullptr;
-		if (hipMalloc((void **)&dev, bytes) != hipSuccess) {
+		if (hipMalloc((void **)&dev, rec_bytes + sizeof(unsigned short) * cnt.size()) != hipSuccess) {
 			dwtx_set_error("tile table hipMalloc failed");
 			return DWTX_ERR_NOMEM;
 		}
-		p->tiles.base = (const int *)dev;   // (plan_destroy frees the one allocation through this pointer)
-		p->tiles.blk = (const int *)(dev + o_blk);
-		p->tiles.cnt = (const unsigned short *)(dev + o_cnt);
-		if (hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+		p->tiles.rec = (const dwtx_tile_rec *)dev;
+		p->tiles.cnt = (const unsigned short *)(dev + rec_bytes);
+		if (hipMemcpy(dev, host.data(), rec_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+			hipMemcpy(dev + rec_bytes, cnt.data(), sizeof(unsigned short) * cnt.size(), hipMemcpyHostToDevice) != hipSuccess) {
 			dwtx_set_error("tile table upload failed");
 			return DWTX_ERR_DEVICE;
 		}

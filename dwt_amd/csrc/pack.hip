@@ -72,13 +72,10 @@ struct PackGeom {
 	const short *fine16;   // or null: the rings of the levels in lv16 are not in pyr but here, as 16-bit coefficients (same pitch and positions)
 	unsigned lv16;
 	unsigned sq_levels;    // ring levels whose tiles are read from the pyramid's 32x32 squares instead of `lin` (hilbert_dev.h)
-	int side[DWTX_MAX_LEVELS + 1];          // outer side of ring level l (lengths[l+1])
 	int pixels[DWTX_MAX_LEVELS + 1];
 	int tile_first[DWTX_MAX_LEVELS + 1];   // tile_first[levels] = tiles per plane
-	// the tiles (dwtx_tiles): ring index of a tile's first coefficient, its coefficients, its block on the level's curve
-	const int *tile_base;
-	const unsigned short *tile_cnt;
-	const int *tile_blk;
+	const dwtx_tile_rec *tile_rec;   // the tiles (dwtx_tiles): one record each, read with tile_rec() (hilbert_dev.h)
+	const unsigned short *tile_cnt;  // their counts, dense (k_entries_count)
 };
 
 struct ImgInfo {
@@ -206,25 +203,25 @@ struct __attribute__((packed, aligned(4))) Int4U {
 	int x, y, z, w;
 };
 
-__device__ __forceinline__ void load_tile16(const PackGeom &g, const int *__restrict__ lin, int plane, int l, int tile, int lane, int nvalid,
+__device__ __forceinline__ void load_tile16(const PackGeom &g, const int *__restrict__ lin, int plane, const TileRec &tr, int lane,
 	int nv, unsigned *lds, int (&val)[16])
 {
+	const int l = tr.l, nvalid = tr.cnt;
 	if (((g.sq_levels >> l) & 1u) && nvalid == TILE) {   // uniform
 		if ((g.lv16 >> l) & 1u)
-			load_square16(g.fine16 + (long)plane * g.total, g.W, g.side[l], g.tile_blk[tile], lane, lds, val);
+			load_square16(g.fine16 + (long)plane * g.total, g.W, tr.map, lane, lds, val);
 		else
-			load_square16(g.pyr + (long)plane * g.total, g.W, g.side[l], g.tile_blk[tile], lane, lds, val);
+			load_square16(g.pyr + (long)plane * g.total, g.W, tr.map, lane, lds, val);
 		return;
 	}
-	const int tbase = g.tile_base[tile];
-	const int *src = lin + (long)plane * g.total + g.pixels[l] + tbase + 16 * lane;
+	const int *src = lin + (long)plane * g.total + tr.at + 16 * lane;
 	// A ring starts wherever the levels before it end: its tiles are 16-byte aligned only by luck (always for
 	// power-of-two shapes).  A 16-byte load from a 4-byte aligned address is split up by the memory pipeline, so
 	// an unaligned tile is read as five aligned quads around the lane's 16 coefficients and shifted in registers
 	// by the ring's (uniform) misalignment.  The quad after a ring's last tile may lie outside the buffer: that
 	// tile takes the scalar path.
 	const int k = (int)(((uintptr_t)src >> 2) & 3);   // uniform: lanes are 64 bytes apart
-	const bool last_of_ring = g.pixels[l] + (long)tbase + TILE >= g.pixels[l + 1];
+	const bool last_of_ring = (long)tr.at + TILE >= g.pixels[l + 1];
 	if (nvalid == TILE && (k == 0 || !last_of_ring)) {
 		const int4 *A = reinterpret_cast<const int4 *>(src - k);
 		int t[20];
@@ -282,16 +279,15 @@ __device__ __forceinline__ void load_tile16(const PackGeom &g, const int *__rest
 __device__ __forceinline__ void hist_load(const PackGeom &g, const int *__restrict__ lin, int plane, int tile, int lane, int (&val)[16],
 	unsigned &ok, int &nvalid)
 {
-	int l = 0;
-	while (l + 1 < g.levels && tile >= g.tile_first[l + 1])
-		++l;
-	const long base = g.pixels[l] + g.tile_base[tile];
-	nvalid = g.tile_cnt[tile];
+	const TileRec tr = tile_rec(g.tile_rec, tile);
+	const int l = tr.l;
+	const long base = tr.at;
+	nvalid = tr.cnt;
 	ok = 0xffffu;
 	if (((g.sq_levels >> l) & 1u) && nvalid == TILE) {
 		// the tile is a 32x32 square of the pyramid (hilbert_dev.h); a histogram does not care about the order:
 		// every lane takes four consecutive coefficients of four rows
-		const SquareMap m = square_map(g.side[l], (unsigned)g.tile_blk[tile]);
+		const SquareMap &m = tr.map;
 		const long at = (long)plane * g.total + (long)(m.my & ~31u) * g.W + (m.mx & ~31u);
 		if ((g.lv16 >> l) & 1u) {   // 16-bit rows: eight coefficients of two rows
 			const short *sq = g.fine16 + at;
@@ -411,7 +407,7 @@ __global__ __launch_bounds__(256) void k_hist_init(PackGeom g, Work w)
 	if (i >= w.NT * (NCUM / 2))
 		return;
 	const int tile = i / (NCUM / 2), d = i - tile * (NCUM / 2);
-	const unsigned cnt = g.tile_cnt[tile];
+	const unsigned cnt = (unsigned)tile_rec(g.tile_rec, tile).cnt;
 	reinterpret_cast<unsigned *>(w.cum + ((long)plane * w.NT + tile) * NCUM)[d] = d < 8 ? 0u : d < 15 ? cnt * 0x00010001u : cnt;
 	if (d == 0)
 		w.tile_mx[(long)plane * w.NTP + tile] = 0u;
@@ -426,9 +422,7 @@ __global__ __launch_bounds__(256) void k_hist(PackGeom g, const int *__restrict_
 	if (tile0 >= w.NT)
 		return;
 	if (done_levels) {   // (a wave's two tiles lie on one level, or the first is the last of its level: the pair is split then)
-		int l = 0;
-		while (l + 1 < g.levels && tile0 >= g.tile_first[l + 1])
-			++l;
+		const int l = tile_rec(g.tile_rec, tile0).l;
 		const bool d0 = (done_levels >> l) & 1u;
 		const bool same = tile0 + 1 < g.tile_first[l + 1];
 		const bool d1 = same ? d0 : (l + 1 < g.levels ? ((done_levels >> (l + 1)) & 1u) != 0 : true);
@@ -742,7 +736,7 @@ __global__ __launch_bounds__(ENT_BLOCK) void k_entries_count(PackGeom g, Work w)
 		seg_unpack(sd[k], c, l, p);
 		const int j = e - eb[k];
 		const int ntile = g.tile_first[l + 1] - g.tile_first[l];
-		const int cnt = g.tile_cnt[g.tile_first[l] + j];
+		const int cnt = g.tile_cnt[g.tile_first[l] + j];   // (from the records the kernel was slower: eight times the cache lines for two bytes a thread)
 		const unsigned short *cum = w.cum + ((long)(img * g.C + c) * w.NT + g.tile_first[l] + j) * NCUM;
 		const int z = cum[p], upto = cum[p + 1];
 		w.ent_seg[img * w.ES + e] = (unsigned short)k;
@@ -1266,16 +1260,15 @@ __device__ __forceinline__ void code_tile(CodeLds &L, const unsigned char *pext4
 // variant runs a small grid that strides over the tiles, so that launching it for nothing costs nothing.
 template <bool WIDE>
 __device__ __forceinline__ void code_one(const PackGeom &g, const int *__restrict__ lin, const Work &w, CodeLds &L, const unsigned char *pext4, int tile,
-	int plane, int lane)
+	int img, int c, int lane)
 {
-	const int img = plane / g.C, c = plane - img * g.C;
+	const int plane = img * g.C + c;
 	const ImgInfo &I = w.info[img];
 	{
-	int l = 0;
-	while (l + 1 < g.levels && tile >= g.tile_first[l + 1])
-		++l;
+	const TileRec tr = tile_rec(g.tile_rec, tile);   // (a scalar tile: scalar loads)
+	const int l = tr.l;
 	const int j = tile - g.tile_first[l];
-	const int nvalid = g.tile_cnt[tile];
+	const int nvalid = tr.cnt;
 	const int P = I.planes[c] < MAX_PLANES ? I.planes[c] : MAX_PLANES;
 	const unsigned live = w.live[(long)img * 48 + c * 16 + l];   // planes of this ring that are coded (k_cut)
 	if (!live)
@@ -1299,7 +1292,7 @@ __device__ __forceinline__ void code_one(const PackGeom &g, const int *__restric
 	// ---- the coefficients, once (the class table's LDS words stage a pyramid square meanwhile) ----
 	static_assert(sizeof(L.tab) >= sizeof(unsigned) * SQ_WORDS, "the class table doubles as the square's staging area");
 	int val[16];
-	load_tile16(g, lin, plane, l, tile, lane, nvalid, nv, L.tab, val);
+	load_tile16(g, lin, plane, tr, lane, nv, L.tab, val);
 	// per-plane bookkeeping of this tile's entries (lanes 0..15 take a plane each): three dependent look-ups
 	// whose results are only needed after the first passes over the coefficients — they stay in registers till then
 	unsigned my_tokbase = 0;
@@ -1332,10 +1325,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
 {
 	__shared__ CodeLds lds[4];
 	__shared__ unsigned char pext4[256];
-	// (the deep planes' kernel keeps the index per lane: as a scalar it would push more scalar registers into spills there)
-	const int lane = threadIdx.x & 63, wv = WIDE ? (int)(threadIdx.x >> 6) : wave_in_block();
-	const int plane = blockIdx.y;
-	const int img = plane / g.C, c = plane - img * g.C;
+	// (both kernels: with the level search and the square's map gone into the tile's record, the deep planes' kernel spills less
+	// with a scalar index than it did with the index per lane)
+	const int lane = threadIdx.x & 63, wv = wave_in_block();
+	const int c = blockIdx.y, img = blockIdx.z;   // (the grid names channel and image: no division of a plane index by C)
 	if ((w.info[img].planes[c] > 8) != WIDE)
 		return;   // (uniform over the workgroup) the other kernel's plane
 	if (!WIDE) {
@@ -1343,10 +1336,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
 		__syncthreads();   // the only point where the workgroup's waves meet
 		const int tile = blockIdx.x * 4 + wv;
 		if (tile < w.NT)   // whole wave; nothing below synchronises across waves
-			code_one<false>(g, lin, w, lds[wv], pext4, tile, plane, lane);
+			code_one<false>(g, lin, w, lds[wv], pext4, tile, img, c, lane);
 	} else {
 		for (int tile = blockIdx.x * 4 + wv; tile < w.NT; tile += gridDim.x * 4) {
-			code_one<true>(g, lin, w, lds[wv], pext4, tile, plane, lane);
+			code_one<true>(g, lin, w, lds[wv], pext4, tile, img, c, lane);
 			wave_sync();   // the wave's next tile reuses its LDS
 		}
 	}
@@ -2605,6 +2598,7 @@ static int pack_geometry(dwtx_ctx *ctx, int W, int H, int C, int n, PackGeom &g,
 	const int rc = dwtx_fill_geom(ctx, W, H, C, g, tiles);
 	if (rc)
 		return rc;
+	g.tile_cnt = tiles.cnt;
 	memset(&w, 0, sizeof(w));
 	w.NT = tiles.NT;
 	w.NTP = (tiles.NT + 3) / 4 * 4;
@@ -2776,8 +2770,8 @@ int dwtx_encode_planes_ex(dwtx_ctx *ctx, const int32_t *lin, const int32_t *pyr,
 	hipLaunchKernelGGL(k_entries_finish, dim3((unsigned)w.NCB, n), dim3(ENT_BLOCK), 0, s, w);
 	hipLaunchKernelGGL(k_entries_segs, dim3(n), dim3(ENT_BLOCK), 0, s, w);
 	hipLaunchKernelGGL(k_cut, dim3(n), dim3(ENT_BLOCK), 0, s, w, capacity, (int)(ctx->opt[DWTX_OPT_NO_CAPACITY_CUT] != 0));
-	hipLaunchKernelGGL(k_code<false>, dim3(dwtx_cdiv(NT, 4), nplanes), dim3(256), 0, s, g, lin, w);
-	hipLaunchKernelGGL(k_code<true>, dim3(dwtx_cdiv(NT, 4) < 64 ? dwtx_cdiv(NT, 4) : 64, nplanes), dim3(256), 0, s, g, lin, w);
+	hipLaunchKernelGGL(k_code<false>, dim3(dwtx_cdiv(NT, 4), C, n), dim3(256), 0, s, g, lin, w);
+	hipLaunchKernelGGL(k_code<true>, dim3(dwtx_cdiv(NT, 4) < 64 ? dwtx_cdiv(NT, 4) : 64, C, n), dim3(256), 0, s, g, lin, w);
 	hipLaunchKernelGGL(k_carry_local, dim3((unsigned)w.NCB, n), dim3(CARRY_THREADS), 0, s, w);
 	hipLaunchKernelGGL(k_carry_blocks, dim3(n), dim3(CARRY_BLOCK), 0, s, w);
 	if (dev_index)

@@ -73,11 +73,7 @@ struct UnpackGeom {
 	short *fine16;                            // or null: the squares of the ring levels in lv16 go here as 16-bit coefficients instead (same positions and pitch)
 	unsigned lv16;
 	unsigned sq_levels;                       // ring levels written as 32x32 squares of the pyramid instead of into `lin` (hilbert_dev.h)
-	int side[DWTX_MAX_LEVELS + 1];            // outer side of ring level l (lengths[l+1])
-	// the tiles (dwtx_tiles): ring index of a tile's first coefficient, its coefficients, its block on the level's curve
-	const int *tile_base;
-	const unsigned short *tile_cnt;
-	const int *tile_blk;
+	const dwtx_tile_rec *tile_rec;            // the tiles (dwtx_tiles): one record each, read with tile_rec() (hilbert_dev.h)
 };
 
 struct DecInfo {
@@ -2027,9 +2023,7 @@ __global__ __launch_bounds__(256) void k_count(UnpackGeom g, DWork w, int p)
 	const int img = plane / g.C;
 	if (tile >= w.NT)
 		return;
-	int l = 0;
-	while (l + 1 < g.levels && tile >= g.tile_first[l + 1])
-		++l;
+	const int l = tile_rec(g.tile_rec, tile).l;   // (a tile per lane: one vector load)
 	const unsigned long long cb = w.count_base[(long)plane * 16 + l];
 	if (!cb)
 		return;
@@ -2137,20 +2131,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
 	__syncthreads();
 	const unsigned char *dsym = dep, *dref = dep + 4096;
 	const int lane = threadIdx.x & 63, wv = wave_in_block();
-	const int tile = blockIdx.x * 4 + wv;   // scalar: the level search, the square's map and every table read below are scalar work
-	const int plane = blockIdx.y;
+	const int tile = blockIdx.x * 4 + wv;   // scalar: the tile's record and every table read below are scalar loads
+	const int c = blockIdx.y, img = blockIdx.z;   // (the grid names channel and image: no division of a plane index by C)
+	const int plane = img * g.C + c;
 	if (tile >= w.NT)
 		return;
-	const int img = plane / g.C, c = plane - img * g.C;
 	const DecInfo &I = w.info[img];
 	if (I.status)
 		return;
-	int l = 0;
-	while (l + 1 < g.levels && tile >= g.tile_first[l + 1])
-		++l;
-	const unsigned tbase = (unsigned)g.tile_base[tile];   // ring index of the tile's first coefficient
-	const long base = g.pixels[l] + (long)tbase;
-	const int nvalid = g.tile_cnt[tile];
+	const TileRec tr = tile_rec(g.tile_rec, tile);   // one scalar load: level, ring offset, count and the square's map
+	const int l = tr.l;
+	const unsigned tbase = (unsigned)tr.base;   // ring index of the tile's first coefficient
+	const long base = tr.at;
+	const int nvalid = tr.cnt;
 	const int first = 16 * lane;
 	const int nv = nvalid - first < 0 ? 0 : nvalid - first > 16 ? 16 : nvalid - first;   // this lane's coefficients
 	const int vb = first < nvalid ? first : nvalid;                                      // coefficients in the lanes before
@@ -2348,9 +2341,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
 			val[i] = v;
 		}
 		if ((g.lv16 >> l) & 1u)
-			store_square16(g.fine16 + (long)plane * g.lin_stride, g.W, g.side[l], g.tile_blk[tile], lane, ap_mem[wv], val);
+			store_square16(g.fine16 + (long)plane * g.lin_stride, g.W, tr.map, lane, ap_mem[wv], val);
 		else
-			store_square16(g.pyr + (long)plane * g.lin_stride, g.W, g.side[l], g.tile_blk[tile], lane, ap_mem[wv], val);
+			store_square16(g.pyr + (long)plane * g.lin_stride, g.W, tr.map, lane, ap_mem[wv], val);
 		return;
 	}
 	int *dst = lin + (long)plane * g.lin_stride + base + first;
@@ -2379,10 +2372,7 @@ __global__ __launch_bounds__(256) void k_tiles_init(UnpackGeom g, DWork w, int n
 	const int plane = blockIdx.y;
 	if (tile >= w.NT || plane >= nplanes)
 		return;
-	int l = 0;
-	while (l + 1 < g.levels && tile >= g.tile_first[l + 1])
-		++l;
-	w.tile_nonsig[(long)plane * w.NT + tile] = g.tile_cnt[tile];
+	w.tile_nonsig[(long)plane * w.NT + tile] = (unsigned short)tile_rec(g.tile_rec, tile).cnt;
 }
 
 // The chunk tables are laid out for the stream stride, but only the chunks that hold stream bytes are
@@ -2739,7 +2729,7 @@ struct DecodeCall {
 		ga.fine16 = fine ? p16.planes + (size_t)p.first * C * g.lin_stride : nullptr;
 		ga.lv16 = fine ? p16.levels : 0u;
 		p.fused = ga.sq_levels | (fine ? DWTX_FUSED_FINE16 : 0u);
-		hipLaunchKernelGGL(k_apply_all, dim3(dwtx_cdiv(w.NT, 4), p.count * C), dim3(256), 0, p.stream, ga, h,
+		hipLaunchKernelGGL(k_apply_all, dim3(dwtx_cdiv(w.NT, 4), C, p.count), dim3(256), 0, p.stream, ga, h,
 			streams + (size_t)p.first * stream_stride, (long)stream_stride, lin + (size_t)p.first * C * g.lin_stride);
 		DWTX_LAUNCH_CHECK();
 		return DWTX_OK;
