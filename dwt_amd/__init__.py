@@ -10,10 +10,10 @@ raise.
 import ctypes as C
 
 from . import _lib
-from ._lib import Geom, Stats, StreamInfo, DecodeInfo, Index, SegIndex, View, TileGroup, FloatFormat, INDEX_MAGIC, INDEX_MAX_SEGS, LIB_PATH  # noqa: F401
+from ._lib import Geom, Stats, StreamInfo, DecodeInfo, Index, SegIndex, View, TileGroup, FloatFormat, CropRect, INDEX_MAGIC, INDEX_MAX_SEGS, LIB_PATH  # noqa: F401
 
-__all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "tile_groups", "view_fields", "view_order", "float_format",
-           "Geom", "Stats", "View", "TileGroup", "FloatFormat"]
+__all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "tile_groups", "view_fields", "view_order", "float_format", "crop_plan",
+           "Geom", "Stats", "View", "TileGroup", "FloatFormat", "CropRect"]
 
 
 class DwtxError(RuntimeError):
@@ -50,6 +50,16 @@ def tile_groups(W, H, tile):
     if k < 0:
         raise DwtxError(k, "dwtx_tile_groups")
     return [TileGroup.from_buffer_copy(bytes(out[i])) for i in range(k)]
+
+
+def crop_plan(W, H, x0, y0, cw, ch):
+    """dwtx_crop_plan: the rectangles (x0, y0, w, h) of the LL band of every level, root first and the crop itself last, that
+    the cw x ch crop at (x0, y0) of a W x H picture needs.  Host arithmetic only."""
+    out = (CropRect * (_lib.MAX_LEVELS + 1))()
+    k = _lib.load().dwtx_crop_plan(W, H, x0, y0, cw, ch, out)
+    if k < 0:
+        raise DwtxError(k, "dwtx_crop_plan")
+    return [(r.x0, r.y0, r.w, r.h) for r in out[:k + 1]]
 
 
 ORDERS = {"rgb": 0, "bgr": 1}   # enum DWTX_ORDER_* (include/dwtx.h)
@@ -640,4 +650,36 @@ class Context:
         infos = (DecodeInfo * n)()
         _check(self.lib.dwtx_decode_view_float(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step,
                                                order, C.byref(fmt), C.cast(infos, C.c_void_p)), "dwtx_decode_view_float")
+        return list(infos)
+
+    def decode_view_crop(self, streams, lens, into, size, origins=None, maxval=None, scale=None, bias=None, levels_max=-1, stepped=False,
+                         order="rgb"):
+        """dwtx_decode_view_crop: decode_view — or decode_view_float, when `into` is a float tensor — of a window of each
+        picture: `into` holds windows of the crop's size ([n,ch,cw,C] or [bands,cols,ch,cw,C], any strides decode_view takes),
+        size=(W, H) is the streams' geometry, origins a sequence of n (x0, y0) pairs, one pair for all, or None for (0, 0).
+        Window i receives the picture's samples from (x0_i, y0_i) on, as far as the stream supports them, and nothing else of
+        `into`'s storage is written.  scale, bias: float tensors only.  Returns the list of DecodeInfo; syncs once."""
+        order = view_order(order)
+        torch = self.torch
+        W, H = (int(v) for v in size)
+        floats = hasattr(into, "dtype") and into.dtype in (torch.float32, torch.float16, torch.bfloat16)
+        if not floats and (scale is not None or bias is not None):
+            raise ValueError("scale and bias belong to float tensors")
+        fmt = float_format(into.dtype, 1.0 if scale is None else scale, 0.0 if bias is None else bias) if floats else None
+        if floats and maxval is None:
+            maxval = 255
+        v, cw, ch, Cn, n, step = self._view(into, None if maxval is None else int(maxval), stepped, floats=floats)
+        org = None
+        if origins is not None:
+            flat = [int(c) for c in origins] if len(origins) == 2 and not hasattr(origins[0], "__len__") else None
+            pairs = [tuple(flat)] * n if flat is not None else [(int(x), int(y)) for x, y in origins]
+            if len(pairs) != n:
+                raise ValueError(f"origins: one (x0, y0) pair or {n}, not {len(pairs)}")
+            org = (C.c_int * (2 * n))(*[c for p in pairs for c in p])
+        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
+        assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
+        infos = (DecodeInfo * n)()
+        _check(self.lib.dwtx_decode_view_crop(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
+                                              C.byref(fmt) if fmt is not None else None, cw, ch, org, C.cast(infos, C.c_void_p)),
+               "dwtx_decode_view_crop")
         return list(infos)

@@ -73,6 +73,11 @@ class TileGroup(C.Structure):
     _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("W", C.c_int), ("H", C.c_int), ("cols", C.c_int), ("rows", C.c_int)]
 
 
+class CropRect(C.Structure):
+    """dwtx_crop_rect: the w x h rectangle at (x0, y0) of one level's LL band that a crop needs (dwtx_crop_plan)."""
+    _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("meta_bits", C.c_int),
@@ -88,7 +93,7 @@ class Stats(C.Structure):
 OPTIONS = {name: i for i, name in enumerate((
     "exact_orders", "no_square_tiles", "part_images", "one_stream", "decode_parts", "two_families", "no_second_walk",
     "no_index", "no_index_fallback", "no_capacity_cut", "no_fine16", "no_fused_levels", "no_pixels16", "lift_rows",
-    "count_every_plane"))}
+    "count_every_plane", "crop_route"))}
 
 # name -> (restype, argtypes); must list every symbol include/dwtx.h declares
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
@@ -147,6 +152,8 @@ SYMBOLS = {
     "dwtx_decode_view_order": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, _vp]),
     "dwtx_decode_view_float": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), _vp]),
     "dwtx_encode_view_float": (_i, [_vp, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), _i, _i, _i, C.c_long, _vp, _sz, _vp]),
+    "dwtx_decode_view_crop": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), _i, _i, C.POINTER(_i), _vp]),
+    "dwtx_crop_plan": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(CropRect)]),
     "dwtx_tile_groups": (_i, [_i, _i, _i, C.POINTER(TileGroup)]),
     "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }

@@ -262,10 +262,21 @@ extern "C" int dwtx_encode_device16(dwtx_ctx *ctx, const uint16_t *dev_pix, int 
 	return encode_device(ctx, dwtx_pixels16(dev_pix, C, (size_t)W * H * C), W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
 }
 
+// dwtx_decode_view_crop: the windows of px are w x h, picture i's crop starts at origins[2 * i], origins[2 * i + 1] (host
+// memory; null: all at (0, 0)); checked by the caller
+struct CropCall {
+	int w, h;
+	const int *origins;
+};
+
 // streams (device) -> pixels (device).  Image i is written at px.image(i) — densely (ow*oh*C samples), or with the view's
 // row pitch into its window's corner; its size is widths/heights[info[i].level + 1].
+// crop (optional): only that window of every picture is written, into the view's windows of its size.  The entropy stage,
+// the reconstruction and the host's part / finish logic are the plain call's, with every ring in the int32 pyramid; then
+// dwtx_inv_crop and the general conversion take the place of pixels_from_pyramid.
 static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
-	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_pixels &px, dwtx_decode_info *host_info)
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_pixels &px, dwtx_decode_info *host_info,
+	const CropCall *crop = nullptr)
 {
 	const int C = px.channels;
 	if (!ctx || !dev_streams || !dev_lens || !px.base || !host_info || n < 1 || !px.sample_aligned())
@@ -289,8 +300,50 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 	// every level; the LL bands between the levels are sums of those and stay int32
 	dwtx_p16 fine16;
 	const unsigned sq = ctx->opt[DWTX_OPT_NO_SQUARE_TILES] ? 0u : dwtx_square_levels(W, H);
-	if ((rc = rings16(ctx, px, W, H, n, ctx->opt[DWTX_OPT_NO_FINE16] ? 0u : sq, nullptr, &fine16)))
+	if ((rc = rings16(ctx, px, W, H, n, ctx->opt[DWTX_OPT_NO_FINE16] || crop ? 0u : sq, nullptr, &fine16)))
 		return rc;
+	// A crop's rectangles, for the pictures that come out whole: where picture i's rectangle of plane t starts, [t][i] (x, y),
+	// rows 0 .. tail_from (dwtx_inv_crop).  One small copy that is over before the walk begins — the call synchronises anyway,
+	// and the host table does not outlive this block.  (On the context's stream: an earlier call's kernels may still read the slot.)
+	long route = 0;
+	int *crop_tab = nullptr;
+	if (crop) {
+		route = ctx->opt[DWTX_OPT_CROP_ROUTE];
+		if (route < 0 || route > 2) {
+			dwtx_set_error("DWTX_OPT_CROP_ROUTE is %ld: it takes 0 (automatic), 1 (windowed levels) or 2 (whole inverse, then a gather)", route);
+			return DWTX_ERR_ARG;
+		}
+		// (automatic: the windowed levels for every crop but the whole picture, which never comes here — no crop size has
+		// been measured slower than decode-then-slice yet)
+		if (!route)
+			route = 1;
+		dwtx_crop_steps S;
+		if ((rc = dwtx_crop_steps_of(W, H, crop->w, crop->h, &S)))
+			return rc;
+		const size_t rows = (size_t)S.tail_from + 1, tab_bytes = sizeof(int) * 2 * rows * (size_t)n;
+		crop_tab = (int *)dwtx_scratch(ctx, SLOT_CD_CROP, tab_bytes);
+		int *host_tab = (int *)malloc(tab_bytes);
+		if (!crop_tab || !host_tab) {
+			free(host_tab);
+			return DWTX_ERR_NOMEM;
+		}
+		for (int i = 0; i < n; ++i) {
+			int xs[DWTX_MAX_LEVELS + 2], ys[DWTX_MAX_LEVELS + 2];
+			dwtx_crop_origins(S, crop->origins ? crop->origins[2 * i] : 0, crop->origins ? crop->origins[2 * i + 1] : 0, xs, ys);
+			for (size_t t = 0; t < rows; ++t) {
+				host_tab[2 * (t * (size_t)n + i)] = xs[t];
+				host_tab[2 * (t * (size_t)n + i) + 1] = ys[t];
+			}
+		}
+		hipError_t e = hipMemcpyAsync(crop_tab, host_tab, tab_bytes, hipMemcpyHostToDevice, ctx->stream);
+		if (e == hipSuccess)
+			e = hipStreamSynchronize(ctx->stream);
+		free(host_tab);
+		if (e != hipSuccess) {
+			dwtx_set_error("crop origins -> %s", hipGetErrorString(e));
+			return DWTX_ERR_DEVICE;
+		}
+	}
 	// scratch both parts of the batch will ask for, sized once for the larger request (a slot that grows waits for the
 	// stream: `finish` must not grow one in the middle of the pipeline)
 	if (!dwtx_scratch(ctx, SLOT_CD_INFO, sizeof(int) * 48 * (size_t)n))
@@ -333,6 +386,27 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 		fused &= ~DWTX_FUSED_FINE16;
 		if (const int r = dwtx_reconstruction_ex(ctx, pyr, lin, miss, lo, W, H, C, count, fused, f16))    // decode.c:257 (the rest of it)
 			return r;
+		if (crop) {
+			const int32_t *planes;
+			if (lo == g.levels) {   // whole pictures: one launch per level for all of them, each with its own origin
+				if (const int r = dwtx_inv_crop(ctx, img, pyr, W, H, count, C, crop->w, crop->h, crop_tab + 2 * (size_t)first, n, 0, 0, (int)route, &planes))
+					return r;
+				return dwtx_planes_to_pixels(ctx, px.image(first), planes, crop->w, crop->h, count);
+			}
+			// reduced pictures one by one: what of the crop lies inside ow x oh, if anything
+			for (int i = 0; i < count; ++i) {
+				const int x0 = crop->origins ? crop->origins[2 * (first + i)] : 0, y0 = crop->origins ? crop->origins[2 * (first + i) + 1] : 0;
+				const int cw = (x0 + crop->w < ow ? x0 + crop->w : ow) - x0, ch = (y0 + crop->h < oh ? y0 + crop->h : oh) - y0;
+				if (cw < 1 || ch < 1)
+					continue;
+				const size_t at = (size_t)ow * oh * C * i;
+				if (const int r = dwtx_inv_crop(ctx, img + at, pyr + at, ow, oh, 1, C, cw, ch, nullptr, 0, x0, y0, (int)route, &planes))
+					return r;
+				if (const int r = dwtx_planes_to_pixels(ctx, px.image(first + i), planes, cw, ch, 1))
+					return r;
+			}
+			return DWTX_OK;
+		}
 		return pixels_from_pyramid(ctx, px.image(first), pyr, img, ow, oh, count, &f16);          // decode.c:258-264
 	};
 	// called by the decoder for each part of the batch as soon as its coefficients are on their way
@@ -377,7 +451,8 @@ extern "C" int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, s
 // order (the *_view_order calls; the others pass DWTX_ORDER_RGB): kept for RGB views and checked first, nothing else here looks at it.
 // kind (dwtx_decode_view_float, dwtx_encode_view_float; the others pass none): the float samples the view must hold — its sample_bytes their size,
 // any maxval a deep picture may have; every stride counts those samples, and every rule below holds as it stands.
-static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, dwtx_pixels *px, int kind = -1)
+// window (dwtx_decode_view_crop; the others pass false): W x H is a crop of a picture the caller has checked, a side from 1 up.
+static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, dwtx_pixels *px, int kind = -1, bool window = false)
 {
 	if (order != DWTX_ORDER_RGB && order != DWTX_ORDER_BGR) {
 		dwtx_set_error("view: channel order %d (DWTX_ORDER_RGB = 0 or DWTX_ORDER_BGR = 1)", order);
@@ -387,7 +462,10 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 		dwtx_set_error("no view, no pixels or no windows");
 		return DWTX_ERR_ARG;
 	}
-	DWTX_CHECK_DIMS(W, H);
+	if (!window)
+		DWTX_CHECK_DIMS(W, H);
+	else if (W < 1 || H < 1 || W > DWTX_MAX_SIDE || H > DWTX_MAX_SIDE)
+		return DWTX_ERR_ARG;
 	if (kind >= 0 && v->sample_bytes != (kind == DWTX_SAMPLE_F32 ? 4 : 2)) {
 		dwtx_set_error("view: sample_bytes %d does not match the float type (%d bytes a sample)", v->sample_bytes, kind == DWTX_SAMPLE_F32 ? 4 : 2);
 		return DWTX_ERR_ARG;
@@ -559,6 +637,67 @@ extern "C" int dwtx_decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams,
 		return rc;
 	set_float_format(&px, fmt);
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
+}
+
+extern "C" int dwtx_crop_plan(int W, int H, int x0, int y0, int cw, int ch, dwtx_crop_rect out[DWTX_MAX_LEVELS + 1])
+{
+	DWTX_CHECK_DIMS(W, H);
+	if (!out || cw < 1 || ch < 1 || x0 < 0 || y0 < 0 || x0 > W - cw || y0 > H - ch) {
+		dwtx_set_error("crop plan: %dx%d at (%d, %d) is no window of a %dx%d picture", cw, ch, x0, y0, W, H);
+		return DWTX_ERR_ARG;
+	}
+	dwtx_geom g;
+	if (const int rc = dwtx_geometry(&g, W, H))
+		return rc;
+	// (margins: include/dwtx.h, and lift.hip where the kernel is) outputs [a, b) of a line need k0 - 1 .. k1 of the level below
+	int xa = x0, xb = x0 + cw, ya = y0, yb = y0 + ch;
+	out[g.levels] = dwtx_crop_rect{ xa, ya, xb - xa, yb - ya };
+	for (int l = g.levels - 1; l >= 0; --l) {
+		xa = xa / 2 - 1 > 0 ? xa / 2 - 1 : 0;
+		ya = ya / 2 - 1 > 0 ? ya / 2 - 1 : 0;
+		xb = (xb + 1) / 2 + 1 < g.widths[l] ? (xb + 1) / 2 + 1 : g.widths[l];
+		yb = (yb + 1) / 2 + 1 < g.heights[l] ? (yb + 1) / 2 + 1 : g.heights[l];
+		out[l] = dwtx_crop_rect{ xa, ya, xb - xa, yb - ya };
+	}
+	return g.levels;
+}
+
+extern "C" int dwtx_decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, dwtx_decode_info *host_info)
+{
+	DWTX_CHECK_DIMS(W, H);
+	if (crop_w < 1 || crop_w > W || crop_h < 1 || crop_h > H) {
+		dwtx_set_error("crop: %dx%d is no window of a %dx%d picture (sides of 1 up to the picture's)", crop_w, crop_h, W, H);
+		return DWTX_ERR_ARG;
+	}
+	if (n < 1) {
+		dwtx_set_error("no view, no pixels or no windows");
+		return DWTX_ERR_ARG;
+	}
+	bool whole = crop_w == W && crop_h == H;
+	for (int i = 0; host_origins && i < n; ++i) {
+		const int x0 = host_origins[2 * i], y0 = host_origins[2 * i + 1];
+		if (x0 < 0 || y0 < 0 || x0 > W - crop_w || y0 > H - crop_h) {
+			dwtx_set_error("crop: origin (%d, %d) of picture %d puts its %dx%d window outside the %dx%d picture", x0, y0, i, crop_w, crop_h, W, H);
+			return DWTX_ERR_ARG;
+		}
+		whole = whole && !x0 && !y0;
+	}
+	if (whole)   // the plain call, on its own path
+		return fmt ? dwtx_decode_view_float(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, host_info)
+		           : dwtx_decode_view_order(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, host_info);
+	int kind = -1;
+	if (fmt)
+		if (const int rc = float_kind(fmt, &kind))
+			return rc;
+	dwtx_pixels px;
+	if (const int rc = pixels_of_view(dst, pixel_step, order, crop_w, crop_h, n, true, &px, kind, true))
+		return rc;
+	if (fmt)
+		set_float_format(&px, fmt);
+	const CropCall crop = { crop_w, crop_h, host_origins };
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info, &crop);
 }
 
 // The source's maxval is the quantiser's clamp (the one encode that reads it): up to 255 the picture is one of bytes and takes

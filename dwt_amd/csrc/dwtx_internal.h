@@ -6,7 +6,7 @@
 #include <stddef.h>
 #include "../../include/dwtx.h"
 
-#define DWTX_SCRATCH_SLOTS 24
+#define DWTX_SCRATCH_SLOTS 25
 #define DWTX_PART_STREAMS 4   // parts a batch runs as at the most, one stream each
 #define DWTX_ENC_PARTS DWTX_PART_STREAMS
 
@@ -141,9 +141,9 @@ enum {
 	SLOT_LIFT_A = 0, SLOT_LIFT_B,   // lift.hip
 	SLOT_PK_CUM, SLOT_PK_SMALL, SLOT_PK_ENT, SLOT_PK_TOKBIG, SLOT_PK_TOK16, SLOT_PK_LUT, SLOT_PK_CHUNK, SLOT_PK_STAGE,   // pack.hip
 	SLOT_UP_SMALL = 12, SLOT_UP_BITS, SLOT_UP_TILES, SLOT_UP_CHUNKS,   // unpack.hip
-	SLOT_CD_A, SLOT_CD_B, SLOT_CD_INFO, SLOT_CD_IO, SLOT_CD_IO2, SLOT_CD_LENS, SLOT_CD_F16, SLOT_CD_INDEX,   // codec.hip
+	SLOT_CD_A, SLOT_CD_B, SLOT_CD_INFO, SLOT_CD_IO, SLOT_CD_IO2, SLOT_CD_LENS, SLOT_CD_F16, SLOT_CD_INDEX, SLOT_CD_CROP,   // codec.hip
 };
-static_assert(SLOT_CD_INDEX < DWTX_SCRATCH_SLOTS, "more scratch slots than dwtx_ctx has");
+static_assert(SLOT_CD_CROP < DWTX_SCRATCH_SLOTS, "more scratch slots than dwtx_ctx has");
 
 static inline size_t dwtx_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -361,6 +361,25 @@ int dwtx_fwd_pixels(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels &px, int W, i
 int dwtx_inv_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *in, int W, int H, int n, const dwtx_p16 *p16 = nullptr);
 int dwtx_transformation_fwd_hist(dwtx_ctx *ctx, int32_t *out, const int32_t *in, int W, int H, int nplanes, const dwtx_hist_sink *sink,
 	unsigned *hist_levels);
+// lift.hip: the inverse transform of a window of each picture (dwtx_decode_view_crop).  Plane t of a W x H transform (0: the
+// picture, T: the root) is ws[t] x hs[t]; of it every picture of a call holds a w[t] x h[t] rectangle — the crop itself for
+// t = 0, the whole plane from the LDS tail's first step on (t >= tail_from), in between what the finer rectangle's margins
+// ask for, for either parity of its origin.  dwtx_crop_origins: where the rectangles of a picture whose crop starts at
+// (x0, y0) start, xs / ys [T + 1].
+struct dwtx_crop_steps {
+	int T, tail_from;
+	int ws[DWTX_MAX_LEVELS + 2], hs[DWTX_MAX_LEVELS + 2];
+	int w[DWTX_MAX_LEVELS + 2], h[DWTX_MAX_LEVELS + 2];
+};
+int dwtx_crop_steps_of(int W, int H, int cw, int ch, dwtx_crop_steps *S);
+void dwtx_crop_origins(const dwtx_crop_steps &S, int x0, int y0, int *xs, int *ys);
+// pyramids [n*C][H][W] -> dense planes [n*C][ch][cw], *result: the cw x ch window at (x0, y0) of every picture, or — dev_org,
+// device memory — at a place of its own for each: (x, y) pairs, the rectangle of picture i on plane t at dev_org[2 * (t *
+// org_stride + i)], rows 0 .. tail_from (dwtx_crop_origins).  route 1: windowed levels above the LDS tail, into `planes`;
+// route 2 (and any picture that is all tail): the whole inverse into `planes` [n*C][H][W], then a gather into `pyr`, which is
+// dead by then.  Either way *result says where the window's planes are.
+int dwtx_inv_crop(dwtx_ctx *ctx, int32_t *planes, int32_t *pyr, int W, int H, int n, int C, int cw, int ch,
+	const int *dev_org, long org_stride, int x0, int y0, int route, const int32_t **result);
 int dwtx_get_tiles(dwtx_ctx *ctx, int W, int H, dwtx_tiles *out);
 
 // What the entropy stage's geometries (PackGeom in pack.hip, UnpackGeom in unpack.hip) share: sizes, rings and tiles,

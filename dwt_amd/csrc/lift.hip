@@ -3835,3 +3835,291 @@ int dwtx_inv_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *in, int
 		return DWTX_ERR_ARG;
 	return lift_inv(ctx, nullptr, &px, in, W, H, n * px.channels, p16);
 }
+
+// ------------------------------------------------------------- crop decode ---
+// The inverse transform of a window (dwtx_decode_view_crop): every plane t of the transform is held
+// as a compact rectangle instead of whole, and k_inv_level_roi — k_inv_level for the pair range of a rectangle — rebuilds
+// the rectangle of plane t from the rectangle of plane t + 1 and the detail bands, which it reads from the int32 pyramid at
+// their absolute Mallat positions.
+//
+// Margins (cdf53.h:36-61, icdf53): sample 2k of a line is s[k] - (d[k-1] + d[k]) / 4 (cdf53.h:40-46; d[-1] := d[0], and the
+// last even sample of an odd line is s[k] itself), sample 2k+1 is d[k] + (x[2k] + x[2k+2]) / 2 (cdf53.h:47-53; x[N] := x[N-2]).
+// Outputs [xa, xb) are the pairs k0 = xa / 2 .. k1 - 1 with k1 = ceil(xb / 2); their even samples need d[k0-1 .. k1-1], and the
+// last odd one, 2 k1 - 1, needs x[2 k1], that is s[k1], d[k1-1] and d[k1].  Columns are undone first, rows last
+// (decode.c:21-29), so s and d of the row pass are themselves outputs of the column pass: the row pass needs columns
+// k0-1 .. k1 of its inputs, the column pass rows j0-1 .. j1 of LL and of the three detail bands — one pair more on every
+// side, clipped to the band.  (The s[k0-1] this keeps is never read; a rectangle is simpler than two.)
+//
+// All pictures of a launch share the rectangles' sizes, so that one grid serves them: the size that fits both parities of
+// an origin, s / 2 + 3 for a finer side of s (s / 2 + 1 pairs at the most, and the margins), or the whole band where that is
+// smaller.  A picture's rectangle starts at k0 - 1, shifted back inside the band where it would cross an edge: it then holds
+// more than its pictures' margins ask for, never less.  Planes from the LDS tail on are whole bands.
+namespace {
+
+struct RoiArgs {
+	const int *src;  long src_ps;  int spitch;  int sw, sh;   // LL rectangles of plane t + 1: sw x sh each, compact
+	int *dst;        long dst_ps;  int opitch;  int dw, dh;   // output rectangles of plane t: dw x dh each, compact
+	const int *det;  long det_ps;  int dpitch;                // Mallat pyramid, absolute positions
+	int w, h, w2, h2;                                         // the whole planes t and t + 1
+	int rpw;
+	int C;                                                    // planes per picture
+	const int2 *src_org, *dst_org;                            // [picture]: where its rectangles start in their planes; null: (sx, sy) / (dx, dy) for all
+	int sx, sy, dx, dy;
+};
+
+struct RoiLane {
+	int k;
+	bool valid, has_odd, right_in, frozen, writes;   // InvLane's, from the absolute pair index and the whole line's length
+};
+
+// inv_row for a rectangle's row: `row` is where column dx of the plane lies; only samples dx .. dx + dw - 1 are written
+__device__ __forceinline__ void inv_row_roi(int *__restrict__ row, const RoiLane &L, int dx, int dw, int lo, int hi)
+{
+	int hl = __shfl_up(hi, 1);
+	if (L.k <= 0)
+		hl = hi;
+	const int e = L.frozen ? lo : lo - tdiv4(hl + hi);
+	int er = __shfl_down(e, 1);
+	if (!L.right_in)
+		er = e;
+	const int o = hi + tdiv2(e + er);
+	const int x = 2 * L.k - dx;
+	if (L.writes) {
+		if (x >= 0 && x < dw)
+			row[x] = e;
+		if (L.has_odd && x + 1 >= 0 && x + 1 < dw)
+			row[x + 1] = o;
+	}
+}
+
+// grid (strips of 62 pairs over the widest pair range, strips of rpw row pairs, plane).  The picture's origins are the same
+// for the whole workgroup: they come from blockIdx alone, so the table is read with scalar loads and every range below
+// (kA, kB, jA, jB, the strip's rows) is scalar arithmetic; readfirstlane only says so once more.
+__global__ __launch_bounds__(64 * WAVES) void k_inv_level_roi(RoiArgs a)
+{
+	const int lane = threadIdx.x & 63;
+	const int wv = wave_in_block();
+	const int plane = blockIdx.z;
+	int sx = a.sx, sy = a.sy, dx = a.dx, dy = a.dy;
+	if (a.dst_org) {
+		const int img = a.C == 3 ? plane / 3 : plane;
+		const int2 d = a.dst_org[img];
+		dx = __builtin_amdgcn_readfirstlane(d.x);
+		dy = __builtin_amdgcn_readfirstlane(d.y);
+		if (a.src_org) {
+			const int2 s = a.src_org[img];
+			sx = __builtin_amdgcn_readfirstlane(s.x);
+			sy = __builtin_amdgcn_readfirstlane(s.y);
+		}
+	}
+	// the pairs and row pairs that hold the rectangle's samples
+	const int kA = dx >> 1, kB = (dx + a.dw + 1) >> 1;
+	const int jA = dy >> 1, jB = (dy + a.dh + 1) >> 1;
+	const int kb = kA + blockIdx.x * INV_PAIRS;
+	const int j0 = jA + (blockIdx.y * WAVES + wv) * a.rpw;
+	if (kb >= kB || j0 >= jB)
+		return;
+	if (dx < 0 || dy < 0 || dx + a.dw > a.w || dy + a.dh > a.h)   // (no rectangle of the plane: the host never makes one)
+		return;
+	const int j1 = min(j0 + a.rpw, jB);
+	RoiLane L;
+	L.k = kb - 1 + lane;
+	const bool mine = L.k >= 0 && L.k <= kB;   // (pair kB is the halo of the rectangle's last odd sample: nothing beyond it is read)
+	L.valid = mine && 2 * L.k < a.w;
+	L.has_odd = mine && 2 * L.k + 1 < a.w;
+	L.right_in = 2 * L.k + 2 < a.w;
+	L.frozen = (a.w & 1) && 2 * L.k == a.w - 1;
+	L.writes = L.valid && lane >= 1 && lane <= INV_PAIRS;
+
+	const int *llp = a.src + plane * a.src_ps;
+	const int *det = a.det + plane * a.det_ps;
+	int *dst = a.dst + plane * a.dst_ps;
+	const int kk = L.k < 0 ? 0 : L.k;
+	// the LL rectangle holds every (j, k) the margins ask for; the test keeps a lane inside it whatever the table says
+	const int lx = kk - sx;
+	const bool ll_col = L.valid && lx >= 0 && lx < a.sw;
+	const bool h_odd = a.h & 1;
+
+	auto details = [&](int j, int &fsh, int &fdl, int &fdh) {
+		fsh = L.has_odd ? det[(long)j * a.dpitch + a.w2 + kk] : 0;
+		const bool d_in = 2 * j + 1 < a.h;
+		fdl = (d_in && L.valid) ? det[(long)(a.h2 + j) * a.dpitch + kk] : 0;
+		fdh = (d_in && L.has_odd) ? det[(long)(a.h2 + j) * a.dpitch + a.w2 + kk] : 0;
+	};
+	auto fetch = [&](int j, int &fsl, int &fsh, int &fdl, int &fdh) {
+		const int ly = j - sy;
+		fsl = (ll_col && ly >= 0 && ly < a.sh) ? llp[(long)ly * a.spitch + lx] : 0;
+		details(j, fsh, fdl, fdh);
+	};
+	auto even_of = [&](int j, int s, int dprev, int dcur) {
+		if (h_odd && 2 * j == a.h - 1)
+			return s;
+		return s - tdiv4((j ? dprev : dcur) + dcur);
+	};
+
+	int sl, sh, dl = 0, dh = 0, pdl = 0, pdh = 0;
+	if (j0 > 0) {
+		int t1;
+		details(j0 - 1, t1, pdl, pdh);
+	}
+	fetch(j0, sl, sh, dl, dh);
+	int el = even_of(j0, sl, pdl, dl);
+	int eh = even_of(j0, sh, pdh, dh);
+	for (int jj = j0; jj < j1; ++jj) {
+		const int r0 = 2 * jj, r1 = r0 + 1;
+		int nsl = 0, nsh = 0, ndl = 0, ndh = 0;
+		int nel = el, neh = eh;          // mirror: x[h] := x[h-2]
+		if (r1 + 1 < a.h) {
+			fetch(jj + 1, nsl, nsh, ndl, ndh);
+			nel = even_of(jj + 1, nsl, dl, ndl);
+			neh = even_of(jj + 1, nsh, dh, ndh);
+		}
+		if (r0 >= dy && r0 < dy + a.dh)
+			inv_row_roi(dst + (long)(r0 - dy) * a.opitch, L, dx, a.dw, el, eh);
+		if (r1 < a.h && r1 >= dy && r1 < dy + a.dh) {
+			const int ol = dl + tdiv2(el + nel);
+			const int oh = dh + tdiv2(eh + neh);
+			inv_row_roi(dst + (long)(r1 - dy) * a.opitch, L, dx, a.dw, ol, oh);
+		}
+		dl = ndl;
+		dh = ndh;
+		el = nel;
+		eh = neh;
+	}
+}
+
+// compact cw x ch planes out of whole w x h planes: grid (64 columns, 4 rows, plane), a wave per row as the conversions have it
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_crop_planes(int *__restrict__ dst, const int *__restrict__ src, int w, int h, int cw, int ch, int C,
+	const int2 *__restrict__ org, int x0, int y0)
+{
+	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
+	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
+	const int plane = blockIdx.z;
+	if (org) {
+		const int2 o = org[C == 3 ? plane / 3 : plane];
+		x0 = __builtin_amdgcn_readfirstlane(o.x);
+		y0 = __builtin_amdgcn_readfirstlane(o.y);
+	}
+	if (x >= cw || y >= ch || x0 + x >= w || y0 + y >= h)
+		return;
+	dst[(long)plane * cw * ch + (long)y * cw + x] = src[(long)plane * w * h + (long)(y0 + y) * w + x0 + x];
+}
+
+} // namespace
+
+int dwtx_crop_steps_of(int W, int H, int cw, int ch, dwtx_crop_steps *S)
+{
+	if (!S || cw < 1 || ch < 1 || cw > W || ch > H)
+		return DWTX_ERR_ARG;
+	LiftLayout L;
+	lift_layout(nullptr, W, H, 0, L);
+	S->T = L.T;
+	S->tail_from = L.tail_from;
+	for (int t = 0; t <= L.T; ++t) {
+		S->ws[t] = L.ws[t];
+		S->hs[t] = L.hs[t];
+		const bool whole = t >= L.tail_from;
+		S->w[t] = t == 0 ? cw : whole ? L.ws[t] : min(L.ws[t], S->w[t - 1] / 2 + 3);
+		S->h[t] = t == 0 ? ch : whole ? L.hs[t] : min(L.hs[t], S->h[t - 1] / 2 + 3);
+	}
+	return DWTX_OK;
+}
+
+void dwtx_crop_origins(const dwtx_crop_steps &S, int x0, int y0, int *xs, int *ys)
+{
+	xs[0] = x0;
+	ys[0] = y0;
+	for (int t = 1; t <= S.T; ++t) {
+		xs[t] = max(0, min((xs[t - 1] >> 1) - 1, S.ws[t] - S.w[t]));
+		ys[t] = max(0, min((ys[t - 1] >> 1) - 1, S.hs[t] - S.h[t]));
+	}
+}
+
+int dwtx_inv_crop(dwtx_ctx *ctx, int32_t *planes, int32_t *pyr, int W, int H, int n, int C, int cw, int ch,
+	const int *dev_org, long org_stride, int x0, int y0, int route, const int32_t **result)
+{
+	if (!ctx || !planes || !pyr || !result || n < 1 || (C != 1 && C != 3) || W < 2 || H < 2 || x0 < 0 || y0 < 0 ||
+		!dwtx_count_ok((long)n * C, DWTX_MAX_PLANES_PER_CALL, "planes"))
+		return DWTX_ERR_ARG;
+	if (!dev_org && (x0 + cw > W || y0 + ch > H))
+		return DWTX_ERR_ARG;
+	dwtx_crop_steps S;
+	if (const int rc = dwtx_crop_steps_of(W, H, cw, ch, &S))
+		return rc;
+	DWTX_ENTER(ctx);
+	const int nplanes = n * C;
+	const int2 *org = reinterpret_cast<const int2 *>(dev_org);
+	if (route == 2 || S.tail_from == 0) {   // the whole inverse, then the gather (a transform that is all tail has no windowed level)
+		if (const int rc = lift_inv(ctx, planes, nullptr, pyr, W, H, nplanes))
+			return rc;
+		const dim3 grid((unsigned)dwtx_cdiv(cw, PX_LANES), (unsigned)dwtx_cdiv(ch, PX_ROWS), (unsigned)nplanes);
+		hipLaunchKernelGGL(k_crop_planes, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, pyr, planes, W, H, cw, ch, C, org, x0, y0);
+		DWTX_LAUNCH_CHECK();
+		*result = pyr;
+		return DWTX_OK;
+	}
+	int forced;
+	if (const int rc = forced_rows(ctx, &forced))
+		return rc;
+	LiftLayout L;
+	if (const int rc = lift_layout(ctx, W, H, nplanes, L))
+		return rc;
+	const int T = L.T, tail_from = L.tail_from;
+	const long full_ps = (long)W * H;
+	// the rectangles of plane k: level1 for odd k, small for even k (k >= 2), as lift_inv's one-level steps have it — a
+	// rectangle is never larger than its plane
+	auto plane_of = [&](int k) { return k & 1 ? L.level1 : L.small; };
+	int xs[DWTX_MAX_LEVELS + 2], ys[DWTX_MAX_LEVELS + 2];
+	dwtx_crop_origins(S, x0, y0, xs, ys);
+	const int *cur = pyr;   // (without a tail the first step reads the root LL in the pyramid itself)
+	long cur_ps = full_ps;
+	int cur_pitch = W;
+	if (tail_from < T) {
+		TailArgs ta = tail_args(L, pyr);
+		ta.dst = plane_of(tail_from);
+		ta.dst_ps = (long)L.ws[tail_from] * L.hs[tail_from];
+		ta.dpitch2 = L.ws[tail_from];
+		hipLaunchKernelGGL(k_inv_tail, dim3(nplanes), dim3(TAIL_THREADS), 0, ctx->stream, ta);
+		DWTX_LAUNCH_CHECK();
+		cur = ta.dst;
+		cur_ps = ta.dst_ps;
+		cur_pitch = ta.dpitch2;
+	}
+	for (int t = tail_from - 1; t >= 0; --t) {
+		RoiArgs a{};
+		a.src = cur;
+		a.src_ps = cur_ps;
+		a.spitch = cur_pitch;
+		a.sw = S.w[t + 1];
+		a.sh = S.h[t + 1];
+		a.dst = t == 0 ? planes : plane_of(t);
+		a.dst_ps = (long)S.w[t] * S.h[t];
+		a.opitch = S.w[t];
+		a.dw = S.w[t];
+		a.dh = S.h[t];
+		a.det = pyr;
+		a.det_ps = full_ps;
+		a.dpitch = W;
+		a.w = L.ws[t];
+		a.h = L.hs[t];
+		a.w2 = L.ws[t + 1];
+		a.h2 = L.hs[t + 1];
+		a.C = C;
+		a.dst_org = org ? org + (long)t * org_stride : nullptr;
+		a.src_org = org ? org + (long)(t + 1) * org_stride : nullptr;
+		a.sx = xs[t + 1];
+		a.sy = ys[t + 1];
+		a.dx = xs[t];
+		a.dy = ys[t];
+		const int pairs_x = a.dw / 2 + 1, pairs_y = a.dh / 2 + 1;   // the most a rectangle's samples lie in, whatever its origin's parity
+		const int sx = dwtx_cdiv(pairs_x, INV_PAIRS);
+		a.rpw = pick_rpw(sx, pairs_y, nplanes, forced);
+		hipLaunchKernelGGL(k_inv_level_roi, dim3(sx, dwtx_cdiv(pairs_y, WAVES * a.rpw), nplanes), dim3(64 * WAVES), 0, ctx->stream, a);
+		DWTX_LAUNCH_CHECK();
+		cur = a.dst;
+		cur_ps = a.dst_ps;
+		cur_pitch = a.opitch;
+	}
+	*result = planes;
+	return DWTX_OK;
+}

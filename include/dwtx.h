@@ -177,6 +177,8 @@ enum dwtx_option {
 	DWTX_OPT_LIFT_ROWS,            /* transforms: row pairs per wave strip of every lifting launch, 4, 8, 16, 32 or 64 (0 = automatic, by the size of the batch);
 	                                * the two-levels-per-pass kernels take max(2, value / 8) of their coarser row pairs; any other value: DWTX_ERR_ARG from the call */
 	DWTX_OPT_COUNT_EVERY_PLANE,    /* decoder: the ones count reads every (plane, ring) segment, also those in which no one was set */
+	DWTX_OPT_CROP_ROUTE,           /* dwtx_decode_view_crop: 1 = windowed levels above the LDS tail, 2 = the whole inverse transform into int32 planes and
+	                                * a gather of the windows (what a picture that is all tail takes anyway); 0 = automatic; any other value: DWTX_ERR_ARG from the call */
 	DWTX_OPT_COUNT
 };
 int dwtx_ctx_set_option(dwtx_ctx *ctx, int option, long value);
@@ -497,6 +499,43 @@ int dwtx_decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t str
 int dwtx_encode_view_float(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order,
 	const dwtx_float_format *fmt, int W, int H, int n, long capacity,
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
+
+/* ---- crop decode: a window of each picture straight into a view ---------------------------------------------------------
+ * dwtx_decode_view_order (fmt == NULL: integer samples) or dwtx_decode_view_float (fmt given) for the step an image pipeline
+ * takes next: a training loader's random crop, a viewer's viewport, one detection box of a large frame — without the
+ * full-size frame, the inverse transform and the egress of what nobody keeps, and the copy per picture that crops with
+ * origins of their own need afterwards.  W, H are the streams' geometry; the windows of dst are crop_w x crop_h, and every
+ * rule of the plain call holds word for word with the crop's sides in place of the picture's: disjointness, row length,
+ * alignment, the planar forms, pixel_step, order and maxval.  A crop side may be anything from 1 up (the 8-pixel minimum
+ * belongs to pictures, not to windows).  host_origins: [n][2] ints in host memory, (x0, y0) of picture i's crop, read
+ * before the call returns; NULL: all (0, 0).
+ * Contract: let P_i be what the plain call would write into a full W x H window for stream i — the ow x oh picture the stream
+ * supports, all clamps and the missing-plane bias of decode.c:51-58 applied.  Sample (x, y) of window i receives
+ * P_i(x0_i + x, y0_i + y) for every (x0_i + x, y0_i + y) inside ow x oh, and NO OTHER SAMPLE is written: not the rest of the
+ * window when the stream came out reduced, not the space between stepped pixels, not the frame around the windows, not the
+ * windows of streams with status 1 or 2.  A crop that lies wholly outside a reduced picture writes nothing.  host_info[i]
+ * is exactly what the plain call reports, and the call synchronises where the plain call does.
+ * With crop_w == W, crop_h == H and all origins (0, 0) the call IS the plain call: it takes its path.
+ * Otherwise the entropy stage runs as ever, with every ring in the int32 pyramid (as under DWTX_OPT_NO_FINE16); above the
+ * LDS tail (levels of at most 64 per side) the inverse transform rebuilds only the rectangle of each level that the crop
+ * needs (dwtx_crop_plan), and the general conversion writes the windows.  DWTX_OPT_CROP_ROUTE chooses between that and
+ * the whole inverse transform followed by a gather; the results are the same.
+ * DWTX_ERR_ARG (with a dwtx_last_error() text, nothing written): crop_w outside 1..W or crop_h outside 1..H; an origin with
+ * x0 < 0, y0 < 0, x0 + crop_w > W or y0 + crop_h > H; and everything the plain calls refuse. */
+int dwtx_decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, dwtx_decode_info *host_info);
+
+/* Host arithmetic only, like dwtx_tile_groups: the rectangle of every level that the cw x ch crop at (x0, y0) of a W x H
+ * picture needs.  out[l] is the rectangle of the widths[l] x heights[l] LL band (dwtx_geometry; l = levels is the picture
+ * itself, l = 0 the root) that must be held — and, at the same coordinates, of each of the three detail bands beside it —
+ * clipped to the band.  From icdf53 (cdf53.h:36-61): sample 2k is s[k] - (d[k-1] + d[k]) / 4 (cdf53.h:40-46), sample 2k+1
+ * is d[k] + (x[2k] + x[2k+2]) / 2 (cdf53.h:47-53), so outputs [xa, xb) — the pairs k0 = xa / 2 .. ceil(xb / 2) - 1 — need
+ * columns k0 - 1 .. k1 = ceil(xb / 2) of the level below, and rows likewise (decode.c:21-29 undoes columns first, so the
+ * row pass's inputs are the column pass's outputs and both bands' margins apply to all four bands).  Returns `levels`;
+ * DWTX_ERR_ARG for a picture no entry point takes, a crop side below 1 and a crop that leaves the picture. */
+typedef struct dwtx_crop_rect { int x0, y0, w, h; } dwtx_crop_rect;
+int dwtx_crop_plan(int W, int H, int x0, int y0, int cw, int ch, dwtx_crop_rect out[DWTX_MAX_LEVELS + 1]);
 
 /* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
  * interior, right column, bottom row, corner, in that order, those that exist — each a cols x rows grid of W x H tiles
