@@ -13,6 +13,7 @@ from . import _lib
 from ._lib import Geom, Stats, StreamInfo, DecodeInfo, Index, SegIndex, View, TileGroup, FloatFormat, CropRect, INDEX_MAGIC, INDEX_MAX_SEGS, LIB_PATH  # noqa: F401
 
 __all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "tile_groups", "view_fields", "view_order", "float_format", "crop_plan",
+           "view_list_fields", "view_list_check",
            "Geom", "Stats", "View", "TileGroup", "FloatFormat", "CropRect"]
 
 
@@ -130,6 +131,47 @@ def view_fields(shape, strides, stepped=False):
         n, cols, band = shape[0] * shape[1], shape[1], strides[0]
     return dict(W=W, H=H, channels=Cn, n=n, cols=cols, row_pitch=sh, image_stride=strides[-4], band_stride=band,
                 channel_stride=sc if planar else 0, pixel_step=step)
+
+
+def view_list_fields(windows, stepped=False):
+    """A sequence of n tensors [H,W,C] — separately allocated pictures, slices of a frame, permuted [C,H,W] tensors — of
+    one shape, one set of strides, one dtype and one device -> (fields, pointers): view_fields of the shape with a leading
+    1 (n set to the list's length; cols, image_stride and band_stride say nothing of a list), and the tensors' data
+    pointers.  A ValueError names the first tensor that differs from the first one."""
+    ws = list(windows)
+    if not ws:
+        raise ValueError("a window list needs at least one tensor")
+    t0 = ws[0]
+    if len(t0.shape) != 3:
+        raise ValueError(f"a window list holds tensors [H,W,C], not {tuple(t0.shape)}")
+    key0 = (t0.shape, t0.stride(), t0.dtype, t0.device)
+    for i, t in enumerate(ws):
+        if (t.shape, t.stride(), t.dtype, t.device) == key0:   # (one comparison per window: a list may hold thousands)
+            continue
+        for what, a, b in (("shape", tuple(t.shape), tuple(t0.shape)), ("strides", tuple(t.stride()), tuple(t0.stride())),
+                           ("dtype", t.dtype, t0.dtype), ("device", t.device, t0.device)):
+            if a != b:
+                raise ValueError(f"window {i} has {what} {a}, window 0 has {b}: the windows of a list share them")
+    f = view_fields((1,) + tuple(t0.shape), (0,) + tuple(t0.stride()), stepped)
+    f.update(n=len(ws), cols=0, image_stride=0, band_stride=0)
+    return f, [t.data_ptr() for t in ws]
+
+
+def view_list_check(pointers, W, H, channels=1, row_pitch=None, channel_stride=0, pixel_step=0, sample_bytes=1, maxval=None, dst=True):
+    """dwtx_view_list_check: what encode_view_list (dst=False) and decode_view_list (dst=True) say to n windows of W x H at
+    `pointers` (plain integers, never dereferenced; None or 0: a NULL entry) -> (rc, text): (0, "") for a list they take,
+    else the error code and the text of the refusal.  Strides count samples, as in view_fields; row_pitch None: dense
+    rows.  Host arithmetic only: needs no device."""
+    lib = _lib.load()
+    if row_pitch is None:
+        row_pitch = W if channels == 3 and channel_stride else ((W - 1) * pixel_step + channels if pixel_step else W * channels)
+    if maxval is None:
+        maxval = 255 if sample_bytes == 1 else 65535
+    v = View(None, sample_bytes, channels, maxval, 0, row_pitch, 0, 0, channel_stride)
+    ptrs = list(pointers)
+    arr = (C.c_void_p * max(len(ptrs), 1))(*[p or None for p in ptrs])
+    rc = lib.dwtx_view_list_check(C.byref(v), pixel_step, W, H, len(ptrs), arr, 1 if dst else 0)
+    return rc, (lib.dwtx_last_error().decode(errors="replace") if rc else "")
 
 
 def _ptr(t):
@@ -682,4 +724,75 @@ class Context:
         _check(self.lib.dwtx_decode_view_crop(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
                                               C.byref(fmt) if fmt is not None else None, cw, ch, org, C.cast(infos, C.c_void_p)),
                "dwtx_decode_view_crop")
+        return list(infos)
+
+    # -- window lists: one pointer per picture (dwtx_encode_view_list / dwtx_decode_view_list) ------------------------
+
+    def _view_list(self, windows, maxval, stepped):
+        """The View (dev NULL), the ctypes array of the windows' pointers and the fields of a list of device tensors [H,W,C]
+        (view_list_fields); floats: whether they hold float samples, and then their FloatFormat's dtype."""
+        torch = self.torch
+        f, ptrs = view_list_fields(windows, stepped)
+        t0 = windows[0]
+        floats = t0.dtype in (torch.float32, torch.float16, torch.bfloat16)
+        if (not floats and t0.dtype not in (torch.uint8, torch.uint16, torch.int16)) or t0.device != self.device:
+            raise ValueError("a window list holds uint8, uint16 / int16 or float32 / float16 / bfloat16 tensors [H,W,C] on the context's device")
+        if maxval is None:
+            maxval = 255 if floats or t0.dtype == torch.uint8 else 65535
+        v = View(None, t0.element_size(), f["channels"], int(maxval), 0, f["row_pitch"], 0, 0, f["channel_stride"])
+        return v, (C.c_void_p * len(ptrs))(*ptrs), f, floats
+
+    def encode_view_list(self, windows, maxval=None, scale=None, bias=None, capacity=0, out=None, info=None, stepped=False, order="rgb"):
+        """dwtx_encode_view_list: encode_view — or encode_view_float, when the windows are float tensors — of a sequence of n
+        device tensors [H,W,C] that lie wherever they lie: separately allocated pictures, boxes of a frame, tiles in any
+        order, permuted [C,H,W] tensors; one shape, one set of strides, one dtype (view_list_fields).  Windows may overlap
+        and repeat.  No stack is built: the library reads each window in place.  maxval (float windows: the quantiser's
+        clamp, default 255), scale, bias: as for encode_view_float; stepped, order: as for encode_view.  Returns (streams,
+        info) like encode_view; async."""
+        order = view_order(order)
+        torch = self.torch
+        v, arr, f, floats = self._view_list(windows, maxval, stepped)
+        if not floats and (scale is not None or bias is not None):
+            raise ValueError("scale and bias belong to float tensors")
+        fmt = float_format(windows[0].dtype, 1.0 if scale is None else scale, 0.0 if bias is None else bias) if floats else None
+        W, H, Cn, n = f["W"], f["H"], f["channels"], f["n"]
+        deep = v.maxval > 255 if floats else v.sample_bytes == 2
+        bound = self.lib.dwtx_encode_bound16 if deep else self.lib.dwtx_encode_bound
+        stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
+        if out is None:
+            out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
+        if info is None:
+            info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
+        _check(self.lib.dwtx_encode_view_list(self.h, C.byref(v), f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, arr,
+                                              W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view_list")
+        return out, info
+
+    def decode_view_list(self, streams, lens, windows, size=None, origins=None, maxval=None, scale=None, bias=None, levels_max=-1,
+                         stepped=False, order="rgb"):
+        """dwtx_decode_view_list: decode_view_crop into a sequence of n device tensors [H,W,C] that lie wherever they lie (the
+        lists encode_view_list takes), which must be provably disjoint (include/dwtx.h).  size=None: whole pictures of the
+        windows' size; else size=(W, H) is the streams' geometry, the windows are crops of it and origins their (x0, y0), as for
+        decode_view_crop.  Float windows are written as decode_view_float writes them (maxval, scale, bias).  Nothing but
+        the windows' samples is written.  Returns the list of DecodeInfo; syncs once."""
+        order = view_order(order)
+        torch = self.torch
+        v, arr, f, floats = self._view_list(windows, maxval, stepped)
+        if not floats and (scale is not None or bias is not None):
+            raise ValueError("scale and bias belong to float tensors")
+        fmt = float_format(windows[0].dtype, 1.0 if scale is None else scale, 0.0 if bias is None else bias) if floats else None
+        cw, ch, n = f["W"], f["H"], f["n"]
+        W, H = (cw, ch) if size is None else (int(s) for s in size)
+        org = None
+        if origins is not None:
+            flat = [int(c) for c in origins] if len(origins) == 2 and not hasattr(origins[0], "__len__") else None
+            pairs = [tuple(flat)] * n if flat is not None else [(int(x), int(y)) for x, y in origins]
+            if len(pairs) != n:
+                raise ValueError(f"origins: one (x0, y0) pair or {n}, not {len(pairs)}")
+            org = (C.c_int * (2 * n))(*[c for p in pairs for c in p])
+        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
+        assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
+        infos = (DecodeInfo * n)()
+        _check(self.lib.dwtx_decode_view_list(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
+                                              f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, cw, ch, org, arr,
+                                              C.cast(infos, C.c_void_p)), "dwtx_decode_view_list")
         return list(infos)

@@ -154,6 +154,11 @@ SYMBOLS = {
     "dwtx_encode_view_float": (_i, [_vp, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), _i, _i, _i, C.c_long, _vp, _sz, _vp]),
     "dwtx_decode_view_crop": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), _i, _i, C.POINTER(_i), _vp]),
     "dwtx_crop_plan": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(CropRect)]),
+    # window lists: one device pointer per picture, in a host array
+    "dwtx_encode_view_list": (_i, [_vp, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), C.POINTER(_vp), _i, _i, _i, C.c_long, _vp, _sz, _vp]),
+    "dwtx_decode_view_list": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), _i, _i, C.POINTER(_i),
+                                   C.POINTER(_vp), _vp]),
+    "dwtx_view_list_check": (_i, [C.POINTER(View), _sz, _i, _i, _i, C.POINTER(_vp), _i]),
     "dwtx_tile_groups": (_i, [_i, _i, _i, C.POINTER(TileGroup)]),
     "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }

@@ -7,6 +7,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+#include <vector>
+
 static size_t encode_bound(int bytes_per_sample, int W, int H, int C)
 {
 	size_t b = (size_t)bytes_per_sample * W * H * C + 4096;
@@ -452,13 +455,27 @@ extern "C" int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, s
 // kind (dwtx_decode_view_float, dwtx_encode_view_float; the others pass none): the float samples the view must hold — its sample_bytes their size,
 // any maxval a deep picture may have; every stride counts those samples, and every rule below holds as it stands.
 // window (dwtx_decode_view_crop; the others pass false): W x H is a crop of a picture the caller has checked, a side from 1 up.
-static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, dwtx_pixels *px, int kind = -1, bool window = false)
+// list (the *_view_list calls; the others pass none): the windows lie where list->windows says; the view's dev, cols,
+// image_stride and band_stride are not looked at, every other check is the grid's, and list_windows takes the place of the
+// rules about where the windows lie.  px->offs is not set yet: the caller brings list->offs to the device (send_list).
+struct WinList {
+	const void *const *windows;   // [n] device pointers in host memory
+	std::vector<long long> offs;  // out: each window's first sample, in samples from the lowest pointer
+};
+static int list_windows(const dwtx_view *v, size_t cs, size_t row, int H, int n, bool dst, WinList *list, dwtx_pixels *px);
+
+static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, dwtx_pixels *px, int kind = -1, bool window = false,
+	WinList *list = nullptr)
 {
 	if (order != DWTX_ORDER_RGB && order != DWTX_ORDER_BGR) {
 		dwtx_set_error("view: channel order %d (DWTX_ORDER_RGB = 0 or DWTX_ORDER_BGR = 1)", order);
 		return DWTX_ERR_ARG;
 	}
-	if (!v || !v->dev || n < 1) {
+	if (list && !list->windows) {
+		dwtx_set_error("view list: no list of windows (the grid calls take a view without one)");
+		return DWTX_ERR_ARG;
+	}
+	if (!v || (!list && !v->dev) || n < 1) {
 		dwtx_set_error("no view, no pixels or no windows");
 		return DWTX_ERR_ARG;
 	}
@@ -470,7 +487,7 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 		dwtx_set_error("view: sample_bytes %d does not match the float type (%d bytes a sample)", v->sample_bytes, kind == DWTX_SAMPLE_F32 ? 4 : 2);
 		return DWTX_ERR_ARG;
 	}
-	if ((kind < 0 && v->sample_bytes != 1 && v->sample_bytes != 2) || (v->channels != 1 && v->channels != 3) || v->cols < 0) {
+	if ((kind < 0 && v->sample_bytes != 1 && v->sample_bytes != 2) || (v->channels != 1 && v->channels != 3) || (!list && v->cols < 0)) {
 		dwtx_set_error("view: sample_bytes %d (1 or 2), channels %d (1 or 3), cols %d (>= 0)", v->sample_bytes, v->channels, v->cols);
 		return DWTX_ERR_ARG;
 	}
@@ -490,18 +507,18 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 		dwtx_set_error("view: row_pitch %zu is less than a window's row of %zu samples", v->row_pitch, row);
 		return DWTX_ERR_ARG;
 	}
-	if ((uintptr_t)v->dev % (size_t)v->sample_bytes) {
+	if (!list && (uintptr_t)v->dev % (size_t)v->sample_bytes) {
 		dwtx_set_error("view: dev is not aligned to its %d-byte samples", v->sample_bytes);
 		return DWTX_ERR_ARG;
 	}
-	const size_t cols = v->cols && v->cols < n ? (size_t)v->cols : (size_t)n;
+	const size_t cols = list ? (size_t)n : v->cols && v->cols < n ? (size_t)v->cols : (size_t)n;
 	const bool bands = cols < (size_t)n;
-	if (dst) {
-		if (v->sample_bytes == 1 ? v->maxval != 255 : !dwtx_maxval_ok(v->maxval)) {
-			if (v->sample_bytes == 1)
-				dwtx_set_error("view: maxval %d with 1-byte samples (255)", v->maxval);
-			return DWTX_ERR_ARG;
-		}
+	if (dst && (v->sample_bytes == 1 ? v->maxval != 255 : !dwtx_maxval_ok(v->maxval))) {
+		if (v->sample_bytes == 1)
+			dwtx_set_error("view: maxval %d with 1-byte samples (255)", v->maxval);
+		return DWTX_ERR_ARG;
+	}
+	if (dst && !list) {
 		const size_t window = (size_t)(H - 1) * v->row_pitch + row;   // from a window's (a plane's) first sample to behind its last
 		const bool stacked = v->image_stride >= window;
 		const bool beside = v->image_stride >= row && v->row_pitch >= (cols - 1) * v->image_stride + row;
@@ -528,17 +545,117 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 			}
 		}
 	}
-	*px = kind >= 0            ? dwtx_pixels_float(v->dev, kind, v->channels, v->image_stride, v->maxval)
-		: v->sample_bytes == 1 ? dwtx_pixels8((const uint8_t *)v->dev, v->channels, v->image_stride)
-		                       : dwtx_pixels16((const uint16_t *)v->dev, v->channels, v->image_stride, dst ? v->maxval : 65535);
+	const size_t image_stride = list ? 0 : v->image_stride;
+	*px = kind >= 0            ? dwtx_pixels_float(v->dev, kind, v->channels, image_stride, v->maxval)
+		: v->sample_bytes == 1 ? dwtx_pixels8((const uint8_t *)v->dev, v->channels, image_stride)
+		                       : dwtx_pixels16((const uint16_t *)v->dev, v->channels, image_stride, dst ? v->maxval : 65535);
 	px->row_pitch = v->row_pitch;
 	px->channel_stride = cs;
 	px->pixel_step = step;
 	px->order = v->channels == 3 ? order : DWTX_ORDER_RGB;
+	if (list)
+		return list_windows(v, cs, row, H, n, dst, list, px);
 	if (bands) {
 		px->cols = (int)cols;
 		px->band_stride = v->band_stride;
 	}
+	return DWTX_OK;
+}
+
+// What a listed view adds to pixels_of_view (include/dwtx.h, the *_view_list calls): every pointer given and on its sample;
+// px->base the lowest of them and list->offs the windows' offsets from it; whether all of them are on the wide kernels' quad;
+// and, for a destination, that the units — the n windows, or the 3n planes of planar RGB — are provably disjoint.
+// Two units whose first samples lie d apart are disjoint if d >= span (one ends before the other begins), or if, with dx =
+// d % pitch, dx >= row and dx + row <= pitch: unit A covers the columns [0, row) of the lattice of rows `pitch` apart that
+// starts at its first sample, unit B the columns [dx, dx + row) of the same lattice.  Sorted by address, only the units that
+// begin inside a unit's span have to be held against it: a frame of tiles costs each tile the tiles of its own band.
+static int list_windows(const dwtx_view *v, size_t cs, size_t row, int H, int n, bool dst, WinList *list, dwtx_pixels *px)
+{
+	if (dst ? !dwtx_count_ok(n, DWTX_MAX_PLANES_PER_CALL / 3, "streams to decode") : !dwtx_count_ok((long)n * v->channels, DWTX_MAX_PLANES_PER_CALL, "planes"))
+		return DWTX_ERR_ARG;
+	const uintptr_t sb = (uintptr_t)v->sample_bytes;
+	uintptr_t lowest = ~(uintptr_t)0;
+	bool quad = true;
+	for (int i = 0; i < n; ++i) {
+		const uintptr_t p = (uintptr_t)list->windows[i];
+		if (!p) {
+			dwtx_set_error("view list: window %d of %d is NULL", i, n);
+			return DWTX_ERR_ARG;
+		}
+		if (p % sb) {
+			dwtx_set_error("view list: window %d (%p) is not aligned to its %d-byte samples", i, list->windows[i], v->sample_bytes);
+			return DWTX_ERR_ARG;
+		}
+		quad = quad && p % (4 * sb) == 0;
+		lowest = p < lowest ? p : lowest;
+	}
+	struct Unit {
+		unsigned long long at;
+		int window;
+	};
+	std::vector<Unit> units;
+	try {
+		list->offs.resize((size_t)n);
+		if (dst)
+			units.reserve((size_t)n * (cs ? 3 : 1));
+	} catch (...) {
+		return DWTX_ERR_NOMEM;
+	}
+	for (int i = 0; i < n; ++i)
+		list->offs[(size_t)i] = (long long)(((uintptr_t)list->windows[i] - lowest) / sb);
+	if (dst) {
+		const unsigned long long pitch = v->row_pitch, span = (unsigned long long)(H - 1) * pitch + row;
+		for (int i = 0; i < n; ++i)
+			for (int c = 0; c < (cs ? 3 : 1); ++c)
+				units.push_back(Unit{ (unsigned long long)list->offs[(size_t)i] + (unsigned long long)c * cs, i });
+		std::sort(units.begin(), units.end(), [](const Unit &a, const Unit &b) { return a.at < b.at; });
+		for (size_t i = 0; i < units.size(); ++i)
+			for (size_t j = i + 1; j < units.size() && units[j].at - units[i].at < span; ++j) {
+				const unsigned long long d = units[j].at - units[i].at, dx = d % pitch;
+				if (dx >= row && dx + row <= pitch)
+					continue;
+				dwtx_set_error("view list: windows %d and %d are not provably disjoint (%s %llu samples apart: less than the %llu a %s spans, "
+					"and column %llu of a pitch of %llu leaves no room for two rows of %zu)", units[i].window, units[j].window,
+					cs ? "two of their planes lie" : "they lie", d, span, cs ? "plane" : "window", dx, pitch, row);
+				return DWTX_ERR_ARG;
+			}
+	}
+	px->base = (void *)lowest;
+	px->offs_on_quad = quad;
+	return DWTX_OK;
+}
+
+// The table's way to the device: into the context's page-locked buffer — the caller's array and list.offs may go as soon as the
+// call returns — and from there into SLOT_CD_LIST by an asynchronous copy on the context's stream, in order with the kernels of an
+// earlier listed call that still read the slot and ahead of this call's.  The host waits only for list_sent, the earlier listed
+// call's own copy; a slot or a buffer that has to grow waits for more, as every scratch slot does.  Sets px->offs.
+static int send_list(dwtx_ctx *ctx, const WinList &list, dwtx_pixels *px)
+{
+	if (!ctx)
+		return DWTX_ERR_ARG;
+	DWTX_ENTER(ctx);
+	const size_t n = list.offs.size(), bytes = sizeof(long long) * n;
+	if (!ctx->have_list_sent) {
+		DWTX_HIP(hipEventCreateWithFlags(&ctx->list_sent, hipEventDisableTiming));
+		ctx->have_list_sent = true;
+	}
+	DWTX_HIP(hipEventSynchronize(ctx->list_sent));   // (an event that was never recorded counts as reached)
+	if (ctx->list_cap < n) {
+		if (ctx->list_host)
+			(void)hipHostFree(ctx->list_host);
+		ctx->list_host = nullptr;
+		ctx->list_cap = 0;
+		const size_t want = n + n / 8 + 64;
+		DWTX_HIP(hipHostMalloc((void **)&ctx->list_host, sizeof(long long) * want, hipHostMallocDefault));
+		ctx->list_cap = want;
+	}
+	long long *dev = (long long *)dwtx_scratch(ctx, SLOT_CD_LIST, bytes);
+	if (!dev)
+		return DWTX_ERR_NOMEM;
+	memcpy(ctx->list_host, list.offs.data(), bytes);
+	DWTX_HIP(hipMemcpyAsync(dev, ctx->list_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+	DWTX_HIP(hipEventRecord(ctx->list_sent, ctx->stream));
+	px->offs = dev;
 	return DWTX_OK;
 }
 
@@ -662,9 +779,8 @@ extern "C" int dwtx_crop_plan(int W, int H, int x0, int y0, int cw, int ch, dwtx
 	return g.levels;
 }
 
-extern "C" int dwtx_decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
-	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int crop_w, int crop_h, const int *host_origins, dwtx_decode_info *host_info)
+// what the crop calls refuse of a crop and its origins; *whole: the crop is every picture itself (the plain call)
+static int crop_of_call(int W, int H, int n, int crop_w, int crop_h, const int *host_origins, bool *whole)
 {
 	DWTX_CHECK_DIMS(W, H);
 	if (crop_w < 1 || crop_w > W || crop_h < 1 || crop_h > H) {
@@ -675,15 +791,25 @@ extern "C" int dwtx_decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, 
 		dwtx_set_error("no view, no pixels or no windows");
 		return DWTX_ERR_ARG;
 	}
-	bool whole = crop_w == W && crop_h == H;
+	*whole = crop_w == W && crop_h == H;
 	for (int i = 0; host_origins && i < n; ++i) {
 		const int x0 = host_origins[2 * i], y0 = host_origins[2 * i + 1];
 		if (x0 < 0 || y0 < 0 || x0 > W - crop_w || y0 > H - crop_h) {
 			dwtx_set_error("crop: origin (%d, %d) of picture %d puts its %dx%d window outside the %dx%d picture", x0, y0, i, crop_w, crop_h, W, H);
 			return DWTX_ERR_ARG;
 		}
-		whole = whole && !x0 && !y0;
+		*whole = *whole && !x0 && !y0;
 	}
+	return DWTX_OK;
+}
+
+extern "C" int dwtx_decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, dwtx_decode_info *host_info)
+{
+	bool whole;
+	if (const int rc = crop_of_call(W, H, n, crop_w, crop_h, host_origins, &whole))
+		return rc;
 	if (whole)   // the plain call, on its own path
 		return fmt ? dwtx_decode_view_float(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, host_info)
 		           : dwtx_decode_view_order(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, host_info);
@@ -716,6 +842,66 @@ extern "C" int dwtx_encode_view_float(dwtx_ctx *ctx, const dwtx_view *src, size_
 		return DWTX_ERR_ARG;
 	set_float_format(&px, fmt);
 	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
+}
+
+// ---- window lists (include/dwtx.h): one pointer per picture --------------------------------------------------------------
+
+extern "C" int dwtx_view_list_check(const dwtx_view *v, size_t pixel_step, int W, int H, int n, const void *const *host_windows, int dst)
+{
+	WinList list{ host_windows, {} };
+	dwtx_pixels px;
+	// (a view of 4-byte samples is one of fp32 samples; fp16 and bf16 views are addressed, and checked, like 16-bit integers)
+	return pixels_of_view(v, pixel_step, DWTX_ORDER_RGB, W, H, n, dst != 0, &px, v && v->sample_bytes == 4 ? DWTX_SAMPLE_F32 : -1, true, &list);
+}
+
+extern "C" int dwtx_encode_view_list(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	const void *const *host_windows, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	if (!ctx || !dev_out || !dev_info)
+		return DWTX_ERR_ARG;
+	int kind = -1;
+	if (fmt)
+		if (const int rc = float_kind(fmt, &kind))
+			return rc;
+	WinList list{ host_windows, {} };
+	dwtx_pixels px;
+	if (const int rc = pixels_of_view(src, pixel_step, order, W, H, n, false, &px, kind, false, &list))
+		return rc;
+	if (fmt) {
+		if (!dwtx_maxval_ok(src->maxval))
+			return DWTX_ERR_ARG;
+		set_float_format(&px, fmt);
+	}
+	if (const int rc = send_list(ctx, list, &px))
+		return rc;
+	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx->enc_index);
+}
+
+extern "C" int dwtx_decode_view_list(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, dwtx_decode_info *host_info)
+{
+	if (!ctx || !dev_streams || !dev_lens || !host_info)
+		return DWTX_ERR_ARG;
+	bool whole;
+	if (const int rc = crop_of_call(W, H, n, crop_w, crop_h, host_origins, &whole))
+		return rc;
+	int kind = -1;
+	if (fmt)
+		if (const int rc = float_kind(fmt, &kind))
+			return rc;
+	WinList list{ host_windows, {} };
+	dwtx_pixels px;
+	if (const int rc = pixels_of_view(dst, pixel_step, order, crop_w, crop_h, n, true, &px, kind, !whole, &list))
+		return rc;
+	if (fmt)
+		set_float_format(&px, fmt);
+	if (const int rc = send_list(ctx, list, &px))
+		return rc;
+	if (whole)
+		return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
+	const CropCall crop = { crop_w, crop_h, host_origins };
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info, &crop);
 }
 
 // one axis of dwtx_tile_groups: `full` tiles of `tile`, then one of `last` (0: none)

@@ -188,6 +188,10 @@ extern "C" void dwtx_ctx_destroy(dwtx_ctx *c)
 		(void)hipStreamDestroy(c->side[i]);
 	if (c->nside)
 		destroy_events(c->dec_ev);
+	if (c->list_host)
+		(void)hipHostFree(c->list_host);
+	if (c->have_list_sent)
+		(void)hipEventDestroy(c->list_sent);
 	if (c->have_copy) {
 		(void)hipStreamDestroy(c->copy);
 		destroy_events(c->copy_ev);

@@ -6,7 +6,7 @@
 #include <stddef.h>
 #include "../../include/dwtx.h"
 
-#define DWTX_SCRATCH_SLOTS 25
+#define DWTX_SCRATCH_SLOTS 26
 #define DWTX_PART_STREAMS 4   // parts a batch runs as at the most, one stream each
 #define DWTX_ENC_PARTS DWTX_PART_STREAMS
 
@@ -46,6 +46,13 @@ struct dwtx_ctx {
 	size_t index_base;            // entry of the current call's first image (the host pipeline decodes a batch in parts)
 	dwtx_index *enc_index;        // dwtx_ctx_set_encode_index: where the encode calls leave the sidecar indices of their streams
 	long opt[DWTX_OPT_COUNT];     // dwtx_ctx_set_option: diagnostic switches (tests, tools), all 0 by default
+	// the *_view_list calls (codec.hip): the window table's way to SLOT_CD_LIST.  A page-locked buffer of list_cap offsets that an
+	// asynchronous copy reads after the call has returned; list_sent fires when the copy has read it, and the next listed call
+	// waits for that — for its own predecessor's copy, never for the stream — before it fills the buffer again
+	long long *list_host;
+	size_t list_cap;
+	hipEvent_t list_sent;
+	bool have_list_sent;
 };
 
 // Every entry point that allocates, launches or copies makes the context's device the calling thread's current
@@ -141,9 +148,9 @@ enum {
 	SLOT_LIFT_A = 0, SLOT_LIFT_B,   // lift.hip
 	SLOT_PK_CUM, SLOT_PK_SMALL, SLOT_PK_ENT, SLOT_PK_TOKBIG, SLOT_PK_TOK16, SLOT_PK_LUT, SLOT_PK_CHUNK, SLOT_PK_STAGE,   // pack.hip
 	SLOT_UP_SMALL = 12, SLOT_UP_BITS, SLOT_UP_TILES, SLOT_UP_CHUNKS,   // unpack.hip
-	SLOT_CD_A, SLOT_CD_B, SLOT_CD_INFO, SLOT_CD_IO, SLOT_CD_IO2, SLOT_CD_LENS, SLOT_CD_F16, SLOT_CD_INDEX, SLOT_CD_CROP,   // codec.hip
+	SLOT_CD_A, SLOT_CD_B, SLOT_CD_INFO, SLOT_CD_IO, SLOT_CD_IO2, SLOT_CD_LENS, SLOT_CD_F16, SLOT_CD_INDEX, SLOT_CD_CROP, SLOT_CD_LIST,   // codec.hip
 };
-static_assert(SLOT_CD_CROP < DWTX_SCRATCH_SLOTS, "more scratch slots than dwtx_ctx has");
+static_assert(SLOT_CD_LIST < DWTX_SCRATCH_SLOTS, "more scratch slots than dwtx_ctx has");
 
 static inline size_t dwtx_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -179,6 +186,8 @@ template <class F> char *carve(dwtx_ctx *ctx, int slot, F &&fn)
 // samples, whatever their size.  (A view of a source is only read; the view does not say which it is.)
 // The pictures may be windows of a larger frame (include/dwtx.h, dwtx_view): rows row_pitch apart, the windows a grid of
 // bands of `cols` each.  Window i of the view is window first + i of the grid, which starts at `base`.
+// Or the windows lie wherever the caller's list says (offs, the *_view_list calls): window i of the view starts offs[first + i]
+// samples after `base`, the lowest pointer of the list; cols, image_stride and band_stride then say nothing.
 // RGB samples are interleaved, or planar (channel_stride != 0, views only: include/dwtx.h): three planes per window,
 // columns one sample apart; the host-buffer pipelines and every dense entry point stay interleaved.
 // Interleaved and gray pixels may lie further apart than their own samples (pixel_step, the *_view_step calls only): the
@@ -210,6 +219,8 @@ struct dwtx_pixels {
 	int order = DWTX_ORDER_RGB;  // which colour the three channels are as they lie (DWTX_ORDER_*; image() and moved() keep it); gray pixels have none
 	int kind = DWTX_SAMPLE_U8;   // dwtx_sample_kind (dwtx_pixels8 / dwtx_pixels16 / dwtx_pixels_float set it with sample_bytes)
 	float scale[3] = { 1.f, 1.f, 1.f }, bias[3] = { 0.f, 0.f, 0.f };   // float samples: per colour R, G, B (gray: [0])
+	const long long *offs = nullptr;   // listed windows: DEVICE table of their first samples' offsets from base (>= 0), read-only while kernels run; image() and moved() keep it
+	bool offs_on_quad = true;          // listed windows: every offset is a multiple of 4 (what wide() asks of each window beyond base)
 
 	// uint16_t samples — and with them the kernel family that clamps at maxval and keeps no 16-bit ring planes
 	bool deep() const { return kind == DWTX_SAMPLE_U16; }
@@ -223,7 +234,8 @@ struct dwtx_pixels {
 	// (lift.hip's LevelArgs::src8 / dst8, whose kernels know which they were compiled for)
 	uint8_t *u8() const { return static_cast<uint8_t *>(base); }
 	uint16_t *u16() const { return static_cast<uint16_t *>(base); }
-	bool one_band() const { return cols == 0; }
+	bool listed() const { return offs != nullptr; }
+	bool one_band() const { return cols == 0 && !listed(); }
 	bool planar() const { return channel_stride != 0; }
 	bool stepped() const { return pixel_step != 0; }
 	bool bgr() const { return order == DWTX_ORDER_BGR && channels == 3; }
@@ -241,7 +253,7 @@ struct dwtx_pixels {
 	// 8-bit RGB in 4-byte pixels (RGBA / RGBX surfaces): the one stepped layout lift.hip's wide kernels take
 	bool rgbx8() const { return pixel_step == 4 && channels == 3 && sample_bytes == 1 && !planar(); }
 	size_t pitch(int W) const { return row_pitch ? row_pitch : (size_t)W * (planar() ? 1 : channels); }
-	// the same pictures from image i on: a one-band view moves its base (first stays 0), a grid keeps its origin and moves the index
+	// the same pictures from image i on: a one-band view moves its base (first stays 0), a grid or a list keeps its origin and moves the index
 	dwtx_pixels image(size_t i) const
 	{
 		dwtx_pixels p = *this;
@@ -265,6 +277,8 @@ struct dwtx_pixels {
 	// interleaved RGB lanes take three) — is one aligned access in every row of every image
 	bool wide() const
 	{
+		if (listed())   // (no grid: the strides between windows say nothing; every window's own pointer is on the quad instead)
+			return row_pitch % 4 == 0 && channel_stride % 4 == 0 && aligned(4 * (size_t)sample_bytes) && offs_on_quad;
 		return image_stride % 4 == 0 && row_pitch % 4 == 0 && band_stride % 4 == 0 && channel_stride % 4 == 0 && aligned(4 * (size_t)sample_bytes);
 	}
 };

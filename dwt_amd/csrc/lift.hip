@@ -35,20 +35,30 @@ constexpr int MAX_ROWS_PER_WAVE = 64; // output row pairs per wave strip (fewer 
 
 // Where the pictures of a launch that reads / writes pixels lie when they are windows of a larger frame (dwtx_pixels):
 // picture i is window first + i of a grid of bands of `cols` windows, the windows of a band `ps` samples apart (the
-// launch's src_ps / ll_ps / dst_ps), the bands band_ps.  cols == 0: one band, picture i at i * ps as ever.
+// launch's src_ps / ll_ps / dst_ps), the bands band_ps.  cols == 0: one band, picture i at i * ps as ever.  Or, offs set,
+// picture i is window first + i of a list (dwtx_pixels::offs): offs[first + i] samples from the origin, whatever ps says.
 struct WinGrid {
 	unsigned cols, first;
 	long band_ps;
+	const long long *offs;   // device memory that no launch writes: [first + pictures of the launch]
 };
 
 // The one place the kernels take a window's first sample from: its offset from the grid's origin, in samples.  The
 // picture's index is the same for a whole wave, so the division is scalar arithmetic (readfirstlane says so where the
 // index was computed from a vector register), and a one-band launch pays a compare for it.
+// A list's offset is one 8-byte load at a wave-uniform index of a table that no kernel writes while a launch reads it: read
+// through a pointer to the constant address space (memory that does not change during a kernel), with the index from
+// readfirstlane, it is a scalar load at every site, beside kernels that store through pointers of their own too (DESIGN.md
+// section 4.18: with a plain const __restrict__ pointer 28 of the sites kept a vector load per lane).
 __device__ __forceinline__ long win_off(const WinGrid &g, long ps, int image)
 {
-	if (g.cols == 0)
+	if (g.cols == 0 && !g.offs)   // (the one-band launch first: it pays two scalar compares and nothing else)
 		return image * ps;
 	const unsigned i = (unsigned)__builtin_amdgcn_readfirstlane(image) + g.first;   // (both below 65536: a call's windows, dwtx_count_ok)
+	if (g.offs) {
+		typedef const long long __attribute__((address_space(4))) *ConstTable;
+		return (long)((ConstTable)g.offs)[i];
+	}
 	const unsigned band = i / g.cols;
 	return (long)band * g.band_ps + (long)(i - band * g.cols) * ps;
 }
@@ -3079,7 +3089,7 @@ struct LiftLayout {
 
 // (cols and first in 32 bits: both are window counts of one call, at most DWTX_MAX_PLANES_PER_CALL — dwtx_count_ok — so that
 // win_off's unsigned `i + first` cannot wrap)
-WinGrid win_grid(const dwtx_pixels &px) { return WinGrid{ (unsigned)px.cols, (unsigned)px.first, (long)px.band_stride }; }
+WinGrid win_grid(const dwtx_pixels &px) { return WinGrid{ (unsigned)px.cols, (unsigned)px.first, (long)px.band_stride, px.offs }; }
 
 // ctx null: the sizes only
 int lift_layout(dwtx_ctx *ctx, int W, int H, int nplanes, LiftLayout &L)

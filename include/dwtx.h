@@ -537,6 +537,47 @@ int dwtx_decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stre
 typedef struct dwtx_crop_rect { int x0, y0, w, h; } dwtx_crop_rect;
 int dwtx_crop_plan(int W, int H, int x0, int y0, int cw, int ch, dwtx_crop_rect out[DWTX_MAX_LEVELS + 1]);
 
+/* ---- window lists: encode from and decode into one pointer per picture ---------------------------------------------------
+ * The most general view call of each direction — dwtx_encode_view_order or dwtx_encode_view_float (fmt given), and
+ * dwtx_decode_view_crop — for windows that lie on no grid: separately allocated pictures (a list of tensors, a decoder's
+ * surface pool, the images of a swap chain), patches at arbitrary places of a frame (detection boxes of one size), a subset
+ * or a permutation of a tile grid (only the dirty tiles, tiles in priority order).
+ * host_windows: [n] device pointers in HOST memory, read before the call returns — the caller may free or overwrite the
+ * array at once, after the asynchronous encode too.  Entry i is window i's lowest-addressed channel's first sample: what
+ * `dev` is for window 0 of a grid.  view->dev, cols, image_stride and band_stride are ignored (dev may be NULL); row_pitch,
+ * channel_stride, sample_bytes, channels, maxval, pixel_step, order and fmt keep their meaning word for word.  A list that
+ * spells out a grid gives exactly what the grid call gives: streams, dev_info and host_info, every written sample, and
+ * nothing else written.  host_windows == NULL is DWTX_ERR_ARG, not silently the grid call.
+ * Encode: windows may overlap and a pointer may occur twice; stream i is that of window i's dense interleaved R, G, B copy.
+ * Asynchronous on the context's stream; the call does not wait for earlier work on that stream (the table travels through
+ * a page-locked buffer of the context; a second listed call waits for the first one's table to have left that buffer).
+ * Decode: with crop_w == W, crop_h == H and host_origins == NULL (or all (0, 0)) the plain decode; otherwise the rules of
+ * dwtx_decode_view_crop with the listed windows of the crop's size.  The windows must be provably disjoint, else
+ * DWTX_ERR_ARG and nothing is written.  The units are the n windows, for planar RGB the 3n planes at p_i + c *
+ * channel_stride, with the crop's sides where there is a crop.  With row = W for a plane, else (W-1)*step + channels (step:
+ * pixel_step, or channels), pitch = row_pitch and span = (H-1)*pitch + row, every two units, their first samples d samples
+ * apart, must meet one of
+ *   d >= span                                                  (one unit ends before the other begins), or
+ *   with dx = d % pitch: dx >= row and dx + row <= pitch       (different columns of one pitch lattice: tiles or boxes
+ *                                                               side by side in one frame).
+ * Sufficient, not necessary, like the rules of dwtx_decode_view.
+ * DWTX_ERR_ARG (with a dwtx_last_error() text, nothing written): a NULL entry; an entry not aligned to sample_bytes; more
+ * windows than a call takes (65535 planes to encode, 21845 streams to decode); and everything the plain call of the same
+ * direction refuses.
+ * Gray, interleaved or planar windows are read / written by the transform's finest level itself when the grid call's
+ * conditions hold for row_pitch and channel_stride and EVERY pointer is on the lane's quad, 4 * sample_bytes bytes; one
+ * pointer off the quad sends the whole call through the general conversions: the same bytes. */
+int dwtx_encode_view_list(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order,
+	const dwtx_float_format *fmt /* NULL: integer samples */, const void *const *host_windows,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
+int dwtx_decode_view_list(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, dwtx_decode_info *host_info);
+/* Host arithmetic only, like dwtx_crop_plan: what the two calls above accept of a list — DWTX_OK, or the DWTX_ERR_ARG (and
+ * text) they would return for the view, the step and the list.  W x H: the windows' sides (the crop's where there is one,
+ * from 1 up); dst != 0: the list is a decode's and must be disjoint.  A view of 4-byte samples is taken for fp32 samples. */
+int dwtx_view_list_check(const dwtx_view *v, size_t pixel_step, int W, int H, int n, const void *const *host_windows, int dst);
+
 /* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
  * interior, right column, bottom row, corner, in that order, those that exist — each a cols x rows grid of W x H tiles
  * whose first tile's corner is (x0, y0): one dwtx_encode_view / dwtx_decode_view call per group.  Per axis, with
