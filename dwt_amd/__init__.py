@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import Geom, Stats, StreamInfo, DecodeInfo, Index, SegIndex, View, TileGroup, FloatFormat, CropRect, INDEX_MAGIC, INDEX_MAX_SEGS, LIB_PATH  # noqa: F401
 
 __all__ = ["Context", "DwtxError", "compute_lengths", "geometry", "index_from_row", "tile_groups", "view_fields", "view_order", "float_format", "crop_plan",
-           "view_list_fields", "view_list_check",
+           "view_list_fields", "view_list_check", "view_flips", "view_flip_plan",
            "Geom", "Stats", "View", "TileGroup", "FloatFormat", "CropRect"]
 
 
@@ -172,6 +172,70 @@ def view_list_check(pointers, W, H, channels=1, row_pitch=None, channel_stride=0
     arr = (C.c_void_p * max(len(ptrs), 1))(*[p or None for p in ptrs])
     rc = lib.dwtx_view_list_check(C.byref(v), pixel_step, W, H, len(ptrs), arr, 1 if dst else 0)
     return rc, (lib.dwtx_last_error().decode(errors="replace") if rc else "")
+
+
+FLIPS = {"": 0, "x": 1, "y": 2, "xy": 3, "yx": 3}   # enum DWTX_FLIP_X = 1, DWTX_FLIP_Y = 2 (include/dwtx.h): a mask
+
+
+def _flip_flag(f):
+    if isinstance(f, str) and f in FLIPS:
+        return FLIPS[f]
+    if f is None:
+        return 0
+    if isinstance(f, bool) or not hasattr(f, "__index__") or not 0 <= int(f) <= 3:
+        raise ValueError(f"flip {f!r}: None, 0, 'x', 'y', 'xy' or a mask 1..3 (x = 1, y = 2)")
+    return int(f)
+
+
+def view_flips(flip, n):
+    """The `flip` keyword of the view calls -> None when no window is flipped (None, 0, or a sequence of zeros: the call
+    made is the one made without the keyword), else (flip, flips) for the *_view_flip calls: one mask for all windows and
+    None, or 0 and a ctypes array of n masks.  Takes None, 0, "x", "y", "xy", 1..3 (x = 1, y = 2), or a sequence of n of
+    those (a tensor or an array of integers too).  Anything else is a ValueError — raised here, before any device call."""
+    if flip is None or isinstance(flip, (str, int)) or (hasattr(flip, "__index__") and not hasattr(flip, "__len__")):
+        f = _flip_flag(flip)
+        return (f, None) if f else None
+    if hasattr(flip, "tolist"):
+        flip = flip.tolist()
+    try:
+        flags = [_flip_flag(f) for f in flip]
+    except TypeError:
+        raise ValueError(f"flip {flip!r}: one value or a sequence of {n}") from None
+    if len(flags) != n:
+        raise ValueError(f"flip: one value or {n}, one per window, not {len(flags)}")
+    if not any(flags):
+        return None
+    return 0, (C.c_ubyte * n)(*flags)
+
+
+def view_flip_plan(W, H, n, flip, pointers=None, channels=1, row_pitch=None, image_stride=None, cols=0, band_stride=0, channel_stride=0,
+                   pixel_step=0, sample_bytes=1, maxval=None, dst=True, flips=None):
+    """dwtx_view_flip_plan: what a flipped encode (dst=False) or decode (dst=True) says to n windows of W x H — at `pointers`
+    (plain integers, never dereferenced), or, pointers None, on the grid that cols, image_stride and band_stride describe —
+    and the table it walks them with -> (rc, text, origin, pitch, step): rc 0 and "" for a call it takes, else the error
+    code and the text of the refusal (and three empty lists).  origin[i]: where pixel (0, 0) of window i's picture lies, in
+    samples from the grid's first sample or from the lowest pointer; pitch[i], step[i]: the signed row pitch and pixel step
+    the picture is walked with from there.  flip: one mask 0..3 for all windows; flips: a sequence of n masks instead — both
+    go to the library as they are, a refusal is the library's.  Strides count samples; row_pitch None: dense rows,
+    image_stride None: dense windows.  Host arithmetic only: needs no device."""
+    lib = _lib.load()
+    if row_pitch is None:
+        row_pitch = W if channels == 3 and channel_stride else ((W - 1) * pixel_step + channels if pixel_step else W * channels)
+    if image_stride is None:
+        image_stride = row_pitch * H
+    if maxval is None:
+        maxval = 255 if sample_bytes == 1 else 65535
+    arr = None
+    if pointers is not None:
+        ptrs = list(pointers)
+        arr = (C.c_void_p * max(len(ptrs), 1))(*[p or None for p in ptrs])
+    v = View(None if arr is not None else 4096, sample_bytes, channels, maxval, cols, row_pitch, image_stride, band_stride, channel_stride)
+    fl = None if flips is None else (C.c_ubyte * max(len(flips), 1))(*[int(f) for f in flips])
+    out = [(C.c_longlong * max(n, 1))() for _ in range(3)]
+    rc = lib.dwtx_view_flip_plan(C.byref(v), pixel_step, W, H, n, arr, int(flip), fl, 1 if dst else 0, *out)
+    if rc:
+        return rc, lib.dwtx_last_error().decode(errors="replace"), [], [], []
+    return (0, "") + tuple(list(a[:n]) for a in out)
 
 
 def _ptr(t):
@@ -600,23 +664,29 @@ class Context:
                  f["channel_stride"])
         return v, f["W"], f["H"], f["channels"], f["n"], f["pixel_step"]
 
-    def encode_view(self, t, capacity=0, out=None, info=None, stepped=False, order="rgb"):
+    def encode_view(self, t, capacity=0, out=None, info=None, stepped=False, order="rgb", flip=None):
         """dwtx_encode_view: the windows of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (a slice, a crop, a
         grid of tiles, a channel-first batch permuted to channel-last: see _view) -> (streams uint8 [n,stride], info uint8
         [n,sizeof(StreamInfo)]) on device, as encode_device / encode_device16 give for the contiguous copy; async.
         stepped=True: dwtx_encode_view_step — `rgba[..., :3]`, `rgba[..., 3:]` and `uv[:, :, 0::2]` are views as they lie.
         order="bgr": dwtx_encode_view_order — the channels lie as B, G, R (`bgra[..., :3]` with stepped=True, an OpenCV
-        frame, planar B, G, R planes); the streams are those of the R, G, B picture."""
+        frame, planar B, G, R planes); the streams are those of the R, G, B picture.
+        flip: dwtx_encode_view_flip — "y" for bottom-up surfaces, "x" for mirrored ones, "xy", or one of those per window
+        (view_flips); the streams are those of `t.flip(...)` of each window, which is never built."""
         order = view_order(order)
         torch = self.torch
         v, W, H, Cn, n, step = self._view(t, None, stepped)
+        flips = view_flips(flip, n)
         bound = self.lib.dwtx_encode_bound16 if v.sample_bytes == 2 else self.lib.dwtx_encode_bound
         stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
         if out is None:
             out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         if info is None:
             info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
-        if order:
+        if flips:
+            _check(self.lib.dwtx_encode_view_flip(self.h, C.byref(v), step, order, None, None, flips[0], flips[1], W, H, n, capacity, _ptr(out),
+                                                  out.shape[1], _ptr(info)), "dwtx_encode_view_flip")
+        elif order:
             _check(self.lib.dwtx_encode_view_order(self.h, C.byref(v), step, order, W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
                    "dwtx_encode_view_order")
         elif stepped:
@@ -626,43 +696,55 @@ class Context:
             _check(self.lib.dwtx_encode_view(self.h, C.byref(v), W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view")
         return out, info
 
-    def encode_view_float(self, t, maxval=255, scale=1.0, bias=0.0, capacity=0, out=None, info=None, stepped=False, order="rgb"):
+    def encode_view_float(self, t, maxval=255, scale=1.0, bias=0.0, capacity=0, out=None, info=None, stepped=False, order="rgb", flip=None):
         """dwtx_encode_view_float: encode_view of a float32 / float16 / bfloat16 strided device tensor (the shapes and
         strides encode_view takes, stepped and order="bgr" included).  The picture that is coded is, per sample,
         `(x.float() * scale + bias).round().clamp(0, maxval)` — two float32 roundings, ties to even, NaN -> 0 — and the
         streams are those of encode_device (maxval <= 255) or encode_device16 (above) on that picture; async.  scale,
         bias: a number, or three, per colour R, G, B.  Returns (streams, info) like encode_view.  A tensor that holds no
-        floats, a wrong length of scale or bias and values that are not finite raise ValueError before any device call."""
+        floats, a wrong length of scale or bias and values that are not finite raise ValueError before any device call.
+        flip: encode_view's keyword."""
         order = view_order(order)
         torch = self.torch
         if not hasattr(t, "dtype") or t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
             raise ValueError(f"encode_view_float reads float32, float16 or bfloat16 tensors, not {getattr(t, 'dtype', type(t))}")
         fmt = float_format(t.dtype, scale, bias)
         v, W, H, Cn, n, step = self._view(t, int(maxval), stepped, floats=True)
+        flips = view_flips(flip, n)
         bound = self.lib.dwtx_encode_bound16 if int(maxval) > 255 else self.lib.dwtx_encode_bound
         stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
         if out is None:
             out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         if info is None:
             info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
+        if flips:
+            _check(self.lib.dwtx_encode_view_flip(self.h, C.byref(v), step, order, C.byref(fmt), None, flips[0], flips[1], W, H, n, capacity,
+                                                  _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view_flip")
+            return out, info
         _check(self.lib.dwtx_encode_view_float(self.h, C.byref(v), step, order, C.byref(fmt), W, H, n, capacity, _ptr(out), out.shape[1],
                                                _ptr(info)), "dwtx_encode_view_float")
         return out, info
 
-    def decode_view(self, streams, lens, into, maxval=None, levels_max=-1, stepped=False, order="rgb"):
+    def decode_view(self, streams, lens, into, maxval=None, levels_max=-1, stepped=False, order="rgb", flip=None):
         """dwtx_decode_view: device streams [n,stride] + int64 lens -> the windows of the strided device tensor `into`
         ([n,H,W,C] or [bands,cols,H,W,C]), each picture in its window's top-left corner at the size its stream supports;
         nothing else of `into`'s storage is written.  maxval: the deep pictures' (default 65535).  Returns the list of
         DecodeInfo; syncs once.  stepped=True: dwtx_decode_view_step, for the tensors encode_view takes with it; the
         samples between the pixels (an RGBA surface's alpha) are not written either.  order="bgr": dwtx_decode_view_order —
-        R and B are written at each other's places."""
+        R and B are written at each other's places.  flip: dwtx_decode_view_flip — "x", "y", "xy" or one of those per window
+        (view_flips): each window holds what `.flip(...)` of the unflipped result would, and a reduced picture lies in the
+        corner where its pixel (0, 0) lies."""
         order = view_order(order)
         torch = self.torch
         v, W, H, Cn, n, step = self._view(into, maxval, stepped)
+        flips = view_flips(flip, n)
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
         assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
         infos = (DecodeInfo * n)()
-        if order:
+        if flips:
+            _check(self.lib.dwtx_decode_view_flip(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
+                                                  None, W, H, None, None, flips[0], flips[1], C.cast(infos, C.c_void_p)), "dwtx_decode_view_flip")
+        elif order:
             _check(self.lib.dwtx_decode_view_order(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step,
                                                    order, C.cast(infos, C.c_void_p)), "dwtx_decode_view_order")
         elif stepped:
@@ -673,34 +755,42 @@ class Context:
                                              C.cast(infos, C.c_void_p)), "dwtx_decode_view")
         return list(infos)
 
-    def decode_view_float(self, streams, lens, into, maxval=255, scale=1.0, bias=0.0, levels_max=-1, stepped=False, order="rgb"):
+    def decode_view_float(self, streams, lens, into, maxval=255, scale=1.0, bias=0.0, levels_max=-1, stepped=False, order="rgb", flip=None):
         """dwtx_decode_view_float: decode_view into a float32 / float16 / bfloat16 strided device tensor `into` (the shapes
         and strides decode_view takes, stepped and order="bgr" included): every sample decode_view would write becomes
         `v * scale + bias` — two float32 roundings, then the tensor's dtype, bit for bit torch's unfused
         `x.float() * scale + bias` (and `.to(dtype)`) of the integer decode — and nothing else of `into`'s storage is
         written.  maxval: what the streams were encoded from (255, or a deep picture's).  scale, bias: a number, or three,
         per colour R, G, B.  Returns the list of DecodeInfo; syncs once.  A wrong dtype, a wrong length of scale or bias
-        and values that are not finite raise ValueError before any device call."""
+        and values that are not finite raise ValueError before any device call.  flip: decode_view's keyword (a loader's
+        per-picture horizontal flip: a sequence of 0 and "x")."""
         order = view_order(order)
         torch = self.torch
         if not hasattr(into, "dtype") or into.dtype not in (torch.float32, torch.float16, torch.bfloat16):
             raise ValueError(f"decode_view_float writes float32, float16 or bfloat16 tensors, not {getattr(into, 'dtype', type(into))}")
         fmt = float_format(into.dtype, scale, bias)
         v, W, H, Cn, n, step = self._view(into, int(maxval), stepped, floats=True)
+        flips = view_flips(flip, n)
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
         assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
         infos = (DecodeInfo * n)()
+        if flips:
+            _check(self.lib.dwtx_decode_view_flip(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
+                                                  C.byref(fmt), W, H, None, None, flips[0], flips[1], C.cast(infos, C.c_void_p)),
+                   "dwtx_decode_view_flip")
+            return list(infos)
         _check(self.lib.dwtx_decode_view_float(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step,
                                                order, C.byref(fmt), C.cast(infos, C.c_void_p)), "dwtx_decode_view_float")
         return list(infos)
 
     def decode_view_crop(self, streams, lens, into, size, origins=None, maxval=None, scale=None, bias=None, levels_max=-1, stepped=False,
-                         order="rgb"):
+                         order="rgb", flip=None):
         """dwtx_decode_view_crop: decode_view — or decode_view_float, when `into` is a float tensor — of a window of each
         picture: `into` holds windows of the crop's size ([n,ch,cw,C] or [bands,cols,ch,cw,C], any strides decode_view takes),
         size=(W, H) is the streams' geometry, origins a sequence of n (x0, y0) pairs, one pair for all, or None for (0, 0).
         Window i receives the picture's samples from (x0_i, y0_i) on, as far as the stream supports them, and nothing else of
-        `into`'s storage is written.  scale, bias: float tensors only.  Returns the list of DecodeInfo; syncs once."""
+        `into`'s storage is written.  scale, bias: float tensors only.  flip: decode_view's keyword — the crop is flipped inside its window.
+        Returns the list of DecodeInfo; syncs once."""
         order = view_order(order)
         torch = self.torch
         W, H = (int(v) for v in size)
@@ -711,6 +801,7 @@ class Context:
         if floats and maxval is None:
             maxval = 255
         v, cw, ch, Cn, n, step = self._view(into, None if maxval is None else int(maxval), stepped, floats=floats)
+        flips = view_flips(flip, n)
         org = None
         if origins is not None:
             flat = [int(c) for c in origins] if len(origins) == 2 and not hasattr(origins[0], "__len__") else None
@@ -721,6 +812,11 @@ class Context:
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
         assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
         infos = (DecodeInfo * n)()
+        if flips:
+            _check(self.lib.dwtx_decode_view_flip(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
+                                                  C.byref(fmt) if fmt is not None else None, cw, ch, org, None, flips[0], flips[1],
+                                                  C.cast(infos, C.c_void_p)), "dwtx_decode_view_flip")
+            return list(infos)
         _check(self.lib.dwtx_decode_view_crop(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
                                               C.byref(fmt) if fmt is not None else None, cw, ch, org, C.cast(infos, C.c_void_p)),
                "dwtx_decode_view_crop")
@@ -742,13 +838,14 @@ class Context:
         v = View(None, t0.element_size(), f["channels"], int(maxval), 0, f["row_pitch"], 0, 0, f["channel_stride"])
         return v, (C.c_void_p * len(ptrs))(*ptrs), f, floats
 
-    def encode_view_list(self, windows, maxval=None, scale=None, bias=None, capacity=0, out=None, info=None, stepped=False, order="rgb"):
+    def encode_view_list(self, windows, maxval=None, scale=None, bias=None, capacity=0, out=None, info=None, stepped=False, order="rgb",
+                         flip=None):
         """dwtx_encode_view_list: encode_view — or encode_view_float, when the windows are float tensors — of a sequence of n
         device tensors [H,W,C] that lie wherever they lie: separately allocated pictures, boxes of a frame, tiles in any
         order, permuted [C,H,W] tensors; one shape, one set of strides, one dtype (view_list_fields).  Windows may overlap
         and repeat.  No stack is built: the library reads each window in place.  maxval (float windows: the quantiser's
-        clamp, default 255), scale, bias: as for encode_view_float; stepped, order: as for encode_view.  Returns (streams,
-        info) like encode_view; async."""
+        clamp, default 255), scale, bias: as for encode_view_float; stepped, order, flip: as for encode_view.  Returns
+        (streams, info) like encode_view; async."""
         order = view_order(order)
         torch = self.torch
         v, arr, f, floats = self._view_list(windows, maxval, stepped)
@@ -756,6 +853,7 @@ class Context:
             raise ValueError("scale and bias belong to float tensors")
         fmt = float_format(windows[0].dtype, 1.0 if scale is None else scale, 0.0 if bias is None else bias) if floats else None
         W, H, Cn, n = f["W"], f["H"], f["channels"], f["n"]
+        flips = view_flips(flip, n)
         deep = v.maxval > 255 if floats else v.sample_bytes == 2
         bound = self.lib.dwtx_encode_bound16 if deep else self.lib.dwtx_encode_bound
         stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
@@ -763,17 +861,22 @@ class Context:
             out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         if info is None:
             info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
+        if flips:
+            _check(self.lib.dwtx_encode_view_flip(self.h, C.byref(v), f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, arr,
+                                                  flips[0], flips[1], W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
+                   "dwtx_encode_view_flip")
+            return out, info
         _check(self.lib.dwtx_encode_view_list(self.h, C.byref(v), f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, arr,
                                               W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view_list")
         return out, info
 
     def decode_view_list(self, streams, lens, windows, size=None, origins=None, maxval=None, scale=None, bias=None, levels_max=-1,
-                         stepped=False, order="rgb"):
+                         stepped=False, order="rgb", flip=None):
         """dwtx_decode_view_list: decode_view_crop into a sequence of n device tensors [H,W,C] that lie wherever they lie (the
         lists encode_view_list takes), which must be provably disjoint (include/dwtx.h).  size=None: whole pictures of the
         windows' size; else size=(W, H) is the streams' geometry, the windows are crops of it and origins their (x0, y0), as for
         decode_view_crop.  Float windows are written as decode_view_float writes them (maxval, scale, bias).  Nothing but
-        the windows' samples is written.  Returns the list of DecodeInfo; syncs once."""
+        the windows' samples is written.  flip: decode_view's keyword.  Returns the list of DecodeInfo; syncs once."""
         order = view_order(order)
         torch = self.torch
         v, arr, f, floats = self._view_list(windows, maxval, stepped)
@@ -781,6 +884,7 @@ class Context:
             raise ValueError("scale and bias belong to float tensors")
         fmt = float_format(windows[0].dtype, 1.0 if scale is None else scale, 0.0 if bias is None else bias) if floats else None
         cw, ch, n = f["W"], f["H"], f["n"]
+        flips = view_flips(flip, n)
         W, H = (cw, ch) if size is None else (int(s) for s in size)
         org = None
         if origins is not None:
@@ -792,6 +896,11 @@ class Context:
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
         assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
         infos = (DecodeInfo * n)()
+        if flips:
+            _check(self.lib.dwtx_decode_view_flip(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
+                                                  f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, cw, ch, org, arr,
+                                                  flips[0], flips[1], C.cast(infos, C.c_void_p)), "dwtx_decode_view_flip")
+            return list(infos)
         _check(self.lib.dwtx_decode_view_list(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
                                               f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, cw, ch, org, arr,
                                               C.cast(infos, C.c_void_p)), "dwtx_decode_view_list")

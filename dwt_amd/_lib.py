@@ -159,6 +159,13 @@ SYMBOLS = {
     "dwtx_decode_view_list": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), _i, _i, C.POINTER(_i),
                                    C.POINTER(_vp), _vp]),
     "dwtx_view_list_check": (_i, [C.POINTER(View), _sz, _i, _i, _i, C.POINTER(_vp), _i]),
+    # flips: the list calls (or, without a list, the grid calls) plus a mask of DWTX_FLIP_X / DWTX_FLIP_Y per window
+    "dwtx_encode_view_flip": (_i, [_vp, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), C.POINTER(_vp), _i, C.POINTER(C.c_ubyte), _i, _i, _i,
+                                   C.c_long, _vp, _sz, _vp]),
+    "dwtx_decode_view_flip": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), _i, _i, C.POINTER(_i),
+                                   C.POINTER(_vp), _i, C.POINTER(C.c_ubyte), _vp]),
+    "dwtx_view_flip_plan": (_i, [C.POINTER(View), _sz, _i, _i, _i, C.POINTER(_vp), _i, C.POINTER(C.c_ubyte), _i, C.POINTER(C.c_longlong),
+                                 C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "dwtx_tile_groups": (_i, [_i, _i, _i, C.POINTER(TileGroup)]),
     "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }

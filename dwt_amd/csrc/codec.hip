@@ -904,6 +904,186 @@ extern "C" int dwtx_decode_view_list(dwtx_ctx *ctx, const uint8_t *dev_streams, 
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info, &crop);
 }
 
+// ---- flips in views (include/dwtx.h): a mask of DWTX_FLIP_X and DWTX_FLIP_Y per window ---------------------------------------
+
+// window i's flags of a *_view_flip call, checked: host_flips[i], or `flip` for all; *any: one of them is not 0
+static int flip_flags(int n, int flip, const unsigned char *host_flips, std::vector<unsigned char> *flags, bool *any)
+{
+	*any = false;
+	if (host_flips && flip) {
+		dwtx_set_error("flip: flags for all windows (%d) together with a flag per window (host_flips): one of the two", flip);
+		return DWTX_ERR_ARG;
+	}
+	if (flip < 0 || flip > (DWTX_FLIP_X | DWTX_FLIP_Y)) {
+		dwtx_set_error("flip: flags %d (a mask of DWTX_FLIP_X = 1 and DWTX_FLIP_Y = 2: 0..3)", flip);
+		return DWTX_ERR_ARG;
+	}
+	if (n < 1) {
+		dwtx_set_error("no view, no pixels or no windows");
+		return DWTX_ERR_ARG;
+	}
+	try {
+		flags->assign((size_t)n, (unsigned char)flip);
+	} catch (...) {
+		return DWTX_ERR_NOMEM;
+	}
+	for (int i = 0; i < n; ++i) {
+		if (host_flips)
+			(*flags)[(size_t)i] = host_flips[i];
+		if ((*flags)[(size_t)i] > (DWTX_FLIP_X | DWTX_FLIP_Y)) {
+			dwtx_set_error("flip: flags %d of window %d (a mask of DWTX_FLIP_X = 1 and DWTX_FLIP_Y = 2: 0..3)", (int)(*flags)[(size_t)i], i);
+			return DWTX_ERR_ARG;
+		}
+		*any = *any || (*flags)[(size_t)i];
+	}
+	return DWTX_OK;
+}
+
+// pixels_of_view for a call with flips: the listed view as it is, or (windows null) the view's own grid, checked as a grid
+// and then spelled out — list->offs from v->dev, px a listed view — so that every flipped call travels as a listed one.
+// px->offs is not set yet and list->offs carries no flags yet (flip_entries)
+static int flipped_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, int kind, bool window,
+	const void *const *windows, WinList *list, dwtx_pixels *px)
+{
+	list->windows = windows;
+	if (windows) {
+		if (const int rc = pixels_of_view(v, pixel_step, order, W, H, n, dst, px, kind, window, list))
+			return rc;
+	} else {
+		if (const int rc = pixels_of_view(v, pixel_step, order, W, H, n, dst, px, kind, window))
+			return rc;
+		if (dst ? !dwtx_count_ok(n, DWTX_MAX_PLANES_PER_CALL / 3, "streams to decode") : !dwtx_count_ok((long)n * v->channels, DWTX_MAX_PLANES_PER_CALL, "planes"))
+			return DWTX_ERR_ARG;
+		try {
+			list->offs.resize((size_t)n);
+		} catch (...) {
+			return DWTX_ERR_NOMEM;
+		}
+		const size_t cols = px->cols ? (size_t)px->cols : (size_t)n;
+		for (size_t i = 0; i < (size_t)n; ++i)
+			list->offs[i] = (long long)(i / cols * px->band_stride + i % cols * px->image_stride);
+		px->cols = 0;
+		px->band_stride = px->image_stride = 0;
+		px->offs_on_quad = true;   // (what wide() asks of a list: every window's own first sample on the quad)
+		for (size_t i = 0; i < (size_t)n; ++i)
+			px->offs_on_quad = px->offs_on_quad && list->offs[i] % 4 == 0;
+	}
+	px->flips = true;
+	px->flip_w = W;
+	px->flip_h = H;
+	return DWTX_OK;
+}
+
+// the flags into the top bits of the windows' table entries (dwtx_pixels::flips; offsets are sample counts of one allocation, far below)
+static void flip_entries(WinList *list, const std::vector<unsigned char> &flags)
+{
+	for (size_t i = 0; i < list->offs.size(); ++i)
+		list->offs[i] = (long long)((unsigned long long)list->offs[i] | (unsigned long long)flags[i] << DWTX_FLIP_SHIFT);
+}
+
+extern "C" int dwtx_view_flip_plan(const dwtx_view *v, size_t pixel_step, int W, int H, int n, const void *const *host_windows,
+	int flip, const unsigned char *host_flips, int dst, long long *origin, long long *pitch, long long *step)
+{
+	std::vector<unsigned char> flags;
+	bool any;
+	if (const int rc = flip_flags(n, flip, host_flips, &flags, &any))
+		return rc;
+	WinList list{ nullptr, {} };
+	dwtx_pixels px;
+	// (a view of 4-byte samples is one of fp32 samples, as for dwtx_view_list_check)
+	if (const int rc = flipped_view(v, pixel_step, DWTX_ORDER_RGB, W, H, n, dst != 0, v && v->sample_bytes == 4 ? DWTX_SAMPLE_F32 : -1, true, host_windows, &list, &px))
+		return rc;
+	const long long p = (long long)px.row_pitch, s = (long long)px.step();
+	for (int i = 0; i < n; ++i) {
+		const bool fx = flags[(size_t)i] & DWTX_FLIP_X, fy = flags[(size_t)i] & DWTX_FLIP_Y;
+		if (origin)
+			origin[i] = list.offs[(size_t)i] + (fy ? (long long)(H - 1) * p : 0) + (fx ? (long long)(W - 1) * s : 0);
+		if (pitch)
+			pitch[i] = fy ? -p : p;
+		if (step)
+			step[i] = fx ? -s : s;
+	}
+	return DWTX_OK;
+}
+
+extern "C" int dwtx_encode_view_flip(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	const void *const *host_windows, int flip, const unsigned char *host_flips,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	std::vector<unsigned char> flags;
+	bool any;
+	if (const int rc = flip_flags(n, flip, host_flips, &flags, &any))
+		return rc;
+	if (!any)   // the unflipped call, on its own path
+		return host_windows ? dwtx_encode_view_list(ctx, src, pixel_step, order, fmt, host_windows, W, H, n, capacity, dev_out, out_stride, dev_info)
+		     : fmt          ? dwtx_encode_view_float(ctx, src, pixel_step, order, fmt, W, H, n, capacity, dev_out, out_stride, dev_info)
+		                    : dwtx_encode_view_order(ctx, src, pixel_step, order, W, H, n, capacity, dev_out, out_stride, dev_info);
+	if (!ctx || !dev_out || !dev_info)
+		return DWTX_ERR_ARG;
+	int kind = -1;
+	if (fmt)
+		if (const int rc = float_kind(fmt, &kind))
+			return rc;
+	WinList list{ nullptr, {} };
+	dwtx_pixels px;
+	if (const int rc = flipped_view(src, pixel_step, order, W, H, n, false, kind, false, host_windows, &list, &px))
+		return rc;
+	if (fmt) {
+		if (!dwtx_maxval_ok(src->maxval))
+			return DWTX_ERR_ARG;
+		set_float_format(&px, fmt);
+	}
+	// bottom-up windows go through the wide forward kernels like upright ones; a mirrored one sends the call through the general conversion
+	px.flip_wide = true;
+	for (int i = 0; i < n; ++i)
+		px.flip_wide = px.flip_wide && !(flags[(size_t)i] & DWTX_FLIP_X);
+	flip_entries(&list, flags);
+	if (const int rc = send_list(ctx, list, &px))
+		return rc;
+	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx->enc_index);
+}
+
+extern "C" int dwtx_decode_view_flip(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, int flip, const unsigned char *host_flips,
+	dwtx_decode_info *host_info)
+{
+	std::vector<unsigned char> flags;
+	bool any;
+	if (const int rc = flip_flags(n, flip, host_flips, &flags, &any))
+		return rc;
+	if (!any)   // the unflipped call, on its own path
+		return host_windows ? dwtx_decode_view_list(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h,
+		                          host_origins, host_windows, host_info)
+		                    : dwtx_decode_view_crop(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h,
+		                          host_origins, host_info);
+	if (!ctx || !dev_streams || !dev_lens || !host_info)
+		return DWTX_ERR_ARG;
+	bool whole;
+	if (const int rc = crop_of_call(W, H, n, crop_w, crop_h, host_origins, &whole))
+		return rc;
+	int kind = -1;
+	if (fmt)
+		if (const int rc = float_kind(fmt, &kind))
+			return rc;
+	WinList list{ nullptr, {} };
+	dwtx_pixels px;
+	if (const int rc = flipped_view(dst, pixel_step, order, crop_w, crop_h, n, true, kind, !whole, host_windows, &list, &px))
+		return rc;
+	if (fmt)
+		set_float_format(&px, fmt);
+	px.flip_sink = true;
+	for (int i = 0; i < n; ++i)
+		px.flip_x = px.flip_x || (flags[(size_t)i] & DWTX_FLIP_X);
+	flip_entries(&list, flags);
+	if (const int rc = send_list(ctx, list, &px))
+		return rc;
+	if (whole)
+		return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
+	const CropCall crop = { crop_w, crop_h, host_origins };
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info, &crop);
+}
+
 // one axis of dwtx_tile_groups: `full` tiles of `tile`, then one of `last` (0: none)
 static void tile_axis(int side, int tile, int *full, int *last)
 {

@@ -221,6 +221,15 @@ struct dwtx_pixels {
 	float scale[3] = { 1.f, 1.f, 1.f }, bias[3] = { 0.f, 0.f, 0.f };   // float samples: per colour R, G, B (gray: [0])
 	const long long *offs = nullptr;   // listed windows: DEVICE table of their first samples' offsets from base (>= 0), read-only while kernels run; image() and moved() keep it
 	bool offs_on_quad = true;          // listed windows: every offset is a multiple of 4 (what wide() asks of each window beyond base)
+	// flipped windows (the *_view_flip calls, always listed): entry i of offs carries window i's DWTX_FLIP_* flags in its top two
+	// bits (DWTX_FLIP_SHIFT), which only lift.hip's general conversions and the FY instances of its wide forward kernels take
+	// apart — dwtx_pixels_ok says no to every other kernel, so that none meets such an entry — and flip_w x flip_h are the
+	// WINDOWS' sides: a picture that comes out reduced, or a part of a crop, is mirrored inside its window, not inside itself.
+	// flip_wide: the view is an encode's SOURCE and no window carries DWTX_FLIP_X: the wide forward kernels may read it
+	// flip_sink: the view is a decode's DESTINATION, which the FL instances of the wide inverse kernels write; flip_x: a window
+	// of it carries DWTX_FLIP_X (those need the windows' width on the quad: a mirrored quad is one aligned access)
+	bool flips = false, flip_wide = false, flip_sink = false, flip_x = false;
+	int flip_w = 0, flip_h = 0;
 
 	// uint16_t samples — and with them the kernel family that clamps at maxval and keeps no 16-bit ring planes
 	bool deep() const { return kind == DWTX_SAMPLE_U16; }
@@ -282,6 +291,7 @@ struct dwtx_pixels {
 		return image_stride % 4 == 0 && row_pitch % 4 == 0 && band_stride % 4 == 0 && channel_stride % 4 == 0 && aligned(4 * (size_t)sample_bytes);
 	}
 };
+constexpr int DWTX_FLIP_SHIFT = 62;   // a flipped window's flags in its 8-byte table entry; the offset is what lies below
 static inline dwtx_pixels dwtx_pixels8(const uint8_t *pix, int channels, size_t image_stride)
 {
 	return dwtx_pixels{ const_cast<uint8_t *>(pix), 1, channels, image_stride, 255 };
@@ -306,6 +316,8 @@ static inline dwtx_pixels dwtx_pixels_float(void *pix, int kind, int channels, s
 // picture's channel stride on the quad grid too), and windows the kernels can address (lift.hip).  Of the stepped views
 // (dwtx_pixels::pixel_step) only 8-bit RGB in 4-byte pixels qualifies: every other one takes the general conversions.
 // Of float views gray and planar RGB qualify, in both directions; interleaved float RGB takes the general way.
+// Flipped windows (dwtx_pixels::flips) qualify as their unflipped twins do: a destination (flip_sink) with any flags — a mirrored
+// window needs its width on the quad —, a source (flip_wide) unless one of its windows carries DWTX_FLIP_X.
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H);
 // lift.hip: asks for the scratch planes every lifting call of a W*H transform over nplanes planes asks for
 int dwtx_lift_scratch(dwtx_ctx *ctx, int W, int H, int nplanes);

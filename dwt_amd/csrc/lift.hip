@@ -63,6 +63,41 @@ __device__ __forceinline__ long win_off(const WinGrid &g, long ps, int image)
 	return (long)band * g.band_ps + (long)(i - band * g.cols) * ps;
 }
 
+// A flipped call's window (the *_view_flip calls; dwtx_pixels::flips): the same scalar load of the same table, whose entry
+// carries the window's DWTX_FLIP_* flags above DWTX_FLIP_SHIFT.  Only the FLIP instances of the general conversions call
+// it and the FY instances of the wide forward kernels call it, and only their launches see such a table (dwtx_pixels_ok).
+__device__ __forceinline__ long win_off_flip(const WinGrid &g, int image, unsigned &flags)
+{
+	typedef const unsigned long long __attribute__((address_space(4))) *ConstTable;
+	const unsigned i = (unsigned)__builtin_amdgcn_readfirstlane(image) + g.first;
+	const unsigned long long e = ((ConstTable)g.offs)[i];
+	flags = (unsigned)(e >> DWTX_FLIP_SHIFT);
+	return (long)(e & ((1ull << DWTX_FLIP_SHIFT) - 1));
+}
+
+// A destination window as a wave of an inverse kernel that writes pixels finds it.  FL 0: win_off, today's code.  FL 1 and 2, the
+// instances for a flipped call's windows: the entry's offset and flags; a bottom-up window
+// (DWTX_FLIP_Y) starts at its last row in memory — row fh - 1 of the WINDOW, so that a reduced picture lies in its bottom rows
+// — with the pitch negated.  FL 2 alone looks at DWTX_FLIP_X: a mirrored window's quad q goes to quad fwq - 1 - q with its four
+// pixels reversed (flip_quad, flip_q).  -> the offset of the picture's row 0 in samples; pitch and fx are the wave's.
+template <int FL>
+__device__ __forceinline__ long flip_dst(const WinGrid &g, long ps, int image, int fh, int &pitch, bool &fx)
+{
+	fx = false;
+	if constexpr (FL == 0) {
+		return win_off(g, ps, image);
+	} else {
+		unsigned flags;
+		long off = win_off_flip(g, image, flags);
+		if (flags & DWTX_FLIP_Y) {
+			off += (long)(fh - 1) * pitch;
+			pitch = -pitch;
+		}
+		fx = FL == 2 && (flags & DWTX_FLIP_X) != 0;
+		return off;
+	}
+}
+
 struct LevelArgs {
 	const int *src;  long src_ps;  int spitch;  // forward: input w*h      | inverse: LL (w2*h2)
 	int *ll;         long ll_ps;   int llpitch; // forward: LL out (w2*h2) | inverse: output w*h
@@ -316,6 +351,8 @@ struct LevelArgsW {
 	                  // where the planes lie as B, G, R (src8 / dst8 is then the R plane all the same); 0: interleaved.
 	                  // (After everything else, so that the interleaved kernels find their arguments where they were.)
 	FloatFmt fmt;     // inverse, float pixels behind dst8 (only the float sinks read it)
+	int ppw;          // the FY instances of the forward kernels: planes per window, 1 or 3 (which entry of the windows' table a plane reads)
+	int fh, fwq;      // the flipped instances of the inverse kernels (FL): the WINDOWS' height and quads per row (dwtx_pixels::flip_h, flip_w / 4)
 };
 
 // Per lane and subband: counts of "magnitude below 2^q" for q = 0..15 — nibbles of R for the last few coefficients
@@ -1453,7 +1490,11 @@ struct FwdSrc<FloatPix<F, true, true>> : FwdInt32, FwdFloatRows<F> {
 // — uniformly — into the three instances: Co is one subtraction per pixel pair, and neither it nor Cg needs what only Y needs;
 // with the channel as a run-time value every workgroup computed all three and selected: 1.84 -> 1.6 ms per 256 frames of
 // 1080p); below 0: whatever base() says, a run-time uniform.
-template <typename Src, bool HIST, int CH>
+// FY: the windows are a flipped call's whose flags are 0 or DWTX_FLIP_Y (dwtx_pixels::flip_wide): the wave takes its window's
+// offset and flag from the table entry (win_off_flip) and, bottom-up, starts at the window's last row in memory with the
+// pitch negated — picture row r is memory row h - 1 - r, every address it forms is one the upright walk forms, and the
+// columns, the halo words and the quad alignment are untouched.  Instances of their own: the others keep their code.
+template <typename Src, bool HIST, int CH, bool FY = false>
 __device__ __forceinline__ void fwd_level_body(const LevelArgsW &A, int bx, int by)
 {
 	typedef FwdSrc<Src> T;
@@ -1470,7 +1511,23 @@ __device__ __forceinline__ void fwd_level_body(const LevelArgsW &A, int bx, int 
 	const int plane = T::RGB_GRID ? (int)blockIdx.z * 3 + CH : (int)blockIdx.z;
 	const bool valid = q < A.nquads;
 	int ch_rt = 0;
-	const auto src = T::base(a, plane, ch_rt);
+	int spitch = a.spitch;   // (the wave's: negated for a bottom-up window)
+	const auto src = [&] {
+		if constexpr (FY) {
+			LevelArgs b = a;   // base() without a window: the pixels' first sample and the channel
+			b.grid = WinGrid{ 0u, 0u, 0, nullptr };
+			b.src_ps = 0;
+			unsigned flags;
+			auto p = T::base(b, plane, ch_rt) + win_off_flip(a.grid, A.ppw == 3 ? plane / 3 : plane, flags);
+			if (flags & DWTX_FLIP_Y) {
+				p += (long)(a.h - 1) * a.spitch;
+				spitch = -spitch;
+			}
+			return p;
+		} else {
+			return T::base(a, plane, ch_rt);
+		}
+	}();
 	const int ch = CH >= 0 ? CH : ch_rt;   // (uniform)
 	int *ll = a.ll + plane * a.ll_ps;
 	short *ll16 = a.ll16 ? a.ll16 + plane * a.ll_ps : nullptr;   // (uniform)
@@ -1488,8 +1545,8 @@ __device__ __forceinline__ void fwd_level_body(const LevelArgsW &A, int bx, int 
 		else
 			return T::used(r, ch);
 	};
-	T::lift(use(T::load(src + (long)(2 * jfirst) * a.spitch, at, A.cstride, ch)), ch, q, lane, A.nquads, l0, h0);
-	auto rowp = [&](int r) { return src + (long)min(r, a.h - 1) * a.spitch; };
+	T::lift(use(T::load(src + (long)(2 * jfirst) * spitch, at, A.cstride, ch)), ch, q, lane, A.nquads, l0, h0);
+	auto rowp = [&](int r) { return src + (long)min(r, a.h - 1) * spitch; };
 	typename T::Used cur[2 * S];
 	typename T::Loaded nxt[2 * S];
 #pragma unroll
@@ -1596,49 +1653,49 @@ __device__ __forceinline__ void fwd_level_body(const LevelArgsW &A, int bx, int 
 
 // The two entry points pick the strip mapping and the channel dispatch.  k_fwd_level_w: bands and deep pixels, a workgroup
 // column per plane.  k_fwd_pixels_w: 8-bit pixels.
-template <bool HIST, int SRC>
+template <bool HIST, int SRC, bool FY = false>
 __global__ __launch_bounds__(64 * WAVES) void k_fwd_level_w(LevelArgsW A)
 {
 	int bx, by;
 	xcd_strip(bx, by);
-	fwd_level_body<Band<SRC>, HIST, -1>(A, bx, by);
+	fwd_level_body<Band<SRC>, HIST, -1, FY>(A, bx, by);
 }
 
-template <typename SrcT, bool HIST>
+template <typename SrcT, bool HIST, bool FY = false>
 __global__ __launch_bounds__(64 * WAVES) void k_fwd_pixels_w(LevelArgsW A)
 {
 	int bx, by, chan = 0;
 	if (FwdSrc<SrcT>::RGB_GRID) {
 		xcd_strip_rgb(bx, by, chan);
 		if (chan == 0)
-			fwd_level_body<SrcT, HIST, 0>(A, bx, by);
+			fwd_level_body<SrcT, HIST, 0, FY>(A, bx, by);
 		else if (chan == 1)
-			fwd_level_body<SrcT, HIST, 1>(A, bx, by);
+			fwd_level_body<SrcT, HIST, 1, FY>(A, bx, by);
 		else
-			fwd_level_body<SrcT, HIST, 2>(A, bx, by);
+			fwd_level_body<SrcT, HIST, 2, FY>(A, bx, by);
 	} else {
 		xcd_strip(bx, by);
-		fwd_level_body<SrcT, HIST, 0>(A, bx, by);
+		fwd_level_body<SrcT, HIST, 0, FY>(A, bx, by);
 	}
 }
 
 // k_fwd_float_w: float pixels (FloatPix<>).  The 8-bit route's planar RGB as k_fwd_pixels_w runs RgbP8; gray and the deep
 // route a workgroup column per plane, the channel whatever base() says.
-template <typename SrcT, bool HIST>
+template <typename SrcT, bool HIST, bool FY = false>
 __global__ __launch_bounds__(64 * WAVES) void k_fwd_float_w(LevelArgsW A)
 {
 	int bx, by, chan = 0;
 	if (FwdSrc<SrcT>::RGB_GRID) {
 		xcd_strip_rgb(bx, by, chan);
 		if (chan == 0)
-			fwd_level_body<SrcT, HIST, 0>(A, bx, by);
+			fwd_level_body<SrcT, HIST, 0, FY>(A, bx, by);
 		else if (chan == 1)
-			fwd_level_body<SrcT, HIST, 1>(A, bx, by);
+			fwd_level_body<SrcT, HIST, 1, FY>(A, bx, by);
 		else
-			fwd_level_body<SrcT, HIST, 2>(A, bx, by);
+			fwd_level_body<SrcT, HIST, 2, FY>(A, bx, by);
 	} else {
 		xcd_strip(bx, by);
-		fwd_level_body<SrcT, HIST, -1>(A, bx, by);
+		fwd_level_body<SrcT, HIST, -1, FY>(A, bx, by);
 	}
 }
 
@@ -1796,6 +1853,25 @@ struct DetPtr<true> {
 struct Quad4 {
 	int v[4];
 };
+// the FL 2 instances: a mirrored window's quad, its four pixels the other way round, and where it goes (flip_dst)
+template <int FL>
+__device__ __forceinline__ Quad4 flip_quad(const Quad4 &q, bool fx)
+{
+	if constexpr (FL != 2) {
+		return q;
+	} else {
+		Quad4 r = { { fx ? q.v[3] : q.v[0], fx ? q.v[2] : q.v[1], fx ? q.v[1] : q.v[2], fx ? q.v[0] : q.v[3] } };
+		return r;
+	}
+}
+template <int FL>
+__device__ __forceinline__ int flip_q(int q, int fwq, bool fx)
+{
+	if constexpr (FL != 2)
+		return q;
+	else
+		return fx ? fwq - 1 - q : q;
+}
 
 __device__ __forceinline__ Quad4 inv_row_vals(int qd, int nquads, I2 lo, I2 hi)
 {
@@ -2022,7 +2098,7 @@ __device__ __forceinline__ Quad4 inv_row_vals_h(int qd, int nquads, int lane, co
 // Inverse level: int32 planes, or — the finest level of a gray image — clamped 8-bit pixels out (and, F16, the detail
 // bands in as 16-bit values); DstT = float / Half16: the clamped pixels (at a.maxval, whatever it is) as floats, A.fmt.
 // The loop is batched like the forward kernel's (see there): one wait per S row pairs.
-template <typename DstT, bool F16>
+template <typename DstT, bool F16, int FL = 0>
 __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 {
 	const LevelArgs &a = A.a;
@@ -2040,7 +2116,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 	const typename DetPtr<F16>::type det = DetPtr<F16>::of(a, plane);
 	typedef InvRawT<F16> InvRaw;
 	typedef OutRow<DstT> Out;
-	DstT *dst = inv_dst<DstT>(a) + inv_dst_off<DstT>(a, plane);
+	int opitch = a.llpitch;   // (the wave's: negated for a bottom-up window)
+	bool fx = false;
+	DstT *dst = inv_dst<DstT>(a);
+	if constexpr (FL == 0)
+		dst += inv_dst_off<DstT>(a, plane);
+	else
+		dst += flip_dst<FL>(a.grid, a.ll_ps, plane, A.fh, opitch, fx);
+	const int qs = flip_q<FL>(qd, A.fwq, fx);   // the quad of the row that the lane's quad goes to
 	const InvAt at = inv_at(a, qd, A.nquads);
 
 	constexpr int S = 2;
@@ -2061,9 +2144,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 		for (int s = 0; s < S; ++s) {
 			const int j = jb + s;
 			if (j < j1 && writes) {
-				Out::store(dst + (long)(2 * j) * a.llpitch, qd, orow[2 * s]);
+				Out::store(dst + (long)(2 * j) * opitch, qs, orow[2 * s]);
 				if (2 * j + 1 < a.h)
-					Out::store(dst + (long)(2 * j + 1) * a.llpitch, qd, orow[2 * s + 1]);
+					Out::store(dst + (long)(2 * j + 1) * opitch, qs, orow[2 * s + 1]);
 			}
 		}
 	};
@@ -2091,11 +2174,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 			inv_cols(a, jj, c, cur[s], e, o);
 			inv_cols(a, jj, cx, curx[s], ex, ox);
 			if constexpr (FloatSample<DstT>::value) {
-				orow[2 * s] = Out::of(inv_row_vals_h(qd, A.nquads, lane, e, ex), a.maxval, A.fmt);
-				orow[2 * s + 1] = Out::of(inv_row_vals_h(qd, A.nquads, lane, o, ox), a.maxval, A.fmt);
+				orow[2 * s] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, e, ex), fx), a.maxval, A.fmt);
+				orow[2 * s + 1] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, o, ox), fx), a.maxval, A.fmt);
 			} else {
-				orow[2 * s] = Out::of(inv_row_vals_h(qd, A.nquads, lane, e, ex), a.maxval);
-				orow[2 * s + 1] = Out::of(inv_row_vals_h(qd, A.nquads, lane, o, ox), a.maxval);
+				orow[2 * s] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, e, ex), fx), a.maxval);
+				orow[2 * s + 1] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, o, ox), fx), a.maxval);
 			}
 		}
 	}
@@ -2120,6 +2203,7 @@ struct Inv2Args {
 	uint8_t *dst8;        // 8-bit output (the finest level of a gray picture: pnm.h:108's clamp fused), dst_ps / opitch in bytes
 	WinGrid grid;         // the windows behind dst8 (dst_ps apart in a band)
 	long cstride;         // planar RGB pixels behind dst8: from a window's R plane to G, from G to B (bytes; signed as in LevelArgsW); 0: interleaved.  (Last, as in LevelArgsW.)
+	int fh, fwq;          // the flipped instances (FL): the WINDOWS' height and quads per row
 };
 constexpr int V2_FIRST = 4, V2_OWN = 56;
 
@@ -2209,7 +2293,7 @@ struct OutPlane<uint8_t> {
 // level of a gray picture — clamped pixels, 4 bytes per lane: a wave's 224 bytes are seven 32-byte pieces, and the block's four waves
 // sit SIDE BY SIDE so that together they write seven whole lines.  F16: both levels' detail bands are 16-bit values (the codec's
 // pipelines, dwtx_p16); the arithmetic is int32 either way.
-template <typename DstT, bool F16>
+template <typename DstT, bool F16, int FL = 0>
 __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w(Inv2Args a)
 {
 	constexpr bool SIDE = sizeof(DstT) == 1;
@@ -2231,7 +2315,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w(Inv2Args a)
 	const int qc = min(max(q + max(V2_FIRST - 1 - lane, 0) - max(lane - (V2_FIRST + V2_OWN), 0), 0), a.nquads - 1);
 	const int *ll2 = a.ll2 + plane * a.ll2_ps + qc;
 	const typename DetBand<F16>::ptr det = DetBand<F16>::of(a, plane);
-	DstT *dst = OutPlane<DstT>::of(a, plane);
+	int opitch = a.opitch;   // (the wave's: negated for a bottom-up window)
+	bool fx = false;
+	DstT *dst;
+	if constexpr (FL == 0)
+		dst = OutPlane<DstT>::of(a, plane);
+	else
+		dst = a.dst8 + flip_dst<FL>(a.grid, a.dst_ps, plane, a.fh, opitch, fx);   // (FL: 8-bit gray pixels only)
+	const int qs = flip_q<FL>(q, a.fwq, fx);
 	typedef typename DetBand<F16>::raw1 Raw1;
 	auto load2 = [&](int m) {
 		const int mm = min(max(m, 0), h4 - 1);
@@ -2272,7 +2363,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w(Inv2Args a)
 			return;
 #pragma unroll
 		for (int k = 0; k < 4; ++k)
-			OutPlane<DstT>::store(dst + (long)(4 * m + k) * a.opitch + 4 * q, orow[k]);
+			OutPlane<DstT>::store(dst + (long)(4 * m + k) * opitch + 4 * qs, orow[k]);
 	};
 	// one row pair of level k: state (pair jj) + the next pair's samples -> its two output rows; the state moves on
 	auto pair1 = [&](int jj, I2 nsl, const Raw1 &n, typename OutPlane<DstT>::row &even, typename OutPlane<DstT>::row &odd) {
@@ -2285,8 +2376,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w(Inv2Args a)
 		}
 		const Quad4 ev = inv_row_vals(q, a.nquads, cel, ceh);
 		const Quad4 od = inv_row_vals(q, a.nquads, i2_add2(cdl, cel, nel), i2_add2(cdh, ceh, neh));
-		even = OutRow<DstT>::of(ev, 0);
-		odd = OutRow<DstT>::of(od, 0);
+		even = OutRow<DstT>::of(flip_quad<FL>(ev, fx), 0);
+		odd = OutRow<DstT>::of(flip_quad<FL>(od, fx), 0);
 		cdl = ndl;
 		cdh = ndh;
 		cel = nel;
@@ -2578,7 +2669,7 @@ struct RgbOut<uint8_t, PIX_STEP4_BGR> : RgbOut<uint8_t, PIX_STEP4> {
 // PIX_PLANAR: dst8 is the R plane of the window, G and B A.cstride samples apart each (signed), llpitch the pitch of a plane's rows
 // PIX_STEP4: llpitch is the pitch of rows of 4-byte pixels; the step is the constant 4 here, no argument carries it
 // PixT = float / Half16 (PIX_PLANAR only): float samples, strides in samples, clamps at a.maxval, the conversion in A.fmt
-template <bool F16, typename PixT = uint8_t, PixLayout LAYOUT = PIX_PACKED>
+template <bool F16, typename PixT = uint8_t, PixLayout LAYOUT = PIX_PACKED, int FL = 0>
 __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 {
 	const LevelArgs &a = A.a;
@@ -2602,7 +2693,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 		det[ch] = DetPtr<F16>::of(a, 3 * image + ch);
 	}
 	typedef RgbOut<PixT, LAYOUT> Out;
-	uint8_t *dst = a.dst8 + win_off(a.grid, a.ll_ps, image) * (long)sizeof(PixT);
+	int opitch = a.llpitch;   // (the wave's: negated for a bottom-up window)
+	bool fx = false;
+	uint8_t *dst = a.dst8 + flip_dst<FL>(a.grid, a.ll_ps, image, A.fh, opitch, fx) * (long)sizeof(PixT);
+	const int qs = flip_q<FL>(qd, A.fwq, fx);   // the quad of the row that the lane's quad goes to
 	const InvAt at = inv_at(a, qd, A.nquads);
 
 	// (one row pair per batch: three planes' worth of arithmetic lies between two waits as it is)
@@ -2617,13 +2711,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 	auto store_pair = [&](int j) {
 		if (writes) {   // twelve bytes per lane in one store: the wave's 56 lanes write 672 consecutive bytes (deep pixels: twice that; planar: a third of it to each plane)
 			if constexpr (FloatSample<PixT>::AT_STORE) {
-				Out::store(dst, a.llpitch, 2 * j, qd, orow[0], A.cstride, A.fmt);
+				Out::store(dst, opitch, 2 * j, qs, orow[0], A.cstride, A.fmt);
 				if (2 * j + 1 < a.h)
-					Out::store(dst, a.llpitch, 2 * j + 1, qd, orow[1], A.cstride, A.fmt);
+					Out::store(dst, opitch, 2 * j + 1, qs, orow[1], A.cstride, A.fmt);
 			} else {
-				Out::store(dst, a.llpitch, 2 * j, qd, orow[0], A.cstride);
+				Out::store(dst, opitch, 2 * j, qs, orow[0], A.cstride);
 				if (2 * j + 1 < a.h)
-					Out::store(dst, a.llpitch, 2 * j + 1, qd, orow[1], A.cstride);
+					Out::store(dst, opitch, 2 * j + 1, qs, orow[1], A.cstride);
 			}
 		}
 	};
@@ -2642,6 +2736,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 #pragma unroll
 		for (int ch = 0; ch < 3; ++ch)
 			inv_pair(a, jj, qd, A.nquads, c[ch], cur[ch], even[ch], odd[ch]);
+		if constexpr (FL == 2) {
+#pragma unroll
+			for (int ch = 0; ch < 3; ++ch) {
+				even[ch] = flip_quad<FL>(even[ch], fx);
+				odd[ch] = flip_quad<FL>(odd[ch], fx);
+			}
+		}
 		if constexpr (FloatSample<PixT>::value) {
 			orow[0] = Out::of(even[0], even[1], even[2], a.maxval, A.fmt);
 			orow[1] = Out::of(odd[0], odd[1], odd[2], a.maxval, A.fmt);
@@ -2661,7 +2762,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 // 3 B read) are gone.  grid.z = image.
 // PIX_PLANAR: the lane's four pixels go out as one word to each of the window's three planes (a.cstride apart) instead
 // PIX_STEP4: into 4-byte pixels, three bytes of each (rgbx_store)
-template <bool F16, PixLayout LAYOUT = PIX_PACKED>
+template <bool F16, PixLayout LAYOUT = PIX_PACKED, int FL = 0>
 __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 {
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -2687,7 +2788,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 		ll2[ch] = a.ll2 + (long)(3 * image + ch) * a.ll2_ps + qc;
 		det[ch] = DetBand<F16>::of(a, 3 * image + ch);
 	}
-	uint8_t *dst = a.dst8 + win_off(a.grid, a.dst_ps, image);
+	int opitch = a.opitch;   // (the wave's: negated for a bottom-up window)
+	bool fx = false;
+	uint8_t *dst = a.dst8 + flip_dst<FL>(a.grid, a.dst_ps, image, a.fh, opitch, fx);
+	const int qs = flip_q<FL>(q, a.fwq, fx);
 	auto load2 = [&](int ch, int m) {
 		const int mm = min(max(m, 0), h4 - 1);
 		Raw2 r = { ll2[ch][(long)mm * a.ll2pitch], (int)det[ch][(long)mm * a.dpitch + w4 + qc], (int)det[ch][(long)(h4 + mm) * a.dpitch + qc],
@@ -2728,15 +2832,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 #pragma unroll
 		for (int k = 0; k < 4; ++k) {
 			if constexpr (LAYOUT == PIX_STEP4 || LAYOUT == PIX_STEP4_BGR) {
-				rgbx_store<true>(dst + (long)(4 * m + k) * a.opitch + 16 * q, orow[k]);
+				rgbx_store<true>(dst + (long)(4 * m + k) * opitch + 16 * qs, orow[k]);
 			} else if constexpr (LAYOUT == PIX_PLANAR) {
-				uint8_t *p = dst + (long)(4 * m + k) * a.opitch + 4 * q;
+				uint8_t *p = dst + (long)(4 * m + k) * opitch + 4 * qs;
 #pragma unroll
 				for (int c = 0; c < 3; ++c)
 					__builtin_nontemporal_store(orow[k].w[c], reinterpret_cast<unsigned *>(p + c * a.cstride));
 			} else {
 				const U32x3 v = { orow[k].w[0], orow[k].w[1], orow[k].w[2] };
-				__builtin_nontemporal_store(v, reinterpret_cast<U32x3 *>(dst + (long)(4 * m + k) * a.opitch + 12 * q));
+				__builtin_nontemporal_store(v, reinterpret_cast<U32x3 *>(dst + (long)(4 * m + k) * opitch + 12 * qs));
 			}
 		}
 	};
@@ -2797,7 +2901,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 		}
 #pragma unroll
 		for (int k = 0; k < 4; ++k)
-			orow[k] = RgbOut<uint8_t, LAYOUT>::of(rows[0][k], rows[1][k], rows[2][k], 255);
+			orow[k] = RgbOut<uint8_t, LAYOUT>::of(flip_quad<FL>(rows[0][k], fx), flip_quad<FL>(rows[1][k], fx), flip_quad<FL>(rows[2][k], fx), 255);
 	}
 	store_rows(m1 - 1);
 }
@@ -2955,7 +3059,21 @@ struct PixGrid {
 	int W, H, C, n;
 	long chan_stride;   // RGB: from a pixel's R sample to its G, from G to B (dwtx_pixels::colour_stride()) — 1 interleaved, the channel stride planar, negative where the pixels lie as B, G, R
 	int col_step;       // from a pixel to the next one of its row: C interleaved (dwtx_pixels::pixel_step where a view has one), 1 planar
+	int fw, fh;         // the FLIP instances: the windows' sides (dwtx_pixels::flip_w, flip_h), inside which a W x H picture is mirrored
 };
+
+// The FLIP instances of the conversions (a flipped call's windows): pixel (x, y) of window `win`'s PICTURE lies at the mirrored
+// memory position of the window — column fw - 1 - x under DWTX_FLIP_X, row fh - 1 - y under DWTX_FLIP_Y — by the flags of the
+// window's table entry.  -> the memory row, and x becomes the memory column.  The flags are the wave's; the two selects are all
+// a lane adds.  The other instances keep the code they had.
+template <class P>
+__device__ __forceinline__ P *flipped_row(P *pix, const PixGrid &g, unsigned win, int &x, int y)
+{
+	unsigned flags;
+	const long off = win_off_flip(g.grid, (int)win, flags);
+	x = (flags & DWTX_FLIP_X) ? g.fw - 1 - x : x;
+	return pix + off + (long)((flags & DWTX_FLIP_Y) ? g.fh - 1 - y : y) * g.row_pitch;
+}
 
 constexpr int PX_LANES = 64, PX_ROWS = 4;   // a workgroup of the conversions: one wave per row, a lane per pixel
 
@@ -2973,7 +3091,7 @@ __device__ __forceinline__ int sample_in<_Float16>(_Float16 v, const FloatFmt &f
 template <>
 __device__ __forceinline__ int sample_in<__bf16>(__bf16 v, const FloatFmt &f, int c, int M) { return quant_of((float)v, f.scale[c], f.bias[c], (float)M); }
 
-template <class P>
+template <class P, bool FLIP = false>
 __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *__restrict__ planes, const P *__restrict__ pix, PixGrid g, int M, FloatFmt f)
 {
 	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
@@ -2982,12 +3100,13 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *
 		return;
 	const long npix = (long)g.W * g.H;
 	for (unsigned win = blockIdx.z; win < (unsigned)g.n; win += gridDim.z) {
-		const P *row = pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
+		int mx = x;   // (the memory column: x itself but in a mirrored window)
+		const P *row = FLIP ? flipped_row(pix, g, win, mx, y) : pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
 		int *dst = planes + (long)win * g.C * npix + (long)y * g.W + x;
 		if (g.C == 1) {
-			dst[0] = sample_in<P>(row[(long)x * g.col_step], f, 0, M);
+			dst[0] = sample_in<P>(row[(long)mx * g.col_step], f, 0, M);
 		} else {
-			const P *p = row + (long)x * g.col_step;
+			const P *p = row + (long)mx * g.col_step;
 			const int r = sample_in<P>(p[0], f, 0, M), gr = sample_in<P>(p[g.chan_stride], f, 1, M), b = sample_in<P>(p[2 * g.chan_stride], f, 2, M);
 			const int co = r - b;
 			const int t = b + tdiv2(co);
@@ -3019,7 +3138,7 @@ __device__ __forceinline__ _Float16 sample_of<_Float16>(int v, const FloatFmt &f
 template <>
 __device__ __forceinline__ __bf16 sample_of<__bf16>(int v, const FloatFmt &f, int c) { return (__bf16)float_of(v, f.scale[c], f.bias[c]); }
 
-template <class P>
+template <class P, bool FLIP = false>
 __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, int M, FloatFmt f)
 {
 	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
@@ -3028,10 +3147,11 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__
 		return;
 	const long npix = (long)g.W * g.H;
 	for (unsigned win = blockIdx.z; win < (unsigned)g.n; win += gridDim.z) {
-		P *row = pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
+		int mx = x;   // (the memory column: x itself but in a mirrored window)
+		P *row = FLIP ? flipped_row(pix, g, win, mx, y) : pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
 		const int *src = planes + (long)win * g.C * npix + (long)y * g.W + x;
 		if (g.C == 1) {
-			row[(long)x * g.col_step] = sample_of<P>(clampi(src[0], 0, M), f, 0);
+			row[(long)mx * g.col_step] = sample_of<P>(clampi(src[0], 0, M), f, 0);
 		} else {
 			const int yy = clampi(src[0], 0, M);
 			const int co = clampi(src[npix], -M, M);
@@ -3040,7 +3160,7 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__
 			const int gr = cg + t;
 			const int b = t - tdiv2(co);
 			const int r = b + co;
-			P *p = row + (long)x * g.col_step;
+			P *p = row + (long)mx * g.col_step;
 			p[0] = sample_of<P>(clampi(r, 0, M), f, 0);
 			p[g.chan_stride] = sample_of<P>(clampi(gr, 0, M), f, 1);
 			p[2 * g.chan_stride] = sample_of<P>(clampi(b, 0, M), f, 2);
@@ -3138,7 +3258,7 @@ extern "C" int dwtx_synth_pixels(dwtx_ctx *ctx, uint8_t *pix, int W, int H, int 
 static PixGrid pix_grid(const dwtx_pixels &px, int W, int H, int n, dim3 *grid)
 {
 	*grid = dim3((unsigned)dwtx_cdiv(W, PX_LANES), (unsigned)dwtx_cdiv(H, PX_ROWS), (unsigned)min(n, 65535));
-	return PixGrid{ (long)px.image_stride, (long)px.pitch(W), win_grid(px), W, H, px.channels, n, px.colour_stride(), (int)px.step() };
+	return PixGrid{ (long)px.image_stride, (long)px.pitch(W), win_grid(px), W, H, px.channels, n, px.colour_stride(), (int)px.step(), px.flip_w, px.flip_h };
 }
 
 // the kernels' copy of a float destination's conversion (integer pixels: the identity, which nothing reads)
@@ -3153,6 +3273,20 @@ static FloatFmt float_fmt(const dwtx_pixels &px)
 	return f;
 }
 
+// the conversions' launches for samples of type P: the FLIP instance for a flipped call's windows, else the plain one
+template <class P>
+static void launch_planes_from_pixels(dwtx_ctx *ctx, dim3 grid, int32_t *planes, const dwtx_pixels &px, const PixGrid &g, const FloatFmt &f)
+{
+	const auto kernel = px.flips ? k_planes_from_pixels<P, true> : k_planes_from_pixels<P, false>;
+	hipLaunchKernelGGL(kernel, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, static_cast<const P *>(px.red()), g, px.maxval, f);
+}
+template <class P>
+static void launch_pixels_from_planes(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const int32_t *planes, const PixGrid &g, const FloatFmt &f)
+{
+	const auto kernel = px.flips ? k_pixels_from_planes<P, true> : k_pixels_from_planes<P, false>;
+	hipLaunchKernelGGL(kernel, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), planes, g, px.maxval, f);
+}
+
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
 {
 	const int C = px.channels;
@@ -3160,26 +3294,27 @@ int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px,
 		return DWTX_ERR_ARG;
 	if (px.is_float() && !dwtx_maxval_ok(px.maxval))   // (the quantiser's clamp; integer sources have no use for a maxval)
 		return DWTX_ERR_ARG;
+	if (px.flips && (!px.offs || W > px.flip_w || H > px.flip_h))   // (a picture is mirrored inside its window: the mirrored index stays in it)
+		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	dim3 grid;
 	const PixGrid g = pix_grid(px, W, H, n, &grid);
 	const FloatFmt f = float_fmt(px);
-	const dim3 block(PX_LANES * PX_ROWS);
 	switch (px.kind) {
 	case DWTX_SAMPLE_U8:
-		hipLaunchKernelGGL(k_planes_from_pixels<uint8_t>, grid, block, 0, ctx->stream, planes, static_cast<const uint8_t *>(px.red()), g, px.maxval, f);
+		launch_planes_from_pixels<uint8_t>(ctx, grid, planes, px, g, f);
 		break;
 	case DWTX_SAMPLE_U16:
-		hipLaunchKernelGGL(k_planes_from_pixels<uint16_t>, grid, block, 0, ctx->stream, planes, static_cast<const uint16_t *>(px.red()), g, px.maxval, f);
+		launch_planes_from_pixels<uint16_t>(ctx, grid, planes, px, g, f);
 		break;
 	case DWTX_SAMPLE_F32:
-		hipLaunchKernelGGL(k_planes_from_pixels<float>, grid, block, 0, ctx->stream, planes, static_cast<const float *>(px.red()), g, px.maxval, f);
+		launch_planes_from_pixels<float>(ctx, grid, planes, px, g, f);
 		break;
 	case DWTX_SAMPLE_F16:
-		hipLaunchKernelGGL(k_planes_from_pixels<_Float16>, grid, block, 0, ctx->stream, planes, static_cast<const _Float16 *>(px.red()), g, px.maxval, f);
+		launch_planes_from_pixels<_Float16>(ctx, grid, planes, px, g, f);
 		break;
 	case DWTX_SAMPLE_BF16:
-		hipLaunchKernelGGL(k_planes_from_pixels<__bf16>, grid, block, 0, ctx->stream, planes, static_cast<const __bf16 *>(px.red()), g, px.maxval, f);
+		launch_planes_from_pixels<__bf16>(ctx, grid, planes, px, g, f);
 		break;
 	default:
 		return DWTX_ERR_ARG;
@@ -3195,26 +3330,27 @@ int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *p
 		return DWTX_ERR_ARG;
 	if (!dwtx_maxval_ok(px.maxval))
 		return DWTX_ERR_ARG;
+	if (px.flips && (!px.offs || W > px.flip_w || H > px.flip_h))   // (a picture is mirrored inside its window: the mirrored index stays in it)
+		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	dim3 grid;
 	const PixGrid g = pix_grid(px, W, H, n, &grid);
 	const FloatFmt f = float_fmt(px);
-	const dim3 block(PX_LANES * PX_ROWS);
 	switch (px.kind) {
 	case DWTX_SAMPLE_U8:
-		hipLaunchKernelGGL(k_pixels_from_planes<uint8_t>, grid, block, 0, ctx->stream, static_cast<uint8_t *>(px.red()), planes, g, px.maxval, f);
+		launch_pixels_from_planes<uint8_t>(ctx, grid, px, planes, g, f);
 		break;
 	case DWTX_SAMPLE_U16:
-		hipLaunchKernelGGL(k_pixels_from_planes<uint16_t>, grid, block, 0, ctx->stream, static_cast<uint16_t *>(px.red()), planes, g, px.maxval, f);
+		launch_pixels_from_planes<uint16_t>(ctx, grid, px, planes, g, f);
 		break;
 	case DWTX_SAMPLE_F32:
-		hipLaunchKernelGGL(k_pixels_from_planes<float>, grid, block, 0, ctx->stream, static_cast<float *>(px.red()), planes, g, px.maxval, f);
+		launch_pixels_from_planes<float>(ctx, grid, px, planes, g, f);
 		break;
 	case DWTX_SAMPLE_F16:
-		hipLaunchKernelGGL(k_pixels_from_planes<_Float16>, grid, block, 0, ctx->stream, static_cast<_Float16 *>(px.red()), planes, g, px.maxval, f);
+		launch_pixels_from_planes<_Float16>(ctx, grid, px, planes, g, f);
 		break;
 	case DWTX_SAMPLE_BF16:
-		hipLaunchKernelGGL(k_pixels_from_planes<__bf16>, grid, block, 0, ctx->stream, static_cast<__bf16 *>(px.red()), planes, g, px.maxval, f);
+		launch_pixels_from_planes<__bf16>(ctx, grid, px, planes, g, f);
 		break;
 	default:
 		return DWTX_ERR_ARG;
@@ -3336,7 +3472,7 @@ static FwdSource fwd_source(const dwtx_pixels *px, bool src16)
 }
 
 // the wide kernel of a source, without and with histograms (deep pixels leave none: lift_fwd refuses the call)
-static WideKernel fwd_wide_kernel(int src, bool hist)
+static WideKernel fwd_wide_kernel(int src, bool hist, bool flip_y = false)
 {
 	static const WideKernel K[SRC_COUNT][2] = {
 		{ k_fwd_level_w<false, SRC_I32>, k_fwd_level_w<true, SRC_I32> },
@@ -3360,7 +3496,30 @@ static WideKernel fwd_wide_kernel(int src, bool hist)
 		{ k_fwd_float_w<FloatPix<float, true, true>, false>, nullptr },
 		{ k_fwd_float_w<FloatPix<Half16, true, true>, false>, nullptr },
 	};
-	return K[src][hist];
+	// the same sources for the windows of a flipped call (FY; pixels only: a band has no windows)
+	static const WideKernel KY[SRC_COUNT][2] = {
+		{ nullptr, nullptr },
+		{ nullptr, nullptr },
+		{ k_fwd_level_w<false, SRC_U16, true>, nullptr },
+		{ k_fwd_level_w<false, SRC_RGB16, true>, nullptr },
+		{ k_fwd_level_w<false, SRC_RGBP16, true>, nullptr },
+		{ k_fwd_pixels_w<uint8_t, false, true>, k_fwd_pixels_w<uint8_t, true, true> },
+		{ k_fwd_pixels_w<Rgb8, false, true>, k_fwd_pixels_w<Rgb8, true, true> },
+		{ k_fwd_pixels_w<RgbP8, false, true>, k_fwd_pixels_w<RgbP8, true, true> },
+		{ k_fwd_pixels_w<Rgbx8, false, true>, k_fwd_pixels_w<Rgbx8, true, true> },
+		{ k_fwd_level_w<false, SRC_BGR16, true>, nullptr },
+		{ k_fwd_pixels_w<Bgr8, false, true>, k_fwd_pixels_w<Bgr8, true, true> },
+		{ k_fwd_pixels_w<Bgrx8, false, true>, k_fwd_pixels_w<Bgrx8, true, true> },
+		{ k_fwd_float_w<FloatPix<float, false, false>, false, true>, k_fwd_float_w<FloatPix<float, false, false>, true, true> },
+		{ k_fwd_float_w<FloatPix<Half16, false, false>, false, true>, k_fwd_float_w<FloatPix<Half16, false, false>, true, true> },
+		{ k_fwd_float_w<FloatPix<float, true, false>, false, true>, k_fwd_float_w<FloatPix<float, true, false>, true, true> },
+		{ k_fwd_float_w<FloatPix<Half16, true, false>, false, true>, k_fwd_float_w<FloatPix<Half16, true, false>, true, true> },
+		{ k_fwd_float_w<FloatPix<float, false, true>, false, true>, nullptr },
+		{ k_fwd_float_w<FloatPix<Half16, false, true>, false, true>, nullptr },
+		{ k_fwd_float_w<FloatPix<float, true, true>, false, true>, nullptr },
+		{ k_fwd_float_w<FloatPix<Half16, true, true>, false, true>, nullptr },
+	};
+	return flip_y ? KY[src][hist] : K[src][hist];
 }
 
 // px != nullptr (`in` is then not read): the source is pixels, gray (plane p = image p) or RGB, interleaved or planar (plane p =
@@ -3508,7 +3667,8 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			const int sx = dwtx_cdiv(strips, 1 << A.wx_log2), gy = dwtx_cdiv(a.h2, (WAVES >> A.wx_log2) * a.rpw);
 			// (8-bit RGB: the three channels of a strip side by side, xcd_strip_rgb; deep RGB: a block per plane, each taking its channel)
 			const dim3 grid = from.rgb_grid ? dim3(sx * 3, gy, nplanes / 3) : dim3(sx, gy, nplanes);
-			const WideKernel kernel = fwd_wide_kernel(from.src, hist_here);
+			A.ppw = pix_in ? px->channels : 1;
+			const WideKernel kernel = fwd_wide_kernel(from.src, hist_here, pix_in && px->flips);
 			if (!kernel)
 				return DWTX_ERR_ARG;
 			hipLaunchKernelGGL(kernel, grid, dim3(64 * WAVES), 0, ctx->stream, A);
@@ -3538,10 +3698,13 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 // rows, so all they ask is that every row of every window — of every plane of a planar window — starts on a quad (px.wide())
 // and that the pitch fits their int.  Pixels with a step (dwtx_pixels::pixel_step): only 8-bit RGB in 4-byte pixels, which the
 // Rgbx8 / PIX_STEP4 instances address with the constant 4; the others would be read and written with dense addressing.
-// Any other view goes through the general conversions (dwtx_pixels_to_planes / dwtx_planes_to_pixels).
+// Any other view goes through the general conversions (dwtx_pixels_to_planes / dwtx_planes_to_pixels) — flipped windows
+// A flipped call's windows (dwtx_pixels::flips) carry flags in their table entries that only win_off_flip takes apart: a SOURCE
+// qualifies when no window carries DWTX_FLIP_X (flip_wide: the FY instances of the wide forward kernels read it), a destination
+// (flip_sink: the FL instances of the wide inverse kernels write it) with any flags, a mirrored one if the windows' width is on the quad.
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H)
 {
-	return W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide() && px.pitch(W) <= 0x7fffffffu && (!px.stepped() || px.rgbx8()) &&
+	return (!px.flips || px.flip_wide || (px.flip_sink && (!px.flip_x || px.flip_w % 4 == 0))) && W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide() && px.pitch(W) <= 0x7fffffffu && (!px.stepped() || px.rgbx8()) &&
 		(!px.is_float() || px.channels == 1 || px.planar());   // (float sinks: OutRow<F> and RgbOut<F, PIX_PLANAR>, float sources: FloatPix<>; interleaved float RGB has neither)
 }
 
@@ -3583,54 +3746,71 @@ int dwtx_transformation_fwd_hist(dwtx_ctx *ctx, int32_t *out, const int32_t *in,
 
 using Inv2Kernel = void (*)(Inv2Args);
 
+// FL of the kernels that write these pixels: 0, or for a flipped call's windows 1 (upright and bottom-up ones) or 2 (a mirrored one among them)
+static int flip_level(const dwtx_pixels *px) { return !px || !px->flips ? 0 : px->flip_x ? 2 : 1; }
+
 // px: the pair writes these pixels (8-bit ones, gray or RGB), which it does from 16-bit bands only
+template <int FL>
+static Inv2Kernel inv2_pixel_kernel(const dwtx_pixels *px)
+{
+	if (px->channels == 3) {
+		if (px->planar())
+			return k_inv2_level_w_rgb<true, PIX_PLANAR, FL>;
+		if (px->bgr())
+			return px->rgbx8() ? k_inv2_level_w_rgb<true, PIX_STEP4_BGR, FL> : k_inv2_level_w_rgb<true, PIX_PACKED_BGR, FL>;
+		return px->rgbx8() ? k_inv2_level_w_rgb<true, PIX_STEP4, FL> : k_inv2_level_w_rgb<true, PIX_PACKED, FL>;
+	}
+	return k_inv2_level_w<uint8_t, true, FL>;
+}
 static Inv2Kernel inv2_kernel(const dwtx_pixels *px, bool det16)
 {
-	if (px && px->channels == 3) {
-		if (px->planar())
-			return k_inv2_level_w_rgb<true, PIX_PLANAR>;
-		if (px->bgr())
-			return px->rgbx8() ? k_inv2_level_w_rgb<true, PIX_STEP4_BGR> : k_inv2_level_w_rgb<true, PIX_PACKED_BGR>;
-		return px->rgbx8() ? k_inv2_level_w_rgb<true, PIX_STEP4> : k_inv2_level_w_rgb<true>;
+	if (px) {
+		const int fl = flip_level(px);
+		return fl == 2 ? inv2_pixel_kernel<2>(px) : fl == 1 ? inv2_pixel_kernel<1>(px) : inv2_pixel_kernel<0>(px);
 	}
-	if (px)
-		return k_inv2_level_w<uint8_t, true>;
 	return det16 ? k_inv2_level_w<int, true> : k_inv2_level_w<int, false>;
 }
 
-// The wide kernel of an inverse step.  px: the step writes these pixels (gray or RGB; deep ones never from 16-bit bands)
-static WideKernel inv_wide_kernel(const dwtx_pixels *px, bool det16)
+// The wide kernel of an inverse step that writes these pixels (gray or RGB; deep ones never from 16-bit bands)
+template <int FL>
+static WideKernel inv_pixel_kernel(const dwtx_pixels *px, bool det16)
 {
-	if (px && px->is_float()) {   // gray, or planar RGB in either order (dwtx_pixels_ok); from int32 and from 16-bit bands
+	if (px->is_float()) {   // gray, or planar RGB in either order (dwtx_pixels_ok); from int32 and from 16-bit bands
 		const bool f32 = px->kind == DWTX_SAMPLE_F32;
 		if (px->channels == 3)
-			return f32 ? (det16 ? k_inv_level_w_rgb<true, float, PIX_PLANAR> : k_inv_level_w_rgb<false, float, PIX_PLANAR>)
-			           : (det16 ? k_inv_level_w_rgb<true, Half16, PIX_PLANAR> : k_inv_level_w_rgb<false, Half16, PIX_PLANAR>);
-		return f32 ? (det16 ? k_inv_level_w<float, true> : k_inv_level_w<float, false>)
-		           : (det16 ? k_inv_level_w<Half16, true> : k_inv_level_w<Half16, false>);
+			return f32 ? (det16 ? k_inv_level_w_rgb<true, float, PIX_PLANAR, FL> : k_inv_level_w_rgb<false, float, PIX_PLANAR, FL>)
+			           : (det16 ? k_inv_level_w_rgb<true, Half16, PIX_PLANAR, FL> : k_inv_level_w_rgb<false, Half16, PIX_PLANAR, FL>);
+		return f32 ? (det16 ? k_inv_level_w<float, true, FL> : k_inv_level_w<float, false, FL>)
+		           : (det16 ? k_inv_level_w<Half16, true, FL> : k_inv_level_w<Half16, false, FL>);
 	}
-	const int channels8 = px && !px->deep() ? px->channels : 0;
-	if (px && px->channels == 3 && px->planar()) {
+	const int channels8 = !px->deep() ? px->channels : 0;
+	if (px->channels == 3 && px->planar()) {
 		if (px->deep())
-			return k_inv_level_w_rgb<false, uint16_t, PIX_PLANAR>;
-		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_PLANAR> : k_inv_level_w_rgb<false, uint8_t, PIX_PLANAR>;
+			return k_inv_level_w_rgb<false, uint16_t, PIX_PLANAR, FL>;
+		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_PLANAR, FL> : k_inv_level_w_rgb<false, uint8_t, PIX_PLANAR, FL>;
 	}
-	if (px && px->bgr()) {   // (interleaved: the layouts' B, G, R twins)
+	if (px->bgr()) {   // (interleaved: the layouts' B, G, R twins)
 		if (px->rgbx8())
-			return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_STEP4_BGR> : k_inv_level_w_rgb<false, uint8_t, PIX_STEP4_BGR>;
+			return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_STEP4_BGR, FL> : k_inv_level_w_rgb<false, uint8_t, PIX_STEP4_BGR, FL>;
 		if (px->deep())
-			return k_inv_level_w_rgb<false, uint16_t, PIX_PACKED_BGR>;
-		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_PACKED_BGR> : k_inv_level_w_rgb<false, uint8_t, PIX_PACKED_BGR>;
+			return k_inv_level_w_rgb<false, uint16_t, PIX_PACKED_BGR, FL>;
+		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_PACKED_BGR, FL> : k_inv_level_w_rgb<false, uint8_t, PIX_PACKED_BGR, FL>;
 	}
-	if (px && px->rgbx8())
-		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_STEP4> : k_inv_level_w_rgb<false, uint8_t, PIX_STEP4>;
+	if (px->rgbx8())
+		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_STEP4, FL> : k_inv_level_w_rgb<false, uint8_t, PIX_STEP4, FL>;
 	if (channels8 == 3)
-		return det16 ? k_inv_level_w_rgb<true> : k_inv_level_w_rgb<false>;
+		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_PACKED, FL> : k_inv_level_w_rgb<false, uint8_t, PIX_PACKED, FL>;
 	if (channels8)
-		return det16 ? k_inv_level_w<uint8_t, true> : k_inv_level_w<uint8_t, false>;
-	if (!px)
-		return det16 ? k_inv_level_w<int, true> : k_inv_level_w<int, false>;
-	return px->channels == 3 ? k_inv_level_w_rgb<false, uint16_t> : k_inv_level_w<uint16_t, false>;
+		return det16 ? k_inv_level_w<uint8_t, true, FL> : k_inv_level_w<uint8_t, false, FL>;
+	return px->channels == 3 ? k_inv_level_w_rgb<false, uint16_t, PIX_PACKED, FL> : k_inv_level_w<uint16_t, false, FL>;
+}
+static WideKernel inv_wide_kernel(const dwtx_pixels *px, bool det16)
+{
+	if (px) {
+		const int fl = flip_level(px);
+		return fl == 2 ? inv_pixel_kernel<2>(px, det16) : fl == 1 ? inv_pixel_kernel<1>(px, det16) : inv_pixel_kernel<0>(px, det16);
+	}
+	return det16 ? k_inv_level_w<int, true> : k_inv_level_w<int, false>;
 }
 
 // px != nullptr (`out` is then not written): the finest level writes clamped pixels (gray, or RGB — interleaved or planar — after the
@@ -3638,6 +3818,9 @@ static WideKernel inv_wide_kernel(const dwtx_pixels *px, bool det16)
 static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const int32_t *in, int W, int H, int nplanes, const dwtx_p16 *p16 = nullptr)
 {
 	if (px && px->deep() && p16 && p16->planes)
+		return DWTX_ERR_ARG;
+	// (a flipped window holds its picture, mirrored quads and all: what keeps a mirrored index inside the window)
+	if (px && px->flips && (!px->offs || W > px->flip_w || H > px->flip_h || (px->flip_x && px->flip_w % 4 != 0)))
 		return DWTX_ERR_ARG;
 	if (!ctx || (!out && !px) || !in || W < 2 || H < 2 || nplanes < 1 || !dwtx_count_ok(nplanes, DWTX_MAX_PLANES_PER_CALL, "planes"))
 		return DWTX_ERR_ARG;
@@ -3744,6 +3927,8 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 				f.opitch = (int)px->pitch(W);
 				f.grid = win_grid(*px);
 				f.cstride = wide_cstride(*px);
+				f.fh = px->flip_h;
+				f.fwq = px->flip_w / 4;
 			} else if (t - 1 == 0) {
 				f.dst = out;
 				f.dst_ps = full_ps;
@@ -3815,8 +4000,11 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 			a.rpw = pick_rpw(sx, a.h2, nplanes, forced);
 			A.a = a;
 			A.cstride = rgb ? wide_cstride(*px) : 0;
-			if (pix_out)
+			if (pix_out) {
 				A.fmt = float_fmt(*px);
+				A.fh = px->flip_h;
+				A.fwq = px->flip_w / 4;
+			}
 			const dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), rgb ? nplanes / 3 : nplanes);
 			hipLaunchKernelGGL(inv_wide_kernel(pix_out, a.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {

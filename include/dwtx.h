@@ -578,6 +578,60 @@ int dwtx_decode_view_list(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stre
  * from 1 up); dst != 0: the list is a decode's and must be disjoint.  A view of 4-byte samples is taken for fp32 samples. */
 int dwtx_view_list_check(const dwtx_view *v, size_t pixel_step, int W, int H, int n, const void *const *host_windows, int dst);
 
+/* ---- flips in views: bottom-up surfaces and mirrored pictures coded in place ------------------------------------------------
+ * The most general call of each direction — dwtx_encode_view_list and dwtx_decode_view_list — plus a flip per window, for
+ * pictures whose rows run upwards (OpenGL read-backs, BMP / DIB sections, arrays with y pointing up) or whose columns run
+ * backwards (a loader's random horizontal flip): every stride of a dwtx_view is a size_t, so neither can be written as a
+ * view, and the caller's flip before an encode or after a decode is a pass over the batch.  (No reference counterpart: the
+ * reference reads and writes upright PNM files and nothing else.)
+ * Everything the two list calls say about their arguments holds, except that host_windows == NULL is allowed here and means
+ * the grid the view describes, as in dwtx_encode_view_float and dwtx_decode_view_crop.  Window i's flags are host_flips ?
+ * host_flips[i] : flip, a mask of DWTX_FLIP_X and DWTX_FLIP_Y.  host_flips is [n] bytes of HOST memory, read before the call
+ * returns, like host_windows, after the asynchronous encode too.
+ * Contract: let the window's sides be Ww x Hw (W x H, or crop_w x crop_h where there is a crop).  Memory position (x, y) of
+ * window i is what it is in every other view call: the pixel whose samples lie at first_i + y * row_pitch + x * step (+ c, or
+ * + c * channel_stride), first_i the window's lowest-addressed sample as the view or the list gives it.  A flip changes no
+ * stride, no `dev` and no pointer: with flags f, memory position (x, y) holds pixel (u, v) of the window's picture, where
+ *   u = (f & DWTX_FLIP_X) ? Ww - 1 - x : x        v = (f & DWTX_FLIP_Y) ? Hw - 1 - y : y.
+ * order, pixel_step, channel_stride, scale and bias keep their meaning (scale and bias belong to colours).  A flip does not
+ * change which samples a window covers, so row length, alignment and the disjointness rules are the unflipped call's.
+ * Encode: stream i and dev_info[i] are byte for byte those of the dense interleaved R, G, B picture Q(u, v) = memory(x(u),
+ * y(v)); only the windows' samples are read.
+ * Decode: with P_i the plain call's picture (dwtx_decode_view_crop), memory position (x, y) receives P_i(x0 + u, y0 + v) for
+ * every (x0 + u, y0 + v) inside ow x oh, and NO OTHER SAMPLE is written: a picture that comes out reduced lies in the corner
+ * of its window where its pixel (0, 0) lies — with DWTX_FLIP_Y the bottom rows, with DWTX_FLIP_X the right-hand columns.
+ * host_info is the plain call's, and the call synchronises where the plain call does.
+ * With all flags 0 the call IS dwtx_encode_view_list / dwtx_decode_view_list when host_windows is given, and otherwise
+ * dwtx_encode_view_float (fmt given), dwtx_encode_view_order or dwtx_decode_view_crop: it takes their path.
+ * A call with any flag set travels as a listed one (a grid is spelled out on the host) with the flags in the top two bits of
+ * each window's 8-byte table entry.  Wherever the unflipped call's windows are read / written by the transform's finest level
+ * itself, a flipped call's are too, per window: every wave takes its window's first row and the sign of the pitch from the
+ * table (DWTX_FLIP_Y, both directions), and a DECODE writes a mirrored window's quads at the mirrored place with their four
+ * pixels reversed (DWTX_FLIP_X: gray, planar, interleaved RGB and RGBX sinks of every sample type; a window wider than its
+ * reduced picture must then have Ww % 4 == 0).  An ENCODE with one mirrored window (DWTX_FLIP_X) goes through the general
+ * conversion into int32 planes, like an alpha-first surface — the same bytes, one pass more: the forward kernels' halo words
+ * would swap sides.  Crops, and views off the quad grid, take the general conversions as they do unflipped.  (Measured:
+ * DESIGN.md section 4.19.)
+ * DWTX_ERR_ARG (with a dwtx_last_error() text, nothing written): a flag outside 0..3; a non-zero `flip` together with
+ * host_flips; and everything the list calls (host_windows given) or the grid calls (NULL) refuse. */
+enum { DWTX_FLIP_X = 1, DWTX_FLIP_Y = 2 };
+int dwtx_encode_view_flip(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order,
+	const dwtx_float_format *fmt /* NULL: integer samples */, const void *const *host_windows /* NULL: the view's own grid */,
+	int flip, const unsigned char *host_flips /* [n] or NULL */,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
+int dwtx_decode_view_flip(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, void *const *host_windows /* NULL: the view's own grid */,
+	int flip, const unsigned char *host_flips, dwtx_decode_info *host_info);
+/* Host arithmetic only, like dwtx_view_list_check: DWTX_OK, or the DWTX_ERR_ARG (and text) the two calls above would return
+ * for this view, step, list and flags — and the one table the kernels walk a flipped window with.  W x H: the windows' sides
+ * (the crop's where there is one); dst != 0: the windows are a decode's.  origin[i]: where pixel (0, 0) of window i's PICTURE
+ * lies — its lowest-addressed channel — in samples from v->dev (a grid) or from the lowest pointer of the list; pitch[i] and
+ * step[i]: the signed row pitch and pixel step with which the picture is walked from there (negative where the flag is set).
+ * Each of the three may be NULL.  A view of 4-byte samples is taken for fp32 samples. */
+int dwtx_view_flip_plan(const dwtx_view *v, size_t pixel_step, int W, int H, int n, const void *const *host_windows,
+	int flip, const unsigned char *host_flips, int dst, long long *origin /* [n] */, long long *pitch /* [n] */, long long *step /* [n] */);
+
 /* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
  * interior, right column, bottom row, corner, in that order, those that exist — each a cols x rows grid of W x H tiles
  * whose first tile's corner is (x0, y0): one dwtx_encode_view / dwtx_decode_view call per group.  Per axis, with
