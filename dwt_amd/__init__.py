@@ -483,8 +483,9 @@ class Context:
         streams = [out[i, : lens[i]].tobytes() for i in range(n)]
         return (streams[0], stats[0]) if single else (streams, list(stats))
 
-    def _decode(self, sym, dtype, streams, pixels_max, maxval=None):
-        """maxval None: bytes; else deep pixels, whose symbol takes maxval and (unused here) an array of DecodeInfo."""
+    def _decode(self, sym, dtype, streams, pixels_max, maxval=None, minval=None):
+        """maxval None: bytes; else deep pixels, whose symbol takes maxval (signed ones: minval before it) and (unused here)
+        an array of DecodeInfo."""
         import numpy as np
 
         single = isinstance(streams, (bytes, bytearray))
@@ -503,7 +504,7 @@ class Context:
         pstride = W * H * Cn
         pix = np.empty((n, pstride), dtype=dtype)
         ow, oh, oc = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        sizes = (ow, oh, oc) if maxval is None else (maxval, ow, oh, oc, None)
+        sizes = (ow, oh, oc) if maxval is None else (maxval, ow, oh, oc, None) if minval is None else (minval, maxval, ow, oh, oc, None)
         rc = getattr(self.lib, sym)(self.h, host.ctypes.data, stride, C.cast(lens, C.c_void_p), n, pixels_max,
                                     pix.ctypes.data, pstride, *sizes)
         if rc == -1 and n == 1:   # one unreadable stream is an error code (decode.c exits 1), in a batch it is a missing picture
@@ -633,6 +634,23 @@ class Context:
 
         return self._decode("dwtx_decode_images16", np.uint16, streams, pixels_max, maxval)
 
+    def encode16s(self, pix, capacity=0):
+        """int16 numpy [n,H,W,C] (or [H,W,C]) -> list of .dwt byte strings, list of Stats: dwtx_encode_images_s16, the signed
+        integers coded as they are.  A picture that needs more than 16 bit planes raises DwtxError (rc -3)."""
+        import numpy as np
+
+        if np.asarray(pix).dtype != np.int16:
+            raise ValueError(f"encode16s reads int16 pictures, not {np.asarray(pix).dtype}")
+        return self._encode("dwtx_encode_images_s16", np.int16, self.lib.dwtx_encode_bound16, pix, capacity)
+
+    def decode16s(self, streams, minval=-32768, maxval=32767, pixels_max=-1):
+        """.dwt byte string (or list of same-geometry ones) -> int16 numpy [h,w,C] (or list); None if unreadable:
+        dwtx_decode_images_s16.  [minval, maxval] is the range the pictures were encoded from (a .dwt does not record it):
+        what the clamps of a stream that was cut short act at."""
+        import numpy as np
+
+        return self._decode("dwtx_decode_images_s16", np.int16, streams, pixels_max, int(maxval), int(minval))
+
     def encode_device16(self, pix, capacity=0, out=None, info=None):
         """16-bit device tensor [n,H,W,C] -> (streams uint8 [n,stride], info uint8 [n,sizeof(StreamInfo)]) on device; async."""
         assert self._is16(pix)
@@ -645,7 +663,21 @@ class Context:
 
     # -- strided views: windows and tile grids of a larger frame (dwtx_encode_view / dwtx_decode_view) -----------
 
-    def _view(self, t, maxval, stepped=False, floats=False):
+    def _signed_range(self, signed, minval, maxval, floats=False):
+        """The `signed`, `minval` and `maxval` keywords of the view calls -> (minval or None, maxval or None): minval None means
+        the unsigned call.  signed=True: int16 samples, range [-32768, 32767] unless the keywords say otherwise; float tensors
+        take minval alone (0 or None: the unsigned call)."""
+        if signed:
+            if floats:
+                raise ValueError("signed=True takes int16 tensors; float tensors take minval=")
+            return (-32768 if minval is None else int(minval)), (32767 if maxval is None else int(maxval))
+        if minval is not None and int(minval) != 0:
+            if not floats:
+                raise ValueError("minval belongs to signed=True (int16 tensors) and to float tensors")
+            return int(minval), maxval
+        return None, maxval
+
+    def _view(self, t, maxval, stepped=False, floats=False, signed=False):
         """View of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (uint8, or uint16 / int16 for deep pixels):
         the windows stay where they are.  RGB pixels are interleaved (channel stride 1, column stride 3) or planar (column
         stride 1, any channel stride): `nchw.permute(0, 2, 3, 1)` and `chw.permute(1, 2, 0)` are views as they are.
@@ -654,6 +686,8 @@ class Context:
         if floats:   # (decode_view_float, encode_view_float: the same views of float32 / float16 / bfloat16 samples)
             if t.dtype not in (torch.float32, torch.float16, torch.bfloat16) or t.device != self.device or t.dim() not in (4, 5):
                 raise ValueError("a float view needs a float32 / float16 / bfloat16 tensor [n,H,W,C] or [bands,cols,H,W,C] on the context's device")
+        elif signed and t.dtype != torch.int16:
+            raise ValueError(f"signed=True takes int16 tensors only, not {t.dtype}")
         elif t.dtype not in (torch.uint8, torch.uint16, torch.int16) or t.device != self.device or t.dim() not in (4, 5):
             raise ValueError("a view needs a uint8 / uint16 / int16 tensor [n,H,W,C] or [bands,cols,H,W,C] on the context's device")
         f = view_fields(tuple(t.shape), tuple(t.stride()), stepped)
@@ -664,7 +698,7 @@ class Context:
                  f["channel_stride"])
         return v, f["W"], f["H"], f["channels"], f["n"], f["pixel_step"]
 
-    def encode_view(self, t, capacity=0, out=None, info=None, stepped=False, order="rgb", flip=None):
+    def encode_view(self, t, capacity=0, out=None, info=None, stepped=False, order="rgb", flip=None, signed=False):
         """dwtx_encode_view: the windows of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (a slice, a crop, a
         grid of tiles, a channel-first batch permuted to channel-last: see _view) -> (streams uint8 [n,stride], info uint8
         [n,sizeof(StreamInfo)]) on device, as encode_device / encode_device16 give for the contiguous copy; async.
@@ -672,10 +706,14 @@ class Context:
         order="bgr": dwtx_encode_view_order — the channels lie as B, G, R (`bgra[..., :3]` with stepped=True, an OpenCV
         frame, planar B, G, R planes); the streams are those of the R, G, B picture.
         flip: dwtx_encode_view_flip — "y" for bottom-up surfaces, "x" for mirrored ones, "xy", or one of those per window
-        (view_flips); the streams are those of `t.flip(...)` of each window, which is never built."""
+        (view_flips); the streams are those of `t.flip(...)` of each window, which is never built.
+        signed=True: dwtx_encode_view_signed — an int16 tensor (nothing else) whose samples are the signed integers they
+        look like: CT slices in Hounsfield units, elevation tiles, residuals; every other keyword keeps its meaning.
+        Without it an int16 tensor stays what it has always been here: the carrier of uint16 bytes (torch's uint16 has few
+        operators on the device), so that a picture that crosses zero is read as one that jumps by 65535 there."""
         order = view_order(order)
         torch = self.torch
-        v, W, H, Cn, n, step = self._view(t, None, stepped)
+        v, W, H, Cn, n, step = self._view(t, None, stepped, signed=signed)
         flips = view_flips(flip, n)
         bound = self.lib.dwtx_encode_bound16 if v.sample_bytes == 2 else self.lib.dwtx_encode_bound
         stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
@@ -683,7 +721,11 @@ class Context:
             out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         if info is None:
             info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
-        if flips:
+        if signed:
+            fl = flips or (0, None)
+            _check(self.lib.dwtx_encode_view_signed(self.h, C.byref(v), step, order, None, None, fl[0], fl[1], 0, W, H, n, capacity, _ptr(out),
+                                                    out.shape[1], _ptr(info)), "dwtx_encode_view_signed")
+        elif flips:
             _check(self.lib.dwtx_encode_view_flip(self.h, C.byref(v), step, order, None, None, flips[0], flips[1], W, H, n, capacity, _ptr(out),
                                                   out.shape[1], _ptr(info)), "dwtx_encode_view_flip")
         elif order:
@@ -696,14 +738,16 @@ class Context:
             _check(self.lib.dwtx_encode_view(self.h, C.byref(v), W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view")
         return out, info
 
-    def encode_view_float(self, t, maxval=255, scale=1.0, bias=0.0, capacity=0, out=None, info=None, stepped=False, order="rgb", flip=None):
+    def encode_view_float(self, t, maxval=255, scale=1.0, bias=0.0, capacity=0, out=None, info=None, stepped=False, order="rgb", flip=None,
+                          minval=0):
         """dwtx_encode_view_float: encode_view of a float32 / float16 / bfloat16 strided device tensor (the shapes and
         strides encode_view takes, stepped and order="bgr" included).  The picture that is coded is, per sample,
         `(x.float() * scale + bias).round().clamp(0, maxval)` — two float32 roundings, ties to even, NaN -> 0 — and the
         streams are those of encode_device (maxval <= 255) or encode_device16 (above) on that picture; async.  scale,
         bias: a number, or three, per colour R, G, B.  Returns (streams, info) like encode_view.  A tensor that holds no
         floats, a wrong length of scale or bias and values that are not finite raise ValueError before any device call.
-        flip: encode_view's keyword."""
+        flip: encode_view's keyword.  minval (other than 0): dwtx_encode_view_signed — the clamp is `.clamp(minval, maxval)`,
+        -32768 <= minval < maxval <= 32767, and the streams are those of the signed integer picture."""
         order = view_order(order)
         torch = self.torch
         if not hasattr(t, "dtype") or t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
@@ -711,12 +755,18 @@ class Context:
         fmt = float_format(t.dtype, scale, bias)
         v, W, H, Cn, n, step = self._view(t, int(maxval), stepped, floats=True)
         flips = view_flips(flip, n)
-        bound = self.lib.dwtx_encode_bound16 if int(maxval) > 255 else self.lib.dwtx_encode_bound
+        lo = self._signed_range(False, minval, maxval, floats=True)[0]
+        bound = self.lib.dwtx_encode_bound16 if int(maxval) > 255 or lo is not None else self.lib.dwtx_encode_bound
         stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
         if out is None:
             out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         if info is None:
             info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
+        if lo is not None:
+            fl = flips or (0, None)
+            _check(self.lib.dwtx_encode_view_signed(self.h, C.byref(v), step, order, C.byref(fmt), None, fl[0], fl[1], lo, W, H, n, capacity,
+                                                    _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view_signed")
+            return out, info
         if flips:
             _check(self.lib.dwtx_encode_view_flip(self.h, C.byref(v), step, order, C.byref(fmt), None, flips[0], flips[1], W, H, n, capacity,
                                                   _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view_flip")
@@ -725,7 +775,7 @@ class Context:
                                                _ptr(info)), "dwtx_encode_view_float")
         return out, info
 
-    def decode_view(self, streams, lens, into, maxval=None, levels_max=-1, stepped=False, order="rgb", flip=None):
+    def decode_view(self, streams, lens, into, maxval=None, levels_max=-1, stepped=False, order="rgb", flip=None, signed=False, minval=None):
         """dwtx_decode_view: device streams [n,stride] + int64 lens -> the windows of the strided device tensor `into`
         ([n,H,W,C] or [bands,cols,H,W,C]), each picture in its window's top-left corner at the size its stream supports;
         nothing else of `into`'s storage is written.  maxval: the deep pictures' (default 65535).  Returns the list of
@@ -733,15 +783,23 @@ class Context:
         samples between the pixels (an RGBA surface's alpha) are not written either.  order="bgr": dwtx_decode_view_order —
         R and B are written at each other's places.  flip: dwtx_decode_view_flip — "x", "y", "xy" or one of those per window
         (view_flips): each window holds what `.flip(...)` of the unflipped result would, and a reduced picture lies in the
-        corner where its pixel (0, 0) lies."""
+        corner where its pixel (0, 0) lies.
+        signed=True: dwtx_decode_view_signed — `into` is an int16 tensor (nothing else) that receives signed samples;
+        [minval, maxval] (defaults -32768 and 32767) is the range the pictures were encoded from, what the clamps of a stream
+        that was cut short act at.  Without it an int16 tensor is the carrier of uint16 bytes, as for encode_view."""
         order = view_order(order)
         torch = self.torch
-        v, W, H, Cn, n, step = self._view(into, maxval, stepped)
+        lo, maxval = self._signed_range(signed, minval, maxval)
+        v, W, H, Cn, n, step = self._view(into, maxval, stepped, signed=signed)
         flips = view_flips(flip, n)
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
         assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
         infos = (DecodeInfo * n)()
-        if flips:
+        if signed:
+            fl = flips or (0, None)
+            _check(self.lib.dwtx_decode_view_signed(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
+                                                    None, W, H, None, None, fl[0], fl[1], lo, C.cast(infos, C.c_void_p)), "dwtx_decode_view_signed")
+        elif flips:
             _check(self.lib.dwtx_decode_view_flip(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
                                                   None, W, H, None, None, flips[0], flips[1], C.cast(infos, C.c_void_p)), "dwtx_decode_view_flip")
         elif order:
@@ -755,7 +813,8 @@ class Context:
                                              C.cast(infos, C.c_void_p)), "dwtx_decode_view")
         return list(infos)
 
-    def decode_view_float(self, streams, lens, into, maxval=255, scale=1.0, bias=0.0, levels_max=-1, stepped=False, order="rgb", flip=None):
+    def decode_view_float(self, streams, lens, into, maxval=255, scale=1.0, bias=0.0, levels_max=-1, stepped=False, order="rgb", flip=None,
+                          minval=0):
         """dwtx_decode_view_float: decode_view into a float32 / float16 / bfloat16 strided device tensor `into` (the shapes
         and strides decode_view takes, stepped and order="bgr" included): every sample decode_view would write becomes
         `v * scale + bias` — two float32 roundings, then the tensor's dtype, bit for bit torch's unfused
@@ -763,7 +822,9 @@ class Context:
         written.  maxval: what the streams were encoded from (255, or a deep picture's).  scale, bias: a number, or three,
         per colour R, G, B.  Returns the list of DecodeInfo; syncs once.  A wrong dtype, a wrong length of scale or bias
         and values that are not finite raise ValueError before any device call.  flip: decode_view's keyword (a loader's
-        per-picture horizontal flip: a sequence of 0 and "x")."""
+        per-picture horizontal flip: a sequence of 0 and "x").  minval (other than 0): dwtx_decode_view_signed — the streams
+        hold signed pictures of the range [minval, maxval], and v is the signed, clamped integer (a CT slice straight into
+        float16 Hounsfield units)."""
         order = view_order(order)
         torch = self.torch
         if not hasattr(into, "dtype") or into.dtype not in (torch.float32, torch.float16, torch.bfloat16):
@@ -771,9 +832,16 @@ class Context:
         fmt = float_format(into.dtype, scale, bias)
         v, W, H, Cn, n, step = self._view(into, int(maxval), stepped, floats=True)
         flips = view_flips(flip, n)
+        lo = self._signed_range(False, minval, maxval, floats=True)[0]
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
         assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
         infos = (DecodeInfo * n)()
+        if lo is not None:
+            fl = flips or (0, None)
+            _check(self.lib.dwtx_decode_view_signed(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
+                                                    C.byref(fmt), W, H, None, None, fl[0], fl[1], lo, C.cast(infos, C.c_void_p)),
+                   "dwtx_decode_view_signed")
+            return list(infos)
         if flips:
             _check(self.lib.dwtx_decode_view_flip(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
                                                   C.byref(fmt), W, H, None, None, flips[0], flips[1], C.cast(infos, C.c_void_p)),
@@ -784,12 +852,13 @@ class Context:
         return list(infos)
 
     def decode_view_crop(self, streams, lens, into, size, origins=None, maxval=None, scale=None, bias=None, levels_max=-1, stepped=False,
-                         order="rgb", flip=None):
+                         order="rgb", flip=None, signed=False, minval=None):
         """dwtx_decode_view_crop: decode_view — or decode_view_float, when `into` is a float tensor — of a window of each
         picture: `into` holds windows of the crop's size ([n,ch,cw,C] or [bands,cols,ch,cw,C], any strides decode_view takes),
         size=(W, H) is the streams' geometry, origins a sequence of n (x0, y0) pairs, one pair for all, or None for (0, 0).
         Window i receives the picture's samples from (x0_i, y0_i) on, as far as the stream supports them, and nothing else of
         `into`'s storage is written.  scale, bias: float tensors only.  flip: decode_view's keyword — the crop is flipped inside its window.
+        signed, minval: decode_view's keywords (int16 tensors), and decode_view_float's minval for float tensors.
         Returns the list of DecodeInfo; syncs once."""
         order = view_order(order)
         torch = self.torch
@@ -800,7 +869,8 @@ class Context:
         fmt = float_format(into.dtype, 1.0 if scale is None else scale, 0.0 if bias is None else bias) if floats else None
         if floats and maxval is None:
             maxval = 255
-        v, cw, ch, Cn, n, step = self._view(into, None if maxval is None else int(maxval), stepped, floats=floats)
+        lo, maxval = self._signed_range(signed, minval, maxval, floats=floats)
+        v, cw, ch, Cn, n, step = self._view(into, None if maxval is None else int(maxval), stepped, floats=floats, signed=signed)
         flips = view_flips(flip, n)
         org = None
         if origins is not None:
@@ -812,6 +882,12 @@ class Context:
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
         assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
         infos = (DecodeInfo * n)()
+        if lo is not None:
+            fl = flips or (0, None)
+            _check(self.lib.dwtx_decode_view_signed(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
+                                                    C.byref(fmt) if fmt is not None else None, cw, ch, org, None, fl[0], fl[1], lo,
+                                                    C.cast(infos, C.c_void_p)), "dwtx_decode_view_signed")
+            return list(infos)
         if flips:
             _check(self.lib.dwtx_decode_view_flip(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
                                                   C.byref(fmt) if fmt is not None else None, cw, ch, org, None, flips[0], flips[1],
@@ -824,13 +900,15 @@ class Context:
 
     # -- window lists: one pointer per picture (dwtx_encode_view_list / dwtx_decode_view_list) ------------------------
 
-    def _view_list(self, windows, maxval, stepped):
+    def _view_list(self, windows, maxval, stepped, signed=False):
         """The View (dev NULL), the ctypes array of the windows' pointers and the fields of a list of device tensors [H,W,C]
         (view_list_fields); floats: whether they hold float samples, and then their FloatFormat's dtype."""
         torch = self.torch
         f, ptrs = view_list_fields(windows, stepped)
         t0 = windows[0]
         floats = t0.dtype in (torch.float32, torch.float16, torch.bfloat16)
+        if signed and t0.dtype != torch.int16:
+            raise ValueError(f"signed=True takes int16 tensors only, not {t0.dtype}")
         if (not floats and t0.dtype not in (torch.uint8, torch.uint16, torch.int16)) or t0.device != self.device:
             raise ValueError("a window list holds uint8, uint16 / int16 or float32 / float16 / bfloat16 tensors [H,W,C] on the context's device")
         if maxval is None:
@@ -839,28 +917,36 @@ class Context:
         return v, (C.c_void_p * len(ptrs))(*ptrs), f, floats
 
     def encode_view_list(self, windows, maxval=None, scale=None, bias=None, capacity=0, out=None, info=None, stepped=False, order="rgb",
-                         flip=None):
+                         flip=None, signed=False, minval=None):
         """dwtx_encode_view_list: encode_view — or encode_view_float, when the windows are float tensors — of a sequence of n
         device tensors [H,W,C] that lie wherever they lie: separately allocated pictures, boxes of a frame, tiles in any
         order, permuted [C,H,W] tensors; one shape, one set of strides, one dtype (view_list_fields).  Windows may overlap
         and repeat.  No stack is built: the library reads each window in place.  maxval (float windows: the quantiser's
-        clamp, default 255), scale, bias: as for encode_view_float; stepped, order, flip: as for encode_view.  Returns
-        (streams, info) like encode_view; async."""
+        clamp, default 255), scale, bias: as for encode_view_float; stepped, order, flip: as for encode_view.  signed: as for
+        encode_view (int16 windows); minval: as for encode_view_float (float windows).  Returns (streams, info) like
+        encode_view; async."""
         order = view_order(order)
         torch = self.torch
-        v, arr, f, floats = self._view_list(windows, maxval, stepped)
+        v, arr, f, floats = self._view_list(windows, maxval, stepped, signed)
+        lo = self._signed_range(signed, minval, maxval, floats=floats)[0]
         if not floats and (scale is not None or bias is not None):
             raise ValueError("scale and bias belong to float tensors")
         fmt = float_format(windows[0].dtype, 1.0 if scale is None else scale, 0.0 if bias is None else bias) if floats else None
         W, H, Cn, n = f["W"], f["H"], f["channels"], f["n"]
         flips = view_flips(flip, n)
-        deep = v.maxval > 255 if floats else v.sample_bytes == 2
+        deep = (v.maxval > 255 or lo is not None) if floats else v.sample_bytes == 2
         bound = self.lib.dwtx_encode_bound16 if deep else self.lib.dwtx_encode_bound
         stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
         if out is None:
             out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         if info is None:
             info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
+        if lo is not None:
+            fl = flips or (0, None)
+            _check(self.lib.dwtx_encode_view_signed(self.h, C.byref(v), f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, arr,
+                                                    fl[0], fl[1], lo if floats else 0, W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
+                   "dwtx_encode_view_signed")
+            return out, info
         if flips:
             _check(self.lib.dwtx_encode_view_flip(self.h, C.byref(v), f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, arr,
                                                   flips[0], flips[1], W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
@@ -871,15 +957,18 @@ class Context:
         return out, info
 
     def decode_view_list(self, streams, lens, windows, size=None, origins=None, maxval=None, scale=None, bias=None, levels_max=-1,
-                         stepped=False, order="rgb", flip=None):
+                         stepped=False, order="rgb", flip=None, signed=False, minval=None):
         """dwtx_decode_view_list: decode_view_crop into a sequence of n device tensors [H,W,C] that lie wherever they lie (the
         lists encode_view_list takes), which must be provably disjoint (include/dwtx.h).  size=None: whole pictures of the
         windows' size; else size=(W, H) is the streams' geometry, the windows are crops of it and origins their (x0, y0), as for
         decode_view_crop.  Float windows are written as decode_view_float writes them (maxval, scale, bias).  Nothing but
-        the windows' samples is written.  flip: decode_view's keyword.  Returns the list of DecodeInfo; syncs once."""
+        the windows' samples is written.  flip: decode_view's keyword.  signed, minval: decode_view's keywords (int16 windows),
+        and decode_view_float's minval for float windows.  Returns the list of DecodeInfo; syncs once."""
         order = view_order(order)
         torch = self.torch
-        v, arr, f, floats = self._view_list(windows, maxval, stepped)
+        floats_ = windows[0].dtype in (torch.float32, torch.float16, torch.bfloat16)
+        lo, maxval = self._signed_range(signed, minval, maxval, floats=floats_)
+        v, arr, f, floats = self._view_list(windows, maxval, stepped, signed)
         if not floats and (scale is not None or bias is not None):
             raise ValueError("scale and bias belong to float tensors")
         fmt = float_format(windows[0].dtype, 1.0 if scale is None else scale, 0.0 if bias is None else bias) if floats else None
@@ -896,6 +985,12 @@ class Context:
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
         assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
         infos = (DecodeInfo * n)()
+        if lo is not None:
+            fl = flips or (0, None)
+            _check(self.lib.dwtx_decode_view_signed(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
+                                                    f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, cw, ch, org, arr,
+                                                    fl[0], fl[1], lo, C.cast(infos, C.c_void_p)), "dwtx_decode_view_signed")
+            return list(infos)
         if flips:
             _check(self.lib.dwtx_decode_view_flip(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
                                                   f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, cw, ch, org, arr,

@@ -166,6 +166,13 @@ SYMBOLS = {
                                    C.POINTER(_vp), _i, C.POINTER(C.c_ubyte), _vp]),
     "dwtx_view_flip_plan": (_i, [C.POINTER(View), _sz, _i, _i, _i, C.POINTER(_vp), _i, C.POINTER(C.c_ubyte), _i, C.POINTER(C.c_longlong),
                                  C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    # signed samples: the flip calls plus minval; the host pair with int16 pixels
+    "dwtx_encode_view_signed": (_i, [_vp, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), C.POINTER(_vp), _i, C.POINTER(C.c_ubyte), _i, _i, _i, _i,
+                                     C.c_long, _vp, _sz, _vp]),
+    "dwtx_decode_view_signed": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, C.POINTER(View), _sz, _i, C.POINTER(FloatFormat), _i, _i, C.POINTER(_i),
+                                     C.POINTER(_vp), _i, C.POINTER(C.c_ubyte), _i, _vp]),
+    "dwtx_encode_images_s16": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp, _vp]),
+    "dwtx_decode_images_s16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     "dwtx_tile_groups": (_i, [_i, _i, _i, C.POINTER(TileGroup)]),
     "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }

@@ -284,7 +284,7 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 	const int C = px.channels;
 	if (!ctx || !dev_streams || !dev_lens || !px.base || !host_info || n < 1 || !px.sample_aligned())
 		return DWTX_ERR_ARG;
-	if (!dwtx_maxval_ok(px.maxval) || !dwtx_count_ok(n, DWTX_MAX_PLANES_PER_CALL / 3, "streams to decode"))   // (before any scratch is asked for)
+	if (!px.range_ok() || !dwtx_count_ok(n, DWTX_MAX_PLANES_PER_CALL / 3, "streams to decode"))   // (before any scratch is asked for)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	DWTX_CHECK_DIMS(W, H);
@@ -458,6 +458,9 @@ extern "C" int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, s
 // list (the *_view_list calls; the others pass none): the windows lie where list->windows says; the view's dev, cols,
 // image_stride and band_stride are not looked at, every other check is the grid's, and list_windows takes the place of the
 // rules about where the windows lie.  px->offs is not set yet: the caller brings list->offs to the device (send_list).
+// minval (the *_view_signed calls; the others pass none): integer samples are int16_t (sample_bytes 2, nothing else), coded as
+// they are, and a destination's range is [*minval, maxval] (dwtx_range_ok); float samples with *minval != 0 get that range as
+// their lower bound too (a source's: checked by the caller, source_range_ok), with *minval == 0 they are the unsigned call's.
 struct WinList {
 	const void *const *windows;   // [n] device pointers in host memory
 	std::vector<long long> offs;  // out: each window's first sample, in samples from the lowest pointer
@@ -465,8 +468,9 @@ struct WinList {
 static int list_windows(const dwtx_view *v, size_t cs, size_t row, int H, int n, bool dst, WinList *list, dwtx_pixels *px);
 
 static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, dwtx_pixels *px, int kind = -1, bool window = false,
-	WinList *list = nullptr)
+	WinList *list = nullptr, const int *minval = nullptr)
 {
+	const bool sgn = minval && (kind < 0 || *minval != 0);
 	if (order != DWTX_ORDER_RGB && order != DWTX_ORDER_BGR) {
 		dwtx_set_error("view: channel order %d (DWTX_ORDER_RGB = 0 or DWTX_ORDER_BGR = 1)", order);
 		return DWTX_ERR_ARG;
@@ -491,6 +495,10 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 		dwtx_set_error("view: sample_bytes %d (1 or 2), channels %d (1 or 3), cols %d (>= 0)", v->sample_bytes, v->channels, v->cols);
 		return DWTX_ERR_ARG;
 	}
+	if (sgn && kind < 0 && v->sample_bytes != 2) {
+		dwtx_set_error("view: signed integer samples are int16_t: sample_bytes %d (2)", v->sample_bytes);
+		return DWTX_ERR_ARG;
+	}
 	const size_t cs = v->channels == 3 ? v->channel_stride : 0;   // planar RGB; a gray view has no use for it
 	const size_t step = pixel_step == (size_t)v->channels ? 0 : pixel_step;
 	if (step && (step < (size_t)v->channels || step > 0x7fffffffu)) {
@@ -513,7 +521,10 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 	}
 	const size_t cols = list ? (size_t)n : v->cols && v->cols < n ? (size_t)v->cols : (size_t)n;
 	const bool bands = cols < (size_t)n;
-	if (dst && (v->sample_bytes == 1 ? v->maxval != 255 : !dwtx_maxval_ok(v->maxval))) {
+	if (dst && sgn) {
+		if (!dwtx_range_ok(*minval, v->maxval))
+			return DWTX_ERR_ARG;
+	} else if (dst && (v->sample_bytes == 1 ? v->maxval != 255 : !dwtx_maxval_ok(v->maxval))) {
 		if (v->sample_bytes == 1)
 			dwtx_set_error("view: maxval %d with 1-byte samples (255)", v->maxval);
 		return DWTX_ERR_ARG;
@@ -547,8 +558,11 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 	}
 	const size_t image_stride = list ? 0 : v->image_stride;
 	*px = kind >= 0            ? dwtx_pixels_float(v->dev, kind, v->channels, image_stride, v->maxval)
+		: sgn                  ? dwtx_pixels_s16((const int16_t *)v->dev, v->channels, image_stride, dst ? *minval : -32768, dst ? v->maxval : 32767)
 		: v->sample_bytes == 1 ? dwtx_pixels8((const uint8_t *)v->dev, v->channels, image_stride)
 		                       : dwtx_pixels16((const uint16_t *)v->dev, v->channels, image_stride, dst ? v->maxval : 65535);
+	if (sgn && kind >= 0)
+		px->minval = *minval;
 	px->row_pitch = v->row_pitch;
 	px->channel_stride = cs;
 	px->pixel_step = step;
@@ -695,23 +709,39 @@ extern "C" int dwtx_decode_view_step(dwtx_ctx *ctx, const uint8_t *dev_streams, 
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
 }
 
+// The view calls from here on are one body each for the unsigned entry point and for its way through dwtx_encode_view_signed /
+// dwtx_decode_view_signed (further down): `minval` is null in the former and the signed call's lower bound in the latter —
+// what pixels_of_view makes of it is all that differs.
+static int encode_view_order(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, int W, int H, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, const int *minval)
+{
+	dwtx_pixels px;
+	if (const int rc = pixels_of_view(src, pixel_step, order, W, H, n, false, &px, -1, false, nullptr, minval))
+		return rc;
+	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
+}
+
 extern "C" int dwtx_encode_view_order(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, int W, int H, int n, long capacity,
 	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
 {
+	return encode_view_order(ctx, src, pixel_step, order, W, H, n, capacity, dev_out, out_stride, dev_info, nullptr);
+}
+
+static int decode_view_order(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
+	dwtx_decode_info *host_info, const int *minval)
+{
 	dwtx_pixels px;
-	if (const int rc = pixels_of_view(src, pixel_step, order, W, H, n, false, &px))
+	if (const int rc = pixels_of_view(dst, pixel_step, order, W, H, n, true, &px, -1, false, nullptr, minval))
 		return rc;
-	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
 }
 
 extern "C" int dwtx_decode_view_order(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
 	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
 	dwtx_decode_info *host_info)
 {
-	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, pixel_step, order, W, H, n, true, &px))
-		return rc;
-	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
+	return decode_view_order(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, host_info, nullptr);
 }
 
 // dwtx_float_format -> the sample kind of dwtx_pixels, checked (what both float calls refuse alike)
@@ -742,18 +772,31 @@ static void set_float_format(dwtx_pixels *px, const dwtx_float_format *fmt)
 	}
 }
 
-extern "C" int dwtx_decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+// the quantiser's clamp of a float source: maxval alone, or the range of a signed call with a lower bound other than 0
+static bool source_range_ok(const dwtx_view *src, const int *minval)
+{
+	return minval && *minval ? dwtx_range_ok(*minval, src->maxval) : dwtx_maxval_ok(src->maxval);
+}
+
+static int decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
 	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
-	const dwtx_float_format *fmt, dwtx_decode_info *host_info)
+	const dwtx_float_format *fmt, dwtx_decode_info *host_info, const int *minval)
 {
 	int kind;
 	if (const int rc = float_kind(fmt, &kind))
 		return rc;
 	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, pixel_step, order, W, H, n, true, &px, kind))
+	if (const int rc = pixels_of_view(dst, pixel_step, order, W, H, n, true, &px, kind, false, nullptr, minval))
 		return rc;
 	set_float_format(&px, fmt);
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
+}
+
+extern "C" int dwtx_decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
+	const dwtx_float_format *fmt, dwtx_decode_info *host_info)
+{
+	return decode_view_float(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, host_info, nullptr);
 }
 
 extern "C" int dwtx_crop_plan(int W, int H, int x0, int y0, int cw, int ch, dwtx_crop_rect out[DWTX_MAX_LEVELS + 1])
@@ -803,22 +846,22 @@ static int crop_of_call(int W, int H, int n, int crop_w, int crop_h, const int *
 	return DWTX_OK;
 }
 
-extern "C" int dwtx_decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+static int decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
 	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int crop_w, int crop_h, const int *host_origins, dwtx_decode_info *host_info)
+	int crop_w, int crop_h, const int *host_origins, dwtx_decode_info *host_info, const int *minval)
 {
 	bool whole;
 	if (const int rc = crop_of_call(W, H, n, crop_w, crop_h, host_origins, &whole))
 		return rc;
 	if (whole)   // the plain call, on its own path
-		return fmt ? dwtx_decode_view_float(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, host_info)
-		           : dwtx_decode_view_order(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, host_info);
+		return fmt ? decode_view_float(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, host_info, minval)
+		           : decode_view_order(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, host_info, minval);
 	int kind = -1;
 	if (fmt)
 		if (const int rc = float_kind(fmt, &kind))
 			return rc;
 	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, pixel_step, order, crop_w, crop_h, n, true, &px, kind, true))
+	if (const int rc = pixels_of_view(dst, pixel_step, order, crop_w, crop_h, n, true, &px, kind, true, nullptr, minval))
 		return rc;
 	if (fmt)
 		set_float_format(&px, fmt);
@@ -826,22 +869,36 @@ extern "C" int dwtx_decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, 
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info, &crop);
 }
 
+extern "C" int dwtx_decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, dwtx_decode_info *host_info)
+{
+	return decode_view_crop(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h, host_origins,
+		host_info, nullptr);
+}
+
 // The source's maxval is the quantiser's clamp (the one encode that reads it): up to 255 the picture is one of bytes and takes
 // their route, beyond it a deep picture's (dwtx_pixels::deep_source()); the streams are those of dwtx_encode_device /
 // dwtx_encode_device16 on the quantised picture either way.
-extern "C" int dwtx_encode_view_float(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+static int encode_view_float(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, const int *minval)
 {
 	int kind;
 	if (const int rc = float_kind(fmt, &kind))
 		return rc;
 	dwtx_pixels px;
-	if (const int rc = pixels_of_view(src, pixel_step, order, W, H, n, false, &px, kind))
+	if (const int rc = pixels_of_view(src, pixel_step, order, W, H, n, false, &px, kind, false, nullptr, minval))
 		return rc;
-	if (!dwtx_maxval_ok(src->maxval))
+	if (!source_range_ok(src, minval))
 		return DWTX_ERR_ARG;
 	set_float_format(&px, fmt);
 	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
+}
+
+extern "C" int dwtx_encode_view_float(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	return encode_view_float(ctx, src, pixel_step, order, fmt, W, H, n, capacity, dev_out, out_stride, dev_info, nullptr);
 }
 
 // ---- window lists (include/dwtx.h): one pointer per picture --------------------------------------------------------------
@@ -854,8 +911,9 @@ extern "C" int dwtx_view_list_check(const dwtx_view *v, size_t pixel_step, int W
 	return pixels_of_view(v, pixel_step, DWTX_ORDER_RGB, W, H, n, dst != 0, &px, v && v->sample_bytes == 4 ? DWTX_SAMPLE_F32 : -1, true, &list);
 }
 
-extern "C" int dwtx_encode_view_list(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	const void *const *host_windows, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+static int encode_view_list(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	const void *const *host_windows, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info,
+	const int *minval)
 {
 	if (!ctx || !dev_out || !dev_info)
 		return DWTX_ERR_ARG;
@@ -865,10 +923,10 @@ extern "C" int dwtx_encode_view_list(dwtx_ctx *ctx, const dwtx_view *src, size_t
 			return rc;
 	WinList list{ host_windows, {} };
 	dwtx_pixels px;
-	if (const int rc = pixels_of_view(src, pixel_step, order, W, H, n, false, &px, kind, false, &list))
+	if (const int rc = pixels_of_view(src, pixel_step, order, W, H, n, false, &px, kind, false, &list, minval))
 		return rc;
 	if (fmt) {
-		if (!dwtx_maxval_ok(src->maxval))
+		if (!source_range_ok(src, minval))
 			return DWTX_ERR_ARG;
 		set_float_format(&px, fmt);
 	}
@@ -877,9 +935,15 @@ extern "C" int dwtx_encode_view_list(dwtx_ctx *ctx, const dwtx_view *src, size_t
 	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx->enc_index);
 }
 
-extern "C" int dwtx_decode_view_list(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+extern "C" int dwtx_encode_view_list(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	const void *const *host_windows, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	return encode_view_list(ctx, src, pixel_step, order, fmt, host_windows, W, H, n, capacity, dev_out, out_stride, dev_info, nullptr);
+}
+
+static int decode_view_list(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
 	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, dwtx_decode_info *host_info)
+	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, dwtx_decode_info *host_info, const int *minval)
 {
 	if (!ctx || !dev_streams || !dev_lens || !host_info)
 		return DWTX_ERR_ARG;
@@ -892,7 +956,7 @@ extern "C" int dwtx_decode_view_list(dwtx_ctx *ctx, const uint8_t *dev_streams, 
 			return rc;
 	WinList list{ host_windows, {} };
 	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, pixel_step, order, crop_w, crop_h, n, true, &px, kind, !whole, &list))
+	if (const int rc = pixels_of_view(dst, pixel_step, order, crop_w, crop_h, n, true, &px, kind, !whole, &list, minval))
 		return rc;
 	if (fmt)
 		set_float_format(&px, fmt);
@@ -902,6 +966,14 @@ extern "C" int dwtx_decode_view_list(dwtx_ctx *ctx, const uint8_t *dev_streams, 
 		return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
 	const CropCall crop = { crop_w, crop_h, host_origins };
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info, &crop);
+}
+
+extern "C" int dwtx_decode_view_list(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, dwtx_decode_info *host_info)
+{
+	return decode_view_list(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h, host_origins,
+		host_windows, host_info, nullptr);
 }
 
 // ---- flips in views (include/dwtx.h): a mask of DWTX_FLIP_X and DWTX_FLIP_Y per window ---------------------------------------
@@ -943,14 +1015,14 @@ static int flip_flags(int n, int flip, const unsigned char *host_flips, std::vec
 // and then spelled out — list->offs from v->dev, px a listed view — so that every flipped call travels as a listed one.
 // px->offs is not set yet and list->offs carries no flags yet (flip_entries)
 static int flipped_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, int kind, bool window,
-	const void *const *windows, WinList *list, dwtx_pixels *px)
+	const void *const *windows, WinList *list, dwtx_pixels *px, const int *minval = nullptr)
 {
 	list->windows = windows;
 	if (windows) {
-		if (const int rc = pixels_of_view(v, pixel_step, order, W, H, n, dst, px, kind, window, list))
+		if (const int rc = pixels_of_view(v, pixel_step, order, W, H, n, dst, px, kind, window, list, minval))
 			return rc;
 	} else {
-		if (const int rc = pixels_of_view(v, pixel_step, order, W, H, n, dst, px, kind, window))
+		if (const int rc = pixels_of_view(v, pixel_step, order, W, H, n, dst, px, kind, window, nullptr, minval))
 			return rc;
 		if (dst ? !dwtx_count_ok(n, DWTX_MAX_PLANES_PER_CALL / 3, "streams to decode") : !dwtx_count_ok((long)n * v->channels, DWTX_MAX_PLANES_PER_CALL, "planes"))
 			return DWTX_ERR_ARG;
@@ -1006,18 +1078,18 @@ extern "C" int dwtx_view_flip_plan(const dwtx_view *v, size_t pixel_step, int W,
 	return DWTX_OK;
 }
 
-extern "C" int dwtx_encode_view_flip(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+static int encode_view_flip(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
 	const void *const *host_windows, int flip, const unsigned char *host_flips,
-	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, const int *minval)
 {
 	std::vector<unsigned char> flags;
 	bool any;
 	if (const int rc = flip_flags(n, flip, host_flips, &flags, &any))
 		return rc;
 	if (!any)   // the unflipped call, on its own path
-		return host_windows ? dwtx_encode_view_list(ctx, src, pixel_step, order, fmt, host_windows, W, H, n, capacity, dev_out, out_stride, dev_info)
-		     : fmt          ? dwtx_encode_view_float(ctx, src, pixel_step, order, fmt, W, H, n, capacity, dev_out, out_stride, dev_info)
-		                    : dwtx_encode_view_order(ctx, src, pixel_step, order, W, H, n, capacity, dev_out, out_stride, dev_info);
+		return host_windows ? encode_view_list(ctx, src, pixel_step, order, fmt, host_windows, W, H, n, capacity, dev_out, out_stride, dev_info, minval)
+		     : fmt          ? encode_view_float(ctx, src, pixel_step, order, fmt, W, H, n, capacity, dev_out, out_stride, dev_info, minval)
+		                    : encode_view_order(ctx, src, pixel_step, order, W, H, n, capacity, dev_out, out_stride, dev_info, minval);
 	if (!ctx || !dev_out || !dev_info)
 		return DWTX_ERR_ARG;
 	int kind = -1;
@@ -1026,10 +1098,10 @@ extern "C" int dwtx_encode_view_flip(dwtx_ctx *ctx, const dwtx_view *src, size_t
 			return rc;
 	WinList list{ nullptr, {} };
 	dwtx_pixels px;
-	if (const int rc = flipped_view(src, pixel_step, order, W, H, n, false, kind, false, host_windows, &list, &px))
+	if (const int rc = flipped_view(src, pixel_step, order, W, H, n, false, kind, false, host_windows, &list, &px, minval))
 		return rc;
 	if (fmt) {
-		if (!dwtx_maxval_ok(src->maxval))
+		if (!source_range_ok(src, minval))
 			return DWTX_ERR_ARG;
 		set_float_format(&px, fmt);
 	}
@@ -1043,20 +1115,34 @@ extern "C" int dwtx_encode_view_flip(dwtx_ctx *ctx, const dwtx_view *src, size_t
 	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx->enc_index);
 }
 
-extern "C" int dwtx_decode_view_flip(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+extern "C" int dwtx_encode_view_flip(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	const void *const *host_windows, int flip, const unsigned char *host_flips,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	return encode_view_flip(ctx, src, pixel_step, order, fmt, host_windows, flip, host_flips, W, H, n, capacity, dev_out, out_stride, dev_info, nullptr);
+}
+
+extern "C" int dwtx_encode_view_signed(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	const void *const *host_windows, int flip, const unsigned char *host_flips, int minval,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	return encode_view_flip(ctx, src, pixel_step, order, fmt, host_windows, flip, host_flips, W, H, n, capacity, dev_out, out_stride, dev_info, &minval);
+}
+
+static int decode_view_flip(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
 	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
 	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, int flip, const unsigned char *host_flips,
-	dwtx_decode_info *host_info)
+	dwtx_decode_info *host_info, const int *minval)
 {
 	std::vector<unsigned char> flags;
 	bool any;
 	if (const int rc = flip_flags(n, flip, host_flips, &flags, &any))
 		return rc;
 	if (!any)   // the unflipped call, on its own path
-		return host_windows ? dwtx_decode_view_list(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h,
-		                          host_origins, host_windows, host_info)
-		                    : dwtx_decode_view_crop(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h,
-		                          host_origins, host_info);
+		return host_windows ? decode_view_list(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h,
+		                          host_origins, host_windows, host_info, minval)
+		                    : decode_view_crop(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h,
+		                          host_origins, host_info, minval);
 	if (!ctx || !dev_streams || !dev_lens || !host_info)
 		return DWTX_ERR_ARG;
 	bool whole;
@@ -1068,7 +1154,7 @@ extern "C" int dwtx_decode_view_flip(dwtx_ctx *ctx, const uint8_t *dev_streams, 
 			return rc;
 	WinList list{ nullptr, {} };
 	dwtx_pixels px;
-	if (const int rc = flipped_view(dst, pixel_step, order, crop_w, crop_h, n, true, kind, !whole, host_windows, &list, &px))
+	if (const int rc = flipped_view(dst, pixel_step, order, crop_w, crop_h, n, true, kind, !whole, host_windows, &list, &px, minval))
 		return rc;
 	if (fmt)
 		set_float_format(&px, fmt);
@@ -1082,6 +1168,24 @@ extern "C" int dwtx_decode_view_flip(dwtx_ctx *ctx, const uint8_t *dev_streams, 
 		return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
 	const CropCall crop = { crop_w, crop_h, host_origins };
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info, &crop);
+}
+
+extern "C" int dwtx_decode_view_flip(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, int flip, const unsigned char *host_flips,
+	dwtx_decode_info *host_info)
+{
+	return decode_view_flip(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h, host_origins,
+		host_windows, flip, host_flips, host_info, nullptr);
+}
+
+extern "C" int dwtx_decode_view_signed(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, int flip, const unsigned char *host_flips, int minval,
+	dwtx_decode_info *host_info)
+{
+	return decode_view_flip(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h, host_origins,
+		host_windows, flip, host_flips, host_info, &minval);
 }
 
 // one axis of dwtx_tile_groups: `full` tiles of `tile`, then one of `last` (0: none)
@@ -1338,6 +1442,12 @@ extern "C" int dwtx_encode_images16(dwtx_ctx *ctx, const uint16_t *pix, int W, i
 	return encode_images(ctx, dwtx_pixels16(pix, C, (size_t)W * H * C), W, H, n, capacity, out, out_stride, out_lens, stats);
 }
 
+extern "C" int dwtx_encode_images_s16(dwtx_ctx *ctx, const int16_t *pix, int W, int H, int C, int n, long capacity,
+	uint8_t *out, size_t out_stride, size_t *out_lens, dwtx_stats *stats)
+{
+	return encode_images(ctx, dwtx_pixels_s16(pix, C, (size_t)W * H * C), W, H, n, capacity, out, out_stride, out_lens, stats);
+}
+
 extern "C" int dwtx_decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_stride, const size_t *lens, int n,
 	int pixels_max, uint8_t *pix, size_t pix_stride, int *outW, int *outH, int *outC)
 {
@@ -1350,7 +1460,7 @@ static int decode_images(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_st
 {
 	if (!ctx || !streams || !lens || !host.base || !outW || !outH || !outC || n < 1 || (stream_stride & 7))
 		return DWTX_ERR_ARG;
-	if (!dwtx_maxval_ok(host.maxval))
+	if (!host.range_ok())
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	// decode.c:142-159: geometry comes from the first stream's header; all streams of a batch share it
@@ -1483,4 +1593,10 @@ extern "C" int dwtx_decode_images16(dwtx_ctx *ctx, const uint8_t *streams, size_
 	int pixels_max, uint16_t *pix, size_t pix_stride, int maxval, int *outW, int *outH, int *outC, dwtx_decode_info *infos)
 {
 	return decode_images(ctx, streams, stream_stride, lens, n, pixels_max, dwtx_pixels16(pix, 0, pix_stride, maxval), outW, outH, outC, infos);
+}
+
+extern "C" int dwtx_decode_images_s16(dwtx_ctx *ctx, const uint8_t *streams, size_t stream_stride, const size_t *lens, int n,
+	int pixels_max, int16_t *pix, size_t pix_stride, int minval, int maxval, int *outW, int *outH, int *outC, dwtx_decode_info *infos)
+{
+	return decode_images(ctx, streams, stream_stride, lens, n, pixels_max, dwtx_pixels_s16(pix, 0, pix_stride, minval, maxval), outW, outH, outC, infos);
 }

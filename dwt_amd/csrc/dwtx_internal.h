@@ -114,6 +114,14 @@ static inline bool dwtx_maxval_ok(int maxval)
 	dwtx_set_error("maxval %d is outside 1..65535", maxval);
 	return false;
 }
+// the range a signed call is told (include/dwtx.h, dwtx_*_view_signed): what an int16_t sample can hold
+static inline bool dwtx_range_ok(int minval, int maxval)
+{
+	if (minval >= -32768 && minval < maxval && maxval <= 32767)
+		return true;
+	dwtx_set_error("range [%d, %d]: signed samples need -32768 <= minval < maxval <= 32767", minval, maxval);
+	return false;
+}
 
 // The planes (images * channels) of one call: a dimension of most launches' grids (blockIdx.y / .z), which holds 65535, and
 // what WinGrid's unsigned `first + i` (lift.hip) and the kernels' int plane indices count.  32-bit by design (DESIGN.md
@@ -203,13 +211,20 @@ template <class F> char *carve(dwtx_ctx *ctx, int slot, F &&fn)
 // A source may hold them too (dwtx_encode_view_float): the picture that is coded is rint(x * scale + bias) per COLOUR, two
 // fp32 roundings, clamped to [0, maxval] (NaN: 0) — lift.hip's quant_of.  Up to a maxval of 255 those integers meet every
 // bound of 8-bit samples and the source takes their route; above it the deep pictures' (deep_source()).
-enum dwtx_sample_kind { DWTX_SAMPLE_U8 = 0, DWTX_SAMPLE_U16, DWTX_SAMPLE_F32, DWTX_SAMPLE_F16, DWTX_SAMPLE_BF16 };
+// Signed samples (the *_view_signed calls and the *_images_s16 pair): native-endian int16_t, coded as the integers they are;
+// and float samples with a lower bound other than 0 (minval).  The inverse direction clamps gray, Y and every output sample
+// to [minval, maxval] and Co, Cg to [-R, R], R = maxval - minval; the quantiser clamps to [minval, maxval].  Both take the
+// deep pictures' route — no histograms from the transform, no 16-bit ring planes: those bounds are for samples in [0, 255] —
+// through the wide kernels wherever a deep view of the same layout goes through them (lift.hip: the deep sources' signed twins,
+// the deep and float sinks with the lower clamp), else through the general conversions, which know the bound too.
+enum dwtx_sample_kind { DWTX_SAMPLE_U8 = 0, DWTX_SAMPLE_U16, DWTX_SAMPLE_S16, DWTX_SAMPLE_F32, DWTX_SAMPLE_F16, DWTX_SAMPLE_BF16 };
 struct dwtx_pixels {
 	void *base;            // the grid's window 0, first sample
 	int sample_bytes;      // 1 or 2; a float destination's 4 or 2 (kind says which samples they are)
 	int channels;          // 1 gray, 3 RGB (interleaved unless channel_stride says otherwise)
 	size_t image_stride;   // from a window to the next one of its band
 	int maxval;            // 255 for bytes; a deep picture's own (what the inverse direction clamps at)
+	int minval = 0;        // the lower bound beside it: 0 but for signed samples and the float views of the *_view_signed calls
 	size_t row_pitch = 0;  // from a row to the next; 0: dense rows — the width a call works at (a reduced decode's own) times channels
 	int cols = 0;          // windows per band; 0: one band
 	size_t band_stride = 0;   // from a band's first window to the next band's
@@ -217,7 +232,7 @@ struct dwtx_pixels {
 	size_t channel_stride = 0;   // 0: interleaved; else planar RGB: from a window's plane of one channel to the next one's (image() and moved() keep it)
 	size_t pixel_step = 0;       // 0: dense (a pixel is its channels); else from a pixel to the next one of its row, above channels (image() and moved() keep it)
 	int order = DWTX_ORDER_RGB;  // which colour the three channels are as they lie (DWTX_ORDER_*; image() and moved() keep it); gray pixels have none
-	int kind = DWTX_SAMPLE_U8;   // dwtx_sample_kind (dwtx_pixels8 / dwtx_pixels16 / dwtx_pixels_float set it with sample_bytes)
+	int kind = DWTX_SAMPLE_U8;   // dwtx_sample_kind (dwtx_pixels8 / dwtx_pixels16 / dwtx_pixels_s16 / dwtx_pixels_float set it with sample_bytes)
 	float scale[3] = { 1.f, 1.f, 1.f }, bias[3] = { 0.f, 0.f, 0.f };   // float samples: per colour R, G, B (gray: [0])
 	const long long *offs = nullptr;   // listed windows: DEVICE table of their first samples' offsets from base (>= 0), read-only while kernels run; image() and moved() keep it
 	bool offs_on_quad = true;          // listed windows: every offset is a multiple of 4 (what wide() asks of each window beyond base)
@@ -231,12 +246,16 @@ struct dwtx_pixels {
 	bool flips = false, flip_wide = false, flip_sink = false, flip_x = false;
 	int flip_w = 0, flip_h = 0;
 
-	// uint16_t samples — and with them the kernel family that clamps at maxval and keeps no 16-bit ring planes
-	bool deep() const { return kind == DWTX_SAMPLE_U16; }
+	// uint16_t or int16_t samples — and with them the kernel family that clamps at [minval, maxval] and keeps no 16-bit ring planes
+	bool deep() const { return kind == DWTX_SAMPLE_U16 || kind == DWTX_SAMPLE_S16; }
 	bool is_float() const { return kind >= DWTX_SAMPLE_F32; }
+	// int16_t samples, or a lower bound of their own: the range rule of the signed calls holds (range_ok)
+	bool signed_range() const { return kind == DWTX_SAMPLE_S16 || minval != 0; }
 	// as a SOURCE: the family whose forward transform keeps no histograms and no 16-bit ring planes (both bounds are for samples
-	// of at most 255): uint16_t samples, and floats that quantise to more than 255
-	bool deep_source() const { return deep() || (is_float() && maxval > 255); }
+	// in [0, 255]): uint16_t and int16_t samples, and floats that quantise to more than 255 or to less than 0
+	bool deep_source() const { return deep() || (is_float() && (maxval > 255 || minval < 0)); }
+	// what the inverse direction is told: maxval alone, or the range of a signed call
+	bool range_ok() const { return signed_range() ? dwtx_range_ok(minval, maxval) : dwtx_maxval_ok(maxval); }
 	size_t bytes(size_t samples) const { return samples * (size_t)sample_bytes; }
 	void *at(size_t sample) const { return static_cast<char *>(base) + bytes(sample); }
 	// typed for the kernels: u16() for deep pixels; u8() for bytes — and for the fields that carry either kind as bytes
@@ -300,6 +319,14 @@ static inline dwtx_pixels dwtx_pixels16(const uint16_t *pix, int channels, size_
 {
 	dwtx_pixels p{ const_cast<uint16_t *>(pix), 2, channels, image_stride, maxval };
 	p.kind = DWTX_SAMPLE_U16;
+	return p;
+}
+// signed samples: coded as they are; minval and maxval are what the inverse direction clamps at
+static inline dwtx_pixels dwtx_pixels_s16(const int16_t *pix, int channels, size_t image_stride, int minval = -32768, int maxval = 32767)
+{
+	dwtx_pixels p{ const_cast<int16_t *>(pix), 2, channels, image_stride, maxval };
+	p.kind = DWTX_SAMPLE_S16;
+	p.minval = minval;
 	return p;
 }
 // a float destination or source (kind: DWTX_SAMPLE_F32 / _F16 / _BF16); the caller fills scale and bias

@@ -111,13 +111,23 @@ struct LevelArgs {
 	short *ll16;           // forward, or null: the LL band goes out as 16-bit values (pitch and plane stride of ll)
 	int maxval;            // deep pixels (uint16_t samples behind src8 / dst8, strides in samples): the inverse's clamps; 0 = 8-bit pixels
 	WinGrid grid;          // the windows behind src8 / dst8 (src_ps / ll_ps apart in a band)
+	int minval;            // the lower bound beside maxval (dwtx_pixels::minval): 0 but for int16_t samples behind dst8 and float views of the *_view_signed calls
 };
+
+// What a sink clamps at (image.h:41-43, pnm.h:108): gray, Y and every sample written to [lo, hi], Co and Cg to [-r(), r()] — with
+// lo = 0 the unsigned pixels' [0, maxval] and [-maxval, maxval].  The 8-bit sinks are handed constants and read none of it.
+struct Clamp {
+	int lo, hi;
+	__device__ __forceinline__ int r() const { return hi - lo; }
+};
+__device__ __forceinline__ Clamp clamp_of(const LevelArgs &a) { return Clamp{ a.minval, a.maxval }; }
 
 // A float destination (dwtx_pixels::kind): scale and bias per COLOUR — R, G, B, whatever the order the channels lie in; gray
 // uses [0] — and which of the two 16-bit types a Half16 sink writes (the two differ in the convert only: one kernel for both)
 struct FloatFmt {
 	float scale[3], bias[3];
 	int bf16;
+	int sext;   // the fp32 planar sink's rows wait as 16-bit integers: negative ones among them (minval < 0), to be widened with their sign
 };
 
 // ---------------------------------------------------------------- forward ---
@@ -658,11 +668,12 @@ __device__ __forceinline__ FwdRawRgb16 hold(const FwdRawRgb16 &r)
 	return o;
 }
 
-template <bool BGR = false>
+// (SGN, here and for the planar row: int16_t samples, widened with their sign — the signed twins of the deep sources)
+template <bool BGR = false, bool SGN = false>
 __device__ __forceinline__ FwdRaw widen(const FwdRawRgb16 &r, int ch)
 {
-	auto lo = [](unsigned w) { return (int)(w & 0xffffu); };
-	auto hi = [](unsigned w) { return (int)(w >> 16); };
+	auto lo = [](unsigned w) { return SGN ? (int)(short)(w & 0xffffu) : (int)(w & 0xffffu); };
+	auto hi = [](unsigned w) { return SGN ? (int)w >> 16 : (int)(w >> 16); };
 	FwdRaw o;
 	o.x.x = ycocg_lies<BGR>(lo(r.a.x), hi(r.a.x), lo(r.a.y), ch);
 	o.x.y = ycocg_lies<BGR>(hi(r.a.y), lo(r.b.x), hi(r.b.x), ch);
@@ -685,9 +696,10 @@ __device__ __forceinline__ FwdRawRgbS3 hold(const FwdRawRgbS3 &p)
 	return o;
 }
 
+template <bool SGN = false>
 __device__ __forceinline__ FwdRaw widen(const FwdRawRgbS3 &p, int ch)
 {
-	const FwdRaw r = widen_u(p.r), g = widen_u(p.g), b = widen_u(p.b);
+	const FwdRaw r = SGN ? widen_s(p.r) : widen_u(p.r), g = SGN ? widen_s(p.g) : widen_u(p.g), b = SGN ? widen_s(p.b) : widen_u(p.b);
 	FwdRaw o;
 	o.x.x = ycocg_ch(r.x.x, g.x.x, b.x.x, ch);
 	o.x.y = ycocg_ch(r.x.y, g.x.y, b.x.y, ch);
@@ -1110,7 +1122,9 @@ struct FwdSrc;
 // three B, G, R twins: Band<SRC_BGR16>, Bgr8, Bgrx8)
 enum { SRC_I32 = 0, SRC_I16, SRC_U16, SRC_RGB16, SRC_RGBP16, SRC_U8, SRC_RGB8, SRC_RGBP8, SRC_RGBX8, SRC_BGR16, SRC_BGR8, SRC_BGRX8,
 	// float pixels (FloatPix<> below), gray and planar (P) fp32 and fp16 / bf16: quantised to at most 255, and (D) beyond
-	SRC_F32, SRC_H16, SRC_F32P, SRC_H16P, SRC_F32D, SRC_H16D, SRC_F32PD, SRC_H16PD, SRC_COUNT };
+	SRC_F32, SRC_H16, SRC_F32P, SRC_H16P, SRC_F32D, SRC_H16D, SRC_F32PD, SRC_H16PD,
+	// int16_t pixels (dwtx_encode_view_signed): the twins of SRC_U16, SRC_RGB16, SRC_RGBP16 and SRC_BGR16 that widen with the sign
+	SRC_S16, SRC_RGB16S, SRC_RGBP16S, SRC_BGR16S, SRC_COUNT };
 template <int SRC>
 struct Band {};
 // 8-bit interleaved RGB pixels, of which each plane's workgroup takes its own YCoCg-R channel (image.h:52-65 fused; 8-bit
@@ -1232,6 +1246,25 @@ struct FwdSrc<Band<SRC_RGBP16>> : FwdInt32 {
 	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int ch) { return widen(r, ch); }
 };
 
+// Signed pixels: each deep source with the one difference that the samples widen with their sign (image.h:52-65 is reversible on
+// any int, and nothing after the widening knows where the samples came from)
+template <>
+struct FwdSrc<Band<SRC_S16>> : FwdSrc<Band<SRC_U16>> {
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int) { return widen_s(r); }
+};
+template <>
+struct FwdSrc<Band<SRC_RGB16S>> : FwdSrc<Band<SRC_RGB16>> {
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int ch) { return widen<false, true>(r, ch); }
+};
+template <>
+struct FwdSrc<Band<SRC_BGR16S>> : FwdSrc<Band<SRC_RGB16>> {
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int ch) { return widen<true, true>(r, ch); }
+};
+template <>
+struct FwdSrc<Band<SRC_RGBP16S>> : FwdSrc<Band<SRC_RGBP16>> {
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int ch) { return widen<true>(r, ch); }
+};
+
 template <>
 struct FwdSrc<uint8_t> : FwdPacked {
 	typedef FwdRaw8 Loaded;
@@ -1311,6 +1344,19 @@ __device__ __forceinline__ int quant_of(float x, float scale, float bias, float 
 	return (int)(lo > M ? M : lo);
 }
 
+// The same quantiser with a lower bound of its own (the *_view_signed calls: what every source runs, L = 0 elsewhere): v = min(max(q, L), M),
+// and a NaN becomes 0 BEFORE the clamp — 0 clamped into [L, M] — so that L = 0 gives quant_of above bit for bit: -inf takes L.
+__device__ __forceinline__ int quant_of(float x, float scale, float bias, float L, float M)
+{
+#pragma clang fp contract(off)
+	const float m = x * scale;
+	const float r = m + bias;
+	const float q = __builtin_rintf(r);
+	const float z = q == q ? q : 0.f;
+	const float lo = z >= L ? z : L;
+	return (int)(lo > M ? M : lo);
+}
+
 // the 16-bit float types widen exactly (fp16 subnormals kept): which of the two the bits are is uniform (FloatFmt::bf16)
 __device__ __forceinline__ float half_float(unsigned bits16, int bf16)
 {
@@ -1359,16 +1405,16 @@ struct Quant6 {
 };
 __device__ __forceinline__ Quant6 quant_row(const FwdRawF<float> &r, const LevelArgsW &A, int c)
 {
-	const float s = A.fmt.scale[c], b = A.fmt.bias[c], M = (float)A.a.maxval;
-	auto q = [s, b, M](unsigned bits) { return quant_of(__builtin_bit_cast(float, bits), s, b, M); };
+	const float s = A.fmt.scale[c], b = A.fmt.bias[c], L = (float)A.a.minval, M = (float)A.a.maxval;
+	auto q = [s, b, L, M](unsigned bits) { return quant_of(__builtin_bit_cast(float, bits), s, b, L, M); };
 	Quant6 o = { q(r.x.x), q(r.x.y), q(r.x.z), q(r.x.w), q(r.e.x), q(r.e.y) };
 	return o;
 }
 __device__ __forceinline__ Quant6 quant_row(const FwdRawF<Half16> &r, const LevelArgsW &A, int c)
 {
-	const float s = A.fmt.scale[c], b = A.fmt.bias[c], M = (float)A.a.maxval;
+	const float s = A.fmt.scale[c], b = A.fmt.bias[c], L = (float)A.a.minval, M = (float)A.a.maxval;
 	const int bf16 = A.fmt.bf16;
-	auto q = [s, b, M, bf16](unsigned bits16) { return quant_of(half_float(bits16, bf16), s, b, M); };
+	auto q = [s, b, L, M, bf16](unsigned bits16) { return quant_of(half_float(bits16, bf16), s, b, L, M); };
 	Quant6 o = { q(r.x.x & 0xffffu), q(r.x.x >> 16), q(r.x.y & 0xffffu), q(r.x.y >> 16), q(r.e & 0xffffu), q(r.e >> 16) };
 	return o;
 }
@@ -1895,16 +1941,16 @@ __device__ __forceinline__ Quad4 inv_row_vals(int qd, int nquads, I2 lo, I2 hi)
 template <typename DstT>
 struct OutRow {
 	typedef int4 type;
-	static __device__ __forceinline__ type of(const Quad4 &v, int) { return make_int4(v.v[0], v.v[1], v.v[2], v.v[3]); }
+	static __device__ __forceinline__ type of(const Quad4 &v, Clamp) { return make_int4(v.v[0], v.v[1], v.v[2], v.v[3]); }
 	static __device__ __forceinline__ void store(int *__restrict__ row, int qd, const type &v) { *reinterpret_cast<int4 *>(row + 4 * qd) = v; }
 };
-// four deep pixels clamped to [0, maxval] (pnm.h:108 with the picture's maxval for 255): 8 bytes per lane
+// four deep pixels clamped to [0, maxval] (pnm.h:108 with the picture's maxval for 255; signed ones to [minval, maxval]): 8 bytes per lane
 template <>
 struct OutRow<uint16_t> {
 	typedef uint2 type;
-	static __device__ __forceinline__ type of(const Quad4 &v, int M)
+	static __device__ __forceinline__ type of(const Quad4 &v, Clamp M)
 	{
-		auto c = [M](int x) { return (unsigned)(x < 0 ? 0 : x > M ? M : x); };
+		auto c = [M](int x) { return (unsigned)(x < M.lo ? M.lo : x > M.hi ? M.hi : x) & 0xffffu; };   // (two's complement: int16_t samples)
 		return make_uint2(c(v.v[0]) | (c(v.v[1]) << 16), c(v.v[2]) | (c(v.v[3]) << 16));
 	}
 	static __device__ __forceinline__ void store(uint16_t *__restrict__ row, int qd, const type &v) { *reinterpret_cast<uint2 *>(row + 4 * qd) = v; }
@@ -1912,7 +1958,7 @@ struct OutRow<uint16_t> {
 template <>
 struct OutRow<uint8_t> {
 	typedef unsigned type;
-	static __device__ __forceinline__ type of(const Quad4 &v, int)
+	static __device__ __forceinline__ type of(const Quad4 &v, Clamp)
 	{
 		auto c8 = [](int x) { return (unsigned)(x < 0 ? 0 : x > 255 ? 255 : x); };
 		return c8(v.v[0]) | (c8(v.v[1]) << 8) | (c8(v.v[2]) << 16) | (c8(v.v[3]) << 24);
@@ -1962,9 +2008,9 @@ struct FloatSample<Half16> {
 template <>
 struct OutRow<float> {
 	typedef float4 type;
-	static __device__ __forceinline__ type of(const Quad4 &v, int M, const FloatFmt &f)
+	static __device__ __forceinline__ type of(const Quad4 &v, Clamp M, const FloatFmt &f)
 	{
-		auto c = [M, &f](int x) { return float_of(x < 0 ? 0 : x > M ? M : x, f.scale[0], f.bias[0]); };
+		auto c = [M, &f](int x) { return float_of(x < M.lo ? M.lo : x > M.hi ? M.hi : x, f.scale[0], f.bias[0]); };
 		return make_float4(c(v.v[0]), c(v.v[1]), c(v.v[2]), c(v.v[3]));
 	}
 	static __device__ __forceinline__ void store(float *__restrict__ row, int qd, const type &v) { *reinterpret_cast<float4 *>(row + 4 * qd) = v; }
@@ -1972,9 +2018,9 @@ struct OutRow<float> {
 template <>
 struct OutRow<Half16> {
 	typedef uint2 type;
-	static __device__ __forceinline__ type of(const Quad4 &v, int M, const FloatFmt &f)
+	static __device__ __forceinline__ type of(const Quad4 &v, Clamp M, const FloatFmt &f)
 	{
-		auto c = [M, &f](int x) { return float_of(x < 0 ? 0 : x > M ? M : x, f.scale[0], f.bias[0]); };
+		auto c = [M, &f](int x) { return float_of(x < M.lo ? M.lo : x > M.hi ? M.hi : x, f.scale[0], f.bias[0]); };
 		const float q[4] = { c(v.v[0]), c(v.v[1]), c(v.v[2]), c(v.v[3]) };
 		return half_quad(q, f.bf16);
 	}
@@ -2174,11 +2220,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 			inv_cols(a, jj, c, cur[s], e, o);
 			inv_cols(a, jj, cx, curx[s], ex, ox);
 			if constexpr (FloatSample<DstT>::value) {
-				orow[2 * s] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, e, ex), fx), a.maxval, A.fmt);
-				orow[2 * s + 1] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, o, ox), fx), a.maxval, A.fmt);
+				orow[2 * s] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, e, ex), fx), clamp_of(a), A.fmt);
+				orow[2 * s + 1] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, o, ox), fx), clamp_of(a), A.fmt);
 			} else {
-				orow[2 * s] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, e, ex), fx), a.maxval);
-				orow[2 * s + 1] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, o, ox), fx), a.maxval);
+				orow[2 * s] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, e, ex), fx), clamp_of(a));
+				orow[2 * s + 1] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, o, ox), fx), clamp_of(a));
 			}
 		}
 	}
@@ -2376,8 +2422,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w(Inv2Args a)
 		}
 		const Quad4 ev = inv_row_vals(q, a.nquads, cel, ceh);
 		const Quad4 od = inv_row_vals(q, a.nquads, i2_add2(cdl, cel, nel), i2_add2(cdh, ceh, neh));
-		even = OutRow<DstT>::of(flip_quad<FL>(ev, fx), 0);
-		odd = OutRow<DstT>::of(flip_quad<FL>(od, fx), 0);
+		even = OutRow<DstT>::of(flip_quad<FL>(ev, fx), Clamp{ 0, 0 });
+		odd = OutRow<DstT>::of(flip_quad<FL>(od, fx), Clamp{ 0, 0 });
 		cdl = ndl;
 		cdh = ndh;
 		cel = nel;
@@ -2433,48 +2479,48 @@ struct Rgb24 {
 // (BGR, here and in rgbx_of and rgb_of: the pixels lie as B, G, R — dwtx_pixels::order — so R and B trade places AFTER the
 // clamps, which act on the colours)
 template <bool BGR = false>
-__device__ __forceinline__ Rgb24 rgb16_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M)
+__device__ __forceinline__ Rgb24 rgb16_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp M)
 {
 	unsigned px[12];
 #pragma unroll
 	for (int k = 0; k < 4; ++k) {
-		const int yy = clamp_to(y.v[k], 0, M), c0 = clamp_to(co.v[k], -M, M), c1 = clamp_to(cg.v[k], -M, M);
+		const int yy = clamp_to(y.v[k], M.lo, M.hi), c0 = clamp_to(co.v[k], -M.r(), M.r()), c1 = clamp_to(cg.v[k], -M.r(), M.r());
 		const int t = yy - tdiv2(c1);
 		const int g = c1 + t;
 		const int b = t - tdiv2(c0);
 		const int r = b + c0;
-		px[3 * k + (BGR ? 2 : 0)] = (unsigned)clamp_to(r, 0, M);
-		px[3 * k + 1] = (unsigned)clamp_to(g, 0, M);
-		px[3 * k + (BGR ? 0 : 2)] = (unsigned)clamp_to(b, 0, M);
+		px[3 * k + (BGR ? 2 : 0)] = (unsigned)clamp_to(r, M.lo, M.hi);
+		px[3 * k + 1] = (unsigned)clamp_to(g, M.lo, M.hi);
+		px[3 * k + (BGR ? 0 : 2)] = (unsigned)clamp_to(b, M.lo, M.hi);
 	}
 	Rgb24 o;
 #pragma unroll
 	for (int k = 0; k < 6; ++k)
-		o.w[k] = px[2 * k] | (px[2 * k + 1] << 16);
+		o.w[k] = (px[2 * k] & 0xffffu) | (px[2 * k + 1] << 16);   // (two's complement: a negative sample's upper bits stay out of its neighbour)
 	return o;
 }
 
 // the same colour transform and clamps (M: 255, or a deep picture's maxval) for planar pixels: the lane's four pixels as one
 // quad per channel — px[c][k] = channel c of pixel k
-__device__ __forceinline__ void rgb_planes_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M, unsigned (&px)[3][4])
+__device__ __forceinline__ void rgb_planes_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp M, unsigned (&px)[3][4])
 {
 #pragma unroll
 	for (int k = 0; k < 4; ++k) {
-		const int yy = clamp_to(y.v[k], 0, M), c0 = clamp_to(co.v[k], -M, M), c1 = clamp_to(cg.v[k], -M, M);
+		const int yy = clamp_to(y.v[k], M.lo, M.hi), c0 = clamp_to(co.v[k], -M.r(), M.r()), c1 = clamp_to(cg.v[k], -M.r(), M.r());
 		const int t = yy - tdiv2(c1);
 		const int g = c1 + t;
 		const int b = t - tdiv2(c0);
 		const int r = b + c0;
-		px[0][k] = (unsigned)clamp_to(r, 0, M);
-		px[1][k] = (unsigned)clamp_to(g, 0, M);
-		px[2][k] = (unsigned)clamp_to(b, 0, M);
+		px[0][k] = (unsigned)clamp_to(r, M.lo, M.hi);
+		px[1][k] = (unsigned)clamp_to(g, M.lo, M.hi);
+		px[2][k] = (unsigned)clamp_to(b, M.lo, M.hi);
 	}
 }
 // w[c] = the four bytes of channel c
 __device__ __forceinline__ Rgb12 rgb_planar_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg)
 {
 	unsigned px[3][4];
-	rgb_planes_of(y, co, cg, 255, px);
+	rgb_planes_of(y, co, cg, Clamp{ 0, 255 }, px);
 	Rgb12 o;
 #pragma unroll
 	for (int c = 0; c < 3; ++c)
@@ -2482,15 +2528,15 @@ __device__ __forceinline__ Rgb12 rgb_planar_of(const Quad4 &y, const Quad4 &co, 
 	return o;
 }
 // w[2c], w[2c+1] = the four samples of channel c
-__device__ __forceinline__ Rgb24 rgb16_planar_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M)
+__device__ __forceinline__ Rgb24 rgb16_planar_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp M)
 {
 	unsigned px[3][4];
 	rgb_planes_of(y, co, cg, M, px);
 	Rgb24 o;
 #pragma unroll
 	for (int c = 0; c < 3; ++c) {
-		o.w[2 * c] = px[c][0] | (px[c][1] << 16);
-		o.w[2 * c + 1] = px[c][2] | (px[c][3] << 16);
+		o.w[2 * c] = (px[c][0] & 0xffffu) | (px[c][1] << 16);   // (two's complement, as in rgb16_of)
+		o.w[2 * c + 1] = (px[c][2] & 0xffffu) | (px[c][3] << 16);
 	}
 	return o;
 }
@@ -2525,7 +2571,7 @@ __device__ __forceinline__ void rgbx_store(uint8_t *p, const Rgbx16 &v)
 template <typename PixT, PixLayout LAYOUT = PIX_PACKED>
 struct RgbOut {
 	typedef Rgb12 row;
-	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int);
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp);
 	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long)
 	{
 		U32x3 x = { v.w[0], v.w[1], v.w[2] };
@@ -2535,7 +2581,7 @@ struct RgbOut {
 template <>
 struct RgbOut<uint16_t, PIX_PACKED> {
 	typedef Rgb24 row;
-	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M) { return rgb16_of(y, co, cg, M); }
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp M) { return rgb16_of(y, co, cg, M); }
 	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long)   // (pitch in samples; rows and quads are multiples of 8 bytes)
 	{
 		uint2 *p = reinterpret_cast<uint2 *>(reinterpret_cast<uint16_t *>(dst) + r * pitch + 12 * qd);
@@ -2547,7 +2593,7 @@ struct RgbOut<uint16_t, PIX_PACKED> {
 template <>
 struct RgbOut<uint8_t, PIX_PLANAR> {
 	typedef Rgb12 row;
-	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgb_planar_of(y, co, cg); }
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp) { return rgb_planar_of(y, co, cg); }
 	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long cs)
 	{
 		uint8_t *p = dst + r * pitch + 4 * qd;
@@ -2559,7 +2605,7 @@ struct RgbOut<uint8_t, PIX_PLANAR> {
 template <>
 struct RgbOut<uint16_t, PIX_PLANAR> {
 	typedef Rgb24 row;
-	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M) { return rgb16_planar_of(y, co, cg, M); }
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp M) { return rgb16_planar_of(y, co, cg, M); }
 	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long cs)
 	{
 		uint16_t *p = reinterpret_cast<uint16_t *>(dst) + r * pitch + 4 * qd;
@@ -2575,21 +2621,24 @@ struct RgbOut<uint16_t, PIX_PLANAR> {
 template <>
 struct RgbOut<float, PIX_PLANAR> {
 	typedef Rgb24 row;
-	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M, const FloatFmt &) { return rgb16_planar_of(y, co, cg, M); }
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp M, const FloatFmt &) { return rgb16_planar_of(y, co, cg, M); }
 	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long cs, const FloatFmt &f)
 	{
 		float *p = reinterpret_cast<float *>(dst) + r * pitch + 4 * qd;
 #pragma unroll
 		for (int c = 0; c < 3; ++c) {
 			const unsigned lo = v.w[2 * c], hi = v.w[2 * c + 1];
-			*reinterpret_cast<float4 *>(p + c * cs) = make_float4(float_of((int)(lo & 0xffffu), f.scale[c], f.bias[c]), float_of((int)(lo >> 16), f.scale[c], f.bias[c]),
-				float_of((int)(hi & 0xffffu), f.scale[c], f.bias[c]), float_of((int)(hi >> 16), f.scale[c], f.bias[c]));
+			const int sx = f.sext;   // (uniform: a range below 0 never reaches beyond 32767)
+			auto l16 = [sx](unsigned w) { return sx ? (int)(short)(w & 0xffffu) : (int)(w & 0xffffu); };
+			auto h16 = [sx](unsigned w) { return sx ? (int)w >> 16 : (int)(w >> 16); };
+			*reinterpret_cast<float4 *>(p + c * cs) = make_float4(float_of(l16(lo), f.scale[c], f.bias[c]), float_of(h16(lo), f.scale[c], f.bias[c]),
+				float_of(l16(hi), f.scale[c], f.bias[c]), float_of(h16(hi), f.scale[c], f.bias[c]));
 		}
 	}
 };
 template <>
 struct RgbOut<Half16, PIX_PLANAR> : RgbOut<uint16_t, PIX_PLANAR> {   // (the deep planar sink's row and store: the same 8 bytes per plane)
-	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M, const FloatFmt &f)
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp M, const FloatFmt &f)
 	{
 		unsigned px[3][4];
 		rgb_planes_of(y, co, cg, M, px);
@@ -2609,7 +2658,7 @@ template <bool BGR = false>
 __device__ __forceinline__ Rgbx16 rgbx_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg)
 {
 	unsigned px[3][4];
-	rgb_planes_of(y, co, cg, 255, px);
+	rgb_planes_of(y, co, cg, Clamp{ 0, 255 }, px);
 	Rgbx16 o;
 #pragma unroll
 	for (int k = 0; k < 4; ++k)
@@ -2619,7 +2668,7 @@ __device__ __forceinline__ Rgbx16 rgbx_of(const Quad4 &y, const Quad4 &co, const
 template <>
 struct RgbOut<uint8_t, PIX_STEP4> {
 	typedef Rgbx16 row;
-	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgbx_of(y, co, cg); }
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp) { return rgbx_of(y, co, cg); }
 	static __device__ __forceinline__ void store(uint8_t *dst, long pitch, int r, int qd, const row &v, long)
 	{
 		rgbx_store<false>(dst + r * pitch + 16 * qd, v);
@@ -2649,20 +2698,20 @@ __device__ __forceinline__ Rgb12 rgb_of(const Quad4 &y, const Quad4 &co, const Q
 }
 
 template <typename PixT, PixLayout LAYOUT>
-__device__ __forceinline__ typename RgbOut<PixT, LAYOUT>::row RgbOut<PixT, LAYOUT>::of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgb_of(y, co, cg); }
+__device__ __forceinline__ typename RgbOut<PixT, LAYOUT>::row RgbOut<PixT, LAYOUT>::of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp) { return rgb_of(y, co, cg); }
 
 // the B, G, R twins: their RGB layout's row and store, R and B swapped in the row
 template <>
 struct RgbOut<uint8_t, PIX_PACKED_BGR> : RgbOut<uint8_t, PIX_PACKED> {
-	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgb_of<true>(y, co, cg); }
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp) { return rgb_of<true>(y, co, cg); }
 };
 template <>
 struct RgbOut<uint16_t, PIX_PACKED_BGR> : RgbOut<uint16_t, PIX_PACKED> {
-	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int M) { return rgb16_of<true>(y, co, cg, M); }
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp M) { return rgb16_of<true>(y, co, cg, M); }
 };
 template <>
 struct RgbOut<uint8_t, PIX_STEP4_BGR> : RgbOut<uint8_t, PIX_STEP4> {
-	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, int) { return rgbx_of<true>(y, co, cg); }
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp) { return rgbx_of<true>(y, co, cg); }
 };
 
 // PixT = uint16_t: deep pixels (dst8 points to uint16_t samples, ll_ps / llpitch count samples, clamps at a.maxval)
@@ -2744,11 +2793,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 			}
 		}
 		if constexpr (FloatSample<PixT>::value) {
-			orow[0] = Out::of(even[0], even[1], even[2], a.maxval, A.fmt);
-			orow[1] = Out::of(odd[0], odd[1], odd[2], a.maxval, A.fmt);
+			orow[0] = Out::of(even[0], even[1], even[2], clamp_of(a), A.fmt);
+			orow[1] = Out::of(odd[0], odd[1], odd[2], clamp_of(a), A.fmt);
 		} else {
-			orow[0] = Out::of(even[0], even[1], even[2], a.maxval);
-			orow[1] = Out::of(odd[0], odd[1], odd[2], a.maxval);
+			orow[0] = Out::of(even[0], even[1], even[2], clamp_of(a));
+			orow[1] = Out::of(odd[0], odd[1], odd[2], clamp_of(a));
 		}
 	}
 	store_pair(j1 - 1);
@@ -2901,7 +2950,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w_rgb(Inv2Args a)
 		}
 #pragma unroll
 		for (int k = 0; k < 4; ++k)
-			orow[k] = RgbOut<uint8_t, LAYOUT>::of(flip_quad<FL>(rows[0][k], fx), flip_quad<FL>(rows[1][k], fx), flip_quad<FL>(rows[2][k], fx), 255);
+			orow[k] = RgbOut<uint8_t, LAYOUT>::of(flip_quad<FL>(rows[0][k], fx), flip_quad<FL>(rows[1][k], fx), flip_quad<FL>(rows[2][k], fx), Clamp{ 0, 255 });
 	}
 	store_rows(m1 - 1);
 }
@@ -3077,22 +3126,28 @@ __device__ __forceinline__ P *flipped_row(P *pix, const PixGrid &g, unsigned win
 
 constexpr int PX_LANES = 64, PX_ROWS = 4;   // a workgroup of the conversions: one wave per row, a lane per pixel
 
-// pnm.h:69-74 (byte -> int) fused with image.h:52-65 rgb2ycocg.  P = uint8_t, or uint16_t for deep pixels (the same
-// arithmetic: nothing in it knows the depth).  grid: (64 pixels of a row, 4 rows, window): a wave reads 64 neighbouring
+// pnm.h:69-74 (byte -> int) fused with image.h:52-65 rgb2ycocg.  P = uint8_t, uint16_t for deep pixels or int16_t for signed
+// ones, which widen with their sign (the same arithmetic: nothing in it knows the depth, and image.h:53-65 is reversible on
+// any int).  grid: (64 pixels of a row, 4 rows, window): a wave reads 64 neighbouring
 // pixels of one row, and nothing divides per sample.  Planar RGB: the wave reads 64 neighbouring samples of each plane.
 // P = float, _Float16 or __bf16 (dwtx_encode_view_float): the integers the samples quantise to — quant_of with colour c's scale
-// and bias, clamped at M — in any layout the integer instances take; those read neither f nor M.
+// and bias, clamped to [L, M] (L: dwtx_pixels::minval, 0 but in the *_view_signed calls) — in any layout the integer instances
+// take; those read neither f nor the bounds.
 template <class P>
-__device__ __forceinline__ int sample_in(P v, const FloatFmt &, int, int) { return (int)v; }
+__device__ __forceinline__ int sample_in(P v, const FloatFmt &, int, int, int) { return (int)v; }
 template <>
-__device__ __forceinline__ int sample_in<float>(float v, const FloatFmt &f, int c, int M) { return quant_of(v, f.scale[c], f.bias[c], (float)M); }
+__device__ __forceinline__ int sample_in<float>(float v, const FloatFmt &f, int c, int L, int M) { return quant_of(v, f.scale[c], f.bias[c], (float)L, (float)M); }
 template <>
-__device__ __forceinline__ int sample_in<_Float16>(_Float16 v, const FloatFmt &f, int c, int M) { return quant_of((float)v, f.scale[c], f.bias[c], (float)M); }
+__device__ __forceinline__ int sample_in<_Float16>(_Float16 v, const FloatFmt &f, int c, int L, int M) { return quant_of((float)v, f.scale[c], f.bias[c], (float)L, (float)M); }
 template <>
-__device__ __forceinline__ int sample_in<__bf16>(__bf16 v, const FloatFmt &f, int c, int M) { return quant_of((float)v, f.scale[c], f.bias[c], (float)M); }
+__device__ __forceinline__ int sample_in<__bf16>(__bf16 v, const FloatFmt &f, int c, int L, int M) { return quant_of((float)v, f.scale[c], f.bias[c], (float)L, (float)M); }
+
+// the sample types whose lower bound is 0 whatever the launch says: their instances keep the constant
+template <class P>
+constexpr bool px_unsigned = std::is_same<P, uint8_t>::value || std::is_same<P, uint16_t>::value;
 
 template <class P, bool FLIP = false>
-__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *__restrict__ planes, const P *__restrict__ pix, PixGrid g, int M, FloatFmt f)
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *__restrict__ planes, const P *__restrict__ pix, PixGrid g, int L, int M, FloatFmt f)
 {
 	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
 	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
@@ -3104,10 +3159,10 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *
 		const P *row = FLIP ? flipped_row(pix, g, win, mx, y) : pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
 		int *dst = planes + (long)win * g.C * npix + (long)y * g.W + x;
 		if (g.C == 1) {
-			dst[0] = sample_in<P>(row[(long)mx * g.col_step], f, 0, M);
+			dst[0] = sample_in<P>(row[(long)mx * g.col_step], f, 0, L, M);
 		} else {
 			const P *p = row + (long)mx * g.col_step;
-			const int r = sample_in<P>(p[0], f, 0, M), gr = sample_in<P>(p[g.chan_stride], f, 1, M), b = sample_in<P>(p[2 * g.chan_stride], f, 2, M);
+			const int r = sample_in<P>(p[0], f, 0, L, M), gr = sample_in<P>(p[g.chan_stride], f, 1, L, M), b = sample_in<P>(p[2 * g.chan_stride], f, 2, L, M);
 			const int co = r - b;
 			const int t = b + tdiv2(co);
 			const int cg = gr - t;
@@ -3124,7 +3179,9 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi)
 }
 
 // image.h:39-50 ycocg2rgb (input clamps included) + pnm.h:108 output clamp, with M (the pixels' maxval) where the
-// reference has 255: Y and the output to [0, M], Co and Cg to [-M, M].  P = uint8_t (M = 255) or uint16_t.  Same grid as
+// reference has 255: Y and the output to [0, M], Co and Cg to [-M, M].  P = uint8_t (M = 255) or uint16_t.  With a lower
+// bound L of its own (P = int16_t, written as two's complement, and the float types: dwtx_pixels::minval) Y and the output go to
+// [L, M] and Co and Cg to [-R, R], R = M - L: the extremes R - B and G - T can reach on samples in [L, M].  Same grid as
 // above; only the C samples of the W pixels of a window's H rows are written — with a column step above C nothing between
 // the pixels is: no word is read, merged and written back (another stream may be writing the samples in between).
 // P = float, _Float16 or __bf16: the same clamped integers through float_of with colour c's scale and bias (f; the integer
@@ -3139,8 +3196,9 @@ template <>
 __device__ __forceinline__ __bf16 sample_of<__bf16>(int v, const FloatFmt &f, int c) { return (__bf16)float_of(v, f.scale[c], f.bias[c]); }
 
 template <class P, bool FLIP = false>
-__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, int M, FloatFmt f)
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, int L_, int M, FloatFmt f)
 {
+	const int L = px_unsigned<P> ? 0 : L_, R = M - L;
 	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
 	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
 	if (x >= g.W || y >= g.H)
@@ -3151,19 +3209,19 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__
 		P *row = FLIP ? flipped_row(pix, g, win, mx, y) : pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
 		const int *src = planes + (long)win * g.C * npix + (long)y * g.W + x;
 		if (g.C == 1) {
-			row[(long)mx * g.col_step] = sample_of<P>(clampi(src[0], 0, M), f, 0);
+			row[(long)mx * g.col_step] = sample_of<P>(clampi(src[0], L, M), f, 0);
 		} else {
-			const int yy = clampi(src[0], 0, M);
-			const int co = clampi(src[npix], -M, M);
-			const int cg = clampi(src[2 * npix], -M, M);
+			const int yy = clampi(src[0], L, M);
+			const int co = clampi(src[npix], -R, R);
+			const int cg = clampi(src[2 * npix], -R, R);
 			const int t = yy - tdiv2(cg);
 			const int gr = cg + t;
 			const int b = t - tdiv2(co);
 			const int r = b + co;
 			P *p = row + (long)mx * g.col_step;
-			p[0] = sample_of<P>(clampi(r, 0, M), f, 0);
-			p[g.chan_stride] = sample_of<P>(clampi(gr, 0, M), f, 1);
-			p[2 * g.chan_stride] = sample_of<P>(clampi(b, 0, M), f, 2);
+			p[0] = sample_of<P>(clampi(r, L, M), f, 0);
+			p[g.chan_stride] = sample_of<P>(clampi(gr, L, M), f, 1);
+			p[2 * g.chan_stride] = sample_of<P>(clampi(b, L, M), f, 2);
 		}
 	}
 }
@@ -3270,6 +3328,7 @@ static FloatFmt float_fmt(const dwtx_pixels &px)
 		f.bias[c] = px.bias[c];
 	}
 	f.bf16 = px.kind == DWTX_SAMPLE_BF16;
+	f.sext = px.minval < 0;
 	return f;
 }
 
@@ -3278,13 +3337,13 @@ template <class P>
 static void launch_planes_from_pixels(dwtx_ctx *ctx, dim3 grid, int32_t *planes, const dwtx_pixels &px, const PixGrid &g, const FloatFmt &f)
 {
 	const auto kernel = px.flips ? k_planes_from_pixels<P, true> : k_planes_from_pixels<P, false>;
-	hipLaunchKernelGGL(kernel, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, static_cast<const P *>(px.red()), g, px.maxval, f);
+	hipLaunchKernelGGL(kernel, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, static_cast<const P *>(px.red()), g, px.minval, px.maxval, f);
 }
 template <class P>
 static void launch_pixels_from_planes(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const int32_t *planes, const PixGrid &g, const FloatFmt &f)
 {
 	const auto kernel = px.flips ? k_pixels_from_planes<P, true> : k_pixels_from_planes<P, false>;
-	hipLaunchKernelGGL(kernel, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), planes, g, px.maxval, f);
+	hipLaunchKernelGGL(kernel, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), planes, g, px.minval, px.maxval, f);
 }
 
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
@@ -3292,7 +3351,7 @@ int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px,
 	const int C = px.channels;
 	if (!ctx || !planes || !px.base || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || !px.sample_aligned())
 		return DWTX_ERR_ARG;
-	if (px.is_float() && !dwtx_maxval_ok(px.maxval))   // (the quantiser's clamp; integer sources have no use for a maxval)
+	if (px.is_float() && !px.range_ok())   // (the quantiser's clamp; integer sources have no use for a maxval)
 		return DWTX_ERR_ARG;
 	if (px.flips && (!px.offs || W > px.flip_w || H > px.flip_h))   // (a picture is mirrored inside its window: the mirrored index stays in it)
 		return DWTX_ERR_ARG;
@@ -3306,6 +3365,9 @@ int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px,
 		break;
 	case DWTX_SAMPLE_U16:
 		launch_planes_from_pixels<uint16_t>(ctx, grid, planes, px, g, f);
+		break;
+	case DWTX_SAMPLE_S16:
+		launch_planes_from_pixels<int16_t>(ctx, grid, planes, px, g, f);
 		break;
 	case DWTX_SAMPLE_F32:
 		launch_planes_from_pixels<float>(ctx, grid, planes, px, g, f);
@@ -3328,7 +3390,7 @@ int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *p
 	const int C = px.channels;
 	if (!ctx || !planes || !px.base || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || !px.sample_aligned())
 		return DWTX_ERR_ARG;
-	if (!dwtx_maxval_ok(px.maxval))
+	if (!px.range_ok())
 		return DWTX_ERR_ARG;
 	if (px.flips && (!px.offs || W > px.flip_w || H > px.flip_h))   // (a picture is mirrored inside its window: the mirrored index stays in it)
 		return DWTX_ERR_ARG;
@@ -3342,6 +3404,9 @@ int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *p
 		break;
 	case DWTX_SAMPLE_U16:
 		launch_pixels_from_planes<uint16_t>(ctx, grid, px, planes, g, f);
+		break;
+	case DWTX_SAMPLE_S16:
+		launch_pixels_from_planes<int16_t>(ctx, grid, px, planes, g, f);
 		break;
 	case DWTX_SAMPLE_F32:
 		launch_pixels_from_planes<float>(ctx, grid, px, planes, g, f);
@@ -3462,10 +3527,12 @@ static FwdSource fwd_source(const dwtx_pixels *px, bool src16)
 		const int src = (px->kind == DWTX_SAMPLE_F32 ? SRC_F32 : SRC_H16) + (rgb ? SRC_F32P - SRC_F32 : 0) + (far ? SRC_F32D - SRC_F32 : 0);
 		return { src, rgb && !far, wide_cstride(*px) };
 	}
+	const bool sgn = px->kind == DWTX_SAMPLE_S16;   // (deep() too: the deep sources' signed twins)
 	if (px->channels != 3)
-		return { deep ? SRC_U16 : SRC_U8, false, 0 };
-	const int src = px->planar() ? (deep ? SRC_RGBP16 : SRC_RGBP8)
+		return { sgn ? SRC_S16 : deep ? SRC_U16 : SRC_U8, false, 0 };
+	const int src = px->planar() ? (sgn ? SRC_RGBP16S : deep ? SRC_RGBP16 : SRC_RGBP8)
 		: px->rgbx8()            ? (bgr ? SRC_BGRX8 : SRC_RGBX8)
+		: sgn                    ? (bgr ? SRC_BGR16S : SRC_RGB16S)
 		: deep                   ? (bgr ? SRC_BGR16 : SRC_RGB16)
 		                         : (bgr ? SRC_BGR8 : SRC_RGB8);
 	return { src, !deep, wide_cstride(*px) };
@@ -3495,6 +3562,10 @@ static WideKernel fwd_wide_kernel(int src, bool hist, bool flip_y = false)
 		{ k_fwd_float_w<FloatPix<Half16, false, true>, false>, nullptr },
 		{ k_fwd_float_w<FloatPix<float, true, true>, false>, nullptr },
 		{ k_fwd_float_w<FloatPix<Half16, true, true>, false>, nullptr },
+		{ k_fwd_level_w<false, SRC_S16>, nullptr },
+		{ k_fwd_level_w<false, SRC_RGB16S>, nullptr },
+		{ k_fwd_level_w<false, SRC_RGBP16S>, nullptr },
+		{ k_fwd_level_w<false, SRC_BGR16S>, nullptr },
 	};
 	// the same sources for the windows of a flipped call (FY; pixels only: a band has no windows)
 	static const WideKernel KY[SRC_COUNT][2] = {
@@ -3518,6 +3589,10 @@ static WideKernel fwd_wide_kernel(int src, bool hist, bool flip_y = false)
 		{ k_fwd_float_w<FloatPix<Half16, false, true>, false, true>, nullptr },
 		{ k_fwd_float_w<FloatPix<float, true, true>, false, true>, nullptr },
 		{ k_fwd_float_w<FloatPix<Half16, true, true>, false, true>, nullptr },
+		{ k_fwd_level_w<false, SRC_S16, true>, nullptr },
+		{ k_fwd_level_w<false, SRC_RGB16S, true>, nullptr },
+		{ k_fwd_level_w<false, SRC_RGBP16S, true>, nullptr },
+		{ k_fwd_level_w<false, SRC_BGR16S, true>, nullptr },
 	};
 	return flip_y ? KY[src][hist] : K[src][hist];
 }
@@ -3529,7 +3604,7 @@ static WideKernel fwd_wide_kernel(int src, bool hist, bool flip_y = false)
 static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_pixels *px, int W, int H, int nplanes,
 	const dwtx_hist_sink *sink = nullptr, unsigned *hist_levels = nullptr, dwtx_p16 p16 = dwtx_p16{ nullptr, 0u })
 {
-	if (px && ((px->deep_source() && (sink || p16.planes)) || (px->is_float() && !dwtx_maxval_ok(px->maxval))))
+	if (px && ((px->deep_source() && (sink || p16.planes)) || (px->is_float() && !px->range_ok())))
 		return DWTX_ERR_ARG;
 	if (hist_levels)
 		*hist_levels = 0u;
@@ -3614,8 +3689,10 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			a.src_ps = (long)px->image_stride;
 			a.spitch = (int)px->pitch(W);
 			a.grid = win_grid(*px);
-			if (px->is_float())
-				a.maxval = px->maxval;   // (what the quantiser clamps at; no other forward source reads it)
+			if (px->is_float()) {
+				a.maxval = px->maxval;   // (what the quantiser clamps at; no other forward source reads them)
+				a.minval = px->minval;
+			}
 		} else {
 			a.src = src;
 			a.src_ps = src_ps;
@@ -3699,6 +3776,8 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 // and that the pitch fits their int.  Pixels with a step (dwtx_pixels::pixel_step): only 8-bit RGB in 4-byte pixels, which the
 // Rgbx8 / PIX_STEP4 instances address with the constant 4; the others would be read and written with dense addressing.
 // Any other view goes through the general conversions (dwtx_pixels_to_planes / dwtx_planes_to_pixels) — flipped windows
+// Signed samples (int16_t) qualify as deep ones do: the deep sources' signed twins read them, the deep sinks write them with the
+// lower clamp (LevelArgs::minval), which the float sources and sinks take as well.
 // A flipped call's windows (dwtx_pixels::flips) carry flags in their table entries that only win_off_flip takes apart: a SOURCE
 // qualifies when no window carries DWTX_FLIP_X (flip_wide: the FY instances of the wide forward kernels read it), a destination
 // (flip_sink: the FL instances of the wide inverse kernels write it) with any flags, a mirrored one if the windows' width is on the quad.
@@ -3969,6 +4048,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 			a.llpitch = (int)px->pitch(W);
 			a.grid = win_grid(*px);
 			a.maxval = px->deep() || px->is_float() ? px->maxval : 0;   // (float sinks clamp at whatever the maxval is, 255 included)
+			a.minval = px->minval;   // (0 but for int16_t samples and the float views of the signed calls)
 		} else if (t == 0) {
 			a.ll = out;
 			a.ll_ps = full_ps;
@@ -4029,7 +4109,7 @@ extern "C" int dwtx_transformation_inv(dwtx_ctx *ctx, int32_t *out, const int32_
 
 int dwtx_inv_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *in, int W, int H, int n, const dwtx_p16 *p16)
 {
-	if (!px.base || W < 2 || H < 2 || (px.channels != 1 && px.channels != 3) || px.maxval < 1 || px.maxval > 65535 || !dwtx_pixels_ok(px, W, H))
+	if (!px.base || W < 2 || H < 2 || (px.channels != 1 && px.channels != 3) || !px.range_ok() || !dwtx_pixels_ok(px, W, H))
 		return DWTX_ERR_ARG;
 	return lift_inv(ctx, nullptr, &px, in, W, H, n * px.channels, p16);
 }

@@ -349,7 +349,7 @@ int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
  * windows.  The streams are those of the interleaved copy: the .dwt format knows nothing of the layout. */
 typedef struct dwtx_view {
 	void  *dev;            /* first sample of window 0 */
-	int    sample_bytes;   /* 1: uint8_t, 2: native-endian uint16_t (deep pixels) */
+	int    sample_bytes;   /* 1: uint8_t, 2: native-endian uint16_t (deep pixels; int16_t in the dwtx_*_view_signed calls) */
 	int    channels;       /* 1 or 3 (interleaved, or planar: channel_stride) */
 	int    maxval;         /* decode: clamp bound (255 required when sample_bytes == 1); encode ignores it (but dwtx_encode_view_float: the quantiser's clamp) */
 	int    cols;           /* windows per band; 0 or >= n: all n windows in one band */
@@ -632,6 +632,46 @@ int dwtx_decode_view_flip(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stre
 int dwtx_view_flip_plan(const dwtx_view *v, size_t pixel_step, int W, int H, int n, const void *const *host_windows,
 	int flip, const unsigned char *host_flips, int dst, long long *origin /* [n] */, long long *pitch /* [n] */, long long *step /* [n] */);
 
+/* ---- signed samples: int16_t pictures coded as they are ------------------------------------------------------------------------
+ * The most general call of each direction — dwtx_encode_view_flip and dwtx_decode_view_flip — for pictures whose samples are
+ * signed: CT slices in Hounsfield units, elevation tiles, sensor frames after black-level subtraction, residuals.  Nothing in
+ * the algorithm knows a sign of the samples: encode.c:97-131 codes signs in the root image and in every plane (Co and Cg are
+ * negative in every RGB picture), and image.h:53-65 is reversible on any int.  The .dwt format is unchanged, with no new field:
+ * the coded picture is the signed integers as they lie, RGB through YCoCg-R on signed ints.  The range is the caller's knowledge,
+ * as maxval is: [minval, maxval] with -32768 <= minval < maxval <= 32767.  With R = maxval - minval, the decoder's clamps
+ * (image.h:41-43, pnm.h:108) become: gray and Y to [minval, maxval], Co and Cg to [-R, R], every output sample to [minval,
+ * maxval] — with minval = 0 today's clamps; they only act on streams that were cut short.  (No reference counterpart beyond
+ * those lines: the reference reads and writes 8-bit PNM.)
+ * Everything the two flip calls say about their arguments holds word for word; `minval` is the one argument more.
+ * Encode, integer samples (fmt NULL): src->sample_bytes must be 2; the samples are native-endian int16_t and are coded as they
+ * are; minval and src->maxval are not read.  Float samples (fmt given): the quantiser of dwtx_encode_view_float with
+ * v = min(max(q, minval), maxval); NaN and -0.0 -> 0, clamped into the range; +inf -> maxval, -inf -> minval.  Streams and
+ * dev_info are byte for byte those of the reference's stages (encode.c:155-221) on that integer picture: the same bytes as
+ * dwtx_encode_device16's where no sample is negative.  dwtx_encode_bound16 is the safe out_stride.  A picture that needs more
+ * than 16 bit planes is refused as ever (dev_info[i].error = 1, the others of its batch are coded): with R <= 4095 none is,
+ * gray ones with R <= 8191 neither.
+ * Decode: the upper bound is dst->maxval.  Integer destinations are int16_t (sample_bytes 2), two's complement.  Float
+ * destinations receive (float)v * scale + bias of the signed, clamped v, under dwtx_decode_view_float's rounding contract.
+ * Everything the view calls guarantee holds word for word: nothing written outside the ow x oh rectangle, the disjointness
+ * rules, status 1 / 2 windows untouched, crops, lists, flips, reduced pictures in their corners, planar, step, B-G-R.
+ * Equivalences: fmt given and minval == 0: the call IS the flip call and takes its path.  Integer samples all in [0, 32767]: the
+ * encode gives the bytes of the unsigned call.  minval == 0: the decode gives the unsigned call's samples bit for bit.
+ * Route: signed pictures, and float sources with minval < 0, take the deep pictures' route in every respect (histograms from
+ * the entropy stage's own pass, no 16-bit ring planes; DWTX_OPT_NO_PIXELS16 covers them).  Wherever a uint16_t view is read /
+ * written by the transform's finest level itself, an int16_t view of the same layout is too — gray, interleaved, planar and
+ * B-G-R, windows and lists, bottom-up both ways and mirrored decodes — and float views keep their path whatever minval is;
+ * every other view goes through the general conversions: the same bytes.
+ * DWTX_ERR_ARG (with a dwtx_last_error() text, nothing written): a range outside the rule above (decodes, and float encodes
+ * with minval != 0); sample_bytes 1 without fmt; and everything the flip calls refuse. */
+int dwtx_encode_view_signed(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order,
+	const dwtx_float_format *fmt /* NULL: int16_t samples */, const void *const *host_windows /* NULL: the view's own grid */,
+	int flip, const unsigned char *host_flips /* [n] or NULL */, int minval,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
+int dwtx_decode_view_signed(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, void *const *host_windows /* NULL: the view's own grid */,
+	int flip, const unsigned char *host_flips, int minval, dwtx_decode_info *host_info);
+
 /* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
  * interior, right column, bottom row, corner, in that order, those that exist — each a cols x rows grid of W x H tiles
  * whose first tile's corner is (x0, y0): one dwtx_encode_view / dwtx_decode_view call per group.  Per axis, with
@@ -684,6 +724,14 @@ int dwtx_encode_images16(dwtx_ctx *ctx, const uint16_t *host_pix, int W, int H, 
 	uint8_t *host_out, size_t out_stride, size_t *out_lens, dwtx_stats *stats);
 int dwtx_decode_images16(dwtx_ctx *ctx, const uint8_t *host_streams, size_t stream_stride, const size_t *lens, int n,
 	int pixels_max, uint16_t *host_pix, size_t pix_stride, int maxval, int *outW, int *outH, int *outC, dwtx_decode_info *infos);
+
+/* dwtx_encode_images16 / dwtx_decode_images16 with native-endian int16_t pixels, coded as they are (see dwtx_encode_view_signed
+ * for what that means, and for the clamps a decode applies at [minval, maxval], -32768 <= minval < maxval <= 32767, else
+ * DWTX_ERR_ARG): the same staging, parts and errors. */
+int dwtx_encode_images_s16(dwtx_ctx *ctx, const int16_t *host_pix, int W, int H, int C, int n, long capacity,
+	uint8_t *host_out, size_t out_stride, size_t *out_lens, dwtx_stats *stats);
+int dwtx_decode_images_s16(dwtx_ctx *ctx, const uint8_t *host_streams, size_t stream_stride, const size_t *lens, int n,
+	int pixels_max, int16_t *host_pix, size_t pix_stride, int minval, int maxval, int *outW, int *outH, int *outC, dwtx_decode_info *infos);
 
 #ifdef __cplusplus
 }
