@@ -174,6 +174,26 @@ def view_list_check(pointers, W, H, channels=1, row_pitch=None, channel_stride=0
     return rc, (lib.dwtx_last_error().decode(errors="replace") if rc else "")
 
 
+def view_delta_check(fields, base_fields, pointer, base_pointer, sample_bytes=1, base_sample_bytes=None, signed=False, minval=0, maxval=None, dst=True):
+    """dwtx_view_delta_check: what encode_view (dst=False) and decode_view (dst=True) with base= say to two grid views ->
+    (rc, text): (0, "") for a pair they take, else the error code and the text of the refusal.  fields, base_fields:
+    view_fields dicts (strides in samples) of the view and of its base; pointer, base_pointer: their first samples' addresses
+    as plain integers, never dereferenced.  Host arithmetic only: needs no device."""
+    lib = _lib.load()
+    if base_sample_bytes is None:
+        base_sample_bytes = sample_bytes
+    if maxval is None:
+        maxval = 255 if sample_bytes == 1 else 32767 if signed else 65535
+
+    def view(f, ptr, sb):
+        return View(ptr or None, sb, f["channels"], maxval, f["cols"], f["row_pitch"], f["image_stride"], f["band_stride"], f["channel_stride"])
+
+    v, vb = view(fields, pointer, sample_bytes), view(base_fields, base_pointer, base_sample_bytes)
+    rc = lib.dwtx_view_delta_check(C.byref(v), fields["pixel_step"], C.byref(vb), base_fields["pixel_step"], 1 if signed else 0, int(minval),
+                                   fields["W"], fields["H"], fields["n"], 1 if dst else 0)
+    return rc, (lib.dwtx_last_error().decode(errors="replace") if rc else "")
+
+
 FLIPS = {"": 0, "x": 1, "y": 2, "xy": 3, "yx": 3}   # enum DWTX_FLIP_X = 1, DWTX_FLIP_Y = 2 (include/dwtx.h): a mask
 
 
@@ -698,7 +718,26 @@ class Context:
                  f["channel_stride"])
         return v, f["W"], f["H"], f["channels"], f["n"], f["pixel_step"]
 
-    def encode_view(self, t, capacity=0, out=None, info=None, stepped=False, order="rgb", flip=None, signed=False):
+    def _delta_views(self, t, base, maxval, stepped, signed, flip, levels_max=-1):
+        """The `base=` keyword of encode_view / decode_view -> the two views of a delta call, or a ValueError before any device
+        call: flips, float tensors, levels_max, and a base of another dtype or shape than `t` are not the delta calls'."""
+        torch = self.torch
+        if flip is not None:
+            raise ValueError("base= does not combine with flip (the delta calls take no flips)")
+        if levels_max != -1:
+            raise ValueError("base= does not combine with levels_max (a coarse residual has no base of its size)")
+        for what, x in (("the tensor", t), ("base", base)):
+            if not hasattr(x, "dtype") or x.dtype in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
+                raise ValueError(f"base= takes integer tensors: {what} holds {getattr(x, 'dtype', type(x))}")
+        if base.dtype != t.dtype:
+            raise ValueError(f"base= needs the tensor's dtype {t.dtype}, not {base.dtype}")
+        if tuple(base.shape[-3:]) != tuple(t.shape[-3:]) or base.numel() != t.numel():   # (a grid of tiles against a stack of as many: fine)
+            raise ValueError(f"base= needs the tensor's windows, {t.numel() // max(1, t[..., 0, 0, 0].numel())} of {tuple(t.shape[-3:])}, not shape {tuple(base.shape)}")
+        v, W, H, Cn, n, step = self._view(t, maxval, stepped, signed=signed)
+        vb, _, _, _, _, bstep = self._view(base, None, stepped, signed=signed)
+        return v, vb, W, H, Cn, n, step, bstep
+
+    def encode_view(self, t, capacity=0, out=None, info=None, stepped=False, order="rgb", flip=None, signed=False, base=None):
         """dwtx_encode_view: the windows of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (a slice, a crop, a
         grid of tiles, a channel-first batch permuted to channel-last: see _view) -> (streams uint8 [n,stride], info uint8
         [n,sizeof(StreamInfo)]) on device, as encode_device / encode_device16 give for the contiguous copy; async.
@@ -710,9 +749,23 @@ class Context:
         signed=True: dwtx_encode_view_signed — an int16 tensor (nothing else) whose samples are the signed integers they
         look like: CT slices in Hounsfield units, elevation tiles, residuals; every other keyword keeps its meaning.
         Without it an int16 tensor stays what it has always been here: the carrier of uint16 bytes (torch's uint16 has few
-        operators on the device), so that a picture that crosses zero is read as one that jumps by 65535 there."""
+        operators on the device), so that a picture that crosses zero is read as one that jumps by 65535 there.
+        base: dwtx_encode_view_delta — a tensor of `t`'s dtype, windows [H,W,C] and number of windows (any strides a view
+        takes, its own pitch, grid, planar or interleaved form and step): the streams are those of the integer picture `t - base`, which is never built and
+        need not fit any sample type.  Both tensors are only read: `t[1:]` against `t[:-1]` is one call.  Combines with
+        stepped, order and signed; not with flip.  The streams' slots are dwtx_encode_bound16's, 8-bit pictures included."""
         order = view_order(order)
         torch = self.torch
+        if base is not None:
+            v, vb, W, H, Cn, n, step, bstep = self._delta_views(t, base, None, stepped, signed, flip)
+            stride = self.lib.dwtx_encode_bound16(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
+            if out is None:
+                out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
+            if info is None:
+                info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
+            _check(self.lib.dwtx_encode_view_delta(self.h, C.byref(v), step, C.byref(vb), bstep, order, 1 if signed else 0, W, H, n, capacity,
+                                                   _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view_delta")
+            return out, info
         v, W, H, Cn, n, step = self._view(t, None, stepped, signed=signed)
         flips = view_flips(flip, n)
         bound = self.lib.dwtx_encode_bound16 if v.sample_bytes == 2 else self.lib.dwtx_encode_bound
@@ -775,7 +828,8 @@ class Context:
                                                _ptr(info)), "dwtx_encode_view_float")
         return out, info
 
-    def decode_view(self, streams, lens, into, maxval=None, levels_max=-1, stepped=False, order="rgb", flip=None, signed=False, minval=None):
+    def decode_view(self, streams, lens, into, maxval=None, levels_max=-1, stepped=False, order="rgb", flip=None, signed=False, minval=None,
+                    base=None):
         """dwtx_decode_view: device streams [n,stride] + int64 lens -> the windows of the strided device tensor `into`
         ([n,H,W,C] or [bands,cols,H,W,C]), each picture in its window's top-left corner at the size its stream supports;
         nothing else of `into`'s storage is written.  maxval: the deep pictures' (default 65535).  Returns the list of
@@ -786,10 +840,23 @@ class Context:
         corner where its pixel (0, 0) lies.
         signed=True: dwtx_decode_view_signed — `into` is an int16 tensor (nothing else) that receives signed samples;
         [minval, maxval] (defaults -32768 and 32767) is the range the pictures were encoded from, what the clamps of a stream
-        that was cut short act at.  Without it an int16 tensor is the carrier of uint16 bytes, as for encode_view."""
+        that was cut short act at.  Without it an int16 tensor is the carrier of uint16 bytes, as for encode_view.
+        base: dwtx_decode_view_delta — the streams hold residuals against `base` (encode_view's keyword): each window
+        receives `(base + d).clamp(minval, maxval)` with d the decoded residual under the clamps for [-R, R], R = maxval -
+        minval; a whole stream gives back the picture exactly.  A window whose stream is unreadable, or cut before its finest
+        level, stays as it is (the DecodeInfo says which).  `base=into` decodes in place; otherwise no window of `into` may
+        meet one of `base` (view_delta_check).  Not with flip or levels_max."""
         order = view_order(order)
         torch = self.torch
         lo, maxval = self._signed_range(signed, minval, maxval)
+        if base is not None:
+            v, vb, W, H, Cn, n, step, bstep = self._delta_views(into, base, maxval, stepped, signed, flip, levels_max)
+            assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
+            assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
+            infos = (DecodeInfo * n)()
+            _check(self.lib.dwtx_decode_view_delta(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, C.byref(v), step, C.byref(vb), bstep,
+                                                   order, 1 if signed else 0, lo if signed else 0, C.cast(infos, C.c_void_p)), "dwtx_decode_view_delta")
+            return list(infos)
         v, W, H, Cn, n, step = self._view(into, maxval, stepped, signed=signed)
         flips = view_flips(flip, n)
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0

@@ -173,6 +173,10 @@ SYMBOLS = {
                                      C.POINTER(_vp), _i, C.POINTER(C.c_ubyte), _i, _vp]),
     "dwtx_encode_images_s16": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp, _vp]),
     "dwtx_decode_images_s16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    # delta views: a second view, the base pictures', with a pixel step of its own
+    "dwtx_encode_view_delta": (_i, [_vp, C.POINTER(View), _sz, C.POINTER(View), _sz, _i, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
+    "dwtx_decode_view_delta": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, C.POINTER(View), _sz, C.POINTER(View), _sz, _i, _i, _i, _vp]),
+    "dwtx_view_delta_check": (_i, [C.POINTER(View), _sz, C.POINTER(View), _sz, _i, _i, _i, _i, _i, _i]),
     "dwtx_tile_groups": (_i, [_i, _i, _i, C.POINTER(TileGroup)]),
     "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }

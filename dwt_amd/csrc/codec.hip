@@ -358,6 +358,8 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 		const dwtx_decode_info &I = host_info[first];
 		const int lo = I.level + 1;                                          // decode.c:251
 		const int ow = g.widths[lo], oh = g.heights[lo];
+		if (px.is_delta() && lo != g.levels)   // (a delta view: a coarse residual has no base of its size — the group's windows stay as they are)
+			return DWTX_OK;
 		if (!px.row_pitch && (size_t)ow * oh * C > px.image_stride)   // (dense slots; a window with a pitch holds its own corner)
 			return DWTX_ERR_ARG;
 		int *miss = nullptr;
@@ -1186,6 +1188,127 @@ extern "C" int dwtx_decode_view_signed(dwtx_ctx *ctx, const uint8_t *dev_streams
 {
 	return decode_view_flip(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h, host_origins,
 		host_windows, flip, host_flips, host_info, &minval);
+}
+
+// ---- delta views (include/dwtx.h): a picture coded as its difference from a base view ------------------------------
+
+// The units of a grid view — its n windows, or the 3n planes of planar RGB, as in list_windows — as byte spans [first, first +
+// (H-1)*row_pitch + row) of the address space, appended to `spans` with `tag`
+struct DeltaSpan {
+	uintptr_t at, end;
+	int tag, window;
+};
+static void delta_spans(const dwtx_pixels &px, int W, int H, int n, int tag, std::vector<DeltaSpan> *spans)
+{
+	const size_t row = px.planar() ? (size_t)W : px.stepped() ? (size_t)(W - 1) * px.pixel_step + px.channels : (size_t)W * px.channels;
+	const size_t span = (size_t)(H - 1) * px.pitch(W) + row;
+	for (int i = 0; i < n; ++i) {
+		const size_t w = px.first + (size_t)i;
+		const size_t off = px.one_band() ? w * px.image_stride : w / (size_t)px.cols * px.band_stride + w % (size_t)px.cols * px.image_stride;
+		for (int c = 0; c < (px.planar() ? 3 : 1); ++c) {
+			const uintptr_t at = (uintptr_t)px.at(off + (size_t)c * px.channel_stride);
+			spans->push_back(DeltaSpan{ at, at + px.bytes(span), tag, i });
+		}
+	}
+}
+
+// The two views of a delta call -> one dwtx_pixels that carries both (dwtx_pixels::delta), checked: each view as the *_view_order /
+// *_view_signed calls check theirs (pixels_of_view; the base is only ever read, and its maxval is not), the shared sample type,
+// and for a decode that the base is the destination itself — every field that places a sample equal: the in-place decode, each
+// sample read and written by the same lane — or that no unit of the destination meets a unit of the base.  One sort and one
+// sweep: by address, a span that begins before a span of the other view has ended meets it.
+static int delta_view(const dwtx_view *v, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step, int order, int sgn, int minval,
+	int W, int H, int n, bool dst, dwtx_pixels *px)
+{
+	if (!v || !base) {
+		dwtx_set_error("delta view: no view or no base view");
+		return DWTX_ERR_ARG;
+	}
+	if (sgn != 0 && sgn != 1) {
+		dwtx_set_error("delta view: sgn %d (0: uint8_t / uint16_t samples, 1: int16_t samples)", sgn);
+		return DWTX_ERR_ARG;
+	}
+	if (!sgn && minval != 0) {
+		dwtx_set_error("delta view: minval %d without sgn (unsigned samples start at 0)", minval);
+		return DWTX_ERR_ARG;
+	}
+	if (v->channels != base->channels) {
+		dwtx_set_error("delta view: the view has %d channels, its base %d", v->channels, base->channels);
+		return DWTX_ERR_ARG;
+	}
+	if (v->sample_bytes != base->sample_bytes) {
+		dwtx_set_error("delta view: the view has %d-byte samples, its base %d-byte ones", v->sample_bytes, base->sample_bytes);
+		return DWTX_ERR_ARG;
+	}
+	const int *lower = sgn ? &minval : nullptr;
+	dwtx_pixels bp;
+	if (const int rc = pixels_of_view(v, pixel_step, order, W, H, n, dst, px, -1, false, nullptr, lower))
+		return rc;
+	if (const int rc = pixels_of_view(base, base_pixel_step, order, W, H, n, false, &bp, -1, false, nullptr, lower))
+		return rc;
+	const bool same = px->base == bp.base && px->row_pitch == bp.row_pitch && px->image_stride == bp.image_stride && px->cols == bp.cols &&
+		px->band_stride == bp.band_stride && px->channel_stride == bp.channel_stride && px->pixel_step == bp.pixel_step;
+	if (dst && !same) {
+		std::vector<DeltaSpan> spans;
+		try {
+			spans.reserve(6 * (size_t)n);
+			delta_spans(*px, W, H, n, 0, &spans);
+			delta_spans(bp, W, H, n, 1, &spans);
+		} catch (...) {
+			return DWTX_ERR_NOMEM;
+		}
+		std::sort(spans.begin(), spans.end(), [](const DeltaSpan &a, const DeltaSpan &b) { return a.at < b.at; });
+		uintptr_t end[2] = { 0, 0 };
+		int last[2] = { -1, -1 };
+		for (const DeltaSpan &s : spans) {
+			const int other = 1 - s.tag;
+			if (s.at < end[other]) {
+				const int wd = s.tag ? last[other] : s.window, wb = s.tag ? s.window : last[other];
+				dwtx_set_error("delta view: window %d of the destination meets window %d of the base (neither the same view, which decodes in place, "
+					"nor disjoint spans: a decode that writes what it has yet to read is a chain, not one call)", wd, wb);
+				return DWTX_ERR_ARG;
+			}
+			if (s.end > end[s.tag]) {
+				end[s.tag] = s.end;
+				last[s.tag] = s.window;
+			}
+		}
+	}
+	px->delta.base = bp.base;
+	px->delta.image_stride = bp.image_stride;
+	px->delta.row_pitch = bp.row_pitch;
+	px->delta.band_stride = bp.band_stride;
+	px->delta.first = bp.first;
+	px->delta.channel_stride = bp.channel_stride;
+	px->delta.pixel_step = bp.pixel_step;
+	px->delta.cols = bp.cols;
+	return DWTX_OK;
+}
+
+extern "C" int dwtx_view_delta_check(const dwtx_view *v, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step,
+	int sgn, int minval, int W, int H, int n, int dst)
+{
+	dwtx_pixels px;
+	return delta_view(v, pixel_step, base, base_pixel_step, DWTX_ORDER_RGB, sgn, minval, W, H, n, dst != 0, &px);
+}
+
+extern "C" int dwtx_encode_view_delta(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step,
+	int order, int sgn, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	dwtx_pixels px;
+	if (const int rc = delta_view(src, pixel_step, base, base_pixel_step, order, sgn, 0, W, H, n, false, &px))
+		return rc;
+	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
+}
+
+extern "C" int dwtx_decode_view_delta(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, const dwtx_view *dst, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step, int order, int sgn, int minval,
+	dwtx_decode_info *host_info)
+{
+	dwtx_pixels px;
+	if (const int rc = delta_view(dst, pixel_step, base, base_pixel_step, order, sgn, minval, W, H, n, true, &px))
+		return rc;
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, -1, px, host_info);
 }
 
 // one axis of dwtx_tile_groups: `full` tiles of `tile`, then one of `last` (0: none)

@@ -217,7 +217,19 @@ template <class F> char *carve(dwtx_ctx *ctx, int slot, F &&fn)
 // deep pictures' route — no histograms from the transform, no 16-bit ring planes: those bounds are for samples in [0, 255] —
 // through the wide kernels wherever a deep view of the same layout goes through them (lift.hip: the deep sources' signed twins,
 // the deep and float sinks with the lower clamp), else through the general conversions, which know the bound too.
+// A delta view (dwtx_encode_view_delta / dwtx_decode_view_delta) carries a second grid of windows, its base pictures (`delta`:
+// where they lie; kind, channels, sample_bytes and order are the view's own): the picture that is coded is S - B on integers,
+// the sample that is written min(max(B + d, minval), maxval) with d the residual under the signed clamps for [-R, R], R = maxval -
+// minval.  A residual has twice its pictures' range, so a delta view takes the deep pictures' route whatever its sample size
+// (deep() and deep_source() hold): through the wide kernels where both views qualify and are gray, or interleaved 8-bit RGB
+// (lift.hip: the delta sources and sinks), else through the general conversions' delta instances, which take every pair of layouts.
 enum dwtx_sample_kind { DWTX_SAMPLE_U8 = 0, DWTX_SAMPLE_U16, DWTX_SAMPLE_S16, DWTX_SAMPLE_F32, DWTX_SAMPLE_F16, DWTX_SAMPLE_BF16 };
+// where the base pictures of a delta view lie: a grid of its own (dwtx_pixels' fields of the same names); base null: no delta view
+struct dwtx_base_grid {
+	void *base = nullptr;
+	size_t image_stride = 0, row_pitch = 0, band_stride = 0, first = 0, channel_stride = 0, pixel_step = 0;
+	int cols = 0;
+};
 struct dwtx_pixels {
 	void *base;            // the grid's window 0, first sample
 	int sample_bytes;      // 1 or 2; a float destination's 4 or 2 (kind says which samples they are)
@@ -245,9 +257,26 @@ struct dwtx_pixels {
 	// of it carries DWTX_FLIP_X (those need the windows' width on the quad: a mirrored quad is one aligned access)
 	bool flips = false, flip_wide = false, flip_sink = false, flip_x = false;
 	int flip_w = 0, flip_h = 0;
+	dwtx_base_grid delta;   // a delta view's base pictures, window for window (image() moves both grids; moved() keeps the base where it is)
 
-	// uint16_t or int16_t samples — and with them the kernel family that clamps at [minval, maxval] and keeps no 16-bit ring planes
-	bool deep() const { return kind == DWTX_SAMPLE_U16 || kind == DWTX_SAMPLE_S16; }
+	bool is_delta() const { return delta.base != nullptr; }
+	// the base pictures as a view of their own: the samples, the channels and their order are this view's
+	dwtx_pixels base_pixels() const
+	{
+		dwtx_pixels p = *this;
+		p.base = delta.base;
+		p.image_stride = delta.image_stride;
+		p.row_pitch = delta.row_pitch;
+		p.band_stride = delta.band_stride;
+		p.first = delta.first;
+		p.channel_stride = delta.channel_stride;
+		p.pixel_step = delta.pixel_step;
+		p.cols = delta.cols;
+		p.delta = dwtx_base_grid();
+		return p;
+	}
+	// uint16_t or int16_t samples, or a delta view of any — and with them the kernel family that clamps at [minval, maxval] and keeps no 16-bit ring planes
+	bool deep() const { return kind == DWTX_SAMPLE_U16 || kind == DWTX_SAMPLE_S16 || is_delta(); }
 	bool is_float() const { return kind >= DWTX_SAMPLE_F32; }
 	// int16_t samples, or a lower bound of their own: the range rule of the signed calls holds (range_ok)
 	bool signed_range() const { return kind == DWTX_SAMPLE_S16 || minval != 0; }
@@ -289,6 +318,12 @@ struct dwtx_pixels {
 			p.base = at(image_stride * i);
 		else
 			p.first += i;
+		if (is_delta()) {
+			if (delta.cols == 0)
+				p.delta.base = static_cast<char *>(delta.base) + bytes(delta.image_stride * i);
+			else
+				p.delta.first += i;
+		}
 		return p;
 	}
 	// the same layout somewhere else
@@ -345,6 +380,8 @@ static inline dwtx_pixels dwtx_pixels_float(void *pix, int kind, int channels, s
 // Of float views gray and planar RGB qualify, in both directions; interleaved float RGB takes the general way.
 // Flipped windows (dwtx_pixels::flips) qualify as their unflipped twins do: a destination (flip_sink) with any flags — a mirrored
 // window needs its width on the quad —, a source (flip_wide) unless one of its windows carries DWTX_FLIP_X.
+// A delta view (dwtx_pixels::delta) qualifies when the view and its base each would, both are dense pixels (no step, not planar),
+// and the pictures are gray — uint8_t, uint16_t or int16_t — or interleaved 8-bit RGB, in either order.
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H);
 // lift.hip: asks for the scratch planes every lifting call of a W*H transform over nplanes planes asks for
 int dwtx_lift_scratch(dwtx_ctx *ctx, int W, int H, int nplanes);

@@ -363,6 +363,12 @@ struct LevelArgsW {
 	FloatFmt fmt;     // inverse, float pixels behind dst8 (only the float sinks read it)
 	int ppw;          // the FY instances of the forward kernels: planes per window, 1 or 3 (which entry of the windows' table a plane reads)
 	int fh, fwq;      // the flipped instances of the inverse kernels (FL): the WINDOWS' height and quads per row (dwtx_pixels::flip_h, flip_w / 4)
+	// the delta sources of the forward kernels and the delta sinks of the inverse ones (dwtx_pixels::delta): the base pictures behind
+	// base8 as the pixels lie behind src8 / dst8 — their own window stride, pitch and grid, in samples; no other kernel reads them
+	const uint8_t *base8;
+	long base_ps;
+	int bpitch;
+	WinGrid bgrid;
 };
 
 // Per lane and subband: counts of "magnitude below 2^q" for q = 0..15 — nibbles of R for the last few coefficients
@@ -1124,7 +1130,9 @@ enum { SRC_I32 = 0, SRC_I16, SRC_U16, SRC_RGB16, SRC_RGBP16, SRC_U8, SRC_RGB8, S
 	// float pixels (FloatPix<> below), gray and planar (P) fp32 and fp16 / bf16: quantised to at most 255, and (D) beyond
 	SRC_F32, SRC_H16, SRC_F32P, SRC_H16P, SRC_F32D, SRC_H16D, SRC_F32PD, SRC_H16PD,
 	// int16_t pixels (dwtx_encode_view_signed): the twins of SRC_U16, SRC_RGB16, SRC_RGBP16 and SRC_BGR16 that widen with the sign
-	SRC_S16, SRC_RGB16S, SRC_RGBP16S, SRC_BGR16S, SRC_COUNT };
+	SRC_S16, SRC_RGB16S, SRC_RGBP16S, SRC_BGR16S,
+	// delta views (dwtx_encode_view_delta): the picture and its base, gray of the three sample types and interleaved 8-bit RGB in both orders
+	SRC_DELTA_U8, SRC_DELTA_U16, SRC_DELTA_S16, SRC_DELTA_RGB8, SRC_DELTA_BGR8, SRC_COUNT };
 template <int SRC>
 struct Band {};
 // 8-bit interleaved RGB pixels, of which each plane's workgroup takes its own YCoCg-R channel (image.h:52-65 fused; 8-bit
@@ -1149,6 +1157,7 @@ __device__ __forceinline__ long rgb_window(const LevelArgs &a, int plane, int &c
 
 struct FwdInt32 {
 	static constexpr bool FLOAT = false;   // (the float sources' used() takes the launch's arguments as well)
+	static constexpr bool DELTA = false;   // (the delta sources walk two views: rows() for base(), DeltaRows for the row pointer)
 	typedef I2 Pair;
 	typedef FwdRaw Used;
 	static constexpr int S = 2;
@@ -1160,6 +1169,7 @@ struct FwdInt32 {
 
 struct FwdPacked {
 	static constexpr bool FLOAT = false;
+	static constexpr bool DELTA = false;
 	typedef P2 Pair;
 	static constexpr int S = 2;
 	static constexpr bool RGB_GRID = false;
@@ -1328,6 +1338,134 @@ template <>
 struct FwdSrc<Bgrx8> : FwdSrc<Rgbx8> {
 	static __device__ __forceinline__ void lift(const FwdRawRgbx &r, int ch, int q, int lane, int nquads, P2 &lo, P2 &hi) { fwd_lift_p(row_p<true>(r, ch), q, lane, nquads, lo, hi); }
 };
+
+// ---- delta sources (dwtx_encode_view_delta): the finest level reads a picture S and its base B and lifts S - B ----
+// Sources of the int32 family (a residual has twice its pictures' range: no histograms, no 16-bit bands).  A lane loads its quad
+// and its edge piece of S and of B — two views with a window stride, a pitch and a grid each, of one layout: the same LaneAt
+// serves both — widens both by the sample type, and the row that is lifted is their difference, per colour before image.h:52-65
+// (the colour transform rounds: it does not commute with the subtraction).  Both rows' loads travel in one Loaded and are in
+// flight together, a batch ahead of their use, as every source's are.
+template <typename P>
+struct DeltaRows {
+	const P *s, *b;   // the same row of the picture's and of the base's window
+	int bpitch;
+};
+// a source's row r from its window's first row: a pointer and the wave's pitch, or both views of a delta source
+template <typename Ptr>
+__device__ __forceinline__ Ptr row_at(Ptr p, int r, int spitch) { return p + (long)r * spitch; }
+template <typename P>
+__device__ __forceinline__ DeltaRows<P> row_at(DeltaRows<P> p, int r, int spitch)
+{
+	DeltaRows<P> o = { p.s + (long)r * spitch, p.b + (long)r * p.bpitch, p.bpitch };
+	return o;
+}
+template <typename Raw>
+struct DeltaRaw {
+	Raw s, b;
+};
+template <typename Raw>
+__device__ __forceinline__ DeltaRaw<Raw> hold(const DeltaRaw<Raw> &r)
+{
+	DeltaRaw<Raw> o = { hold(r.s), hold(r.b) };
+	return o;
+}
+__device__ __forceinline__ FwdRaw operator-(const FwdRaw &a, const FwdRaw &b)
+{
+	FwdRaw o;
+	o.x = make_int4(a.x.x - b.x.x, a.x.y - b.x.y, a.x.z - b.x.z, a.x.w - b.x.w);
+	o.xr = a.xr - b.xr;
+	o.left = make_int2(a.left.x - b.left.x, a.left.y - b.left.y);
+	return o;
+}
+// a gray 8-bit row as ints (fwd_load_8: lane 0's edge word ends in x[4q-2], x[4q-1], the other lanes' begins with x[4q+4])
+__device__ __forceinline__ FwdRaw widen_8(const FwdRaw8 &r)
+{
+	FwdRaw o;
+	o.x = make_int4((int)(r.v & 255u), (int)((r.v >> 8) & 255u), (int)((r.v >> 16) & 255u), (int)(r.v >> 24));
+	o.xr = (int)(r.edge & 255u);
+	o.left = make_int2((int)((r.edge >> 16) & 255u), (int)(r.edge >> 24));
+	return o;
+}
+// byte k (a constant) of a lane's twelve, and of its eight edge bytes
+__device__ __forceinline__ int rgb_byte(const U32x3 &v, int k) { return (int)(((k < 4 ? v.x : k < 8 ? v.y : v.z) >> (8 * (k & 3))) & 255u); }
+__device__ __forceinline__ int rgb_byte(const U32x2 &v, int k) { return (int)(((k < 4 ? v.x : v.y) >> (8 * (k & 3))) & 255u); }
+// channel ch of image.h:52-65 on the difference of two interleaved 8-bit rows (FwdSrc<Rgb8>::load's layout: pixel p of the
+// quad in bytes 3p .. 3p+2; the edge: pixel 4q+4 in bytes 0 .. 2, or — lane 0 — pixels 4q-2 and 4q-1 in bytes 2 .. 7)
+template <bool BGR>
+__device__ __forceinline__ FwdRaw delta_rgb8(const FwdRawRgb &s, const FwdRawRgb &b, int ch)
+{
+	auto quad = [&](int k) { return ycocg_lies<BGR>(rgb_byte(s.abc, k) - rgb_byte(b.abc, k), rgb_byte(s.abc, k + 1) - rgb_byte(b.abc, k + 1), rgb_byte(s.abc, k + 2) - rgb_byte(b.abc, k + 2), ch); };
+	auto edge = [&](int k) { return ycocg_lies<BGR>(rgb_byte(s.e, k) - rgb_byte(b.e, k), rgb_byte(s.e, k + 1) - rgb_byte(b.e, k + 1), rgb_byte(s.e, k + 2) - rgb_byte(b.e, k + 2), ch); };
+	FwdRaw o;
+	o.x = make_int4(quad(0), quad(3), quad(6), quad(9));
+	o.xr = edge(0);
+	o.left = make_int2(edge(2), edge(5));
+	return o;
+}
+
+template <int SRC>
+struct FwdDeltaGray : FwdInt32 {
+	static constexpr bool DELTA = true;
+	typedef typename std::conditional<SRC == SRC_DELTA_U8, uint8_t, uint16_t>::type P;
+	typedef typename std::conditional<SRC == SRC_DELTA_U8, FwdRaw8, FwdRawS>::type Raw;
+	typedef DeltaRaw<Raw> Loaded;
+	static __device__ __forceinline__ DeltaRows<P> rows(const LevelArgsW &A, int plane, int &)
+	{
+		DeltaRows<P> o = { reinterpret_cast<const P *>(A.a.src8) + win_off(A.a.grid, A.a.src_ps, plane),
+			reinterpret_cast<const P *>(A.base8) + win_off(A.bgrid, A.base_ps, plane), A.bpitch };
+		return o;
+	}
+	static __device__ __forceinline__ LaneAt at(int q, int lane, int nquads) { return lane_at(q, lane, nquads, 4, SRC == SRC_DELTA_U8 ? 4 : 2); }
+	static __device__ __forceinline__ Loaded load(const DeltaRows<P> &row, const LaneAt &at, long, int)
+	{
+		if constexpr (SRC == SRC_DELTA_U8) {
+			Loaded r = { fwd_load_8(row.s, at), fwd_load_8(row.b, at) };
+			return r;
+		} else {
+			Loaded r = { fwd_load_s(row.s, at), fwd_load_s(row.b, at) };
+			return r;
+		}
+	}
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int)
+	{
+		if constexpr (SRC == SRC_DELTA_U8)
+			return widen_8(r.s) - widen_8(r.b);
+		else if constexpr (SRC == SRC_DELTA_S16)
+			return widen_s(r.s) - widen_s(r.b);
+		else
+			return widen_u(r.s) - widen_u(r.b);
+	}
+};
+template <>
+struct FwdSrc<Band<SRC_DELTA_U8>> : FwdDeltaGray<SRC_DELTA_U8> {};
+template <>
+struct FwdSrc<Band<SRC_DELTA_U16>> : FwdDeltaGray<SRC_DELTA_U16> {};
+template <>
+struct FwdSrc<Band<SRC_DELTA_S16>> : FwdDeltaGray<SRC_DELTA_S16> {};
+
+// interleaved 8-bit RGB: a workgroup column per plane, each taking its channel (as the deep interleaved source does)
+template <bool BGR>
+struct FwdDeltaRgb8 : FwdInt32 {
+	static constexpr bool DELTA = true;
+	typedef DeltaRaw<FwdRawRgb> Loaded;
+	static __device__ __forceinline__ DeltaRows<uint8_t> rows(const LevelArgsW &A, int plane, int &ch)
+	{
+		ch = plane % 3;
+		DeltaRows<uint8_t> o = { A.a.src8 + win_off(A.a.grid, A.a.src_ps, plane / 3), A.base8 + win_off(A.bgrid, A.base_ps, plane / 3), A.bpitch };
+		return o;
+	}
+	static __device__ __forceinline__ LaneAt at(int q, int lane, int nquads) { return lane_at(q, lane, nquads, 12, 8); }
+	static __device__ __forceinline__ Loaded load(const DeltaRows<uint8_t> &row, const LaneAt &at, long, int)
+	{
+		Loaded r = { FwdSrc<Rgb8>::load(row.s, at, 0, 0), FwdSrc<Rgb8>::load(row.b, at, 0, 0) };
+		return r;
+	}
+	static __device__ __forceinline__ FwdRaw used(const Loaded &r, int ch) { return delta_rgb8<BGR>(r.s, r.b, ch); }
+};
+template <>
+struct FwdSrc<Band<SRC_DELTA_RGB8>> : FwdDeltaRgb8<false> {};
+template <>
+struct FwdSrc<Band<SRC_DELTA_BGR8>> : FwdDeltaRgb8<true> {};
 
 // ---- float sources (dwtx_encode_view_float): the finest level reads fp32, fp16 or bf16 samples and quantises them itself ----
 // The picture that is coded, per sample x of colour c: m = fl32(x * scale[c]), r = fl32(m + bias[c]) — two roundings, as the
@@ -1559,7 +1697,9 @@ __device__ __forceinline__ void fwd_level_body(const LevelArgsW &A, int bx, int 
 	int ch_rt = 0;
 	int spitch = a.spitch;   // (the wave's: negated for a bottom-up window)
 	const auto src = [&] {
-		if constexpr (FY) {
+		if constexpr (T::DELTA) {
+			return T::rows(A, plane, ch_rt);
+		} else if constexpr (FY) {
 			LevelArgs b = a;   // base() without a window: the pixels' first sample and the channel
 			b.grid = WinGrid{ 0u, 0u, 0, nullptr };
 			b.src_ps = 0;
@@ -1591,8 +1731,8 @@ __device__ __forceinline__ void fwd_level_body(const LevelArgsW &A, int bx, int 
 		else
 			return T::used(r, ch);
 	};
-	T::lift(use(T::load(src + (long)(2 * jfirst) * spitch, at, A.cstride, ch)), ch, q, lane, A.nquads, l0, h0);
-	auto rowp = [&](int r) { return src + (long)min(r, a.h - 1) * spitch; };
+	T::lift(use(T::load(row_at(src, 2 * jfirst, spitch), at, A.cstride, ch)), ch, q, lane, A.nquads, l0, h0);
+	auto rowp = [&](int r) { return row_at(src, min(r, a.h - 1), spitch); };
 	typename T::Used cur[2 * S];
 	typename T::Loaded nxt[2 * S];
 #pragma unroll
@@ -1966,6 +2106,62 @@ struct OutRow<uint8_t> {
 	static __device__ __forceinline__ void store(uint8_t *__restrict__ row, int qd, const type &v) { *reinterpret_cast<unsigned *>(row + 4 * qd) = v; }
 };
 
+// ---- delta sinks (dwtx_decode_view_delta): the finest level adds the base pictures' samples and clamps twice ----
+// DeltaPix<P> as a kernel's DstT / PixT: the pixels are P samples (uint8_t, uint16_t, int16_t) of a delta view.  A lane loads the
+// quad of the base B that lies where its own quad goes — from the base's own window, pitch and grid (LevelArgsW::base8 ..), a
+// batch ahead of its use, as every row is — and the sample it writes is min(max(B + d, lo), hi), d the inverse transform's value
+// under the clamps of the range [-R, R], R = hi - lo (R may be 65535: ints throughout).  Every sample is read and written by the
+// same lane, the read a batch before the write, and the lanes and rows that only ride along (halo lanes, clamped rows) use nothing
+// of what they load: the base may be the destination itself (the in-place decode).  InvPix: what a kernel's pointer counts.
+template <typename P>
+struct DeltaPix {};
+struct NoBase {};   // the rows of a base in a kernel instance that has none
+__device__ __forceinline__ NoBase hold(NoBase) { return NoBase{}; }
+template <typename DstT>
+struct InvPix {
+	typedef DstT type;
+	typedef NoBase base;
+	static constexpr bool DELTA = false;
+};
+__device__ __forceinline__ int delta_sample(int v, int b, Clamp M)
+{
+	const int R = M.r();
+	const int d = v < -R ? -R : v > R ? R : v;
+	const int o = b + d;
+	return o < M.lo ? M.lo : o > M.hi ? M.hi : o;
+}
+template <typename P>
+struct OutRow<DeltaPix<P>> {
+	typedef typename std::conditional<sizeof(P) == 1, unsigned, uint2>::type type;   // four samples: the finished row, and the base's quad as it is loaded
+	static __device__ __forceinline__ type load(const P *row, int qd) { return *reinterpret_cast<const type *>(row + 4 * qd); }
+	static __device__ __forceinline__ int base_of(unsigned b, int k) { return (int)((b >> (8 * k)) & 255u); }
+	static __device__ __forceinline__ int base_of(uint2 b, int k)
+	{
+		const unsigned w = k < 2 ? b.x : b.y;
+		if (std::is_signed<P>::value)
+			return k & 1 ? (int)w >> 16 : (int)(short)(w & 0xffffu);
+		return (int)(k & 1 ? w >> 16 : w & 0xffffu);
+	}
+	static __device__ __forceinline__ type of(const Quad4 &v, Clamp M, const type &b)
+	{
+		unsigned o[4];
+#pragma unroll
+		for (int k = 0; k < 4; ++k)
+			o[k] = (unsigned)delta_sample(v.v[k], base_of(b, k), M);
+		if constexpr (sizeof(P) == 1)
+			return o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24);
+		else
+			return make_uint2((o[0] & 0xffffu) | (o[1] << 16), (o[2] & 0xffffu) | (o[3] << 16));   // (two's complement: int16_t samples)
+	}
+	static __device__ __forceinline__ void store(P *row, int qd, const type &v) { *reinterpret_cast<type *>(row + 4 * qd) = v; }
+};
+template <typename P>
+struct InvPix<DeltaPix<P>> {
+	typedef P type;
+	typedef typename OutRow<DeltaPix<P>>::type base;
+	static constexpr bool DELTA = true;
+};
+
 // ---- float sinks: the value an integer sink would write, as a float: v * scale + bias in fp32, then the sample's type ----
 // Two roundings, as torch's unfused `x.float() * scale + bias` has them.  hipcc contracts a * b + c into an fma by default, and
 // __fmul_rn / __fadd_rn are plain operators in a header compiled that way — they fuse all the same (v_fma_f32, and
@@ -2028,7 +2224,7 @@ struct OutRow<Half16> {
 };
 
 template <typename DstT>
-__device__ __forceinline__ DstT *inv_dst(const LevelArgs &a);
+__device__ __forceinline__ typename InvPix<DstT>::type *inv_dst(const LevelArgs &a);
 template <>
 __device__ __forceinline__ int *inv_dst<int>(const LevelArgs &a) { return a.ll; }
 template <>
@@ -2040,6 +2236,13 @@ __device__ __forceinline__ float *inv_dst<float>(const LevelArgs &a) { return re
 template <>
 __device__ __forceinline__ Half16 *inv_dst<Half16>(const LevelArgs &a) { return reinterpret_cast<Half16 *>(a.dst8); }
 // (planes lie one after the other; pixels may be windows of a frame)
+template <>
+__device__ __forceinline__ uint8_t *inv_dst<DeltaPix<uint8_t>>(const LevelArgs &a) { return a.dst8; }
+template <>
+__device__ __forceinline__ uint16_t *inv_dst<DeltaPix<uint16_t>>(const LevelArgs &a) { return reinterpret_cast<uint16_t *>(a.dst8); }
+template <>
+__device__ __forceinline__ int16_t *inv_dst<DeltaPix<int16_t>>(const LevelArgs &a) { return reinterpret_cast<int16_t *>(a.dst8); }
+
 template <typename DstT>
 __device__ __forceinline__ long inv_dst_off(const LevelArgs &a, int plane) { return win_off(a.grid, a.ll_ps, plane); }
 template <>
@@ -2164,13 +2367,23 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 	typedef OutRow<DstT> Out;
 	int opitch = a.llpitch;   // (the wave's: negated for a bottom-up window)
 	bool fx = false;
-	DstT *dst = inv_dst<DstT>(a);
+	typename InvPix<DstT>::type *dst = inv_dst<DstT>(a);
 	if constexpr (FL == 0)
 		dst += inv_dst_off<DstT>(a, plane);
 	else
 		dst += flip_dst<FL>(a.grid, a.ll_ps, plane, A.fh, opitch, fx);
 	const int qs = flip_q<FL>(qd, A.fwq, fx);   // the quad of the row that the lane's quad goes to
 	const InvAt at = inv_at(a, qd, A.nquads);
+	// a delta sink's base rows (DeltaPix<>): row r of the base's window at the lane's quad, clamped into the window
+	typedef typename InvPix<DstT>::base BaseRow;
+	auto load_base = [&](int r) {
+		if constexpr (InvPix<DstT>::DELTA) {
+			const typename InvPix<DstT>::type *b = reinterpret_cast<const typename InvPix<DstT>::type *>(A.base8) + win_off(A.bgrid, A.base_ps, plane);
+			return Out::load(b + (long)min(r, a.h - 1) * A.bpitch, min(qd, A.nquads - 1));
+		} else {
+			return NoBase{};
+		}
+	};
 
 	constexpr int S = 2;
 	const int jb4 = j0 > 0 ? j0 - 1 : 0;
@@ -2179,10 +2392,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 	InvRaw nxt[S], cur[S];
 	InvHalo nxtx[S];
 	HaloPairs curx[S];
+	BaseRow nxtb[2 * S], curb[2 * S];
 #pragma unroll
 	for (int s = 0; s < S; ++s) {
 		nxt[s] = inv_load_w(a, llp, det, j0 + 1 + s, at);
 		nxtx[s] = inv_load_halo(a, llp, det, j0 + 1 + s, at);
+		nxtb[2 * s] = load_base(2 * (j0 + s));
+		nxtb[2 * s + 1] = load_base(2 * (j0 + s) + 1);
 	}
 	typename Out::type orow[2 * S];   // a batch's rows wait here for the next iteration's stores
 	auto store_batch = [&](int jb) {
@@ -2201,6 +2417,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 		for (int s = 0; s < S; ++s) {
 			cur[s] = hold(nxt[s]);   // the one wait of the iteration
 			curx[s] = hold(nxtx[s]);
+			curb[2 * s] = hold(nxtb[2 * s]);
+			curb[2 * s + 1] = hold(nxtb[2 * s + 1]);
 		}
 		if (jb > j0)
 			store_batch(jb - S);
@@ -2209,6 +2427,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 			for (int s = 0; s < S; ++s) {
 				nxt[s] = inv_load_w(a, llp, det, jb + S + 1 + s, at);
 				nxtx[s] = inv_load_halo(a, llp, det, jb + S + 1 + s, at);
+				nxtb[2 * s] = load_base(2 * (jb + S + s));
+				nxtb[2 * s + 1] = load_base(2 * (jb + S + s) + 1);
 			}
 		}
 #pragma unroll
@@ -2219,7 +2439,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w(LevelArgsW A)
 			RowLH e, o, ex, ox;
 			inv_cols(a, jj, c, cur[s], e, o);
 			inv_cols(a, jj, cx, curx[s], ex, ox);
-			if constexpr (FloatSample<DstT>::value) {
+			if constexpr (InvPix<DstT>::DELTA) {
+				orow[2 * s] = Out::of(inv_row_vals_h(qd, A.nquads, lane, e, ex), clamp_of(a), curb[2 * s]);
+				orow[2 * s + 1] = Out::of(inv_row_vals_h(qd, A.nquads, lane, o, ox), clamp_of(a), curb[2 * s + 1]);
+			} else if constexpr (FloatSample<DstT>::value) {
 				orow[2 * s] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, e, ex), fx), clamp_of(a), A.fmt);
 				orow[2 * s + 1] = Out::of(flip_quad<FL>(inv_row_vals_h(qd, A.nquads, lane, o, ox), fx), clamp_of(a), A.fmt);
 			} else {
@@ -2714,6 +2937,53 @@ struct RgbOut<uint8_t, PIX_STEP4_BGR> : RgbOut<uint8_t, PIX_STEP4> {
 	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp) { return rgbx_of<true>(y, co, cg); }
 };
 
+// a delta view's interleaved 8-bit pixels (DeltaPix<uint8_t>): the residual's clamps for [-R, R] — Y and every colour to [-R, R], Co
+// and Cg to [-2R, 2R] — then each colour plus the base's byte of the same place, clamped to the range; the base's twelve bytes
+// travel as they were loaded
+template <bool BGR>
+__device__ __forceinline__ Rgb12 rgb_delta_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp M, const U32x3 &base)
+{
+	const int R = M.r();
+	unsigned char px[12];
+#pragma unroll
+	for (int k = 0; k < 4; ++k) {
+		const int yy = clamp_to(y.v[k], -R, R), c0 = clamp_to(co.v[k], -2 * R, 2 * R), c1 = clamp_to(cg.v[k], -2 * R, 2 * R);
+		const int t = yy - tdiv2(c1);
+		const int g = c1 + t;
+		const int b = t - tdiv2(c0);
+		const int r = b + c0;
+		px[3 * k] = (unsigned char)delta_sample(BGR ? b : r, rgb_byte(base, 3 * k), M);
+		px[3 * k + 1] = (unsigned char)delta_sample(g, rgb_byte(base, 3 * k + 1), M);
+		px[3 * k + 2] = (unsigned char)delta_sample(BGR ? r : b, rgb_byte(base, 3 * k + 2), M);
+	}
+	Rgb12 o;
+#pragma unroll
+	for (int k = 0; k < 3; ++k)
+		o.w[k] = px[4 * k] | (px[4 * k + 1] << 8) | (px[4 * k + 2] << 16) | ((unsigned)px[4 * k + 3] << 24);
+	return o;
+}
+template <>
+struct RgbOut<DeltaPix<uint8_t>, PIX_PACKED> : RgbOut<uint8_t, PIX_PACKED> {
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp M, const U32x3 &base) { return rgb_delta_of<false>(y, co, cg, M, base); }
+};
+template <>
+struct RgbOut<DeltaPix<uint8_t>, PIX_PACKED_BGR> : RgbOut<uint8_t, PIX_PACKED> {
+	static __device__ __forceinline__ row of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp M, const U32x3 &base) { return rgb_delta_of<true>(y, co, cg, M, base); }
+};
+template <typename PixT>
+struct RgbBase {
+	typedef NoBase type;
+};
+template <>
+struct RgbBase<DeltaPix<uint8_t>> {
+	typedef U32x3 type;
+};
+__device__ __forceinline__ U32x3 hold(const U32x3 &v)
+{
+	U32x3 o = { hold(v.x), hold(v.y), hold(v.z) };
+	return o;
+}
+
 // PixT = uint16_t: deep pixels (dst8 points to uint16_t samples, ll_ps / llpitch count samples, clamps at a.maxval)
 // PIX_PLANAR: dst8 is the R plane of the window, G and B A.cstride samples apart each (signed), llpitch the pitch of a plane's rows
 // PIX_STEP4: llpitch is the pitch of rows of 4-byte pixels; the step is the constant 4 here, no argument carries it
@@ -2748,14 +3018,28 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 	const int qs = flip_q<FL>(qd, A.fwq, fx);   // the quad of the row that the lane's quad goes to
 	const InvAt at = inv_at(a, qd, A.nquads);
 
+	// a delta sink's base rows (DeltaPix<uint8_t>): the twelve bytes of row r of the base's window where the lane's quad goes, clamped into the window
+	typedef typename RgbBase<PixT>::type BaseRow;
+	constexpr bool DELTA = !std::is_same<BaseRow, NoBase>::value;
+	auto load_base = [&](int r) {
+		if constexpr (DELTA) {
+			const uint8_t *b = A.base8 + win_off(A.bgrid, A.base_ps, image);
+			return *reinterpret_cast<const U32x3 *>(b + (long)min(r, a.h - 1) * A.bpitch + 12 * min(max(qd, 0), A.nquads - 1));
+		} else {
+			return NoBase{};
+		}
+	};
 	// (one row pair per batch: three planes' worth of arithmetic lies between two waits as it is)
 	InvCols c[3];
 	InvRaw nxt[3], cur[3];
+	BaseRow nxtb[2], curb[2];
 #pragma unroll
 	for (int ch = 0; ch < 3; ++ch) {
 		c[ch] = inv_first(a, j0, inv_load_w(a, llp[ch], det[ch], j0 > 0 ? j0 - 1 : 0, at), inv_load_w(a, llp[ch], det[ch], j0, at));
 		nxt[ch] = inv_load_w(a, llp[ch], det[ch], j0 + 1, at);
 	}
+	nxtb[0] = load_base(2 * j0);
+	nxtb[1] = load_base(2 * j0 + 1);
 	typename Out::row orow[2];
 	auto store_pair = [&](int j) {
 		if (writes) {   // twelve bytes per lane in one store: the wave's 56 lanes write 672 consecutive bytes (deep pixels: twice that; planar: a third of it to each plane)
@@ -2774,12 +3058,16 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 #pragma unroll
 		for (int ch = 0; ch < 3; ++ch)
 			cur[ch] = hold(nxt[ch]);   // the one wait of the iteration
+		curb[0] = hold(nxtb[0]);
+		curb[1] = hold(nxtb[1]);
 		if (jj > j0)
 			store_pair(jj - 1);
 		if (jj + 1 < j1) {
 #pragma unroll
 			for (int ch = 0; ch < 3; ++ch)
 				nxt[ch] = inv_load_w(a, llp[ch], det[ch], jj + 2, at);
+			nxtb[0] = load_base(2 * (jj + 1));
+			nxtb[1] = load_base(2 * (jj + 1) + 1);
 		}
 		Quad4 even[3], odd[3];
 #pragma unroll
@@ -2792,7 +3080,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_w_rgb(LevelArgsW A)
 				odd[ch] = flip_quad<FL>(odd[ch], fx);
 			}
 		}
-		if constexpr (FloatSample<PixT>::value) {
+		if constexpr (DELTA) {
+			orow[0] = Out::of(even[0], even[1], even[2], clamp_of(a), curb[0]);
+			orow[1] = Out::of(odd[0], odd[1], odd[2], clamp_of(a), curb[1]);
+		} else if constexpr (FloatSample<PixT>::value) {
 			orow[0] = Out::of(even[0], even[1], even[2], clamp_of(a), A.fmt);
 			orow[1] = Out::of(odd[0], odd[1], odd[2], clamp_of(a), A.fmt);
 		} else {
@@ -3226,6 +3517,72 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__
 	}
 }
 
+// The conversions of a delta view (dwtx_pixels::delta; P = uint8_t, uint16_t or int16_t): a second pointer and a second grid,
+// the base pictures', window for window and colour for colour — each view with its own pitch, strides, step and planar or
+// interleaved form; the samples' type, the channels and their order are shared.  Kernels of their own: the instances above keep
+// their arguments and their code.  Forward: the planes of the integer picture S - B, both samples widened by their type.
+template <class P>
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels_delta(int *__restrict__ planes, const P *pix, PixGrid g, const P *base, PixGrid gb)
+{
+	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
+	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
+	if (x >= g.W || y >= g.H)
+		return;
+	const long npix = (long)g.W * g.H;
+	for (unsigned win = blockIdx.z; win < (unsigned)g.n; win += gridDim.z) {
+		const P *p = pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch + (long)x * g.col_step;
+		const P *q = base + win_off(gb.grid, gb.image_stride, (int)win) + (long)y * gb.row_pitch + (long)x * gb.col_step;
+		int *dst = planes + (long)win * g.C * npix + (long)y * g.W + x;
+		if (g.C == 1) {
+			dst[0] = (int)p[0] - (int)q[0];
+		} else {
+			const int r = (int)p[0] - (int)q[0], gr = (int)p[g.chan_stride] - (int)q[gb.chan_stride], b = (int)p[2 * g.chan_stride] - (int)q[2 * gb.chan_stride];
+			const int co = r - b;
+			const int t = b + tdiv2(co);
+			const int cg = gr - t;
+			dst[0] = t + tdiv2(cg);
+			dst[npix] = co;
+			dst[2 * npix] = cg;
+		}
+	}
+}
+
+// Inverse: the residual d under the signed clamps for [-R, R], R = M - L (k_pixels_from_planes with lo = -R, hi = R: gray, Y and
+// every sample of d to [-R, R], Co and Cg to [-2R, 2R]), then min(max(B + d, L), M) in P.  R reaches 65535 and 2R + R stays far
+// inside an int.  Every sample is read (base) and written (pix) by the same lane, the read first: the two views may be the
+// same memory (the in-place decode); the host refuses every other overlap.  Neither pointer is __restrict__ for that.
+template <class P>
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes_delta(P *pix, const int *__restrict__ planes, PixGrid g, const P *base, PixGrid gb, int L, int M)
+{
+	const int R = M - L;
+	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
+	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
+	if (x >= g.W || y >= g.H)
+		return;
+	const long npix = (long)g.W * g.H;
+	for (unsigned win = blockIdx.z; win < (unsigned)g.n; win += gridDim.z) {
+		P *p = pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch + (long)x * g.col_step;
+		const P *q = base + win_off(gb.grid, gb.image_stride, (int)win) + (long)y * gb.row_pitch + (long)x * gb.col_step;
+		const int *src = planes + (long)win * g.C * npix + (long)y * g.W + x;
+		if (g.C == 1) {
+			const int b0 = (int)q[0];
+			p[0] = (P)clampi(b0 + clampi(src[0], -R, R), L, M);
+		} else {
+			const int b0 = (int)q[0], b1 = (int)q[gb.chan_stride], b2 = (int)q[2 * gb.chan_stride];
+			const int yy = clampi(src[0], -R, R);
+			const int co = clampi(src[npix], -2 * R, 2 * R);
+			const int cg = clampi(src[2 * npix], -2 * R, 2 * R);
+			const int t = yy - tdiv2(cg);
+			const int gr = cg + t;
+			const int b = t - tdiv2(co);
+			const int r = b + co;
+			p[0] = (P)clampi(b0 + clampi(r, -R, R), L, M);
+			p[g.chan_stride] = (P)clampi(b1 + clampi(gr, -R, R), L, M);
+			p[2 * g.chan_stride] = (P)clampi(b2 + clampi(b, -R, R), L, M);
+		}
+	}
+}
+
 // Integer-only synthetic frames: seed = frame index, so every box
 // renders identical bytes.  kind 0 "smooth+noise", kind 1 uniform noise.
 __global__ __launch_bounds__(256) void k_synth(uint8_t *__restrict__ pix, int W, int H, int C, long total,
@@ -3346,6 +3703,39 @@ static void launch_pixels_from_planes(dwtx_ctx *ctx, dim3 grid, const dwtx_pixel
 	hipLaunchKernelGGL(kernel, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), planes, g, px.minval, px.maxval, f);
 }
 
+// a delta view's conversions (dwtx_pixels::delta): to_planes, or from_planes — integer samples on a grid, nothing flipped or listed
+template <class P>
+static void launch_delta_of(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const PixGrid &g, const dwtx_pixels &bp, const PixGrid &gb, int32_t *to_planes,
+	const int32_t *from_planes)
+{
+	if (to_planes)
+		hipLaunchKernelGGL(k_planes_from_pixels_delta<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, to_planes, static_cast<const P *>(px.red()), g,
+			static_cast<const P *>(bp.red()), gb);
+	else
+		hipLaunchKernelGGL(k_pixels_from_planes_delta<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), from_planes, g,
+			static_cast<const P *>(bp.red()), gb, px.minval, px.maxval);
+}
+static int launch_delta(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const PixGrid &g, int W, int H, int n, int32_t *to_planes, const int32_t *from_planes)
+{
+	if (px.is_float() || px.flips || px.listed() || !px.base_pixels().sample_aligned())
+		return DWTX_ERR_ARG;
+	const dwtx_pixels bp = px.base_pixels();
+	dim3 same;
+	const PixGrid gb = pix_grid(bp, W, H, n, &same);
+	switch (px.kind) {
+	case DWTX_SAMPLE_U8:
+		launch_delta_of<uint8_t>(ctx, grid, px, g, bp, gb, to_planes, from_planes);
+		break;
+	case DWTX_SAMPLE_U16:
+		launch_delta_of<uint16_t>(ctx, grid, px, g, bp, gb, to_planes, from_planes);
+		break;
+	default:
+		launch_delta_of<int16_t>(ctx, grid, px, g, bp, gb, to_planes, from_planes);
+		break;
+	}
+	return DWTX_OK;
+}
+
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
 {
 	const int C = px.channels;
@@ -3359,6 +3749,12 @@ int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px,
 	dim3 grid;
 	const PixGrid g = pix_grid(px, W, H, n, &grid);
 	const FloatFmt f = float_fmt(px);
+	if (px.is_delta()) {
+		if (const int rc = launch_delta(ctx, grid, px, g, W, H, n, planes, nullptr))
+			return rc;
+		DWTX_LAUNCH_CHECK();
+		return DWTX_OK;
+	}
 	switch (px.kind) {
 	case DWTX_SAMPLE_U8:
 		launch_planes_from_pixels<uint8_t>(ctx, grid, planes, px, g, f);
@@ -3398,6 +3794,12 @@ int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *p
 	dim3 grid;
 	const PixGrid g = pix_grid(px, W, H, n, &grid);
 	const FloatFmt f = float_fmt(px);
+	if (px.is_delta()) {
+		if (const int rc = launch_delta(ctx, grid, px, g, W, H, n, nullptr, planes))
+			return rc;
+		DWTX_LAUNCH_CHECK();
+		return DWTX_OK;
+	}
 	switch (px.kind) {
 	case DWTX_SAMPLE_U8:
 		launch_pixels_from_planes<uint8_t>(ctx, grid, px, planes, g, f);
@@ -3522,6 +3924,8 @@ static FwdSource fwd_source(const dwtx_pixels *px, bool src16)
 	if (!px)
 		return { src16 ? SRC_I16 : SRC_I32, false, 0 };
 	const bool deep = px->deep(), bgr = px->bgr();
+	if (px->is_delta())   // gray, or interleaved 8-bit RGB (dwtx_pixels_ok): a workgroup column per plane
+		return { px->channels == 3 ? (bgr ? SRC_DELTA_BGR8 : SRC_DELTA_RGB8) : px->kind == DWTX_SAMPLE_U8 ? SRC_DELTA_U8 : px->kind == DWTX_SAMPLE_S16 ? SRC_DELTA_S16 : SRC_DELTA_U16, false, 0 };
 	if (px->is_float()) {   // gray, or planar RGB in either order (dwtx_pixels_ok): by sample size, layout and route
 		const bool rgb = px->channels == 3, far = px->deep_source();
 		const int src = (px->kind == DWTX_SAMPLE_F32 ? SRC_F32 : SRC_H16) + (rgb ? SRC_F32P - SRC_F32 : 0) + (far ? SRC_F32D - SRC_F32 : 0);
@@ -3566,6 +3970,11 @@ static WideKernel fwd_wide_kernel(int src, bool hist, bool flip_y = false)
 		{ k_fwd_level_w<false, SRC_RGB16S>, nullptr },
 		{ k_fwd_level_w<false, SRC_RGBP16S>, nullptr },
 		{ k_fwd_level_w<false, SRC_BGR16S>, nullptr },
+		{ k_fwd_level_w<false, SRC_DELTA_U8>, nullptr },
+		{ k_fwd_level_w<false, SRC_DELTA_U16>, nullptr },
+		{ k_fwd_level_w<false, SRC_DELTA_S16>, nullptr },
+		{ k_fwd_level_w<false, SRC_DELTA_RGB8>, nullptr },
+		{ k_fwd_level_w<false, SRC_DELTA_BGR8>, nullptr },
 	};
 	// the same sources for the windows of a flipped call (FY; pixels only: a band has no windows)
 	static const WideKernel KY[SRC_COUNT][2] = {
@@ -3593,6 +4002,11 @@ static WideKernel fwd_wide_kernel(int src, bool hist, bool flip_y = false)
 		{ k_fwd_level_w<false, SRC_RGB16S, true>, nullptr },
 		{ k_fwd_level_w<false, SRC_RGBP16S, true>, nullptr },
 		{ k_fwd_level_w<false, SRC_BGR16S, true>, nullptr },
+		{ nullptr, nullptr },   // (a delta call takes no flips)
+		{ nullptr, nullptr },
+		{ nullptr, nullptr },
+		{ nullptr, nullptr },
+		{ nullptr, nullptr },
 	};
 	return flip_y ? KY[src][hist] : K[src][hist];
 }
@@ -3736,6 +4150,13 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			A.cstride = from.cstride;
 			if (pix_in && px->is_float())
 				A.fmt = float_fmt(*px);
+			if (pix_in && px->is_delta()) {
+				const dwtx_pixels bp = px->base_pixels();
+				A.base8 = wide_base(bp);
+				A.base_ps = (long)bp.image_stride;
+				A.bpitch = (int)bp.pitch(W);
+				A.bgrid = win_grid(bp);
+			}
 			if (hist_here) {
 				A.hist = HistArgs{ sink->cum32, sink->tile_mx, sink->tiles.xy2tile + sink->tiles.xy_first[level], sink->NT, sink->NTP,
 					sink->tiles.nbs[level] };
@@ -3783,6 +4204,15 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 // (flip_sink: the FL instances of the wide inverse kernels write it) with any flags, a mirrored one if the windows' width is on the quad.
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H)
 {
+	if (px.is_delta()) {
+		// a delta view: both views must qualify, as the plain views of their samples would (the 16-bit ones as deep views), gray or
+		// 8-bit interleaved RGB, dense pixels — every other pair takes the general conversions' delta instances
+		dwtx_pixels own = px;
+		own.delta = dwtx_base_grid();
+		const dwtx_pixels bp = px.base_pixels();
+		return !px.planar() && !bp.planar() && !px.stepped() && !bp.stepped() && (px.channels == 1 || px.kind == DWTX_SAMPLE_U8) && dwtx_pixels_ok(own, W, H) &&
+			dwtx_pixels_ok(bp, W, H);
+	}
 	return (!px.flips || px.flip_wide || (px.flip_sink && (!px.flip_x || px.flip_w % 4 == 0))) && W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide() && px.pitch(W) <= 0x7fffffffu && (!px.stepped() || px.rgbx8()) &&
 		(!px.is_float() || px.channels == 1 || px.planar());   // (float sinks: OutRow<F> and RgbOut<F, PIX_PLANAR>, float sources: FloatPix<>; interleaved float RGB has neither)
 }
@@ -3854,6 +4284,12 @@ static Inv2Kernel inv2_kernel(const dwtx_pixels *px, bool det16)
 template <int FL>
 static WideKernel inv_pixel_kernel(const dwtx_pixels *px, bool det16)
 {
+	if (px->is_delta()) {   // gray, or interleaved 8-bit RGB (dwtx_pixels_ok); never flipped, never from 16-bit bands
+		if (px->channels == 3)
+			return px->bgr() ? k_inv_level_w_rgb<false, DeltaPix<uint8_t>, PIX_PACKED_BGR, 0> : k_inv_level_w_rgb<false, DeltaPix<uint8_t>, PIX_PACKED, 0>;
+		return px->kind == DWTX_SAMPLE_U8 ? k_inv_level_w<DeltaPix<uint8_t>, false, 0>
+			: px->kind == DWTX_SAMPLE_S16 ? k_inv_level_w<DeltaPix<int16_t>, false, 0> : k_inv_level_w<DeltaPix<uint16_t>, false, 0>;
+	}
 	if (px->is_float()) {   // gray, or planar RGB in either order (dwtx_pixels_ok); from int32 and from 16-bit bands
 		const bool f32 = px->kind == DWTX_SAMPLE_F32;
 		if (px->channels == 3)
@@ -4084,6 +4520,13 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 				A.fmt = float_fmt(*px);
 				A.fh = px->flip_h;
 				A.fwq = px->flip_w / 4;
+			}
+			if (pix_out && px->is_delta()) {
+				const dwtx_pixels bp = px->base_pixels();
+				A.base8 = wide_base(bp);
+				A.base_ps = (long)bp.image_stride;
+				A.bpitch = (int)bp.pitch(W);
+				A.bgrid = win_grid(bp);
 			}
 			const dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), rgb ? nplanes / 3 : nplanes);
 			hipLaunchKernelGGL(inv_wide_kernel(pix_out, a.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);

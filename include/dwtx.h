@@ -349,7 +349,7 @@ int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
  * windows.  The streams are those of the interleaved copy: the .dwt format knows nothing of the layout. */
 typedef struct dwtx_view {
 	void  *dev;            /* first sample of window 0 */
-	int    sample_bytes;   /* 1: uint8_t, 2: native-endian uint16_t (deep pixels; int16_t in the dwtx_*_view_signed calls) */
+	int    sample_bytes;   /* 1: uint8_t, 2: native-endian uint16_t (deep pixels; int16_t in the dwtx_*_view_signed calls and, with sgn, in the delta calls) */
 	int    channels;       /* 1 or 3 (interleaved, or planar: channel_stride) */
 	int    maxval;         /* decode: clamp bound (255 required when sample_bytes == 1); encode ignores it (but dwtx_encode_view_float: the quantiser's clamp) */
 	int    cols;           /* windows per band; 0 or >= n: all n windows in one band */
@@ -671,6 +671,56 @@ int dwtx_decode_view_signed(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t st
 	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
 	int crop_w, int crop_h, const int *host_origins, void *const *host_windows /* NULL: the view's own grid */,
 	int flip, const unsigned char *host_flips, int minval, dwtx_decode_info *host_info);
+
+/* ---- delta views: a picture coded as its difference from a base view -----------------------------------------------------------
+ * Residual coding without the caller's pass over the batch: a CT slice against the slice before it, a static camera's frame
+ * against its background plate, a render against the previous frame.  The .dwt format is unchanged, with no new field: the coded
+ * picture is the integers D = S - B, and the base is the caller's knowledge, as maxval is.  (No reference counterpart beyond the
+ * stages named below: the reference codes the pictures it is given.)
+ * Views: `src` / `dst` and `base` are two grid views of n windows of W x H, window i of `base` belonging to window i of the
+ * other.  Each has its own dev, cols, row_pitch, image_stride, band_stride, channel_stride and pixel step — a pitched base under
+ * a dense picture, a planar one under an interleaved one —; channels (1 or 3), sample_bytes (1 or 2), the sample type and
+ * `order` are shared.  sgn == 0: uint8_t or uint16_t samples, and minval must be 0.  sgn == 1: int16_t samples (sample_bytes 2)
+ * and the range rule of the signed calls for [minval, dst->maxval].  base->maxval is not read; an encode reads no maxval at all.
+ * Encode: asynchronous on the context's stream.  D = S - B on integers, per colour (with DWTX_ORDER_BGR both views lie as B, G,
+ * R); stream i and dev_info[i] are byte for byte those of the reference's stages (encode.c:155-221) on the integer picture D.
+ * Both views are only read and may overlap each other and themselves in any way: frames 1.. of a stack against frames 0.. is
+ * one call.  A residual lies in [-R, R], R = maxval - minval, twice its pictures' range: one that needs more than 16 bit planes
+ * is refused as ever (dev_info[i].error = 1, the others of its batch are coded); RGB pictures with R <= 2047 and gray ones with
+ * R <= 4095 never are, all 8-bit pictures among them.  dwtx_encode_bound16 is the safe out_stride for
+ * every delta encode, 8-bit ones included.  capacity, the zero padding behind a stream and the encode index keep their meaning.
+ * Decode: synchronises where dwtx_decode_view does.  A stream with status 0 that supports the whole picture (host_info[i].level
+ * + 1 == levels) is written: with E the inverse transform's output (the missing-plane bias of decode.c:51-58 included), d is E
+ * under the signed clamps for [-R, R] — gray and Y to [-R, R], Co and Cg to [-2R, 2R], YCoCg-R inverse, every sample to [-R, R]
+ * (R may be 65535) — and the sample written is min(max(B + d, minval), maxval) in dst's type.  A whole stream gives back S
+ * exactly; the clamps only act on streams that lost planes, which give an approximation of S.  A stream with status 1 or 2
+ * leaves its window untouched, and so does one that supports less than W x H (cut before its finest level: a coarse residual has
+ * no base of its size); host_info[i] is the plain call's either way.  Nothing but the `channels` samples of the W x H pixels of a
+ * written window is written, and every disjointness rule of dwtx_decode_view_step holds for dst.
+ * Base against destination (decode): either the two views are identical — dev, every stride and the step: the decode is in
+ * place, each sample read and written by the same lane — or every unit of dst is disjoint from every unit of base, a unit being a
+ * window (for planar RGB a plane) and disjoint meaning that the spans [first, first + (H-1)*row_pitch + row) do not intersect.
+ * The rule is sufficient, not necessary: it takes odd frames against even frames and a frame against another allocation, and
+ * refuses frames 1.. against frames 0.. of one stack — that decode is a chain of n calls.
+ * Not in this call, left for later: float samples, window lists, flips, crops and levels_max.
+ * Route: a delta view takes the deep pictures' route in both directions whatever its sample size (histograms from the entropy
+ * stage's own pass, no 16-bit ring planes; DWTX_OPT_NO_PIXELS16 covers it).  Where both views are ones the transform's finest
+ * level reads / writes itself (W % 4 == 0, more than 64 pixels on a side, every row of every window on the quad of its samples)
+ * and hold dense gray pixels of any of the three sample types, or dense interleaved 8-bit RGB in either order, the finest level
+ * loads both views, or adds the base and clamps, itself; every other pair — planar, stepped, 16-bit RGB, off the quad, mixed —
+ * goes through the general conversions' delta instances: the same bytes and samples.
+ * DWTX_ERR_ARG (with a dwtx_last_error() text, nothing written): mismatched channels or sample_bytes, sgn with 1-byte samples,
+ * minval != 0 without sgn, a range outside the rule, a destination that meets its base, and everything dwtx_encode_view_order /
+ * dwtx_decode_view_order refuse for either view. */
+int dwtx_encode_view_delta(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step,
+	int order, int sgn, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
+int dwtx_decode_view_delta(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, const dwtx_view *dst, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step,
+	int order, int sgn, int minval, dwtx_decode_info *host_info);
+/* Host arithmetic only, like dwtx_view_list_check: DWTX_OK, or the DWTX_ERR_ARG (and text) the two calls above would return for
+ * these two views (dst != 0: the decode's rules, base against destination among them). */
+int dwtx_view_delta_check(const dwtx_view *v, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step,
+	int sgn, int minval, int W, int H, int n, int dst);
 
 /* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
  * interior, right column, bottom row, corner, in that order, those that exist — each a cols x rows grid of W x H tiles
