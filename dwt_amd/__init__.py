@@ -194,6 +194,30 @@ def view_delta_check(fields, base_fields, pointer, base_pointer, sample_bytes=1,
     return rc, (lib.dwtx_last_error().decode(errors="replace") if rc else "")
 
 
+def view_chain_check(fields, key_fields, pointer, key_pointer, sample_bytes=1, key_sample_bytes=None, signed=False, minval=0, maxval=None, dst=True):
+    """dwtx_view_chain_check: what encode_view_chain (dst=False) and decode_view_chain (dst=True) say to a grid view and a key ->
+    (rc, text): (0, "") for a pair they take, else the error code and the text of the refusal.  fields: the view_fields dict of
+    the view; key_fields: that of the key, ONE window (its n, cols, image_stride and band_stride are not looked at; None: a
+    NULL key); pointer, key_pointer: the first samples' addresses as plain integers, never dereferenced.  Host arithmetic only:
+    needs no device."""
+    lib = _lib.load()
+    if key_sample_bytes is None:
+        key_sample_bytes = sample_bytes
+    if maxval is None:
+        maxval = 255 if sample_bytes == 1 else 32767 if signed else 65535
+    v = View(pointer or None, sample_bytes, fields["channels"], maxval, fields["cols"], fields["row_pitch"], fields["image_stride"],
+             fields["band_stride"], fields["channel_stride"])
+    if key_fields is None:
+        key, kstep = None, 0
+    else:
+        key = C.byref(View(key_pointer or None, key_sample_bytes, key_fields["channels"], maxval, 0, key_fields["row_pitch"], 0, 0,
+                           key_fields["channel_stride"]))
+        kstep = key_fields["pixel_step"]
+    rc = lib.dwtx_view_chain_check(C.byref(v), fields["pixel_step"], key, kstep, 1 if signed else 0, int(minval), fields["W"], fields["H"],
+                                   fields["n"], 1 if dst else 0)
+    return rc, (lib.dwtx_last_error().decode(errors="replace") if rc else "")
+
+
 FLIPS = {"": 0, "x": 1, "y": 2, "xy": 3, "yx": 3}   # enum DWTX_FLIP_X = 1, DWTX_FLIP_Y = 2 (include/dwtx.h): a mask
 
 
@@ -878,6 +902,72 @@ class Context:
         else:
             _check(self.lib.dwtx_decode_view(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
                                              C.cast(infos, C.c_void_p)), "dwtx_decode_view")
+        return list(infos)
+
+    # -- delta chains: each picture against its predecessor, the first against a key (dwtx_*_view_chain) ------------------------
+
+    _NOT_IN_CHAINS = {"flip": "the chain calls take no flips", "levels_max": "a coarse residual has no base of its size",
+                      "crop": "the chain calls take no crops", "origins": "the chain calls take no crops", "base": "the key is the base of picture 0, "
+                      "and every other picture's base is the picture before it", "scale": "the chain calls take integer samples",
+                      "bias": "the chain calls take integer samples", "windows": "the chain calls take no window lists"}
+
+    def _chain_views(self, t, key, maxval, stepped, signed, unsupported):
+        """The tensors of a chain call -> its two views, or a ValueError before any device call: the keywords of the other view
+        calls that a chain does not take, lists, float tensors, a missing key, and a key of another dtype or window shape."""
+        torch = self.torch
+        for k in unsupported:
+            raise ValueError(f"a chain call does not take {k}= ({self._NOT_IN_CHAINS.get(k, 'no view call has that keyword')})")
+        if isinstance(t, (list, tuple)):
+            raise ValueError("a chain call takes one grid view, not a list of windows")
+        if key is None:
+            raise ValueError("a chain call needs its key, the base of picture 0")
+        for what, x in (("the tensor", t), ("key", key)):
+            if not hasattr(x, "dtype") or x.dtype in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
+                raise ValueError(f"a chain call takes integer tensors: {what} holds {getattr(x, 'dtype', type(x))}")
+        if key.dtype != t.dtype:
+            raise ValueError(f"key needs the tensor's dtype {t.dtype}, not {key.dtype}")
+        if key.dim() == 3:
+            key = key.unsqueeze(0)
+        if key.dim() != 4 or key.shape[0] != 1 or tuple(key.shape[-3:]) != tuple(t.shape[-3:]):
+            raise ValueError(f"key is one window {tuple(t.shape[-3:])} or (1,) + that (one call is one chain), not shape {tuple(key.shape)}")
+        v, W, H, Cn, n, step = self._view(t, maxval, stepped, signed=signed)
+        vk, _, _, _, _, kstep = self._view(key, None, stepped, signed=signed)
+        return v, vk, W, H, Cn, n, step, kstep
+
+    def encode_view_chain(self, t, key, capacity=0, out=None, info=None, stepped=False, order="rgb", signed=False, **unsupported):
+        """dwtx_encode_view_chain: the windows of `t` (any tensor encode_view takes), each against the one before it and window 0
+        against `key` — one window [H,W,C] or [1,H,W,C] of `t`'s dtype with any strides a view takes — -> (streams, info) as
+        encode_view(t, base=...) gives for those pairs; async.  `frames[1:]` with `frames[0]` as key codes a whole clip.  The
+        streams' slots are dwtx_encode_bound16's.  Not with flip, levels_max, float tensors or lists: ValueError."""
+        order = view_order(order)
+        torch = self.torch
+        v, vk, W, H, Cn, n, step, kstep = self._chain_views(t, key, None, stepped, signed, unsupported)
+        stride = self.lib.dwtx_encode_bound16(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
+        if out is None:
+            out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
+        if info is None:
+            info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
+        _check(self.lib.dwtx_encode_view_chain(self.h, C.byref(v), step, C.byref(vk), kstep, order, 1 if signed else 0, W, H, n, capacity,
+                                               _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view_chain")
+        return out, info
+
+    def decode_view_chain(self, streams, lens, into, key, maxval=None, stepped=False, order="rgb", signed=False, minval=None, **unsupported):
+        """dwtx_decode_view_chain: device streams [n,stride] + int64 lens of a chain's residuals -> the windows of `into`, window i
+        receiving `(window i-1 + d_i).clamp(minval, maxval)` and window 0 `(key + d_0).clamp(...)`: what n calls of
+        decode_view(..., base=previous window) of one stream each give, in one call.  A window whose stream is unreadable or cut
+        before its finest level stays as it is, and the next picture takes what lies there as its base.  key: one window [H,W,C]
+        or [1,H,W,C] of `into`'s dtype, disjoint from every window of `into` (view_chain_check); `frames[0]` as key and
+        `frames[1:]` as `into` is the layout it is made for.  Returns the list of DecodeInfo; syncs once.  Not with flip,
+        levels_max, float tensors or lists: ValueError."""
+        order = view_order(order)
+        torch = self.torch
+        lo, maxval = self._signed_range(signed, minval, maxval)
+        v, vk, W, H, Cn, n, step, kstep = self._chain_views(into, key, maxval, stepped, signed, unsupported)
+        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
+        assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
+        infos = (DecodeInfo * n)()
+        _check(self.lib.dwtx_decode_view_chain(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, C.byref(v), step, C.byref(vk), kstep,
+                                               order, 1 if signed else 0, lo if signed else 0, C.cast(infos, C.c_void_p)), "dwtx_decode_view_chain")
         return list(infos)
 
     def decode_view_float(self, streams, lens, into, maxval=255, scale=1.0, bias=0.0, levels_max=-1, stepped=False, order="rgb", flip=None,

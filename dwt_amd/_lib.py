@@ -177,6 +177,10 @@ SYMBOLS = {
     "dwtx_encode_view_delta": (_i, [_vp, C.POINTER(View), _sz, C.POINTER(View), _sz, _i, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
     "dwtx_decode_view_delta": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, C.POINTER(View), _sz, C.POINTER(View), _sz, _i, _i, _i, _vp]),
     "dwtx_view_delta_check": (_i, [C.POINTER(View), _sz, C.POINTER(View), _sz, _i, _i, _i, _i, _i, _i]),
+    # delta chains: the view and ONE window, the key, with a pixel step of its own
+    "dwtx_encode_view_chain": (_i, [_vp, C.POINTER(View), _sz, C.POINTER(View), _sz, _i, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
+    "dwtx_decode_view_chain": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, C.POINTER(View), _sz, C.POINTER(View), _sz, _i, _i, _i, _vp]),
+    "dwtx_view_chain_check": (_i, [C.POINTER(View), _sz, C.POINTER(View), _sz, _i, _i, _i, _i, _i, _i]),
     "dwtx_tile_groups": (_i, [_i, _i, _i, C.POINTER(TileGroup)]),
     "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }

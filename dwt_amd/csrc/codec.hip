@@ -391,6 +391,18 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 		fused &= ~DWTX_FUSED_FINE16;
 		if (const int r = dwtx_reconstruction_ex(ctx, pyr, lin, miss, lo, W, H, C, count, fused, f16))    // decode.c:257 (the rest of it)
 			return r;
+		if (px.chain) {
+			// A chain (dwtx_decode_view_chain): the group's residuals through the int32 transform into planes, never the fused sinks,
+			// then one launch that walks windows first .. first + count in order from window first - 1 as it lies in memory (first
+			// == 0: the key).  That window is in memory when the launch runs: dwtx_decode_planes_ex calls `part` for the parts in
+			// ascending order (unpack.hip, run()), the non-uniform fallback of `part` calls finish(i, 1) in ascending order, and
+			// everything either queues goes onto ctx->stream — so every launch that writes a window before `first` is ahead of this
+			// one on one stream.  A window no launch writes (status 1 or 2, cut before its finest level) needs no table: the next
+			// group reads the bytes the caller left there.
+			if (const int r = dwtx_transformation_inv(ctx, img, pyr, W, H, count * C))                   // decode.c:258
+				return r;
+			return dwtx_planes_to_pixels_chain(ctx, px, img, W, H, first, count);
+		}
 		if (crop) {
 			const int32_t *planes;
 			if (lo == g.levels) {   // whole pictures: one launch per level for all of them, each with its own origin
@@ -1308,6 +1320,139 @@ extern "C" int dwtx_decode_view_delta(dwtx_ctx *ctx, const uint8_t *dev_streams,
 	dwtx_pixels px;
 	if (const int rc = delta_view(dst, pixel_step, base, base_pixel_step, order, sgn, minval, W, H, n, true, &px))
 		return rc;
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, -1, px, host_info);
+}
+
+// ---- delta chains (include/dwtx.h): each picture coded against its predecessor, the first against a key -------------------------
+
+static void base_grid_of(const dwtx_pixels &bp, dwtx_base_grid *g)
+{
+	g->base = bp.base;
+	g->image_stride = bp.image_stride;
+	g->row_pitch = bp.row_pitch;
+	g->band_stride = bp.band_stride;
+	g->first = bp.first;
+	g->channel_stride = bp.channel_stride;
+	g->pixel_step = bp.pixel_step;
+	g->cols = bp.cols;
+}
+
+// The view and the key of a chain call -> *px, the view's pixels, and *kp, the key's one window; checked as delta_view checks its
+// two views.  For a decode every unit of the destination (a window; a plane of planar RGB) must be disjoint from every unit of the
+// key: delta_view's spans with one base window, so each destination unit is held against the key's one or three directly, no
+// sort.  Two spans that intersect are still disjoint where both units have the same pitch in bytes and lie in different columns of
+// the lattice of rows that pitch apart (list_windows' rule): a key in the gap between a window's rows and its pitch.
+static int chain_view(const dwtx_view *v, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step, int order, int sgn, int minval,
+	int W, int H, int n, bool dst, dwtx_pixels *px, dwtx_pixels *kp)
+{
+	if (!v) {
+		dwtx_set_error("chain view: no view");
+		return DWTX_ERR_ARG;
+	}
+	if (!key || !key->dev) {
+		dwtx_set_error("chain view: no key (the base of picture 0 is required: a chain without one is a plain call and n - 1 links)");
+		return DWTX_ERR_ARG;
+	}
+	if (sgn != 0 && sgn != 1) {
+		dwtx_set_error("chain view: sgn %d (0: uint8_t / uint16_t samples, 1: int16_t samples)", sgn);
+		return DWTX_ERR_ARG;
+	}
+	if (!sgn && minval != 0) {
+		dwtx_set_error("chain view: minval %d without sgn (unsigned samples start at 0)", minval);
+		return DWTX_ERR_ARG;
+	}
+	if (v->channels != key->channels) {
+		dwtx_set_error("chain view: the view has %d channels, its key %d", v->channels, key->channels);
+		return DWTX_ERR_ARG;
+	}
+	if (v->sample_bytes != key->sample_bytes) {
+		dwtx_set_error("chain view: the view has %d-byte samples, its key %d-byte ones", v->sample_bytes, key->sample_bytes);
+		return DWTX_ERR_ARG;
+	}
+	const int *lower = sgn ? &minval : nullptr;
+	if (const int rc = pixels_of_view(v, pixel_step, order, W, H, n, dst, px, -1, false, nullptr, lower))
+		return rc;
+	dwtx_view one = *key;   // one window: what lies between windows is not the key's to say
+	one.cols = 0;
+	one.image_stride = 0;
+	one.band_stride = 0;
+	if (const int rc = pixels_of_view(&one, key_pixel_step, order, W, H, 1, false, kp, -1, false, nullptr, lower))
+		return rc;
+	if (!dst)
+		return DWTX_OK;
+	std::vector<DeltaSpan> spans;
+	try {
+		spans.reserve(3 * (size_t)n + 3);
+		delta_spans(*kp, W, H, 1, 1, &spans);
+		delta_spans(*px, W, H, n, 0, &spans);
+	} catch (...) {
+		return DWTX_ERR_NOMEM;
+	}
+	const size_t nkey = kp->planar() ? 3 : 1;
+	const uintptr_t pitch = px->bytes(px->pitch(W)), kpitch = kp->bytes(kp->pitch(W));
+	const uintptr_t krow = spans[0].end - spans[0].at - (uintptr_t)(H - 1) * kpitch;   // a unit's row, in bytes
+	for (size_t i = nkey; i < spans.size(); ++i) {
+		const DeltaSpan &d = spans[i];
+		const uintptr_t row = d.end - d.at - (uintptr_t)(H - 1) * pitch;
+		for (size_t k = 0; k < nkey; ++k) {
+			const DeltaSpan &b = spans[k];
+			if (d.end <= b.at || b.end <= d.at)
+				continue;
+			if (pitch == kpitch) {   // the key's columns [dx, dx + krow) on the lattice of the window's rows, which holds [0, row)
+				const uintptr_t dx = b.at >= d.at ? (b.at - d.at) % pitch : (pitch - (d.at - b.at) % pitch) % pitch;
+				if (dx >= row && dx + krow <= pitch)
+					continue;
+			}
+			dwtx_set_error("chain view: window %d of the destination meets the key (every unit of the destination must be disjoint from the key's: "
+				"frame 0 of a stack as the key of frames 1.. is the layout to use)", d.window);
+			return DWTX_ERR_ARG;
+		}
+	}
+	return DWTX_OK;
+}
+
+extern "C" int dwtx_view_chain_check(const dwtx_view *v, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step,
+	int sgn, int minval, int W, int H, int n, int dst)
+{
+	dwtx_pixels px, kp;
+	return chain_view(v, pixel_step, key, key_pixel_step, DWTX_ORDER_RGB, sgn, minval, W, H, n, dst != 0, &px, &kp);
+}
+
+// Stream 0 is window 0 minus the key, stream i window i minus window i - 1: two delta encodes, the second `src[1:]` against
+// `src[:-1]` — the streams, the records and the encode index land at entry i for stream i.
+extern "C" int dwtx_encode_view_chain(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step,
+	int order, int sgn, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	dwtx_pixels px, kp;
+	if (const int rc = chain_view(src, pixel_step, key, key_pixel_step, order, sgn, 0, W, H, n, false, &px, &kp))
+		return rc;
+	if (!ctx || !dev_out || !dev_info)
+		return DWTX_ERR_ARG;
+	dwtx_index *index = ctx->enc_index;
+	dwtx_pixels head = px;
+	base_grid_of(kp, &head.delta);
+	if (const int rc = encode_device(ctx, head, W, H, 1, capacity, dev_out, out_stride, dev_info, index))
+		return rc;
+	if (n == 1)
+		return DWTX_OK;
+	dwtx_pixels tail = px.image(1);   // (px has no base yet: only the view moves, and its base is the view from window 0 on)
+	base_grid_of(px, &tail.delta);
+	return encode_device(ctx, tail, W, H, n - 1, capacity, dev_out + out_stride, out_stride, dev_info + 1, index ? index + 1 : nullptr);
+}
+
+extern "C" int dwtx_decode_view_chain(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, const dwtx_view *dst, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step, int order, int sgn, int minval,
+	dwtx_decode_info *host_info)
+{
+	dwtx_pixels px, kp;
+	if (const int rc = chain_view(dst, pixel_step, key, key_pixel_step, order, sgn, minval, W, H, n, true, &px, &kp))
+		return rc;
+	if (n == 1)   // one link is dwtx_decode_view_delta with base = key, and takes its path (the fused sinks where the pair qualifies)
+		base_grid_of(kp, &px.delta);
+	else {
+		px.chain = true;
+		base_grid_of(kp, &px.key);
+	}
 	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, -1, px, host_info);
 }
 

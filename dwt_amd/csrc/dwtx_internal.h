@@ -258,8 +258,30 @@ struct dwtx_pixels {
 	bool flips = false, flip_wide = false, flip_sink = false, flip_x = false;
 	int flip_w = 0, flip_h = 0;
 	dwtx_base_grid delta;   // a delta view's base pictures, window for window (image() moves both grids; moved() keeps the base where it is)
+	// A chain (dwtx_decode_view_chain): a delta view whose window i has window i - 1 of the view itself as its base, and window 0
+	// the one window at `key` (its own pitch, channel stride and step; image_stride, band_stride, first and cols stay 0).  `delta`
+	// stays empty: no kernel that walks two grids window for window meets a chain, whose one conversion (lift.hip,
+	// dwtx_planes_to_pixels_chain) walks the windows of a group in order.  image() and moved() keep both fields.
+	bool chain = false;
+	dwtx_base_grid key;
 
-	bool is_delta() const { return delta.base != nullptr; }
+	bool is_delta() const { return delta.base != nullptr || chain; }
+	// the key of a chain as a view of its own, one window
+	dwtx_pixels key_pixels() const
+	{
+		dwtx_pixels p = *this;
+		p.base = key.base;
+		p.image_stride = 0;
+		p.row_pitch = key.row_pitch;
+		p.band_stride = 0;
+		p.first = 0;
+		p.channel_stride = key.channel_stride;
+		p.pixel_step = key.pixel_step;
+		p.cols = 0;
+		p.chain = false;
+		p.key = dwtx_base_grid();
+		return p;
+	}
 	// the base pictures as a view of their own: the samples, the channels and their order are this view's
 	dwtx_pixels base_pixels() const
 	{
@@ -318,7 +340,7 @@ struct dwtx_pixels {
 			p.base = at(image_stride * i);
 		else
 			p.first += i;
-		if (is_delta()) {
+		if (delta.base) {
 			if (delta.cols == 0)
 				p.delta.base = static_cast<char *>(delta.base) + bytes(delta.image_stride * i);
 			else
@@ -390,6 +412,10 @@ int dwtx_lift_scratch(dwtx_ctx *ctx, int W, int H, int nplanes);
 // windows, whatever their pitch, strides (a planar view's channel stride too) and grid; only the W*C samples of a window's H rows are read / written
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n);
 int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int n);
+// lift.hip: the one conversion of a chain (dwtx_pixels::chain; px is the whole view of the call): the planes of the residuals of
+// windows first .. first + count, in order, onto window first - 1 as it lies in memory when the launch runs (first == 0: the
+// key) — window i receives clamp(window i - 1 + d_i), the running sample kept in a register.  One launch, on ctx->stream.
+int dwtx_planes_to_pixels_chain(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int first, int count);
 
 // The entropy stage's tiles (linearize.hip): the Hilbert curve of ring level l visits every aligned 32x32 square of
 // its lengths[l+1]-sided square contiguously ("curve block"), so the ring's coefficients, in the order of

@@ -3583,6 +3583,110 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes_delta
 	}
 }
 
+// The conversion of a chain (dwtx_decode_view_chain; dwtx_pixels::chain): windows first .. first + count of ONE view, each the
+// delta decode of its residual onto the window before it — S_i = clamp(S_{i-1} + d_i) with exactly the arithmetic of
+// k_pixels_from_planes_delta — and the base of the first of them at `base` (the window before the group as it lies in memory,
+// or the key: one window behind its own PixGrid).  grid: (64 pixels of a row, 4 rows) and nothing over windows: a lane owns one
+// pixel position, loads its base sample(s) once and walks the pictures in order, the running sample in a register.  The chain's
+// only dependence is that register: the plane samples of the next CHAIN_AHEAD pictures are loaded before the current one's
+// arithmetic and store run (a batch of loads, one wait, then the batch's serial adds), so that the walk waits on memory once a
+// batch and not once a picture.  The host guarantees that the base window is disjoint from the written ones (codec.hip,
+// chain_view, and decode_device's ordering argument): planes, pixels and base are __restrict__.
+constexpr int CHAIN_AHEAD = 4;
+struct ChainRaw {
+	int v[3];
+};
+template <int C>
+__device__ __forceinline__ ChainRaw chain_load(const int *__restrict__ src, long npix)
+{
+	ChainRaw r;
+	r.v[0] = src[0];
+	if (C == 3) {
+		r.v[1] = src[npix];
+		r.v[2] = src[2 * npix];
+	}
+	return r;
+}
+// one link: the residual's clamps, the YCoCg-R inverse, the clamp of d, the sum's clamp — b[] in, b[] out
+template <int C>
+__device__ __forceinline__ void chain_link(const ChainRaw &r, int (&b)[3], int R, int L, int M)
+{
+	if (C == 1) {
+		b[0] = clampi(b[0] + clampi(r.v[0], -R, R), L, M);
+	} else {
+		const int yy = clampi(r.v[0], -R, R);
+		const int co = clampi(r.v[1], -2 * R, 2 * R);
+		const int cg = clampi(r.v[2], -2 * R, 2 * R);
+		const int t = yy - tdiv2(cg);
+		const int gr = cg + t;
+		const int bl = t - tdiv2(co);
+		const int rd = bl + co;
+		b[0] = clampi(b[0] + clampi(rd, -R, R), L, M);
+		b[1] = clampi(b[1] + clampi(gr, -R, R), L, M);
+		b[2] = clampi(b[2] + clampi(bl, -R, R), L, M);
+	}
+}
+template <class P, int C>
+__device__ __forceinline__ void chain_walk(P *__restrict__ pix, const int *__restrict__ planes, const PixGrid &g, const P *__restrict__ base, const PixGrid &gb,
+	int L, int M, int x, int y)
+{
+	const int R = M - L;
+	const long npix = (long)g.W * g.H;
+	const long wstep = (long)C * npix;   // from a picture's planes to the next one's
+	const long at = (long)y * g.row_pitch + (long)x * g.col_step;
+	const P *q = base + win_off(gb.grid, gb.image_stride, 0) + (long)y * gb.row_pitch + (long)x * gb.col_step;
+	int b[3];
+	b[0] = (int)q[0];
+	if (C == 3) {
+		b[1] = (int)q[gb.chan_stride];
+		b[2] = (int)q[2 * gb.chan_stride];
+	}
+	const int *src = planes + (long)y * g.W + x;
+	auto store = [&](int win) {
+		P *p = pix + win_off(g.grid, g.image_stride, win) + at;
+		p[0] = (P)b[0];
+		if (C == 3) {
+			p[g.chan_stride] = (P)b[1];
+			p[2 * g.chan_stride] = (P)b[2];
+		}
+	};
+	const int n = g.n;
+	ChainRaw nxt[CHAIN_AHEAD], cur[CHAIN_AHEAD];
+#pragma unroll
+	for (int k = 0; k < CHAIN_AHEAD; ++k)   // (a picture past the group's end: the last one's planes once more, never used)
+		nxt[k] = chain_load<C>(src + (long)min(k, n - 1) * wstep, npix);
+	for (int w0 = 0; w0 < n; w0 += CHAIN_AHEAD) {
+#pragma unroll
+		for (int k = 0; k < CHAIN_AHEAD; ++k)   // the one wait of the iteration
+			for (int c = 0; c < C; ++c)
+				cur[k].v[c] = hold(nxt[k].v[c]);
+		if (w0 + CHAIN_AHEAD < n) {   // the next batch's loads go out before this batch's arithmetic and stores
+#pragma unroll
+			for (int k = 0; k < CHAIN_AHEAD; ++k)
+				nxt[k] = chain_load<C>(src + (long)min(w0 + CHAIN_AHEAD + k, n - 1) * wstep, npix);
+		}
+#pragma unroll
+		for (int k = 0; k < CHAIN_AHEAD; ++k)
+			if (w0 + k < n) {
+				chain_link<C>(cur[k], b, R, L, M);
+				store(w0 + k);
+			}
+	}
+}
+template <class P>
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_chain_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, const P *__restrict__ base,
+	PixGrid gb, int L, int M)
+{
+	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
+	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
+	if (x >= g.W || y >= g.H)
+		return;
+	if (g.C == 1)
+		chain_walk<P, 1>(pix, planes, g, base, gb, L, M, x, y);
+	else
+		chain_walk<P, 3>(pix, planes, g, base, gb, L, M, x, y);
+}
+
 // Integer-only synthetic frames: seed = frame index, so every box
 // renders identical bytes.  kind 0 "smooth+noise", kind 1 uniform noise.
 __global__ __launch_bounds__(256) void k_synth(uint8_t *__restrict__ pix, int W, int H, int C, long total,
@@ -3717,7 +3821,7 @@ static void launch_delta_of(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, con
 }
 static int launch_delta(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const PixGrid &g, int W, int H, int n, int32_t *to_planes, const int32_t *from_planes)
 {
-	if (px.is_float() || px.flips || px.listed() || !px.base_pixels().sample_aligned())
+	if (px.chain || px.is_float() || px.flips || px.listed() || !px.base_pixels().sample_aligned())   // (a chain has a conversion of its own, below)
 		return DWTX_ERR_ARG;
 	const dwtx_pixels bp = px.base_pixels();
 	dim3 same;
@@ -3733,6 +3837,46 @@ static int launch_delta(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const P
 		launch_delta_of<int16_t>(ctx, grid, px, g, bp, gb, to_planes, from_planes);
 		break;
 	}
+	return DWTX_OK;
+}
+
+template <class P>
+static void launch_chain_of(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const PixGrid &g, const dwtx_pixels &bp, const PixGrid &gb, const int32_t *planes)
+{
+	hipLaunchKernelGGL(k_chain_from_planes<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), planes, g,
+		static_cast<const P *>(bp.red()), gb, px.minval, px.maxval);
+}
+
+int dwtx_planes_to_pixels_chain(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int first, int count)
+{
+	const int C = px.channels;
+	if (!ctx || !planes || !px.base || !px.chain || !px.key.base || W < 1 || H < 1 || (C != 1 && C != 3) || first < 0 || count < 1)
+		return DWTX_ERR_ARG;
+	if (px.is_float() || px.flips || px.listed() || !px.sample_aligned() || !px.key_pixels().sample_aligned() || !px.range_ok())
+		return DWTX_ERR_ARG;
+	DWTX_ENTER(ctx);
+	// the written windows, and the one before them as a view of one window: the key, or window first - 1 of the view itself
+	dwtx_pixels own = px;
+	own.chain = false;
+	own.key = dwtx_base_grid();
+	const dwtx_pixels dst = own.image((size_t)first);
+	const dwtx_pixels bp = first ? own.image((size_t)first - 1) : px.key_pixels();
+	dim3 grid, one;
+	const PixGrid g = pix_grid(dst, W, H, count, &grid);
+	const PixGrid gb = pix_grid(bp, W, H, 1, &one);
+	grid.z = 1;   // (the pictures of a chain are walked in order by each lane)
+	switch (px.kind) {
+	case DWTX_SAMPLE_U8:
+		launch_chain_of<uint8_t>(ctx, grid, dst, g, bp, gb, planes);
+		break;
+	case DWTX_SAMPLE_U16:
+		launch_chain_of<uint16_t>(ctx, grid, dst, g, bp, gb, planes);
+		break;
+	default:
+		launch_chain_of<int16_t>(ctx, grid, dst, g, bp, gb, planes);
+		break;
+	}
+	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
 
@@ -4204,6 +4348,8 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 // (flip_sink: the FL instances of the wide inverse kernels write it) with any flags, a mirrored one if the windows' width is on the quad.
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H)
 {
+	if (px.chain)   // (a chain's base is the window before: no sink that walks the windows side by side takes it)
+		return false;
 	if (px.is_delta()) {
 		// a delta view: both views must qualify, as the plain views of their samples would (the 16-bit ones as deep views), gray or
 		// 8-bit interleaved RGB, dense pixels — every other pair takes the general conversions' delta instances

@@ -701,7 +701,7 @@ int dwtx_decode_view_signed(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t st
  * place, each sample read and written by the same lane — or every unit of dst is disjoint from every unit of base, a unit being a
  * window (for planar RGB a plane) and disjoint meaning that the spans [first, first + (H-1)*row_pitch + row) do not intersect.
  * The rule is sufficient, not necessary: it takes odd frames against even frames and a frame against another allocation, and
- * refuses frames 1.. against frames 0.. of one stack — that decode is a chain of n calls.
+ * refuses frames 1.. against frames 0.. of one stack — that decode is a chain of n calls, or one dwtx_decode_view_chain (below).
  * Not in this call, left for later: float samples, window lists, flips, crops and levels_max.
  * Route: a delta view takes the deep pictures' route in both directions whatever its sample size (histograms from the entropy
  * stage's own pass, no 16-bit ring planes; DWTX_OPT_NO_PIXELS16 covers it).  Where both views are ones the transform's finest
@@ -720,6 +720,46 @@ int dwtx_decode_view_delta(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t str
 /* Host arithmetic only, like dwtx_view_list_check: DWTX_OK, or the DWTX_ERR_ARG (and text) the two calls above would return for
  * these two views (dst != 0: the decode's rules, base against destination among them). */
 int dwtx_view_delta_check(const dwtx_view *v, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step,
+	int sgn, int minval, int W, int H, int n, int dst);
+
+/* ---- delta chains: each picture coded against its predecessor, the first against a key, in one call ------------------------------
+ * The CT volume and the clip of the delta views: slice i against slice i - 1.  The encode of such a chain was one call already
+ * (frames 1.. against frames 0.. of a stack); the decode was a chain of n delta decodes of one picture each, because picture i's
+ * base is picture i - 1 and that is not there yet.  These calls are that chain: the entropy stage, the reconstruction and the
+ * inverse transform of the n residuals run as the batch they are, and one kernel walks S_i = clamp(S_{i-1} + d_i) along the chain.
+ * Views: `src` / `dst` is a grid view of n windows, exactly as in the delta calls.  `key` describes ONE window, the base of
+ * picture 0, and is required: its dev, row_pitch, channel_stride and pixel step are its own (a planar key under an interleaved
+ * stack), its cols, image_stride and band_stride are ignored; channels, sample_bytes, sgn and order are shared with the other
+ * view, and sgn, minval and the range follow the delta calls' rules.
+ * Decode, stated by equivalence: the result — every byte of the destination and of the key, and host_info — is that of n calls
+ * of dwtx_decode_view_delta, call i decoding stream i alone into window i with window i - 1 as it lies in memory after call
+ * i - 1 as its base, and the key for i == 0.  So the base of picture i is the clamped sample that was written for picture i - 1,
+ * not an unclamped running sum; a stream with status 1 or 2, or one that stops before its finest level, leaves its window as it
+ * is, and picture i + 1 takes the bytes the caller left in window i as its base; host_info[i] is the plain call's; the call
+ * synchronises where dwtx_decode_view does.  n == 1 IS dwtx_decode_view_delta with base = key and takes its path.
+ * Disjointness (decode): dst must pass dwtx_decode_view_step's rules, and every unit of dst (a window; for planar RGB a plane) must
+ * be disjoint from every unit of the key: their spans [first, first + (H-1)*row_pitch + row) do not intersect, or both have the
+ * same row pitch in bytes and lie in different columns of the lattice of rows that pitch apart (a key in a window's pitch gap).
+ * Frame 0 of a stack as the key and frames 1.. as the destination is the layout this is made for.
+ * Encode: asynchronous.  Stream 0 is window 0 minus the key, stream i window i minus window i - 1; the bytes and dev_info are
+ * those of dwtx_encode_view_delta on those pairs — the call is two of them, with the encode index landing at entry i for stream
+ * i.  The views are only read and may overlap in any way.
+ * Route (decode, n > 1): the deep pictures' route as for every delta view, never the fused sinks: the int32 inverse transform
+ * into planes, then per group of the batch one launch of lift.hip's k_chain_from_planes, each lane walking its pixel through
+ * the group's pictures in order with the running sample in a register.
+ * Not in these calls, for the reasons the delta calls give: float samples, window lists, flips, crops, levels_max, a NULL key, and
+ * several chains per call (one call is one chain: a batch of volumes is a call per volume).
+ * DWTX_ERR_ARG (with a dwtx_last_error() text, nothing written): a NULL key, mismatched channels or sample_bytes, sgn with 1-byte
+ * samples, minval != 0 without sgn, a range outside the rule, a destination that meets the key, and everything
+ * dwtx_encode_view_order / dwtx_decode_view_order refuse for either view. */
+int dwtx_decode_view_chain(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, const dwtx_view *dst, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step,
+	int order, int sgn, int minval, dwtx_decode_info *host_info);
+int dwtx_encode_view_chain(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step,
+	int order, int sgn, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
+/* Host arithmetic only, like dwtx_view_delta_check: DWTX_OK, or the DWTX_ERR_ARG (and text) the two calls above would return for
+ * this view and key (dst != 0: the decode's rules, the key against the destination among them). */
+int dwtx_view_chain_check(const dwtx_view *v, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step,
 	int sgn, int minval, int W, int H, int n, int dst);
 
 /* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
