@@ -761,6 +761,86 @@ class Context:
         vb, _, _, _, _, bstep = self._view(base, None, stepped, signed=signed)
         return v, vb, W, H, Cn, n, step, bstep
 
+    def _encode_views(self, v, step, order, fmt, windows, flips, lo, W, H, n, capacity, out, info, pair=None):
+        """Every view encode: allocates `out` and `info` where the caller brought none — slots of dwtx_encode_bound, or of
+        dwtx_encode_bound16 for deep, signed and delta pictures — and makes the call through the narrowest entry point that has
+        the arguments given.  step: None without the `stepped` keyword; fmt, windows (a ctypes array), flips (view_flips) and lo
+        (the signed calls' minval): None for a call without them; pair: (symbol, other view, its step, sgn) of a delta or chain."""
+        torch = self.torch
+        deep = pair is not None or ((v.maxval > 255 or lo is not None) if fmt is not None else v.sample_bytes == 2)
+        bound = self.lib.dwtx_encode_bound16 if deep else self.lib.dwtx_encode_bound
+        stride = bound(W, H, v.channels) if capacity <= 0 else (capacity + 15) // 8 * 8
+        if out is None:
+            out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
+        if info is None:
+            info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
+        view = (self.h, C.byref(v), step or 0, order)
+        pf = C.byref(fmt) if fmt is not None else None
+        if pair is not None:
+            sym, args = pair[0], view[:3] + (C.byref(pair[1]), pair[2], order, pair[3])
+        elif lo is not None:
+            fl = flips or (0, None)
+            sym, args = "dwtx_encode_view_signed", view + (pf, windows, fl[0], fl[1], lo)
+        elif flips:
+            sym, args = "dwtx_encode_view_flip", view + (pf, windows, flips[0], flips[1])
+        elif windows is not None:
+            sym, args = "dwtx_encode_view_list", view + (pf, windows)
+        elif fmt is not None:
+            sym, args = "dwtx_encode_view_float", view + (pf,)
+        elif order:
+            sym, args = "dwtx_encode_view_order", view
+        elif step is not None:
+            sym, args = "dwtx_encode_view_step", view[:3]
+        else:
+            sym, args = "dwtx_encode_view", view[:2]
+        _check(getattr(self.lib, sym)(*args, W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), sym)
+        return out, info
+
+    def _decode_views(self, streams, lens, v, step, order, fmt, crop, windows, flips, lo, W, H, n, levels_max, pair=None):
+        """Every view decode, through the narrowest entry point that has the arguments given -> the list of DecodeInfo.  crop: None,
+        or (cw, ch, origins as a ctypes array or None); pair: (symbol, other view, its step, sgn, minval); the rest as for
+        _encode_views."""
+        torch = self.torch
+        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
+        assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
+        infos = (DecodeInfo * n)()
+        head = (self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n)
+        view = (levels_max, C.byref(v), step or 0, order)
+        pf = C.byref(fmt) if fmt is not None else None
+        window = (pf,) + (crop or (W, H, None))
+        if pair is not None:
+            sym, args = pair[0], view[1:3] + (C.byref(pair[1]), pair[2], order, pair[3], pair[4])
+        elif lo is not None:
+            fl = flips or (0, None)
+            sym, args = "dwtx_decode_view_signed", view + window + (windows, fl[0], fl[1], lo)
+        elif flips:
+            sym, args = "dwtx_decode_view_flip", view + window + (windows, flips[0], flips[1])
+        elif windows is not None:
+            sym, args = "dwtx_decode_view_list", view + window + (windows,)
+        elif crop is not None:
+            sym, args = "dwtx_decode_view_crop", view + window
+        elif fmt is not None:
+            sym, args = "dwtx_decode_view_float", view + (pf,)
+        elif order:
+            sym, args = "dwtx_decode_view_order", view
+        elif step is not None:
+            sym, args = "dwtx_decode_view_step", view[:3]
+        else:
+            sym, args = "dwtx_decode_view", view[:2]
+        _check(getattr(self.lib, sym)(*head, *args, C.cast(infos, C.c_void_p)), sym)
+        return list(infos)
+
+    @staticmethod
+    def _origins(origins, n):
+        """The `origins` keyword of the crop calls -> a ctypes array of n (x0, y0) pairs, or None for (0, 0)"""
+        if origins is None:
+            return None
+        flat = [int(c) for c in origins] if len(origins) == 2 and not hasattr(origins[0], "__len__") else None
+        pairs = [tuple(flat)] * n if flat is not None else [(int(x), int(y)) for x, y in origins]
+        if len(pairs) != n:
+            raise ValueError(f"origins: one (x0, y0) pair or {n}, not {len(pairs)}")
+        return (C.c_int * (2 * n))(*[c for p in pairs for c in p])
+
     def encode_view(self, t, capacity=0, out=None, info=None, stepped=False, order="rgb", flip=None, signed=False, base=None):
         """dwtx_encode_view: the windows of a strided device tensor [n,H,W,C] or [bands,cols,H,W,C] (a slice, a crop, a
         grid of tiles, a channel-first batch permuted to channel-last: see _view) -> (streams uint8 [n,stride], info uint8
@@ -779,41 +859,13 @@ class Context:
         need not fit any sample type.  Both tensors are only read: `t[1:]` against `t[:-1]` is one call.  Combines with
         stepped, order and signed; not with flip.  The streams' slots are dwtx_encode_bound16's, 8-bit pictures included."""
         order = view_order(order)
-        torch = self.torch
         if base is not None:
             v, vb, W, H, Cn, n, step, bstep = self._delta_views(t, base, None, stepped, signed, flip)
-            stride = self.lib.dwtx_encode_bound16(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
-            if out is None:
-                out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
-            if info is None:
-                info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
-            _check(self.lib.dwtx_encode_view_delta(self.h, C.byref(v), step, C.byref(vb), bstep, order, 1 if signed else 0, W, H, n, capacity,
-                                                   _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view_delta")
-            return out, info
+            return self._encode_views(v, step, order, None, None, None, None, W, H, n, capacity, out, info,
+                                      pair=("dwtx_encode_view_delta", vb, bstep, 1 if signed else 0))
         v, W, H, Cn, n, step = self._view(t, None, stepped, signed=signed)
         flips = view_flips(flip, n)
-        bound = self.lib.dwtx_encode_bound16 if v.sample_bytes == 2 else self.lib.dwtx_encode_bound
-        stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
-        if out is None:
-            out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
-        if info is None:
-            info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
-        if signed:
-            fl = flips or (0, None)
-            _check(self.lib.dwtx_encode_view_signed(self.h, C.byref(v), step, order, None, None, fl[0], fl[1], 0, W, H, n, capacity, _ptr(out),
-                                                    out.shape[1], _ptr(info)), "dwtx_encode_view_signed")
-        elif flips:
-            _check(self.lib.dwtx_encode_view_flip(self.h, C.byref(v), step, order, None, None, flips[0], flips[1], W, H, n, capacity, _ptr(out),
-                                                  out.shape[1], _ptr(info)), "dwtx_encode_view_flip")
-        elif order:
-            _check(self.lib.dwtx_encode_view_order(self.h, C.byref(v), step, order, W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
-                   "dwtx_encode_view_order")
-        elif stepped:
-            _check(self.lib.dwtx_encode_view_step(self.h, C.byref(v), step, W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
-                   "dwtx_encode_view_step")
-        else:
-            _check(self.lib.dwtx_encode_view(self.h, C.byref(v), W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view")
-        return out, info
+        return self._encode_views(v, step if stepped else None, order, None, None, flips, 0 if signed else None, W, H, n, capacity, out, info)
 
     def encode_view_float(self, t, maxval=255, scale=1.0, bias=0.0, capacity=0, out=None, info=None, stepped=False, order="rgb", flip=None,
                           minval=0):
@@ -833,24 +885,7 @@ class Context:
         v, W, H, Cn, n, step = self._view(t, int(maxval), stepped, floats=True)
         flips = view_flips(flip, n)
         lo = self._signed_range(False, minval, maxval, floats=True)[0]
-        bound = self.lib.dwtx_encode_bound16 if int(maxval) > 255 or lo is not None else self.lib.dwtx_encode_bound
-        stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
-        if out is None:
-            out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
-        if info is None:
-            info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
-        if lo is not None:
-            fl = flips or (0, None)
-            _check(self.lib.dwtx_encode_view_signed(self.h, C.byref(v), step, order, C.byref(fmt), None, fl[0], fl[1], lo, W, H, n, capacity,
-                                                    _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view_signed")
-            return out, info
-        if flips:
-            _check(self.lib.dwtx_encode_view_flip(self.h, C.byref(v), step, order, C.byref(fmt), None, flips[0], flips[1], W, H, n, capacity,
-                                                  _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view_flip")
-            return out, info
-        _check(self.lib.dwtx_encode_view_float(self.h, C.byref(v), step, order, C.byref(fmt), W, H, n, capacity, _ptr(out), out.shape[1],
-                                               _ptr(info)), "dwtx_encode_view_float")
-        return out, info
+        return self._encode_views(v, step, order, fmt, None, flips, lo, W, H, n, capacity, out, info)
 
     def decode_view(self, streams, lens, into, maxval=None, levels_max=-1, stepped=False, order="rgb", flip=None, signed=False, minval=None,
                     base=None):
@@ -871,38 +906,14 @@ class Context:
         level, stays as it is (the DecodeInfo says which).  `base=into` decodes in place; otherwise no window of `into` may
         meet one of `base` (view_delta_check).  Not with flip or levels_max."""
         order = view_order(order)
-        torch = self.torch
         lo, maxval = self._signed_range(signed, minval, maxval)
         if base is not None:
             v, vb, W, H, Cn, n, step, bstep = self._delta_views(into, base, maxval, stepped, signed, flip, levels_max)
-            assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
-            assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
-            infos = (DecodeInfo * n)()
-            _check(self.lib.dwtx_decode_view_delta(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, C.byref(v), step, C.byref(vb), bstep,
-                                                   order, 1 if signed else 0, lo if signed else 0, C.cast(infos, C.c_void_p)), "dwtx_decode_view_delta")
-            return list(infos)
+            return self._decode_views(streams, lens, v, step, order, None, None, None, None, None, W, H, n, -1,
+                                      pair=("dwtx_decode_view_delta", vb, bstep, 1 if signed else 0, lo if signed else 0))
         v, W, H, Cn, n, step = self._view(into, maxval, stepped, signed=signed)
         flips = view_flips(flip, n)
-        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
-        assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
-        infos = (DecodeInfo * n)()
-        if signed:
-            fl = flips or (0, None)
-            _check(self.lib.dwtx_decode_view_signed(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
-                                                    None, W, H, None, None, fl[0], fl[1], lo, C.cast(infos, C.c_void_p)), "dwtx_decode_view_signed")
-        elif flips:
-            _check(self.lib.dwtx_decode_view_flip(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
-                                                  None, W, H, None, None, flips[0], flips[1], C.cast(infos, C.c_void_p)), "dwtx_decode_view_flip")
-        elif order:
-            _check(self.lib.dwtx_decode_view_order(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step,
-                                                   order, C.cast(infos, C.c_void_p)), "dwtx_decode_view_order")
-        elif stepped:
-            _check(self.lib.dwtx_decode_view_step(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step,
-                                                  C.cast(infos, C.c_void_p)), "dwtx_decode_view_step")
-        else:
-            _check(self.lib.dwtx_decode_view(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
-                                             C.cast(infos, C.c_void_p)), "dwtx_decode_view")
-        return list(infos)
+        return self._decode_views(streams, lens, v, step if stepped else None, order, None, None, None, flips, lo, W, H, n, levels_max)
 
     # -- delta chains: each picture against its predecessor, the first against a key (dwtx_*_view_chain) ------------------------
 
@@ -940,16 +951,9 @@ class Context:
         encode_view(t, base=...) gives for those pairs; async.  `frames[1:]` with `frames[0]` as key codes a whole clip.  The
         streams' slots are dwtx_encode_bound16's.  Not with flip, levels_max, float tensors or lists: ValueError."""
         order = view_order(order)
-        torch = self.torch
         v, vk, W, H, Cn, n, step, kstep = self._chain_views(t, key, None, stepped, signed, unsupported)
-        stride = self.lib.dwtx_encode_bound16(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
-        if out is None:
-            out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
-        if info is None:
-            info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
-        _check(self.lib.dwtx_encode_view_chain(self.h, C.byref(v), step, C.byref(vk), kstep, order, 1 if signed else 0, W, H, n, capacity,
-                                               _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view_chain")
-        return out, info
+        return self._encode_views(v, step, order, None, None, None, None, W, H, n, capacity, out, info,
+                                  pair=("dwtx_encode_view_chain", vk, kstep, 1 if signed else 0))
 
     def decode_view_chain(self, streams, lens, into, key, maxval=None, stepped=False, order="rgb", signed=False, minval=None, **unsupported):
         """dwtx_decode_view_chain: device streams [n,stride] + int64 lens of a chain's residuals -> the windows of `into`, window i
@@ -960,15 +964,10 @@ class Context:
         `frames[1:]` as `into` is the layout it is made for.  Returns the list of DecodeInfo; syncs once.  Not with flip,
         levels_max, float tensors or lists: ValueError."""
         order = view_order(order)
-        torch = self.torch
         lo, maxval = self._signed_range(signed, minval, maxval)
         v, vk, W, H, Cn, n, step, kstep = self._chain_views(into, key, maxval, stepped, signed, unsupported)
-        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
-        assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
-        infos = (DecodeInfo * n)()
-        _check(self.lib.dwtx_decode_view_chain(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, C.byref(v), step, C.byref(vk), kstep,
-                                               order, 1 if signed else 0, lo if signed else 0, C.cast(infos, C.c_void_p)), "dwtx_decode_view_chain")
-        return list(infos)
+        return self._decode_views(streams, lens, v, step, order, None, None, None, None, None, W, H, n, -1,
+                                  pair=("dwtx_decode_view_chain", vk, kstep, 1 if signed else 0, lo if signed else 0))
 
     def decode_view_float(self, streams, lens, into, maxval=255, scale=1.0, bias=0.0, levels_max=-1, stepped=False, order="rgb", flip=None,
                           minval=0):
@@ -990,23 +989,7 @@ class Context:
         v, W, H, Cn, n, step = self._view(into, int(maxval), stepped, floats=True)
         flips = view_flips(flip, n)
         lo = self._signed_range(False, minval, maxval, floats=True)[0]
-        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
-        assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
-        infos = (DecodeInfo * n)()
-        if lo is not None:
-            fl = flips or (0, None)
-            _check(self.lib.dwtx_decode_view_signed(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
-                                                    C.byref(fmt), W, H, None, None, fl[0], fl[1], lo, C.cast(infos, C.c_void_p)),
-                   "dwtx_decode_view_signed")
-            return list(infos)
-        if flips:
-            _check(self.lib.dwtx_decode_view_flip(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
-                                                  C.byref(fmt), W, H, None, None, flips[0], flips[1], C.cast(infos, C.c_void_p)),
-                   "dwtx_decode_view_flip")
-            return list(infos)
-        _check(self.lib.dwtx_decode_view_float(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step,
-                                               order, C.byref(fmt), C.cast(infos, C.c_void_p)), "dwtx_decode_view_float")
-        return list(infos)
+        return self._decode_views(streams, lens, v, step, order, fmt, None, None, flips, lo, W, H, n, levels_max)
 
     def decode_view_crop(self, streams, lens, into, size, origins=None, maxval=None, scale=None, bias=None, levels_max=-1, stepped=False,
                          order="rgb", flip=None, signed=False, minval=None):
@@ -1029,31 +1012,8 @@ class Context:
         lo, maxval = self._signed_range(signed, minval, maxval, floats=floats)
         v, cw, ch, Cn, n, step = self._view(into, None if maxval is None else int(maxval), stepped, floats=floats, signed=signed)
         flips = view_flips(flip, n)
-        org = None
-        if origins is not None:
-            flat = [int(c) for c in origins] if len(origins) == 2 and not hasattr(origins[0], "__len__") else None
-            pairs = [tuple(flat)] * n if flat is not None else [(int(x), int(y)) for x, y in origins]
-            if len(pairs) != n:
-                raise ValueError(f"origins: one (x0, y0) pair or {n}, not {len(pairs)}")
-            org = (C.c_int * (2 * n))(*[c for p in pairs for c in p])
-        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
-        assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
-        infos = (DecodeInfo * n)()
-        if lo is not None:
-            fl = flips or (0, None)
-            _check(self.lib.dwtx_decode_view_signed(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
-                                                    C.byref(fmt) if fmt is not None else None, cw, ch, org, None, fl[0], fl[1], lo,
-                                                    C.cast(infos, C.c_void_p)), "dwtx_decode_view_signed")
-            return list(infos)
-        if flips:
-            _check(self.lib.dwtx_decode_view_flip(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
-                                                  C.byref(fmt) if fmt is not None else None, cw, ch, org, None, flips[0], flips[1],
-                                                  C.cast(infos, C.c_void_p)), "dwtx_decode_view_flip")
-            return list(infos)
-        _check(self.lib.dwtx_decode_view_crop(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v), step, order,
-                                              C.byref(fmt) if fmt is not None else None, cw, ch, org, C.cast(infos, C.c_void_p)),
-               "dwtx_decode_view_crop")
-        return list(infos)
+        org = self._origins(origins, n)
+        return self._decode_views(streams, lens, v, step, order, fmt, (cw, ch, org), None, flips, lo, W, H, n, levels_max)
 
     # -- window lists: one pointer per picture (dwtx_encode_view_list / dwtx_decode_view_list) ------------------------
 
@@ -1083,35 +1043,15 @@ class Context:
         encode_view (int16 windows); minval: as for encode_view_float (float windows).  Returns (streams, info) like
         encode_view; async."""
         order = view_order(order)
-        torch = self.torch
         v, arr, f, floats = self._view_list(windows, maxval, stepped, signed)
         lo = self._signed_range(signed, minval, maxval, floats=floats)[0]
         if not floats and (scale is not None or bias is not None):
             raise ValueError("scale and bias belong to float tensors")
         fmt = float_format(windows[0].dtype, 1.0 if scale is None else scale, 0.0 if bias is None else bias) if floats else None
-        W, H, Cn, n = f["W"], f["H"], f["channels"], f["n"]
-        flips = view_flips(flip, n)
-        deep = (v.maxval > 255 or lo is not None) if floats else v.sample_bytes == 2
-        bound = self.lib.dwtx_encode_bound16 if deep else self.lib.dwtx_encode_bound
-        stride = bound(W, H, Cn) if capacity <= 0 else (capacity + 15) // 8 * 8
-        if out is None:
-            out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
-        if info is None:
-            info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
-        if lo is not None:
-            fl = flips or (0, None)
-            _check(self.lib.dwtx_encode_view_signed(self.h, C.byref(v), f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, arr,
-                                                    fl[0], fl[1], lo if floats else 0, W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
-                   "dwtx_encode_view_signed")
-            return out, info
-        if flips:
-            _check(self.lib.dwtx_encode_view_flip(self.h, C.byref(v), f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, arr,
-                                                  flips[0], flips[1], W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)),
-                   "dwtx_encode_view_flip")
-            return out, info
-        _check(self.lib.dwtx_encode_view_list(self.h, C.byref(v), f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, arr,
-                                              W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), "dwtx_encode_view_list")
-        return out, info
+        flips = view_flips(flip, f["n"])
+        if lo is not None and not floats:   # (int16 windows: the source's range is its samples')
+            lo = 0
+        return self._encode_views(v, f["pixel_step"], order, fmt, arr, flips, lo, f["W"], f["H"], f["n"], capacity, out, info)
 
     def decode_view_list(self, streams, lens, windows, size=None, origins=None, maxval=None, scale=None, bias=None, levels_max=-1,
                          stepped=False, order="rgb", flip=None, signed=False, minval=None):
@@ -1132,28 +1072,5 @@ class Context:
         cw, ch, n = f["W"], f["H"], f["n"]
         flips = view_flips(flip, n)
         W, H = (cw, ch) if size is None else (int(s) for s in size)
-        org = None
-        if origins is not None:
-            flat = [int(c) for c in origins] if len(origins) == 2 and not hasattr(origins[0], "__len__") else None
-            pairs = [tuple(flat)] * n if flat is not None else [(int(x), int(y)) for x, y in origins]
-            if len(pairs) != n:
-                raise ValueError(f"origins: one (x0, y0) pair or {n}, not {len(pairs)}")
-            org = (C.c_int * (2 * n))(*[c for p in pairs for c in p])
-        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
-        assert lens.dtype == torch.int64 and lens.numel() == n and lens.is_contiguous()
-        infos = (DecodeInfo * n)()
-        if lo is not None:
-            fl = flips or (0, None)
-            _check(self.lib.dwtx_decode_view_signed(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
-                                                    f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, cw, ch, org, arr,
-                                                    fl[0], fl[1], lo, C.cast(infos, C.c_void_p)), "dwtx_decode_view_signed")
-            return list(infos)
-        if flips:
-            _check(self.lib.dwtx_decode_view_flip(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
-                                                  f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, cw, ch, org, arr,
-                                                  flips[0], flips[1], C.cast(infos, C.c_void_p)), "dwtx_decode_view_flip")
-            return list(infos)
-        _check(self.lib.dwtx_decode_view_list(self.h, _ptr(streams), streams.shape[1], _ptr(lens), W, H, n, levels_max, C.byref(v),
-                                              f["pixel_step"], order, C.byref(fmt) if fmt is not None else None, cw, ch, org, arr,
-                                              C.cast(infos, C.c_void_p)), "dwtx_decode_view_list")
-        return list(infos)
+        org = self._origins(origins, n)
+        return self._decode_views(streams, lens, v, f["pixel_step"], order, fmt, (cw, ch, org), arr, flips, lo, W, H, n, levels_max)

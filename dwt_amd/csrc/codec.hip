@@ -462,34 +462,55 @@ extern "C" int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, s
 
 // ---- views (include/dwtx.h): windows and tile grids of a larger frame ----------------------------------------------
 
-// dwtx_view -> dwtx_pixels for n windows of W x H, checked; `dst`: the view will be written (maxval, disjoint windows).
-// pixel_step (the *_view_step calls; the plain ones pass 0): samples from a pixel to the next one of its row; 0 and
-// `channels` are both the dense case and leave px->pixel_step 0, so that everything downstream is the plain call's.
-// order (the *_view_order calls; the others pass DWTX_ORDER_RGB): kept for RGB views and checked first, nothing else here looks at it.
-// kind (dwtx_decode_view_float, dwtx_encode_view_float; the others pass none): the float samples the view must hold — its sample_bytes their size,
-// any maxval a deep picture may have; every stride counts those samples, and every rule below holds as it stands.
-// window (dwtx_decode_view_crop; the others pass false): W x H is a crop of a picture the caller has checked, a side from 1 up.
-// list (the *_view_list calls; the others pass none): the windows lie where list->windows says; the view's dev, cols,
-// image_stride and band_stride are not looked at, every other check is the grid's, and list_windows takes the place of the
-// rules about where the windows lie.  px->offs is not set yet: the caller brings list->offs to the device (send_list).
-// minval (the *_view_signed calls; the others pass none): integer samples are int16_t (sample_bytes 2, nothing else), coded as
-// they are, and a destination's range is [*minval, maxval] (dwtx_range_ok); float samples with *minval != 0 get that range as
-// their lower bound too (a source's: checked by the caller, source_range_ok), with *minval == 0 they are the unsigned call's.
-struct WinList {
-	const void *const *windows;   // [n] device pointers in host memory
-	std::vector<long long> offs;  // out: each window's first sample, in samples from the lowest pointer
-};
-static int list_windows(const dwtx_view *v, size_t cs, size_t row, int H, int n, bool dst, WinList *list, dwtx_pixels *px);
+// Everything a view entry point can say, each field's default its neutral value: an extern "C" entry names the fields its ABI
+// has and calls encode_views / decode_views, which resolve the call with plan_view.
+enum { PAIR_NONE = 0, PAIR_DELTA, PAIR_CHAIN };
+struct ViewCall {
+	const dwtx_view *view = nullptr;
+	size_t pixel_step = 0;                       // samples from a pixel to the next one of its row; 0 and `channels` are both the dense case
+	int order = DWTX_ORDER_RGB;                  // kept for RGB views and checked first, nothing else on the host looks at it
+	const dwtx_float_format *fmt = nullptr;      // null: integer samples
+	const void *const *windows = nullptr;        // [n] device pointers in host memory; null: the view's own grid
+	int flip = 0;                                // DWTX_FLIP_* flags for all windows, or
+	const unsigned char *host_flips = nullptr;   // one mask per window
+	const int *minval = nullptr;                 // the *_view_signed calls' lower bound (a pair call's: what `sgn` makes of it); null: the unsigned call
+	bool crop = false;                           // a decode writes a crop_w x crop_h window of each picture, picture i's from host_origins[2 * i], [2 * i + 1]
+	int crop_w = 0, crop_h = 0;
+	const int *host_origins = nullptr;           // (host memory; null: all at (0, 0))
+	int levels_max = -1;                         // a decode's
+	int pair = PAIR_NONE;                        // a delta or chain call: `other` is the base view / the key, with its own step
+	const dwtx_view *other = nullptr;
+	size_t other_step = 0;
+	int sgn = 0;
+	int W = 0, H = 0, n = 0;                     // the pictures' size and number
+	bool dst = false;                            // the view will be written (maxval, disjoint windows)
+	// what single entries insist on: the float calls on a format, the list calls on a list
+	bool needs_fmt = false, needs_windows = false;
+	// the host-only exports: a view of 4-byte samples is one of fp32 samples (fp16 and bf16 views are addressed, and checked, like
+	// 16-bit integers); windows with sides from 1 up; the table of windows is built whatever the flags (dwtx_view_flip_plan reads it)
+	bool kind_from_bytes = false, thin = false, table = false;
 
-static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, dwtx_pixels *px, int kind = -1, bool window = false,
-	WinList *list = nullptr, const int *minval = nullptr)
+	int win_w() const { return crop ? crop_w : W; }   // the windows' sides
+	int win_h() const { return crop ? crop_h : H; }
+};
+
+// dwtx_view -> dwtx_pixels for c.n windows of win_w() x win_h(), checked; the call as plan_view has normalised it.
+// kind: the float samples the view must hold — its sample_bytes their size, any maxval a deep picture may have; every stride counts
+// those samples, and every rule below holds as it stands — or -1 for integer samples.
+// Listed windows (c.windows): the view's dev, cols, image_stride and band_stride are not looked at, every other check is the
+// grid's, and list_windows (the caller's next step) takes the place of the rules about where the windows lie.
+// c.minval: integer samples are int16_t (sample_bytes 2, nothing else), coded as they are, and a destination's range is [*minval,
+// maxval] (dwtx_range_ok); float samples get that range as their lower bound too.
+static int view_pixels(const ViewCall &c, int kind, dwtx_pixels *px)
 {
-	const bool sgn = minval && (kind < 0 || *minval != 0);
-	if (order != DWTX_ORDER_RGB && order != DWTX_ORDER_BGR) {
-		dwtx_set_error("view: channel order %d (DWTX_ORDER_RGB = 0 or DWTX_ORDER_BGR = 1)", order);
+	const dwtx_view *v = c.view;
+	const int W = c.win_w(), H = c.win_h(), n = c.n;
+	const bool dst = c.dst, list = c.windows || c.needs_windows, sgn = c.minval != nullptr;
+	if (c.order != DWTX_ORDER_RGB && c.order != DWTX_ORDER_BGR) {
+		dwtx_set_error("view: channel order %d (DWTX_ORDER_RGB = 0 or DWTX_ORDER_BGR = 1)", c.order);
 		return DWTX_ERR_ARG;
 	}
-	if (list && !list->windows) {
+	if (list && !c.windows) {
 		dwtx_set_error("view list: no list of windows (the grid calls take a view without one)");
 		return DWTX_ERR_ARG;
 	}
@@ -497,9 +518,9 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 		dwtx_set_error("no view, no pixels or no windows");
 		return DWTX_ERR_ARG;
 	}
-	if (!window)
+	if (!c.crop && !c.thin)
 		DWTX_CHECK_DIMS(W, H);
-	else if (W < 1 || H < 1 || W > DWTX_MAX_SIDE || H > DWTX_MAX_SIDE)
+	else if (W < 1 || H < 1 || W > DWTX_MAX_SIDE || H > DWTX_MAX_SIDE)   // (a crop of a picture that crop_of_call has checked)
 		return DWTX_ERR_ARG;
 	if (kind >= 0 && v->sample_bytes != (kind == DWTX_SAMPLE_F32 ? 4 : 2)) {
 		dwtx_set_error("view: sample_bytes %d does not match the float type (%d bytes a sample)", v->sample_bytes, kind == DWTX_SAMPLE_F32 ? 4 : 2);
@@ -514,17 +535,27 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 		return DWTX_ERR_ARG;
 	}
 	const size_t cs = v->channels == 3 ? v->channel_stride : 0;   // planar RGB; a gray view has no use for it
-	const size_t step = pixel_step == (size_t)v->channels ? 0 : pixel_step;
+	const size_t step = c.pixel_step == (size_t)v->channels ? 0 : c.pixel_step;   // (the dense case: everything downstream is the plain call's)
 	if (step && (step < (size_t)v->channels || step > 0x7fffffffu)) {
-		dwtx_set_error("view: pixel_step %zu is less than the %d channels of a pixel (or beyond 2^31)", pixel_step, v->channels);
+		dwtx_set_error("view: pixel_step %zu is less than the %d channels of a pixel (or beyond 2^31)", c.pixel_step, v->channels);
 		return DWTX_ERR_ARG;
 	}
 	if (step && cs) {
-		dwtx_set_error("view: pixel_step %zu with planar pixels (channel_stride %zu): the rows of a plane are dense", pixel_step, cs);
+		dwtx_set_error("view: pixel_step %zu with planar pixels (channel_stride %zu): the rows of a plane are dense", c.pixel_step, cs);
 		return DWTX_ERR_ARG;
 	}
-	// a row of a window (planar: of one of its planes), from its first sample to behind its last
-	const size_t row = cs ? (size_t)W : step ? (size_t)(W - 1) * step + v->channels : (size_t)W * v->channels;
+	const size_t image_stride = list ? 0 : v->image_stride;
+	*px = kind >= 0            ? dwtx_pixels_float(v->dev, kind, v->channels, image_stride, v->maxval)
+		: sgn                  ? dwtx_pixels_s16((const int16_t *)v->dev, v->channels, image_stride, dst ? *c.minval : -32768, dst ? v->maxval : 32767)
+		: v->sample_bytes == 1 ? dwtx_pixels8((const uint8_t *)v->dev, v->channels, image_stride)
+		                       : dwtx_pixels16((const uint16_t *)v->dev, v->channels, image_stride, dst ? v->maxval : 65535);
+	if (sgn && kind >= 0)
+		px->minval = *c.minval;
+	px->row_pitch = v->row_pitch;
+	px->channel_stride = cs;
+	px->pixel_step = step;
+	px->order = v->channels == 3 ? c.order : DWTX_ORDER_RGB;
+	const size_t row = px->row_samples(W);
 	if (v->row_pitch < row) {
 		dwtx_set_error("view: row_pitch %zu is less than a window's row of %zu samples", v->row_pitch, row);
 		return DWTX_ERR_ARG;
@@ -536,7 +567,7 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 	const size_t cols = list ? (size_t)n : v->cols && v->cols < n ? (size_t)v->cols : (size_t)n;
 	const bool bands = cols < (size_t)n;
 	if (dst && sgn) {
-		if (!dwtx_range_ok(*minval, v->maxval))
+		if (!dwtx_range_ok(*c.minval, v->maxval))
 			return DWTX_ERR_ARG;
 	} else if (dst && (v->sample_bytes == 1 ? v->maxval != 255 : !dwtx_maxval_ok(v->maxval))) {
 		if (v->sample_bytes == 1)
@@ -570,19 +601,6 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 			}
 		}
 	}
-	const size_t image_stride = list ? 0 : v->image_stride;
-	*px = kind >= 0            ? dwtx_pixels_float(v->dev, kind, v->channels, image_stride, v->maxval)
-		: sgn                  ? dwtx_pixels_s16((const int16_t *)v->dev, v->channels, image_stride, dst ? *minval : -32768, dst ? v->maxval : 32767)
-		: v->sample_bytes == 1 ? dwtx_pixels8((const uint8_t *)v->dev, v->channels, image_stride)
-		                       : dwtx_pixels16((const uint16_t *)v->dev, v->channels, image_stride, dst ? v->maxval : 65535);
-	if (sgn && kind >= 0)
-		px->minval = *minval;
-	px->row_pitch = v->row_pitch;
-	px->channel_stride = cs;
-	px->pixel_step = step;
-	px->order = v->channels == 3 ? order : DWTX_ORDER_RGB;
-	if (list)
-		return list_windows(v, cs, row, H, n, dst, list, px);
 	if (bands) {
 		px->cols = (int)cols;
 		px->band_stride = v->band_stride;
@@ -590,28 +608,40 @@ static int pixels_of_view(const dwtx_view *v, size_t pixel_step, int order, int 
 	return DWTX_OK;
 }
 
-// What a listed view adds to pixels_of_view (include/dwtx.h, the *_view_list calls): every pointer given and on its sample;
-// px->base the lowest of them and list->offs the windows' offsets from it; whether all of them are on the wide kernels' quad;
-// and, for a destination, that the units — the n windows, or the 3n planes of planar RGB — are provably disjoint.
-// Two units whose first samples lie d apart are disjoint if d >= span (one ends before the other begins), or if, with dx =
-// d % pitch, dx >= row and dx + row <= pitch: unit A covers the columns [0, row) of the lattice of rows `pitch` apart that
-// starts at its first sample, unit B the columns [dx, dx + row) of the same lattice.  Sorted by address, only the units that
-// begin inside a unit's span have to be held against it: a frame of tiles costs each tile the tiles of its own band.
-static int list_windows(const dwtx_view *v, size_t cs, size_t row, int H, int n, bool dst, WinList *list, dwtx_pixels *px)
+// The planes of a call that walks a table of windows, listed or flipped: refused before the table is built
+static bool table_count_ok(const ViewCall &c, int channels)
 {
-	if (dst ? !dwtx_count_ok(n, DWTX_MAX_PLANES_PER_CALL / 3, "streams to decode") : !dwtx_count_ok((long)n * v->channels, DWTX_MAX_PLANES_PER_CALL, "planes"))
-		return DWTX_ERR_ARG;
-	const uintptr_t sb = (uintptr_t)v->sample_bytes;
+	return c.dst ? dwtx_count_ok(c.n, DWTX_MAX_PLANES_PER_CALL / 3, "streams to decode") : dwtx_count_ok((long)c.n * channels, DWTX_MAX_PLANES_PER_CALL, "planes");
+}
+
+// The lattice rule for two units whose rows lie `pitch` apart: unit A covers the columns [0, row_a) of the lattice that starts at
+// its first sample, unit B, which starts in column dx of it, the columns [dx, dx + row_b).  Disjoint columns: disjoint units.
+static bool other_columns(unsigned long long dx, unsigned long long row_a, unsigned long long row_b, unsigned long long pitch)
+{
+	return dx >= row_a && dx + row_b <= pitch;
+}
+
+// What a listed view adds to view_pixels (include/dwtx.h, the *_view_list calls): every pointer given and on its sample;
+// px->base the lowest of them and *offs the windows' offsets from it, in samples; whether all of them are on the wide kernels'
+// quad; and, for a destination, that the units — the n windows, or the 3n planes of planar RGB — are provably disjoint.
+// Two units whose first samples lie d apart are disjoint if d >= span (one ends before the other begins), or by the lattice rule
+// with dx = d % pitch.  Sorted by address, only the units that begin inside a unit's span have to be held against it: a frame of
+// tiles costs each tile the tiles of its own band.  px->offs is not set yet: send_list brings the table to the device.
+static int list_windows(const ViewCall &c, std::vector<long long> *offs, dwtx_pixels *px)
+{
+	const int n = c.n;
+	const size_t cs = px->channel_stride, row = px->row_samples(c.win_w());
+	const uintptr_t sb = (uintptr_t)px->sample_bytes;
 	uintptr_t lowest = ~(uintptr_t)0;
 	bool quad = true;
 	for (int i = 0; i < n; ++i) {
-		const uintptr_t p = (uintptr_t)list->windows[i];
+		const uintptr_t p = (uintptr_t)c.windows[i];
 		if (!p) {
 			dwtx_set_error("view list: window %d of %d is NULL", i, n);
 			return DWTX_ERR_ARG;
 		}
 		if (p % sb) {
-			dwtx_set_error("view list: window %d (%p) is not aligned to its %d-byte samples", i, list->windows[i], v->sample_bytes);
+			dwtx_set_error("view list: window %d (%p) is not aligned to its %d-byte samples", i, c.windows[i], px->sample_bytes);
 			return DWTX_ERR_ARG;
 		}
 		quad = quad && p % (4 * sb) == 0;
@@ -623,24 +653,24 @@ static int list_windows(const dwtx_view *v, size_t cs, size_t row, int H, int n,
 	};
 	std::vector<Unit> units;
 	try {
-		list->offs.resize((size_t)n);
-		if (dst)
+		offs->resize((size_t)n);
+		if (c.dst)
 			units.reserve((size_t)n * (cs ? 3 : 1));
 	} catch (...) {
 		return DWTX_ERR_NOMEM;
 	}
 	for (int i = 0; i < n; ++i)
-		list->offs[(size_t)i] = (long long)(((uintptr_t)list->windows[i] - lowest) / sb);
-	if (dst) {
-		const unsigned long long pitch = v->row_pitch, span = (unsigned long long)(H - 1) * pitch + row;
+		(*offs)[(size_t)i] = (long long)(((uintptr_t)c.windows[i] - lowest) / sb);
+	if (c.dst) {
+		const unsigned long long pitch = px->row_pitch, span = (unsigned long long)(c.win_h() - 1) * pitch + row;
 		for (int i = 0; i < n; ++i)
-			for (int c = 0; c < (cs ? 3 : 1); ++c)
-				units.push_back(Unit{ (unsigned long long)list->offs[(size_t)i] + (unsigned long long)c * cs, i });
+			for (int ch = 0; ch < (cs ? 3 : 1); ++ch)
+				units.push_back(Unit{ (unsigned long long)(*offs)[(size_t)i] + (unsigned long long)ch * cs, i });
 		std::sort(units.begin(), units.end(), [](const Unit &a, const Unit &b) { return a.at < b.at; });
 		for (size_t i = 0; i < units.size(); ++i)
 			for (size_t j = i + 1; j < units.size() && units[j].at - units[i].at < span; ++j) {
 				const unsigned long long d = units[j].at - units[i].at, dx = d % pitch;
-				if (dx >= row && dx + row <= pitch)
+				if (other_columns(dx, row, row, pitch))
 					continue;
 				dwtx_set_error("view list: windows %d and %d are not provably disjoint (%s %llu samples apart: less than the %llu a %s spans, "
 					"and column %llu of a pitch of %llu leaves no room for two rows of %zu)", units[i].window, units[j].window,
@@ -653,16 +683,14 @@ static int list_windows(const dwtx_view *v, size_t cs, size_t row, int H, int n,
 	return DWTX_OK;
 }
 
-// The table's way to the device: into the context's page-locked buffer — the caller's array and list.offs may go as soon as the
+// The table's way to the device: into the context's page-locked buffer — the caller's array and `offs` may go as soon as the
 // call returns — and from there into SLOT_CD_LIST by an asynchronous copy on the context's stream, in order with the kernels of an
 // earlier listed call that still read the slot and ahead of this call's.  The host waits only for list_sent, the earlier listed
 // call's own copy; a slot or a buffer that has to grow waits for more, as every scratch slot does.  Sets px->offs.
-static int send_list(dwtx_ctx *ctx, const WinList &list, dwtx_pixels *px)
+static int send_list(dwtx_ctx *ctx, const std::vector<long long> &offs, dwtx_pixels *px)
 {
-	if (!ctx)
-		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
-	const size_t n = list.offs.size(), bytes = sizeof(long long) * n;
+	const size_t n = offs.size(), bytes = sizeof(long long) * n;
 	if (!ctx->have_list_sent) {
 		DWTX_HIP(hipEventCreateWithFlags(&ctx->list_sent, hipEventDisableTiming));
 		ctx->have_list_sent = true;
@@ -680,82 +708,11 @@ static int send_list(dwtx_ctx *ctx, const WinList &list, dwtx_pixels *px)
 	long long *dev = (long long *)dwtx_scratch(ctx, SLOT_CD_LIST, bytes);
 	if (!dev)
 		return DWTX_ERR_NOMEM;
-	memcpy(ctx->list_host, list.offs.data(), bytes);
+	memcpy(ctx->list_host, offs.data(), bytes);
 	DWTX_HIP(hipMemcpyAsync(dev, ctx->list_host, bytes, hipMemcpyHostToDevice, ctx->stream));
 	DWTX_HIP(hipEventRecord(ctx->list_sent, ctx->stream));
 	px->offs = dev;
 	return DWTX_OK;
-}
-
-extern "C" int dwtx_encode_view(dwtx_ctx *ctx, const dwtx_view *src, int W, int H, int n, long capacity,
-	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
-{
-	dwtx_pixels px;
-	if (const int rc = pixels_of_view(src, 0, DWTX_ORDER_RGB, W, H, n, false, &px))
-		return rc;
-	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
-}
-
-extern "C" int dwtx_encode_view_step(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int W, int H, int n, long capacity,
-	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
-{
-	dwtx_pixels px;
-	if (const int rc = pixels_of_view(src, pixel_step, DWTX_ORDER_RGB, W, H, n, false, &px))
-		return rc;
-	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
-}
-
-extern "C" int dwtx_decode_view(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
-	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, dwtx_decode_info *host_info)
-{
-	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, 0, DWTX_ORDER_RGB, W, H, n, true, &px))
-		return rc;
-	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
-}
-
-extern "C" int dwtx_decode_view_step(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
-	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, dwtx_decode_info *host_info)
-{
-	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, pixel_step, DWTX_ORDER_RGB, W, H, n, true, &px))
-		return rc;
-	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
-}
-
-// The view calls from here on are one body each for the unsigned entry point and for its way through dwtx_encode_view_signed /
-// dwtx_decode_view_signed (further down): `minval` is null in the former and the signed call's lower bound in the latter —
-// what pixels_of_view makes of it is all that differs.
-static int encode_view_order(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, int W, int H, int n, long capacity,
-	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, const int *minval)
-{
-	dwtx_pixels px;
-	if (const int rc = pixels_of_view(src, pixel_step, order, W, H, n, false, &px, -1, false, nullptr, minval))
-		return rc;
-	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
-}
-
-extern "C" int dwtx_encode_view_order(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, int W, int H, int n, long capacity,
-	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
-{
-	return encode_view_order(ctx, src, pixel_step, order, W, H, n, capacity, dev_out, out_stride, dev_info, nullptr);
-}
-
-static int decode_view_order(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
-	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
-	dwtx_decode_info *host_info, const int *minval)
-{
-	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, pixel_step, order, W, H, n, true, &px, -1, false, nullptr, minval))
-		return rc;
-	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
-}
-
-extern "C" int dwtx_decode_view_order(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
-	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
-	dwtx_decode_info *host_info)
-{
-	return decode_view_order(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, host_info, nullptr);
 }
 
 // dwtx_float_format -> the sample kind of dwtx_pixels, checked (what both float calls refuse alike)
@@ -776,41 +733,6 @@ static int float_kind(const dwtx_float_format *fmt, int *kind)
 		}
 	*kind = fmt->type == DWTX_FLOAT32 ? DWTX_SAMPLE_F32 : fmt->type == DWTX_FLOAT16 ? DWTX_SAMPLE_F16 : DWTX_SAMPLE_BF16;
 	return DWTX_OK;
-}
-
-static void set_float_format(dwtx_pixels *px, const dwtx_float_format *fmt)
-{
-	for (int c = 0; c < 3; ++c) {
-		px->scale[c] = fmt->scale[c];
-		px->bias[c] = fmt->bias[c];
-	}
-}
-
-// the quantiser's clamp of a float source: maxval alone, or the range of a signed call with a lower bound other than 0
-static bool source_range_ok(const dwtx_view *src, const int *minval)
-{
-	return minval && *minval ? dwtx_range_ok(*minval, src->maxval) : dwtx_maxval_ok(src->maxval);
-}
-
-static int decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
-	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
-	const dwtx_float_format *fmt, dwtx_decode_info *host_info, const int *minval)
-{
-	int kind;
-	if (const int rc = float_kind(fmt, &kind))
-		return rc;
-	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, pixel_step, order, W, H, n, true, &px, kind, false, nullptr, minval))
-		return rc;
-	set_float_format(&px, fmt);
-	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
-}
-
-extern "C" int dwtx_decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
-	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
-	const dwtx_float_format *fmt, dwtx_decode_info *host_info)
-{
-	return decode_view_float(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, host_info, nullptr);
 }
 
 extern "C" int dwtx_crop_plan(int W, int H, int x0, int y0, int cw, int ch, dwtx_crop_rect out[DWTX_MAX_LEVELS + 1])
@@ -837,22 +759,23 @@ extern "C" int dwtx_crop_plan(int W, int H, int x0, int y0, int cw, int ch, dwtx
 }
 
 // what the crop calls refuse of a crop and its origins; *whole: the crop is every picture itself (the plain call)
-static int crop_of_call(int W, int H, int n, int crop_w, int crop_h, const int *host_origins, bool *whole)
+static int crop_of_call(const ViewCall &c, bool *whole)
 {
+	const int W = c.W, H = c.H;
 	DWTX_CHECK_DIMS(W, H);
-	if (crop_w < 1 || crop_w > W || crop_h < 1 || crop_h > H) {
-		dwtx_set_error("crop: %dx%d is no window of a %dx%d picture (sides of 1 up to the picture's)", crop_w, crop_h, W, H);
+	if (c.crop_w < 1 || c.crop_w > W || c.crop_h < 1 || c.crop_h > H) {
+		dwtx_set_error("crop: %dx%d is no window of a %dx%d picture (sides of 1 up to the picture's)", c.crop_w, c.crop_h, W, H);
 		return DWTX_ERR_ARG;
 	}
-	if (n < 1) {
+	if (c.n < 1) {
 		dwtx_set_error("no view, no pixels or no windows");
 		return DWTX_ERR_ARG;
 	}
-	*whole = crop_w == W && crop_h == H;
-	for (int i = 0; host_origins && i < n; ++i) {
-		const int x0 = host_origins[2 * i], y0 = host_origins[2 * i + 1];
-		if (x0 < 0 || y0 < 0 || x0 > W - crop_w || y0 > H - crop_h) {
-			dwtx_set_error("crop: origin (%d, %d) of picture %d puts its %dx%d window outside the %dx%d picture", x0, y0, i, crop_w, crop_h, W, H);
+	*whole = c.crop_w == W && c.crop_h == H;
+	for (int i = 0; c.host_origins && i < c.n; ++i) {
+		const int x0 = c.host_origins[2 * i], y0 = c.host_origins[2 * i + 1];
+		if (x0 < 0 || y0 < 0 || x0 > W - c.crop_w || y0 > H - c.crop_h) {
+			dwtx_set_error("crop: origin (%d, %d) of picture %d puts its %dx%d window outside the %dx%d picture", x0, y0, i, c.crop_w, c.crop_h, W, H);
 			return DWTX_ERR_ARG;
 		}
 		*whole = *whole && !x0 && !y0;
@@ -860,162 +783,30 @@ static int crop_of_call(int W, int H, int n, int crop_w, int crop_h, const int *
 	return DWTX_OK;
 }
 
-static int decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
-	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int crop_w, int crop_h, const int *host_origins, dwtx_decode_info *host_info, const int *minval)
-{
-	bool whole;
-	if (const int rc = crop_of_call(W, H, n, crop_w, crop_h, host_origins, &whole))
-		return rc;
-	if (whole)   // the plain call, on its own path
-		return fmt ? decode_view_float(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, host_info, minval)
-		           : decode_view_order(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, host_info, minval);
-	int kind = -1;
-	if (fmt)
-		if (const int rc = float_kind(fmt, &kind))
-			return rc;
-	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, pixel_step, order, crop_w, crop_h, n, true, &px, kind, true, nullptr, minval))
-		return rc;
-	if (fmt)
-		set_float_format(&px, fmt);
-	const CropCall crop = { crop_w, crop_h, host_origins };
-	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info, &crop);
-}
-
-extern "C" int dwtx_decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
-	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int crop_w, int crop_h, const int *host_origins, dwtx_decode_info *host_info)
-{
-	return decode_view_crop(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h, host_origins,
-		host_info, nullptr);
-}
-
-// The source's maxval is the quantiser's clamp (the one encode that reads it): up to 255 the picture is one of bytes and takes
-// their route, beyond it a deep picture's (dwtx_pixels::deep_source()); the streams are those of dwtx_encode_device /
-// dwtx_encode_device16 on the quantised picture either way.
-static int encode_view_float(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, const int *minval)
-{
-	int kind;
-	if (const int rc = float_kind(fmt, &kind))
-		return rc;
-	dwtx_pixels px;
-	if (const int rc = pixels_of_view(src, pixel_step, order, W, H, n, false, &px, kind, false, nullptr, minval))
-		return rc;
-	if (!source_range_ok(src, minval))
-		return DWTX_ERR_ARG;
-	set_float_format(&px, fmt);
-	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
-}
-
-extern "C" int dwtx_encode_view_float(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
-{
-	return encode_view_float(ctx, src, pixel_step, order, fmt, W, H, n, capacity, dev_out, out_stride, dev_info, nullptr);
-}
-
-// ---- window lists (include/dwtx.h): one pointer per picture --------------------------------------------------------------
-
-extern "C" int dwtx_view_list_check(const dwtx_view *v, size_t pixel_step, int W, int H, int n, const void *const *host_windows, int dst)
-{
-	WinList list{ host_windows, {} };
-	dwtx_pixels px;
-	// (a view of 4-byte samples is one of fp32 samples; fp16 and bf16 views are addressed, and checked, like 16-bit integers)
-	return pixels_of_view(v, pixel_step, DWTX_ORDER_RGB, W, H, n, dst != 0, &px, v && v->sample_bytes == 4 ? DWTX_SAMPLE_F32 : -1, true, &list);
-}
-
-static int encode_view_list(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	const void *const *host_windows, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info,
-	const int *minval)
-{
-	if (!ctx || !dev_out || !dev_info)
-		return DWTX_ERR_ARG;
-	int kind = -1;
-	if (fmt)
-		if (const int rc = float_kind(fmt, &kind))
-			return rc;
-	WinList list{ host_windows, {} };
-	dwtx_pixels px;
-	if (const int rc = pixels_of_view(src, pixel_step, order, W, H, n, false, &px, kind, false, &list, minval))
-		return rc;
-	if (fmt) {
-		if (!source_range_ok(src, minval))
-			return DWTX_ERR_ARG;
-		set_float_format(&px, fmt);
-	}
-	if (const int rc = send_list(ctx, list, &px))
-		return rc;
-	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx->enc_index);
-}
-
-extern "C" int dwtx_encode_view_list(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	const void *const *host_windows, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
-{
-	return encode_view_list(ctx, src, pixel_step, order, fmt, host_windows, W, H, n, capacity, dev_out, out_stride, dev_info, nullptr);
-}
-
-static int decode_view_list(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
-	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, dwtx_decode_info *host_info, const int *minval)
-{
-	if (!ctx || !dev_streams || !dev_lens || !host_info)
-		return DWTX_ERR_ARG;
-	bool whole;
-	if (const int rc = crop_of_call(W, H, n, crop_w, crop_h, host_origins, &whole))
-		return rc;
-	int kind = -1;
-	if (fmt)
-		if (const int rc = float_kind(fmt, &kind))
-			return rc;
-	WinList list{ host_windows, {} };
-	dwtx_pixels px;
-	if (const int rc = pixels_of_view(dst, pixel_step, order, crop_w, crop_h, n, true, &px, kind, !whole, &list, minval))
-		return rc;
-	if (fmt)
-		set_float_format(&px, fmt);
-	if (const int rc = send_list(ctx, list, &px))
-		return rc;
-	if (whole)
-		return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
-	const CropCall crop = { crop_w, crop_h, host_origins };
-	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info, &crop);
-}
-
-extern "C" int dwtx_decode_view_list(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
-	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, dwtx_decode_info *host_info)
-{
-	return decode_view_list(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h, host_origins,
-		host_windows, host_info, nullptr);
-}
-
-// ---- flips in views (include/dwtx.h): a mask of DWTX_FLIP_X and DWTX_FLIP_Y per window ---------------------------------------
-
-// window i's flags of a *_view_flip call, checked: host_flips[i], or `flip` for all; *any: one of them is not 0
-static int flip_flags(int n, int flip, const unsigned char *host_flips, std::vector<unsigned char> *flags, bool *any)
+// window i's flags of a call with flips, checked: host_flips[i], or `flip` for all; *any: one of them is not 0
+static int flip_flags(const ViewCall &c, std::vector<unsigned char> *flags, bool *any)
 {
 	*any = false;
-	if (host_flips && flip) {
-		dwtx_set_error("flip: flags for all windows (%d) together with a flag per window (host_flips): one of the two", flip);
+	if (c.host_flips && c.flip) {
+		dwtx_set_error("flip: flags for all windows (%d) together with a flag per window (host_flips): one of the two", c.flip);
 		return DWTX_ERR_ARG;
 	}
-	if (flip < 0 || flip > (DWTX_FLIP_X | DWTX_FLIP_Y)) {
-		dwtx_set_error("flip: flags %d (a mask of DWTX_FLIP_X = 1 and DWTX_FLIP_Y = 2: 0..3)", flip);
+	if (c.flip < 0 || c.flip > (DWTX_FLIP_X | DWTX_FLIP_Y)) {
+		dwtx_set_error("flip: flags %d (a mask of DWTX_FLIP_X = 1 and DWTX_FLIP_Y = 2: 0..3)", c.flip);
 		return DWTX_ERR_ARG;
 	}
-	if (n < 1) {
+	if (c.n < 1) {
 		dwtx_set_error("no view, no pixels or no windows");
 		return DWTX_ERR_ARG;
 	}
 	try {
-		flags->assign((size_t)n, (unsigned char)flip);
+		flags->assign((size_t)c.n, (unsigned char)c.flip);
 	} catch (...) {
 		return DWTX_ERR_NOMEM;
 	}
-	for (int i = 0; i < n; ++i) {
-		if (host_flips)
-			(*flags)[(size_t)i] = host_flips[i];
+	for (int i = 0; i < c.n; ++i) {
+		if (c.host_flips)
+			(*flags)[(size_t)i] = c.host_flips[i];
 		if ((*flags)[(size_t)i] > (DWTX_FLIP_X | DWTX_FLIP_Y)) {
 			dwtx_set_error("flip: flags %d of window %d (a mask of DWTX_FLIP_X = 1 and DWTX_FLIP_Y = 2: 0..3)", (int)(*flags)[(size_t)i], i);
 			return DWTX_ERR_ARG;
@@ -1025,184 +816,28 @@ static int flip_flags(int n, int flip, const unsigned char *host_flips, std::vec
 	return DWTX_OK;
 }
 
-// pixels_of_view for a call with flips: the listed view as it is, or (windows null) the view's own grid, checked as a grid
-// and then spelled out — list->offs from v->dev, px a listed view — so that every flipped call travels as a listed one.
-// px->offs is not set yet and list->offs carries no flags yet (flip_entries)
-static int flipped_view(const dwtx_view *v, size_t pixel_step, int order, int W, int H, int n, bool dst, int kind, bool window,
-	const void *const *windows, WinList *list, dwtx_pixels *px, const int *minval = nullptr)
+// What the delta and the chain calls refuse of their two views before either is looked at alone: `what` view and its `other`
+static int pair_refusals(const ViewCall &c, const char *what, const char *other)
 {
-	list->windows = windows;
-	if (windows) {
-		if (const int rc = pixels_of_view(v, pixel_step, order, W, H, n, dst, px, kind, window, list, minval))
-			return rc;
-	} else {
-		if (const int rc = pixels_of_view(v, pixel_step, order, W, H, n, dst, px, kind, window, nullptr, minval))
-			return rc;
-		if (dst ? !dwtx_count_ok(n, DWTX_MAX_PLANES_PER_CALL / 3, "streams to decode") : !dwtx_count_ok((long)n * v->channels, DWTX_MAX_PLANES_PER_CALL, "planes"))
-			return DWTX_ERR_ARG;
-		try {
-			list->offs.resize((size_t)n);
-		} catch (...) {
-			return DWTX_ERR_NOMEM;
-		}
-		const size_t cols = px->cols ? (size_t)px->cols : (size_t)n;
-		for (size_t i = 0; i < (size_t)n; ++i)
-			list->offs[i] = (long long)(i / cols * px->band_stride + i % cols * px->image_stride);
-		px->cols = 0;
-		px->band_stride = px->image_stride = 0;
-		px->offs_on_quad = true;   // (what wide() asks of a list: every window's own first sample on the quad)
-		for (size_t i = 0; i < (size_t)n; ++i)
-			px->offs_on_quad = px->offs_on_quad && list->offs[i] % 4 == 0;
+	const int minval = c.minval ? *c.minval : 0;
+	if (c.sgn != 0 && c.sgn != 1) {
+		dwtx_set_error("%s view: sgn %d (0: uint8_t / uint16_t samples, 1: int16_t samples)", what, c.sgn);
+		return DWTX_ERR_ARG;
 	}
-	px->flips = true;
-	px->flip_w = W;
-	px->flip_h = H;
-	return DWTX_OK;
-}
-
-// the flags into the top bits of the windows' table entries (dwtx_pixels::flips; offsets are sample counts of one allocation, far below)
-static void flip_entries(WinList *list, const std::vector<unsigned char> &flags)
-{
-	for (size_t i = 0; i < list->offs.size(); ++i)
-		list->offs[i] = (long long)((unsigned long long)list->offs[i] | (unsigned long long)flags[i] << DWTX_FLIP_SHIFT);
-}
-
-extern "C" int dwtx_view_flip_plan(const dwtx_view *v, size_t pixel_step, int W, int H, int n, const void *const *host_windows,
-	int flip, const unsigned char *host_flips, int dst, long long *origin, long long *pitch, long long *step)
-{
-	std::vector<unsigned char> flags;
-	bool any;
-	if (const int rc = flip_flags(n, flip, host_flips, &flags, &any))
-		return rc;
-	WinList list{ nullptr, {} };
-	dwtx_pixels px;
-	// (a view of 4-byte samples is one of fp32 samples, as for dwtx_view_list_check)
-	if (const int rc = flipped_view(v, pixel_step, DWTX_ORDER_RGB, W, H, n, dst != 0, v && v->sample_bytes == 4 ? DWTX_SAMPLE_F32 : -1, true, host_windows, &list, &px))
-		return rc;
-	const long long p = (long long)px.row_pitch, s = (long long)px.step();
-	for (int i = 0; i < n; ++i) {
-		const bool fx = flags[(size_t)i] & DWTX_FLIP_X, fy = flags[(size_t)i] & DWTX_FLIP_Y;
-		if (origin)
-			origin[i] = list.offs[(size_t)i] + (fy ? (long long)(H - 1) * p : 0) + (fx ? (long long)(W - 1) * s : 0);
-		if (pitch)
-			pitch[i] = fy ? -p : p;
-		if (step)
-			step[i] = fx ? -s : s;
+	if (!c.sgn && minval != 0) {
+		dwtx_set_error("%s view: minval %d without sgn (unsigned samples start at 0)", what, minval);
+		return DWTX_ERR_ARG;
+	}
+	if (c.view->channels != c.other->channels) {
+		dwtx_set_error("%s view: the view has %d channels, its %s %d", what, c.view->channels, other, c.other->channels);
+		return DWTX_ERR_ARG;
+	}
+	if (c.view->sample_bytes != c.other->sample_bytes) {
+		dwtx_set_error("%s view: the view has %d-byte samples, its %s %d-byte ones", what, c.view->sample_bytes, other, c.other->sample_bytes);
+		return DWTX_ERR_ARG;
 	}
 	return DWTX_OK;
 }
-
-static int encode_view_flip(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	const void *const *host_windows, int flip, const unsigned char *host_flips,
-	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info, const int *minval)
-{
-	std::vector<unsigned char> flags;
-	bool any;
-	if (const int rc = flip_flags(n, flip, host_flips, &flags, &any))
-		return rc;
-	if (!any)   // the unflipped call, on its own path
-		return host_windows ? encode_view_list(ctx, src, pixel_step, order, fmt, host_windows, W, H, n, capacity, dev_out, out_stride, dev_info, minval)
-		     : fmt          ? encode_view_float(ctx, src, pixel_step, order, fmt, W, H, n, capacity, dev_out, out_stride, dev_info, minval)
-		                    : encode_view_order(ctx, src, pixel_step, order, W, H, n, capacity, dev_out, out_stride, dev_info, minval);
-	if (!ctx || !dev_out || !dev_info)
-		return DWTX_ERR_ARG;
-	int kind = -1;
-	if (fmt)
-		if (const int rc = float_kind(fmt, &kind))
-			return rc;
-	WinList list{ nullptr, {} };
-	dwtx_pixels px;
-	if (const int rc = flipped_view(src, pixel_step, order, W, H, n, false, kind, false, host_windows, &list, &px, minval))
-		return rc;
-	if (fmt) {
-		if (!source_range_ok(src, minval))
-			return DWTX_ERR_ARG;
-		set_float_format(&px, fmt);
-	}
-	// bottom-up windows go through the wide forward kernels like upright ones; a mirrored one sends the call through the general conversion
-	px.flip_wide = true;
-	for (int i = 0; i < n; ++i)
-		px.flip_wide = px.flip_wide && !(flags[(size_t)i] & DWTX_FLIP_X);
-	flip_entries(&list, flags);
-	if (const int rc = send_list(ctx, list, &px))
-		return rc;
-	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx->enc_index);
-}
-
-extern "C" int dwtx_encode_view_flip(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	const void *const *host_windows, int flip, const unsigned char *host_flips,
-	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
-{
-	return encode_view_flip(ctx, src, pixel_step, order, fmt, host_windows, flip, host_flips, W, H, n, capacity, dev_out, out_stride, dev_info, nullptr);
-}
-
-extern "C" int dwtx_encode_view_signed(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	const void *const *host_windows, int flip, const unsigned char *host_flips, int minval,
-	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
-{
-	return encode_view_flip(ctx, src, pixel_step, order, fmt, host_windows, flip, host_flips, W, H, n, capacity, dev_out, out_stride, dev_info, &minval);
-}
-
-static int decode_view_flip(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
-	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, int flip, const unsigned char *host_flips,
-	dwtx_decode_info *host_info, const int *minval)
-{
-	std::vector<unsigned char> flags;
-	bool any;
-	if (const int rc = flip_flags(n, flip, host_flips, &flags, &any))
-		return rc;
-	if (!any)   // the unflipped call, on its own path
-		return host_windows ? decode_view_list(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h,
-		                          host_origins, host_windows, host_info, minval)
-		                    : decode_view_crop(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h,
-		                          host_origins, host_info, minval);
-	if (!ctx || !dev_streams || !dev_lens || !host_info)
-		return DWTX_ERR_ARG;
-	bool whole;
-	if (const int rc = crop_of_call(W, H, n, crop_w, crop_h, host_origins, &whole))
-		return rc;
-	int kind = -1;
-	if (fmt)
-		if (const int rc = float_kind(fmt, &kind))
-			return rc;
-	WinList list{ nullptr, {} };
-	dwtx_pixels px;
-	if (const int rc = flipped_view(dst, pixel_step, order, crop_w, crop_h, n, true, kind, !whole, host_windows, &list, &px, minval))
-		return rc;
-	if (fmt)
-		set_float_format(&px, fmt);
-	px.flip_sink = true;
-	for (int i = 0; i < n; ++i)
-		px.flip_x = px.flip_x || (flags[(size_t)i] & DWTX_FLIP_X);
-	flip_entries(&list, flags);
-	if (const int rc = send_list(ctx, list, &px))
-		return rc;
-	if (whole)
-		return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info);
-	const CropCall crop = { crop_w, crop_h, host_origins };
-	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, px, host_info, &crop);
-}
-
-extern "C" int dwtx_decode_view_flip(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
-	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, int flip, const unsigned char *host_flips,
-	dwtx_decode_info *host_info)
-{
-	return decode_view_flip(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h, host_origins,
-		host_windows, flip, host_flips, host_info, nullptr);
-}
-
-extern "C" int dwtx_decode_view_signed(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
-	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
-	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, int flip, const unsigned char *host_flips, int minval,
-	dwtx_decode_info *host_info)
-{
-	return decode_view_flip(ctx, dev_streams, stream_stride, dev_lens, W, H, n, levels_max, dst, pixel_step, order, fmt, crop_w, crop_h, host_origins,
-		host_windows, flip, host_flips, host_info, &minval);
-}
-
-// ---- delta views (include/dwtx.h): a picture coded as its difference from a base view ------------------------------
 
 // The units of a grid view — its n windows, or the 3n planes of planar RGB, as in list_windows — as byte spans [first, first +
 // (H-1)*row_pitch + row) of the address space, appended to `spans` with `tag`
@@ -1212,197 +847,72 @@ struct DeltaSpan {
 };
 static void delta_spans(const dwtx_pixels &px, int W, int H, int n, int tag, std::vector<DeltaSpan> *spans)
 {
-	const size_t row = px.planar() ? (size_t)W : px.stepped() ? (size_t)(W - 1) * px.pixel_step + px.channels : (size_t)W * px.channels;
-	const size_t span = (size_t)(H - 1) * px.pitch(W) + row;
-	for (int i = 0; i < n; ++i) {
-		const size_t w = px.first + (size_t)i;
-		const size_t off = px.one_band() ? w * px.image_stride : w / (size_t)px.cols * px.band_stride + w % (size_t)px.cols * px.image_stride;
+	const size_t span = (size_t)(H - 1) * px.pitch(W) + px.row_samples(W);
+	for (int i = 0; i < n; ++i)
 		for (int c = 0; c < (px.planar() ? 3 : 1); ++c) {
-			const uintptr_t at = (uintptr_t)px.at(off + (size_t)c * px.channel_stride);
+			const uintptr_t at = (uintptr_t)px.at(px.grid_offset((size_t)i) + (size_t)c * px.channel_stride);
 			spans->push_back(DeltaSpan{ at, at + px.bytes(span), tag, i });
 		}
-	}
 }
 
-// The two views of a delta call -> one dwtx_pixels that carries both (dwtx_pixels::delta), checked: each view as the *_view_order /
-// *_view_signed calls check theirs (pixels_of_view; the base is only ever read, and its maxval is not), the shared sample type,
-// and for a decode that the base is the destination itself — every field that places a sample equal: the in-place decode, each
-// sample read and written by the same lane — or that no unit of the destination meets a unit of the base.  One sort and one
-// sweep: by address, a span that begins before a span of the other view has ended meets it.
-static int delta_view(const dwtx_view *v, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step, int order, int sgn, int minval,
-	int W, int H, int n, bool dst, dwtx_pixels *px)
+// A delta decode whose base is not the destination itself (the in-place decode: each sample read and written by the same lane):
+// no unit of the destination may meet a unit of the base.  One sort and one sweep: by address, a span that begins before a span
+// of the other view has ended meets it.
+static int delta_disjoint(const dwtx_pixels &px, const dwtx_pixels &bp, int W, int H, int n)
 {
-	if (!v || !base) {
-		dwtx_set_error("delta view: no view or no base view");
-		return DWTX_ERR_ARG;
-	}
-	if (sgn != 0 && sgn != 1) {
-		dwtx_set_error("delta view: sgn %d (0: uint8_t / uint16_t samples, 1: int16_t samples)", sgn);
-		return DWTX_ERR_ARG;
-	}
-	if (!sgn && minval != 0) {
-		dwtx_set_error("delta view: minval %d without sgn (unsigned samples start at 0)", minval);
-		return DWTX_ERR_ARG;
-	}
-	if (v->channels != base->channels) {
-		dwtx_set_error("delta view: the view has %d channels, its base %d", v->channels, base->channels);
-		return DWTX_ERR_ARG;
-	}
-	if (v->sample_bytes != base->sample_bytes) {
-		dwtx_set_error("delta view: the view has %d-byte samples, its base %d-byte ones", v->sample_bytes, base->sample_bytes);
-		return DWTX_ERR_ARG;
-	}
-	const int *lower = sgn ? &minval : nullptr;
-	dwtx_pixels bp;
-	if (const int rc = pixels_of_view(v, pixel_step, order, W, H, n, dst, px, -1, false, nullptr, lower))
-		return rc;
-	if (const int rc = pixels_of_view(base, base_pixel_step, order, W, H, n, false, &bp, -1, false, nullptr, lower))
-		return rc;
-	const bool same = px->base == bp.base && px->row_pitch == bp.row_pitch && px->image_stride == bp.image_stride && px->cols == bp.cols &&
-		px->band_stride == bp.band_stride && px->channel_stride == bp.channel_stride && px->pixel_step == bp.pixel_step;
-	if (dst && !same) {
-		std::vector<DeltaSpan> spans;
-		try {
-			spans.reserve(6 * (size_t)n);
-			delta_spans(*px, W, H, n, 0, &spans);
-			delta_spans(bp, W, H, n, 1, &spans);
-		} catch (...) {
-			return DWTX_ERR_NOMEM;
-		}
-		std::sort(spans.begin(), spans.end(), [](const DeltaSpan &a, const DeltaSpan &b) { return a.at < b.at; });
-		uintptr_t end[2] = { 0, 0 };
-		int last[2] = { -1, -1 };
-		for (const DeltaSpan &s : spans) {
-			const int other = 1 - s.tag;
-			if (s.at < end[other]) {
-				const int wd = s.tag ? last[other] : s.window, wb = s.tag ? s.window : last[other];
-				dwtx_set_error("delta view: window %d of the destination meets window %d of the base (neither the same view, which decodes in place, "
-					"nor disjoint spans: a decode that writes what it has yet to read is a chain, not one call)", wd, wb);
-				return DWTX_ERR_ARG;
-			}
-			if (s.end > end[s.tag]) {
-				end[s.tag] = s.end;
-				last[s.tag] = s.window;
-			}
-		}
-	}
-	px->delta.base = bp.base;
-	px->delta.image_stride = bp.image_stride;
-	px->delta.row_pitch = bp.row_pitch;
-	px->delta.band_stride = bp.band_stride;
-	px->delta.first = bp.first;
-	px->delta.channel_stride = bp.channel_stride;
-	px->delta.pixel_step = bp.pixel_step;
-	px->delta.cols = bp.cols;
-	return DWTX_OK;
-}
-
-extern "C" int dwtx_view_delta_check(const dwtx_view *v, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step,
-	int sgn, int minval, int W, int H, int n, int dst)
-{
-	dwtx_pixels px;
-	return delta_view(v, pixel_step, base, base_pixel_step, DWTX_ORDER_RGB, sgn, minval, W, H, n, dst != 0, &px);
-}
-
-extern "C" int dwtx_encode_view_delta(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step,
-	int order, int sgn, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
-{
-	dwtx_pixels px;
-	if (const int rc = delta_view(src, pixel_step, base, base_pixel_step, order, sgn, 0, W, H, n, false, &px))
-		return rc;
-	return encode_device(ctx, px, W, H, n, capacity, dev_out, out_stride, dev_info, ctx ? ctx->enc_index : nullptr);
-}
-
-extern "C" int dwtx_decode_view_delta(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
-	int W, int H, int n, const dwtx_view *dst, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step, int order, int sgn, int minval,
-	dwtx_decode_info *host_info)
-{
-	dwtx_pixels px;
-	if (const int rc = delta_view(dst, pixel_step, base, base_pixel_step, order, sgn, minval, W, H, n, true, &px))
-		return rc;
-	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, -1, px, host_info);
-}
-
-// ---- delta chains (include/dwtx.h): each picture coded against its predecessor, the first against a key -------------------------
-
-static void base_grid_of(const dwtx_pixels &bp, dwtx_base_grid *g)
-{
-	g->base = bp.base;
-	g->image_stride = bp.image_stride;
-	g->row_pitch = bp.row_pitch;
-	g->band_stride = bp.band_stride;
-	g->first = bp.first;
-	g->channel_stride = bp.channel_stride;
-	g->pixel_step = bp.pixel_step;
-	g->cols = bp.cols;
-}
-
-// The view and the key of a chain call -> *px, the view's pixels, and *kp, the key's one window; checked as delta_view checks its
-// two views.  For a decode every unit of the destination (a window; a plane of planar RGB) must be disjoint from every unit of the
-// key: delta_view's spans with one base window, so each destination unit is held against the key's one or three directly, no
-// sort.  Two spans that intersect are still disjoint where both units have the same pitch in bytes and lie in different columns of
-// the lattice of rows that pitch apart (list_windows' rule): a key in the gap between a window's rows and its pitch.
-static int chain_view(const dwtx_view *v, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step, int order, int sgn, int minval,
-	int W, int H, int n, bool dst, dwtx_pixels *px, dwtx_pixels *kp)
-{
-	if (!v) {
-		dwtx_set_error("chain view: no view");
-		return DWTX_ERR_ARG;
-	}
-	if (!key || !key->dev) {
-		dwtx_set_error("chain view: no key (the base of picture 0 is required: a chain without one is a plain call and n - 1 links)");
-		return DWTX_ERR_ARG;
-	}
-	if (sgn != 0 && sgn != 1) {
-		dwtx_set_error("chain view: sgn %d (0: uint8_t / uint16_t samples, 1: int16_t samples)", sgn);
-		return DWTX_ERR_ARG;
-	}
-	if (!sgn && minval != 0) {
-		dwtx_set_error("chain view: minval %d without sgn (unsigned samples start at 0)", minval);
-		return DWTX_ERR_ARG;
-	}
-	if (v->channels != key->channels) {
-		dwtx_set_error("chain view: the view has %d channels, its key %d", v->channels, key->channels);
-		return DWTX_ERR_ARG;
-	}
-	if (v->sample_bytes != key->sample_bytes) {
-		dwtx_set_error("chain view: the view has %d-byte samples, its key %d-byte ones", v->sample_bytes, key->sample_bytes);
-		return DWTX_ERR_ARG;
-	}
-	const int *lower = sgn ? &minval : nullptr;
-	if (const int rc = pixels_of_view(v, pixel_step, order, W, H, n, dst, px, -1, false, nullptr, lower))
-		return rc;
-	dwtx_view one = *key;   // one window: what lies between windows is not the key's to say
-	one.cols = 0;
-	one.image_stride = 0;
-	one.band_stride = 0;
-	if (const int rc = pixels_of_view(&one, key_pixel_step, order, W, H, 1, false, kp, -1, false, nullptr, lower))
-		return rc;
-	if (!dst)
-		return DWTX_OK;
 	std::vector<DeltaSpan> spans;
 	try {
-		spans.reserve(3 * (size_t)n + 3);
-		delta_spans(*kp, W, H, 1, 1, &spans);
-		delta_spans(*px, W, H, n, 0, &spans);
+		spans.reserve(6 * (size_t)n);
+		delta_spans(px, W, H, n, 0, &spans);
+		delta_spans(bp, W, H, n, 1, &spans);
 	} catch (...) {
 		return DWTX_ERR_NOMEM;
 	}
-	const size_t nkey = kp->planar() ? 3 : 1;
-	const uintptr_t pitch = px->bytes(px->pitch(W)), kpitch = kp->bytes(kp->pitch(W));
-	const uintptr_t krow = spans[0].end - spans[0].at - (uintptr_t)(H - 1) * kpitch;   // a unit's row, in bytes
+	std::sort(spans.begin(), spans.end(), [](const DeltaSpan &a, const DeltaSpan &b) { return a.at < b.at; });
+	uintptr_t end[2] = { 0, 0 };
+	int last[2] = { -1, -1 };
+	for (const DeltaSpan &s : spans) {
+		const int other = 1 - s.tag;
+		if (s.at < end[other]) {
+			const int wd = s.tag ? last[other] : s.window, wb = s.tag ? s.window : last[other];
+			dwtx_set_error("delta view: window %d of the destination meets window %d of the base (neither the same view, which decodes in place, "
+				"nor disjoint spans: a decode that writes what it has yet to read is a chain, not one call)", wd, wb);
+			return DWTX_ERR_ARG;
+		}
+		if (s.end > end[s.tag]) {
+			end[s.tag] = s.end;
+			last[s.tag] = s.window;
+		}
+	}
+	return DWTX_OK;
+}
+
+// A chain decode: every unit of the destination (a window; a plane of planar RGB) must be disjoint from every unit of the key:
+// delta_disjoint's spans with one base window, so each destination unit is held against the key's one or three directly, no
+// sort.  Two spans that intersect are still disjoint where both units have the same pitch in bytes and lie in different columns of
+// the lattice of rows that pitch apart (other_columns): a key in the gap between a window's rows and its pitch.
+static int chain_disjoint(const dwtx_pixels &px, const dwtx_pixels &kp, int W, int H, int n)
+{
+	std::vector<DeltaSpan> spans;
+	try {
+		spans.reserve(3 * (size_t)n + 3);
+		delta_spans(kp, W, H, 1, 1, &spans);
+		delta_spans(px, W, H, n, 0, &spans);
+	} catch (...) {
+		return DWTX_ERR_NOMEM;
+	}
+	const size_t nkey = kp.planar() ? 3 : 1;
+	const uintptr_t pitch = px.bytes(px.pitch(W)), kpitch = kp.bytes(kp.pitch(W));
+	const uintptr_t row = px.bytes(px.row_samples(W)), krow = kp.bytes(kp.row_samples(W));
 	for (size_t i = nkey; i < spans.size(); ++i) {
 		const DeltaSpan &d = spans[i];
-		const uintptr_t row = d.end - d.at - (uintptr_t)(H - 1) * pitch;
 		for (size_t k = 0; k < nkey; ++k) {
 			const DeltaSpan &b = spans[k];
 			if (d.end <= b.at || b.end <= d.at)
 				continue;
-			if (pitch == kpitch) {   // the key's columns [dx, dx + krow) on the lattice of the window's rows, which holds [0, row)
-				const uintptr_t dx = b.at >= d.at ? (b.at - d.at) % pitch : (pitch - (d.at - b.at) % pitch) % pitch;
-				if (dx >= row && dx + krow <= pitch)
-					continue;
-			}
+			// (the key's columns on the lattice of the window's rows)
+			if (pitch == kpitch && other_columns(b.at >= d.at ? (b.at - d.at) % pitch : (pitch - (d.at - b.at) % pitch) % pitch, row, krow, pitch))
+				continue;
 			dwtx_set_error("chain view: window %d of the destination meets the key (every unit of the destination must be disjoint from the key's: "
 				"frame 0 of a stack as the key of frames 1.. is the layout to use)", d.window);
 			return DWTX_ERR_ARG;
@@ -1411,49 +921,413 @@ static int chain_view(const dwtx_view *v, size_t pixel_step, const dwtx_view *ke
 	return DWTX_OK;
 }
 
-extern "C" int dwtx_view_chain_check(const dwtx_view *v, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step,
-	int sgn, int minval, int W, int H, int n, int dst)
+// What plan_view makes of a call: all that encode_device / decode_device are told
+struct ViewPlan {
+	dwtx_pixels px;                // the view (offs not set yet: send_list)
+	std::vector<long long> offs;   // the windows' table in host memory: each one's first sample, in samples from px.base, a flipped one's
+	                               // flags on top (dwtx_pixels::flips); empty unless the call is listed or flipped
+	bool cropped = false;          // crop: only that window of every picture is written; else whole pictures
+	CropCall crop;
+	dwtx_pixels key;               // a chain encode: the key's one window
+};
+
+// The one resolver of every view call: host arithmetic only, no context and no device.  It refuses, in this order (DESIGN.md
+// section 4.23): the flags; the crop and its origins; the float format; of a delta or chain pair the missing view, sgn, minval,
+// channels and sample bytes; the view itself (view_pixels), the size of its table and its list (list_windows); a float
+// source's range; the pair's other view and the places where the two meet.  Four calls are, by the header's word, another call
+// with fewer arguments, and become that call here — nowhere else is a neutral argument looked at.
+static int plan_view(const ViewCall &call, ViewPlan *plan)
 {
-	dwtx_pixels px, kp;
-	return chain_view(v, pixel_step, key, key_pixel_step, DWTX_ORDER_RGB, sgn, minval, W, H, n, dst != 0, &px, &kp);
+	ViewCall c = call;
+	dwtx_pixels &px = plan->px;
+	int rc;
+	std::vector<unsigned char> flags;
+	bool flipped = false;
+	if (c.flip || c.host_flips || c.table) {
+		// no window flipped: "the list / plain call, and takes its path" — `flipped` stays false, and a grid stays a grid
+		if ((rc = flip_flags(c, &flags, &flipped)))
+			return rc;
+		flipped = flipped || c.table;
+	}
+	if (c.crop) {
+		bool whole;
+		if ((rc = crop_of_call(c, &whole)))
+			return rc;
+		// the whole picture at (0, 0): "the call without a crop"
+		c.crop = !whole;
+	}
+	int kind = -1;
+	if (c.fmt || c.needs_fmt) {
+		if ((rc = float_kind(c.fmt, &kind)))
+			return rc;
+	} else if (c.kind_from_bytes && c.view && c.view->sample_bytes == 4)
+		kind = DWTX_SAMPLE_F32;
+	// float samples with minval == 0: "the unsigned call's"
+	if (kind >= 0 && c.minval && *c.minval == 0)
+		c.minval = nullptr;
+	if (c.pair == PAIR_DELTA) {
+		if (!c.view || !c.other) {
+			dwtx_set_error("delta view: no view or no base view");
+			return DWTX_ERR_ARG;
+		}
+		if ((rc = pair_refusals(c, "delta", "base")))
+			return rc;
+	} else if (c.pair == PAIR_CHAIN) {
+		if (!c.view) {
+			dwtx_set_error("chain view: no view");
+			return DWTX_ERR_ARG;
+		}
+		if (!c.other || !c.other->dev) {
+			dwtx_set_error("chain view: no key (the base of picture 0 is required: a chain without one is a plain call and n - 1 links)");
+			return DWTX_ERR_ARG;
+		}
+		if ((rc = pair_refusals(c, "chain", "key")))
+			return rc;
+	}
+	if (c.pair && !c.sgn)
+		c.minval = nullptr;
+	if ((rc = view_pixels(c, kind, &px)))
+		return rc;
+	if ((c.windows || flipped) && !table_count_ok(c, px.channels))
+		return DWTX_ERR_ARG;
+	if (c.windows && (rc = list_windows(c, &plan->offs, &px)))
+		return rc;
+	if (c.fmt) {
+		// the quantiser's clamp of a float source: maxval alone, or the range of a signed call with a lower bound other than 0
+		if (!c.dst && !(c.minval ? dwtx_range_ok(*c.minval, c.view->maxval) : dwtx_maxval_ok(c.view->maxval)))
+			return DWTX_ERR_ARG;
+		for (int k = 0; k < 3; ++k) {
+			px.scale[k] = c.fmt->scale[k];
+			px.bias[k] = c.fmt->bias[k];
+		}
+	}
+	if (c.pair) {
+		// The other view, checked as the *_view_order / *_view_signed calls check theirs: it is only ever read, and its maxval is not.
+		// A key is one window: what lies between windows is not the key's to say.
+		ViewCall o = c;
+		dwtx_view one = *c.other;
+		if (c.pair == PAIR_CHAIN) {
+			one.cols = 0;
+			one.image_stride = one.band_stride = 0;
+			o.n = 1;
+		}
+		o.view = &one;
+		o.pixel_step = c.other_step;
+		o.dst = false;
+		dwtx_pixels op;
+		if ((rc = view_pixels(o, kind, &op)))
+			return rc;
+		const int W = c.win_w(), H = c.win_h();
+		if (c.pair == PAIR_DELTA) {
+			if (c.dst && !(px.grid() == op.grid()) && (rc = delta_disjoint(px, op, W, H, c.n)))
+				return rc;
+			px.delta = op.grid();
+		} else {
+			if (c.dst && (rc = chain_disjoint(px, op, W, H, c.n)))
+				return rc;
+			if (!c.dst)
+				plan->key = op;   // (two delta encodes: encode_views)
+			else if (c.n == 1)
+				px.delta = op.grid();   // one link: "dwtx_decode_view_delta with base = key", the fused sinks where the pair qualifies
+			else {
+				px.chain = true;
+				px.key = op.grid();
+			}
+		}
+	}
+	if (flipped) {
+		// Every flipped call travels as a listed one: a grid is spelled out, its table from the view's own strides
+		if (!c.windows) {
+			try {
+				plan->offs.resize((size_t)c.n);
+			} catch (...) {
+				return DWTX_ERR_NOMEM;
+			}
+			px.offs_on_quad = true;   // (what wide() asks of a list: every window's own first sample on the quad)
+			for (size_t i = 0; i < (size_t)c.n; ++i) {
+				plan->offs[i] = (long long)px.grid_offset(i);
+				px.offs_on_quad = px.offs_on_quad && plan->offs[i] % 4 == 0;
+			}
+			px.cols = 0;
+			px.band_stride = px.image_stride = 0;
+		}
+		px.flips = true;
+		px.flip_w = c.win_w();
+		px.flip_h = c.win_h();
+		// a source: bottom-up windows go through the wide forward kernels like upright ones, a mirrored one sends the call through the
+		// general conversion; a destination: the FL instances of the wide inverse kernels, which ask whether any window is mirrored
+		bool mirrored = false;
+		for (size_t i = 0; i < (size_t)c.n; ++i) {
+			mirrored = mirrored || (flags[i] & DWTX_FLIP_X);
+			// the flags into the top bits of the windows' table entries (offsets are sample counts of one allocation, far below)
+			plan->offs[i] = (long long)((unsigned long long)plan->offs[i] | (unsigned long long)flags[i] << DWTX_FLIP_SHIFT);
+		}
+		px.flip_wide = !c.dst && !mirrored;
+		px.flip_sink = c.dst;
+		px.flip_x = c.dst && mirrored;
+	}
+	plan->cropped = c.crop;
+	plan->crop = CropCall{ c.crop_w, c.crop_h, c.host_origins };
+	return DWTX_OK;
 }
 
-// Stream 0 is window 0 minus the key, stream i window i minus window i - 1: two delta encodes, the second `src[1:]` against
-// `src[:-1]` — the streams, the records and the encode index land at entry i for stream i.
-extern "C" int dwtx_encode_view_chain(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step,
-	int order, int sgn, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+// A view call's pixels (device) -> streams (device): resolve, check the call's own pointers, send the table if there is one, encode
+static int encode_views(dwtx_ctx *ctx, const ViewCall &call, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
 {
-	dwtx_pixels px, kp;
-	if (const int rc = chain_view(src, pixel_step, key, key_pixel_step, order, sgn, 0, W, H, n, false, &px, &kp))
+	ViewPlan plan;
+	if (const int rc = plan_view(call, &plan))
 		return rc;
 	if (!ctx || !dev_out || !dev_info)
 		return DWTX_ERR_ARG;
+	if (!plan.offs.empty())
+		if (const int rc = send_list(ctx, plan.offs, &plan.px))
+			return rc;
 	dwtx_index *index = ctx->enc_index;
-	dwtx_pixels head = px;
-	base_grid_of(kp, &head.delta);
-	if (const int rc = encode_device(ctx, head, W, H, 1, capacity, dev_out, out_stride, dev_info, index))
+	if (call.pair != PAIR_CHAIN)
+		return encode_device(ctx, plan.px, call.W, call.H, call.n, capacity, dev_out, out_stride, dev_info, index);
+	// A chain: stream 0 is window 0 minus the key, stream i window i minus window i - 1: two delta encodes, the second `src[1:]`
+	// against `src[:-1]` — the streams, the records and the encode index land at entry i for stream i.
+	dwtx_pixels head = plan.px;
+	head.delta = plan.key.grid();
+	if (const int rc = encode_device(ctx, head, call.W, call.H, 1, capacity, dev_out, out_stride, dev_info, index))
 		return rc;
-	if (n == 1)
+	if (call.n == 1)
 		return DWTX_OK;
-	dwtx_pixels tail = px.image(1);   // (px has no base yet: only the view moves, and its base is the view from window 0 on)
-	base_grid_of(px, &tail.delta);
-	return encode_device(ctx, tail, W, H, n - 1, capacity, dev_out + out_stride, out_stride, dev_info + 1, index ? index + 1 : nullptr);
+	dwtx_pixels tail = plan.px.image(1);   // (the view has no base yet: only the view moves, and its base is the view from window 0 on)
+	tail.delta = plan.px.grid();
+	return encode_device(ctx, tail, call.W, call.H, call.n - 1, capacity, dev_out + out_stride, out_stride, dev_info + 1, index ? index + 1 : nullptr);
+}
+
+// streams (device) -> a view call's pixels (device): the same steps
+static int decode_views(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens, const ViewCall &call,
+	dwtx_decode_info *host_info)
+{
+	ViewPlan plan;
+	if (const int rc = plan_view(call, &plan))
+		return rc;
+	if (!ctx || !dev_streams || !dev_lens || !host_info)
+		return DWTX_ERR_ARG;
+	if (!plan.offs.empty())
+		if (const int rc = send_list(ctx, plan.offs, &plan.px))
+			return rc;
+	return decode_device(ctx, dev_streams, stream_stride, dev_lens, call.W, call.H, call.n, call.levels_max, plan.px, host_info,
+		plan.cropped ? &plan.crop : nullptr);
+}
+
+// The entry points (include/dwtx.h): each names the fields that its ABI has, and nothing else
+
+extern "C" int dwtx_encode_view(dwtx_ctx *ctx, const dwtx_view *src, int W, int H, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	const ViewCall c = { .view = src, .W = W, .H = H, .n = n };
+	return encode_views(ctx, c, capacity, dev_out, out_stride, dev_info);
+}
+
+extern "C" int dwtx_encode_view_step(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int W, int H, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	const ViewCall c = { .view = src, .pixel_step = pixel_step, .W = W, .H = H, .n = n };
+	return encode_views(ctx, c, capacity, dev_out, out_stride, dev_info);
+}
+
+extern "C" int dwtx_encode_view_order(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, int W, int H, int n, long capacity,
+	uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	const ViewCall c = { .view = src, .pixel_step = pixel_step, .order = order, .W = W, .H = H, .n = n };
+	return encode_views(ctx, c, capacity, dev_out, out_stride, dev_info);
+}
+
+// The source's maxval is the quantiser's clamp (the one encode that reads it): up to 255 the picture is one of bytes and takes
+// their route, beyond it a deep picture's (dwtx_pixels::deep_source()); the streams are those of dwtx_encode_device /
+// dwtx_encode_device16 on the quantised picture either way.
+extern "C" int dwtx_encode_view_float(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	const ViewCall c = { .view = src, .pixel_step = pixel_step, .order = order, .fmt = fmt, .W = W, .H = H, .n = n, .needs_fmt = true };
+	return encode_views(ctx, c, capacity, dev_out, out_stride, dev_info);
+}
+
+extern "C" int dwtx_encode_view_list(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	const void *const *host_windows, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	const ViewCall c = { .view = src, .pixel_step = pixel_step, .order = order, .fmt = fmt, .windows = host_windows, .W = W, .H = H, .n = n,
+		.needs_windows = true };
+	return encode_views(ctx, c, capacity, dev_out, out_stride, dev_info);
+}
+
+extern "C" int dwtx_encode_view_flip(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	const void *const *host_windows, int flip, const unsigned char *host_flips,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	const ViewCall c = { .view = src, .pixel_step = pixel_step, .order = order, .fmt = fmt, .windows = host_windows, .flip = flip,
+		.host_flips = host_flips, .W = W, .H = H, .n = n };
+	return encode_views(ctx, c, capacity, dev_out, out_stride, dev_info);
+}
+
+extern "C" int dwtx_encode_view_signed(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	const void *const *host_windows, int flip, const unsigned char *host_flips, int minval,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	const ViewCall c = { .view = src, .pixel_step = pixel_step, .order = order, .fmt = fmt, .windows = host_windows, .flip = flip,
+		.host_flips = host_flips, .minval = &minval, .W = W, .H = H, .n = n };
+	return encode_views(ctx, c, capacity, dev_out, out_stride, dev_info);
+}
+
+extern "C" int dwtx_encode_view_delta(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step,
+	int order, int sgn, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	const int minval = 0;   // (a source is only read: its range is its samples')
+	const ViewCall c = { .view = src, .pixel_step = pixel_step, .order = order, .minval = &minval, .pair = PAIR_DELTA, .other = base,
+		.other_step = base_pixel_step, .sgn = sgn, .W = W, .H = H, .n = n };
+	return encode_views(ctx, c, capacity, dev_out, out_stride, dev_info);
+}
+
+extern "C" int dwtx_encode_view_chain(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step,
+	int order, int sgn, int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	const int minval = 0;   // (a source is only read: its range is its samples')
+	const ViewCall c = { .view = src, .pixel_step = pixel_step, .order = order, .minval = &minval, .pair = PAIR_CHAIN, .other = key,
+		.other_step = key_pixel_step, .sgn = sgn, .W = W, .H = H, .n = n };
+	return encode_views(ctx, c, capacity, dev_out, out_stride, dev_info);
+}
+
+extern "C" int dwtx_decode_view(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, dwtx_decode_info *host_info)
+{
+	const ViewCall c = { .view = dst, .levels_max = levels_max, .W = W, .H = H, .n = n, .dst = true };
+	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
+}
+
+extern "C" int dwtx_decode_view_step(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, dwtx_decode_info *host_info)
+{
+	const ViewCall c = { .view = dst, .pixel_step = pixel_step, .levels_max = levels_max, .W = W, .H = H, .n = n, .dst = true };
+	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
+}
+
+extern "C" int dwtx_decode_view_order(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
+	dwtx_decode_info *host_info)
+{
+	const ViewCall c = { .view = dst, .pixel_step = pixel_step, .order = order, .levels_max = levels_max, .W = W, .H = H, .n = n, .dst = true };
+	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
+}
+
+extern "C" int dwtx_decode_view_float(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
+	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order,
+	const dwtx_float_format *fmt, dwtx_decode_info *host_info)
+{
+	const ViewCall c = { .view = dst, .pixel_step = pixel_step, .order = order, .fmt = fmt, .levels_max = levels_max, .W = W, .H = H, .n = n,
+		.dst = true, .needs_fmt = true };
+	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
+}
+
+extern "C" int dwtx_decode_view_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, dwtx_decode_info *host_info)
+{
+	const ViewCall c = { .view = dst, .pixel_step = pixel_step, .order = order, .fmt = fmt, .crop = true, .crop_w = crop_w, .crop_h = crop_h,
+		.host_origins = host_origins, .levels_max = levels_max, .W = W, .H = H, .n = n, .dst = true };
+	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
+}
+
+extern "C" int dwtx_decode_view_list(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, dwtx_decode_info *host_info)
+{
+	const ViewCall c = { .view = dst, .pixel_step = pixel_step, .order = order, .fmt = fmt, .windows = host_windows, .crop = true, .crop_w = crop_w,
+		.crop_h = crop_h, .host_origins = host_origins, .levels_max = levels_max, .W = W, .H = H, .n = n, .dst = true, .needs_windows = true };
+	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
+}
+
+extern "C" int dwtx_decode_view_flip(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, int flip, const unsigned char *host_flips,
+	dwtx_decode_info *host_info)
+{
+	const ViewCall c = { .view = dst, .pixel_step = pixel_step, .order = order, .fmt = fmt, .windows = host_windows, .flip = flip,
+		.host_flips = host_flips, .crop = true, .crop_w = crop_w, .crop_h = crop_h, .host_origins = host_origins, .levels_max = levels_max,
+		.W = W, .H = H, .n = n, .dst = true };
+	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
+}
+
+extern "C" int dwtx_decode_view_signed(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, int levels_max, const dwtx_view *dst, size_t pixel_step, int order, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, void *const *host_windows, int flip, const unsigned char *host_flips, int minval,
+	dwtx_decode_info *host_info)
+{
+	const ViewCall c = { .view = dst, .pixel_step = pixel_step, .order = order, .fmt = fmt, .windows = host_windows, .flip = flip,
+		.host_flips = host_flips, .minval = &minval, .crop = true, .crop_w = crop_w, .crop_h = crop_h, .host_origins = host_origins,
+		.levels_max = levels_max, .W = W, .H = H, .n = n, .dst = true };
+	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
+}
+
+extern "C" int dwtx_decode_view_delta(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, const dwtx_view *dst, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step, int order, int sgn, int minval,
+	dwtx_decode_info *host_info)
+{
+	const ViewCall c = { .view = dst, .pixel_step = pixel_step, .order = order, .minval = &minval, .pair = PAIR_DELTA, .other = base,
+		.other_step = base_pixel_step, .sgn = sgn, .W = W, .H = H, .n = n, .dst = true };
+	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
 }
 
 extern "C" int dwtx_decode_view_chain(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
 	int W, int H, int n, const dwtx_view *dst, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step, int order, int sgn, int minval,
 	dwtx_decode_info *host_info)
 {
-	dwtx_pixels px, kp;
-	if (const int rc = chain_view(dst, pixel_step, key, key_pixel_step, order, sgn, minval, W, H, n, true, &px, &kp))
+	const ViewCall c = { .view = dst, .pixel_step = pixel_step, .order = order, .minval = &minval, .pair = PAIR_CHAIN, .other = key,
+		.other_step = key_pixel_step, .sgn = sgn, .W = W, .H = H, .n = n, .dst = true };
+	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
+}
+
+// The host-only exports: the resolver's verdict, and for the flip plan its table read back
+
+extern "C" int dwtx_view_list_check(const dwtx_view *v, size_t pixel_step, int W, int H, int n, const void *const *host_windows, int dst)
+{
+	const ViewCall c = { .view = v, .pixel_step = pixel_step, .order = DWTX_ORDER_RGB, .windows = host_windows, .W = W, .H = H, .n = n, .dst = dst != 0,
+		.needs_windows = true, .kind_from_bytes = true, .thin = true };
+	ViewPlan plan;
+	return plan_view(c, &plan);
+}
+
+extern "C" int dwtx_view_flip_plan(const dwtx_view *v, size_t pixel_step, int W, int H, int n, const void *const *host_windows,
+	int flip, const unsigned char *host_flips, int dst, long long *origin, long long *pitch, long long *step)
+{
+	const ViewCall c = { .view = v, .pixel_step = pixel_step, .order = DWTX_ORDER_RGB, .windows = host_windows, .flip = flip, .host_flips = host_flips,
+		.W = W, .H = H, .n = n, .dst = dst != 0, .kind_from_bytes = true, .thin = true, .table = true };
+	ViewPlan plan;
+	if (const int rc = plan_view(c, &plan))
 		return rc;
-	if (n == 1)   // one link is dwtx_decode_view_delta with base = key, and takes its path (the fused sinks where the pair qualifies)
-		base_grid_of(kp, &px.delta);
-	else {
-		px.chain = true;
-		base_grid_of(kp, &px.key);
+	const long long p = (long long)plan.px.row_pitch, s = (long long)plan.px.step();
+	for (int i = 0; i < n; ++i) {
+		const unsigned long long entry = (unsigned long long)plan.offs[(size_t)i], flags = entry >> DWTX_FLIP_SHIFT;
+		const bool fx = flags & DWTX_FLIP_X, fy = flags & DWTX_FLIP_Y;
+		if (origin)
+			origin[i] = (long long)(entry & ((1ull << DWTX_FLIP_SHIFT) - 1)) + (fy ? (long long)(H - 1) * p : 0) + (fx ? (long long)(W - 1) * s : 0);
+		if (pitch)
+			pitch[i] = fy ? -p : p;
+		if (step)
+			step[i] = fx ? -s : s;
 	}
-	return decode_device(ctx, dev_streams, stream_stride, dev_lens, W, H, n, -1, px, host_info);
+	return DWTX_OK;
+}
+
+extern "C" int dwtx_view_delta_check(const dwtx_view *v, size_t pixel_step, const dwtx_view *base, size_t base_pixel_step,
+	int sgn, int minval, int W, int H, int n, int dst)
+{
+	const ViewCall c = { .view = v, .pixel_step = pixel_step, .order = DWTX_ORDER_RGB, .minval = &minval, .pair = PAIR_DELTA, .other = base,
+		.other_step = base_pixel_step, .sgn = sgn, .W = W, .H = H, .n = n, .dst = dst != 0 };
+	ViewPlan plan;
+	return plan_view(c, &plan);
+}
+
+extern "C" int dwtx_view_chain_check(const dwtx_view *v, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step,
+	int sgn, int minval, int W, int H, int n, int dst)
+{
+	const ViewCall c = { .view = v, .pixel_step = pixel_step, .order = DWTX_ORDER_RGB, .minval = &minval, .pair = PAIR_CHAIN, .other = key,
+		.other_step = key_pixel_step, .sgn = sgn, .W = W, .H = H, .n = n, .dst = dst != 0 };
+	ViewPlan plan;
+	return plan_view(c, &plan);
 }
 
 // one axis of dwtx_tile_groups: `full` tiles of `tile`, then one of `last` (0: none)

@@ -229,6 +229,12 @@ struct dwtx_base_grid {
 	void *base = nullptr;
 	size_t image_stride = 0, row_pitch = 0, band_stride = 0, first = 0, channel_stride = 0, pixel_step = 0;
 	int cols = 0;
+	// the same windows: every field that places a sample is equal
+	bool operator==(const dwtx_base_grid &o) const
+	{
+		return base == o.base && image_stride == o.image_stride && row_pitch == o.row_pitch && band_stride == o.band_stride && first == o.first &&
+			channel_stride == o.channel_stride && pixel_step == o.pixel_step && cols == o.cols;
+	}
 };
 struct dwtx_pixels {
 	void *base;            // the grid's window 0, first sample
@@ -266,18 +272,25 @@ struct dwtx_pixels {
 	dwtx_base_grid key;
 
 	bool is_delta() const { return delta.base != nullptr || chain; }
+	// where the view's own windows lie, and the same samples on another grid: the one place that knows which fields are the layout
+	dwtx_base_grid grid() const { return dwtx_base_grid{ base, image_stride, row_pitch, band_stride, first, channel_stride, pixel_step, cols }; }
+	dwtx_pixels with_grid(const dwtx_base_grid &g) const
+	{
+		dwtx_pixels p = *this;
+		p.base = g.base;
+		p.image_stride = g.image_stride;
+		p.row_pitch = g.row_pitch;
+		p.band_stride = g.band_stride;
+		p.first = g.first;
+		p.channel_stride = g.channel_stride;
+		p.pixel_step = g.pixel_step;
+		p.cols = g.cols;
+		return p;
+	}
 	// the key of a chain as a view of its own, one window
 	dwtx_pixels key_pixels() const
 	{
-		dwtx_pixels p = *this;
-		p.base = key.base;
-		p.image_stride = 0;
-		p.row_pitch = key.row_pitch;
-		p.band_stride = 0;
-		p.first = 0;
-		p.channel_stride = key.channel_stride;
-		p.pixel_step = key.pixel_step;
-		p.cols = 0;
+		dwtx_pixels p = with_grid(key);
 		p.chain = false;
 		p.key = dwtx_base_grid();
 		return p;
@@ -285,15 +298,7 @@ struct dwtx_pixels {
 	// the base pictures as a view of their own: the samples, the channels and their order are this view's
 	dwtx_pixels base_pixels() const
 	{
-		dwtx_pixels p = *this;
-		p.base = delta.base;
-		p.image_stride = delta.image_stride;
-		p.row_pitch = delta.row_pitch;
-		p.band_stride = delta.band_stride;
-		p.first = delta.first;
-		p.channel_stride = delta.channel_stride;
-		p.pixel_step = delta.pixel_step;
-		p.cols = delta.cols;
+		dwtx_pixels p = with_grid(delta);
 		p.delta = dwtx_base_grid();
 		return p;
 	}
@@ -332,6 +337,14 @@ struct dwtx_pixels {
 	// 8-bit RGB in 4-byte pixels (RGBA / RGBX surfaces): the one stepped layout lift.hip's wide kernels take
 	bool rgbx8() const { return pixel_step == 4 && channels == 3 && sample_bytes == 1 && !planar(); }
 	size_t pitch(int W) const { return row_pitch ? row_pitch : (size_t)W * (planar() ? 1 : channels); }
+	// a row of a W-wide window (planar: of one of its planes), from its first sample to behind its last
+	size_t row_samples(int W) const { return planar() ? (size_t)W : stepped() ? (size_t)(W - 1) * pixel_step + channels : (size_t)W * channels; }
+	// where window i of a grid view starts, in samples from base
+	size_t grid_offset(size_t i) const
+	{
+		const size_t w = first + i;
+		return cols ? w / (size_t)cols * band_stride + w % (size_t)cols * image_stride : w * image_stride;
+	}
 	// the same pictures from image i on: a one-band view moves its base (first stays 0), a grid or a list keeps its origin and moves the index
 	dwtx_pixels image(size_t i) const
 	{
