@@ -218,6 +218,24 @@ def view_chain_check(fields, key_fields, pointer, key_pointer, sample_bytes=1, k
     return rc, (lib.dwtx_last_error().decode(errors="replace") if rc else "")
 
 
+def view_clips_check(fields, pointer, period, sample_bytes=1, signed=False, minval=0, maxval=None, dst=True):
+    """dwtx_view_clips_check: what encode_view_clips (dst=False) and decode_view_clips (dst=True) say to a grid view whose every
+    period-th window is a key -> (rc, text): (0, "") for a view they take, else the error code and the text of the refusal, which
+    starts "clips view:".  fields: the view_fields dict of the view (None: a NULL view); pointer: its first sample's address as a
+    plain integer, never dereferenced.  Host arithmetic only: needs no device."""
+    lib = _lib.load()
+    if maxval is None:
+        maxval = 255 if sample_bytes == 1 else 32767 if signed else 65535
+    if fields is None:
+        rc = lib.dwtx_view_clips_check(None, 0, int(period), 1 if signed else 0, int(minval), 8, 8, 1, 1 if dst else 0)
+    else:
+        v = View(pointer or None, sample_bytes, fields["channels"], maxval, fields["cols"], fields["row_pitch"], fields["image_stride"],
+                 fields["band_stride"], fields["channel_stride"])
+        rc = lib.dwtx_view_clips_check(C.byref(v), fields["pixel_step"], int(period), 1 if signed else 0, int(minval), fields["W"], fields["H"],
+                                       fields["n"], 1 if dst else 0)
+    return rc, (lib.dwtx_last_error().decode(errors="replace") if rc else "")
+
+
 FLIPS = {"": 0, "x": 1, "y": 2, "xy": 3, "yx": 3}   # enum DWTX_FLIP_X = 1, DWTX_FLIP_Y = 2 (include/dwtx.h): a mask
 
 
@@ -761,13 +779,14 @@ class Context:
         vb, _, _, _, _, bstep = self._view(base, None, stepped, signed=signed)
         return v, vb, W, H, Cn, n, step, bstep
 
-    def _encode_views(self, v, step, order, fmt, windows, flips, lo, W, H, n, capacity, out, info, pair=None):
+    def _encode_views(self, v, step, order, fmt, windows, flips, lo, W, H, n, capacity, out, info, pair=None, clips=None):
         """Every view encode: allocates `out` and `info` where the caller brought none — slots of dwtx_encode_bound, or of
         dwtx_encode_bound16 for deep, signed and delta pictures — and makes the call through the narrowest entry point that has
         the arguments given.  step: None without the `stepped` keyword; fmt, windows (a ctypes array), flips (view_flips) and lo
-        (the signed calls' minval): None for a call without them; pair: (symbol, other view, its step, sgn) of a delta or chain."""
+        (the signed calls' minval): None for a call without them; pair: (symbol, other view, its step, sgn) of a delta or chain;
+        clips: (period, sgn) of a clips call, which has no other view."""
         torch = self.torch
-        deep = pair is not None or ((v.maxval > 255 or lo is not None) if fmt is not None else v.sample_bytes == 2)
+        deep = pair is not None or clips is not None or ((v.maxval > 255 or lo is not None) if fmt is not None else v.sample_bytes == 2)
         bound = self.lib.dwtx_encode_bound16 if deep else self.lib.dwtx_encode_bound
         stride = bound(W, H, v.channels) if capacity <= 0 else (capacity + 15) // 8 * 8
         if out is None:
@@ -776,7 +795,9 @@ class Context:
             info = torch.empty((n, C.sizeof(StreamInfo)), dtype=torch.uint8, device=self.device)
         view = (self.h, C.byref(v), step or 0, order)
         pf = C.byref(fmt) if fmt is not None else None
-        if pair is not None:
+        if clips is not None:
+            sym, args = "dwtx_encode_view_clips", view[:3] + (clips[0], order, clips[1])
+        elif pair is not None:
             sym, args = pair[0], view[:3] + (C.byref(pair[1]), pair[2], order, pair[3])
         elif lo is not None:
             fl = flips or (0, None)
@@ -796,9 +817,10 @@ class Context:
         _check(getattr(self.lib, sym)(*args, W, H, n, capacity, _ptr(out), out.shape[1], _ptr(info)), sym)
         return out, info
 
-    def _decode_views(self, streams, lens, v, step, order, fmt, crop, windows, flips, lo, W, H, n, levels_max, pair=None):
+    def _decode_views(self, streams, lens, v, step, order, fmt, crop, windows, flips, lo, W, H, n, levels_max, pair=None, clips=None):
         """Every view decode, through the narrowest entry point that has the arguments given -> the list of DecodeInfo.  crop: None,
-        or (cw, ch, origins as a ctypes array or None); pair: (symbol, other view, its step, sgn, minval); the rest as for
+        or (cw, ch, origins as a ctypes array or None); pair: (symbol, other view, its step, sgn, minval); clips: (period, sgn,
+        minval); the rest as for
         _encode_views."""
         torch = self.torch
         assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.shape[0] == n and streams.shape[1] % 8 == 0
@@ -808,7 +830,9 @@ class Context:
         view = (levels_max, C.byref(v), step or 0, order)
         pf = C.byref(fmt) if fmt is not None else None
         window = (pf,) + (crop or (W, H, None))
-        if pair is not None:
+        if clips is not None:
+            sym, args = "dwtx_decode_view_clips", view[1:3] + (clips[0], order, clips[1], clips[2])
+        elif pair is not None:
             sym, args = pair[0], view[1:3] + (C.byref(pair[1]), pair[2], order, pair[3], pair[4])
         elif lo is not None:
             fl = flips or (0, None)
@@ -968,6 +992,54 @@ class Context:
         v, vk, W, H, Cn, n, step, kstep = self._chain_views(into, key, maxval, stepped, signed, unsupported)
         return self._decode_views(streams, lens, v, step, order, None, None, None, None, None, W, H, n, -1,
                                   pair=("dwtx_decode_view_chain", vk, kstep, 1 if signed else 0, lo if signed else 0))
+
+    # -- clips: chains with their keys inside the stack, many per call (dwtx_*_view_clips) ---------------------------------------
+
+    _NOT_IN_CLIPS = {"flip": "the clips calls take no flips", "levels_max": "the clips calls write whole pictures only",
+                     "crop": "the clips calls take no crops", "origins": "the clips calls take no crops", "base": "a link's base is the picture "
+                     "before it, inside the stack", "key": "the keys lie inside the stack: a key outside it is encode_view_chain / decode_view_chain",
+                     "scale": "the clips calls take integer samples", "bias": "the clips calls take integer samples",
+                     "windows": "the clips calls take no window lists"}
+
+    def _clips_view(self, t, period, maxval, stepped, signed, unsupported):
+        """The tensor of a clips call -> its view and period, or a ValueError before any device call: the keywords of the other
+        view calls that a clip stack does not take, lists, float tensors and a period that is no integer from 1 up."""
+        torch = self.torch
+        for k in unsupported:
+            raise ValueError(f"a clips call does not take {k}= ({self._NOT_IN_CLIPS.get(k, 'no view call has that keyword')})")
+        if isinstance(t, (list, tuple)):
+            raise ValueError("a clips call takes one grid view, not a list of windows")
+        if not hasattr(t, "dtype") or t.dtype in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
+            raise ValueError(f"a clips call takes integer tensors: the tensor holds {getattr(t, 'dtype', type(t))}")
+        if isinstance(period, bool) or not hasattr(period, "__index__") or int(period) < 1:
+            raise ValueError(f"period is the distance between keys, an integer from 1 up (n or more: one clip), not {period!r}")
+        return self._view(t, maxval, stepped, signed=signed) + (int(period),)
+
+    def encode_view_clips(self, t, period, capacity=0, out=None, info=None, stepped=False, order="rgb", signed=False, **unsupported):
+        """dwtx_encode_view_clips: the windows of `t` (any integer tensor encode_view takes) as a stack of clips: window i with
+        i % period == 0 is a key and gets the stream encode_view gives it — an ordinary stream that any reader shows —, every other
+        window a link with the stream of encode_view(t[i:i+1], base=t[i-1:i]) -> (streams, info); async, one pass for all n.
+        period >= n: one clip with its key at window 0; period == 1: every picture a key; the last clip may be short.  The streams'
+        slots are dwtx_encode_bound16's.  Not with flip, levels_max, crops, float tensors, lists or a key outside the stack
+        (encode_view_chain): ValueError."""
+        order = view_order(order)
+        v, W, H, Cn, n, step, period = self._clips_view(t, period, None, stepped, signed, unsupported)
+        return self._encode_views(v, step, order, None, None, None, None, W, H, n, capacity, out, info,
+                                  clips=(period, 1 if signed else 0))
+
+    def decode_view_clips(self, streams, lens, into, period, maxval=None, stepped=False, order="rgb", signed=False, minval=None, **unsupported):
+        """dwtx_decode_view_clips: device streams [n,stride] + int64 lens of a stack of clips (encode_view_clips) -> the windows
+        of `into`, as walking them in order gives: a key (window i, i % period == 0) whose stream is readable and supports the
+        whole picture receives what decode_view of that stream alone writes, clamps for [minval, maxval] included — one that is
+        not stays as it is, a key cut before its finest level too: nothing is written into its corner —, a link what
+        decode_view(..., base=window i-1 as it lies in memory) gives; an unreadable or cut link leaves its window, and the next
+        link takes what lies there.  Returns the list of DecodeInfo; syncs once.  Not with flip, levels_max, crops, float
+        tensors, lists or a key outside the stack (decode_view_chain): ValueError."""
+        order = view_order(order)
+        lo, maxval = self._signed_range(signed, minval, maxval)
+        v, W, H, Cn, n, step, period = self._clips_view(into, period, maxval, stepped, signed, unsupported)
+        return self._decode_views(streams, lens, v, step, order, None, None, None, None, None, W, H, n, -1,
+                                  clips=(period, 1 if signed else 0, lo if signed else 0))
 
     def decode_view_float(self, streams, lens, into, maxval=255, scale=1.0, bias=0.0, levels_max=-1, stepped=False, order="rgb", flip=None,
                           minval=0):

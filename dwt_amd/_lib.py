@@ -181,6 +181,10 @@ SYMBOLS = {
     "dwtx_encode_view_chain": (_i, [_vp, C.POINTER(View), _sz, C.POINTER(View), _sz, _i, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
     "dwtx_decode_view_chain": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, C.POINTER(View), _sz, C.POINTER(View), _sz, _i, _i, _i, _vp]),
     "dwtx_view_chain_check": (_i, [C.POINTER(View), _sz, C.POINTER(View), _sz, _i, _i, _i, _i, _i, _i]),
+    # clips: one view, every period-th window of it a key
+    "dwtx_encode_view_clips": (_i, [_vp, C.POINTER(View), _sz, _i, _i, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
+    "dwtx_decode_view_clips": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, C.POINTER(View), _sz, _i, _i, _i, _i, _vp]),
+    "dwtx_view_clips_check": (_i, [C.POINTER(View), _sz, _i, _i, _i, _i, _i, _i, _i]),
     "dwtx_tile_groups": (_i, [_i, _i, _i, C.POINTER(TileGroup)]),
     "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }

@@ -403,6 +403,16 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 				return r;
 			return dwtx_planes_to_pixels_chain(ctx, px, img, W, H, first, count);
 		}
+		if (px.clips) {
+			// A clip stack (dwtx_decode_view_clips): the chain's route and the chain's ordering argument, word for word — the group's
+			// pictures (a key's own, a link's residual) through the int32 transform into planes, then ONE launch for windows first ..
+			// first + count that walks the group's segments side by side.  Only a first segment that starts mid-clip reads a window of
+			// another group, window first - 1, and every launch that writes it is ahead of this one on ctx->stream.  A group that
+			// stops before its finest level has returned above, its keys included: the call writes whole pictures only.
+			if (const int r = dwtx_transformation_inv(ctx, img, pyr, W, H, count * C))                   // decode.c:258
+				return r;
+			return dwtx_planes_to_pixels_clips(ctx, px, img, W, H, first, count);
+		}
 		if (crop) {
 			const int32_t *planes;
 			if (lo == g.levels) {   // whole pictures: one launch per level for all of them, each with its own origin
@@ -464,7 +474,7 @@ extern "C" int dwtx_decode_device16(dwtx_ctx *ctx, const uint8_t *dev_streams, s
 
 // Everything a view entry point can say, each field's default its neutral value: an extern "C" entry names the fields its ABI
 // has and calls encode_views / decode_views, which resolve the call with plan_view.
-enum { PAIR_NONE = 0, PAIR_DELTA, PAIR_CHAIN };
+enum { PAIR_NONE = 0, PAIR_DELTA, PAIR_CHAIN, PAIR_CLIPS };
 struct ViewCall {
 	const dwtx_view *view = nullptr;
 	size_t pixel_step = 0;                       // samples from a pixel to the next one of its row; 0 and `channels` are both the dense case
@@ -482,6 +492,7 @@ struct ViewCall {
 	const dwtx_view *other = nullptr;
 	size_t other_step = 0;
 	int sgn = 0;
+	int period = 0;                              // a clips call (PAIR_CLIPS, no `other`): every period-th window of the view is a key
 	int W = 0, H = 0, n = 0;                     // the pictures' size and number
 	bool dst = false;                            // the view will be written (maxval, disjoint windows)
 	// what single entries insist on: the float calls on a format, the list calls on a list
@@ -506,8 +517,12 @@ static int view_pixels(const ViewCall &c, int kind, dwtx_pixels *px)
 	const dwtx_view *v = c.view;
 	const int W = c.win_w(), H = c.win_h(), n = c.n;
 	const bool dst = c.dst, list = c.windows || c.needs_windows, sgn = c.minval != nullptr;
+	// whose view it is, in front of every text: a clips call's refusals all start "clips view:" (include/dwtx.h), also those that
+	// the other calls word without a prefix (`bare`)
+	const bool clips = c.pair == PAIR_CLIPS;
+	const char *who = clips ? "clips view" : "view", *bare = clips ? "clips view: " : "";
 	if (c.order != DWTX_ORDER_RGB && c.order != DWTX_ORDER_BGR) {
-		dwtx_set_error("view: channel order %d (DWTX_ORDER_RGB = 0 or DWTX_ORDER_BGR = 1)", c.order);
+		dwtx_set_error("%s: channel order %d (DWTX_ORDER_RGB = 0 or DWTX_ORDER_BGR = 1)", who, c.order);
 		return DWTX_ERR_ARG;
 	}
 	if (list && !c.windows) {
@@ -515,7 +530,11 @@ static int view_pixels(const ViewCall &c, int kind, dwtx_pixels *px)
 		return DWTX_ERR_ARG;
 	}
 	if (!v || (!list && !v->dev) || n < 1) {
-		dwtx_set_error("no view, no pixels or no windows");
+		dwtx_set_error("%sno view, no pixels or no windows", bare);
+		return DWTX_ERR_ARG;
+	}
+	if (clips && !dwtx_dims_ok(W, H)) {
+		dwtx_set_error("clips view: unsupported image size %dx%d (8..%d per side)", W, H, DWTX_MAX_SIDE);
 		return DWTX_ERR_ARG;
 	}
 	if (!c.crop && !c.thin)
@@ -523,25 +542,25 @@ static int view_pixels(const ViewCall &c, int kind, dwtx_pixels *px)
 	else if (W < 1 || H < 1 || W > DWTX_MAX_SIDE || H > DWTX_MAX_SIDE)   // (a crop of a picture that crop_of_call has checked)
 		return DWTX_ERR_ARG;
 	if (kind >= 0 && v->sample_bytes != (kind == DWTX_SAMPLE_F32 ? 4 : 2)) {
-		dwtx_set_error("view: sample_bytes %d does not match the float type (%d bytes a sample)", v->sample_bytes, kind == DWTX_SAMPLE_F32 ? 4 : 2);
+		dwtx_set_error("%s: sample_bytes %d does not match the float type (%d bytes a sample)", who, v->sample_bytes, kind == DWTX_SAMPLE_F32 ? 4 : 2);
 		return DWTX_ERR_ARG;
 	}
 	if ((kind < 0 && v->sample_bytes != 1 && v->sample_bytes != 2) || (v->channels != 1 && v->channels != 3) || (!list && v->cols < 0)) {
-		dwtx_set_error("view: sample_bytes %d (1 or 2), channels %d (1 or 3), cols %d (>= 0)", v->sample_bytes, v->channels, v->cols);
+		dwtx_set_error("%s: sample_bytes %d (1 or 2), channels %d (1 or 3), cols %d (>= 0)", who, v->sample_bytes, v->channels, v->cols);
 		return DWTX_ERR_ARG;
 	}
 	if (sgn && kind < 0 && v->sample_bytes != 2) {
-		dwtx_set_error("view: signed integer samples are int16_t: sample_bytes %d (2)", v->sample_bytes);
+		dwtx_set_error("%s: signed integer samples are int16_t: sample_bytes %d (2)", who, v->sample_bytes);
 		return DWTX_ERR_ARG;
 	}
 	const size_t cs = v->channels == 3 ? v->channel_stride : 0;   // planar RGB; a gray view has no use for it
 	const size_t step = c.pixel_step == (size_t)v->channels ? 0 : c.pixel_step;   // (the dense case: everything downstream is the plain call's)
 	if (step && (step < (size_t)v->channels || step > 0x7fffffffu)) {
-		dwtx_set_error("view: pixel_step %zu is less than the %d channels of a pixel (or beyond 2^31)", c.pixel_step, v->channels);
+		dwtx_set_error("%s: pixel_step %zu is less than the %d channels of a pixel (or beyond 2^31)", who, c.pixel_step, v->channels);
 		return DWTX_ERR_ARG;
 	}
 	if (step && cs) {
-		dwtx_set_error("view: pixel_step %zu with planar pixels (channel_stride %zu): the rows of a plane are dense", c.pixel_step, cs);
+		dwtx_set_error("%s: pixel_step %zu with planar pixels (channel_stride %zu): the rows of a plane are dense", who, c.pixel_step, cs);
 		return DWTX_ERR_ARG;
 	}
 	const size_t image_stride = list ? 0 : v->image_stride;
@@ -557,21 +576,21 @@ static int view_pixels(const ViewCall &c, int kind, dwtx_pixels *px)
 	px->order = v->channels == 3 ? c.order : DWTX_ORDER_RGB;
 	const size_t row = px->row_samples(W);
 	if (v->row_pitch < row) {
-		dwtx_set_error("view: row_pitch %zu is less than a window's row of %zu samples", v->row_pitch, row);
+		dwtx_set_error("%s: row_pitch %zu is less than a window's row of %zu samples", who, v->row_pitch, row);
 		return DWTX_ERR_ARG;
 	}
 	if (!list && (uintptr_t)v->dev % (size_t)v->sample_bytes) {
-		dwtx_set_error("view: dev is not aligned to its %d-byte samples", v->sample_bytes);
+		dwtx_set_error("%s: dev is not aligned to its %d-byte samples", who, v->sample_bytes);
 		return DWTX_ERR_ARG;
 	}
 	const size_t cols = list ? (size_t)n : v->cols && v->cols < n ? (size_t)v->cols : (size_t)n;
 	const bool bands = cols < (size_t)n;
 	if (dst && sgn) {
-		if (!dwtx_range_ok(*c.minval, v->maxval))
+		if (!dwtx_range_ok(*c.minval, v->maxval, bare))
 			return DWTX_ERR_ARG;
-	} else if (dst && (v->sample_bytes == 1 ? v->maxval != 255 : !dwtx_maxval_ok(v->maxval))) {
+	} else if (dst && (v->sample_bytes == 1 ? v->maxval != 255 : !dwtx_maxval_ok(v->maxval, bare))) {
 		if (v->sample_bytes == 1)
-			dwtx_set_error("view: maxval %d with 1-byte samples (255)", v->maxval);
+			dwtx_set_error("%s: maxval %d with 1-byte samples (255)", who, v->maxval);
 		return DWTX_ERR_ARG;
 	}
 	if (dst && !list) {
@@ -584,19 +603,19 @@ static int view_pixels(const ViewCall &c, int kind, dwtx_pixels *px)
 		if (cs && inside)
 			;   // (disjoint as they are)
 		else if (cols > 1 && !stacked && !beside) {
-			dwtx_set_error("view: windows overlap (image_stride %zu, row_pitch %zu, %zu windows per band of %zu x %d samples)",
+			dwtx_set_error("%s: windows overlap (image_stride %zu, row_pitch %zu, %zu windows per band of %zu x %d samples)", who,
 				v->image_stride, v->row_pitch, cols, row, H);
 			return DWTX_ERR_ARG;
 		} else if (bands && v->band_stride < (cols - 1) * v->image_stride + window) {
-			dwtx_set_error("view: bands overlap (band_stride %zu, a band spans %zu samples)", v->band_stride, (cols - 1) * v->image_stride + window);
+			dwtx_set_error("%s: bands overlap (band_stride %zu, a band spans %zu samples)", who, v->band_stride, (cols - 1) * v->image_stride + window);
 			return DWTX_ERR_ARG;
 		} else if (cs) {
 			// planar, second form: the channel planes of the whole view apart (a CHW frame and its tiles, CNHW)
 			const size_t nbands = ((size_t)n + cols - 1) / cols;
 			const size_t span = (nbands - 1) * (bands ? v->band_stride : 0) + (cols - 1) * v->image_stride + window;
 			if (cs < span) {
-				dwtx_set_error("view: planes overlap (channel_stride %zu: neither at least a window's plane of %zu samples with windows of %zu apart, "
-					"nor at least one channel of the whole view, %zu samples)", cs, window, win3, span);
+				dwtx_set_error("%s: planes overlap (channel_stride %zu: neither at least a window's plane of %zu samples with windows of %zu apart, "
+					"nor at least one channel of the whole view, %zu samples)", who, cs, window, win3, span);
 				return DWTX_ERR_ARG;
 			}
 		}
@@ -839,6 +858,35 @@ static int pair_refusals(const ViewCall &c, const char *what, const char *other)
 	return DWTX_OK;
 }
 
+// What the clips calls refuse before the view is looked at (pair_refusals' place and, without a second view, its rules).  What
+// view_pixels refuses of the view itself — everything dwtx_encode_view_order / dwtx_decode_view_order refuse, the signed calls'
+// sample size and range — it words as theirs: every text of a clips call starts "clips view:"
+static int clips_refusals(const ViewCall &c)
+{
+	const int minval = c.minval ? *c.minval : 0;
+	if (c.period < 1) {
+		dwtx_set_error("clips view: period %d (every period-th window is a key: 1 or more; period >= n is one clip)", c.period);
+		return DWTX_ERR_ARG;
+	}
+	if (!c.view) {
+		dwtx_set_error("clips view: no view");
+		return DWTX_ERR_ARG;
+	}
+	if (c.sgn != 0 && c.sgn != 1) {
+		dwtx_set_error("clips view: sgn %d (0: uint8_t / uint16_t samples, 1: int16_t samples)", c.sgn);
+		return DWTX_ERR_ARG;
+	}
+	if (c.sgn && c.view->sample_bytes == 1) {
+		dwtx_set_error("clips view: sgn with 1-byte samples (signed samples are int16_t)");
+		return DWTX_ERR_ARG;
+	}
+	if (!c.sgn && minval != 0) {
+		dwtx_set_error("clips view: minval %d without sgn (unsigned samples start at 0)", minval);
+		return DWTX_ERR_ARG;
+	}
+	return DWTX_OK;
+}
+
 // The units of a grid view — its n windows, or the 3n planes of planar RGB, as in list_windows — as byte spans [first, first +
 // (H-1)*row_pitch + row) of the address space, appended to `spans` with `tag`
 struct DeltaSpan {
@@ -933,9 +981,10 @@ struct ViewPlan {
 
 // The one resolver of every view call: host arithmetic only, no context and no device.  It refuses, in this order (DESIGN.md
 // section 4.23): the flags; the crop and its origins; the float format; of a delta or chain pair the missing view, sgn, minval,
-// channels and sample bytes; the view itself (view_pixels), the size of its table and its list (list_windows); a float
-// source's range; the pair's other view and the places where the two meet.  Four calls are, by the header's word, another call
-// with fewer arguments, and become that call here — nowhere else is a neutral argument looked at.
+// channels and sample bytes (of a clips call, in that place: the period, the missing view, sgn, its sample size and minval);
+// the view itself (view_pixels), the size of its table and its list (list_windows); a float source's range; the pair's other
+// view and the places where the two meet.  Four calls are, by the header's word, another call with fewer arguments, and become
+// that call here — nowhere else is a neutral argument looked at.
 static int plan_view(const ViewCall &call, ViewPlan *plan)
 {
 	ViewCall c = call;
@@ -983,6 +1032,9 @@ static int plan_view(const ViewCall &call, ViewPlan *plan)
 		}
 		if ((rc = pair_refusals(c, "chain", "key")))
 			return rc;
+	} else if (c.pair == PAIR_CLIPS) {
+		if ((rc = clips_refusals(c)))
+			return rc;
 	}
 	if (c.pair && !c.sgn)
 		c.minval = nullptr;
@@ -1001,7 +1053,10 @@ static int plan_view(const ViewCall &call, ViewPlan *plan)
 			px.bias[k] = c.fmt->bias[k];
 		}
 	}
-	if (c.pair) {
+	if (c.pair == PAIR_CLIPS) {
+		// no second view: the base of a link is the window before it, of the view itself (lift.hip's clips conversions)
+		px.clips = c.period;
+	} else if (c.pair) {
 		// The other view, checked as the *_view_order / *_view_signed calls check theirs: it is only ever read, and its maxval is not.
 		// A key is one window: what lies between windows is not the key's to say.
 		ViewCall o = c;
@@ -1191,6 +1246,16 @@ extern "C" int dwtx_encode_view_chain(dwtx_ctx *ctx, const dwtx_view *src, size_
 	return encode_views(ctx, c, capacity, dev_out, out_stride, dev_info);
 }
 
+// (one encode_device call: the clips instance of the forward conversion subtracts window i - 1 from every window but the keys)
+extern "C" int dwtx_encode_view_clips(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int period, int order, int sgn,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info)
+{
+	const int minval = 0;   // (a source is only read: its range is its samples')
+	const ViewCall c = { .view = src, .pixel_step = pixel_step, .order = order, .minval = &minval, .pair = PAIR_CLIPS, .sgn = sgn, .period = period,
+		.W = W, .H = H, .n = n };
+	return encode_views(ctx, c, capacity, dev_out, out_stride, dev_info);
+}
+
 extern "C" int dwtx_decode_view(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride,
 	const unsigned long long *dev_lens, int W, int H, int n, int levels_max, const dwtx_view *dst, dwtx_decode_info *host_info)
 {
@@ -1280,6 +1345,15 @@ extern "C" int dwtx_decode_view_chain(dwtx_ctx *ctx, const uint8_t *dev_streams,
 	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
 }
 
+extern "C" int dwtx_decode_view_clips(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, const dwtx_view *dst, size_t pixel_step, int period, int order, int sgn, int minval,
+	dwtx_decode_info *host_info)
+{
+	const ViewCall c = { .view = dst, .pixel_step = pixel_step, .order = order, .minval = &minval, .pair = PAIR_CLIPS, .sgn = sgn, .period = period,
+		.W = W, .H = H, .n = n, .dst = true };
+	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
+}
+
 // The host-only exports: the resolver's verdict, and for the flip plan its table read back
 
 extern "C" int dwtx_view_list_check(const dwtx_view *v, size_t pixel_step, int W, int H, int n, const void *const *host_windows, int dst)
@@ -1326,6 +1400,14 @@ extern "C" int dwtx_view_chain_check(const dwtx_view *v, size_t pixel_step, cons
 {
 	const ViewCall c = { .view = v, .pixel_step = pixel_step, .order = DWTX_ORDER_RGB, .minval = &minval, .pair = PAIR_CHAIN, .other = key,
 		.other_step = key_pixel_step, .sgn = sgn, .W = W, .H = H, .n = n, .dst = dst != 0 };
+	ViewPlan plan;
+	return plan_view(c, &plan);
+}
+
+extern "C" int dwtx_view_clips_check(const dwtx_view *v, size_t pixel_step, int period, int sgn, int minval, int W, int H, int n, int dst)
+{
+	const ViewCall c = { .view = v, .pixel_step = pixel_step, .order = DWTX_ORDER_RGB, .minval = &minval, .pair = PAIR_CLIPS, .sgn = sgn, .period = period,
+		.W = W, .H = H, .n = n, .dst = dst != 0 };
 	ViewPlan plan;
 	return plan_view(c, &plan);
 }

@@ -107,19 +107,20 @@ void *dwtx_scratch(dwtx_ctx *ctx, int slot, size_t bytes);
 static inline int dwtx_cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // the maxval a deep decode is told (include/dwtx.h): what a 16-bit sample can hold
-static inline bool dwtx_maxval_ok(int maxval)
+// (`whose`: what stands in front of the text, with its colon and blank)
+static inline bool dwtx_maxval_ok(int maxval, const char *whose = "")
 {
 	if (maxval >= 1 && maxval <= 65535)
 		return true;
-	dwtx_set_error("maxval %d is outside 1..65535", maxval);
+	dwtx_set_error("%smaxval %d is outside 1..65535", whose, maxval);
 	return false;
 }
 // the range a signed call is told (include/dwtx.h, dwtx_*_view_signed): what an int16_t sample can hold
-static inline bool dwtx_range_ok(int minval, int maxval)
+static inline bool dwtx_range_ok(int minval, int maxval, const char *whose = "")
 {
 	if (minval >= -32768 && minval < maxval && maxval <= 32767)
 		return true;
-	dwtx_set_error("range [%d, %d]: signed samples need -32768 <= minval < maxval <= 32767", minval, maxval);
+	dwtx_set_error("%srange [%d, %d]: signed samples need -32768 <= minval < maxval <= 32767", whose, minval, maxval);
 	return false;
 }
 
@@ -270,8 +271,15 @@ struct dwtx_pixels {
 	// dwtx_planes_to_pixels_chain) walks the windows of a group in order.  image() and moved() keep both fields.
 	bool chain = false;
 	dwtx_base_grid key;
+	// A clip stack (the *_view_clips calls): a stack of chains with their keys inside it.  clips is the period (0: no clip stack):
+	// window i of the STACK with i % clips == 0 is a key, coded as itself, every other one a link whose base is window i - 1 of the
+	// view itself.  clip_at is the stack index of the view's window 0, which image() moves (a part of an encode starts anywhere in a
+	// clip).  `delta` and `key` stay empty: like a chain, a clip stack never meets a kernel that walks two grids window for window;
+	// its conversions (lift.hip: the clips instance of the forward delta conversion, dwtx_planes_to_pixels_clips) take the period.
+	int clips = 0;
+	size_t clip_at = 0;
 
-	bool is_delta() const { return delta.base != nullptr || chain; }
+	bool is_delta() const { return delta.base != nullptr || chain || clips; }
 	// where the view's own windows lie, and the same samples on another grid: the one place that knows which fields are the layout
 	dwtx_base_grid grid() const { return dwtx_base_grid{ base, image_stride, row_pitch, band_stride, first, channel_stride, pixel_step, cols }; }
 	dwtx_pixels with_grid(const dwtx_base_grid &g) const
@@ -359,6 +367,8 @@ struct dwtx_pixels {
 			else
 				p.delta.first += i;
 		}
+		if (clips)
+			p.clip_at += i;
 		return p;
 	}
 	// the same layout somewhere else
@@ -429,6 +439,11 @@ int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *p
 // windows first .. first + count, in order, onto window first - 1 as it lies in memory when the launch runs (first == 0: the
 // key) — window i receives clamp(window i - 1 + d_i), the running sample kept in a register.  One launch, on ctx->stream.
 int dwtx_planes_to_pixels_chain(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int first, int count);
+// lift.hip: the one inverse conversion of a clip stack (dwtx_pixels::clips; px is the whole view of the call, clip_at 0): the planes
+// of windows first .. first + count — a key's its own picture's, a link's its residual's — in ONE launch that walks the group's
+// segments side by side: a key receives the plain conversion of its planes, a link clamp(window before + d).  A first segment that
+// starts mid-clip reads window first - 1 as it lies in memory when the launch runs.  On ctx->stream.
+int dwtx_planes_to_pixels_clips(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int first, int count);
 
 // The entropy stage's tiles (linearize.hip): the Hilbert curve of ring level l visits every aligned 32x32 square of
 // its lengths[l+1]-sided square contiguously ("curve block"), so the ring's coefficients, in the order of

@@ -3486,6 +3486,26 @@ __device__ __forceinline__ _Float16 sample_of<_Float16>(int v, const FloatFmt &f
 template <>
 __device__ __forceinline__ __bf16 sample_of<__bf16>(int v, const FloatFmt &f, int c) { return (__bf16)float_of(v, f.scale[c], f.bias[c]); }
 
+// One pixel of that arithmetic, which the general conversion below and the keys of a clip stack (k_clips_from_planes) share:
+// plain_gray is a gray sample's one clamp, plain_rgb the clamps of Y, Co and Cg, the inverse colour transform and pnm.h:108's
+// clamp of each output sample, R = M - L: Y, Co and Cg are read at src[0], src[step] and src[2 * step] (planes in memory, or a
+// lane's three registers with step 1), and out(c, sample) receives colour c = 0, 1, 2 (R, G, B), one after the other.
+__device__ __forceinline__ int plain_gray(int v, int L, int M) { return clampi(v, L, M); }
+template <class Out>
+__device__ __forceinline__ void plain_rgb(const int *src, long step, int R, int L, int M, Out &&out)
+{
+	const int yy = clampi(src[0], L, M);
+	const int co = clampi(src[step], -R, R);
+	const int cg = clampi(src[2 * step], -R, R);
+	const int t = yy - tdiv2(cg);
+	const int gr = cg + t;
+	const int b = t - tdiv2(co);
+	const int r = b + co;
+	out(0, clampi(r, L, M));
+	out(1, clampi(gr, L, M));
+	out(2, clampi(b, L, M));
+}
+
 template <class P, bool FLIP = false>
 __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, int L_, int M, FloatFmt f)
 {
@@ -3500,19 +3520,12 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__
 		P *row = FLIP ? flipped_row(pix, g, win, mx, y) : pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
 		const int *src = planes + (long)win * g.C * npix + (long)y * g.W + x;
 		if (g.C == 1) {
-			row[(long)mx * g.col_step] = sample_of<P>(clampi(src[0], L, M), f, 0);
+			row[(long)mx * g.col_step] = sample_of<P>(plain_gray(src[0], L, M), f, 0);
 		} else {
-			const int yy = clampi(src[0], L, M);
-			const int co = clampi(src[npix], -R, R);
-			const int cg = clampi(src[2 * npix], -R, R);
-			const int t = yy - tdiv2(cg);
-			const int gr = cg + t;
-			const int b = t - tdiv2(co);
-			const int r = b + co;
-			P *p = row + (long)mx * g.col_step;
-			p[0] = sample_of<P>(clampi(r, L, M), f, 0);
-			p[g.chan_stride] = sample_of<P>(clampi(gr, L, M), f, 1);
-			p[2 * g.chan_stride] = sample_of<P>(clampi(b, L, M), f, 2);
+			plain_rgb(src, npix, R, L, M, [&](int c, int v) {
+				P *p = row + (long)mx * g.col_step;
+				p[c * g.chan_stride] = sample_of<P>(v, f, c);
+			});
 		}
 	}
 }
@@ -3537,6 +3550,47 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels_delta
 			dst[0] = (int)p[0] - (int)q[0];
 		} else {
 			const int r = (int)p[0] - (int)q[0], gr = (int)p[g.chan_stride] - (int)q[gb.chan_stride], b = (int)p[2 * g.chan_stride] - (int)q[2 * gb.chan_stride];
+			const int co = r - b;
+			const int t = b + tdiv2(co);
+			const int cg = gr - t;
+			dst[0] = t + tdiv2(cg);
+			dst[npix] = co;
+			dst[2 * npix] = cg;
+		}
+	}
+}
+
+// The delta conversion that takes a period (a clip stack, dwtx_pixels::clips: dwtx_encode_view_clips): the base pictures are the
+// view's own, window `win` against window win - 1 — one pointer, one grid, and win_off is asked for win - 1 — and the window whose
+// index in the stack, at + win, is a multiple of `period` is a key: nothing is subtracted and nothing of a base is loaded (the
+// key test is the wave's, a scalar branch), so that window 0's "window -1" is never addressed.  win - 1 of a launch's window 0 is
+// the window before a part of the batch (dwtx_pixels::image moved the view and `at` with it: a one-band view's pointer, a grid's
+// `first`, which is then at least 1 — win_off's unsigned sum comes out at first - 1).  The view is only read.
+template <class P>
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels_clips(int *__restrict__ planes, const P *__restrict__ pix, PixGrid g, unsigned at, unsigned period)
+{
+	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
+	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
+	if (x >= g.W || y >= g.H)
+		return;
+	const long npix = (long)g.W * g.H;
+	const long in = (long)y * g.row_pitch + (long)x * g.col_step;
+	for (unsigned win = blockIdx.z; win < (unsigned)g.n; win += gridDim.z) {
+		const P *p = pix + win_off(g.grid, g.image_stride, (int)win) + in;
+		int *dst = planes + (long)win * g.C * npix + (long)y * g.W + x;
+		int q0 = 0, q1 = 0, q2 = 0;
+		if ((at + win) % period != 0) {   // a link: the window before
+			const P *q = pix + win_off(g.grid, g.image_stride, (int)win - 1) + in;
+			q0 = (int)q[0];
+			if (g.C != 1) {
+				q1 = (int)q[g.chan_stride];
+				q2 = (int)q[2 * g.chan_stride];
+			}
+		}
+		if (g.C == 1) {
+			dst[0] = (int)p[0] - q0;
+		} else {
+			const int r = (int)p[0] - q0, gr = (int)p[g.chan_stride] - q1, b = (int)p[2 * g.chan_stride] - q2;
 			const int co = r - b;
 			const int t = b + tdiv2(co);
 			const int cg = gr - t;
@@ -3687,6 +3741,96 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_chain_from_planes(P *__r
 		chain_walk<P, 3>(pix, planes, g, base, gb, L, M, x, y);
 }
 
+// The conversion of a clip stack (dwtx_decode_view_clips; dwtx_pixels::clips): windows first .. first + g.n of ONE view, window i of
+// the stack a key where i % period == 0 — its samples the plain conversion of its planes, plain_gray / plain_rgb, exactly k_pixels_from_planes'
+// arithmetic for the sample type — and a link otherwise: chain_link onto the window before it, unchanged.  grid: (64 pixels of a
+// row, 4 rows, SEGMENT): a segment is a maximal run of the group's windows with no key but possibly at its start, and the launch
+// walks all of them side by side, each as k_chain_from_planes walks its chain — a lane owns one pixel position, the running sample
+// stays in a register, CHAIN_AHEAD pictures' plane loads are in flight ahead of a batch's arithmetic and stores.  Where segment z
+// begins and ends follows from first, the count and the period alone: with lead = the windows before the group's first key,
+// segment z covers [s, s + period) cut to the group, s = lead + (z - (lead != 0)) * period — blockIdx.z and kernel arguments only,
+// so the scalar unit computes it once per wave; no table, nothing from the host.  Only the group's first segment can start
+// mid-clip (lead != 0, z == 0): it alone loads a base, window first - 1 as it lies in memory.  Every other segment starts at a key
+// and reads no pixels at all.  So within one launch no segment reads a window another segment writes: the one window that is read,
+// first - 1, lies before every window of the group, and the launch writes windows first .. first + g.n only (a lane writes each
+// position once).  The host's ordering argument (codec.hip, decode_device) has window first - 1 in memory: planes, pixels and
+// base are __restrict__.  g is the WHOLE view's grid (windows counted from the stack's first), g.n the group's count.
+template <class P, int C>
+__device__ __forceinline__ void clips_walk(P *__restrict__ pix, const int *__restrict__ planes, const PixGrid &g, const P *__restrict__ base, int L, int M, int x, int y,
+	int win0, int n, bool keyed)
+{
+	const int R = M - L;
+	const long npix = (long)g.W * g.H;
+	const long wstep = (long)C * npix;   // from a picture's planes to the next one's
+	const long at = (long)y * g.row_pitch + (long)x * g.col_step;
+	int b[3] = { 0, 0, 0 };
+	if (!keyed) {   // (the wave's: a scalar branch)
+		const P *q = base + win_off(g.grid, g.image_stride, win0 - 1) + at;
+		b[0] = (int)q[0];
+		if (C == 3) {
+			b[1] = (int)q[g.chan_stride];
+			b[2] = (int)q[2 * g.chan_stride];
+		}
+	}
+	const int *src = planes + (long)y * g.W + x;
+	auto store = [&](int win) {
+		P *p = pix + win_off(g.grid, g.image_stride, win) + at;
+		p[0] = (P)b[0];
+		if (C == 3) {
+			p[g.chan_stride] = (P)b[1];
+			p[2 * g.chan_stride] = (P)b[2];
+		}
+	};
+	ChainRaw nxt[CHAIN_AHEAD], cur[CHAIN_AHEAD];
+#pragma unroll
+	for (int k = 0; k < CHAIN_AHEAD; ++k)   // (a picture past the segment's end: the last one's planes once more, never used)
+		nxt[k] = chain_load<C>(src + (long)min(k, n - 1) * wstep, npix);
+	for (int w0 = 0; w0 < n; w0 += CHAIN_AHEAD) {
+#pragma unroll
+		for (int k = 0; k < CHAIN_AHEAD; ++k)   // the one wait of the iteration
+			for (int c = 0; c < C; ++c)
+				cur[k].v[c] = hold(nxt[k].v[c]);
+		if (w0 + CHAIN_AHEAD < n) {   // the next batch's loads go out before this batch's arithmetic and stores
+#pragma unroll
+			for (int k = 0; k < CHAIN_AHEAD; ++k)
+				nxt[k] = chain_load<C>(src + (long)min(w0 + CHAIN_AHEAD + k, n - 1) * wstep, npix);
+		}
+#pragma unroll
+		for (int k = 0; k < CHAIN_AHEAD; ++k)
+			if (w0 + k < n) {
+				if (k == 0 && w0 == 0 && keyed) {   // the segment's key: its own picture, no base
+					if (C == 3)
+						plain_rgb(cur[k].v, 1, R, L, M, [&](int c, int v) { b[c] = v; });
+					else
+						b[0] = plain_gray(cur[k].v[0], L, M);
+				} else
+					chain_link<C>(cur[k], b, R, L, M);
+				store(win0 + w0 + k);
+			}
+	}
+}
+template <class P>
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_clips_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, const P *__restrict__ base,
+	int first, int period, int L_, int M)
+{
+	const int L = px_unsigned<P> ? 0 : L_;
+	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
+	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
+	if (x >= g.W || y >= g.H)
+		return;
+	// segment blockIdx.z of the group, in windows of the group: [r0, r1)
+	const int phase = first % period, lead = phase ? period - phase : 0;
+	const int s = lead + ((int)blockIdx.z - (lead ? 1 : 0)) * period;
+	const int r0 = max(s, 0), r1 = min(s + period, g.n);
+	if (r0 >= r1)   // (never: the host launches the group's segments and no more)
+		return;
+	const int *seg = planes + (long)r0 * g.C * g.W * g.H;
+	if (g.C == 1)
+		clips_walk<P, 1>(pix, seg, g, base, L, M, x, y, first + r0, r1 - r0, s >= 0);
+	else
+		clips_walk<P, 3>(pix, seg, g, base, L, M, x, y, first + r0, r1 - r0, s >= 0);
+}
+
 // Integer-only synthetic frames: seed = frame index, so every box
 // renders identical bytes.  kind 0 "smooth+noise", kind 1 uniform noise.
 __global__ __launch_bounds__(256) void k_synth(uint8_t *__restrict__ pix, int W, int H, int C, long total,
@@ -3821,7 +3965,7 @@ static void launch_delta_of(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, con
 }
 static int launch_delta(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const PixGrid &g, int W, int H, int n, int32_t *to_planes, const int32_t *from_planes)
 {
-	if (px.chain || px.is_float() || px.flips || px.listed() || !px.base_pixels().sample_aligned())   // (a chain has a conversion of its own, below)
+	if (px.chain || px.clips || px.is_float() || px.flips || px.listed() || !px.base_pixels().sample_aligned())   // (a chain and a clip stack have conversions of their own, below)
 		return DWTX_ERR_ARG;
 	const dwtx_pixels bp = px.base_pixels();
 	dim3 same;
@@ -3880,6 +4024,48 @@ int dwtx_planes_to_pixels_chain(dwtx_ctx *ctx, const dwtx_pixels &px, const int3
 	return DWTX_OK;
 }
 
+// A clip stack's conversions (dwtx_pixels::clips): the view's own grid is the base pictures' too
+template <class P>
+static void launch_clips_fwd(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const PixGrid &g, int32_t *planes)
+{
+	hipLaunchKernelGGL(k_planes_from_pixels_clips<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, static_cast<const P *>(px.red()), g,
+		(unsigned)(px.clip_at % (size_t)px.clips), (unsigned)px.clips);
+}
+template <class P>
+static void launch_clips_inv(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const PixGrid &g, const int32_t *planes, int first)
+{
+	hipLaunchKernelGGL(k_clips_from_planes<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), planes, g,
+		static_cast<const P *>(px.red()), first, px.clips, px.minval, px.maxval);
+}
+
+int dwtx_planes_to_pixels_clips(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int first, int count)
+{
+	const int C = px.channels;
+	if (!ctx || !planes || !px.base || px.clips < 1 || px.clip_at || px.chain || px.delta.base || W < 1 || H < 1 || (C != 1 && C != 3) || first < 0 || count < 1)
+		return DWTX_ERR_ARG;
+	if (px.is_float() || px.flips || px.listed() || !px.sample_aligned() || !px.range_ok())
+		return DWTX_ERR_ARG;
+	DWTX_ENTER(ctx);
+	dim3 grid;
+	const PixGrid g = pix_grid(px, W, H, count, &grid);
+	// the group's segments: the run before its first key, if it starts mid-clip, and one per key
+	const int phase = first % px.clips, lead = phase ? px.clips - phase : 0;
+	grid.z = lead >= count ? 1u : (unsigned)((lead ? 1 : 0) + dwtx_cdiv(count - lead, px.clips));
+	switch (px.kind) {
+	case DWTX_SAMPLE_U8:
+		launch_clips_inv<uint8_t>(ctx, grid, px, g, planes, first);
+		break;
+	case DWTX_SAMPLE_U16:
+		launch_clips_inv<uint16_t>(ctx, grid, px, g, planes, first);
+		break;
+	default:
+		launch_clips_inv<int16_t>(ctx, grid, px, g, planes, first);
+		break;
+	}
+	DWTX_LAUNCH_CHECK();
+	return DWTX_OK;
+}
+
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
 {
 	const int C = px.channels;
@@ -3893,6 +4079,23 @@ int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px,
 	dim3 grid;
 	const PixGrid g = pix_grid(px, W, H, n, &grid);
 	const FloatFmt f = float_fmt(px);
+	if (px.clips) {   // (before the delta views: a clip stack has no second grid)
+		if (px.chain || px.delta.base || px.is_float() || px.flips || px.listed())
+			return DWTX_ERR_ARG;
+		switch (px.kind) {
+		case DWTX_SAMPLE_U8:
+			launch_clips_fwd<uint8_t>(ctx, grid, px, g, planes);
+			break;
+		case DWTX_SAMPLE_U16:
+			launch_clips_fwd<uint16_t>(ctx, grid, px, g, planes);
+			break;
+		default:
+			launch_clips_fwd<int16_t>(ctx, grid, px, g, planes);
+			break;
+		}
+		DWTX_LAUNCH_CHECK();
+		return DWTX_OK;
+	}
 	if (px.is_delta()) {
 		if (const int rc = launch_delta(ctx, grid, px, g, W, H, n, planes, nullptr))
 			return rc;
@@ -4348,8 +4551,8 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 // (flip_sink: the FL instances of the wide inverse kernels write it) with any flags, a mirrored one if the windows' width is on the quad.
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H)
 {
-	if (px.chain)   // (a chain's base is the window before: no sink that walks the windows side by side takes it)
-		return false;
+	if (px.chain || px.clips)   // (a chain's and a clip stack's base is the window before: no sink that walks the windows side by side takes it,
+		return false;           // and a clip stack's source goes through the general conversion's clips instance, which knows the keys)
 	if (px.is_delta()) {
 		// a delta view: both views must qualify, as the plain views of their samples would (the 16-bit ones as deep views), gray or
 		// 8-bit interleaved RGB, dense pixels — every other pair takes the general conversions' delta instances

@@ -747,8 +747,8 @@ int dwtx_view_delta_check(const dwtx_view *v, size_t pixel_step, const dwtx_view
  * Route (decode, n > 1): the deep pictures' route as for every delta view, never the fused sinks: the int32 inverse transform
  * into planes, then per group of the batch one launch of lift.hip's k_chain_from_planes, each lane walking its pixel through
  * the group's pictures in order with the running sample in a register.
- * Not in these calls, for the reasons the delta calls give: float samples, window lists, flips, crops, levels_max, a NULL key, and
- * several chains per call (one call is one chain: a batch of volumes is a call per volume).
+ * Not in these calls, for the reasons the delta calls give: float samples, window lists, flips, crops, levels_max and a NULL key.
+ * One call is one chain; several chains per call, their keys inside the stack, are the *_view_clips calls below.
  * DWTX_ERR_ARG (with a dwtx_last_error() text, nothing written): a NULL key, mismatched channels or sample_bytes, sgn with 1-byte
  * samples, minval != 0 without sgn, a range outside the rule, a destination that meets the key, and everything
  * dwtx_encode_view_order / dwtx_decode_view_order refuse for either view. */
@@ -761,6 +761,48 @@ int dwtx_encode_view_chain(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_ste
  * this view and key (dst != 0: the decode's rules, the key against the destination among them). */
 int dwtx_view_chain_check(const dwtx_view *v, size_t pixel_step, const dwtx_view *key, size_t key_pixel_step,
 	int sgn, int minval, int W, int H, int n, int dst);
+
+/* ---- clips: chains with their keys inside the stack, many per call ------------------------------------------------------------
+ * A clip with a key frame every `period` frames, a batch of short clips for a loader, a study of several CT volumes: one stack
+ * of n windows in which window i with i % period == 0 is a KEY, coded as itself, and every other window a LINK, coded against
+ * window i - 1 of the same stack.  period >= 1; period >= n is one clip with its key at window 0; period == 1 makes every picture
+ * a key; the last clip may be short.  With the chain calls each clip costs two calls, a plain one for its key and a chain.
+ * Views: `src` / `dst` is ONE grid view of n windows, as in the delta calls, and every layout they take carries over: dense,
+ * pitched, stacks and tile grids, planar and stepped pixels, either channel order, uint8_t, uint16_t and, with sgn, int16_t
+ * samples, gray and RGB.  sgn, minval and the range follow the delta calls' rules.  There is no second view.
+ * Encode: asynchronous, one pass through the pipeline for all n pictures.  Stream i and dev_info[i] of a key are byte for byte
+ * those of the plain call on window i — dwtx_encode_view_signed, or dwtx_encode_view_order when sgn == 0, i.e. of the reference's
+ * stages (encode.c:155-221) on the picture itself: a key is an ordinary stream that any reader shows.  A link's are those of
+ * dwtx_encode_view_delta of window i against window i - 1.  The view is only read.  A picture that needs more than 16 bit planes
+ * gets error = 1 and the others of its batch are coded; dwtx_encode_bound16 is the safe stride; capacity, the zero padding behind
+ * a stream and the encode index (entry i for stream i) keep their meaning.
+ * Decode, stated by equivalence: the result — every byte of the destination's buffer, and host_info — is that of walking i = 0 ..
+ * n - 1 in order.  A key: if stream i has status 0 and supports the whole picture (host_info[i].level + 1 == levels), window i
+ * receives what the plain decode of stream i alone writes there (dwtx_decode_view_signed / dwtx_decode_view_order:
+ * decode.c:174-264 with the missing-plane bias of decode.c:51-58 and their clamps for [minval, maxval]); otherwise the window
+ * stays as it is — the one deliberate difference from a plain call: a key cut before its finest level is NOT written into its
+ * window's corner, for the call has no levels_max and writes whole pictures only.  A link: dwtx_decode_view_delta of stream i
+ * alone into window i with window i - 1 as it lies in memory at that moment as its base; an unreadable link or one cut before its
+ * finest level leaves its window as it is, and the next link takes what lies there.  host_info[i] is the plain call's; the call
+ * synchronises where dwtx_decode_view does.
+ * Disjointness (decode): dwtx_decode_view_step's rules for dst, nothing else.
+ * Route (decode): the deep pictures' route as for every delta view, never the fused sinks: the int32 inverse transform into
+ * planes, then per group of the batch ONE launch of lift.hip's k_clips_from_planes, which walks the group's segments (a run of
+ * windows from a key, or from the group's start, to before the next key) side by side, each lane walking its pixel through a
+ * segment's pictures with the running sample in a register.  Encode: the general conversion's clips
+ * instance (a key subtracts nothing and loads no base), then the deep pictures' pipeline, once.
+ * Not in these calls: float samples, window lists, flips, crops, levels_max, and a key outside the stack (dwtx_*_view_chain).
+ * DWTX_ERR_ARG (with a dwtx_last_error() text that starts "clips view:", nothing written): period < 1, a NULL view, sgn with
+ * 1-byte samples, minval != 0 without sgn, a range outside the signed calls' rule, and everything dwtx_encode_view_order /
+ * dwtx_decode_view_order refuse for the view. */
+int dwtx_encode_view_clips(dwtx_ctx *ctx, const dwtx_view *src, size_t pixel_step, int period, int order, int sgn,
+	int W, int H, int n, long capacity, uint8_t *dev_out, size_t out_stride, dwtx_stream_info *dev_info);
+int dwtx_decode_view_clips(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, const dwtx_view *dst, size_t pixel_step, int period, int order, int sgn, int minval,
+	dwtx_decode_info *host_info);
+/* Host arithmetic only, like dwtx_view_chain_check: DWTX_OK, or the DWTX_ERR_ARG (and text) the two calls above would return for
+ * this view (dst != 0: the decode's rules). */
+int dwtx_view_clips_check(const dwtx_view *v, size_t pixel_step, int period, int sgn, int minval, int W, int H, int n, int dst);
 
 /* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
  * interior, right column, bottom row, corner, in that order, those that exist — each a cols x rows grid of W x H tiles
