@@ -121,6 +121,90 @@ struct Clamp {
 	__device__ __forceinline__ int r() const { return hi - lo; }
 };
 __device__ __forceinline__ Clamp clamp_of(const LevelArgs &a) { return Clamp{ a.minval, a.maxval }; }
+__device__ __forceinline__ int clamp_to(int v, int lo, int hi)
+{
+	return v < lo ? lo : v > hi ? hi : v;
+}
+// a delta sink's sample: the residual v under the clamp of [-R, R], R = hi - lo, onto the base's sample b, the sum clamped to the range
+__device__ __forceinline__ int delta_sample(int v, int b, Clamp M)
+{
+	return clamp_to(b + clamp_to(v, -M.r(), M.r()), M.lo, M.hi);
+}
+
+// ---- the colour transform, once: every source and sink of RGB pixels in this file calls these ----
+// image.h:52-65 rgb2ycocg, reversible on any int: output ch of it — 0 Y, 1 Co, 2 Cg.  A wave of the wide forward kernels works on
+// one plane and asks with its (uniform) channel, so that what the other channels alone need is not evaluated; ycocg_of is the
+// whole triple, in which the compiler finds the three calls' common terms.
+__device__ __forceinline__ int ycocg_ch(int r, int g, int b, int ch)
+{
+	const int co = r - b;
+	if (ch == 1)
+		return co;
+	const int t = b + tdiv2(co);
+	const int cg = g - t;
+	return ch == 2 ? cg : t + tdiv2(cg);
+}
+__device__ __forceinline__ void ycocg_of(int r, int g, int b, int &y, int &co, int &cg)
+{
+	y = ycocg_ch(r, g, b, 0);
+	co = ycocg_ch(r, g, b, 1);
+	cg = ycocg_ch(r, g, b, 2);
+}
+// image.h:39-50 ycocg2rgb without its clamps
+__device__ __forceinline__ void rgb_of_ycocg(int y, int co, int cg, int &r, int &g, int &b)
+{
+	const int t = y - tdiv2(cg);
+	g = cg + t;
+	b = t - tdiv2(co);
+	r = b + co;
+}
+// The two front ends of the inverse.  Both read Y, Co and Cg at src[0], src[step] and src[2 * step] — planes in memory, or a lane's
+// three registers with step 1 — each just before its clamp, and hand on one colour after the other: the form in which every caller
+// keeps the registers it had (a by-value form cost the general conversions one each).
+// The plain regime (a picture's own samples; image.h:41-43 and pnm.h:108 with M for [0, 255]): Y to [lo, hi], Co and Cg to
+// [-R, R], the inverse, each colour to [lo, hi]; out(c, sample) receives colour c = 0, 1, 2 (R, G, B).
+template <class Out>
+__device__ __forceinline__ void rgb_plain(const int *src, long step, Clamp M, Out &&out)
+{
+	const int R = M.r();
+	const int y = clamp_to(src[0], M.lo, M.hi);
+	const int co = clamp_to(src[step], -R, R);
+	const int cg = clamp_to(src[2 * step], -R, R);
+	int r, g, b;
+	rgb_of_ycocg(y, co, cg, r, g, b);
+	out(0, clamp_to(r, M.lo, M.hi));
+	out(1, clamp_to(g, M.lo, M.hi));
+	out(2, clamp_to(b, M.lo, M.hi));
+}
+// The residual regime (a delta view's, a chain's or a clip's link: the planes hold S - B, whose range is [-R, R]): Y to [-R, R],
+// Co and Cg to [-2R, 2R], the inverse, then each colour as delta_sample onto the base's colour — r, g, b: the base in, the sample out.
+__device__ __forceinline__ void rgb_residual(const int *src, long step, Clamp M, int &r, int &g, int &b)
+{
+	const int R = M.r();
+	const int y = clamp_to(src[0], -R, R);
+	const int co = clamp_to(src[step], -2 * R, 2 * R);
+	const int cg = clamp_to(src[2 * step], -2 * R, 2 * R);
+	int dr, dg, db;
+	rgb_of_ycocg(y, co, cg, dr, dg, db);
+	r = delta_sample(dr, r, M);
+	g = delta_sample(dg, g, M);
+	b = delta_sample(db, b, M);
+}
+// (the same two for a lane that holds Y, Co and Cg of a pixel in registers: the wide inverse kernels' rows)
+__device__ __forceinline__ void rgb_plain(int y, int co, int cg, Clamp M, int &r, int &g, int &b)
+{
+	const int v[3] = { y, co, cg };
+	int o[3];
+	rgb_plain(v, 1, M, [&](int c, int s) { o[c] = s; });
+	r = o[0];
+	g = o[1];
+	b = o[2];
+}
+__device__ __forceinline__ void rgb_residual(int y, int co, int cg, Clamp M, int &r, int &g, int &b)
+{
+	const int v[3] = { y, co, cg };
+	rgb_residual(v, 1, M, r, g, b);
+}
 
 // A float destination (dwtx_pixels::kind): scale and bias per COLOUR — R, G, B, whatever the order the channels lie in; gray
 // uses [0] — and which of the two 16-bit types a Half16 sink writes (the two differ in the convert only: one kernel for both)
@@ -638,16 +722,6 @@ __device__ __forceinline__ FwdRaw widen_u(const FwdRawS &r)
 	o.xr = (int)(r.e & 0xffffu);
 	o.left = make_int2(o.xr, (int)(r.e >> 16));
 	return o;
-}
-
-__device__ __forceinline__ int ycocg_ch(int r, int g, int b, int ch)   // image.h:52-65, channel ch (uniform)
-{
-	const int co = r - b;
-	if (ch == 1)
-		return co;
-	const int t = b + tdiv2(co);
-	const int cg = g - t;
-	return ch == 2 ? cg : t + tdiv2(cg);
 }
 
 // The colour transform on a pixel's three samples AS THEY LIE (s0 the lowest-addressed): R, G, B, or — BGR, dwtx_pixels::order —
@@ -2123,13 +2197,6 @@ struct InvPix {
 	typedef NoBase base;
 	static constexpr bool DELTA = false;
 };
-__device__ __forceinline__ int delta_sample(int v, int b, Clamp M)
-{
-	const int R = M.r();
-	const int d = v < -R ? -R : v > R ? R : v;
-	const int o = b + d;
-	return o < M.lo ? M.lo : o > M.hi ? M.hi : o;
-}
 template <typename P>
 struct OutRow<DeltaPix<P>> {
 	typedef typename std::conditional<sizeof(P) == 1, unsigned, uint2>::type type;   // four samples: the finished row, and the base's quad as it is loaded
@@ -2685,12 +2752,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv2_level_w(Inv2Args a)
 
 // The finest inverse level of an RGB image: one wave carries the same columns of the three planes
 // (Y, Co, Cg) and writes interleaved 8-bit pixels — image.h:39-50 ycocg2rgb with its input clamps and
-// the output clamp of pnm.h:108 fused in.  grid.z = image; dst8 rows are 3*w bytes.
-__device__ __forceinline__ int clamp_to(int v, int lo, int hi)
-{
-	return v < lo ? lo : v > hi ? hi : v;
-}
-
+// the output clamp of pnm.h:108 fused in (rgb_plain).  grid.z = image; dst8 rows are 3*w bytes.
 struct Rgb12 {
 	unsigned w[3];   // four pixels
 };
@@ -2707,14 +2769,11 @@ __device__ __forceinline__ Rgb24 rgb16_of(const Quad4 &y, const Quad4 &co, const
 	unsigned px[12];
 #pragma unroll
 	for (int k = 0; k < 4; ++k) {
-		const int yy = clamp_to(y.v[k], M.lo, M.hi), c0 = clamp_to(co.v[k], -M.r(), M.r()), c1 = clamp_to(cg.v[k], -M.r(), M.r());
-		const int t = yy - tdiv2(c1);
-		const int g = c1 + t;
-		const int b = t - tdiv2(c0);
-		const int r = b + c0;
-		px[3 * k + (BGR ? 2 : 0)] = (unsigned)clamp_to(r, M.lo, M.hi);
-		px[3 * k + 1] = (unsigned)clamp_to(g, M.lo, M.hi);
-		px[3 * k + (BGR ? 0 : 2)] = (unsigned)clamp_to(b, M.lo, M.hi);
+		int r, g, b;
+		rgb_plain(y.v[k], co.v[k], cg.v[k], M, r, g, b);
+		px[3 * k + (BGR ? 2 : 0)] = (unsigned)r;
+		px[3 * k + 1] = (unsigned)g;
+		px[3 * k + (BGR ? 0 : 2)] = (unsigned)b;
 	}
 	Rgb24 o;
 #pragma unroll
@@ -2729,14 +2788,11 @@ __device__ __forceinline__ void rgb_planes_of(const Quad4 &y, const Quad4 &co, c
 {
 #pragma unroll
 	for (int k = 0; k < 4; ++k) {
-		const int yy = clamp_to(y.v[k], M.lo, M.hi), c0 = clamp_to(co.v[k], -M.r(), M.r()), c1 = clamp_to(cg.v[k], -M.r(), M.r());
-		const int t = yy - tdiv2(c1);
-		const int g = c1 + t;
-		const int b = t - tdiv2(c0);
-		const int r = b + c0;
-		px[0][k] = (unsigned)clamp_to(r, M.lo, M.hi);
-		px[1][k] = (unsigned)clamp_to(g, M.lo, M.hi);
-		px[2][k] = (unsigned)clamp_to(b, M.lo, M.hi);
+		int r, g, b;
+		rgb_plain(y.v[k], co.v[k], cg.v[k], M, r, g, b);
+		px[0][k] = (unsigned)r;
+		px[1][k] = (unsigned)g;
+		px[2][k] = (unsigned)b;
 	}
 }
 // w[c] = the four bytes of channel c
@@ -2904,14 +2960,11 @@ __device__ __forceinline__ Rgb12 rgb_of(const Quad4 &y, const Quad4 &co, const Q
 	unsigned char px[12];
 #pragma unroll
 	for (int k = 0; k < 4; ++k) {
-		const int yy = clamp_to(y.v[k], 0, 255), c0 = clamp_to(co.v[k], -255, 255), c1 = clamp_to(cg.v[k], -255, 255);
-		const int t = yy - tdiv2(c1);
-		const int g = c1 + t;
-		const int b = t - tdiv2(c0);
-		const int r = b + c0;
-		px[3 * k + (BGR ? 2 : 0)] = (unsigned char)clamp_to(r, 0, 255);
-		px[3 * k + 1] = (unsigned char)clamp_to(g, 0, 255);
-		px[3 * k + (BGR ? 0 : 2)] = (unsigned char)clamp_to(b, 0, 255);
+		int r, g, b;
+		rgb_plain(y.v[k], co.v[k], cg.v[k], Clamp{ 0, 255 }, r, g, b);
+		px[3 * k + (BGR ? 2 : 0)] = (unsigned char)r;
+		px[3 * k + 1] = (unsigned char)g;
+		px[3 * k + (BGR ? 0 : 2)] = (unsigned char)b;
 	}
 	Rgb12 o;
 #pragma unroll
@@ -2943,18 +2996,14 @@ struct RgbOut<uint8_t, PIX_STEP4_BGR> : RgbOut<uint8_t, PIX_STEP4> {
 template <bool BGR>
 __device__ __forceinline__ Rgb12 rgb_delta_of(const Quad4 &y, const Quad4 &co, const Quad4 &cg, Clamp M, const U32x3 &base)
 {
-	const int R = M.r();
 	unsigned char px[12];
 #pragma unroll
 	for (int k = 0; k < 4; ++k) {
-		const int yy = clamp_to(y.v[k], -R, R), c0 = clamp_to(co.v[k], -2 * R, 2 * R), c1 = clamp_to(cg.v[k], -2 * R, 2 * R);
-		const int t = yy - tdiv2(c1);
-		const int g = c1 + t;
-		const int b = t - tdiv2(c0);
-		const int r = b + c0;
-		px[3 * k] = (unsigned char)delta_sample(BGR ? b : r, rgb_byte(base, 3 * k), M);
-		px[3 * k + 1] = (unsigned char)delta_sample(g, rgb_byte(base, 3 * k + 1), M);
-		px[3 * k + 2] = (unsigned char)delta_sample(BGR ? r : b, rgb_byte(base, 3 * k + 2), M);
+		int r = rgb_byte(base, 3 * k + (BGR ? 2 : 0)), g = rgb_byte(base, 3 * k + 1), b = rgb_byte(base, 3 * k + (BGR ? 0 : 2));
+		rgb_residual(y.v[k], co.v[k], cg.v[k], M, r, g, b);
+		px[3 * k + (BGR ? 2 : 0)] = (unsigned char)r;
+		px[3 * k + 1] = (unsigned char)g;
+		px[3 * k + (BGR ? 0 : 2)] = (unsigned char)b;
 	}
 	Rgb12 o;
 #pragma unroll
@@ -3416,6 +3465,22 @@ __device__ __forceinline__ P *flipped_row(P *pix, const PixGrid &g, unsigned win
 }
 
 constexpr int PX_LANES = 64, PX_ROWS = 4;   // a workgroup of the conversions: one wave per row, a lane per pixel
+// the lane's pixel in that grid -> whether it lies inside w x h
+__device__ __forceinline__ bool px_lane(int w, int h, int &x, int &y)
+{
+	x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
+	y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
+	return x < w && y < h;
+}
+// a pixel's colours (or their residuals) as Y, Co and Cg into its place in the three planes, npix apart
+__device__ __forceinline__ void planes_of_rgb(int r, int g, int b, int *dst, long npix)
+{
+	int y, co, cg;
+	ycocg_of(r, g, b, y, co, cg);
+	dst[0] = y;
+	dst[npix] = co;
+	dst[2 * npix] = cg;
+}
 
 // pnm.h:69-74 (byte -> int) fused with image.h:52-65 rgb2ycocg.  P = uint8_t, uint16_t for deep pixels or int16_t for signed
 // ones, which widen with their sign (the same arithmetic: nothing in it knows the depth, and image.h:53-65 is reversible on
@@ -3440,9 +3505,8 @@ constexpr bool px_unsigned = std::is_same<P, uint8_t>::value || std::is_same<P, 
 template <class P, bool FLIP = false>
 __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *__restrict__ planes, const P *__restrict__ pix, PixGrid g, int L, int M, FloatFmt f)
 {
-	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
-	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
-	if (x >= g.W || y >= g.H)
+	int x, y;
+	if (!px_lane(g.W, g.H, x, y))
 		return;
 	const long npix = (long)g.W * g.H;
 	for (unsigned win = blockIdx.z; win < (unsigned)g.n; win += gridDim.z) {
@@ -3454,19 +3518,9 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels(int *
 		} else {
 			const P *p = row + (long)mx * g.col_step;
 			const int r = sample_in<P>(p[0], f, 0, L, M), gr = sample_in<P>(p[g.chan_stride], f, 1, L, M), b = sample_in<P>(p[2 * g.chan_stride], f, 2, L, M);
-			const int co = r - b;
-			const int t = b + tdiv2(co);
-			const int cg = gr - t;
-			dst[0] = t + tdiv2(cg);
-			dst[npix] = co;
-			dst[2 * npix] = cg;
+			planes_of_rgb(r, gr, b, dst, npix);
 		}
 	}
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi)
-{
-	return v < lo ? lo : v > hi ? hi : v;
 }
 
 // image.h:39-50 ycocg2rgb (input clamps included) + pnm.h:108 output clamp, with M (the pixels' maxval) where the
@@ -3487,32 +3541,15 @@ template <>
 __device__ __forceinline__ __bf16 sample_of<__bf16>(int v, const FloatFmt &f, int c) { return (__bf16)float_of(v, f.scale[c], f.bias[c]); }
 
 // One pixel of that arithmetic, which the general conversion below and the keys of a clip stack (k_clips_from_planes) share:
-// plain_gray is a gray sample's one clamp, plain_rgb the clamps of Y, Co and Cg, the inverse colour transform and pnm.h:108's
-// clamp of each output sample, R = M - L: Y, Co and Cg are read at src[0], src[step] and src[2 * step] (planes in memory, or a
-// lane's three registers with step 1), and out(c, sample) receives colour c = 0, 1, 2 (R, G, B), one after the other.
-__device__ __forceinline__ int plain_gray(int v, int L, int M) { return clampi(v, L, M); }
-template <class Out>
-__device__ __forceinline__ void plain_rgb(const int *src, long step, int R, int L, int M, Out &&out)
-{
-	const int yy = clampi(src[0], L, M);
-	const int co = clampi(src[step], -R, R);
-	const int cg = clampi(src[2 * step], -R, R);
-	const int t = yy - tdiv2(cg);
-	const int gr = cg + t;
-	const int b = t - tdiv2(co);
-	const int r = b + co;
-	out(0, clampi(r, L, M));
-	out(1, clampi(gr, L, M));
-	out(2, clampi(b, L, M));
-}
+// plain_gray is a gray sample's one clamp; an RGB pixel's is rgb_plain.
+__device__ __forceinline__ int plain_gray(int v, Clamp M) { return clamp_to(v, M.lo, M.hi); }
 
 template <class P, bool FLIP = false>
-__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, int L_, int M, FloatFmt f)
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, int L_, int M_, FloatFmt f)
 {
-	const int L = px_unsigned<P> ? 0 : L_, R = M - L;
-	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
-	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
-	if (x >= g.W || y >= g.H)
+	const Clamp M = { px_unsigned<P> ? 0 : L_, M_ };
+	int x, y;
+	if (!px_lane(g.W, g.H, x, y))
 		return;
 	const long npix = (long)g.W * g.H;
 	for (unsigned win = blockIdx.z; win < (unsigned)g.n; win += gridDim.z) {
@@ -3520,9 +3557,9 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__
 		P *row = FLIP ? flipped_row(pix, g, win, mx, y) : pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch;
 		const int *src = planes + (long)win * g.C * npix + (long)y * g.W + x;
 		if (g.C == 1) {
-			row[(long)mx * g.col_step] = sample_of<P>(plain_gray(src[0], L, M), f, 0);
+			row[(long)mx * g.col_step] = sample_of<P>(plain_gray(src[0], M), f, 0);
 		} else {
-			plain_rgb(src, npix, R, L, M, [&](int c, int v) {
+			rgb_plain(src, npix, M, [&](int c, int v) {
 				P *p = row + (long)mx * g.col_step;
 				p[c * g.chan_stride] = sample_of<P>(v, f, c);
 			});
@@ -3537,26 +3574,18 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes(P *__
 template <class P>
 __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels_delta(int *__restrict__ planes, const P *pix, PixGrid g, const P *base, PixGrid gb)
 {
-	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
-	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
-	if (x >= g.W || y >= g.H)
+	int x, y;
+	if (!px_lane(g.W, g.H, x, y))
 		return;
 	const long npix = (long)g.W * g.H;
 	for (unsigned win = blockIdx.z; win < (unsigned)g.n; win += gridDim.z) {
 		const P *p = pix + win_off(g.grid, g.image_stride, (int)win) + (long)y * g.row_pitch + (long)x * g.col_step;
 		const P *q = base + win_off(gb.grid, gb.image_stride, (int)win) + (long)y * gb.row_pitch + (long)x * gb.col_step;
 		int *dst = planes + (long)win * g.C * npix + (long)y * g.W + x;
-		if (g.C == 1) {
+		if (g.C == 1)
 			dst[0] = (int)p[0] - (int)q[0];
-		} else {
-			const int r = (int)p[0] - (int)q[0], gr = (int)p[g.chan_stride] - (int)q[gb.chan_stride], b = (int)p[2 * g.chan_stride] - (int)q[2 * gb.chan_stride];
-			const int co = r - b;
-			const int t = b + tdiv2(co);
-			const int cg = gr - t;
-			dst[0] = t + tdiv2(cg);
-			dst[npix] = co;
-			dst[2 * npix] = cg;
-		}
+		else
+			planes_of_rgb((int)p[0] - (int)q[0], (int)p[g.chan_stride] - (int)q[gb.chan_stride], (int)p[2 * g.chan_stride] - (int)q[2 * gb.chan_stride], dst, npix);
 	}
 }
 
@@ -3569,9 +3598,8 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels_delta
 template <class P>
 __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels_clips(int *__restrict__ planes, const P *__restrict__ pix, PixGrid g, unsigned at, unsigned period)
 {
-	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
-	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
-	if (x >= g.W || y >= g.H)
+	int x, y;
+	if (!px_lane(g.W, g.H, x, y))
 		return;
 	const long npix = (long)g.W * g.H;
 	const long in = (long)y * g.row_pitch + (long)x * g.col_step;
@@ -3587,17 +3615,10 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels_clips
 				q2 = (int)q[2 * g.chan_stride];
 			}
 		}
-		if (g.C == 1) {
+		if (g.C == 1)
 			dst[0] = (int)p[0] - q0;
-		} else {
-			const int r = (int)p[0] - q0, gr = (int)p[g.chan_stride] - q1, b = (int)p[2 * g.chan_stride] - q2;
-			const int co = r - b;
-			const int t = b + tdiv2(co);
-			const int cg = gr - t;
-			dst[0] = t + tdiv2(cg);
-			dst[npix] = co;
-			dst[2 * npix] = cg;
-		}
+		else
+			planes_of_rgb((int)p[0] - q0, (int)p[g.chan_stride] - q1, (int)p[2 * g.chan_stride] - q2, dst, npix);
 	}
 }
 
@@ -3606,12 +3627,11 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_planes_from_pixels_clips
 // inside an int.  Every sample is read (base) and written (pix) by the same lane, the read first: the two views may be the
 // same memory (the in-place decode); the host refuses every other overlap.  Neither pointer is __restrict__ for that.
 template <class P>
-__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes_delta(P *pix, const int *__restrict__ planes, PixGrid g, const P *base, PixGrid gb, int L, int M)
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes_delta(P *pix, const int *__restrict__ planes, PixGrid g, const P *base, PixGrid gb, int L, int M_)
 {
-	const int R = M - L;
-	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
-	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
-	if (x >= g.W || y >= g.H)
+	const Clamp M = { L, M_ };
+	int x, y;
+	if (!px_lane(g.W, g.H, x, y))
 		return;
 	const long npix = (long)g.W * g.H;
 	for (unsigned win = blockIdx.z; win < (unsigned)g.n; win += gridDim.z) {
@@ -3620,19 +3640,13 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes_delta
 		const int *src = planes + (long)win * g.C * npix + (long)y * g.W + x;
 		if (g.C == 1) {
 			const int b0 = (int)q[0];
-			p[0] = (P)clampi(b0 + clampi(src[0], -R, R), L, M);
+			p[0] = (P)delta_sample(src[0], b0, M);
 		} else {
-			const int b0 = (int)q[0], b1 = (int)q[gb.chan_stride], b2 = (int)q[2 * gb.chan_stride];
-			const int yy = clampi(src[0], -R, R);
-			const int co = clampi(src[npix], -2 * R, 2 * R);
-			const int cg = clampi(src[2 * npix], -2 * R, 2 * R);
-			const int t = yy - tdiv2(cg);
-			const int gr = cg + t;
-			const int b = t - tdiv2(co);
-			const int r = b + co;
-			p[0] = (P)clampi(b0 + clampi(r, -R, R), L, M);
-			p[g.chan_stride] = (P)clampi(b1 + clampi(gr, -R, R), L, M);
-			p[2 * g.chan_stride] = (P)clampi(b2 + clampi(b, -R, R), L, M);
+			int r = (int)q[0], gr = (int)q[gb.chan_stride], b = (int)q[2 * gb.chan_stride];
+			rgb_residual(src, npix, M, r, gr, b);
+			p[0] = (P)r;
+			p[g.chan_stride] = (P)gr;
+			p[2 * g.chan_stride] = (P)b;
 		}
 	}
 }
@@ -3645,7 +3659,7 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_pixels_from_planes_delta
 // only dependence is that register: the plane samples of the next CHAIN_AHEAD pictures are loaded before the current one's
 // arithmetic and store run (a batch of loads, one wait, then the batch's serial adds), so that the walk waits on memory once a
 // batch and not once a picture.  The host guarantees that the base window is disjoint from the written ones (codec.hip,
-// chain_view, and decode_device's ordering argument): planes, pixels and base are __restrict__.
+// chain_disjoint, and decode_device's ordering argument): planes, pixels and base are __restrict__.
 constexpr int CHAIN_AHEAD = 4;
 struct ChainRaw {
 	int v[3];
@@ -3661,39 +3675,42 @@ __device__ __forceinline__ ChainRaw chain_load(const int *__restrict__ src, long
 	}
 	return r;
 }
-// one link: the residual's clamps, the YCoCg-R inverse, the clamp of d, the sum's clamp — b[] in, b[] out
-template <int C>
-__device__ __forceinline__ void chain_link(const ChainRaw &r, int (&b)[3], int R, int L, int M)
+// the first sample of pixel (x, y) of window `win` of a view
+template <class P>
+__device__ __forceinline__ P *pixel_at(P *pix, const PixGrid &g, int win, int x, int y)
 {
-	if (C == 1) {
-		b[0] = clampi(b[0] + clampi(r.v[0], -R, R), L, M);
-	} else {
-		const int yy = clampi(r.v[0], -R, R);
-		const int co = clampi(r.v[1], -2 * R, 2 * R);
-		const int cg = clampi(r.v[2], -2 * R, 2 * R);
-		const int t = yy - tdiv2(cg);
-		const int gr = cg + t;
-		const int bl = t - tdiv2(co);
-		const int rd = bl + co;
-		b[0] = clampi(b[0] + clampi(rd, -R, R), L, M);
-		b[1] = clampi(b[1] + clampi(gr, -R, R), L, M);
-		b[2] = clampi(b[2] + clampi(bl, -R, R), L, M);
-	}
+	return pix + win_off(g.grid, g.image_stride, win) + (long)y * g.row_pitch + (long)x * g.col_step;
 }
-template <class P, int C>
-__device__ __forceinline__ void chain_walk(P *__restrict__ pix, const int *__restrict__ planes, const PixGrid &g, const P *__restrict__ base, const PixGrid &gb,
-	int L, int M, int x, int y)
+// one link: delta_sample, or rgb_residual, onto the running sample — b[] in, b[] out
+template <int C>
+__device__ __forceinline__ void chain_link(const ChainRaw &r, int (&b)[3], Clamp M)
 {
-	const int R = M - L;
+	if (C == 1)
+		b[0] = delta_sample(r.v[0], b[0], M);
+	else
+		rgb_residual(r.v, 1, M, b[0], b[1], b[2]);
+}
+// The walk of both kernels below: pictures win0 .. win0 + n of the view behind g, their planes from `planes` on, at the lane's
+// pixel (x, y).  How the running sample starts is the caller's: `keyed`, and the first picture is a key — its own plain
+// conversion, nothing read (q is not looked at) — or the first picture is a link onto the base sample at q, whose G and B are
+// qstep and 2 * qstep samples on.  Every later picture is a link onto the one before it.  Keyed is bool where the answer is the
+// wave's (a scalar branch), and std::false_type where a caller has no keys: then the key's code is not compiled at all (behind a
+// bool that is false the chain kernel's loop came out peeled, twice the code and three SGPRs more).  That caller also forms q
+// once per instance of the walk, inside its branch on C, not once before it (two VGPRs).
+template <class P, int C, class Keyed>
+__device__ __forceinline__ void chain_walk(P *__restrict__ pix, const int *__restrict__ planes, const PixGrid &g, const P *__restrict__ q, long qstep, Keyed keyed,
+	Clamp M, int x, int y, int win0, int n)
+{
 	const long npix = (long)g.W * g.H;
 	const long wstep = (long)C * npix;   // from a picture's planes to the next one's
 	const long at = (long)y * g.row_pitch + (long)x * g.col_step;
-	const P *q = base + win_off(gb.grid, gb.image_stride, 0) + (long)y * gb.row_pitch + (long)x * gb.col_step;
-	int b[3];
-	b[0] = (int)q[0];
-	if (C == 3) {
-		b[1] = (int)q[gb.chan_stride];
-		b[2] = (int)q[2 * gb.chan_stride];
+	int b[3] = { 0, 0, 0 };
+	if (!keyed) {
+		b[0] = (int)q[0];
+		if (C == 3) {
+			b[1] = (int)q[qstep];
+			b[2] = (int)q[2 * qstep];
+		}
 	}
 	const int *src = planes + (long)y * g.W + x;
 	auto store = [&](int win) {
@@ -3704,10 +3721,9 @@ __device__ __forceinline__ void chain_walk(P *__restrict__ pix, const int *__res
 			p[2 * g.chan_stride] = (P)b[2];
 		}
 	};
-	const int n = g.n;
 	ChainRaw nxt[CHAIN_AHEAD], cur[CHAIN_AHEAD];
 #pragma unroll
-	for (int k = 0; k < CHAIN_AHEAD; ++k)   // (a picture past the group's end: the last one's planes once more, never used)
+	for (int k = 0; k < CHAIN_AHEAD; ++k)   // (a picture past the walk's end: the last one's planes once more, never used)
 		nxt[k] = chain_load<C>(src + (long)min(k, n - 1) * wstep, npix);
 	for (int w0 = 0; w0 < n; w0 += CHAIN_AHEAD) {
 #pragma unroll
@@ -3722,8 +3738,14 @@ __device__ __forceinline__ void chain_walk(P *__restrict__ pix, const int *__res
 #pragma unroll
 		for (int k = 0; k < CHAIN_AHEAD; ++k)
 			if (w0 + k < n) {
-				chain_link<C>(cur[k], b, R, L, M);
-				store(w0 + k);
+				if (keyed && k == 0 && w0 == 0) {   // the key: its own picture, no base
+					if (C == 3)
+						rgb_plain(cur[k].v, 1, M, [&](int c, int v) { b[c] = v; });
+					else
+						b[0] = plain_gray(cur[k].v[0], M);
+				} else
+					chain_link<C>(cur[k], b, M);
+				store(win0 + w0 + k);
 			}
 	}
 }
@@ -3731,21 +3753,20 @@ template <class P>
 __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_chain_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, const P *__restrict__ base,
 	PixGrid gb, int L, int M)
 {
-	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
-	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
-	if (x >= g.W || y >= g.H)
+	int x, y;
+	if (!px_lane(g.W, g.H, x, y))
 		return;
 	if (g.C == 1)
-		chain_walk<P, 1>(pix, planes, g, base, gb, L, M, x, y);
+		chain_walk<P, 1>(pix, planes, g, pixel_at(base, gb, 0, x, y), gb.chan_stride, std::false_type(), Clamp{ L, M }, x, y, 0, g.n);
 	else
-		chain_walk<P, 3>(pix, planes, g, base, gb, L, M, x, y);
+		chain_walk<P, 3>(pix, planes, g, pixel_at(base, gb, 0, x, y), gb.chan_stride, std::false_type(), Clamp{ L, M }, x, y, 0, g.n);
 }
 
 // The conversion of a clip stack (dwtx_decode_view_clips; dwtx_pixels::clips): windows first .. first + g.n of ONE view, window i of
-// the stack a key where i % period == 0 — its samples the plain conversion of its planes, plain_gray / plain_rgb, exactly k_pixels_from_planes'
+// the stack a key where i % period == 0 — its samples the plain conversion of its planes, plain_gray / rgb_plain, exactly k_pixels_from_planes'
 // arithmetic for the sample type — and a link otherwise: chain_link onto the window before it, unchanged.  grid: (64 pixels of a
 // row, 4 rows, SEGMENT): a segment is a maximal run of the group's windows with no key but possibly at its start, and the launch
-// walks all of them side by side, each as k_chain_from_planes walks its chain — a lane owns one pixel position, the running sample
+// walks all of them side by side, each with the walk k_chain_from_planes has (chain_walk) — a lane owns one pixel position, the running sample
 // stays in a register, CHAIN_AHEAD pictures' plane loads are in flight ahead of a batch's arithmetic and stores.  Where segment z
 // begins and ends follows from first, the count and the period alone: with lead = the windows before the group's first key,
 // segment z covers [s, s + period) cut to the group, s = lead + (z - (lead != 0)) * period — blockIdx.z and kernel arguments only,
@@ -3755,68 +3776,13 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_chain_from_planes(P *__r
 // first - 1, lies before every window of the group, and the launch writes windows first .. first + g.n only (a lane writes each
 // position once).  The host's ordering argument (codec.hip, decode_device) has window first - 1 in memory: planes, pixels and
 // base are __restrict__.  g is the WHOLE view's grid (windows counted from the stack's first), g.n the group's count.
-template <class P, int C>
-__device__ __forceinline__ void clips_walk(P *__restrict__ pix, const int *__restrict__ planes, const PixGrid &g, const P *__restrict__ base, int L, int M, int x, int y,
-	int win0, int n, bool keyed)
-{
-	const int R = M - L;
-	const long npix = (long)g.W * g.H;
-	const long wstep = (long)C * npix;   // from a picture's planes to the next one's
-	const long at = (long)y * g.row_pitch + (long)x * g.col_step;
-	int b[3] = { 0, 0, 0 };
-	if (!keyed) {   // (the wave's: a scalar branch)
-		const P *q = base + win_off(g.grid, g.image_stride, win0 - 1) + at;
-		b[0] = (int)q[0];
-		if (C == 3) {
-			b[1] = (int)q[g.chan_stride];
-			b[2] = (int)q[2 * g.chan_stride];
-		}
-	}
-	const int *src = planes + (long)y * g.W + x;
-	auto store = [&](int win) {
-		P *p = pix + win_off(g.grid, g.image_stride, win) + at;
-		p[0] = (P)b[0];
-		if (C == 3) {
-			p[g.chan_stride] = (P)b[1];
-			p[2 * g.chan_stride] = (P)b[2];
-		}
-	};
-	ChainRaw nxt[CHAIN_AHEAD], cur[CHAIN_AHEAD];
-#pragma unroll
-	for (int k = 0; k < CHAIN_AHEAD; ++k)   // (a picture past the segment's end: the last one's planes once more, never used)
-		nxt[k] = chain_load<C>(src + (long)min(k, n - 1) * wstep, npix);
-	for (int w0 = 0; w0 < n; w0 += CHAIN_AHEAD) {
-#pragma unroll
-		for (int k = 0; k < CHAIN_AHEAD; ++k)   // the one wait of the iteration
-			for (int c = 0; c < C; ++c)
-				cur[k].v[c] = hold(nxt[k].v[c]);
-		if (w0 + CHAIN_AHEAD < n) {   // the next batch's loads go out before this batch's arithmetic and stores
-#pragma unroll
-			for (int k = 0; k < CHAIN_AHEAD; ++k)
-				nxt[k] = chain_load<C>(src + (long)min(w0 + CHAIN_AHEAD + k, n - 1) * wstep, npix);
-		}
-#pragma unroll
-		for (int k = 0; k < CHAIN_AHEAD; ++k)
-			if (w0 + k < n) {
-				if (k == 0 && w0 == 0 && keyed) {   // the segment's key: its own picture, no base
-					if (C == 3)
-						plain_rgb(cur[k].v, 1, R, L, M, [&](int c, int v) { b[c] = v; });
-					else
-						b[0] = plain_gray(cur[k].v[0], L, M);
-				} else
-					chain_link<C>(cur[k], b, R, L, M);
-				store(win0 + w0 + k);
-			}
-	}
-}
 template <class P>
 __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_clips_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, const P *__restrict__ base,
-	int first, int period, int L_, int M)
+	int first, int period, int L_, int M_)
 {
-	const int L = px_unsigned<P> ? 0 : L_;
-	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
-	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
-	if (x >= g.W || y >= g.H)
+	const Clamp M = { px_unsigned<P> ? 0 : L_, M_ };
+	int x, y;
+	if (!px_lane(g.W, g.H, x, y))
 		return;
 	// segment blockIdx.z of the group, in windows of the group: [r0, r1)
 	const int phase = first % period, lead = phase ? period - phase : 0;
@@ -3825,10 +3791,14 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_clips_from_planes(P *__r
 	if (r0 >= r1)   // (never: the host launches the group's segments and no more)
 		return;
 	const int *seg = planes + (long)r0 * g.C * g.W * g.H;
+	const bool keyed = s >= 0;   // (the wave's)
+	const P *q = base;
+	if (!keyed)   // the one segment that starts mid-clip: a link onto window first - 1 as it lies in memory
+		q = pixel_at(base, g, first + r0 - 1, x, y);
 	if (g.C == 1)
-		clips_walk<P, 1>(pix, seg, g, base, L, M, x, y, first + r0, r1 - r0, s >= 0);
+		chain_walk<P, 1>(pix, seg, g, q, g.chan_stride, keyed, M, x, y, first + r0, r1 - r0);
 	else
-		clips_walk<P, 3>(pix, seg, g, base, L, M, x, y, first + r0, r1 - r0, s >= 0);
+		chain_walk<P, 3>(pix, seg, g, q, g.chan_stride, keyed, M, x, y, first + r0, r1 - r0);
 }
 
 // Integer-only synthetic frames: seed = frame index, so every box
@@ -3937,32 +3907,54 @@ static FloatFmt float_fmt(const dwtx_pixels &px)
 	return f;
 }
 
-// the conversions' launches for samples of type P: the FLIP instance for a flipped call's windows, else the plain one
+// The one place a view's sample kind (dwtx_pixels::kind) becomes the kernels' sample type: call(SampleType<P>()) with the kind's P,
+// once, -> DWTX_OK; or nothing is called -> DWTX_ERR_ARG: a kind that is none, or a float kind where the caller admits
+// INT_SAMPLES only (the delta, chain and clips conversions, which have integer instances and no others: `call` is not
+// compiled for a float type there).
 template <class P>
-static void launch_planes_from_pixels(dwtx_ctx *ctx, dim3 grid, int32_t *planes, const dwtx_pixels &px, const PixGrid &g, const FloatFmt &f)
+struct SampleType {
+	typedef P type;
+};
+enum SampleKinds { INT_SAMPLES, ANY_SAMPLES };
+template <SampleKinds ADMITS, class F>
+static int with_sample_type(int kind, F &&call)
 {
-	const auto kernel = px.flips ? k_planes_from_pixels<P, true> : k_planes_from_pixels<P, false>;
-	hipLaunchKernelGGL(kernel, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, static_cast<const P *>(px.red()), g, px.minval, px.maxval, f);
+	switch (kind) {
+	case DWTX_SAMPLE_U8:
+		call(SampleType<uint8_t>());
+		return DWTX_OK;
+	case DWTX_SAMPLE_U16:
+		call(SampleType<uint16_t>());
+		return DWTX_OK;
+	case DWTX_SAMPLE_S16:
+		call(SampleType<int16_t>());
+		return DWTX_OK;
+	}
+	if constexpr (ADMITS == ANY_SAMPLES)
+		switch (kind) {
+		case DWTX_SAMPLE_F32:
+			call(SampleType<float>());
+			return DWTX_OK;
+		case DWTX_SAMPLE_F16:
+			call(SampleType<_Float16>());
+			return DWTX_OK;
+		case DWTX_SAMPLE_BF16:
+			call(SampleType<__bf16>());
+			return DWTX_OK;
+		}
+	return DWTX_ERR_ARG;
 }
-template <class P>
-static void launch_pixels_from_planes(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const int32_t *planes, const PixGrid &g, const FloatFmt &f)
+
+// what the two general entry points ask of their arguments before anything else
+static bool conversion_args_ok(const dwtx_ctx *ctx, const int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
 {
-	const auto kernel = px.flips ? k_pixels_from_planes<P, true> : k_pixels_from_planes<P, false>;
-	hipLaunchKernelGGL(kernel, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), planes, g, px.minval, px.maxval, f);
+	const int C = px.channels;
+	if (!ctx || !planes || !px.base || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || !px.sample_aligned())
+		return false;
+	return !px.flips || (px.offs && W <= px.flip_w && H <= px.flip_h);   // (a picture is mirrored inside its window: the mirrored index stays in it)
 }
 
 // a delta view's conversions (dwtx_pixels::delta): to_planes, or from_planes — integer samples on a grid, nothing flipped or listed
-template <class P>
-static void launch_delta_of(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const PixGrid &g, const dwtx_pixels &bp, const PixGrid &gb, int32_t *to_planes,
-	const int32_t *from_planes)
-{
-	if (to_planes)
-		hipLaunchKernelGGL(k_planes_from_pixels_delta<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, to_planes, static_cast<const P *>(px.red()), g,
-			static_cast<const P *>(bp.red()), gb);
-	else
-		hipLaunchKernelGGL(k_pixels_from_planes_delta<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), from_planes, g,
-			static_cast<const P *>(bp.red()), gb, px.minval, px.maxval);
-}
 static int launch_delta(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const PixGrid &g, int W, int H, int n, int32_t *to_planes, const int32_t *from_planes)
 {
 	if (px.chain || px.clips || px.is_float() || px.flips || px.listed() || !px.base_pixels().sample_aligned())   // (a chain and a clip stack have conversions of their own, below)
@@ -3970,25 +3962,15 @@ static int launch_delta(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const P
 	const dwtx_pixels bp = px.base_pixels();
 	dim3 same;
 	const PixGrid gb = pix_grid(bp, W, H, n, &same);
-	switch (px.kind) {
-	case DWTX_SAMPLE_U8:
-		launch_delta_of<uint8_t>(ctx, grid, px, g, bp, gb, to_planes, from_planes);
-		break;
-	case DWTX_SAMPLE_U16:
-		launch_delta_of<uint16_t>(ctx, grid, px, g, bp, gb, to_planes, from_planes);
-		break;
-	default:
-		launch_delta_of<int16_t>(ctx, grid, px, g, bp, gb, to_planes, from_planes);
-		break;
-	}
-	return DWTX_OK;
-}
-
-template <class P>
-static void launch_chain_of(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const PixGrid &g, const dwtx_pixels &bp, const PixGrid &gb, const int32_t *planes)
-{
-	hipLaunchKernelGGL(k_chain_from_planes<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), planes, g,
-		static_cast<const P *>(bp.red()), gb, px.minval, px.maxval);
+	return with_sample_type<INT_SAMPLES>(px.kind, [&](auto t) {
+		using P = typename decltype(t)::type;
+		if (to_planes)
+			hipLaunchKernelGGL(k_planes_from_pixels_delta<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, to_planes, static_cast<const P *>(px.red()), g,
+				static_cast<const P *>(bp.red()), gb);
+		else
+			hipLaunchKernelGGL(k_pixels_from_planes_delta<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), from_planes, g,
+				static_cast<const P *>(bp.red()), gb, px.minval, px.maxval);
+	});
 }
 
 int dwtx_planes_to_pixels_chain(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int first, int count)
@@ -4009,35 +3991,18 @@ int dwtx_planes_to_pixels_chain(dwtx_ctx *ctx, const dwtx_pixels &px, const int3
 	const PixGrid g = pix_grid(dst, W, H, count, &grid);
 	const PixGrid gb = pix_grid(bp, W, H, 1, &one);
 	grid.z = 1;   // (the pictures of a chain are walked in order by each lane)
-	switch (px.kind) {
-	case DWTX_SAMPLE_U8:
-		launch_chain_of<uint8_t>(ctx, grid, dst, g, bp, gb, planes);
-		break;
-	case DWTX_SAMPLE_U16:
-		launch_chain_of<uint16_t>(ctx, grid, dst, g, bp, gb, planes);
-		break;
-	default:
-		launch_chain_of<int16_t>(ctx, grid, dst, g, bp, gb, planes);
-		break;
-	}
+	const int rc = with_sample_type<INT_SAMPLES>(px.kind, [&](auto t) {
+		using P = typename decltype(t)::type;
+		hipLaunchKernelGGL(k_chain_from_planes<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(dst.red()), planes, g,
+			static_cast<const P *>(bp.red()), gb, dst.minval, dst.maxval);
+	});
+	if (rc)
+		return rc;
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
 
-// A clip stack's conversions (dwtx_pixels::clips): the view's own grid is the base pictures' too
-template <class P>
-static void launch_clips_fwd(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const PixGrid &g, int32_t *planes)
-{
-	hipLaunchKernelGGL(k_planes_from_pixels_clips<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, static_cast<const P *>(px.red()), g,
-		(unsigned)(px.clip_at % (size_t)px.clips), (unsigned)px.clips);
-}
-template <class P>
-static void launch_clips_inv(dwtx_ctx *ctx, dim3 grid, const dwtx_pixels &px, const PixGrid &g, const int32_t *planes, int first)
-{
-	hipLaunchKernelGGL(k_clips_from_planes<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), planes, g,
-		static_cast<const P *>(px.red()), first, px.clips, px.minval, px.maxval);
-}
-
+// A clip stack's conversion back (dwtx_pixels::clips): the view's own grid is the base pictures' too
 int dwtx_planes_to_pixels_clips(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int first, int count)
 {
 	const int C = px.channels;
@@ -4051,124 +4016,75 @@ int dwtx_planes_to_pixels_clips(dwtx_ctx *ctx, const dwtx_pixels &px, const int3
 	// the group's segments: the run before its first key, if it starts mid-clip, and one per key
 	const int phase = first % px.clips, lead = phase ? px.clips - phase : 0;
 	grid.z = lead >= count ? 1u : (unsigned)((lead ? 1 : 0) + dwtx_cdiv(count - lead, px.clips));
-	switch (px.kind) {
-	case DWTX_SAMPLE_U8:
-		launch_clips_inv<uint8_t>(ctx, grid, px, g, planes, first);
-		break;
-	case DWTX_SAMPLE_U16:
-		launch_clips_inv<uint16_t>(ctx, grid, px, g, planes, first);
-		break;
-	default:
-		launch_clips_inv<int16_t>(ctx, grid, px, g, planes, first);
-		break;
-	}
+	const int rc = with_sample_type<INT_SAMPLES>(px.kind, [&](auto t) {
+		using P = typename decltype(t)::type;
+		hipLaunchKernelGGL(k_clips_from_planes<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), planes, g,
+			static_cast<const P *>(px.red()), first, px.clips, px.minval, px.maxval);
+	});
+	if (rc)
+		return rc;
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
 
+// The general conversions: a clip stack's and a delta view's have kernels of their own (integer samples), every other view takes
+// the instance for its sample type — the FLIP one for a flipped call's windows.
 int dwtx_pixels_to_planes(dwtx_ctx *ctx, int32_t *planes, const dwtx_pixels &px, int W, int H, int n)
 {
-	const int C = px.channels;
-	if (!ctx || !planes || !px.base || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || !px.sample_aligned())
+	if (!conversion_args_ok(ctx, planes, px, W, H, n))
 		return DWTX_ERR_ARG;
 	if (px.is_float() && !px.range_ok())   // (the quantiser's clamp; integer sources have no use for a maxval)
-		return DWTX_ERR_ARG;
-	if (px.flips && (!px.offs || W > px.flip_w || H > px.flip_h))   // (a picture is mirrored inside its window: the mirrored index stays in it)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	dim3 grid;
 	const PixGrid g = pix_grid(px, W, H, n, &grid);
 	const FloatFmt f = float_fmt(px);
-	if (px.clips) {   // (before the delta views: a clip stack has no second grid)
+	int rc;
+	if (px.clips) {   // (before the delta views: a clip stack has no second grid, the view's own is the base pictures' too)
 		if (px.chain || px.delta.base || px.is_float() || px.flips || px.listed())
 			return DWTX_ERR_ARG;
-		switch (px.kind) {
-		case DWTX_SAMPLE_U8:
-			launch_clips_fwd<uint8_t>(ctx, grid, px, g, planes);
-			break;
-		case DWTX_SAMPLE_U16:
-			launch_clips_fwd<uint16_t>(ctx, grid, px, g, planes);
-			break;
-		default:
-			launch_clips_fwd<int16_t>(ctx, grid, px, g, planes);
-			break;
-		}
-		DWTX_LAUNCH_CHECK();
-		return DWTX_OK;
+		rc = with_sample_type<INT_SAMPLES>(px.kind, [&](auto t) {
+			using P = typename decltype(t)::type;
+			hipLaunchKernelGGL(k_planes_from_pixels_clips<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, static_cast<const P *>(px.red()), g,
+				(unsigned)(px.clip_at % (size_t)px.clips), (unsigned)px.clips);
+		});
+	} else if (px.is_delta()) {
+		rc = launch_delta(ctx, grid, px, g, W, H, n, planes, nullptr);
+	} else {
+		rc = with_sample_type<ANY_SAMPLES>(px.kind, [&](auto t) {
+			using P = typename decltype(t)::type;
+			const auto kernel = px.flips ? k_planes_from_pixels<P, true> : k_planes_from_pixels<P, false>;
+			hipLaunchKernelGGL(kernel, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, planes, static_cast<const P *>(px.red()), g, px.minval, px.maxval, f);
+		});
 	}
-	if (px.is_delta()) {
-		if (const int rc = launch_delta(ctx, grid, px, g, W, H, n, planes, nullptr))
-			return rc;
-		DWTX_LAUNCH_CHECK();
-		return DWTX_OK;
-	}
-	switch (px.kind) {
-	case DWTX_SAMPLE_U8:
-		launch_planes_from_pixels<uint8_t>(ctx, grid, planes, px, g, f);
-		break;
-	case DWTX_SAMPLE_U16:
-		launch_planes_from_pixels<uint16_t>(ctx, grid, planes, px, g, f);
-		break;
-	case DWTX_SAMPLE_S16:
-		launch_planes_from_pixels<int16_t>(ctx, grid, planes, px, g, f);
-		break;
-	case DWTX_SAMPLE_F32:
-		launch_planes_from_pixels<float>(ctx, grid, planes, px, g, f);
-		break;
-	case DWTX_SAMPLE_F16:
-		launch_planes_from_pixels<_Float16>(ctx, grid, planes, px, g, f);
-		break;
-	case DWTX_SAMPLE_BF16:
-		launch_planes_from_pixels<__bf16>(ctx, grid, planes, px, g, f);
-		break;
-	default:
-		return DWTX_ERR_ARG;
-	}
+	if (rc)
+		return rc;
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
 
 int dwtx_planes_to_pixels(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int n)
 {
-	const int C = px.channels;
-	if (!ctx || !planes || !px.base || W < 1 || H < 1 || (C != 1 && C != 3) || n < 1 || !px.sample_aligned())
+	if (!conversion_args_ok(ctx, planes, px, W, H, n))
 		return DWTX_ERR_ARG;
 	if (!px.range_ok())
-		return DWTX_ERR_ARG;
-	if (px.flips && (!px.offs || W > px.flip_w || H > px.flip_h))   // (a picture is mirrored inside its window: the mirrored index stays in it)
 		return DWTX_ERR_ARG;
 	DWTX_ENTER(ctx);
 	dim3 grid;
 	const PixGrid g = pix_grid(px, W, H, n, &grid);
 	const FloatFmt f = float_fmt(px);
+	int rc;
 	if (px.is_delta()) {
-		if (const int rc = launch_delta(ctx, grid, px, g, W, H, n, nullptr, planes))
-			return rc;
-		DWTX_LAUNCH_CHECK();
-		return DWTX_OK;
+		rc = launch_delta(ctx, grid, px, g, W, H, n, nullptr, planes);
+	} else {
+		rc = with_sample_type<ANY_SAMPLES>(px.kind, [&](auto t) {
+			using P = typename decltype(t)::type;
+			const auto kernel = px.flips ? k_pixels_from_planes<P, true> : k_pixels_from_planes<P, false>;
+			hipLaunchKernelGGL(kernel, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), planes, g, px.minval, px.maxval, f);
+		});
 	}
-	switch (px.kind) {
-	case DWTX_SAMPLE_U8:
-		launch_pixels_from_planes<uint8_t>(ctx, grid, px, planes, g, f);
-		break;
-	case DWTX_SAMPLE_U16:
-		launch_pixels_from_planes<uint16_t>(ctx, grid, px, planes, g, f);
-		break;
-	case DWTX_SAMPLE_S16:
-		launch_pixels_from_planes<int16_t>(ctx, grid, px, planes, g, f);
-		break;
-	case DWTX_SAMPLE_F32:
-		launch_pixels_from_planes<float>(ctx, grid, px, planes, g, f);
-		break;
-	case DWTX_SAMPLE_F16:
-		launch_pixels_from_planes<_Float16>(ctx, grid, px, planes, g, f);
-		break;
-	case DWTX_SAMPLE_BF16:
-		launch_pixels_from_planes<__bf16>(ctx, grid, px, planes, g, f);
-		break;
-	default:
-		return DWTX_ERR_ARG;
-	}
+	if (rc)
+		return rc;
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }
@@ -5062,15 +4978,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_inv_level_roi(RoiArgs a)
 __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_crop_planes(int *__restrict__ dst, const int *__restrict__ src, int w, int h, int cw, int ch, int C,
 	const int2 *__restrict__ org, int x0, int y0)
 {
-	const int x = blockIdx.x * PX_LANES + (threadIdx.x & (PX_LANES - 1));
-	const int y = blockIdx.y * PX_ROWS + (threadIdx.x / PX_LANES);
 	const int plane = blockIdx.z;
 	if (org) {
 		const int2 o = org[C == 3 ? plane / 3 : plane];
 		x0 = __builtin_amdgcn_readfirstlane(o.x);
 		y0 = __builtin_amdgcn_readfirstlane(o.y);
 	}
-	if (x >= cw || y >= ch || x0 + x >= w || y0 + y >= h)
+	int x, y;
+	if (!px_lane(cw, ch, x, y) || x0 + x >= w || y0 + y >= h)
 		return;
 	dst[(long)plane * cw * ch + (long)y * cw + x] = src[(long)plane * w * h + (long)(y0 + y) * w + x0 + x];
 }
