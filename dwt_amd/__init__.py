@@ -236,6 +236,44 @@ def view_clips_check(fields, pointer, period, sample_bytes=1, signed=False, minv
     return rc, (lib.dwtx_last_error().decode(errors="replace") if rc else "")
 
 
+def clip_origins(origins, n, period):
+    """The `origins` keyword of decode_view_clips_crop -> the list of ceil(n / period) (x0, y0) pairs, one per CLIP, or None for
+    all (0, 0): one pair for every clip, or a sequence of one pair per clip.  A wrong number of pairs is a ValueError."""
+    nclips = -(-int(n) // int(period))
+    if origins is None:
+        return None
+    flat = [int(c) for c in origins] if len(origins) == 2 and not hasattr(origins[0], "__len__") else None
+    pairs = [tuple(flat)] * nclips if flat is not None else [(int(x), int(y)) for x, y in origins]
+    if len(pairs) != nclips:
+        raise ValueError(f"origins: one (x0, y0) pair or one per clip ({nclips} clips of period {period} in {n} windows), not {len(pairs)}")
+    return pairs
+
+
+def view_clips_crop_check(fields, pointer, period, size, origins=None, sample_bytes=1, signed=False, minval=0, maxval=None, fmt=None):
+    """dwtx_view_clips_crop_check: what decode_view_clips_crop says to a grid view of crop-sized windows (fields: its view_fields
+    dict, whose W and H are the crop's; None: a NULL view), streams of geometry size=(W, H), origins (a flat or nested sequence of
+    one pair per clip, passed as it is; None: NULL) and fmt (a FloatFormat, or None for integer samples) -> (rc, text): (0, "") for
+    a call it takes, else the error code and the text of the refusal, which starts "clips view:".  pointer: the view's first
+    sample's address as a plain integer, never dereferenced.  Host arithmetic only: needs no device."""
+    lib = _lib.load()
+    if maxval is None:
+        maxval = 255 if sample_bytes == 1 or fmt is not None else 32767 if signed else 65535
+    W, H = (int(v) for v in size)
+    org = None
+    if origins is not None:
+        flat = [int(c) for p in origins for c in (p if hasattr(p, "__len__") else (p,))]
+        org = (C.c_int * max(len(flat), 1))(*flat)
+    pf = C.byref(fmt) if fmt is not None else None
+    if fields is None:
+        rc = lib.dwtx_view_clips_crop_check(None, 0, int(period), 1 if signed else 0, int(minval), pf, W, H, 1, W, H, org)
+    else:
+        v = View(pointer or None, sample_bytes, fields["channels"], maxval, fields["cols"], fields["row_pitch"], fields["image_stride"],
+                 fields["band_stride"], fields["channel_stride"])
+        rc = lib.dwtx_view_clips_crop_check(C.byref(v), fields["pixel_step"], int(period), 1 if signed else 0, int(minval), pf, W, H,
+                                            fields["n"], fields["W"], fields["H"], org)
+    return rc, (lib.dwtx_last_error().decode(errors="replace") if rc else "")
+
+
 FLIPS = {"": 0, "x": 1, "y": 2, "xy": 3, "yx": 3}   # enum DWTX_FLIP_X = 1, DWTX_FLIP_Y = 2 (include/dwtx.h): a mask
 
 
@@ -830,7 +868,9 @@ class Context:
         view = (levels_max, C.byref(v), step or 0, order)
         pf = C.byref(fmt) if fmt is not None else None
         window = (pf,) + (crop or (W, H, None))
-        if clips is not None:
+        if clips is not None and crop is not None:   # (its origins: one pair per clip)
+            sym, args = "dwtx_decode_view_clips_crop", view[1:3] + (clips[0], order, clips[1], clips[2]) + window
+        elif clips is not None:
             sym, args = "dwtx_decode_view_clips", view[1:3] + (clips[0], order, clips[1], clips[2])
         elif pair is not None:
             sym, args = pair[0], view[1:3] + (C.byref(pair[1]), pair[2], order, pair[3], pair[4])
@@ -1040,6 +1080,48 @@ class Context:
         v, W, H, Cn, n, step, period = self._clips_view(into, period, maxval, stepped, signed, unsupported)
         return self._decode_views(streams, lens, v, step, order, None, None, None, None, None, W, H, n, -1,
                                   clips=(period, 1 if signed else 0, lo if signed else 0))
+
+    _NOT_IN_CLIPS_CROP = {"flip": "the clips calls take no flips", "levels_max": "the clips calls write whole pictures only",
+                          "base": "a link's base is the picture before it, inside the stack",
+                          "key": "the keys lie inside the stack: a key outside it is decode_view_chain",
+                          "windows": "the clips calls take no window lists", "crop": "the crop's size is that of `into`'s windows"}
+
+    def decode_view_clips_crop(self, streams, lens, into, period, size, origins=None, maxval=None, scale=None, bias=None, stepped=False,
+                               order="rgb", signed=False, minval=None, **unsupported):
+        """dwtx_decode_view_clips_crop: decode_view_clips of a window of each CLIP, and — when `into` is a float32 / float16 /
+        bfloat16 tensor — with every sample written as `v * scale + bias` (decode_view_float's two float32 roundings, then the
+        dtype): a loader's random crop per clip and its conversion inside the decode.  `into` holds windows of the crop's size
+        ([n,ch,cw,C] or [bands,cols,ch,cw,C], any strides decode_view takes), size=(W, H) is the streams' geometry, origins one
+        (x0, y0) pair per clip (ceil(n / period) of them), one pair for all, or None for (0, 0): every window of a clip is cut at
+        its clip's origin.  Integer tensors: window i receives that window of what decode_view_clips writes, links onto window
+        i - 1 as it lies in memory.  Float tensors (scale, bias: a number or three per colour R, G, B; maxval default 255; minval
+        as decode_view_float's): a float window cannot be a base, so a break ends the clip — a key that is unreadable or cut
+        before its finest level, and every link from the first unreadable or cut one up to the next key, stay as they are; `into`
+        is never read.  Returns the list of DecodeInfo; syncs once.  Not with flip, levels_max, lists or a key outside the
+        stack, a wrong number of origins, or scale / bias with an integer tensor: ValueError before any device call."""
+        order = view_order(order)
+        torch = self.torch
+        for k in unsupported:
+            raise ValueError(f"decode_view_clips_crop does not take {k}= ({self._NOT_IN_CLIPS_CROP.get(k, 'no view call has that keyword')})")
+        if isinstance(into, (list, tuple)):
+            raise ValueError("a clips call takes one grid view, not a list of windows")
+        if isinstance(period, bool) or not hasattr(period, "__index__") or int(period) < 1:
+            raise ValueError(f"period is the distance between keys, an integer from 1 up (n or more: one clip), not {period!r}")
+        period = int(period)
+        W, H = (int(v) for v in size)
+        floats = hasattr(into, "dtype") and into.dtype in (torch.float32, torch.float16, torch.bfloat16)
+        if not floats and (scale is not None or bias is not None):
+            raise ValueError("scale and bias belong to float tensors")
+        fmt = float_format(into.dtype, 1.0 if scale is None else scale, 0.0 if bias is None else bias) if floats else None
+        if floats and maxval is None:
+            maxval = 255
+        lo, maxval = self._signed_range(signed, minval, maxval, floats=floats)
+        v, cw, ch, Cn, n, step = self._view(into, None if maxval is None else int(maxval), stepped, floats=floats, signed=signed)
+        pairs = clip_origins(origins, n, period)
+        org = None if pairs is None else (C.c_int * (2 * len(pairs)))(*[c for p in pairs for c in p])
+        sgn = 1 if lo is not None else 0   # (a float tensor with a lower bound of its own: the signed range rule)
+        return self._decode_views(streams, lens, v, step, order, fmt, (cw, ch, org), None, None, None, W, H, n, -1,
+                                  clips=(period, sgn, lo if sgn else 0))
 
     def decode_view_float(self, streams, lens, into, maxval=255, scale=1.0, bias=0.0, levels_max=-1, stepped=False, order="rgb", flip=None,
                           minval=0):

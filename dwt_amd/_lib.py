@@ -185,6 +185,10 @@ SYMBOLS = {
     "dwtx_encode_view_clips": (_i, [_vp, C.POINTER(View), _sz, _i, _i, _i, _i, _i, _i, C.c_long, _vp, _sz, _vp]),
     "dwtx_decode_view_clips": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, C.POINTER(View), _sz, _i, _i, _i, _i, _vp]),
     "dwtx_view_clips_check": (_i, [C.POINTER(View), _sz, _i, _i, _i, _i, _i, _i, _i]),
+    # clips for loaders: the clips decode plus a float format (or NULL), the crop's sides and one origin per clip
+    "dwtx_decode_view_clips_crop": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, C.POINTER(View), _sz, _i, _i, _i, _i, C.POINTER(FloatFormat), _i, _i,
+                                         C.POINTER(_i), _vp]),
+    "dwtx_view_clips_crop_check": (_i, [C.POINTER(View), _sz, _i, _i, _i, C.POINTER(FloatFormat), _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "dwtx_tile_groups": (_i, [_i, _i, _i, C.POINTER(TileGroup)]),
     "dwtx_decode_images16": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
 }

@@ -353,6 +353,54 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 		return DWTX_ERR_NOMEM;
 	if ((rc = dwtx_lift_scratch(ctx, W, H, (n < 4 ? n : n - n / 2) * C)))
 		return rc;
+	// A clip stack of float windows (dwtx_decode_view_clips_crop with a format): the walk's running INTEGERS cannot be read back
+	// from the view, so a clip that crosses a group — a decoder part, or the one-window launches of `part`'s fallback — hands them
+	// on in a carry picture: int32, C planes of the windows' size.  TWO of them, sized here once like the slots above.  A launch
+	// reads the one the launch before it wrote (its first segment, where that starts mid-clip on a live clip) and writes the
+	// OTHER one (its last segment, where that ends mid-clip): with three segments or more both happen in one launch, in
+	// different workgroups, and one picture would be a read/write race between them.  With two, the only launch that still reads
+	// the picture launch k writes is launch k + 1, behind it on ctx->stream; launch k + 1 writes the picture launch k read, whose
+	// readers are all in launch k — ahead of it on the same stream.  A carry is read only where `live` says
+	// that the launch before left one: never before it is written within a call, and nothing of it outlives the call.
+	struct {
+		int32_t *carry[2] = { nullptr, nullptr };
+		int last = 0;        // the carry picture the latest launch wrote
+		int seen = 0;        // the windows before this one are decided: written, or left as they are
+		bool live = false;   // window seen - 1 was written and its clip goes on: a link at `seen` has a running sample
+	} walk;
+	if (px.clips && px.is_float()) {
+		const size_t one = dwtx_align_up(sizeof(int32_t) * (size_t)(crop ? crop->w : W) * (size_t)(crop ? crop->h : H) * C, 256);
+		char *slot = (char *)dwtx_scratch(ctx, SLOT_CD_CARRY, 2 * one);
+		if (!slot)
+			return DWTX_ERR_NOMEM;
+		walk.carry[0] = (int32_t *)slot;
+		walk.carry[1] = (int32_t *)(slot + one);
+	}
+	// The float walk's break rule (include/dwtx.h) for the group [*first, *first + *count), every window of which is readable and
+	// whole; `finish` and `part` come in ascending order, so a window below *first that no call of this has seen was not written
+	// and broke its clip.  A first segment that starts mid-clip on a dead clip is dropped: the group starts at its first key.
+	// -> whether anything is left to launch; *in / *out: the carry pictures that launch reads and writes, or null.
+	auto float_run = [&](int *first, int *count, const int32_t **in, int32_t **out) -> bool {
+		const int period = px.clips, end = *first + *count;
+		if (walk.seen < *first)
+			walk.live = false;
+		walk.seen = end;
+		const int phase = *first % period, lead = phase ? period - phase : 0;
+		if (lead && !walk.live) {
+			const int skip = lead < *count ? lead : *count;
+			*first += skip;
+			*count -= skip;
+		} else if (lead)
+			*in = walk.carry[walk.last];
+		if (*count < 1)
+			return false;   // (live stays false: the clip is dead up to the next key)
+		if (end < n && end % period != 0) {
+			walk.last ^= 1;
+			*out = walk.carry[walk.last];
+		}
+		walk.live = true;
+		return true;
+	};
 	// reconstruction -> inverse transform -> pixels for images [first, first+count), queued on ctx->stream
 	auto finish = [&](int first, int count, unsigned fused) -> int {
 		const dwtx_decode_info &I = host_info[first];
@@ -409,9 +457,25 @@ static int decode_device(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t strea
 			// first + count that walks the group's segments side by side.  Only a first segment that starts mid-clip reads a window of
 			// another group, window first - 1, and every launch that writes it is ahead of this one on ctx->stream.  A group that
 			// stops before its finest level has returned above, its keys included: the call writes whole pictures only.
-			if (const int r = dwtx_transformation_inv(ctx, img, pyr, W, H, count * C))                   // decode.c:258
+			// With a crop (dwtx_decode_view_clips_crop) the walk is per pixel, so the crop of a clip is the walk over the same crop of its
+			// key and of every residual: dwtx_inv_crop for the group's pictures, each at its CLIP's origin, then the same one launch on
+			// crop-sized planes.  Float windows cannot serve as a base: float_run says which windows of the group a launch writes
+			// and where its running integers come from and go to (the carry pictures, below).
+			int at = first, run = count;
+			const int32_t *carry_in = nullptr;
+			int32_t *carry_out = nullptr;
+			if (px.is_float() && !float_run(&at, &run, &carry_in, &carry_out))
+				return DWTX_OK;
+			const int32_t *planes = img;
+			if (crop) {
+				if (const int r = dwtx_inv_crop(ctx, img, pyr, W, H, count, C, crop->w, crop->h, crop_tab + 2 * (size_t)first, n, 0, 0, (int)route, &planes))
+					return r;
+			} else if (const int r = dwtx_transformation_inv(ctx, img, pyr, W, H, count * C))            // decode.c:258
 				return r;
-			return dwtx_planes_to_pixels_clips(ctx, px, img, W, H, first, count);
+			const int pw = crop ? crop->w : W, ph = crop ? crop->h : H;
+			if (!px.is_float())
+				return dwtx_planes_to_pixels_clips(ctx, px, planes, pw, ph, first, count);
+			return dwtx_planes_to_pixels_clips_float(ctx, px, planes + (size_t)pw * ph * C * (size_t)(at - first), pw, ph, at, run, carry_in, carry_out);
 		}
 		if (crop) {
 			const int32_t *planes;
@@ -493,6 +557,8 @@ struct ViewCall {
 	size_t other_step = 0;
 	int sgn = 0;
 	int period = 0;                              // a clips call (PAIR_CLIPS, no `other`): every period-th window of the view is a key
+	bool clip_crop = false;                      // dwtx_decode_view_clips_crop: host_origins holds one pair per CLIP, fmt is optional, and the crop's and the
+	                                             // format's refusals are the clips call's own (clips_crop_refusals), worded as its
 	int W = 0, H = 0, n = 0;                     // the pictures' size and number
 	bool dst = false;                            // the view will be written (maxval, disjoint windows)
 	// what single entries insist on: the float calls on a format, the list calls on a list
@@ -533,7 +599,7 @@ static int view_pixels(const ViewCall &c, int kind, dwtx_pixels *px)
 		dwtx_set_error("%sno view, no pixels or no windows", bare);
 		return DWTX_ERR_ARG;
 	}
-	if (clips && !dwtx_dims_ok(W, H)) {
+	if (clips && !c.crop && !dwtx_dims_ok(W, H)) {   // (a clip stack's crop: clips_crop_refusals has seen the pictures' own size)
 		dwtx_set_error("clips view: unsupported image size %dx%d (8..%d per side)", W, H, DWTX_MAX_SIDE);
 		return DWTX_ERR_ARG;
 	}
@@ -887,6 +953,63 @@ static int clips_refusals(const ViewCall &c)
 	return DWTX_OK;
 }
 
+// What dwtx_decode_view_clips_crop adds to them, in the same place: the pictures' size (the view's windows are the crop's), the
+// crop's sides, one origin per CLIP (clip k: windows [k * period, (k + 1) * period)), the float type and its scale and bias.
+// *whole: the crop is every picture itself; *kind: the float samples, -1 for integer ones; *per_picture: the origins as
+// dwtx_inv_crop's table is built from them, one pair per picture (empty: all at (0, 0)).
+static int clips_crop_refusals(const ViewCall &c, bool *whole, int *kind, std::vector<int> *per_picture)
+{
+	const int W = c.W, H = c.H;
+	if (!dwtx_dims_ok(W, H)) {
+		dwtx_set_error("clips view: unsupported image size %dx%d (8..%d per side)", W, H, DWTX_MAX_SIDE);
+		return DWTX_ERR_ARG;
+	}
+	if (c.n < 1) {
+		dwtx_set_error("clips view: no view, no pixels or no windows");
+		return DWTX_ERR_ARG;
+	}
+	if (c.crop_w < 1 || c.crop_w > W || c.crop_h < 1 || c.crop_h > H) {
+		dwtx_set_error("clips view: crop %dx%d is no window of a %dx%d picture (sides of 1 up to the picture's)", c.crop_w, c.crop_h, W, H);
+		return DWTX_ERR_ARG;
+	}
+	*whole = c.crop_w == W && c.crop_h == H;
+	const int nclips = (int)(((long)c.n + c.period - 1) / c.period);
+	for (int k = 0; c.host_origins && k < nclips; ++k) {
+		const int x0 = c.host_origins[2 * k], y0 = c.host_origins[2 * k + 1];
+		if (x0 < 0 || y0 < 0 || x0 > W - c.crop_w || y0 > H - c.crop_h) {
+			dwtx_set_error("clips view: origin (%d, %d) of clip %d puts its %dx%d window outside the %dx%d picture", x0, y0, k, c.crop_w, c.crop_h, W, H);
+			return DWTX_ERR_ARG;
+		}
+		*whole = *whole && !x0 && !y0;
+	}
+	*kind = -1;
+	if (c.fmt) {
+		if (c.fmt->type != DWTX_FLOAT32 && c.fmt->type != DWTX_FLOAT16 && c.fmt->type != DWTX_BFLOAT16) {
+			dwtx_set_error("clips view: float type %d (DWTX_FLOAT32 = 0, DWTX_FLOAT16 = 1 or DWTX_BFLOAT16 = 2)", c.fmt->type);
+			return DWTX_ERR_ARG;
+		}
+		for (int k = 0; k < 3; ++k)
+			if (!isfinite(c.fmt->scale[k]) || !isfinite(c.fmt->bias[k])) {
+				dwtx_set_error("clips view: scale[%d] = %g, bias[%d] = %g: both must be finite", k, (double)c.fmt->scale[k], k, (double)c.fmt->bias[k]);
+				return DWTX_ERR_ARG;
+			}
+		*kind = c.fmt->type == DWTX_FLOAT32 ? DWTX_SAMPLE_F32 : c.fmt->type == DWTX_FLOAT16 ? DWTX_SAMPLE_F16 : DWTX_SAMPLE_BF16;
+	}
+	per_picture->clear();
+	if (c.host_origins && !*whole) {
+		try {
+			per_picture->resize(2 * (size_t)c.n);
+		} catch (...) {
+			return DWTX_ERR_NOMEM;
+		}
+		for (int i = 0; i < c.n; ++i) {
+			(*per_picture)[2 * (size_t)i] = c.host_origins[2 * (i / c.period)];
+			(*per_picture)[2 * (size_t)i + 1] = c.host_origins[2 * (i / c.period) + 1];
+		}
+	}
+	return DWTX_OK;
+}
+
 // The units of a grid view — its n windows, or the 3n planes of planar RGB, as in list_windows — as byte spans [first, first +
 // (H-1)*row_pitch + row) of the address space, appended to `spans` with `tag`
 struct DeltaSpan {
@@ -976,6 +1099,7 @@ struct ViewPlan {
 	                               // flags on top (dwtx_pixels::flips); empty unless the call is listed or flipped
 	bool cropped = false;          // crop: only that window of every picture is written; else whole pictures
 	CropCall crop;
+	std::vector<int> origins;      // a clip stack's crop: its per-clip origins spelled out per picture (crop.origins points here)
 	dwtx_pixels key;               // a chain encode: the key's one window
 };
 
@@ -998,7 +1122,7 @@ static int plan_view(const ViewCall &call, ViewPlan *plan)
 			return rc;
 		flipped = flipped || c.table;
 	}
-	if (c.crop) {
+	if (c.crop && !c.clip_crop) {
 		bool whole;
 		if ((rc = crop_of_call(c, &whole)))
 			return rc;
@@ -1006,7 +1130,9 @@ static int plan_view(const ViewCall &call, ViewPlan *plan)
 		c.crop = !whole;
 	}
 	int kind = -1;
-	if (c.fmt || c.needs_fmt) {
+	if (c.clip_crop)
+		;   // (the format of a clip stack's crop call is looked at with the crop, below)
+	else if (c.fmt || c.needs_fmt) {
 		if ((rc = float_kind(c.fmt, &kind)))
 			return rc;
 	} else if (c.kind_from_bytes && c.view && c.view->sample_bytes == 4)
@@ -1035,6 +1161,16 @@ static int plan_view(const ViewCall &call, ViewPlan *plan)
 	} else if (c.pair == PAIR_CLIPS) {
 		if ((rc = clips_refusals(c)))
 			return rc;
+		if (c.clip_crop) {
+			bool whole;
+			if ((rc = clips_crop_refusals(c, &whole, &kind, &plan->origins)))
+				return rc;
+			// the whole picture at (0, 0): the clips call on full-size windows (with integer samples: dwtx_decode_view_clips itself)
+			c.crop = !whole;
+			c.host_origins = plan->origins.empty() ? nullptr : plan->origins.data();   // (per picture from here on, as decode_device reads them)
+			if (kind >= 0 && c.minval && *c.minval == 0)   // float samples from 0 up: the unsigned range rule, as in the float calls
+				c.minval = nullptr;
+		}
 	}
 	if (c.pair && !c.sgn)
 		c.minval = nullptr;
@@ -1354,6 +1490,17 @@ extern "C" int dwtx_decode_view_clips(dwtx_ctx *ctx, const uint8_t *dev_streams,
 	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
 }
 
+// (the clips call with a crop per clip and an optional float format: plan_view makes the full-size integer call the call above)
+extern "C" int dwtx_decode_view_clips_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, const dwtx_view *dst, size_t pixel_step, int period, int order, int sgn, int minval, const dwtx_float_format *fmt,
+	int crop_w, int crop_h, const int *host_origins, dwtx_decode_info *host_info)
+{
+	const ViewCall c = { .view = dst, .pixel_step = pixel_step, .order = order, .fmt = fmt, .minval = &minval, .crop = true, .crop_w = crop_w,
+		.crop_h = crop_h, .host_origins = host_origins, .pair = PAIR_CLIPS, .sgn = sgn, .period = period, .clip_crop = true, .W = W, .H = H, .n = n,
+		.dst = true };
+	return decode_views(ctx, dev_streams, stream_stride, dev_lens, c, host_info);
+}
+
 // The host-only exports: the resolver's verdict, and for the flip plan its table read back
 
 extern "C" int dwtx_view_list_check(const dwtx_view *v, size_t pixel_step, int W, int H, int n, const void *const *host_windows, int dst)
@@ -1408,6 +1555,16 @@ extern "C" int dwtx_view_clips_check(const dwtx_view *v, size_t pixel_step, int 
 {
 	const ViewCall c = { .view = v, .pixel_step = pixel_step, .order = DWTX_ORDER_RGB, .minval = &minval, .pair = PAIR_CLIPS, .sgn = sgn, .period = period,
 		.W = W, .H = H, .n = n, .dst = dst != 0 };
+	ViewPlan plan;
+	return plan_view(c, &plan);
+}
+
+extern "C" int dwtx_view_clips_crop_check(const dwtx_view *v, size_t pixel_step, int period, int sgn, int minval, const dwtx_float_format *fmt,
+	int W, int H, int n, int crop_w, int crop_h, const int *host_origins)
+{
+	const ViewCall c = { .view = v, .pixel_step = pixel_step, .order = DWTX_ORDER_RGB, .fmt = fmt, .minval = &minval, .crop = true, .crop_w = crop_w,
+		.crop_h = crop_h, .host_origins = host_origins, .pair = PAIR_CLIPS, .sgn = sgn, .period = period, .clip_crop = true, .W = W, .H = H, .n = n,
+		.dst = true };
 	ViewPlan plan;
 	return plan_view(c, &plan);
 }

@@ -6,7 +6,7 @@
 #include <stddef.h>
 #include "../../include/dwtx.h"
 
-#define DWTX_SCRATCH_SLOTS 26
+#define DWTX_SCRATCH_SLOTS 27
 #define DWTX_PART_STREAMS 4   // parts a batch runs as at the most, one stream each
 #define DWTX_ENC_PARTS DWTX_PART_STREAMS
 
@@ -157,9 +157,9 @@ enum {
 	SLOT_LIFT_A = 0, SLOT_LIFT_B,   // lift.hip
 	SLOT_PK_CUM, SLOT_PK_SMALL, SLOT_PK_ENT, SLOT_PK_TOKBIG, SLOT_PK_TOK16, SLOT_PK_LUT, SLOT_PK_CHUNK, SLOT_PK_STAGE,   // pack.hip
 	SLOT_UP_SMALL = 12, SLOT_UP_BITS, SLOT_UP_TILES, SLOT_UP_CHUNKS,   // unpack.hip
-	SLOT_CD_A, SLOT_CD_B, SLOT_CD_INFO, SLOT_CD_IO, SLOT_CD_IO2, SLOT_CD_LENS, SLOT_CD_F16, SLOT_CD_INDEX, SLOT_CD_CROP, SLOT_CD_LIST,   // codec.hip
+	SLOT_CD_A, SLOT_CD_B, SLOT_CD_INFO, SLOT_CD_IO, SLOT_CD_IO2, SLOT_CD_LENS, SLOT_CD_F16, SLOT_CD_INDEX, SLOT_CD_CROP, SLOT_CD_LIST, SLOT_CD_CARRY,   // codec.hip
 };
-static_assert(SLOT_CD_LIST < DWTX_SCRATCH_SLOTS, "more scratch slots than dwtx_ctx has");
+static_assert(SLOT_CD_CARRY < DWTX_SCRATCH_SLOTS, "more scratch slots than dwtx_ctx has");
 
 static inline size_t dwtx_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -444,6 +444,12 @@ int dwtx_planes_to_pixels_chain(dwtx_ctx *ctx, const dwtx_pixels &px, const int3
 // segments side by side: a key receives the plain conversion of its planes, a link clamp(window before + d).  A first segment that
 // starts mid-clip reads window first - 1 as it lies in memory when the launch runs.  On ctx->stream.
 int dwtx_planes_to_pixels_clips(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int first, int count);
+// lift.hip: the same for a clip stack of FLOAT windows (dwtx_decode_view_clips_crop with a format; px.kind a float kind): every
+// window of the group is written through the view's scale and bias, and the view is never read — a first segment that starts
+// mid-clip takes its running integers from carry_in (int32 [C][H][W], required then), and where carry_out is given the launch's
+// last segment leaves its own there.  The two are different pictures (the launch refuses one for both).  On ctx->stream.
+int dwtx_planes_to_pixels_clips_float(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int first, int count,
+	const int32_t *carry_in, int32_t *carry_out);
 
 // The entropy stage's tiles (linearize.hip): the Hilbert curve of ring level l visits every aligned 32x32 square of
 // its lengths[l+1]-sided square contiguously ("curve block"), so the ring's coefficients, in the order of

@@ -3697,28 +3697,53 @@ __device__ __forceinline__ void chain_link(const ChainRaw &r, int (&b)[3], Clamp
 // wave's (a scalar branch), and std::false_type where a caller has no keys: then the key's code is not compiled at all (behind a
 // bool that is false the chain kernel's loop came out peeled, twice the code and three SGPRs more).  That caller also forms q
 // once per instance of the walk, inside its branch on C, not once before it (two VGPRs).
-template <class P, int C, class Keyed>
+// Sink: where the running sample goes and, without a key, where it comes from.  IntSink (every integer instance, the code they
+// always had): the sample itself into the view, the start from the base sample at q.  FloatSink (k_clips_float_from_planes): the
+// view holds floats, which cannot be read back as a base — every picture is stored through sample_of<P> with colour c's scale and
+// bias, the running INTEGER starts from the carry picture `in` (int32 planes of the view's W x H, the lane's pixel: one coalesced
+// load per colour; q is not looked at), and after the last picture it is left in the carry picture `out` where there is one.
+struct IntSink {
+	static constexpr bool floats = false;
+};
+struct FloatSink {
+	static constexpr bool floats = true;
+	FloatFmt f;
+	const int *__restrict__ in;
+	int *__restrict__ out;
+};
+template <class P, int C, class Keyed, class Sink = IntSink>
 __device__ __forceinline__ void chain_walk(P *__restrict__ pix, const int *__restrict__ planes, const PixGrid &g, const P *__restrict__ q, long qstep, Keyed keyed,
-	Clamp M, int x, int y, int win0, int n)
+	Clamp M, int x, int y, int win0, int n, const Sink &sink = Sink())
 {
 	const long npix = (long)g.W * g.H;
 	const long wstep = (long)C * npix;   // from a picture's planes to the next one's
 	const long at = (long)y * g.row_pitch + (long)x * g.col_step;
 	int b[3] = { 0, 0, 0 };
 	if (!keyed) {
-		b[0] = (int)q[0];
-		if (C == 3) {
-			b[1] = (int)q[qstep];
-			b[2] = (int)q[2 * qstep];
+		if constexpr (Sink::floats) {
+			const int *ci = sink.in + (long)y * g.W + x;
+			for (int c = 0; c < C; ++c)
+				b[c] = ci[c * npix];
+		} else {
+			b[0] = (int)q[0];
+			if (C == 3) {
+				b[1] = (int)q[qstep];
+				b[2] = (int)q[2 * qstep];
+			}
 		}
 	}
 	const int *src = planes + (long)y * g.W + x;
 	auto store = [&](int win) {
 		P *p = pix + win_off(g.grid, g.image_stride, win) + at;
-		p[0] = (P)b[0];
-		if (C == 3) {
-			p[g.chan_stride] = (P)b[1];
-			p[2 * g.chan_stride] = (P)b[2];
+		if constexpr (Sink::floats) {
+			for (int c = 0; c < C; ++c)
+				p[c * g.chan_stride] = sample_of<P>(b[c], sink.f, c);
+		} else {
+			p[0] = (P)b[0];
+			if (C == 3) {
+				p[g.chan_stride] = (P)b[1];
+				p[2 * g.chan_stride] = (P)b[2];
+			}
 		}
 	};
 	ChainRaw nxt[CHAIN_AHEAD], cur[CHAIN_AHEAD];
@@ -3748,6 +3773,12 @@ __device__ __forceinline__ void chain_walk(P *__restrict__ pix, const int *__res
 				store(win0 + w0 + k);
 			}
 	}
+	if constexpr (Sink::floats)
+		if (sink.out) {   // (the wave's) the segment ends mid-clip: the next launch's first segment goes on from here
+			int *co = sink.out + (long)y * g.W + x;
+			for (int c = 0; c < C; ++c)
+				co[c * npix] = b[c];
+		}
 }
 template <class P>
 __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_chain_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, const P *__restrict__ base,
@@ -3799,6 +3830,36 @@ __global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_clips_from_planes(P *__r
 		chain_walk<P, 1>(pix, seg, g, q, g.chan_stride, keyed, M, x, y, first + r0, r1 - r0);
 	else
 		chain_walk<P, 3>(pix, seg, g, q, g.chan_stride, keyed, M, x, y, first + r0, r1 - r0);
+}
+
+// The clip stack's conversion into FLOAT windows (dwtx_decode_view_clips_crop with a format; P = float, _Float16 or __bf16): the
+// same grid, the same segments and the same walk, with chain_walk's FloatSink.  The view is never read: the one segment that starts
+// mid-clip (z == 0 with lead != 0) takes its running integer from the carry picture carry_in, which the launch before this one
+// left behind, and the launch's LAST segment leaves its own in carry_out where the host asks for it (the segment ends mid-clip).
+// With three segments or more both happen in one launch, in different workgroups: the host hands in two DIFFERENT pictures
+// (codec.hip, decode_device: they alternate per launch), so that no workgroup of a launch reads what another one of it writes.
+// A kernel of its own: the integer instances above keep their arguments and their code.
+template <class P>
+__global__ __launch_bounds__(PX_LANES * PX_ROWS) void k_clips_float_from_planes(P *__restrict__ pix, const int *__restrict__ planes, PixGrid g, int first, int period,
+	int L, int M_, FloatFmt f, const int *__restrict__ carry_in, int *__restrict__ carry_out)
+{
+	const Clamp M = { L, M_ };
+	int x, y;
+	if (!px_lane(g.W, g.H, x, y))
+		return;
+	const int phase = first % period, lead = phase ? period - phase : 0;
+	const int s = lead + ((int)blockIdx.z - (lead ? 1 : 0)) * period;
+	const int r0 = max(s, 0), r1 = min(s + period, g.n);
+	if (r0 >= r1)   // (never: the host launches the group's segments and no more)
+		return;
+	const int *seg = planes + (long)r0 * g.C * g.W * g.H;
+	const bool keyed = s >= 0;   // (the wave's)
+	const FloatSink sink = { f, carry_in, blockIdx.z == gridDim.z - 1 ? carry_out : nullptr };
+	const P *none = nullptr;
+	if (g.C == 1)
+		chain_walk<P, 1>(pix, seg, g, none, 0, keyed, M, x, y, first + r0, r1 - r0, sink);
+	else
+		chain_walk<P, 3>(pix, seg, g, none, 0, keyed, M, x, y, first + r0, r1 - r0, sink);
 }
 
 // Integer-only synthetic frames: seed = frame index, so every box
@@ -4023,6 +4084,43 @@ int dwtx_planes_to_pixels_clips(dwtx_ctx *ctx, const dwtx_pixels &px, const int3
 	});
 	if (rc)
 		return rc;
+	DWTX_LAUNCH_CHECK();
+	return DWTX_OK;
+}
+
+// A clip stack's conversion into float windows: the same segments, the carry pictures in place of the view as a base
+int dwtx_planes_to_pixels_clips_float(dwtx_ctx *ctx, const dwtx_pixels &px, const int32_t *planes, int W, int H, int first, int count,
+	const int32_t *carry_in, int32_t *carry_out)
+{
+	const int C = px.channels;
+	if (!ctx || !planes || !px.base || px.clips < 1 || px.clip_at || px.chain || px.delta.base || W < 1 || H < 1 || (C != 1 && C != 3) || first < 0 || count < 1)
+		return DWTX_ERR_ARG;
+	if (!px.is_float() || px.flips || px.listed() || !px.sample_aligned() || !px.range_ok())
+		return DWTX_ERR_ARG;
+	const int phase = first % px.clips, lead = phase ? px.clips - phase : 0;
+	if ((lead && !carry_in) || (carry_in && carry_in == carry_out))   // a segment that starts mid-clip has nothing else to start from
+		return DWTX_ERR_ARG;
+	DWTX_ENTER(ctx);
+	dim3 grid;
+	const PixGrid g = pix_grid(px, W, H, count, &grid);
+	grid.z = lead >= count ? 1u : (unsigned)((lead ? 1 : 0) + dwtx_cdiv(count - lead, px.clips));
+	const FloatFmt f = float_fmt(px);
+	auto launch = [&](auto t) {
+		using P = typename decltype(t)::type;
+		hipLaunchKernelGGL(k_clips_float_from_planes<P>, grid, dim3(PX_LANES * PX_ROWS), 0, ctx->stream, static_cast<P *>(px.red()), planes, g,
+			first, px.clips, px.minval, px.maxval, f, carry_in, carry_out);
+	};
+	switch (px.kind) {   // (the float kinds alone: with_sample_type would compile an integer walk through FloatSink too)
+	case DWTX_SAMPLE_F32:
+		launch(SampleType<float>());
+		break;
+	case DWTX_SAMPLE_F16:
+		launch(SampleType<_Float16>());
+		break;
+	default:
+		launch(SampleType<__bf16>());
+		break;
+	}
 	DWTX_LAUNCH_CHECK();
 	return DWTX_OK;
 }

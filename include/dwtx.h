@@ -804,6 +804,49 @@ int dwtx_decode_view_clips(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t str
  * this view (dst != 0: the decode's rules). */
 int dwtx_view_clips_check(const dwtx_view *v, size_t pixel_step, int period, int sgn, int minval, int W, int H, int n, int dst);
 
+/* ---- clips for loaders: a crop per clip, and float destinations ---------------------------------------------------------------
+ * What a video loader does next with a batch of clips — one random crop per clip, then x.float() * scale + bias into fp16 or bf16
+ * — inside the decode: dwtx_decode_view_clips with the windows of `dst` crop_w x crop_h and, with fmt, float samples.  W, H are the
+ * streams' geometry.  host_origins holds one (x0, y0) per CLIP, ceil(n / period) pairs: clip k is windows [k * period, (k + 1) *
+ * period) and every one of them receives the crop_w x crop_h window of its picture that starts there.  Host memory, read before the
+ * call returns; NULL: all (0, 0).  One origin per clip is the contract: links with origins of their own would not be a chain.
+ * Every rule of dwtx_decode_view_clips holds with the crop's sides — disjointness by dwtx_decode_view_step's rules, row length,
+ * alignment, planar and stepped forms, order, sgn, minval and the range.
+ * Identity: with fmt == NULL, crop_w == W, crop_h == H and all origins zero the call IS dwtx_decode_view_clips and takes its path.
+ * Integer destinations (fmt == NULL), by equivalence: the walk of dwtx_decode_view_clips, word for word, on crop-sized windows.  A
+ * key whose stream has status 0 and supports the whole picture receives the crop, at its clip's origin, of what the plain decode of
+ * stream i writes (dwtx_decode_view_crop's window of picture i, the clamps for [minval, maxval] included).  A link receives
+ * clamp(B + d), d the same crop of the residual under the signed clamps for [-R, R] (dwtx_decode_view_delta) and B window i - 1 of
+ * dst as it lies in memory at that moment — both are per pixel, so the crop of the walk is the walk of the crops.  A window whose
+ * stream is unreadable or cut before its finest level stays as it is, and the next link takes what lies there.
+ * Float destinations (fmt given): dst->sample_bytes matches fmt->type; dst->maxval, sgn and minval give the range as above (sgn ==
+ * 0 requires minval == 0).  The value written for colour c is (float)v * scale[c], rounded to fp32, plus bias[c], rounded to fp32,
+ * then converted to the type — dwtx_decode_view_float's rounding contract exactly — where v is the clamped integer the integer walk
+ * holds for that sample; scale and bias belong to colours, not to memory positions.  A float window cannot serve as a base, so the
+ * float walk has ONE deliberate difference: A BREAK ENDS THE CLIP.  The walk keeps a flag per clip: a whole key (status 0, level +
+ * 1 == levels) sets it and is written; a key that is not whole clears it, its window untouched; a link is written only if the flag
+ * is set and its own stream is readable and whole; otherwise the link clears the flag and its window stays untouched, and so does
+ * every later link up to the next key.  The float walk never reads the destination.
+ * host_info[i] is the plain call's either way; the call synchronises where dwtx_decode_view does.
+ * Route: the deep pictures' route into the int32 pyramid, as for every clip stack; with a crop dwtx_decode_view_crop's windowed
+ * inverse (or, by DWTX_OPT_CROP_ROUTE, the whole inverse and a gather) for the pictures of a group, each at its clip's origin, then
+ * ONE launch of the clips conversion on crop_w x crop_h planes: k_clips_from_planes, or its float twin k_clips_float_from_planes.
+ * A float group that starts mid-clip takes its running integers from a carry picture (int32, context scratch) that the launch
+ * before it left; two carry pictures alternate per launch, so that no launch reads the one it writes.
+ * Only launches with something live to write are made.
+ * Still not in the call: window lists, flips, levels_max, and a key outside the stack.
+ * DWTX_ERR_ARG (with a dwtx_last_error() text that starts "clips view:", nothing written): everything dwtx_decode_view_clips
+ * refuses; crop_w outside 1..W or crop_h outside 1..H; an origin that leaves the picture; an unknown float type; a sample_bytes
+ * that does not match the type; a scale or bias that is not finite. */
+int dwtx_decode_view_clips_crop(dwtx_ctx *ctx, const uint8_t *dev_streams, size_t stream_stride, const unsigned long long *dev_lens,
+	int W, int H, int n, const dwtx_view *dst, size_t pixel_step, int period, int order, int sgn, int minval,
+	const dwtx_float_format *fmt /* NULL: integer samples */, int crop_w, int crop_h,
+	const int *host_origins /* [ceil(n / period)][2] or NULL */, dwtx_decode_info *host_info);
+/* Host arithmetic only, like dwtx_view_clips_check: DWTX_OK, or the DWTX_ERR_ARG (and text) the call above would return for this
+ * destination view, crop and format. */
+int dwtx_view_clips_crop_check(const dwtx_view *v, size_t pixel_step, int period, int sgn, int minval, const dwtx_float_format *fmt,
+	int W, int H, int n, int crop_w, int crop_h, const int *host_origins);
+
 /* A frame cut into tiles (host arithmetic only; no reference counterpart): the 1 to 4 groups of same-geometry tiles —
  * interior, right column, bottom row, corner, in that order, those that exist — each a cols x rows grid of W x H tiles
  * whose first tile's corner is (x0, y0): one dwtx_encode_view / dwtx_decode_view call per group.  Per axis, with
