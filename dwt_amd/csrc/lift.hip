@@ -1198,15 +1198,16 @@ struct FwdSrc;
 
 // the band a level of k_fwd_level_w reads: int32 planes, 16-bit planes (dwtx_p16: the detail bands go out as 16-bit values
 // too), or — the finest level of a deep picture — uint16_t pixels, gray, interleaved RGB or planar RGB; and the pixels
-// k_fwd_pixels_w reads (the host's names for Band<>'s five and for uint8_t, Rgb8, RgbP8 and Rgbx8, then the
-// three B, G, R twins: Band<SRC_BGR16>, Bgr8, Bgrx8)
+// k_fwd_pixels_w reads (names for Band<>'s five and for uint8_t, Rgb8, RgbP8 and Rgbx8, then the
+// three B, G, R twins: Band<SRC_BGR16>, Bgr8, Bgrx8).  The values are template arguments of Band<>, and so part of the kernels'
+// names, and nothing else: no table is indexed by them (the host's table of pixel ends, wide_row(), names its rows by what the pixels are)
 enum { SRC_I32 = 0, SRC_I16, SRC_U16, SRC_RGB16, SRC_RGBP16, SRC_U8, SRC_RGB8, SRC_RGBP8, SRC_RGBX8, SRC_BGR16, SRC_BGR8, SRC_BGRX8,
 	// float pixels (FloatPix<> below), gray and planar (P) fp32 and fp16 / bf16: quantised to at most 255, and (D) beyond
 	SRC_F32, SRC_H16, SRC_F32P, SRC_H16P, SRC_F32D, SRC_H16D, SRC_F32PD, SRC_H16PD,
 	// int16_t pixels (dwtx_encode_view_signed): the twins of SRC_U16, SRC_RGB16, SRC_RGBP16 and SRC_BGR16 that widen with the sign
 	SRC_S16, SRC_RGB16S, SRC_RGBP16S, SRC_BGR16S,
 	// delta views (dwtx_encode_view_delta): the picture and its base, gray of the three sample types and interleaved 8-bit RGB in both orders
-	SRC_DELTA_U8, SRC_DELTA_U16, SRC_DELTA_S16, SRC_DELTA_RGB8, SRC_DELTA_BGR8, SRC_COUNT };
+	SRC_DELTA_U8, SRC_DELTA_U16, SRC_DELTA_S16, SRC_DELTA_RGB8, SRC_DELTA_BGR8 };
 template <int SRC>
 struct Band {};
 // 8-bit interleaved RGB pixels, of which each plane's workgroup takes its own YCoCg-R channel (image.h:52-65 fused; 8-bit
@@ -4265,111 +4266,186 @@ static TailArgs tail_args(const LiftLayout &L, int *pyr)
 }
 
 using WideKernel = void (*)(LevelArgsW);
+using Inv2Kernel = void (*)(Inv2Args);
 
-// What a wide forward step reads.  px: these pixels; null: int32 planes, or (src16) the 16-bit bands of the level before.
-// The one place that looks at the pixels' layout: the kernel, the launch's grid and LevelArgsW::cstride follow from it.
-struct FwdSource {
-	int src;          // SRC_*
-	bool rgb_grid;    // FwdSrc<>::RGB_GRID: three workgroups per strip and nplanes / 3 in z, against one per plane
-	long cstride;
+// ------------------------------------------------------------- pixel ends ---
+// A pixel end: the pixels that the finest wide level reads (forward) or writes (inverse) in place of an int32 plane, as far as
+// they choose a kernel.  wide_end() is the one place that looks at a view's layout for that, once per
+// call; wide_row() finds the end's row in the one table of kernels, and a view has wide kernels if it has a row
+// (dwtx_pixels_ok).  A new pixel format is its kernels and one row.
+enum WideKind { WK_U8, WK_U16, WK_S16, WK_F32, WK_H16 };   // (H16: fp16 and bf16, which FloatFmt::bf16 tells apart)
+enum WideLayout { WL_NONE, WL_GRAY, WL_PACKED, WL_STEP4, WL_PLANAR };   // NONE: a pixel step that no wide kernel addresses; STEP4: dwtx_pixels::rgbx8()
+// BGR: interleaved pixels that lie as B, G, R run their layout's twin kernels (planar ones their layout's own, from the R plane with
+// a negative channel stride: wide_base, wide_cstride).  DELTA: a delta view.  FAR: float samples that quantise beyond [0, 255]
+// (dwtx_pixels::deep_source()), whose forward kernels keep neither histograms nor 16-bit bands.
+enum WideFlags { WE_BGR = 1, WE_DELTA = 2, WE_FAR = 4 };
+struct WideEnd {
+	int kind, layout;
+	unsigned flags;
+	bool operator==(const WideEnd &o) const { return kind == o.kind && layout == o.layout && flags == o.flags; }
 };
 
-// The order of the channels (dwtx_pixels::order) changes no path: interleaved B, G, R pixels run their layout's twin kernel on
-// the same base, planar ones the same kernel from their R plane with a negative channel stride.  What the wide kernels get as
-// src8 / dst8 and as cstride:
+static WideEnd wide_end(const dwtx_pixels &px)
+{
+	WideEnd e;
+	e.kind = px.kind == DWTX_SAMPLE_U8 ? WK_U8 : px.kind == DWTX_SAMPLE_U16 ? WK_U16 : px.kind == DWTX_SAMPLE_S16 ? WK_S16 : px.kind == DWTX_SAMPLE_F32 ? WK_F32 : WK_H16;
+	e.layout = px.stepped() && !px.rgbx8() ? WL_NONE : px.channels != 3 ? WL_GRAY : px.planar() ? WL_PLANAR : px.rgbx8() ? WL_STEP4 : WL_PACKED;
+	e.flags = (px.bgr() && e.layout != WL_PLANAR ? WE_BGR : 0u) | (px.is_delta() ? WE_DELTA : 0u) | (px.is_float() && px.deep_source() ? WE_FAR : 0u);
+	return e;
+}
+
+// What the wide kernels get as src8 / dst8 and as cstride (the order of planar channels changes no kernel, see WE_BGR)
 static const uint8_t *wide_base(const dwtx_pixels &px) { return px.planar() ? static_cast<const uint8_t *>(px.red()) : px.u8(); }
 static long wide_cstride(const dwtx_pixels &px) { return px.channels == 3 && px.planar() ? px.colour_stride() : 0; }
 
-static FwdSource fwd_source(const dwtx_pixels *px, bool src16)
+// The kernels of a pixel end; a null entry: the instance is not built, and a call that needs it is refused.
+struct FwdSet {
+	WideKernel k[2][2];   // [histograms ride along][a flipped call's windows: FY]
+};
+struct InvSet {
+	WideKernel k[2][3];   // one level, [the detail bands are 16-bit values][FL: flip_level()]
+	Inv2Kernel k2[3];     // two levels in one pass, [FL]: from 16-bit bands only, which only 8-bit pixels take
+};
+struct WideRow {
+	WideEnd end;     // the key
+	bool rgb_grid;   // forward, FwdSrc<>::RGB_GRID: three workgroups per strip and nplanes / 3 in z, against one workgroup column per plane
+	                 // (every inverse RGB kernel takes three planes per wave: WideRow::rgb())
+	FwdSet fwd;
+	InvSet inv;
+	bool rgb() const { return end.layout != WL_GRAY; }
+};
+
+// The sets the rows are made of.  Forward: deep samples (no histograms: the bounds are for 8-bit sources), delta views (nor flips),
+// 8-bit pixels, float samples by their route.  Inverse: the sink's sample type, and for RGB its layout.
+#define FL3(kernel, ...) { kernel<__VA_ARGS__, 0>, kernel<__VA_ARGS__, 1>, kernel<__VA_ARGS__, 2> }
+template <int SRC> static constexpr FwdSet fwd_deep() { return { { { k_fwd_level_w<false, SRC>, k_fwd_level_w<false, SRC, true> }, {} } }; }
+template <int SRC> static constexpr FwdSet fwd_delta() { return { { { k_fwd_level_w<false, SRC>, nullptr }, {} } }; }
+template <class S> static constexpr FwdSet fwd_pix8()
 {
-	if (!px)
-		return { src16 ? SRC_I16 : SRC_I32, false, 0 };
-	const bool deep = px->deep(), bgr = px->bgr();
-	if (px->is_delta())   // gray, or interleaved 8-bit RGB (dwtx_pixels_ok): a workgroup column per plane
-		return { px->channels == 3 ? (bgr ? SRC_DELTA_BGR8 : SRC_DELTA_RGB8) : px->kind == DWTX_SAMPLE_U8 ? SRC_DELTA_U8 : px->kind == DWTX_SAMPLE_S16 ? SRC_DELTA_S16 : SRC_DELTA_U16, false, 0 };
-	if (px->is_float()) {   // gray, or planar RGB in either order (dwtx_pixels_ok): by sample size, layout and route
-		const bool rgb = px->channels == 3, far = px->deep_source();
-		const int src = (px->kind == DWTX_SAMPLE_F32 ? SRC_F32 : SRC_H16) + (rgb ? SRC_F32P - SRC_F32 : 0) + (far ? SRC_F32D - SRC_F32 : 0);
-		return { src, rgb && !far, wide_cstride(*px) };
-	}
-	const bool sgn = px->kind == DWTX_SAMPLE_S16;   // (deep() too: the deep sources' signed twins)
-	if (px->channels != 3)
-		return { sgn ? SRC_S16 : deep ? SRC_U16 : SRC_U8, false, 0 };
-	const int src = px->planar() ? (sgn ? SRC_RGBP16S : deep ? SRC_RGBP16 : SRC_RGBP8)
-		: px->rgbx8()            ? (bgr ? SRC_BGRX8 : SRC_RGBX8)
-		: sgn                    ? (bgr ? SRC_BGR16S : SRC_RGB16S)
-		: deep                   ? (bgr ? SRC_BGR16 : SRC_RGB16)
-		                         : (bgr ? SRC_BGR8 : SRC_RGB8);
-	return { src, !deep, wide_cstride(*px) };
+	return { { { k_fwd_pixels_w<S, false>, k_fwd_pixels_w<S, false, true> }, { k_fwd_pixels_w<S, true>, k_fwd_pixels_w<S, true, true> } } };
+}
+template <class S> static constexpr FwdSet fwd_float()
+{
+	return { { { k_fwd_float_w<S, false>, k_fwd_float_w<S, false, true> }, { k_fwd_float_w<S, true>, k_fwd_float_w<S, true, true> } } };
+}
+template <class S> static constexpr FwdSet fwd_float_far() { return { { { k_fwd_float_w<S, false>, k_fwd_float_w<S, false, true> }, {} } }; }
+static constexpr InvSet inv_gray8() { return { { FL3(k_inv_level_w, uint8_t, false), FL3(k_inv_level_w, uint8_t, true) }, FL3(k_inv2_level_w, uint8_t, true) }; }
+static constexpr InvSet inv_gray_deep() { return { { FL3(k_inv_level_w, uint16_t, false), {} }, {} }; }   // (int16_t samples too: the lower clamp, LevelArgs::minval)
+template <class F> static constexpr InvSet inv_gray_float() { return { { FL3(k_inv_level_w, F, false), FL3(k_inv_level_w, F, true) }, {} }; }
+template <class P> static constexpr InvSet inv_gray_delta() { return { { { k_inv_level_w<DeltaPix<P>, false, 0>, nullptr, nullptr }, {} }, {} }; }
+template <PixLayout L> static constexpr InvSet inv_rgb8()
+{
+	return { { FL3(k_inv_level_w_rgb, false, uint8_t, L), FL3(k_inv_level_w_rgb, true, uint8_t, L) }, FL3(k_inv2_level_w_rgb, true, L) };
+}
+template <PixLayout L> static constexpr InvSet inv_rgb_deep() { return { { FL3(k_inv_level_w_rgb, false, uint16_t, L), {} }, {} }; }
+template <class F> static constexpr InvSet inv_planar_float()
+{
+	return { { FL3(k_inv_level_w_rgb, false, F, PIX_PLANAR), FL3(k_inv_level_w_rgb, true, F, PIX_PLANAR) }, {} };
+}
+template <PixLayout L> static constexpr InvSet inv_rgb_delta() { return { { { k_inv_level_w_rgb<false, DeltaPix<uint8_t>, L, 0>, nullptr, nullptr }, {} }, {} }; }
+#undef FL3
+
+static const WideRow *wide_row(const WideEnd &e)
+{
+	static constexpr WideRow ROWS[] = {
+		// 8-bit pixels: histograms, 16-bit bands and the two-level inverse
+		{ { WK_U8, WL_GRAY, 0 }, false, fwd_pix8<uint8_t>(), inv_gray8() },
+		{ { WK_U8, WL_PACKED, 0 }, true, fwd_pix8<Rgb8>(), inv_rgb8<PIX_PACKED>() },
+		{ { WK_U8, WL_PACKED, WE_BGR }, true, fwd_pix8<Bgr8>(), inv_rgb8<PIX_PACKED_BGR>() },
+		{ { WK_U8, WL_STEP4, 0 }, true, fwd_pix8<Rgbx8>(), inv_rgb8<PIX_STEP4>() },
+		{ { WK_U8, WL_STEP4, WE_BGR }, true, fwd_pix8<Bgrx8>(), inv_rgb8<PIX_STEP4_BGR>() },
+		{ { WK_U8, WL_PLANAR, 0 }, true, fwd_pix8<RgbP8>(), inv_rgb8<PIX_PLANAR>() },
+		// deep pixels, and their signed twins: sources of their own, the same sinks
+		{ { WK_U16, WL_GRAY, 0 }, false, fwd_deep<SRC_U16>(), inv_gray_deep() },
+		{ { WK_U16, WL_PACKED, 0 }, false, fwd_deep<SRC_RGB16>(), inv_rgb_deep<PIX_PACKED>() },
+		{ { WK_U16, WL_PACKED, WE_BGR }, false, fwd_deep<SRC_BGR16>(), inv_rgb_deep<PIX_PACKED_BGR>() },
+		{ { WK_U16, WL_PLANAR, 0 }, false, fwd_deep<SRC_RGBP16>(), inv_rgb_deep<PIX_PLANAR>() },
+		{ { WK_S16, WL_GRAY, 0 }, false, fwd_deep<SRC_S16>(), inv_gray_deep() },
+		{ { WK_S16, WL_PACKED, 0 }, false, fwd_deep<SRC_RGB16S>(), inv_rgb_deep<PIX_PACKED>() },
+		{ { WK_S16, WL_PACKED, WE_BGR }, false, fwd_deep<SRC_BGR16S>(), inv_rgb_deep<PIX_PACKED_BGR>() },
+		{ { WK_S16, WL_PLANAR, 0 }, false, fwd_deep<SRC_RGBP16S>(), inv_rgb_deep<PIX_PLANAR>() },
+		// float samples, gray or planar RGB (interleaved float RGB has no wide kernel); the sinks do not ask about the route
+		{ { WK_F32, WL_GRAY, 0 }, false, fwd_float<FloatPix<float, false, false>>(), inv_gray_float<float>() },
+		{ { WK_H16, WL_GRAY, 0 }, false, fwd_float<FloatPix<Half16, false, false>>(), inv_gray_float<Half16>() },
+		{ { WK_F32, WL_PLANAR, 0 }, true, fwd_float<FloatPix<float, true, false>>(), inv_planar_float<float>() },
+		{ { WK_H16, WL_PLANAR, 0 }, true, fwd_float<FloatPix<Half16, true, false>>(), inv_planar_float<Half16>() },
+		{ { WK_F32, WL_GRAY, WE_FAR }, false, fwd_float_far<FloatPix<float, false, true>>(), inv_gray_float<float>() },
+		{ { WK_H16, WL_GRAY, WE_FAR }, false, fwd_float_far<FloatPix<Half16, false, true>>(), inv_gray_float<Half16>() },
+		{ { WK_F32, WL_PLANAR, WE_FAR }, false, fwd_float_far<FloatPix<float, true, true>>(), inv_planar_float<float>() },
+		{ { WK_H16, WL_PLANAR, WE_FAR }, false, fwd_float_far<FloatPix<Half16, true, true>>(), inv_planar_float<Half16>() },
+		// delta views: dense pixels, gray or interleaved 8-bit RGB; never flipped, never from 16-bit bands
+		{ { WK_U8, WL_GRAY, WE_DELTA }, false, fwd_delta<SRC_DELTA_U8>(), inv_gray_delta<uint8_t>() },
+		{ { WK_U16, WL_GRAY, WE_DELTA }, false, fwd_delta<SRC_DELTA_U16>(), inv_gray_delta<uint16_t>() },
+		{ { WK_S16, WL_GRAY, WE_DELTA }, false, fwd_delta<SRC_DELTA_S16>(), inv_gray_delta<int16_t>() },
+		{ { WK_U8, WL_PACKED, WE_DELTA }, false, fwd_delta<SRC_DELTA_RGB8>(), inv_rgb_delta<PIX_PACKED>() },
+		{ { WK_U8, WL_PACKED, WE_DELTA | WE_BGR }, false, fwd_delta<SRC_DELTA_BGR8>(), inv_rgb_delta<PIX_PACKED_BGR>() },
+	};
+	for (const WideRow &r : ROWS)
+		if (r.end == e)
+			return &r;
+	return nullptr;
 }
 
-// the wide kernel of a source, without and with histograms (deep pixels leave none: lift_fwd refuses the call)
-static WideKernel fwd_wide_kernel(int src, bool hist, bool flip_y = false)
+// No pixels: the wide kernels from plane to plane, which no row chooses — forward from int32 planes or (src16) from the 16-bit
+// bands of the level before, inverse from int32 or (det16) from 16-bit detail bands
+static WideKernel fwd_band_kernel(bool src16, bool hist)
 {
-	static const WideKernel K[SRC_COUNT][2] = {
-		{ k_fwd_level_w<false, SRC_I32>, k_fwd_level_w<true, SRC_I32> },
-		{ k_fwd_level_w<false, SRC_I16>, k_fwd_level_w<true, SRC_I16> },
-		{ k_fwd_level_w<false, SRC_U16>, nullptr },
-		{ k_fwd_level_w<false, SRC_RGB16>, nullptr },
-		{ k_fwd_level_w<false, SRC_RGBP16>, nullptr },
-		{ k_fwd_pixels_w<uint8_t, false>, k_fwd_pixels_w<uint8_t, true> },
-		{ k_fwd_pixels_w<Rgb8, false>, k_fwd_pixels_w<Rgb8, true> },
-		{ k_fwd_pixels_w<RgbP8, false>, k_fwd_pixels_w<RgbP8, true> },
-		{ k_fwd_pixels_w<Rgbx8, false>, k_fwd_pixels_w<Rgbx8, true> },
-		{ k_fwd_level_w<false, SRC_BGR16>, nullptr },
-		{ k_fwd_pixels_w<Bgr8, false>, k_fwd_pixels_w<Bgr8, true> },
-		{ k_fwd_pixels_w<Bgrx8, false>, k_fwd_pixels_w<Bgrx8, true> },
-		{ k_fwd_float_w<FloatPix<float, false, false>, false>, k_fwd_float_w<FloatPix<float, false, false>, true> },
-		{ k_fwd_float_w<FloatPix<Half16, false, false>, false>, k_fwd_float_w<FloatPix<Half16, false, false>, true> },
-		{ k_fwd_float_w<FloatPix<float, true, false>, false>, k_fwd_float_w<FloatPix<float, true, false>, true> },
-		{ k_fwd_float_w<FloatPix<Half16, true, false>, false>, k_fwd_float_w<FloatPix<Half16, true, false>, true> },
-		{ k_fwd_float_w<FloatPix<float, false, true>, false>, nullptr },
-		{ k_fwd_float_w<FloatPix<Half16, false, true>, false>, nullptr },
-		{ k_fwd_float_w<FloatPix<float, true, true>, false>, nullptr },
-		{ k_fwd_float_w<FloatPix<Half16, true, true>, false>, nullptr },
-		{ k_fwd_level_w<false, SRC_S16>, nullptr },
-		{ k_fwd_level_w<false, SRC_RGB16S>, nullptr },
-		{ k_fwd_level_w<false, SRC_RGBP16S>, nullptr },
-		{ k_fwd_level_w<false, SRC_BGR16S>, nullptr },
-		{ k_fwd_level_w<false, SRC_DELTA_U8>, nullptr },
-		{ k_fwd_level_w<false, SRC_DELTA_U16>, nullptr },
-		{ k_fwd_level_w<false, SRC_DELTA_S16>, nullptr },
-		{ k_fwd_level_w<false, SRC_DELTA_RGB8>, nullptr },
-		{ k_fwd_level_w<false, SRC_DELTA_BGR8>, nullptr },
-	};
-	// the same sources for the windows of a flipped call (FY; pixels only: a band has no windows)
-	static const WideKernel KY[SRC_COUNT][2] = {
-		{ nullptr, nullptr },
-		{ nullptr, nullptr },
-		{ k_fwd_level_w<false, SRC_U16, true>, nullptr },
-		{ k_fwd_level_w<false, SRC_RGB16, true>, nullptr },
-		{ k_fwd_level_w<false, SRC_RGBP16, true>, nullptr },
-		{ k_fwd_pixels_w<uint8_t, false, true>, k_fwd_pixels_w<uint8_t, true, true> },
-		{ k_fwd_pixels_w<Rgb8, false, true>, k_fwd_pixels_w<Rgb8, true, true> },
-		{ k_fwd_pixels_w<RgbP8, false, true>, k_fwd_pixels_w<RgbP8, true, true> },
-		{ k_fwd_pixels_w<Rgbx8, false, true>, k_fwd_pixels_w<Rgbx8, true, true> },
-		{ k_fwd_level_w<false, SRC_BGR16, true>, nullptr },
-		{ k_fwd_pixels_w<Bgr8, false, true>, k_fwd_pixels_w<Bgr8, true, true> },
-		{ k_fwd_pixels_w<Bgrx8, false, true>, k_fwd_pixels_w<Bgrx8, true, true> },
-		{ k_fwd_float_w<FloatPix<float, false, false>, false, true>, k_fwd_float_w<FloatPix<float, false, false>, true, true> },
-		{ k_fwd_float_w<FloatPix<Half16, false, false>, false, true>, k_fwd_float_w<FloatPix<Half16, false, false>, true, true> },
-		{ k_fwd_float_w<FloatPix<float, true, false>, false, true>, k_fwd_float_w<FloatPix<float, true, false>, true, true> },
-		{ k_fwd_float_w<FloatPix<Half16, true, false>, false, true>, k_fwd_float_w<FloatPix<Half16, true, false>, true, true> },
-		{ k_fwd_float_w<FloatPix<float, false, true>, false, true>, nullptr },
-		{ k_fwd_float_w<FloatPix<Half16, false, true>, false, true>, nullptr },
-		{ k_fwd_float_w<FloatPix<float, true, true>, false, true>, nullptr },
-		{ k_fwd_float_w<FloatPix<Half16, true, true>, false, true>, nullptr },
-		{ k_fwd_level_w<false, SRC_S16, true>, nullptr },
-		{ k_fwd_level_w<false, SRC_RGB16S, true>, nullptr },
-		{ k_fwd_level_w<false, SRC_RGBP16S, true>, nullptr },
-		{ k_fwd_level_w<false, SRC_BGR16S, true>, nullptr },
-		{ nullptr, nullptr },   // (a delta call takes no flips)
-		{ nullptr, nullptr },
-		{ nullptr, nullptr },
-		{ nullptr, nullptr },
-		{ nullptr, nullptr },
-	};
-	return flip_y ? KY[src][hist] : K[src][hist];
+	static constexpr WideKernel K[2][2] = { { k_fwd_level_w<false, SRC_I32>, k_fwd_level_w<true, SRC_I32> }, { k_fwd_level_w<false, SRC_I16>, k_fwd_level_w<true, SRC_I16> } };
+	return K[src16][hist];
+}
+static WideKernel inv_band_kernel(bool det16) { return det16 ? k_inv_level_w<int, true> : k_inv_level_w<int, false>; }
+static Inv2Kernel inv2_band_kernel(bool det16) { return det16 ? k_inv2_level_w<int, true> : k_inv2_level_w<int, false>; }
+
+// FL of the kernels that write these pixels: 0, or for a flipped call's windows 1 (upright and bottom-up ones) or 2 (a mirrored one among them)
+static int flip_level(const dwtx_pixels *px) { return !px || !px->flips ? 0 : px->flip_x ? 2 : 1; }
+
+// What the drivers below fill in more than one place.
+// A view behind src8 / dst8 / base8: its base, its window stride, its pitch (in samples, like the stride) and its grid of windows
+template <class B>
+static void pixel_block(const dwtx_pixels &px, int W, B *&base, long &image_ps, int &pitch, WinGrid &grid)
+{
+	base = const_cast<B *>(wide_base(px));
+	image_ps = (long)px.image_stride;
+	pitch = (int)px.pitch(W);
+	grid = win_grid(px);
+}
+
+// a delta view's base pictures for its source or sink (every other view leaves the fields empty: no other kernel reads them)
+static void delta_base(LevelArgsW &A, const dwtx_pixels &px, int W)
+{
+	if (px.is_delta())
+		pixel_block(px.base_pixels(), W, A.base8, A.base_ps, A.bpitch, A.bgrid);
+}
+
+// Can a level of width w run its wide kernel?  `quads` is the band whose lanes take four samples of a row at once — the source of
+// a forward step, the output of an inverse one; pixels where pix is not null, whose own rule is dwtx_pixels::wide() — and the other
+// two bands are touched a pair at a time.
+struct BandAt {
+	const void *p;
+	long ps;
+	int pitch;
+};
+static bool wide_level(int w, const dwtx_pixels *pix, const BandAt &quads, const BandAt &pairs_a, const BandAt &pairs_b)
+{
+	return w % 4 == 0 && quads.pitch % 4 == 0 && quads.ps % 4 == 0 && (pix ? pix->wide() : aligned_to(quads.p, 16)) &&
+		pairs_a.pitch % 2 == 0 && pairs_a.ps % 2 == 0 && aligned_to(pairs_a.p, 8) &&
+		pairs_b.pitch % 2 == 0 && pairs_b.ps % 2 == 0 && aligned_to(pairs_b.p, 8);
+}
+
+// The inverse LDS tail, steps T-1 .. tail_from of the pyramid in one launch: plane tail_from of every picture goes to dst, whole,
+// and is the LL band that the next launch reads
+static int inv_tail(dwtx_ctx *ctx, const LiftLayout &L, int *pyr, int nplanes, int *dst, const int *&cur, long &cur_ps, int &cur_pitch)
+{
+	TailArgs ta = tail_args(L, pyr);
+	ta.dst = dst;
+	ta.dst_ps = (long)L.ws[L.tail_from] * L.hs[L.tail_from];
+	ta.dpitch2 = L.ws[L.tail_from];
+	hipLaunchKernelGGL(k_inv_tail, dim3(nplanes), dim3(TAIL_THREADS), 0, ctx->stream, ta);
+	DWTX_LAUNCH_CHECK();
+	cur = ta.dst;
+	cur_ps = ta.dst_ps;
+	cur_pitch = ta.dpitch2;
+	return DWTX_OK;
 }
 
 // px != nullptr (`in` is then not read): the source is pixels, gray (plane p = image p) or RGB, interleaved or planar (plane p =
@@ -4406,9 +4482,10 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 	const int *src = in;
 	long src_ps = full_ps;
 	int spitch = W;
-	if (px && tail_from == 0)
+	const WideRow *row = px ? wide_row(wide_end(*px)) : nullptr;
+	if (px && (tail_from == 0 || !row))
 		return DWTX_ERR_ARG;
-	auto ll_dest = [&](int k, int *&p, long &ps, int &pitch) {   // destination of the ws[k]*hs[k] LL band
+	auto ll_dest =[&](int k, int *&p, long &ps, int &pitch) {   // destination of the ws[k]*hs[k] LL band
 		if (k == T) {
 			p = out;
 			ps = full_ps;
@@ -4460,10 +4537,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 		a.h2 = hs[t + 1];
 		const dwtx_pixels *pix_in = t == 0 ? px : nullptr;   // this step reads the pixels
 		if (pix_in) {   // (deep pixels: uint16_t samples behind src8; src_ps and spitch count samples either way)
-			a.src8 = wide_base(*px);
-			a.src_ps = (long)px->image_stride;
-			a.spitch = (int)px->pitch(W);
-			a.grid = win_grid(*px);
+			pixel_block(*px, W, a.src8, a.src_ps, a.spitch, a.grid);
 			if (px->is_float()) {
 				a.maxval = px->maxval;   // (what the quantiser clamps at; no other forward source reads them)
 				a.minval = px->minval;
@@ -4490,10 +4564,7 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			if (in_mask(t + 1))
 				a.ll16 = reinterpret_cast<short *>(a.ll);
 		}
-		const bool wide = a.w % 4 == 0 && a.spitch % 4 == 0 && a.src_ps % 4 == 0 &&
-			(pix_in ? px->wide() : aligned_to(a.src, 16)) &&
-			a.llpitch % 2 == 0 && a.ll_ps % 2 == 0 && aligned_to(a.ll, 8) &&
-			a.dpitch % 2 == 0 && a.det_ps % 2 == 0 && aligned_to(a.det, 8);
+		const bool wide = wide_level(a.w, pix_in, { a.src, a.src_ps, a.spitch }, { a.ll, a.ll_ps, a.llpitch }, { a.det, a.det_ps, a.dpitch });
 		if ((pix_in || a.det16) && !wide)
 			return DWTX_ERR_ARG;   // callers check dwtx_pixels_ok() / dwtx_levels16() first
 		const int level = T - 1 - t;   // the ring level this step's detail bands are
@@ -4507,16 +4578,11 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			a.rpw = pick_rpw(strips, a.h2, nplanes, forced);
 			A.wx_log2 = strips >= 4 ? 2 : strips >= 2 ? 1 : 0;
 			A.a = a;
-			const FwdSource from = fwd_source(pix_in, a.src16 != nullptr);
-			A.cstride = from.cstride;
-			if (pix_in && px->is_float())
-				A.fmt = float_fmt(*px);
-			if (pix_in && px->is_delta()) {
-				const dwtx_pixels bp = px->base_pixels();
-				A.base8 = wide_base(bp);
-				A.base_ps = (long)bp.image_stride;
-				A.bpitch = (int)bp.pitch(W);
-				A.bgrid = win_grid(bp);
+			if (pix_in) {
+				A.cstride = wide_cstride(*px);
+				if (px->is_float())
+					A.fmt = float_fmt(*px);
+				delta_base(A, *px, W);
 			}
 			if (hist_here) {
 				A.hist = HistArgs{ sink->cum32, sink->tile_mx, sink->tiles.xy2tile + sink->tiles.xy_first[level], sink->NT, sink->NTP,
@@ -4525,9 +4591,9 @@ static int lift_fwd(dwtx_ctx *ctx, int32_t *out, const int32_t *in, const dwtx_p
 			}
 			const int sx = dwtx_cdiv(strips, 1 << A.wx_log2), gy = dwtx_cdiv(a.h2, (WAVES >> A.wx_log2) * a.rpw);
 			// (8-bit RGB: the three channels of a strip side by side, xcd_strip_rgb; deep RGB: a block per plane, each taking its channel)
-			const dim3 grid = from.rgb_grid ? dim3(sx * 3, gy, nplanes / 3) : dim3(sx, gy, nplanes);
+			const dim3 grid = pix_in && row->rgb_grid ? dim3(sx * 3, gy, nplanes / 3) : dim3(sx, gy, nplanes);
 			A.ppw = pix_in ? px->channels : 1;
-			const WideKernel kernel = fwd_wide_kernel(from.src, hist_here, pix_in && px->flips);
+			const WideKernel kernel = pix_in ? row->fwd.k[hist_here][px->flips] : fwd_band_kernel(a.src16 != nullptr, hist_here);
 			if (!kernel)
 				return DWTX_ERR_ARG;
 			hipLaunchKernelGGL(kernel, grid, dim3(64 * WAVES), 0, ctx->stream, A);
@@ -4553,31 +4619,31 @@ extern "C" int dwtx_transformation_fwd(dwtx_ctx *ctx, int32_t *out, const int32_
 }
 
 // Can the finest level of a W*H image read / write these pixels directly?  (wide kernel, not the LDS tail)
-// Windows of a frame too (dwtx_pixels: row pitch, bands): the kernels touch only the W * channels samples of a window's
-// rows, so all they ask is that every row of every window — of every plane of a planar window — starts on a quad (px.wide())
-// and that the pitch fits their int.  Pixels with a step (dwtx_pixels::pixel_step): only 8-bit RGB in 4-byte pixels, which the
-// Rgbx8 / PIX_STEP4 instances address with the constant 4; the others would be read and written with dense addressing.
-// Any other view goes through the general conversions (dwtx_pixels_to_planes / dwtx_planes_to_pixels) — flipped windows
-// Signed samples (int16_t) qualify as deep ones do: the deep sources' signed twins read them, the deep sinks write them with the
-// lower clamp (LevelArgs::minval), which the float sources and sinks take as well.
-// A flipped call's windows (dwtx_pixels::flips) carry flags in their table entries that only win_off_flip takes apart: a SOURCE
-// qualifies when no window carries DWTX_FLIP_X (flip_wide: the FY instances of the wide forward kernels read it), a destination
-// (flip_sink: the FL instances of the wide inverse kernels write it) with any flags, a mirrored one if the windows' width is on the quad.
+// Which formats have wide kernels is what the table of pixel ends says (wide_row): a view without a row, like every view refused
+// here, goes through the general conversions (dwtx_pixels_to_planes / dwtx_planes_to_pixels).  What the table does not say:
+// - the shape: a width on the quad, and a side beyond the LDS tail's;
+// - windows of a frame (dwtx_pixels: row pitch, bands): the kernels touch only the W * channels samples of a window's rows, so all
+//   they ask is that every row of every window — of every plane of a planar window — starts on a quad (px.wide()) and that the
+//   pitch fits their int;
+// - a flipped call's windows (dwtx_pixels::flips) carry flags in their table entries that only win_off_flip takes apart: a SOURCE
+//   qualifies when no window carries DWTX_FLIP_X (flip_wide: the FY instances of the wide forward kernels read it), a destination
+//   (flip_sink: the FL instances of the wide inverse kernels write it) with any flags, a mirrored one if the windows' width is on the quad;
+// - a delta view's base pictures: dense interleaved pixels like the view's own, which the delta rows' kernels address alike, and
+//   both views must qualify as the plain views of their samples would.
 bool dwtx_pixels_ok(const dwtx_pixels &px, int W, int H)
 {
 	if (px.chain || px.clips)   // (a chain's and a clip stack's base is the window before: no sink that walks the windows side by side takes it,
 		return false;           // and a clip stack's source goes through the general conversion's clips instance, which knows the keys)
+	if (!wide_row(wide_end(px)))
+		return false;
 	if (px.is_delta()) {
-		// a delta view: both views must qualify, as the plain views of their samples would (the 16-bit ones as deep views), gray or
-		// 8-bit interleaved RGB, dense pixels — every other pair takes the general conversions' delta instances
 		dwtx_pixels own = px;
 		own.delta = dwtx_base_grid();
 		const dwtx_pixels bp = px.base_pixels();
-		return !px.planar() && !bp.planar() && !px.stepped() && !bp.stepped() && (px.channels == 1 || px.kind == DWTX_SAMPLE_U8) && dwtx_pixels_ok(own, W, H) &&
-			dwtx_pixels_ok(bp, W, H);
+		return !px.planar() && !bp.planar() && !bp.stepped() && dwtx_pixels_ok(own, W, H) && dwtx_pixels_ok(bp, W, H);
 	}
-	return (!px.flips || px.flip_wide || (px.flip_sink && (!px.flip_x || px.flip_w % 4 == 0))) && W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide() && px.pitch(W) <= 0x7fffffffu && (!px.stepped() || px.rgbx8()) &&
-		(!px.is_float() || px.channels == 1 || px.planar());   // (float sinks: OutRow<F> and RgbOut<F, PIX_PLANAR>, float sources: FloatPix<>; interleaved float RGB has neither)
+	return (!px.flips || px.flip_wide || (px.flip_sink && (!px.flip_x || px.flip_w % 4 == 0))) && W % 4 == 0 && (W > TAIL_MAX || H > TAIL_MAX) && px.wide() &&
+		px.pitch(W) <= 0x7fffffffu;
 }
 
 unsigned dwtx_levels16(int W, int H, unsigned sq_levels)
@@ -4614,81 +4680,6 @@ int dwtx_transformation_fwd_hist(dwtx_ctx *ctx, int32_t *out, const int32_t *in,
 	if (!in)
 		return DWTX_ERR_ARG;
 	return lift_fwd(ctx, out, in, nullptr, W, H, nplanes, sink, hist_levels);
-}
-
-using Inv2Kernel = void (*)(Inv2Args);
-
-// FL of the kernels that write these pixels: 0, or for a flipped call's windows 1 (upright and bottom-up ones) or 2 (a mirrored one among them)
-static int flip_level(const dwtx_pixels *px) { return !px || !px->flips ? 0 : px->flip_x ? 2 : 1; }
-
-// px: the pair writes these pixels (8-bit ones, gray or RGB), which it does from 16-bit bands only
-template <int FL>
-static Inv2Kernel inv2_pixel_kernel(const dwtx_pixels *px)
-{
-	if (px->channels == 3) {
-		if (px->planar())
-			return k_inv2_level_w_rgb<true, PIX_PLANAR, FL>;
-		if (px->bgr())
-			return px->rgbx8() ? k_inv2_level_w_rgb<true, PIX_STEP4_BGR, FL> : k_inv2_level_w_rgb<true, PIX_PACKED_BGR, FL>;
-		return px->rgbx8() ? k_inv2_level_w_rgb<true, PIX_STEP4, FL> : k_inv2_level_w_rgb<true, PIX_PACKED, FL>;
-	}
-	return k_inv2_level_w<uint8_t, true, FL>;
-}
-static Inv2Kernel inv2_kernel(const dwtx_pixels *px, bool det16)
-{
-	if (px) {
-		const int fl = flip_level(px);
-		return fl == 2 ? inv2_pixel_kernel<2>(px) : fl == 1 ? inv2_pixel_kernel<1>(px) : inv2_pixel_kernel<0>(px);
-	}
-	return det16 ? k_inv2_level_w<int, true> : k_inv2_level_w<int, false>;
-}
-
-// The wide kernel of an inverse step that writes these pixels (gray or RGB; deep ones never from 16-bit bands)
-template <int FL>
-static WideKernel inv_pixel_kernel(const dwtx_pixels *px, bool det16)
-{
-	if (px->is_delta()) {   // gray, or interleaved 8-bit RGB (dwtx_pixels_ok); never flipped, never from 16-bit bands
-		if (px->channels == 3)
-			return px->bgr() ? k_inv_level_w_rgb<false, DeltaPix<uint8_t>, PIX_PACKED_BGR, 0> : k_inv_level_w_rgb<false, DeltaPix<uint8_t>, PIX_PACKED, 0>;
-		return px->kind == DWTX_SAMPLE_U8 ? k_inv_level_w<DeltaPix<uint8_t>, false, 0>
-			: px->kind == DWTX_SAMPLE_S16 ? k_inv_level_w<DeltaPix<int16_t>, false, 0> : k_inv_level_w<DeltaPix<uint16_t>, false, 0>;
-	}
-	if (px->is_float()) {   // gray, or planar RGB in either order (dwtx_pixels_ok); from int32 and from 16-bit bands
-		const bool f32 = px->kind == DWTX_SAMPLE_F32;
-		if (px->channels == 3)
-			return f32 ? (det16 ? k_inv_level_w_rgb<true, float, PIX_PLANAR, FL> : k_inv_level_w_rgb<false, float, PIX_PLANAR, FL>)
-			           : (det16 ? k_inv_level_w_rgb<true, Half16, PIX_PLANAR, FL> : k_inv_level_w_rgb<false, Half16, PIX_PLANAR, FL>);
-		return f32 ? (det16 ? k_inv_level_w<float, true, FL> : k_inv_level_w<float, false, FL>)
-		           : (det16 ? k_inv_level_w<Half16, true, FL> : k_inv_level_w<Half16, false, FL>);
-	}
-	const int channels8 = !px->deep() ? px->channels : 0;
-	if (px->channels == 3 && px->planar()) {
-		if (px->deep())
-			return k_inv_level_w_rgb<false, uint16_t, PIX_PLANAR, FL>;
-		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_PLANAR, FL> : k_inv_level_w_rgb<false, uint8_t, PIX_PLANAR, FL>;
-	}
-	if (px->bgr()) {   // (interleaved: the layouts' B, G, R twins)
-		if (px->rgbx8())
-			return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_STEP4_BGR, FL> : k_inv_level_w_rgb<false, uint8_t, PIX_STEP4_BGR, FL>;
-		if (px->deep())
-			return k_inv_level_w_rgb<false, uint16_t, PIX_PACKED_BGR, FL>;
-		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_PACKED_BGR, FL> : k_inv_level_w_rgb<false, uint8_t, PIX_PACKED_BGR, FL>;
-	}
-	if (px->rgbx8())
-		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_STEP4, FL> : k_inv_level_w_rgb<false, uint8_t, PIX_STEP4, FL>;
-	if (channels8 == 3)
-		return det16 ? k_inv_level_w_rgb<true, uint8_t, PIX_PACKED, FL> : k_inv_level_w_rgb<false, uint8_t, PIX_PACKED, FL>;
-	if (channels8)
-		return det16 ? k_inv_level_w<uint8_t, true, FL> : k_inv_level_w<uint8_t, false, FL>;
-	return px->channels == 3 ? k_inv_level_w_rgb<false, uint16_t, PIX_PACKED, FL> : k_inv_level_w<uint16_t, false, FL>;
-}
-static WideKernel inv_wide_kernel(const dwtx_pixels *px, bool det16)
-{
-	if (px) {
-		const int fl = flip_level(px);
-		return fl == 2 ? inv_pixel_kernel<2>(px, det16) : fl == 1 ? inv_pixel_kernel<1>(px, det16) : inv_pixel_kernel<0>(px, det16);
-	}
-	return det16 ? k_inv_level_w<int, true> : k_inv_level_w<int, false>;
 }
 
 // px != nullptr (`out` is then not written): the finest level writes clamped pixels (gray, or RGB — interleaved or planar — after the
@@ -4775,18 +4766,15 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 	const int *cur = in;
 	long cur_ps = full_ps;
 	int cur_pitch = W;
+	const WideRow *row = px ? wide_row(wide_end(*px)) : nullptr;
+	const int flip = flip_level(px);
+	if (px && !row)
+		return DWTX_ERR_ARG;
 	if (tail_from < T) {
 		if (tail_from == 0 && px)
 			return DWTX_ERR_ARG;
-		TailArgs ta = tail_args(L, const_cast<int *>(in));
-		ta.dst = tail_from == 0 ? out : plane[tail_from];
-		ta.dst_ps = tail_from == 0 ? full_ps : (long)ws[tail_from] * hs[tail_from];
-		ta.dpitch2 = tail_from == 0 ? W : ws[tail_from];
-		hipLaunchKernelGGL(k_inv_tail, dim3(nplanes), dim3(TAIL_THREADS), 0, ctx->stream, ta);
-		DWTX_LAUNCH_CHECK();
-		cur = ta.dst;
-		cur_ps = ta.dst_ps;
-		cur_pitch = ta.dpitch2;
+		if (const int rc = inv_tail(ctx, L, const_cast<int *>(in), nplanes, tail_from == 0 ? out : plane[tail_from], cur, cur_ps, cur_pitch))
+			return rc;
 	}
 	for (int t = tail_from - 1; t >= 0; --t) {
 		if (pair[t]) {   // steps t and t-1: shapes whose two levels have whole row pairs
@@ -4800,10 +4788,7 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 			f.det16 = in16(t) ? p16->planes : nullptr;
 			const dwtx_pixels *pix_out = t - 1 == 0 ? px : nullptr;   // the pair writes the pixels
 			if (pix_out) {
-				f.dst8 = const_cast<uint8_t *>(wide_base(*px));
-				f.dst_ps = (long)px->image_stride;
-				f.opitch = (int)px->pitch(W);
-				f.grid = win_grid(*px);
+				pixel_block(*px, W, f.dst8, f.dst_ps, f.opitch, f.grid);
 				f.cstride = wide_cstride(*px);
 				f.fh = px->flip_h;
 				f.fwq = px->flip_w / 4;
@@ -4824,7 +4809,10 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 			// (the 8-bit kernels put a block's waves side by side; RGB: three planes per wave)
 			const dim3 grid = pix_out ? dim3(dwtx_cdiv(strips, WAVES), dwtx_cdiv(h4, f.mpw), nplanes / px->channels)
 			                          : dim3(strips, dwtx_cdiv(h4, WAVES * f.mpw), nplanes);
-			hipLaunchKernelGGL(inv2_kernel(pix_out, f.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, f);
+			const Inv2Kernel kernel = pix_out ? row->inv.k2[flip] : inv2_band_kernel(f.det16 != nullptr);
+			if (!kernel)
+				return DWTX_ERR_ARG;
+			hipLaunchKernelGGL(kernel, grid, dim3(64 * WAVES), 0, ctx->stream, f);
 			DWTX_LAUNCH_CHECK();
 			cur = f.dst;
 			cur_ps = f.dst_ps;
@@ -4842,11 +4830,8 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 		a.spitch = cur_pitch;
 		const dwtx_pixels *pix_out = t == 0 ? px : nullptr;   // this step writes the pixels
 		if (pix_out) {   // (deep pixels: uint16_t samples behind dst8; ll_ps and llpitch count samples either way)
-			a.dst8 = const_cast<uint8_t *>(wide_base(*px));
-			a.ll_ps = (long)px->image_stride;
-			a.llpitch = (int)px->pitch(W);
-			a.grid = win_grid(*px);
-			a.maxval = px->deep() || px->is_float() ? px->maxval : 0;   // (float sinks clamp at whatever the maxval is, 255 included)
+			pixel_block(*px, W, a.dst8, a.ll_ps, a.llpitch, a.grid);
+			a.maxval =px->deep() || px->is_float() ? px->maxval : 0;   // (float sinks clamp at whatever the maxval is, 255 included)
 			a.minval = px->minval;   // (0 but for int16_t samples and the float views of the signed calls)
 		} else if (t == 0) {
 			a.ll = out;
@@ -4865,34 +4850,28 @@ static int lift_inv(dwtx_ctx *ctx, int32_t *out, const dwtx_pixels *px, const in
 				return DWTX_ERR_ARG;
 			a.det16 = p16->planes;
 		}
-		const bool wide = a.w % 4 == 0 && a.llpitch % 4 == 0 && a.ll_ps % 4 == 0 &&
-			(pix_out ? px->wide() : aligned_to(a.ll, 16)) &&
-			a.spitch % 2 == 0 && a.src_ps % 2 == 0 && aligned_to(a.src, 8) &&
-			a.dpitch % 2 == 0 && a.det_ps % 2 == 0 && aligned_to(a.det, 8);
+		const bool wide = wide_level(a.w, pix_out, { a.ll, a.ll_ps, a.llpitch }, { a.src, a.src_ps, a.spitch }, { a.det, a.det_ps, a.dpitch });
 		if ((pix_out || a.det16) && !wide)
 			return DWTX_ERR_ARG;
 		if (wide) {
 			LevelArgsW A{};
 			A.nquads = a.w / 4;
-			const bool rgb = pix_out && px->channels == 3;
+			const bool rgb = pix_out && row->rgb();
 			const int sx = dwtx_cdiv(A.nquads, rgb ? INV_QUADS : 64);   // (the RGB kernel's waves overlap by a lane on each side)
 			a.rpw = pick_rpw(sx, a.h2, nplanes, forced);
 			A.a = a;
-			A.cstride = rgb ? wide_cstride(*px) : 0;
 			if (pix_out) {
+				A.cstride = wide_cstride(*px);
 				A.fmt = float_fmt(*px);
 				A.fh = px->flip_h;
 				A.fwq = px->flip_w / 4;
-			}
-			if (pix_out && px->is_delta()) {
-				const dwtx_pixels bp = px->base_pixels();
-				A.base8 = wide_base(bp);
-				A.base_ps = (long)bp.image_stride;
-				A.bpitch = (int)bp.pitch(W);
-				A.bgrid = win_grid(bp);
+				delta_base(A, *px, W);
 			}
 			const dim3 grid(sx, dwtx_cdiv(a.h2, WAVES * a.rpw), rgb ? nplanes / 3 : nplanes);
-			hipLaunchKernelGGL(inv_wide_kernel(pix_out, a.det16 != nullptr), grid, dim3(64 * WAVES), 0, ctx->stream, A);
+			const WideKernel kernel = pix_out ? row->inv.k[a.det16 != nullptr][flip] : inv_band_kernel(a.det16 != nullptr);
+			if (!kernel)
+				return DWTX_ERR_ARG;
+			hipLaunchKernelGGL(kernel, grid, dim3(64 * WAVES), 0, ctx->stream, A);
 		} else {
 			const int sx = dwtx_cdiv(a.w2, INV_PAIRS);
 			a.rpw = pick_rpw(sx, a.h2, nplanes, forced);
@@ -5157,17 +5136,9 @@ int dwtx_inv_crop(dwtx_ctx *ctx, int32_t *planes, int32_t *pyr, int W, int H, in
 	const int *cur = pyr;   // (without a tail the first step reads the root LL in the pyramid itself)
 	long cur_ps = full_ps;
 	int cur_pitch = W;
-	if (tail_from < T) {
-		TailArgs ta = tail_args(L, pyr);
-		ta.dst = plane_of(tail_from);
-		ta.dst_ps = (long)L.ws[tail_from] * L.hs[tail_from];
-		ta.dpitch2 = L.ws[tail_from];
-		hipLaunchKernelGGL(k_inv_tail, dim3(nplanes), dim3(TAIL_THREADS), 0, ctx->stream, ta);
-		DWTX_LAUNCH_CHECK();
-		cur = ta.dst;
-		cur_ps = ta.dst_ps;
-		cur_pitch = ta.dpitch2;
-	}
+	if (tail_from < T)
+		if (const int rc = inv_tail(ctx, L, pyr, nplanes, plane_of(tail_from), cur, cur_ps, cur_pitch))
+			return rc;
 	for (int t = tail_from - 1; t >= 0; --t) {
 		RoiArgs a{};
 		a.src = cur;
